@@ -1,28 +1,32 @@
 #!/usr/bin/env python
 """bench.py -- forward + likelihood evals/sec on synthetic FDEM soundings (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 Workload (BASELINE.json configs[2]): 65 536 soundings x 10 zz frequencies x 8 layers, fp64,
 sharded in contiguous blocks over the N ranks (strong scaling: the total is fixed).  One proposal ROUND
 over the whole batch: every sounding gets a fresh conductivity vector (one of R pre-generated sets
 resident in HBM, so nothing can be cached), the fused kernel evaluates forward solve + chi^2 +
 log-likelihood, and the per-sounding summaries are gathered to rank 0 (RCCL, on a side stream so that it
-overlaps the next round).  One STEP = ``rounds_per_step`` rounds, chosen from the warm-up's round time so
-that the K timed steps last at least 1 s (R >= 8 rounds, wall >= 1 s; a 1 ms round x the
-driver's 20 steps would be a 20 ms region); value = soundings x K x rounds_per_step / elapsed.  Inputs
-are resident in HBM before the timed region.
+overlaps the next round).  One STEP = ``rounds_per_step`` rounds (a fixed number, 8 by default: SURVEY 8d's
+R >= 8 rounds; the caller's K sets the length of the timed region), W warm-up steps run before the K timed
+ones; value = soundings x K x rounds_per_step / elapsed, ms_per_step = elapsed / K.  Inputs are resident in
+HBM before the timed region and identical from run to run (fixed seeds).
 
-The JSON line also carries
-  roofline      frac = the flops the kernel EXECUTES -- SURVEY 8(d)'s min-flop count per (frequency, abscissa)
-                point x the abscissae of each sounding's own window -- / kernel time (HIP events on the launch
-                stream) / the MI355X fp64 vector peak (the path is fp64-VALU bound, not HBM/MFMA): a hardware
-                fraction.  frac_all_abscissae_equivalent counts all 120 abscissae per frequency as SURVEY 8(d)
-                does (useful-work equivalent); roofline.all_abscissae is the same batch with every abscissa
-                evaluated; plus the algorithmic HBM bytes/s for reference;
+--dump-outputs DIR writes what the timed path returned in its last round, the per-sounding (chi^2, logL) that
+rank 0 holds, as DIR/chi2.npy and DIR/logL.npy (float64, whole batch).
+
+A plain run measures the headline alone.  --full adds every other measurement and writes the run's full record
+to --extras-file; the line then also carries
+  roofline.all_abscissae  the same batch with every abscissa evaluated; roofline.other_kernels the rjMCMC
+                sampler, the Jacobian, time-domain and smaller-batch kernels (the headline roofline itself --
+                frac = the flops the kernel EXECUTES, SURVEY 8(d)'s min-flop count per (frequency, abscissa)
+                point x the abscissae of each sounding's own window, / kernel time (HIP events on the launch
+                stream) / the MI355X fp64 vector peak -- comes from the timed steps and is in every line);
   parity_vs_cpu within_bar against the CPU oracle with the test suite's bars; the run exits non-zero when false;
   cpu_baseline  the C oracle (a port of the reference's scalar algorithm) timed on this host's cores on a
-                bounded sample of the same workload (rank 0, N = 1 only).
+                bounded sample of the same workload (rank 0);
+  survey        the end-to-end survey driver, at the north-star sizes too.
 """
 import argparse
 import json
@@ -41,8 +45,7 @@ N_LAYERS = 8
 N_SIGMA_SETS = 4
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # MI355X datasheet, per GPU
 HBM_PEAK_GBPS = 8000.0
-MIN_TIMED_SECONDS = 1.0          # R >= 8 rounds and wall >= 1 s
-TIMED_MARGIN = 1.5               # the probe rounds are not the timed ones (clocks, contention between ranks): aim above the minimum
+ROUNDS_PER_STEP = 8              # R >= 8 rounds; fixed, so that --steps alone sets the timed work
 
 
 def flop_per_eval(L, F):
@@ -475,6 +478,24 @@ def compact_line(full, extras_file=EXTRAS_FILE):
     return line
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # bytes --dump-outputs writes at most (a seeded sample of the rows above it)
+
+
+def dump_outputs(directory, result):
+    """--dump-outputs: what a caller of the timed path receives from its last round -- the per-sounding chi^2 and logL of the whole
+    batch on rank 0 ([N, 2] fp64) -- as directory/chi2.npy and directory/logL.npy.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of
+    the rows is written instead, with the sampled row numbers in directory/rows.npy."""
+    res = result.detach().double().cpu().numpy()
+    cap = DUMP_LIMIT_BYTES // (8 * (res.shape[1] + 1))
+    os.makedirs(directory, exist_ok=True)
+    if res.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(0).choice(res.shape[0], cap, replace=False))
+        res = res[rows]
+        np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(directory, "chi2.npy"), np.ascontiguousarray(res[:, 0]))
+    np.save(os.path.join(directory, "logL.npy"), np.ascontiguousarray(res[:, 1]))
+
+
 def write_extras(full, path=EXTRAS_FILE):
     try:
         os.makedirs(os.path.dirname(os.path.join(ROOT, path)), exist_ok=True)
@@ -489,9 +510,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--rounds-per-step", type=int, default=0,
-                    help="proposal rounds per step (0 = chosen so that the timed region is >= 1 s, SURVEY 8d)")
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds-per-step", type=int, default=ROUNDS_PER_STEP,
+                    help="proposal rounds over the whole batch per step (default %(default)s, SURVEY 8d: R >= 8)")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed warm-up steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last round's per-sounding chi2 and logL as DIR/chi2.npy, DIR/logL.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (all abscissae, rjMCMC, Jacobian, time domain, surveys, "
+                         "CPU baseline + parity; the --no-* options below trim it) and write the full record to --extras-file")
     ap.add_argument("--soundings", type=int, default=B_TOTAL, help="total soundings (default: BASELINE config)")
     ap.add_argument("--layers", type=int, default=N_LAYERS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -500,11 +526,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the extra Jacobian and time-domain measurements")
     ap.add_argument("--no-survey-sizes", action="store_true", help="skip the end-to-end survey runs at the north-star sizes (~30 s)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="soundings in the CPU baseline sample (0 = auto)")
-    ap.add_argument("--extras-file", default=EXTRAS_FILE, help="where the run's full record goes (relative to the repository root; '' = nowhere)")
+    ap.add_argument("--extras-file", default=EXTRAS_FILE, help="with --full: where the run's full record goes (relative to the repository root; '' = nowhere)")
     ap.add_argument("--force-collective", action="store_true",
                     help="with --gpus 1: initialise RCCL with ONE rank and run the N > 1 exchange anyway (side stream + all_gather_into_tensor "
                          "per round) -- executes the multi-GPU code path on a single-GPU box; not the headline configuration")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.rounds_per_step < 1:
+        ap.error("--steps and --rounds-per-step must be >= 1, --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -579,38 +607,21 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    # One STEP = rounds_per_step proposal rounds over the whole batch.  SURVEY 8(d) wants R >= 8 rounds and a timed region of at
-    # least 1 s: the driver's --steps 20 of ONE 1 ms round would be a 20 ms region, so the rounds per step are chosen from the
-    # warm-up's measured round time such that steps x rounds_per_step x round >= 1 s (every rank computes the same number from
-    # the max over ranks).  evals = soundings x steps x rounds_per_step.
-    pending = None
-    for i in range(args.warmup):
-        pending = round_(i, pending)
-    if pending is not None:
-        pending[0].wait()
-        pending = None
-    sync_all()
-    tw0 = time.perf_counter()
-    n_probe = 8
-    for i in range(n_probe):
-        pending = round_(i, pending)
-    if pending is not None:
-        pending[0].wait()
-        pending = None
-    sync_all()
-    t_round = (time.perf_counter() - tw0) / n_probe
-    if world > 1:
-        tr = torch.tensor([t_round], dtype=torch.float64, device=device)
-        dist.all_reduce(tr, op=dist.ReduceOp.MAX)
-        t_round = float(tr[0])
-    rounds_per_step = max(1, int(np.ceil(TIMED_MARGIN * MIN_TIMED_SECONDS / (args.steps * t_round)))) if args.rounds_per_step <= 0 else args.rounds_per_step
-    if args.steps * rounds_per_step < 8:
-        rounds_per_step = int(np.ceil(8 / args.steps))
+    # One STEP = rounds_per_step proposal rounds over the whole batch, a fixed number (R >= 8 rounds), so that the
+    # caller's --steps alone sets the length of the timed region.  evals = soundings x steps x rounds_per_step.
+    rounds_per_step = args.rounds_per_step
 
     def step(i, pending):
         for r in range(rounds_per_step):
             pending = round_(i * rounds_per_step + r, pending)
         return pending
+
+    pending = None
+    for i in range(args.warmup):
+        pending = step(i, pending)
+    if pending is not None:
+        pending[0].wait()
+        pending = None
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     sync_all()
@@ -635,6 +646,8 @@ def main():
     else:
         last = batches[(n_rounds - 1) % N_SIGMA_SETS]
         result = torch.stack([last.chi2, last.logL], dim=1)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
 
     if rank == 0:
         evals = Btot * n_rounds
@@ -671,7 +684,7 @@ def main():
                        "hankel_eps_ppm": batches[0].hankel_eps_ppm,
                        "abscissa_points_per_sounding_mean": pts_exec,
                        "abscissa_points_all": pts_all,
-                       "step": "rounds_per_step proposal rounds over the whole batch (chosen so that the timed region is >= 1 s)"},
+                       "step": "rounds_per_step proposal rounds over the whole batch (a fixed number; --steps sets the timed region)"},
             "roofline": {
                 "bound": "fp64_valu", "achieved": achieved, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": achieved / FP64_VECTOR_PEAK_TFLOPS, "traffic": measured_traffic(Btot, L, world),
@@ -696,7 +709,7 @@ def main():
             line["forced_collective"] = {"backend": backend, "world": world, "rounds": n_rounds,
                                          "gathered_equals_local": bool(torch.equal(result, torch.stack([last.chi2, last.logL], dim=1)[:result.shape[0]])),
                                          "note": "one-rank process group: every round ends with all_gather_into_tensor on a side stream (the N > 1 path)"}
-        if world == 1 and not args.no_windowed:
+        if args.full and world == 1 and not args.no_windowed:
             # the same rounds with ALL 120 abscissae per frequency (FdemBatch(hankel_eps_ppm=0)): what the default's per-sounding
             # abscissa window leaves out is bounded by 1e-12 ppm per output (|rTE| <= 1); measured difference below
             xb = [FdemBatch(system, nl[sl], sg, thk[sl], height[sl], data=obs, relative_error=rel, additive_error=add,
@@ -734,11 +747,11 @@ def main():
                                                  "frac": xach / FP64_VECTOR_PEAK_TFLOPS,
                                                  "note": "FdemBatch(hankel_eps_ppm=0) in the same run: all 1 200 abscissa points per sounding"}
             del xb
-        if world == 1 and not args.no_rjmcmc:
+        if args.full and world == 1 and not args.no_rjmcmc:
             # the caller of the hot path (BASELINE config 5): complete rjMCMC iterations, every chain resident on
             # the device (gbp_rj_run).  Reported next to the headline, not in it.
             line["rjmcmc"] = rjmcmc_extra(system, height, obs, device, Btot)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the rows either side of the headline path, measured in the same run and reported next to it: the Jacobian
             # kernel on the same batch, and the time-domain path (rows 13-14, BASELINE config 4 shape)
             def per_call(fn, n):
@@ -894,7 +907,7 @@ def main():
                                                "22 spline nodes x 19 gates, mean ~4 layers; blocks of 8 192 and 1 024 chains")
             except Exception as e:                               # an extra, never the measurement
                 line["tdem"]["sampler"] = {"error": repr(e)}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 line["survey"] = survey_extra()
             except Exception as e:                               # an extra, never the measurement
@@ -906,7 +919,7 @@ def main():
                         "soundings_65536": survey_at_size(65536, 64, 2000)}
                 except Exception as e:
                     line["survey"]["north_star_sizes"] = {"error": repr(e)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 times the C oracle on the host cores at EVERY N (the other ranks wait at the barrier in front of
             # destroy_process_group); rank 0's shard starts at sounding 0, so the first `sample` rows of the whole-job arrays are its own
             threads = usable_cores()
@@ -962,7 +975,7 @@ def main():
         if others:
             line["roofline"]["other_kernels"] = others
         # the full record goes to a side file; the printed line is the compact one the driver's record can hold (<= 3 KB)
-        wrote = bool(args.extras_file) and write_extras(line, args.extras_file)
+        wrote = args.full and bool(args.extras_file) and write_extras(line, args.extras_file)
         print(json.dumps(compact_line(line, args.extras_file if wrote else None), separators=(",", ":")), flush=True)
         parity_failed = "parity_vs_cpu" in line and not line["parity_vs_cpu"]["within_bar"]
     else:

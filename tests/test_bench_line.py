@@ -74,12 +74,12 @@ import pytest  # noqa: E402
 
 @pytest.mark.gpu
 def test_bench_prints_one_parsable_line_on_the_gpu(tmp_path):
-    """python bench.py (bounded flags) on cuda:0: the LAST stdout line is the compact JSON line -- under 3 KB, the contract's keys, roofline and
-    cpu_baseline objects, parity within the bar -- and the full record lands in the extras file."""
+    """python bench.py --full (bounded flags) on cuda:0: the LAST stdout line is the compact JSON line -- under 3 KB, the contract's keys, roofline
+    and cpu_baseline objects, parity within the bar -- and the full record lands in the extras file."""
     import subprocess
     extras = os.path.join(str(tmp_path), "extras.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--soundings", "8192",
-                        "--no-extras", "--no-rjmcmc", "--cpu-sample", "512", "--extras-file", extras],
+                        "--full", "--no-extras", "--no-rjmcmc", "--cpu-sample", "512", "--extras-file", extras],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     last = r.stdout.strip().splitlines()[-1]
@@ -94,3 +94,29 @@ def test_bench_prints_one_parsable_line_on_the_gpu(tmp_path):
     assert line["parity_vs_cpu"]["within_bar"] is True
     full = json.load(open(extras))
     assert full["value"] == pytest.approx(line["value"], rel=1e-5) and "definition" in full["roofline"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_it_is_given_and_dumps_its_outputs(tmp_path):
+    """python bench.py without --full on cuda:0: the headline alone (no CPU baseline, no extras file), --steps timed steps of a fixed number of
+    rounds, and --dump-outputs writes the last round's per-sounding chi2 / logL -- the same numbers from two runs with the same arguments."""
+    import subprocess
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out = os.path.join(str(tmp_path), "out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--soundings", "8192",
+                            "--dump-outputs", out], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["rounds_per_step"] == bench.ROUNDS_PER_STEP and line["finite"]
+        assert line["ms_per_step"] == pytest.approx(1e3 * line["timed_seconds"] / 4, rel=1e-4)
+        assert line["value"] == pytest.approx(8192 * 4 * bench.ROUNDS_PER_STEP / line["timed_seconds"], rel=1e-4)
+        assert "cpu_baseline" not in line and "parity_vs_cpu" not in line and line["extras_file"] is None
+        assert sorted(os.listdir(out)) == ["chi2.npy", "logL.npy"]
+        arrays = {n: np.load(os.path.join(out, n + ".npy")) for n in ("chi2", "logL")}
+        for a in arrays.values():
+            assert a.dtype == np.float64 and a.shape == (8192,) and np.isfinite(a).all()
+        dumps.append(arrays)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

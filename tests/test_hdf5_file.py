@@ -9,6 +9,7 @@ the result to
     of the seeded sounding;
   * the .npz stand-in of the same container, array for array, bit for bit.
 Skipped (with the reason) where no HDF5 library or no interpreter with h5py exists."""
+import gzip
 import json
 import os
 import shutil
@@ -106,26 +107,13 @@ def test_the_reference_container_as_a_real_hdf5_file(tmp_path):
     assert info["/model/values/posterior/values/data"]["fillvalue"] == np.iinfo(np.int32).min and info["/phids/data"]["fillvalue"] == "nan"
 
 
-def test_the_references_own_readers_open_our_file(tmp_path):
-    """Row f-4's purpose, executed: "the reference's own post-processing can read our outputs".  Build container only (it needs
-    /root/reference and an interpreter that has the real h5py and can import the reference): tests/ref_reads_h5.py opens the .h5 this
-    package wrote with h5py.File and reads sounding 1 with the reference's ``Histogram.fromHdf`` (layer-count, interface-depth and
-    conductivity-depth posteriors), ``Model.fromHdf`` (best model) and ``hdfRead.readKeyFromFile`` (the FdemDataPoint with its error-level
-    posteriors, the counters, the misfit trace) -- and gets back the numbers that were written.  (``Inference1D.fromHdf`` itself cannot be
-    the check: at Inference1D.py:1152-1155 it reads the model through ``StatArray.fromHdf(grp, 'values')``, which looks for
-    'n_posteriors' in the PARENT group (StatArray.py:907) and so returns a DataArray without the posterior ``fromHdf`` then asks for --
-    on the reference's own files as on these.)"""
-    _needs()
-    if not os.path.isdir("/root/reference/geobipy"):
-        pytest.skip("the reference tree is only present in the build container")
-    probe = subprocess.run([CHECKER, "-c", "import h5py, matplotlib, scipy"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the checker interpreter cannot import what the reference needs")
+def _seeded_container(path):
+    """The seeded Resolve container of tests/golden/hdf_schema.json (its iterations run by this package's host sampler), written to
+    ``path`` as a real HDF5 file; returns (arrays by path, the schema's meta)."""
     from geobipy_amd import hdf
     from test_hdf_layout import _run
     meta = json.load(open(os.path.join(GOLDEN, "hdf_schema.json")))["meta"]
     inf = _run(meta["iterations"])
-    path = str(tmp_path / "0.0.h5")
     root = hdf.open_results(path, container="hdf5")
     hdf.create_inference1d(root, inf, add_axis=meta["fiducials"])
     for _ in range(meta["iterations"]):
@@ -135,11 +123,33 @@ def test_the_references_own_readers_open_our_file(tmp_path):
     mem = root.arrays()
     root.container = "hdf5"
     root.save(path)
-    out = str(tmp_path / "read.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME")}
-    r = subprocess.run([CHECKER, os.path.join(ROOT, "tests", "ref_reads_h5.py"), path, "1", out], capture_output=True, text=True, timeout=900, env=env)
-    assert r.returncode == 0, r.stderr[-4000:]
-    got = json.load(open(out))
+    return mem, meta
+
+
+# iterations the reference's side ran for each recorded container (tests/golden/reference_<kind>.h5.gz) and this package's side runs again
+# (the SkyTEM container is sized for 300: 80 keep the CPU tier short)
+REFERENCE_RUN_ITERATIONS = {"resolve": 150, "skytem": 80, "tempest": 60}
+
+
+def test_the_references_own_readers_open_our_file(tmp_path):
+    """Row f-4's purpose: "the reference's own post-processing can read our outputs".  tests/ref_reads_h5.py opened the .h5 this package
+    writes for the seeded container with h5py.File and read sounding 1 with the reference's ``Histogram.fromHdf`` (layer-count,
+    interface-depth and conductivity-depth posteriors), ``Model.fromHdf`` (best model) and ``hdfRead.readKeyFromFile`` (the FdemDataPoint
+    with its error-level posteriors, the counters, the misfit trace); what they returned is recorded in
+    tests/golden/reference_reads_ours.json (tests/golden/make_reference_records.py, where the reference can be imported).  The container
+    written here holds exactly those numbers.  (``Inference1D.fromHdf`` itself cannot be the check: at Inference1D.py:1152-1155 it reads
+    the model through ``StatArray.fromHdf(grp, 'values')``, which looks for 'n_posteriors' in the PARENT group (StatArray.py:907) and so
+    returns a DataArray without the posterior ``fromHdf`` then asks for -- on the reference's own files as on these.)"""
+    _needs()
+    path = str(tmp_path / "0.0.h5")
+    mem, meta = _seeded_container(path)
+    got = json.load(open(os.path.join(GOLDEN, "reference_reads_ours.json")))
+    filed, _ = h5dump(path, tmp_path)                    # the file itself, as the real h5py reads it, holds the arrays compared below
+    for p in ("/model/mesh/nCells/data", "/model/values/data", "/model/mesh/y/edges/data", "/model/mesh/nCells/posterior/values/data",
+              "/model/mesh/y/edges/posterior/values/data", "/model/values/posterior/values/data", "/iteration", "/burned_in", "/halfspace/data",
+              "/multiplier", "/data/data/data", "/data/predicted_data/data", "/data/relative_error/data", "/data/additive_error/data",
+              "/data/relative_error/posterior/values/data", "/data/additive_error/posterior/values/data", "/phids/data"):
+        assert np.array_equal(filed[p], mem[p], equal_nan=filed[p].dtype.kind == "f"), p
     arr = lambda v: np.array([np.nan if q is None else q for q in v], dtype=np.float64)
     k = int(mem["/model/mesh/nCells/data"][1])
     assert got["model"]["nCells"] == k >= 1                                                                  # (the container holds the BEST model)
@@ -169,7 +179,8 @@ def test_the_references_readers_open_a_file_the_device_path_wrote(tmp_path):
     file (tests/golden/make_device_h5.py: the device sampler's rows -> LineSpec tree, hit maps as deflated chunks made from their runs,
     traces), device_survey_summary.npz what the same call returned.  In the build container the REFERENCE's readers open that file through
     the real h5py and return the survey's numbers: best model, layer-count / interface / conductivity-depth posteriors, counters, the data
-    point.  Everywhere: this package's own reader (no h5py) against the summary."""
+    point -- recorded in tests/golden/reference_reads_device_survey.json (tests/golden/make_reference_records.py).  This package's own
+    reader (no h5py) against the summary, and what the reference's readers returned against both."""
     _needs()
     from geobipy_amd import hdf
     path = os.path.join(GOLDEN, "device_survey_0.0.h5")
@@ -182,15 +193,10 @@ def test_the_references_readers_open_a_file_the_device_path_wrote(tmp_path):
     assert np.array_equal(arrays["/iteration"], s["iterations"][order]) and np.array_equal(arrays["/model/mesh/nCells/data"], s["best_n_layers"][order])
     hm = arrays["/model/values/posterior/values/data"]
     assert hm.shape == (8, 250, 440) and np.array_equal(hm.sum(axis=1), np.repeat(s["layer_count_posterior"][order].sum(axis=1)[:, None], 440, axis=1))
-    if not os.path.isdir("/root/reference/geobipy") or subprocess.run([CHECKER, "-c", "import h5py, matplotlib, scipy"], capture_output=True).returncode != 0:
-        return                                                       # (the reference's side: build container only)
-    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME")}
+    recorded = json.load(open(os.path.join(GOLDEN, "reference_reads_device_survey.json")))
     arr = lambda v: np.array([np.nan if q is None else q for q in v], dtype=np.float64)
     for i in (0, 7):
-        out = str(tmp_path / "read{}.json".format(i))
-        r = subprocess.run([CHECKER, os.path.join(ROOT, "tests", "ref_reads_h5.py"), path, str(i), out], capture_output=True, text=True, timeout=900, env=env)
-        assert r.returncode == 0, r.stderr[-4000:]
-        got, j = json.load(open(out)), order[i]
+        got, j = recorded[str(i)], order[i]
         k = int(s["best_n_layers"][j])
         assert got["model"]["nCells"] == k and np.array_equal(arr(got["model"]["values"]), s["best_conductivity"][j, :k])
         assert np.array_equal(arr(got["model"]["edges"])[1:k], s["best_edges"][j, :k - 1]) and arr(got["model"]["edges"])[0] == 0.0
@@ -206,8 +212,9 @@ def test_the_references_readers_open_a_file_the_device_path_wrote(tmp_path):
 
 @pytest.mark.parametrize("kind", ["resolve", "skytem", "tempest"])
 def test_a_file_the_reference_wrote_and_ours_are_the_same_tree(tmp_path, kind):
-    """Build container only.  tests/ref_writes_h5.py lets the REFERENCE write the seeded container into a real ``h5py.File`` (its own
-    createHdf / writeHdf, no stand-in anywhere); this package writes the same sounding through h5lite; the real h5py opens both.  Same
+    """tests/ref_writes_h5.py let the REFERENCE write the seeded container into a real ``h5py.File`` (its own createHdf / writeHdf, no
+    stand-in anywhere; recorded as tests/golden/reference_<kind>.h5.gz by tests/golden/make_reference_records.py); this package writes the
+    same sounding through h5lite; the real h5py opens both.  Same
     paths; per path the same kind, shape, dtype, attributes (and their Python types), FILL VALUE -- NaN for floats, the most negative
     integer for the counters and posterior counts (the reference's NaN fill cast by the library), which is what the rows nothing wrote
     to read -- and the same numbers (integers equal: the chains take the same decisions; floats to 1e-7: the checker's numpy / LAPACK
@@ -217,17 +224,13 @@ def test_a_file_the_reference_wrote_and_ours_are_the_same_tree(tmp_path, kind):
     This comparison is what found the three things the call-recording stand-in could not show (it ignored ``shape=`` next to ``data=`` and
     kept zeros where a NaN fill meets an integer type): 'dimension' is shape (1,), integer fills are INT_MIN, 'fiducial' carries a NaN fill."""
     _needs()
-    if not os.path.isdir("/root/reference/geobipy"):
-        pytest.skip("the reference tree is only present in the build container")
-    if subprocess.run([CHECKER, "-c", "import h5py, matplotlib, scipy"], capture_output=True).returncode != 0:
-        pytest.skip("the checker interpreter cannot import what the reference needs")
     from geobipy_amd import h5lite, hdf
     import test_hdf_layout as L
-    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME")}
     ref_path = str(tmp_path / "reference.h5")
-    n_run = {"resolve": 150, "skytem": 80, "tempest": 60}[kind]      # iterations both sides run (the SkyTEM container is sized for 300: 80 keep the CPU tier short)
-    r = subprocess.run([CHECKER, os.path.join(ROOT, "tests", "ref_writes_h5.py"), ref_path, kind, str(n_run)], capture_output=True, text=True, timeout=1800, env=env, cwd=str(tmp_path))
-    assert r.returncode == 0 and os.path.getsize(ref_path) > 1_000_000, r.stderr[-4000:]
+    n_run = REFERENCE_RUN_ITERATIONS[kind]                            # iterations both sides ran
+    with gzip.open(os.path.join(GOLDEN, "reference_%s.h5.gz" % kind), "rb") as src, open(ref_path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    assert os.path.getsize(ref_path) > 1_000_000
     # (the time-domain kinds: the reference runs on tests/golden/fake_gatdaem1d.py, whose physics is this repository's oracle, and the
     #  host sampler here has the same oracle as its engine -- the CONTAINERS are what is compared, tests/ref_writes_h5.py)
     if kind == "resolve":
