@@ -1262,6 +1262,31 @@ extern "C" gbp_status gbp_hitmap_statistics(int B, int nv, int nz, const int32_t
     return GBP_OK;
 }
 
+// Per-column moments of B hit maps [B, nv, nz] for the line products: mean (as gbp_hitmap_statistics), mode index, n_q quantile indices
+// (q: host array, 0 < q < 1, n_q <= 8), total and sum c ln c -> [B, nz] arrays ([n_q, B, nz] for q_idx)
+extern "C" gbp_status gbp_hitmap_products(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width,
+                                          int n_q, const double* q, double* mean, int32_t* mode_idx, int32_t* q_idx, int64_t* total,
+                                          double* s1, void* stream)
+{
+    if (B < 0 || nv < 1 || nz < 1 || n_q < 0 || n_q > 8 || (n_q > 0 && !q))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: non-positive size, n_q outside 0 .. 8 or q NULL%s");
+    hitmap::Quantiles qs = {};
+    qs.n = n_q;
+    for (int k = 0; k < n_q; ++k) {
+        if (!(q[k] > 0.0 && q[k] < 1.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: every quantile must lie in (0, 1)%s");
+        qs.q[k] = q[k];
+    }
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!hitmap || !log_mean_prior || !mean || !mode_idx || (n_q > 0 && !q_idx) || !total || !s1)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: NULL pointer%s");
+    if ((int64_t)B * nz > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: B * n_depth out of range%s");
+    static_assert(sizeof(long long) == sizeof(int64_t), "int64_t is long long here");
+    hipLaunchKernelGGL(hitmap::k_hitmap_products, dim3(B, (nz + 255) / 256), dim3(256), 0, (hipStream_t)stream, nv, nz, hitmap, log_mean_prior,
+                       half_width, qs, mean, mode_idx, q_idx, (long long*)total, s1);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 // The hit maps' rows (M = nv * nz cells each) as runs.  Call with start == NULL to COUNT (counts[B] <- runs per row), build the
 // exclusive prefix ptr[B + 1] of the counts, allocate ptr[B] entries, then call again with ptr / start / value to WRITE.
 extern "C" gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t* hitmap, int64_t* counts, const int64_t* ptr, int32_t* start,

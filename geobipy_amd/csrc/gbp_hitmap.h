@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gbp_math.h"
+
 namespace hitmap {
 
 // mean[b, z] = sum_v h (c_v) / max(1, sum_v h) + shift_b,  c_v = ((v + 0.5) / nv) 2 hw - hw, shift_b = log_mean_prior[b] / ln 10;
@@ -47,6 +49,61 @@ __global__ __launch_bounds__(256) void k_hitmap_stats(int nv, int nz, const int*
     p05[o] = centre(i05) + shift;
     p50[o] = centre(i50) + shift;
     p95[o] = centre(i95) + shift;
+}
+
+// Up to 8 quantiles in (0, 1), passed by value (kernel arguments: no device copy).
+struct Quantiles {
+    double q[8];
+    int n;
+};
+
+// The per-column moments the line products derive from (python: geobipy_amd/line_products.py), one workgroup per (sounding, 256 depth
+// cells) as k_hitmap_stats, thread z walking the value cells of its column twice -- the second pass reads the 256 KB column tile of the
+// first from L2:
+//   total[b, z] = sum_v c_v (int64);  mean[b, z] = k_hitmap_stats's mean (same expression, same order: the same bits);
+//   mode_idx[b, z] = first v of max_v c_v (numpy argmax; an empty column: 0);  s1[b, z] = sum_v c_v ln c_v (0 ln 0 = 0; gbp::log_pos);
+//   q_idx[k, b, z] = #{v : cumsum_v / max(total, 1) < q_k} clamped to nv - 1 (mesh/Mesh.py _percentile's searchsorted).
+__global__ __launch_bounds__(256) void k_hitmap_products(int nv, int nz, const int* __restrict__ hm, const double* __restrict__ log_mean_prior,
+                                                          double half_width, Quantiles qs, double* __restrict__ mean, int* __restrict__ mode_idx,
+                                                          int* __restrict__ q_idx, long long* __restrict__ total, double* __restrict__ s1)
+{
+    const int b = blockIdx.x, z = blockIdx.y * 256 + threadIdx.x;
+    if (z >= nz) return;
+    const int* col = hm + (size_t)b * nv * nz + z;
+    const double shift = log_mean_prior[b] / 2.302585092994046;
+    const double w = 2.0 * half_width;
+    long long tot = 0;
+    double wsum = 0.0, slog = 0.0;
+    int best = col[0], ibest = 0;
+#pragma unroll 10
+    for (int v = 0; v < nv; ++v) {
+        const int h = col[(size_t)v * nz];
+        tot += h;
+        wsum += (double)h * ((((double)v + 0.5) / (double)nv) * w - half_width);
+        if (h > 0) slog += (double)h * gbp::log_pos((double)h);      // (a branch: a wave whose 64 cells are empty skips the logarithm)
+        ibest = h > best ? v : ibest;
+        best = h > best ? h : best;
+    }
+    const double t = (double)(tot > 1 ? tot : 1);
+    int iq[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) iq[k] = 0;
+    long long cum = 0;
+#pragma unroll 10
+    for (int v = 0; v < nv; ++v) {
+        cum += col[(size_t)v * nz];
+        const double cdf = (double)cum / t;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) iq[k] += (k < qs.n) & (cdf < qs.q[k]);
+    }
+    const size_t o = (size_t)b * nz + z, plane = (size_t)gridDim.x * nz;
+    mean[o] = wsum / t + shift;
+    mode_idx[o] = ibest;
+    total[o] = tot;
+    s1[o] = slog;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < qs.n) q_idx[k * plane + o] = iq[k] < nv - 1 ? iq[k] : nv - 1;
 }
 
 // Runs of a row's flattened cells: a run starts at cell 0 and wherever the count differs from the cell before.

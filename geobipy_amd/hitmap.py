@@ -5,9 +5,12 @@ the conductivity-depth posterior (statistics/Histogram.py:262-284, 369-401 -> me
 the imported reference computed (tests/golden/make_hitmap_stats.py -> hitmap_stats.npz, tests/test_hitmap_gpu.py).  There is no
 fallback: the entries refuse tensors that are not on the device (the torch formulations the kernels were first held to live in
 tests/hitmap_reference.py)."""
+import ctypes
+
 import torch
 
 from . import _lib
+from .line_products import entropy_bits, log10_shift, quantiles, value_centres
 
 
 def _stream(dev):
@@ -52,3 +55,50 @@ def runs(hitmap):
         value = torch.empty(n, dtype=torch.int32, device=dev)
         _lib.check(lib.gbp_hitmap_runs(B, M, hm.data_ptr(), None, ptr.data_ptr(), start.data_ptr(), value.data_ptr(), _stream(dev)))
     return ptr, start, value
+
+
+def moments(hitmap, log_mean_prior, half_width, q):
+    """The per-column moments of the hit maps [B, n_value, n_depth] in one kernel (gbp_hitmap_products): mean (log10, the bits of
+    ``statistics``), mode_idx, q_idx [len(q), B, n_depth], total (int64) and s1 = sum c ln c, on the maps' device."""
+    if hitmap.device.type != "cuda":
+        raise _lib.NativeLibraryError("hitmap.moments runs on the device (gbp_hitmap_products); there is no host fallback")
+    B, nv, nz = hitmap.shape
+    hm = hitmap.contiguous()
+    assert hm.dtype == torch.int32
+    dev = hm.device
+    lmp = log_mean_prior.to(device=dev, dtype=torch.float64).contiguous()
+    qa = (ctypes.c_double * max(len(q), 1))(*q)
+    mean = torch.empty((B, nz), dtype=torch.float64, device=dev)
+    s1 = torch.empty((B, nz), dtype=torch.float64, device=dev)
+    total = torch.empty((B, nz), dtype=torch.int64, device=dev)
+    mode_idx = torch.empty((B, nz), dtype=torch.int32, device=dev)
+    q_idx = torch.empty((len(q), B, nz), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gbp_hitmap_products(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), len(q), qa, mean.data_ptr(),
+                                                   mode_idx.data_ptr(), q_idx.data_ptr(), total.data_ptr(), s1.data_ptr(), _stream(dev)))
+    return dict(mean=mean, mode_idx=mode_idx, q_idx=q_idx, total=total, s1=s1)
+
+
+def products(hitmap, log_mean_prior, half_width, percentiles=(5, 50, 95), credible=90.0, depth_edges=None):
+    """Per-sounding posterior products of the hit maps [B, n_value, n_depth] in log10 conductivity, each [B, n_depth] on the maps' device
+    (the reference's ``Histogram`` along the value axis, statistics/Histogram.py): ``mean``, ``median``, ``mode`` (the centre of the first
+    cell of the largest count), ``percentile_<p>`` for each requested p, ``credible_low`` / ``credible_high`` / ``credible_range`` of the
+    ``credible`` % interval (``credible_range(credible, log=10)``), and ``entropy`` in bits (``Histogram.entropy``: the sum over the value
+    cells of -p log2 p with p the DENSITY c / sum(area c) over the sounding's cells of area dvalue x ddepth; ``depth_edges`` gives ddepth,
+    unit depth cells when None).  One kernel pass (``moments``) and elementwise finishing (line_products)."""
+    B, nv, nz = hitmap.shape
+    q, pos, (klo, khi) = quantiles(percentiles, credible)
+    m = moments(hitmap, log_mean_prior, half_width, q)
+    dev = m["mean"].device
+    shift = log10_shift(log_mean_prior).to(dev)[:, None]
+    centre = lambda idx: value_centres(idx, nv, half_width, shift)          # noqa: E731
+    out = dict(mean=m["mean"], median=centre(m["q_idx"][pos[50.0]]), mode=centre(m["mode_idx"]))
+    for p in percentiles:
+        out["percentile_%g" % float(p)] = centre(m["q_idx"][pos[float(p)]])
+    out["credible_low"], out["credible_high"] = centre(m["q_idx"][klo]), centre(m["q_idx"][khi])
+    out["credible_range"] = (out["credible_high"] - out["credible_low"]).abs()
+    dz = torch.ones(nz, dtype=torch.float64, device=dev) if depth_edges is None else \
+        torch.diff(torch.as_tensor(depth_edges, dtype=torch.float64, device=dev)).abs()
+    out["entropy"] = entropy_bits(m["total"], m["s1"], dz * (2.0 * float(half_width) / nv))
+    out["total"], out["s1"] = m["total"], m["s1"]
+    return out

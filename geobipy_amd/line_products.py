@@ -1,0 +1,286 @@
+"""Posterior line products of a flight line's results container: the mean, median and mode models, percentiles and the credible interval,
+entropy, opacity, depth of investigation (DOI) and interface probability -- what the reference's ``Inference2D`` derives from the hit maps
+(inversion/Inference2D.py: compute_mean/median/mode_parameter, percentile, credible_interval, compute_opacity, compute_doi, entropy,
+interface_probability).
+
+The work splits in two.  Per sounding, one streaming kernel reduces every (sounding, depth cell) column of the int32 hit maps to a few
+moments -- total, sum c ln c, the mode's cell, the quantiles' cells, the mean (csrc/gbp_hitmap.h: k_hitmap_products, through
+``hitmap.products``); the maps go up a block at a time and never leave the device.  Per line, the small functions below finish on
+[N, n_depth] arrays: they run on whichever device their tensors are on (the CPU tier tests them without a GPU).  Everything is log10
+conductivity (S/m) except entropy (bits), opacity (0 - 1) and the depths (m).
+
+    python -m geobipy_amd.line_products <container or directory> [--credible 90] [--doi 67] [--percentiles 5 50 95]
+
+writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.
+"""
+import argparse
+import glob
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+LN10 = 2.302585092994046
+MAX_QUANTILES = 8
+
+VALUES = "/model/values/posterior"            # the conductivity-depth hit maps [N, n_value, n_depth] and their mesh
+INTERFACES = "/model/mesh/y/edges/posterior"  # the interface-depth hit counts [N, n_depth]
+
+
+def _t(x, dtype=torch.float64):
+    return x.to(dtype) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x), dtype=dtype)
+
+
+def credible_bounds(credible):
+    """(low, high) percents of the ``credible`` % interval: 0.5 min(c, 100 - c) and 100 minus it (mesh/Mesh.py:58-78)."""
+    lo = 0.5 * min(float(credible), 100.0 - float(credible))
+    return lo, 100.0 - lo
+
+
+def quantiles(percentiles=(5, 50, 95), credible=90.0):
+    """(q, {percent: position in q}, (low, high) positions of the credible bounds in q): the distinct quantiles in (0, 1), at most 8,
+    one kernel pass needs for the requested percentiles, the median and the ``credible`` % interval.  The two forms differ where a
+    cumulative share falls EXACTLY on a quantile, as the reference's do: a percentile p is the quantile p / 100, correctly rounded
+    (the 0.05 / 0.5 / 0.95 of ``hitmap.statistics``, and the reference's ``Histogram.percentile``, whose shares are cumulative sums of
+    the pmf that round to the same side on such ties), a credible bound b is b * 0.01 (``Histogram.credible_range`` cumulates the
+    integer counts against r_[b, 100 - b] * 0.01, mesh/Mesh.py:58-78: 95 * 0.01 = 0.9500000000000001).  The fixture
+    tests/golden/line_products.npz holds such ties."""
+    lo, hi = credible_bounds(credible)
+    pct = sorted({float(p) for p in percentiles} | {50.0})
+    if not all(0.0 < p < 100.0 for p in pct) or not 0.0 < lo < 100.0:
+        raise ValueError("percentiles and the credible interval must lie in (0, 100): %r, %r" % (pct, credible))
+    q = sorted({p / 100.0 for p in pct} | {lo * 0.01, hi * 0.01})
+    if len(q) > MAX_QUANTILES:
+        raise ValueError("at most %d distinct quantiles (percentiles + median + credible bounds) per pass, got %d" % (MAX_QUANTILES, len(q)))
+    return q, {p: q.index(p / 100.0) for p in pct}, (q.index(lo * 0.01), q.index(hi * 0.01))
+
+
+def log10_shift(log_mean_prior):
+    """The prior mean in log10, ln / 2.302585092994046 as k_hitmap_stats divides it ([B] float64 on the input's device; the division is
+    done by numpy, correctly rounded, where torch's division of a device tensor by a scalar multiplies by the reciprocal)."""
+    dev = log_mean_prior.device if torch.is_tensor(log_mean_prior) else torch.device("cpu")
+    lmp = log_mean_prior.detach().cpu().numpy() if torch.is_tensor(log_mean_prior) else np.asarray(log_mean_prior)
+    return torch.as_tensor(np.asarray(lmp, dtype=np.float64) / LN10).to(dev)
+
+
+def value_centres(idx, n_value, half_width, shift):
+    """log10 conductivity of value cell ``idx``: ((idx + 0.5) / n_value) 2 half_width - half_width + shift, the centre expression of
+    k_hitmap_stats evaluated once per cell by numpy and gathered, so that a percentile here has the bits of ``hitmap.statistics``'s on
+    any device (``shift`` from ``log10_shift``, broadcast against ``idx``)."""
+    idx = idx if torch.is_tensor(idx) else torch.as_tensor(np.asarray(idx))
+    table = ((np.arange(int(n_value), dtype=np.float64) + 0.5) / float(n_value)) * (2.0 * float(half_width)) - float(half_width)
+    c = torch.as_tensor(table).to(idx.device)[idx.long()]
+    return c + _t(shift).to(c.device)
+
+
+def entropy_bits(total, s1, cell_area):
+    """Entropy in bits per depth cell from the column moments [B, n_depth] (``total`` = S0 = sum_v c, ``s1`` = S1 = sum_v c ln c) and the
+    cell areas dvalue x ddepth [n_depth], under the reference's normalisation (``Histogram.entropy`` over ``Histogram.pdf``,
+    statistics/Histogram.py:34-41, 129-148): p = c / Z with Z = sum over the sounding's cells of area c, so
+    H_z = -sum_v p log2 p = -(S1_z - S0_z ln Z) / (Z ln 2).  An empty sounding (Z = 0) has entropy 0, as the reference's zero pdf."""
+    S0 = _t(total)
+    S1 = _t(s1).to(S0.device)
+    Z = (S0 * _t(cell_area).to(S0.device)).sum(dim=-1, keepdim=True)
+    Zs = torch.where(Z > 0, Z, torch.ones_like(Z))
+    H = -(S1 - S0 * torch.log(Zs)) / (Zs * math.log(2.0))
+    return torch.where(Z > 0, H, torch.zeros_like(H))
+
+
+def transparency(credible_range):
+    """The reference's transparency (statistics/Histogram.py:509-542) over a whole line [N, n_depth]: the credible range normalised by
+    its nanmin / nanmax over all soundings and depth cells (shifted only, when they are equal), NaN -> 1."""
+    r = _t(credible_range)
+    fin = r[~torch.isnan(r)]
+    if fin.numel() == 0:
+        return torch.ones_like(r)
+    mn, mx = fin.min(), fin.max()
+    t = (r - mn) / (mx - mn) if float(mx - mn) > 0.0 else r - mn
+    return torch.where(torch.isnan(t), torch.ones_like(t), t)
+
+
+def opacity(credible_range):
+    """1 - ``transparency``: narrow credible intervals are opaque (statistics/Histogram.py:330-354)."""
+    return 1.0 - transparency(credible_range)
+
+
+def doi_index(opac, percent=67.0):
+    """The reference's DOI walk (inversion/Inference2D.py:493-535) per sounding of opacity [N, n_depth]: from the deepest cell up while
+    the opacity is below percent / 100, stopping at cell 0 -- the deepest cell whose opacity reaches the level, else 0 (int64 [N])."""
+    if not 0.0 < float(percent) < 100.0:
+        raise ValueError("the DOI percent must lie in (0, 100)")
+    o = _t(opac)
+    keep = ~(o < 0.01 * float(percent))                               # (a NaN stops the walk, as in the reference's loop)
+    keep[:, 0] = True
+    j = torch.arange(o.shape[-1], device=o.device).expand_as(o)
+    return torch.where(keep, j, torch.zeros_like(j)).max(dim=-1).values
+
+
+def interface_pdf(counts, x_edges, depth_edges):
+    """``Histogram.pdf`` (statistics/Histogram.py:34-41) of the line's interface-depth histogram [N, n_depth] over its 2-D mesh (the
+    container's sounding axis x by depth): counts / sum(area counts) with area = |dx| |ddepth|; all zero when nothing was counted.
+    With one sounding, the pdf over its 1-D depth mesh."""
+    c = _t(counts)
+    area = torch.outer(torch.diff(_t(x_edges)).abs(), torch.diff(_t(depth_edges)).abs()).to(c.device)
+    if float(c.max()) <= 0:
+        return torch.zeros_like(c)
+    return c / (area * c).sum()
+
+
+def _uniform_half_width(edges):
+    e = np.asarray(edges, dtype=np.float64)
+    hw = float(e[-1])
+    n = e.size - 1
+    step = 2.0 * hw / n
+    if abs(e[0] + hw) > 1e-9 * max(1.0, hw) or np.abs(np.diff(e) - step).max() > 1e-9 * max(1.0, step):
+        raise ValueError("the value axis of %s must be uniform and symmetric about the prior mean (edges %r .. %r)" % (VALUES, e[0], e[-1]))
+    return hw
+
+
+def _key(arrays, *names):
+    for n in names:
+        if n in arrays:
+            return np.asarray(arrays[n])
+    return None
+
+
+def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0):
+    """{name: numpy array} of the line products of the results container at ``path`` (``<line>.h5`` or the ``.results[.npz]`` stand-in,
+    read through ``hdf.load_results``; the reference's own files where they hold this layout).  The hit maps go to ``device`` (default
+    cuda:0) ``block`` soundings at a time.  Per sounding [N, n_depth] (log10 S/m): mean, median, mode, percentile_<p>, credible_low /
+    high / range; entropy (bits); per line: transparency and opacity at ``credible`` %, doi_index / doi_depth at ``doi`` % and
+    interface_probability [N, n_depth].
+
+    The reference's DOI is ``mesh.y_centres`` at the index of the walk, and its mesh flips depth to height relative to the data's
+    elevation (Inference2D.mesh: y edges negated, relative_to = elevation), so y_centres = elevation - depth centre.  ``doi_depth`` is
+    the depth centre below the surface (m, positive down); ``doi_elevation`` = elevation - doi_depth is the reference's value, present
+    where the container has /data/elevation."""
+    from . import hdf, hitmap
+    if not 0.0 < float(credible) < 100.0:
+        raise ValueError("credible must lie in (0, 100)")
+    arrays, _ = hdf.load_results(path)
+    hm_all = _key(arrays, VALUES + "/values/data", VALUES + "/values")
+    if hm_all is None or hm_all.ndim != 3:
+        raise ValueError("%s holds no conductivity-depth hit maps [N, n_value, n_depth] at %s" % (path, VALUES))
+    v_edges = _key(arrays, VALUES + "/mesh/y/edges/data")
+    d_edges = _key(arrays, VALUES + "/mesh/z/edges/data")
+    rel = _key(arrays, VALUES + "/mesh/y/relative_to/data")
+    N, nv, nz = hm_all.shape
+    if v_edges is None or d_edges is None or v_edges.size != nv + 1 or d_edges.size != nz + 1:
+        raise ValueError("%s: the hit maps' mesh (%s/mesh/y and /z edges) does not match their shape %r" % (path, VALUES, hm_all.shape))
+    hw = _uniform_half_width(v_edges)
+    rel = np.zeros(N) if rel is None else np.broadcast_to(np.asarray(rel, dtype=np.float64).reshape(-1), (N,))
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    parts = []
+    for b0 in range(0, N, int(block)):
+        b1 = min(N, b0 + int(block))
+        hm = torch.as_tensor(np.ascontiguousarray(hm_all[b0:b1], dtype=np.int32)).to(dev)
+        lmp = torch.as_tensor(rel[b0:b1] * LN10, dtype=torch.float64, device=dev)
+        p = hitmap.products(hm, lmp, hw, percentiles=percentiles, credible=credible, depth_edges=d_edges)
+        parts.append({k: v.cpu() for k, v in p.items()})
+    keys = parts[0].keys() if parts else []
+    out = {k: torch.cat([p_[k] for p_ in parts]).numpy() for k in keys}
+    out.pop("total", None)
+    out.pop("s1", None)
+    cr = torch.as_tensor(out["credible_range"]) if N else torch.zeros((0, nz), dtype=torch.float64)
+    t = transparency(cr) if N else cr
+    out["transparency"] = t.numpy()
+    out["opacity"] = (1.0 - t).numpy()
+    j = doi_index(1.0 - t, doi).numpy() if N else np.zeros(0, dtype=np.int64)
+    depth_centres = 0.5 * (d_edges[1:] + d_edges[:-1])
+    out["doi_index"] = j
+    out["doi_depth"] = depth_centres[j]
+    elev = _key(arrays, "/data/elevation/data", "/data/elevation")
+    if elev is not None and np.asarray(elev).size == N:
+        out["doi_elevation"] = np.asarray(elev, dtype=np.float64).reshape(-1) - out["doi_depth"]
+    ic = _key(arrays, INTERFACES + "/values/data")
+    ix = _key(arrays, INTERFACES + "/mesh/x/edges/data")
+    iz = _key(arrays, INTERFACES + "/mesh/y/edges/data")
+    if ic is not None and ix is not None and iz is not None and ic.ndim == 2 and ic.shape[0] == N:
+        out["interface_probability"] = interface_pdf(ic, ix, iz).numpy()
+        out["interface_depth_edges"] = np.asarray(iz, dtype=np.float64)
+    out["depth_edges"] = np.asarray(d_edges, dtype=np.float64)
+    out["depth_centres"] = depth_centres
+    fid = _key(arrays, "/data/fiducial/data", "/data/fiducial")
+    if fid is not None:
+        out["fiducial"] = np.asarray(fid)
+    out["credible"], out["doi_percent"] = np.float64(credible), np.float64(doi)
+    return out
+
+
+def save(products, path):
+    """Write ``products`` ({name: array}) to ``path`` (``<line>.products.npz``) with np.savez_compressed; returns the path."""
+    np.savez_compressed(path, **{k: np.asarray(v) for k, v in products.items()})
+    return path
+
+
+_SUFFIXES = (".results.npz", ".results", ".hdf5", ".h5")
+
+
+def output_path(container):
+    """``<line>.products.npz`` next to the container ``<line>.h5`` / ``<line>.hdf5`` / ``<line>.results[.npz]``."""
+    for s in _SUFFIXES:
+        if container.endswith(s):
+            return container[:-len(s)] + ".products.npz"
+    return container + ".products.npz"
+
+
+def containers(path):
+    """The results containers at ``path``: the file itself, or a directory's ``*.h5`` / ``*.hdf5`` / ``*.results.npz``, sorted."""
+    if os.path.isdir(path):
+        found = set()
+        for pat in ("*.h5", "*.hdf5", "*.results.npz"):
+            found.update(glob.glob(os.path.join(path, pat)))
+        return sorted(found)
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    return [path]
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="python -m geobipy_amd.line_products",
+                                 description="Posterior line products (mean, median, mode, percentiles, credible range, entropy, opacity, "
+                                             "DOI, interface probability) of GeoBIPy results containers, written to <line>.products.npz.")
+    ap.add_argument("paths", nargs="+", help="results containers (<line>.h5, <line>.results.npz) or directories holding them")
+    ap.add_argument("--credible", type=float, default=90.0, help="credible interval of the opacity, percent (default 90)")
+    ap.add_argument("--doi", type=float, default=67.0, help="opacity level of the depth of investigation, percent (default 67)")
+    ap.add_argument("--percentiles", type=float, nargs="+", default=[5.0, 50.0, 95.0], help="percentiles to write (default 5 50 95)")
+    ap.add_argument("--block", type=int, default=4096, help="soundings per upload (default 4096)")
+    ap.add_argument("--device", default=None, help="torch device of the kernel (default cuda:0)")
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line's arguments, checked: percents in (0, 100), at most 8 distinct quantiles per pass, a positive block."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    for name, v in (("--credible", a.credible), ("--doi", a.doi)):
+        if not 0.0 < v < 100.0:
+            ap.error("%s must lie in (0, 100), got %g" % (name, v))
+    if any(not 0.0 < p < 100.0 for p in a.percentiles):
+        ap.error("--percentiles must lie in (0, 100)")
+    try:
+        quantiles(a.percentiles, a.credible)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.block < 1:
+        ap.error("--block must be positive")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    files = [f for p in a.paths for f in containers(p)]
+    if not files:
+        print("no results containers under %s" % " ".join(a.paths), file=sys.stderr)
+        return 1
+    for f in files:
+        out = from_results(f, device=a.device, block=a.block, percentiles=tuple(a.percentiles), credible=a.credible, doi=a.doi)
+        dst = save(out, output_path(f))
+        print("%s -> %s (%d soundings)" % (f, dst, out["mean"].shape[0]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -598,6 +598,14 @@ gbp_status gbp_hitmap_statistics(int B, int n_value, int n_depth, const int32_t 
                                  double *mean, double *p05, double *p50, double *p95, void *stream);
 gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t *hitmap, int64_t *counts, const int64_t *ptr, int32_t *start, int32_t *value,
                            void *stream);
+/* gbp_hitmap_products -- the per-column moments the line products (mode, percentiles, credible range, opacity, DOI, entropy:
+ * geobipy_amd/line_products.py) derive from, each [B, n_depth]: mean as gbp_hitmap_statistics (the same bits); mode_idx = the first value
+ * bin of the largest count (0 for an empty column); total = sum_v c (int64); s1 = sum_v c ln c (0 ln 0 = 0); and q_idx [n_q, B, n_depth] =
+ * #{v : cumsum_v / max(total, 1) < q[k]} clamped to n_value - 1, the bin of quantile q[k] (q: a HOST array of n_q <= 8 values in (0, 1);
+ * q_idx may be NULL when n_q == 0).  GBP_ERR_INVALID_ARG for bad sizes, NULL pointers or a q outside (0, 1). */
+gbp_status gbp_hitmap_products(int B, int n_value, int n_depth, const int32_t *hitmap, const double *log_mean_prior, double half_width,
+                               int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
+                               void *stream);
 
 /* [host] Results containers (geobipy_amd/h5lite.py; no reference counterpart -- the reference stores its hit maps dense): the rows of
  * a conductivity-depth hit map held as runs (row r owns runs ptr[r] .. ptr[r + 1] - 1; run q holds value[q] from cell start[q] of the row
