@@ -50,6 +50,8 @@ struct BinDesc {
     int chan_off;        // first Channel of the bin in d_bin_chan
     int npts_total;      // points of the bin's flattened list (stride of its SoA)
     long long pts_off;   // first double of the bin's SoA in d_bin_pts
+    int one_per_pass;    // 1: every frequency's window is exactly one 64-point pass, starting at 64 f (forward_passes_1f)
+    int spare;
 };
 
 struct gbp_fdem_system {
@@ -117,10 +119,12 @@ __device__ __forceinline__ void phys_tick(PhysClk* k, int slot)
 #define GBP_TICK(slot) phys_tick(gbp_clk, (slot))
 #define GBP_TICK_ARGS , PhysClk* gbp_clk = nullptr
 #define GBP_TICK_PASS , gbp_clk
+#define GBP_TICK_NONE , nullptr
 #else
 #define GBP_TICK(slot)
 #define GBP_TICK_ARGS
 #define GBP_TICK_PASS
+#define GBP_TICK_NONE
 #endif
 
 // per-workgroup copy of the lookup tables in LDS + the scalar constants in SGPRs
@@ -238,6 +242,24 @@ __device__ __forceinline__ void wave_sum_store(double re, double im, int lane, c
     const double v = wave_sum_pair(re, im, lane);
     if (lane >= 62) reinterpret_cast<double*>(dst)[lane - 62] = v;
 }
+// Two complex sums (a: re0, im0; b: re1, im1) with one tree, stored to dst[0] and dst[2] (the partials of two consecutive passes).  The
+// lane ^ 1 step leaves the real parts of both in the even lanes and the imaginary parts in the odd ones, the lane ^ 2 step pass a in
+// lanes 0, 1 of every quad and pass b in lanes 2, 3; from there on it is wave_sum_pair's tree.  Every value meets the partners it meets
+// in wave_sum_store, in the same order: the same bits, for 37 VALU issues against 2 x 26.
+__device__ __forceinline__ void wave_sum_store2(double re0, double im0, double re1, double im1, int lane, cplx* dst)
+{
+    const bool odd = lane & 1, hi = lane & 2;
+    double x = odd ? im0 : re0, y = odd ? im1 : re1;
+    x += dpp_get<0xB1>(odd ? re0 : im0);     // quad_perm [1,0,3,2]
+    y += dpp_get<0xB1>(odd ? re1 : im1);
+    double v = hi ? y : x;
+    v += dpp_get<0x4E>(hi ? x : y);          // quad_perm [2,3,0,1]
+    v += dpp_get<0x114>(v);
+    v += dpp_get<0x118>(v);
+    v = row_pair_sum<16>(v);
+    v = row_pair_sum<32>(v);
+    if (lane >= 60) reinterpret_cast<double*>(dst)[(lane & 3) + (lane & 2)] = v;   // lanes 60 - 63: re0, im0, re1, im1
+}
 
 // Smallest conductivity of the sounding (wave-uniform, returned in SGPRs; each wave of the workgroup evaluates it).
 __device__ __forceinline__ double wave_min_sigma(const double* __restrict__ sig, int L, int lane)
@@ -340,6 +362,36 @@ __device__ __forceinline__ void forward_passes(const gbp::MathCtx& M, const Chan
     }
 }
 
+// forward_passes for a table set whose every frequency is exactly one pass (BinDesc::one_per_pass: chan[f].off == 64 f, npts == 64):
+// pass p is frequency p, so there is no frequency cursor, no second layer slot, no straddle and no ragged tail.  Each pair of passes
+// goes through one reduction tree (wave_sum_store2); the partials are the ones forward_passes stores, bit for bit.  The plain forward
+// kernel's path (no row scale).
+template <bool DIRECT>
+__device__ __forceinline__ void forward_passes_1f(const gbp::MathCtx& M, const Channel* __restrict__ chan,
+                                                  const double* __restrict__ pts, int P, int L, const double* __restrict__ sig,
+                                                  const double* sh_t2, gbp::LayerK* sh_lay, double alt, int p0, int p1, int lane,
+                                                  cplx* sh_part)
+{
+    cplx prev = gbp::mk(0.0, 0.0);
+    for (int p = p0; p < p1; ++p) {
+        const Channel cc = chan[p];
+        setup_layers(sh_lay, cc.wmu, sig, L, lane);
+        const double hD = cc.hd0 - 2.0 * alt;
+        const gbp::Point pt = gbp::load_point_u(pts, P, (unsigned)(64 * p + lane));
+        cplx num, den;
+        gbp::rte_num_den<DIRECT>(M, pt.a, L, sh_lay, sh_t2, pt.u0, num, den);
+        const bool real_ue = __ballot(pt.ue.im != 0.0) == 0ull;            // (wave-uniform: see hankel_term)
+        const cplx t = gbp::hankel_term(M, num, den, pt.ue, hD, pt.coef, real_ue);
+        if ((p - p0) & 1)
+            wave_sum_store2(prev.re, prev.im, t.re, t.im, lane, sh_part + 2 * (p - 1));
+        else if (p + 1 < p1)
+            prev = t;
+        else
+            wave_sum_store(t.re, t.im, lane, sh_part + 2 * p);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // chi^2 / logL of one sounding from N predicted channels held in `p` (LDS or global); executed by one wave.
 __device__ __forceinline__ void loglike_wave(int N, const double* p, const double* __restrict__ obs, double rel,
                                              double add, int lane, double* chi2, double* logL)
@@ -373,13 +425,16 @@ __device__ __forceinline__ void loglike_wave(int N, const double* p, const doubl
 //   LayerK lay[nwaves][2][Lmax] | cplx part[passes][2] | double t2[Lmax]
 // The passes are shared by the first `nw_use` waves of the workgroup (the others only take part in the barriers); the result
 // does not depend on nw_use (see forward_passes).
-template <bool LIKE>
+// ONE_PER_PASS (the plain forward kernel): the table set's frequencies are one pass each when `one_per_pass` (BinDesc) is set, and
+// forward_passes_1f runs them; the sampler's kernels instantiate the general path only.
+template <bool LIKE, bool ONE_PER_PASS = false>
 __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_out, unsigned char* sh_dyn,
                                              const Channel* __restrict__ chan, const double* __restrict__ pts, int npts_total,
                                              int F, int Lmax, int L, const double* __restrict__ sig,
                                              const double* __restrict__ th, double alt, const double* __restrict__ obs_row,
                                              double rel_b, double add_b, double* __restrict__ pred_row, double* chi2_b,
-                                             double* logL_b, double sigma_direct, int nw_use, double row_scale = 1.0 GBP_TICK_ARGS)
+                                             double* logL_b, double sigma_direct, int nw_use, double row_scale = 1.0 GBP_TICK_ARGS,
+                                             bool one_per_pass = false)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -398,10 +453,16 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
         const int per = (npass + nwaves - 1) / nwaves;
         const int p0 = wave * per;
         const int p1 = min(npass, p0 + per);
-        if (direct)
+        if (ONE_PER_PASS && one_per_pass) {     // (workgroup-uniform: the sounding's own table set)
+            if (direct)
+                forward_passes_1f<true>(M, chan, pts, npts_total, L, sig, sh_t2, sh_lay, alt, p0, p1, lane, sh_part);
+            else
+                forward_passes_1f<false>(M, chan, pts, npts_total, L, sig, sh_t2, sh_lay, alt, p0, p1, lane, sh_part);
+        } else if (direct) {
             forward_passes<true>(M, chan, pts, npts_total, F, L, sig, sh_t2, sh_lay, Lmax, alt, p0, p1, lane, sh_part, row_scale);
-        else
+        } else {
             forward_passes<false>(M, chan, pts, npts_total, F, L, sig, sh_t2, sh_lay, Lmax, alt, p0, p1, lane, sh_part, row_scale);
+        }
     }
     GBP_TICK(4);
     __syncthreads();
@@ -446,6 +507,7 @@ __global__ __launch_bounds__(1024) void k_fdem_forward(const Channel* __restrict
     __shared__ MathLds sh_math;
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
     const int b = blockIdx.x;
+    bool one_per_pass = false;
     if (bins != nullptr) {                                  // this sounding's table set and abscissa window (the bin of its own altitude)
         const int slot = table_slot(height[b], row_set != nullptr ? row_set[b] : 0, bin0, n_bins);
         if (slot >= 0) {                                    // (set 0 below the first bin, NaN: the handle's own tables, all abscissae)
@@ -453,6 +515,7 @@ __global__ __launch_bounds__(1024) void k_fdem_forward(const Channel* __restrict
             chan = bin_chan + d.chan_off;
             pts = bin_pts + d.pts_off;
             npts_total = d.npts_total;
+            one_per_pass = d.one_per_pass != 0;
         }
     }
     const int L = nlayers[b];
@@ -465,10 +528,10 @@ __global__ __launch_bounds__(1024) void k_fdem_forward(const Channel* __restrict
         return;
     }
     const gbp::MathCtx M = math_setup(sh_math);  // ends with __syncthreads()
-    forward_body<LIKE>(M, sh_out, sh_dyn, chan, pts, npts_total, F, Lmax, L, sigma + (size_t)b * Lmax, thk + (size_t)b * Lmax,
-                       height[b], LIKE ? obs + (size_t)b * 2 * F : nullptr, LIKE ? rel[b] : 0.0, LIKE ? add[b] : 0.0,
-                       pred != nullptr ? pred + (size_t)b * 2 * F : nullptr, LIKE ? chi2 + b : nullptr, LIKE ? logL + b : nullptr,
-                       sigma_direct, (int)(blockDim.x >> 6), (SCALED && row_scale != nullptr) ? row_scale[b] : 1.0);
+    forward_body<LIKE, !SCALED>(M, sh_out, sh_dyn, chan, pts, npts_total, F, Lmax, L, sigma + (size_t)b * Lmax, thk + (size_t)b * Lmax,
+                                height[b], LIKE ? obs + (size_t)b * 2 * F : nullptr, LIKE ? rel[b] : 0.0, LIKE ? add[b] : 0.0,
+                                pred != nullptr ? pred + (size_t)b * 2 * F : nullptr, LIKE ? chi2 + b : nullptr, LIKE ? logL + b : nullptr,
+                                sigma_direct, (int)(blockDim.x >> 6), (SCALED && row_scale != nullptr) ? row_scale[b] : 1.0 GBP_TICK_NONE, one_per_pass);
 }
 
 // Jacobian (+ prediction) of ONE sounding by the first `nw_use` waves of the calling workgroup: the body of k_fdem_sens, also
@@ -877,6 +940,9 @@ gbp_status gbp_hankel_system_add_bins(gbp_fdem_system* s, double eps, int relati
                 d.chan_off = (int)pk.chans.size();
                 d.npts_total = t.npts;
                 d.pts_off = (long long)pk.pts.size();
+                d.one_per_pass = t.npts == 64 * (int)t.chan.size();
+                for (size_t f = 0; f < t.chan.size(); ++f) d.one_per_pass &= t.chan[f].off == 64 * (int)f && t.chan[f].npts == 64;
+                d.spare = 0;
                 pk.desc.push_back(d);
                 pk.chans.insert(pk.chans.end(), t.chan.begin(), t.chan.end());
                 pk.pts.insert(pk.pts.end(), t.soa.begin(), t.soa.end());

@@ -54,6 +54,22 @@ GBP_HD Point load_point(const double* __restrict__ pts, int npts_total, int j)
     p.ue = mk(pts[5 * (size_t)npts_total + j], pts[6 * (size_t)npts_total + j]);
     return p;
 }
+// The same point from a wave-uniform base: the column starts (pts + c * npts_total) are uniform, the row's byte offset j * 8 is one
+// 32-bit value shared by the seven loads (a point set holds far fewer than 2^29 points), so each load is a global_load with a scalar
+// base and that offset instead of a 64-bit vector address per column.
+GBP_HD Point load_point_u(const double* __restrict__ pts, int npts_total, unsigned j)
+{
+    const char* base = reinterpret_cast<const char*>(pts);
+    const size_t col = (size_t)npts_total * sizeof(double);
+    const unsigned o = j * (unsigned)sizeof(double);
+    auto ld = [&](int c) { return *reinterpret_cast<const double*>(base + c * col + o); };
+    Point p;
+    p.a = ld(0);
+    p.u0 = mk(ld(1), ld(2));
+    p.coef = mk(ld(3), ld(4));
+    p.ue = mk(ld(5), ld(6));
+    return p;
+}
 
 // The point of the same filter abscissa for a receiver at horizontal distance rho' = rho / s when the tables were built for rho (raw
 // Hankel handles of DIPOLE sources, csrc/gbp_tdem.h: lam = base / rho, coef = lam^2 w / (4 pi rho) or lam w / (4 pi rho^2)): lam -> s lam,
