@@ -101,32 +101,6 @@ __constant__ gbp::MathK GBP_K = GBP_MATHK_INIT;
 __device__ const double GBP_EXP2_64[64] = GBP_EXP2_64_LIST;
 __device__ const double GBP_SINCOS_64[128] = GBP_SINCOS_64_LIST;
 
-#ifdef GBP_RJ_PHYS_CLOCK
-// Measurement builds only (scripts/build_ab.sh NAME -DGBP_RJ_PHYS_CLOCK, scripts/phys_clock.py): s_memtime stamps of the sampler's physics
-// workgroups, summed per slot by thread 0 of every 16th workgroup.  [slot]: ticks of the 100 MHz constant clock; [slot + 32]: samples.
-__device__ long long GBP_PHYS_TICKS[64];
-__device__ long long GBP_PHYS_LIFE[3 * 16 * 3];      // [kind][min(layers, 15)][sum of lives, workgroups, longest life]
-struct PhysClk { bool on; int base; long long t0; };
-__device__ __forceinline__ void phys_tick(PhysClk* k, int slot)
-{
-    if (k != nullptr && k->on) {
-        const long long t1 = (long long)wall_clock64();
-        atomicAdd((unsigned long long*)&GBP_PHYS_TICKS[k->base + slot], (unsigned long long)(t1 - k->t0));
-        atomicAdd((unsigned long long*)&GBP_PHYS_TICKS[k->base + slot + 32], 1ull);
-        k->t0 = t1;
-    }
-}
-#define GBP_TICK(slot) phys_tick(gbp_clk, (slot))
-#define GBP_TICK_ARGS , PhysClk* gbp_clk = nullptr
-#define GBP_TICK_PASS , gbp_clk
-#define GBP_TICK_NONE , nullptr
-#else
-#define GBP_TICK(slot)
-#define GBP_TICK_ARGS
-#define GBP_TICK_PASS
-#define GBP_TICK_NONE
-#endif
-
 // per-workgroup copy of the lookup tables in LDS + the scalar constants in SGPRs
 struct MathLds {
     double exp2_64[64];
@@ -433,7 +407,7 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
                                              int F, int Lmax, int L, const double* __restrict__ sig,
                                              const double* __restrict__ th, double alt, const double* __restrict__ obs_row,
                                              double rel_b, double add_b, double* __restrict__ pred_row, double* chi2_b,
-                                             double* logL_b, double sigma_direct, int nw_use, double row_scale = 1.0 GBP_TICK_ARGS,
+                                             double* logL_b, double sigma_direct, int nw_use, double row_scale = 1.0,
                                              bool one_per_pass = false)
 {
     const int lane = threadIdx.x & 63;
@@ -447,7 +421,6 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
     double* sh_t2 = reinterpret_cast<double*>(sh_part + (size_t)2 * npass);
     for (int k = threadIdx.x; k < L - 1; k += blockDim.x) sh_t2[k] = -2.0 * th[k];
     __syncthreads();
-    GBP_TICK(3);
 
     if (wave < nwaves) {
         const int per = (npass + nwaves - 1) / nwaves;
@@ -464,9 +437,7 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
             forward_passes<false>(M, chan, pts, npts_total, F, L, sig, sh_t2, sh_lay, Lmax, alt, p0, p1, lane, sh_part, row_scale);
         }
     }
-    GBP_TICK(4);
     __syncthreads();
-    GBP_TICK(5);
 
     // out_f = 1e6 * scale * (H - H0) / H0 = g_f * sum of the frequency's per-pass partials in pass order
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
@@ -485,7 +456,6 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
     if (pred_row != nullptr)
         for (int i = threadIdx.x; i < N; i += blockDim.x) pred_row[i] = sh_out[i];
     if (LIKE && wave == 0) loglike_wave(N, sh_out, obs_row, rel_b, add_b, lane, chi2_b, logL_b);
-    GBP_TICK(6);
 }
 
 template <bool LIKE, bool SCALED = false>   // SCALED: the rows carry a distance scale (gbp_fdem_forward_rows_scaled); the plain kernels do not pay for it (4 VGPRs, 36 B of scratch)
@@ -531,7 +501,7 @@ __global__ __launch_bounds__(1024) void k_fdem_forward(const Channel* __restrict
     forward_body<LIKE, !SCALED>(M, sh_out, sh_dyn, chan, pts, npts_total, F, Lmax, L, sigma + (size_t)b * Lmax, thk + (size_t)b * Lmax,
                                 height[b], LIKE ? obs + (size_t)b * 2 * F : nullptr, LIKE ? rel[b] : 0.0, LIKE ? add[b] : 0.0,
                                 pred != nullptr ? pred + (size_t)b * 2 * F : nullptr, LIKE ? chi2 + b : nullptr, LIKE ? logL + b : nullptr,
-                                sigma_direct, (int)(blockDim.x >> 6), (SCALED && row_scale != nullptr) ? row_scale[b] : 1.0 GBP_TICK_NONE, one_per_pass);
+                                sigma_direct, (int)(blockDim.x >> 6), (SCALED && row_scale != nullptr) ? row_scale[b] : 1.0, one_per_pass);
 }
 
 // Jacobian (+ prediction) of ONE sounding by the first `nw_use` waves of the calling workgroup: the body of k_fdem_sens, also
@@ -545,7 +515,7 @@ __device__ __forceinline__ void sens_body(const gbp::MathCtx& M, unsigned char* 
                                           const double* __restrict__ pts, int npts_total, int F, int Lmax, int Lalloc, int L,
                                           const double* __restrict__ sig, const double* __restrict__ th, double alt,
                                           double* __restrict__ Jb /* [2F, Lmax] of this sounding */,
-                                          double* __restrict__ pred_row /* [2F] or NULL */, int nw_use, int zero_to, double row_scale = 1.0 GBP_TICK_ARGS,
+                                          double* __restrict__ pred_row /* [2F] or NULL */, int nw_use, int zero_to, double row_scale = 1.0,
                                           int share = 0, int n_shares = 1)
 {   // share / n_shares: this workgroup evaluates the frequencies  wave * n_shares + share,  + nw_use * n_shares, ...  -- a frequency's
     // rows of J and pred depend on nothing but that frequency, so n_shares workgroups split a sounding's evaluation and write the same bits
@@ -560,7 +530,6 @@ __device__ __forceinline__ void sens_body(const gbp::MathCtx& M, unsigned char* 
     double* sh_t2 = reinterpret_cast<double*>(sh_dyn + (size_t)nwaves * Lalloc * (GBP_SENS_STRIDE * sizeof(cplx) + sizeof(gbp::LayerK)));
     for (int k = threadIdx.x; k < L - 1; k += blockDim.x) sh_t2[k] = -2.0 * th[k];
     __syncthreads();
-    GBP_TICK(3);
     if (wave >= nwaves) return;
 
     for (int f = wave * n_shares + share; f < F; f += nwaves * n_shares) {
@@ -631,7 +600,6 @@ __device__ __forceinline__ void sens_body(const gbp::MathCtx& M, unsigned char* 
             Jb[(size_t)(F + f) * Lmax + m] = 0.0;
         }
     }
-    GBP_TICK(4);
 }
 
 template <bool EXACT, int NG>

@@ -1,15 +1,16 @@
 // Device-resident rjMCMC step (include/geobipy_amd.h, section "Device-resident rjMCMC step").
 // Included at the end of gbp_fdem.hip (same translation unit: shares fail() / GBP_HIP and the kernel launchers).
 //
-// Three kernels hold the host logic of one iteration of the reference's Inference1D.accept_reject
+// Three stages hold the host logic of one iteration of the reference's Inference1D.accept_reject
 // (inversion/Inference1D.py:537-631); between them the forward / Jacobian kernels above are entered with
 // per-chain layer counts of 0 for the chains that do not need them (a workgroup whose sounding has 0 layers exits).
 //   k_rj_propose  one wave (small blocks) or one thread (large blocks) per chain: structural move, value remapping,
 //                 error proposals
-//   k_rj_newton   one wave per chain:  Gauss-Newton precision, its Cholesky factor in LDS, mean and sample
-//   k_rj_accept   one wave per chain:  priors, reversible-jump proposal ratio, Metropolis test, state update, posteriors
-//   k_rj_newton8 / k_rj_accept8: the same for models of <= 8 layers, 8 lanes per chain; their launch may carry the deeper chains'
-//                 workgroups too (one launch per stage, one_stage_launch)
+//   k_rj_newton8  Gauss-Newton precision, its Cholesky factor, mean and sample
+//   k_rj_accept8  priors, reversible-jump proposal ratio, Metropolis test, state update, posteriors
+//   k_rj_step8    k_rj_accept8 of one iteration and the proposal of the next (from the second iteration of a call)
+// Each of the last three is ONE launch per stage: 8 lanes per chain for models of <= 8 layers (newton8_body, accept8_body), then
+// workgroups that scan 64 chains each and run one wave per deeper chain (newton_body, accept_body; for_deep_chains).
 #pragma once
 
 // Register budget of the two per-chain physics kernels (k_rj_physics, k_rj_persistent): they are launched with at most 4 waves
@@ -24,25 +25,17 @@
 // in the Jacobian pass of models above 8 layers; since round 5 that pass sums two row groups per evaluation instead of eight and the
 // kernel has 118 VGPRs, none spilled, no scratch -- GBP_RJ_DEEP_NG below; the table is the measurement that chose four waves).  The persistent kernel is a latency chain per workgroup with at most 4 workgroups of 2 waves resident per
 // CU (LDS): it never uses more than 2 waves per SIMD, so the whole register file is free -- no spills, +13 %.
-#ifndef GBP_RJ_PHYSICS_WAVES_PER_EU
 #define GBP_RJ_PHYSICS_WAVES_PER_EU 4
-#endif
 // Layers of a model whose Jacobian working set (one complex per lane and layer) the lock-step physics kernel keeps in LDS; deeper models
 // work in their chain's global block (sens_body's deep variant: same sums, same bits).  8: 16.6 KB per two-wave workgroup, eight
 // workgroups per CU; 6: 12.5 KB, ten per CU -- what a fifth wave per SIMD (GBP_RJ_PHYSICS_WAVES_PER_EU 5) needs.
-#ifndef GBP_RJ_PHYSICS_LDS_LAYERS
 #define GBP_RJ_PHYSICS_LDS_LAYERS 8
-#endif
-#ifndef GBP_RJ_PERSISTENT_WAVES_PER_EU
 #define GBP_RJ_PERSISTENT_WAVES_PER_EU 2
-#endif
 #include <exception>
 #include <string>
 #include <thread>
 
-#ifndef GBP_RJ_PHYSICS_MAX_WAVES
 #define GBP_RJ_PHYSICS_MAX_WAVES 4
-#endif
 #define GBP_RJ_PHYSICS_BOUNDS __launch_bounds__(64 * GBP_RJ_PHYSICS_MAX_WAVES) __attribute__((amdgpu_waves_per_eu(GBP_RJ_PHYSICS_WAVES_PER_EU, GBP_RJ_PHYSICS_WAVES_PER_EU)))
 #define GBP_RJ_PERSISTENT_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GBP_RJ_PERSISTENT_WAVES_PER_EU, GBP_RJ_PERSISTENT_WAVES_PER_EU)))
 
@@ -129,93 +122,46 @@ __device__ __forceinline__ void wave_sync()
 // Same-box A/B (scripts/ab_rj.py): 8 192 chains 45.6 -> 46.8 M chain-it/s, 4 096: 32.8 -> 33.3; the persistent kernel raises its serial
 // stages (wave 0 of a chain) the same way: 1 024 chains 19.2 -> 19.6 M, 512: + 4.5 %.  (A priority by model depth for the persistent
 // kernel's physics waves -- the launch ends with its slowest chain -- measured nothing.)
-#ifndef GBP_RJ_LATENCY_PRIO
 #define GBP_RJ_LATENCY_PRIO 3
-#endif
-#ifndef GBP_RJ_SHARES_UP_TO
 #define GBP_RJ_SHARES_UP_TO 700
-#endif
 // Round 6: the physics launches take their chains deepest model first (k_rj_order_by_layers, once per call and sub-block): a launch lasts as
 // long as its slowest workgroup, a workgroup's life grows with its chain's layer count (19.6 us + 3.6 us per layer for a Jacobian pass at
 // 8 192 chains), and layer counts change by one per accepted birth / death -- the order of the call's first iteration stays a good one.
-// Which workgroup evaluates which chain changes no bit.  GBP_RJ_SPLIT_DEEP = n > 0: the deepest 1 / n of a launch's chains also get
-// a second workgroup, which takes half of the frequencies of a Jacobian pass of 4 or more layers (share / n_shares of sens_body).
-#ifndef GBP_RJ_ORDERED_PHYSICS
-#define GBP_RJ_ORDERED_PHYSICS 1
-#endif
-#ifndef GBP_RJ_REORDER_EVERY
+// Which workgroup evaluates which chain changes no bit.
 #define GBP_RJ_REORDER_EVERY 256     // iterations between two sorts of a call
-#endif
-#ifndef GBP_RJ_SPLIT_DEEP
-#define GBP_RJ_SPLIT_DEEP 0
-#endif
-#ifndef GBP_RJ_SPLIT_MIN_LAYERS
-#define GBP_RJ_SPLIT_MIN_LAYERS 4
-#endif
 // Row groups (of 8 layers) the Jacobian pass of a model of MORE than 8 layers sums per evaluation (sens_body<EXACT, NG>; the pass is
 // repeated for the next 8 NG layers).  8 -- one evaluation for any model -- keeps 16 complex accumulators and costs the physics kernel 25
 // spilled registers and 104 B of scratch; 2 covers 16 layers per evaluation (two evaluations for 17 - 32 layers) with none: 118 VGPRs,
 // 0 B.  The rows are the same sums in the same order whatever the grouping: same bits (tests/test_rjmcmc_gpu.py, the deep cases).
-#ifndef GBP_RJ_DEEP_NG
 #define GBP_RJ_DEEP_NG 2
-#endif
-#ifndef GBP_RJ_PERSISTENT_PRIO
 #define GBP_RJ_PERSISTENT_PRIO 3
-#endif
 
-#define GBP_RJ_SERIAL_PRIO(P) do { if (GBP_RJ_PERSISTENT_PRIO > 0) __builtin_amdgcn_s_setprio(P); } while (0)
-#define GBP_RJ_RAISE_PRIO() do { if (GBP_RJ_LATENCY_PRIO > 0) __builtin_amdgcn_s_setprio(GBP_RJ_LATENCY_PRIO); } while (0)
-// channels whose Jacobian column the packed stages' one-trip variants hold in registers (N <= this: Resolve 12, ten frequencies 20)
-#ifndef GBP_RJ_COLUMN_ROWS
+#define GBP_RJ_SERIAL_PRIO(P) __builtin_amdgcn_s_setprio(P)
+#define GBP_RJ_RAISE_PRIO() __builtin_amdgcn_s_setprio(GBP_RJ_LATENCY_PRIO)
+// channels whose Jacobian column the packed accept stage's one-trip path holds in registers (N <= this: Resolve 12, ten frequencies 20)
 #define GBP_RJ_COLUMN_ROWS 24
-#endif
-// The one-trip variants of the packed Newton / accept stages (everything requested in one batch behind the move, logarithms and the
-// generator inlined, interface widths from the group's registers, counters as atomic adds).  Round 6: the ACCEPT variant is ON -- with its
-// Cholesky / Jacobian-column requests issued by the groups whose move needs them instead of by every group of a wave, 8 192 chains 52.4 ->
-// 53.5 M chain-it/s, 4 096: 38.0 -> 39.0, 2 048: 24.3 -> 25.1, HBM traffic 157 -> 142 MB per iteration (docs/notes_r6.md); the Newton variant
-// on top adds nothing (25.0 / 38.7 / 52.9) and stays off.  Round 5's measurement, when both were measurement variants only:
+// The one-trip path of the packed accept stage (everything requested in one batch behind the move, logarithms and the generator
+// inlined, interface widths from the group's registers, counters as atomic adds).  Round 6: with its Cholesky / Jacobian-column requests
+// issued by the groups whose move needs them instead of by every group of a wave, 8 192 chains 52.4 -> 53.5 M chain-it/s, 4 096: 38.0 ->
+// 39.0, 2 048: 24.3 -> 25.1, HBM traffic 157 -> 142 MB per iteration (docs/notes_r6.md); the same for the Newton stage on top added
+// nothing (25.0 / 38.7 / 52.9) and was not kept.  Round 5's measurement, when both were measurement variants only:
 // same-box A/B (scripts/ab_rj.py, M chain-it/s, off | Newton | accept | both): 8 192 chains 44.25 | 44.26 | 44.32 | 44.56, 4 096: 30.62 |
 // 30.53 | 30.38 | 30.31, 2 048: 21.01 | 21.18 | 21.06 | 21.33 -- + 1 % at best -- against + 30 MB of HBM traffic per iteration of 8 192
 // chains (203 vs 173 MB: the batch requests what the plain code skipped) and kernels no shorter under the profiler (Newton 25.5 vs 21 us,
 // accept + proposal 46.9 vs 44.2 us).  docs/notes_r5.md.
-#ifndef GBP_RJ_ONE_TRIP_NEWTON
-#define GBP_RJ_ONE_TRIP_NEWTON 0
-#endif
-#ifndef GBP_RJ_ONE_TRIP_ACCEPT
-#define GBP_RJ_ONE_TRIP_ACCEPT 1
-#endif
 // Round 6: the logarithm and the circular functions of these stages are gbp_math.h's log_pos / sincos_quadrant -- 34 and ~40 VALU issues
 // where the library's log took 98 and its cos / sincos behind Box-Muller 150 - 250 (argument reductions for any double; here the arguments
 // are positive normal numbers and an angle in [0, 2 pi]), ~1 ulp either way.  These calls were 40 % of the instructions of an accept +
-// proposal launch, and the stages are dependency chains of one wave.  GBP_RJ_LIBM_MATH restores the library routines (A/B builds).
-#ifdef GBP_RJ_LIBM_MATH
-__device__ GBP_RJ_CALL double rj_log(double x) { return log(x); }
-#else
+// proposal launch, and the stages are dependency chains of one wave.
 __device__ GBP_RJ_CALL double rj_log(double x) { return gbp::log_pos(x); }
-#endif
 __device__ GBP_RJ_CALL double rj_exp(double x) { return exp(x); }
-// (the one-trip stages inline their logarithms -- a call would wait for the loads in flight: the same routine, the same bits)
-#ifdef GBP_RJ_LIBM_MATH
-__device__ __forceinline__ double rj_log_inl(double x) { return log(x); }
-#else
+// (the one-trip path inlines its logarithms -- a call would wait for the loads in flight: the same routine, the same bits)
 __device__ __forceinline__ double rj_log_inl(double x) { return gbp::log_pos(x); }
-#endif
 __device__ GBP_RJ_CALL U4 philox_call(uint64_t seed, uint32_t chain, uint32_t iter, uint32_t stream, uint32_t n)
 {
     return philox(seed, chain, iter, stream, n);
 }
 struct Pair { double a, b; };
-#ifdef GBP_RJ_LIBM_MATH
-__device__ GBP_RJ_CALL double box_muller_cos(double u1, double u2) { return sqrt(-2.0 * log(1.0 - u1)) * cos(TWO_PI * u2); }
-__device__ GBP_RJ_CALL Pair box_muller_pair(double u1, double u2)     // (returned in registers: two output pointers of a call are two objects in scratch)
-{
-    const double rad = sqrt(-2.0 * log(1.0 - u1)), ang = TWO_PI * u2;
-    Pair z;
-    z.a = rad * cos(ang); z.b = rad * sin(ang);
-    return z;
-}
-__device__ __forceinline__ Pair box_muller_pair_inl(double u1, double u2) { return box_muller_pair(u1, u2); }
-#else
 __device__ __forceinline__ Pair box_muller_pair_inl(double u1, double u2)
 {
     const double rad = sqrt(-2.0 * gbp::log_pos(1.0 - u1)), ang = TWO_PI * u2;       // (the angle rounded as the host emulation rounds it)
@@ -230,7 +176,6 @@ __device__ GBP_RJ_CALL Pair box_muller_pair(double u1, double u2)     // (return
     return box_muller_pair_inl(u1, u2);
 }
 __device__ __forceinline__ double box_muller_cos(double u1, double u2) { return box_muller_pair(u1, u2).a; }
-#endif
 
 struct Rng {                                                    // sequential draws of one (chain, iteration, stream)
     uint64_t seed; uint32_t chain, iter, stream, n; double buf; bool have;
@@ -659,12 +604,6 @@ __global__ __launch_bounds__(GBP_RJ_PROPOSE_THREADS) void k_rj_propose_staged(Rj
     }
     __syncthreads();
     if (t < nb) propose_rows<false>(o, c, iter, b0 + t, se + t * KS, ss + t * KS, se + t * KS, ss + t * KS, st + t * KS);
-#ifdef GBP_RJ_PROPOSE_DELAY_TICKS
-    {   // (sensitivity builds only: is an iteration bound by the dependency chain of a sub-block or by the throughput of the physics launches?)
-        const long long d0 = (long long)wall_clock64();
-        while ((long long)wall_clock64() - d0 < GBP_RJ_PROPOSE_DELAY_TICKS) {}
-    }
-#endif
     __syncthreads();
     for (int p = t; p < n_pair; p += GBP_RJ_PROPOSE_THREADS) {
         const int i0 = 2 * p, r0 = i0 / K, c0 = i0 - r0 * K;
@@ -965,14 +904,6 @@ __device__ __forceinline__ void for_deep_chains(int group, bool mine, Body body)
     }
 }
 
-__global__ __launch_bounds__(64) void k_rj_newton(RjOpt o, gbp_rj_chains c, uint32_t iter, int min_k)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
-    const int b = (int)blockIdx.x * 64 + (int)threadIdx.x;
-    for_deep_chains(blockIdx.x, b < c.B && c.k_r[min(b, c.B - 1)] > min_k,
-                    [&](int bb) { newton_body(o, c, iter, min_k, bb, threadIdx.x, sh_dyn); });
-}
-
 // The same for chains with at most 8 layers -- the common case -- packed 8 lanes per chain, 8 chains per wave: row i of the
 // 8 x 8 system lives in the registers of lane i of the chain's group, columns of the Cholesky factor are passed around with
 // cross-lane reads (lane j also keeps column j for the transposed solves), so there is no LDS traffic and no barrier in
@@ -1045,7 +976,7 @@ __device__ __forceinline__ void newton8_core(const RjOpt& o, const gbp_rj_chains
     const int slot = lane >> 3, i = lane & 7, base = lane & ~7;
     const int K = o.max_layers, N = o.n_channels;
     int k = b < c.B ? c.k_r[b] : 0;
-    const bool live = k >= 1 && k <= 8;              // deeper chains: k_rj_newton.  No early exit: idle groups still take
+    const bool live = k >= 1 && k <= 8;              // deeper chains: newton_body.  No early exit: idle groups still take
     if (!live) k = 0;                                //   part in the cross-lane reads
     const size_t bb = b < c.B ? (size_t)b : (size_t)b_idle;   // idle groups read a valid row (never used); not a function of k:
     const bool changed = c.action[bb] != NONE;                 //   the loads below do not wait for the one above
@@ -1054,65 +985,14 @@ __device__ __forceinline__ void newton8_core(const RjOpt& o, const gbp_rj_chains
     const double* e = c.edges_r + bb * K;
     double* P = reinterpret_cast<double*>(sh_dyn) + (size_t)slot * 2 * N;
     double* PR = P + N;
-    // Round 5: an iteration is the dependency chain of a sub-block's launches (docs/notes_r5.md), and this stage's 21 us were dependent
-    // trips to memory -- data and prediction, then the interface row walked through pointers, then sigma, then the Jacobian column in
-    // three batches -- with a library call (which waits for every outstanding load) between them.  ONE_TRIP (the lock-step launches, up to
-    // GBP_RJ_COLUMN_ROWS channels): everything is requested in one batch behind the move, the normal draws are formed while it is in
-    // flight (inlined: a call would wait for the loads first), the widths come from the group's registers.  Same arithmetic, same order.
-    constexpr int NJ = GBP_RJ_COLUMN_ROWS;
-    const bool one_trip = TRIPS && GBP_RJ_ONE_TRIP_NEWTON && N <= NJ;          // (wave-uniform)
-    double t2 = 0.0, lmp, ls = 0.0, z0 = 0.0, z1 = 0.0;
-    double Jc[TRIPS ? NJ : 1];
-    if (one_trip) {
-        const int ic = i < K ? i : 0;
-        const Levels lev = load_levels(o, c.rel, c.add, bb);
-        const double* data = c.data + bb * N;
-        double d_[3], p_[3], as_[3];
-        int rg_[3], ag_[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int n = min(i + 8 * u, N - 1);
-            d_[u] = data[n]; p_[u] = pred[n];
-            rg_[u] = c.rel_group != nullptr ? c.rel_group[n] : 0;
-            ag_[u] = c.add_group != nullptr ? c.add_group[n] : 0;
-            as_[u] = c.add_scale != nullptr ? c.add_scale[n] : 1.0;
-        }
-        const double e_i = e[ic];
-        const double sr_i = c.sigma_r[bb * K + ic];
-        lmp = c.log_mean_prior[bb];
-#pragma unroll
-        for (int n = 0; n < NJ; ++n) Jc[n] = J[(size_t)min(n, N - 1) * K + ic];
-        if (i < 4) {                                                          // (normal_pair, inlined: the same routines, the same bits)
-            const U4 r = philox(o.seed, chain_key(o, c, b), iter, 1, (uint32_t)i);
-            const double u1 = u53(r.x, r.y), u2 = u53(r.z, r.w);
-            const Pair z = box_muller_pair_inl(u1, u2);
-            z0 = z.a; z1 = z.b;
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {                                         // data_weights8, channels i, i + 8, i + 16
-            const int n = i + 8 * u;
-            if (n < N) {
-                const double rd = pick4(lev.rel, rg_[u]) * d_[u];
-                double an = pick4(lev.add, ag_[u]);
-                if (c.add_scale != nullptr) an *= as_[u];
-                const double var = rd * rd + an * an;
-                const bool act = d_[u] > 0.0;
-                const double w = act ? 1.0 / var : 0.0;
-                P[n] = w;
-                PR[n] = act ? w * (p_[u] - d_[u]) : 0.0;
-            }
-        }
-        t2 = prior_t2_group(o, e_i, k, i, base);
-        ls = i < k ? rj_log_inl(sr_i) : 0.0;
-    } else {
-        data_weights8<TRIPS>(c, c.data + bb * N, pred, load_levels(o, c.rel, c.add, bb), N, i, P, PR);
-        if (i < k - 1 && o.solve_gradient) {
-            const double c2c = 0.5 * (width_x(e, k, i) + width_x(e, k, i + 1)) * (double)(k - 1);
-            t2 = o.gradient_precision / (c2c * c2c);
-        }
-        lmp = c.log_mean_prior[bb];
-        ls = i < k ? rj_log(c.sigma_r[bb * K + i]) : 0.0;
+    data_weights8<TRIPS>(c, c.data + bb * N, pred, load_levels(o, c.rel, c.add, bb), N, i, P, PR);
+    double t2 = 0.0;
+    if (i < k - 1 && o.solve_gradient) {
+        const double c2c = 0.5 * (width_x(e, k, i) + width_x(e, k, i + 1)) * (double)(k - 1);
+        t2 = o.gradient_precision / (c2c * c2c);
     }
+    const double lmp = c.log_mean_prior[bb];
+    const double ls = i < k ? rj_log(c.sigma_r[bb * K + i]) : 0.0;
     // (cross-lane reads are issued by all lanes -- a lane that sits out of the instruction cannot be read from)
     const double t2_sh = lane_up(t2);
     const double t2_up = i > 0 ? t2_sh : 0.0;
@@ -1130,14 +1010,7 @@ __device__ __forceinline__ void newton8_core(const RjOpt& o, const gbp_rj_chains
 #pragma unroll
         for (int j = 0; j < KM; ++j) arow[j] += jp * group_bcast(Ji, base, j);
     };
-    if (one_trip) {
-        const bool on = i < k && i < K;
-#pragma unroll
-        for (int n = 0; n < NJ; ++n)
-            if (n < N) jtpj(n, on ? Jc[n] : 0.0);                              // (wave-uniform bound)
-    } else {
-        for_column<TRIPS>(J, K, N, i, i < k && i < K, jtpj);
-    }
+    for_column<TRIPS>(J, K, N, i, i < k && i < K, jtpj);
     {   // + Wm'Wm (tridiagonal), Wm'Wm (ln sigma - ln sigma_ref)
         const double single = o.value_precision + (o.solve_gradient ? o.gradient_precision : 0.0);
         const double diag = k == 1 ? single : o.value_precision + t2_up + t2;
@@ -1187,13 +1060,14 @@ __device__ __forceinline__ void newton8_core(const RjOpt& o, const gbp_rj_chains
         return x;
     };
     const double step = backward(forward(g));        // (C C')^-1 g
-    if (!one_trip && i < 4) normal_pair(o.seed, chain_key(o, c, b), iter, 1, (uint32_t)i, z0, z1);
+    double z0 = 0.0, z1 = 0.0;
+    if (i < 4) normal_pair(o.seed, chain_key(o, c, b), iter, 1, (uint32_t)i, z0, z1);
     const double za = __shfl(z0, base + (i >> 1), 64), zb = __shfl(z1, base + (i >> 1), 64);
     const double w = backward((i & 1) ? zb : za);    // C^-T z
     if (live && i < K) {                             // (max_layers may be smaller than the group)
         const double lp = i < k ? (ls - o.alpha * step) + w : 0.0;
         c.log_prop[bb * K + i] = lp;
-        c.sigma_p[bb * K + i] = i < k ? (one_trip ? exp(lp) : rj_exp(lp)) : 1.0;
+        c.sigma_p[bb * K + i] = i < k ? rj_exp(lp) : 1.0;
         for (int j = i + 8; j < K; j += 8) { c.log_prop[bb * K + j] = 0.0; c.sigma_p[bb * K + j] = 1.0; }
     }
 }
@@ -1212,21 +1086,19 @@ __device__ __forceinline__ void newton8_body(const RjOpt& o, const gbp_rj_chains
     else newton8_core<2, TRIPS>(o, c, iter, lane, b, sh_dyn, b_idle);
 }
 
-// The stage's workgroups: 0 .. n_packed - 1 hold eight chains of at most 8 layers each, workgroup n_packed + b is chain b's own wave
-// if the chain is deeper (it exits at once otherwise).  A launch holds both kinds or the packed ones only (the deep chains then get
-// k_rj_newton: a launch of workgroups that mostly exit at once is faster with that kernel's 69 VGPRs than with the 125 of this one).
-// Which of the two owns a chain follows from what neither of them writes (k_r and the move), so they need no order between them.
-template <bool TRIPS>
+// The stage's workgroups: 0 .. n_packed - 1 hold eight chains of at most 8 layers each; the ones after them, if any, scan 64 chains each
+// for the deeper ones (for_deep_chains).  Which of the two owns a chain follows from what neither of them writes (k_r and the move), so
+// they need no order between them.
 __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_newton8(RjOpt o, gbp_rj_chains c, uint32_t iter, int n_packed)
 {
     GBP_RJ_RAISE_PRIO();
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
-    if ((int)blockIdx.x >= n_packed) {                 // (the deep chains' scanning workgroups: see k_rj_newton)
+    if ((int)blockIdx.x >= n_packed) {                 // (the deep chains' scanning workgroups)
         const int g = (int)blockIdx.x - n_packed, b = g * 64 + (int)threadIdx.x;
         for_deep_chains(g, b < c.B && c.k_r[min(b, c.B - 1)] > 8, [&](int bb) { newton_body(o, c, iter, 8, bb, threadIdx.x, sh_dyn); });
         return;
     }
-    newton8_body<TRIPS>(o, c, iter, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
+    newton8_body<true>(o, c, iter, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
 }
 
 __device__ inline double log_uniform_prior(double x, double llo, double lhi, double nlog_span)
@@ -1570,13 +1442,6 @@ __device__ __forceinline__ bool accept_is_deep(const gbp_rj_chains& c, int b, in
     return max(k, k - (action == INSERT) + (action == DELETE)) > min_k;
 }
 
-__global__ __launch_bounds__(64) void k_rj_accept(RjOpt o, gbp_rj_chains c, uint32_t iter, int accumulate, int min_k)
-{   // (scanning workgroups: see k_rj_newton)
-    extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
-    for_deep_chains(blockIdx.x, accept_is_deep(c, (int)blockIdx.x * 64 + (int)threadIdx.x, min_k),
-                    [&](int bb) { accept_body(o, c, iter, accumulate, min_k, bb, threadIdx.x, sh_dyn); });
-}
-
 // The same for chains whose current and proposed models have at most 8 layers, packed 8 lanes per chain like k_rj_newton8:
 // the reverse-move algebra runs on the Cholesky factor held in registers (row i and column i on lane i), sums over a
 // chain are 8-lane butterflies, state copies and posterior updates are strided by 8.
@@ -1738,7 +1603,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
     // flight) between them.  Everything the decision, the state update, the posteriors and the proposal that follows can need is requested
     // HERE in one batch, logarithms and the generator are inlined, counters are atomic adds nobody waits for.  Same arithmetic, same order.
     constexpr int NJ = GBP_RJ_COLUMN_ROWS;
-    const bool one_trip = TRIPS && GBP_RJ_ONE_TRIP_ACCEPT && N <= NJ;          // (wave-uniform)
+    const bool one_trip = TRIPS && N <= NJ;                                    // (wave-uniform)
     Acc8Pre pre;
     pre.on = one_trip;
     Levels lev_p1;
@@ -1767,11 +1632,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
         for (int j = 0; j < 8; ++j) { pre.cr[j] = 0.0; pre.cc[j] = 0.0; }
 #pragma unroll
         for (int n = 0; n < NJ; ++n) pre.Jc[n] = 0.0;
-#ifdef GBP_RJ_WAVE_PRELOAD
-        if (__ballot(jump) != 0ull) {
-#else
         if (jump) {
-#endif
             const double* C = c.chol + bb * K * K;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -1780,11 +1641,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
                 pre.cc[j] = C[(size_t)jc * K + ic1];
             }
         }
-#ifdef GBP_RJ_WAVE_PRELOAD
-        if (__ballot(action != NONE) != 0ull) {
-#else
         if (action != NONE) {
-#endif
             const double* Js = (action == PERTURB ? c.J_r : c.J_p) + bb * N * K;
 #pragma unroll
             for (int n = 0; n < NJ; ++n) pre.Jc[n] = Js[(size_t)min(n, N - 1) * K + ic1];
@@ -1951,7 +1808,6 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
     if (i == 0 && c.step_flags != nullptr) c.step_flags[bb] = (accept ? 1 : 0) | (bk & 15);
 }
 
-template <bool TRIPS>
 __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_accept8(RjOpt o, gbp_rj_chains c, uint32_t iter, int accumulate, int n_packed)
 {   // (workgroups as in k_rj_newton8)
     GBP_RJ_RAISE_PRIO();
@@ -1961,7 +1817,7 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_accept8(RjOpt o
         for_deep_chains(g, accept_is_deep(c, g * 64 + (int)threadIdx.x, 8), [&](int bb) { accept_body(o, c, iter, accumulate, 8, bb, threadIdx.x, sh_dyn); });
         return;
     }
-    accept8_body<TRIPS>(o, c, iter, accumulate, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
+    accept8_body<true>(o, c, iter, accumulate, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1976,7 +1832,6 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_accept8(RjOpt o
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t step_is_deep(int k_now, int kr) { return max(k_now, kr) > 8 ? 1 : 0; }
 
-template <bool TRIPS>
 __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_step8(RjOpt o, gbp_rj_chains c, uint32_t iter, int accumulate, int n_packed,
                                                  const int32_t* __restrict__ deep_cur, int32_t* __restrict__ deep_next)
 {
@@ -2008,7 +1863,7 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_step8(RjOpt o, 
     const bool frozen = o.schedule == 1 && c.status[bq] != 0;
     // (a chain flagged deep belongs to a scanning workgroup of this launch, which rewrites k_r and the move for iteration + 1 while
     //  this group may still be reading them: a group acts on its chain only when deep_cur says so -- idle groups get chain index c.B)
-    accept8_body<TRIPS>(o, c, iter, accumulate, lane, mine ? b : c.B, sh_dyn, 0, &st);
+    accept8_body<true>(o, c, iter, accumulate, lane, mine ? b : c.B, sh_dyn, 0, &st);
     if (frozen) { st.accepted = false; st.k_now = k_before; }
     wave_sync();
     if (mine) {                                        // (group-uniform; the reads inside stay within the chain's own 8 lanes)
@@ -2028,7 +1883,7 @@ __global__ __launch_bounds__(256) void k_rj_propose_flags(gbp_rj_chains c, int32
 }
 
 // The chains of a launch by descending layer count (counting sort, one workgroup; ties in any order -- which workgroup evaluates which
-// chain changes no bit): the order in which k_rj_physics takes them (GBP_RJ_ORDERED_PHYSICS)
+// chain changes no bit): the order in which k_rj_physics takes them
 __global__ __launch_bounds__(1024) void k_rj_order_by_layers(gbp_rj_chains c, int32_t* __restrict__ order)
 {
     __shared__ int cnt[64], pos[64];
@@ -2359,15 +2214,7 @@ __global__ __launch_bounds__(64) void k_td_loglike(RjOpt o, gbp_rj_chains c, con
 // The stages are separate (non-inlined) functions so that each gets its own register allocation: inlined into one body the
 // kernel needed 300 VGPRs and > 500 SGPR spills (occupancy 1).  They receive pointers only -- the two parameter blocks and the
 // math tables sit in LDS for the workgroup's lifetime, the polynomial coefficients are re-read from constant memory.
-#ifndef GBP_STAGE_ATTR
 #define GBP_STAGE_ATTR __attribute__((noinline))
-#endif
-#ifndef GBP_PHYS_STAGE_ATTR
-#define GBP_PHYS_STAGE_ATTR GBP_STAGE_ATTR
-#endif
-#ifndef GBP_ACCEPT_STAGE_ATTR
-#define GBP_ACCEPT_STAGE_ATTR GBP_STAGE_ATTR
-#endif
 struct PersistentCtx {
     const RjOpt* o;          // LDS copies
     const gbp_rj_chains* c;
@@ -2407,7 +2254,7 @@ __device__ __forceinline__ gbp::MathCtx math_ctx(MathLds* lds)    // math_setup 
 }
 
 template <bool EXACT>
-__device__ GBP_PHYS_STAGE_ATTR void stage_fm_dlogc(const PersistentCtx* x, int at_proposal)
+__device__ GBP_STAGE_ATTR void stage_fm_dlogc(const PersistentCtx* x, int at_proposal)
 {
     const RjOpt& o = *x->o;
     const gbp_rj_chains& c = *x->c;
@@ -2427,7 +2274,7 @@ __device__ GBP_PHYS_STAGE_ATTR void stage_fm_dlogc(const PersistentCtx* x, int a
                              sig, th, alt, Jb, pr, x->nw_deep, min(K, (L + 7) & ~7));
 }
 
-__device__ GBP_PHYS_STAGE_ATTR void stage_forward(const PersistentCtx* x)
+__device__ GBP_STAGE_ATTR void stage_forward(const PersistentCtx* x)
 {
     const RjOpt& o = *x->o;
     const gbp_rj_chains& c = *x->c;
@@ -2452,7 +2299,7 @@ __device__ GBP_STAGE_ATTR void stage_newton(const PersistentCtx* x, uint32_t ite
     else newton_body(*x->o, c, iter, 8, x->b, lane, x->sh_dyn);
 }
 
-__device__ GBP_ACCEPT_STAGE_ATTR void stage_accept(const PersistentCtx* x, uint32_t iter, int accumulate, int lane)
+__device__ GBP_STAGE_ATTR void stage_accept(const PersistentCtx* x, uint32_t iter, int accumulate, int lane)
 {
     const gbp_rj_chains& c = *x->c;
     const int kr = c.k_r[x->b], kp = c.k[x->b];
@@ -2640,7 +2487,7 @@ __global__ GBP_RJ_PHYSICS_BOUNDS void k_rj_physics(RjOpt o, gbp_rj_chains c, con
                                                     int stage, unsigned char* deep_scratch, size_t deep_bytes,
                                                     const BinDesc* __restrict__ bins, int bin0, int n_bins,
                                                     const Channel* __restrict__ bin_chan, const double* __restrict__ bin_pts, int out_offset,
-                                                    const int32_t* __restrict__ order, int n_split)
+                                                    const int32_t* __restrict__ order)
 {
     // The output row lives behind the stages' working set in the dynamic block (out_offset) instead of a static 2 * GBP_MAX_FREQ doubles:
     // with two waves per chain the workgroup's LDS was 20 544 B -- 64 B more than an eighth of a CU's 160 KB -- i.e. seven resident
@@ -2648,42 +2495,23 @@ __global__ GBP_RJ_PHYSICS_BOUNDS void k_rj_physics(RjOpt o, gbp_rj_chains c, con
     __shared__ MathLds sh_math;
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
     double* sh_out = reinterpret_cast<double*>(sh_dyn + out_offset);
-    // Workgroups B ... 2 B - 1 (launched when the Jacobian passes are split, GBP_RJ_JACOBIAN_SHARES = 2) are the second halves of the
+    // Workgroups B ... 2 B - 1 (launched when the Jacobian passes are split, jacobian_shares() == 2) are the second halves of the
     // chains' Jacobian evaluations: a launch lasts as long as its slowest workgroup, the Jacobian workgroups are the slow ones, and a
     // frequency's rows depend on nothing else -- two workgroups take five frequencies each and write the bits one would.
-    // `order` (round 6): workgroup g takes chain order[g] -- the launch's chains by descending layer count at the start of the call;
-    // n_split > 0: the first n_split of them have a second workgroup each (workgroups B ... B + n_split - 1), used by the Jacobian passes
-    // of GBP_RJ_SPLIT_MIN_LAYERS or more layers (both workgroups read the same move and layer count: the same decision)
-    int share = (int)blockIdx.x >= c.B ? 1 : 0;
+    // `order` (round 6): workgroup g takes chain order[g] -- the launch's chains by descending layer count at the start of the call
+    const int share = (int)blockIdx.x >= c.B ? 1 : 0;
     int n_shares = (int)gridDim.x > c.B ? 2 : 1;
     const int slot = (int)blockIdx.x - share * c.B;
     const int b = order != nullptr ? order[slot] : slot;
-    if (n_split > 0 && slot >= n_split) n_shares = 1;
-#ifdef GBP_RJ_PHYS_CLOCK
-    const long long clk_start_ = (long long)wall_clock64();
-    PhysClk clk_{threadIdx.x == 0 && (b & 15) == 0, 0, clk_start_};
-    PhysClk* gbp_clk = &clk_;
-#endif
     // The chain's move, layer count and height are requested together, and the math tables go to LDS while they travel (no barrier of
     // their own: forward_body / sens_body have one behind the layer-thickness fill) -- one trip to memory and one barrier less per workgroup
-#ifndef GBP_RJ_PHYSICS_LATE_TABLES
     const int action = c.action[b];
     const int L_early = c.k_r[b];
     const double alt_early = (stage == 1 && o.solve_height) ? c.height_p[b] : c.height[b];
     const gbp::MathCtx M = math_setup<false>(sh_math);
-#else
-    const int action = c.action[b];
-    const int L_early = c.k_r[b];
-    const double alt_early = (stage == 1 && o.solve_height) ? c.height_p[b] : c.height[b];
-#endif
     if (stage == 0 && action == NONE) return;                     // (workgroup-uniform)
-    if (n_split > 0 && n_shares == 2 && L_early < GBP_RJ_SPLIT_MIN_LAYERS) n_shares = 1;   // (a shallow model: not worth a second prologue)
     if (share != 0 && (n_shares == 1 || (stage == 1 && action != INSERT && action != DELETE) || L_early > GBP_RJ_PHYSICS_LDS_LAYERS)) return;   // (a fused forward, or a deep model: one workgroup)
     if (n_shares == 2 && ((stage == 1 && action != INSERT && action != DELETE) || L_early > GBP_RJ_PHYSICS_LDS_LAYERS)) n_shares = 1;
-#ifdef GBP_RJ_PHYS_CLOCK
-    clk_.base = (stage == 0 ? 0 : ((action == INSERT || action == DELETE) ? 8 : 16));
-#endif
-    GBP_TICK(0);
     const int K = o.max_layers, N = o.n_channels, L = L_early;
     // (a sampled height: the remapped model is evaluated at the chain's current height, the proposal at the proposed one)
     const double alt = alt_early;
@@ -2693,11 +2521,6 @@ __global__ GBP_RJ_PHYSICS_BOUNDS void k_rj_physics(RjOpt o, gbp_rj_chains c, con
         pts = bin_pts + d.pts_off;
         npts_total = d.npts_total;
     }
-    GBP_TICK(1);
-#ifdef GBP_RJ_PHYSICS_LATE_TABLES
-    const gbp::MathCtx M = math_setup(sh_math);                   // ends with __syncthreads()
-#endif
-    GBP_TICK(2);
     const bool jump = action == INSERT || action == DELETE;
     const int nw = (int)(blockDim.x >> 6);
     if (stage == 0 || jump) {
@@ -2706,23 +2529,14 @@ __global__ GBP_RJ_PHYSICS_BOUNDS void k_rj_physics(RjOpt o, gbp_rj_chains c, con
         double* Jb = (at_proposal ? c.J_p : c.J_r) + (size_t)b * N * K;
         double* pr = (at_proposal ? c.pred_p : c.pred_r) + (size_t)b * N;
         const double* th = c.thk_r + (size_t)b * K;
-        if (L <= GBP_RJ_PHYSICS_LDS_LAYERS) sens_body<EXACT, 1>(M, sh_dyn, chan, pts, npts_total, F, K, K < GBP_RJ_PHYSICS_LDS_LAYERS ? K : GBP_RJ_PHYSICS_LDS_LAYERS, L, sig, th, alt, Jb, pr, nw, min(K, 8), 1.0 GBP_TICK_PASS, share, n_shares);
+        if (L <= GBP_RJ_PHYSICS_LDS_LAYERS) sens_body<EXACT, 1>(M, sh_dyn, chan, pts, npts_total, F, K, K < GBP_RJ_PHYSICS_LDS_LAYERS ? K : GBP_RJ_PHYSICS_LDS_LAYERS, L, sig, th, alt, Jb, pr, nw, min(K, 8), 1.0, share, n_shares);
         else sens_body<EXACT, GBP_RJ_DEEP_NG>(M, deep_scratch + (size_t)b * deep_bytes, chan, pts, npts_total, F, K, K, L, sig, th, alt, Jb, pr, nw,
                                  min(K, (L + 7) & ~7));
     } else {
         forward_body<true>(M, sh_out, sh_dyn, chan, pts, npts_total, F, K, L, c.sigma_p + (size_t)b * K, c.thk_r + (size_t)b * K, alt,
                            c.data + (size_t)b * N, c.rel_p[b], c.add_p[b], c.pred_p + (size_t)b * N, c.misfit_p + b, c.like_p + b,
-                           sigma_direct, nw, 1.0 GBP_TICK_PASS);
+                           sigma_direct, nw, 1.0);
     }
-#ifdef GBP_RJ_PHYS_CLOCK
-    if (threadIdx.x == 0) {                            // life of every workgroup (thread 0's wave) by kind and layer count
-        const long long life = (long long)wall_clock64() - clk_start_;
-        long long* h = GBP_PHYS_LIFE + ((stage == 0 ? 0 : (jump ? 1 : 2)) * 16 + min(L, 15)) * 3;
-        atomicAdd((unsigned long long*)&h[0], (unsigned long long)life);
-        atomicAdd((unsigned long long*)&h[1], 1ull);
-        atomicMax((unsigned long long*)&h[2], (unsigned long long)life);
-    }
-#endif
 }
 
 }  // namespace rj
@@ -2737,10 +2551,7 @@ namespace {
 // creating its own (a process that had run the sub-block driver before the time-domain one lost 13 % in the latter: its side and
 // deep streams landed on the queues of the four sub-block streams created earlier).
 struct AuxStreams {
-#ifndef GBP_AUX_STREAMS
-#define GBP_AUX_STREAMS 3
-#endif
-    static const int N = GBP_AUX_STREAMS;
+    static const int N = 3;
     hipStream_t q[N] = {};
     hipEvent_t fork[N] = {}, join[N] = {};
     hipEvent_t start = nullptr;
@@ -2905,92 +2716,43 @@ gbp_status gbp_rj_debug_propose_variant(const gbp_rj_options* o, const gbp_rj_ch
 // 56.1 / 56.2; the persistent kernel with the batched build 17.9 -> 17.2 | 20.1 -> 19.7.  (At 8 192 chains and beyond the iteration
 // is bound by the physics launches of the three sub-blocks, which fill the GPU: shorter per-chain stages change little there.  Atomic
 // adds -- sent and forgotten -- instead of `+=` in the hit map and the counters were measured with it: no difference.)
-static bool packed_trips(int B)
-{
-    (void)B;
-#ifdef GBP_RJ_AB_TRIPS
-    return GBP_RJ_AB_TRIPS != 0;                     // (A/B builds under scripts/ab only)
-#endif
-    return true;
-}
-
-// The launches of a per-chain stage: ONE (packed workgroups, then a wave per chain for the models above 8 layers) or TWO (packed;
-// deep -- mostly workgroups that exit at once).  Measured (scripts/bench_rj_parts.py / bench_tdem_sampler.py, A/B builds interleaved
-// on one box, M chain-iterations/s two / one): the time-domain driver, 14 launches per iteration with a fork and a join around the
-// deep Newton launch, 3.35 / 3.70 at 1 024 chains and 11.2 / 11.8 at 8 192; frequency-domain sub-blocks (chains per launch =
+//
+// The launch of a per-chain stage: the packed workgroups, then B / 64 workgroups that scan for the models above 8 layers
+// (for_deep_chains).  Before the scanning workgroups the deep part was a wave per chain, and two launches per stage (packed; deep --
+// mostly workgroups that exit at once) were measured against one (scripts/bench_rj_parts.py / bench_tdem_sampler.py, A/B builds
+// interleaved on one box, M chain-iterations/s two / one): the time-domain driver, 14 launches per iteration with a fork and a join
+// around the deep Newton launch, 3.35 / 3.70 at 1 024 chains and 11.2 / 11.8 at 8 192; frequency-domain sub-blocks (chains per launch =
 // block / 3): 2 048 chains 18.7 / 19.1, 4 096: 30.8 / 30.8, 8 192: 43.7 / 42.6, 16 384: 52.2 / 50.4 -- with three sub-blocks in flight
 // two short launches interleave better with the other sub-blocks' physics than one --; one block of 65 536: 56.4 / 57.1.
 // (Folding the deep body into the packed WAVES was tried first: inlined it takes the accept stage from 111 to 178 VGPRs, as a call it
 // adds 1.1 - 1.3 KB of scratch per lane; so was running the deep bodies as calls inside the stage-1 physics launch: 104 -> 288 B of
 // scratch there.)
-// Round 5: the deep chains' part of a stage is B / 64 scanning workgroups (k_rj_newton) instead of B that exit at once, so the one launch
-// no longer drags 2 731 empty workgroups through the packed kernel's register budget: ONE launch per stage at every size -- five launches
-// per iteration and sub-block instead of seven.  A/B on one box (scripts/ab_rj.py, ten frequencies, M chain-iterations/s, two repeats;
-// round-4 library | scanning workgroups with the round-4 rule | scanning + one launch): 2 048 chains 18.99 | 18.94 | 18.92, 4 096:
-// 31.23 | 31.20 | 31.19, 8 192: 44.30 | 43.35 | 44.89.  (GBP_RJ_TWO_STAGE_LAUNCHES restores the round-4 rule for A/B builds.)
-static bool one_stage_launch(int n, bool time_domain)
-{
-#ifdef GBP_RJ_TWO_STAGE_LAUNCHES
-    return time_domain || n <= 1536 || n >= 32768;
-#else
-    (void)n; (void)time_domain;
-    return true;
-#endif
-}
-
-static gbp_status rj_newton_launch(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, bool one, void* stream)
+// Round 5: the scanning workgroups no longer drag 2 731 empty workgroups through the packed kernel's register budget: ONE launch per
+// stage at every size -- five launches per iteration and sub-block instead of seven.  A/B on one box (scripts/ab_rj.py, ten frequencies,
+// M chain-iterations/s, two repeats; round-4 library | scanning workgroups with the round-4 rule | scanning + one launch): 2 048 chains
+// 18.99 | 18.94 | 18.92, 4 096: 31.23 | 31.20 | 31.19, 8 192: 44.30 | 43.35 | 44.89.
+gbp_status gbp_rj_newton(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, void* stream)
 {
     gbp_status st = rj_check(o, c);
     if (st != GBP_OK || c->B == 0) return st;
     const int n_packed = (c->B + 7) / 8, n_deep = o->max_layers > 8 ? (c->B + 63) / 64 : 0;      // (deep: scanning workgroups of 64 chains)
     const size_t lds8 = (size_t)16 * o->n_channels * sizeof(double), lds_deep = rj::Lds::bytes(o->max_layers, o->n_channels);
-    auto launch = [&](int grid, size_t lds, int np) {
-        if (packed_trips(c->B))
-            hipLaunchKernelGGL(rj::k_rj_newton8<true>, dim3(grid), dim3(64), lds, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, np);
-        else
-            hipLaunchKernelGGL(rj::k_rj_newton8<false>, dim3(grid), dim3(64), lds, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, np);
-    };
-    if (one || n_deep == 0) launch(n_packed + n_deep, n_deep ? std::max(lds8, lds_deep) : lds8, n_packed);
-    else {
-        launch(n_packed, lds8, n_packed);
-        hipLaunchKernelGGL(rj::k_rj_newton, dim3(n_deep), dim3(64), lds_deep, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, 8);
-    }
+    hipLaunchKernelGGL(rj::k_rj_newton8, dim3(n_packed + n_deep), dim3(64), n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream,
+                       rj::extend(*o), *c, (uint32_t)iteration, n_packed);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
 
-static gbp_status rj_accept_launch(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, int accumulate, bool one, void* stream)
+gbp_status gbp_rj_accept(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, int accumulate, void* stream)
 {
     gbp_status st = rj_check(o, c);
     if (st != GBP_OK || c->B == 0) return st;
     const int n_packed = (c->B + 7) / 8, n_deep = o->max_layers > 8 ? (c->B + 63) / 64 : 0;      // (deep: scanning workgroups of 64 chains)
     const size_t lds8 = (size_t)8 * o->n_channels * sizeof(double), lds_deep = rj::Lds::bytes(o->max_layers, o->n_channels);
-    auto launch = [&](int grid, size_t lds, int np) {
-        if (packed_trips(c->B))
-            hipLaunchKernelGGL(rj::k_rj_accept8<true>, dim3(grid), dim3(64), lds, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration,
-                               accumulate, np);
-        else
-            hipLaunchKernelGGL(rj::k_rj_accept8<false>, dim3(grid), dim3(64), lds, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration,
-                               accumulate, np);
-    };
-    if (one || n_deep == 0) launch(n_packed + n_deep, n_deep ? std::max(lds8, lds_deep) : lds8, n_packed);
-    else {
-        launch(n_packed, lds8, n_packed);
-        hipLaunchKernelGGL(rj::k_rj_accept, dim3(n_deep), dim3(64), lds_deep, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration,
-                           accumulate, 8);
-    }
+    hipLaunchKernelGGL(rj::k_rj_accept8, dim3(n_packed + n_deep), dim3(64), n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream,
+                       rj::extend(*o), *c, (uint32_t)iteration, accumulate, n_packed);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
-}
-
-gbp_status gbp_rj_newton(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, void* stream)
-{
-    return rj_newton_launch(o, c, iteration, one_stage_launch(c ? c->B : 0, false), stream);
-}
-
-gbp_status gbp_rj_accept(const gbp_rj_options* o, const gbp_rj_chains* c, int64_t iteration, int accumulate, void* stream)
-{
-    return rj_accept_launch(o, c, iteration, accumulate, one_stage_launch(c ? c->B : 0, false), stream);
 }
 
 static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_operator* td, const gbp_rj_options* o, const gbp_rj_chains* c,
@@ -3084,18 +2846,6 @@ static gbp_status rj_run_persistent(const gbp_fdem_system* sys, const gbp_rj_opt
     return GBP_OK;
 }
 
-// Waves per workgroup of the stage-0 physics launch (Jacobian pass at the remapped model; results do not depend on it) given the
-// sub-block's wave count `nw` of the stage-1 launch.
-static int stage0_waves(int nw)
-{
-#ifdef GBP_RJ_PHYSICS_NW_STAGE0
-    (void)nw;
-    return GBP_RJ_PHYSICS_NW_STAGE0;                         // (A/B builds under scripts/ab only)
-#else
-    return nw;
-#endif
-}
-
 // Concurrent sub-blocks of the fused lock-step driver by block size.  Each sub-block runs on one of the pool's three helper streams
 // (aux_streams(): as many as map onto hardware queues of their own beside torch's stream; a fourth shares a queue and serialises --
 // the first measurement of four, with the drivers' separate stream sets still in place, lost 30 %).  Measured (reference Jacobian,
@@ -3110,17 +2860,11 @@ static int stage0_waves(int nw)
 // 8 192: 46.0 -> 42.4, 16 384: 51.6 -> 48.9).  Same bits either way (scripts/ab_bits.py).
 static int jacobian_shares(int chains_in_launch)
 {
-#ifdef GBP_RJ_JACOBIAN_SHARES
-    return GBP_RJ_JACOBIAN_SHARES;                           // (A/B builds under scripts/ab only)
-#endif
     return chains_in_launch <= GBP_RJ_SHARES_UP_TO ? 2 : 1;
 }
 
 static int lockstep_parts(int B)
 {
-#ifdef GBP_RJ_LOCKSTEP_PARTS
-    return B >= 2048 ? GBP_RJ_LOCKSTEP_PARTS : 1;              // (A/B builds under scripts/ab only)
-#endif
     return B >= 2048 ? 3 : (B >= 1200 ? 2 : 1);      // (1 600 ... 2 047 chains, two against one: 17.5 vs 15.4, 19.2 vs 15.8, 20.8 vs 17.1 M Resolve; 15.5 vs 13.6 ... 18.3 vs 15.1 M ten frequencies)
 }
 
@@ -3182,25 +2926,6 @@ gbp_status gbp_rj_debug_stage_ticks(int64_t* out, int reset)
     return GBP_OK;
 }
 
-#ifdef GBP_RJ_PHYS_CLOCK
-gbp_status gbp_debug_phys_ticks(int64_t* out, int reset)   // (measurement builds only: not declared in the header)
-{
-    long long h[64];
-    GBP_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(GBP_PHYS_TICKS), sizeof(h)));
-    for (int i = 0; i < 64; ++i) out[i] = (int64_t)h[i];
-    if (reset) { std::memset(h, 0, sizeof(h)); GBP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(GBP_PHYS_TICKS), h, sizeof(h))); }
-    return GBP_OK;
-}
-gbp_status gbp_debug_phys_life(int64_t* out, int reset)    // [3][16][3], see GBP_PHYS_LIFE
-{
-    long long h[144];
-    GBP_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(GBP_PHYS_LIFE), sizeof(h)));
-    for (int i = 0; i < 144; ++i) out[i] = (int64_t)h[i];
-    if (reset) { std::memset(h, 0, sizeof(h)); GBP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(GBP_PHYS_LIFE), h, sizeof(h))); }
-    return GBP_OK;
-}
-#endif
-
 gbp_status gbp_rj_run(const gbp_fdem_system* sys, const gbp_rj_options* o, const gbp_rj_chains* c, int64_t first_iteration,
                       int n_iterations, int accumulate, void* stream)
 {
@@ -3247,13 +2972,10 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
         for (int d = 1; d <= F; ++d)                    // the largest divisor of nF not (much) above the target
             if (F % d == 0 && d <= 16 && (double)d <= 1.15 * want) sw = d;
         // time-domain handles carry 22 ... 75 "frequencies" (spline nodes x basis integrals): at least four waves per chain, whether
-        // or not four divides their number -- measured (scripts/bench_tdem_sampler.py through -DGBP_RJ_SENS_WAVES builds; 22 nodes,
+        // or not four divides their number -- measured (scripts/bench_tdem_sampler.py through A/B builds; 22 nodes,
         // M chain-iterations/s with 2 / 3 / 4 / 6 waves): 4 096 chains 7.0 7.4 7.7 7.4; 8 192: 10.4 10.9 11.1 10.9; 16 384: 13.6 13.9
         // 14.1 12.9; 44 nodes, 8 192 chains: 5.4 - 5.8 5.5
         if (td != nullptr) sw = std::max(sw, std::min(4, F));
-#ifdef GBP_RJ_SENS_WAVES
-        sw = GBP_RJ_SENS_WAVES;                              // (A/B builds under scripts/ab only)
-#endif
     }
     const int fw = o->forward_waves;   // 0: the forward kernels choose from the batch size
     const int N = o->n_channels;
@@ -3333,7 +3055,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
     // (scripts/bench_rj_modes.py, mode 1 vs 3: +17 % at 1 024 chains, +4 % at 8 192, -8 % at 65 536, where the forward chains
     // would run at the Jacobian pass's occupancy).
     if (fused && td == nullptr && (long long)B * sys->t.nF < 196608) {
-        // One physics launch per stage (k_rj_physics): 5 - 7 launches per iteration and sub-block (one_stage_launch).  `parts` > 1: the block is cut into
+        // One physics launch per stage (k_rj_physics): 5 - 7 launches per iteration and sub-block.  `parts` > 1: the block is cut into
         // that many contiguous sub-blocks which advance CONCURRENTLY, each on a stream of its own, launches issued round-robin --
         // the latency-bound per-chain stages of one sub-block (propose / Newton / accept: 23 + 28 + 38 us at 8 192 chains, one
         // wave per SIMD) overlap the physics of another, and a physics launch of a quarter of the chains has a shorter tail.
@@ -3344,7 +3066,6 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
         if (P > 1 && bs == nullptr) return fail(GBP_ERR_HIP, "sub-block streams: %s", hipGetErrorString(hipGetLastError()));
         struct Part { gbp_rj_options o; gbp_rj_chains c; hipStream_t q; unsigned char* deep; int nw; size_t lds; int32_t* flags; int32_t* order; };
         std::vector<Part> part(P);
-        const size_t deep_per_chain = K > 8 ? 1 : 0;
         for (int p = 0; p < P; ++p) {
             const int b0 = (int)((long long)B * p / P), n = (int)((long long)B * (p + 1) / P) - b0;
             Part& t = part[p];
@@ -3356,7 +3077,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             t.flags = nullptr;
             t.order = nullptr;
             // Waves per workgroup of the physics launches (results do not depend on it).  Measured per sub-block size n
-            // (scripts/bench_rj_parts.py through -DGBP_RJ_PHYSICS_NW builds, M chain-iterations/s with 1 / 2 / 3 / 4 waves; ten
+            // (scripts/bench_rj_parts.py through A/B builds, M chain-iterations/s with 1 / 2 / 3 / 4 waves; ten
             // frequencies | Resolve): n = 1 024: 11.9 15.3 16.5 17.1 | 14.6 17.5 18.5 19.6;  2 048: 20.4 25.9 27.0 27.5 | 25.7 30.1 31.0
             // 31.7;  4 096: 31.9 40.6 40.4 38.5 | 41.0 47.0 45.8 45.2;  8 192: 48.7 51.5 48.1 44.9 | 61.2 61.3 56.3 53.1 -- a
             // chain's frequencies spread over four waves while the launch would not fill the SIMDs otherwise (<= 8 192 waves), two
@@ -3367,26 +3088,18 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             // n = 910: 23.4 25.4 25.6;  1 365: 31.3 32.2 30.6;  1 820: 37.3 36.2 33.8;  2 731: 44.1 40.5 38.0 -- with a shorter chain per
             // sub-block the physics launches of the three overlap more, and the switch points move down.
             t.nw = std::min(n <= GBP_RJ_SHARES_UP_TO ? 3 : (n <= 1100 ? 4 : (n <= 1600 ? 3 : 2)), GBP_RJ_PHYSICS_MAX_WAVES);   // (two workgroups per Jacobian in the smallest launches: three waves each, 2 048 chains 22.6 -> 23.3 M)
-#ifdef GBP_RJ_PHYSICS_NW
-            t.nw = GBP_RJ_PHYSICS_NW;                          // (A/B builds under scripts/ab only)
-#endif
             t.lds = (std::max(dyn_lds_bytes(t.nw, K, (sys->t.npts + 63) / 64), sens_lds_bytes(t.nw, K < GBP_RJ_PHYSICS_LDS_LAYERS ? K : GBP_RJ_PHYSICS_LDS_LAYERS)) + 15) & ~(size_t)15;     // + the output row, physics()
         }
-        (void)deep_per_chain;
         if (P > 1) {
             GBP_HIP(hipEventRecord(bs->start, main_q));
             for (int p = 0; p < P; ++p) GBP_HIP(hipStreamWaitEvent(part[p].q, bs->start, 0));
         }
         // (the accept stage of an iteration and the proposal of the next share a launch -- k_rj_step8 -- from the second iteration of a call:
         //  two rows of ownership flags per sub-block, written by the proposals, read by the accept stages)
-#ifdef GBP_RJ_NO_FUSED_STEP
-        const bool fused_step = false;                               // (A/B builds only)
-#else
         const bool fused_step = n_iterations > 1;
-#endif
         bool alloc_failed = false;
         for (int p = 0; p < P && !alloc_failed; ++p) {
-            const size_t deep_bytes = K > GBP_RJ_PHYSICS_LDS_LAYERS ? ((sens_lds_bytes(std::max(part[p].nw, stage0_waves(part[p].nw)), K) + 255) & ~(size_t)255) : 0;
+            const size_t deep_bytes = K > GBP_RJ_PHYSICS_LDS_LAYERS ? ((sens_lds_bytes(part[p].nw, K) + 255) & ~(size_t)255) : 0;
             if (deep_bytes > 0 && hipMallocAsync((void**)&part[p].deep, deep_bytes * (size_t)part[p].c.B, part[p].q) != hipSuccess) {
                 part[p].deep = nullptr;
                 alloc_failed = true;
@@ -3396,7 +3109,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
                 part[p].flags = nullptr;
                 alloc_failed = true;
             }
-            if (!alloc_failed && GBP_RJ_ORDERED_PHYSICS && n_iterations >= 4 && part[p].c.B > 64 &&
+            if (!alloc_failed && n_iterations >= 4 && part[p].c.B > 64 &&
                 hipMallocAsync((void**)&part[p].order, sizeof(int32_t) * (size_t)part[p].c.B, part[p].q) != hipSuccess) {
                 part[p].order = nullptr;
                 alloc_failed = true;
@@ -3413,26 +3126,19 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             return fail(GBP_ERR_HIP, "sampler sub-blocks: working set of the deep models: %s", hipGetErrorString(e));
         }
         auto physics = [&](const Part& t, int stage) {
-            // (stage 0 -- the Jacobian pass at the remapped model: half of the workgroups leave at once -- may take a wave count of its own;
-            //  the deep models' global working set is sized for the larger of the two)
-            const int nw_s = stage == 0 ? stage0_waves(t.nw) : t.nw;
-            const size_t lds_s = stage == 0 ? ((std::max(dyn_lds_bytes(nw_s, K, (sys->t.npts + 63) / 64), sens_lds_bytes(nw_s, K < GBP_RJ_PHYSICS_LDS_LAYERS ? K : GBP_RJ_PHYSICS_LDS_LAYERS)) + 15) & ~(size_t)15) : t.lds;
-            const size_t deep_bytes = K > GBP_RJ_PHYSICS_LDS_LAYERS ? ((sens_lds_bytes(std::max(t.nw, stage0_waves(t.nw)), K) + 255) & ~(size_t)255) : 0;
+            const size_t deep_bytes = K > GBP_RJ_PHYSICS_LDS_LAYERS ? ((sens_lds_bytes(t.nw, K) + 255) & ~(size_t)255) : 0;
             const rj::RjOpt ox = rj::extend(t.o);
             const size_t out_bytes = (size_t)o->n_channels * sizeof(double);          // the output row behind the stages' block (k_rj_physics)
-            const int out_offset = (int)lds_s;
-            // (the deepest 1 / GBP_RJ_SPLIT_DEEP of an ordered launch's chains get a second workgroup where the launch does not split every chain's)
-            const int shares = jacobian_shares(t.c.B);
-            const int n_split = (GBP_RJ_SPLIT_DEEP > 0 && shares == 1 && t.order != nullptr) ? t.c.B / GBP_RJ_SPLIT_DEEP : 0;
-            const int grid = t.c.B * shares + n_split;
+            const int out_offset = (int)t.lds;
+            const int grid = t.c.B * jacobian_shares(t.c.B);
             if (o->exact_jacobian)
-                hipLaunchKernelGGL(rj::k_rj_physics<true>, dim3(grid), dim3(64 * nw_s), lds_s + out_bytes, t.q, ox, t.c, sys->d_chan, sys->d_pts, sys->t.npts,
+                hipLaunchKernelGGL(rj::k_rj_physics<true>, dim3(grid), dim3(64 * t.nw), t.lds + out_bytes, t.q, ox, t.c, sys->d_chan, sys->d_pts, sys->t.npts,
                                    sys->t.nF, sys->sigma_direct, stage, t.deep, deep_bytes, sys->d_bins, sys->bin0, sys->n_bins, sys->d_bin_chan,
-                                   sys->d_bin_pts, out_offset, t.order, n_split);
+                                   sys->d_bin_pts, out_offset, t.order);
             else
-                hipLaunchKernelGGL(rj::k_rj_physics<false>, dim3(grid), dim3(64 * nw_s), lds_s + out_bytes, t.q, ox, t.c, sys->d_chan, sys->d_pts, sys->t.npts,
+                hipLaunchKernelGGL(rj::k_rj_physics<false>, dim3(grid), dim3(64 * t.nw), t.lds + out_bytes, t.q, ox, t.c, sys->d_chan, sys->d_pts, sys->t.npts,
                                    sys->t.nF, sys->sigma_direct, stage, t.deep, deep_bytes, sys->d_bins, sys->bin0, sys->n_bins, sys->d_bin_chan,
-                                   sys->d_bin_pts, out_offset, t.order, n_split);
+                                   sys->d_bin_pts, out_offset, t.order);
         };
         // One host thread per sub-block issues that sub-block's launches (7 per iteration at ~9 us each: one thread issuing for
         // four sub-blocks would be slower than the GPU -- measured 31 vs 37.6 M chain-iterations/s at 8 192 chains; with a thread
@@ -3462,12 +3168,8 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
                 const size_t lds = std::max((size_t)8 * o->n_channels * sizeof(double), n_deep ? rj::Lds::bytes(K, o->n_channels) : (size_t)0);
                 const int32_t* cur = t.flags + (size_t)(it & 1) * nB;
                 int32_t* nxt = t.flags + (size_t)((it + 1) & 1) * nB;
-                if (packed_trips(nB))
-                    hipLaunchKernelGGL(rj::k_rj_step8<true>, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o), t.c, (uint32_t)iter, accumulate,
-                                       n_packed, cur, nxt);
-                else
-                    hipLaunchKernelGGL(rj::k_rj_step8<false>, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o), t.c, (uint32_t)iter, accumulate,
-                                       n_packed, cur, nxt);
+                hipLaunchKernelGGL(rj::k_rj_step8, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o), t.c, (uint32_t)iter, accumulate,
+                                   n_packed, cur, nxt);
                 return GBP_OK;
             }
             return gbp_rj_accept(&t.o, &t.c, iter, accumulate, t.q);
@@ -3480,16 +3182,6 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             pst[p] = s2;
             if (s2 != GBP_OK) perr[p] = gbp_last_error();      // (the message is per host thread: hand it to the caller's)
         };
-#ifdef GBP_RJ_SINGLE_ISSUER
-        {   // (A/B builds only: the caller's thread issues for every sub-block in turn)
-            gbp_status s2 = GBP_OK;
-            for (int it = 0; it < n_iterations && s2 == GBP_OK; ++it)
-                for (int p = 0; p < P && s2 == GBP_OK; ++p) s2 = issue(p, it);
-            if (s2 == GBP_OK && hipGetLastError() != hipSuccess) s2 = GBP_ERR_HIP;
-            pst[0] = s2;
-            if (s2 != GBP_OK) perr[0] = gbp_last_error();
-        }
-#else
         {
             // (std::thread's constructor throws std::system_error when the process is out of threads: nothing may leave an
             //  extern "C" entry -- the sub-blocks that got no thread run on the caller's, after its own)
@@ -3503,7 +3195,6 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             for (int p : inline_parts) run_part(p);
             for (auto& w : workers) w.join();
         }
-#endif
         for (int p = 0; p < P; ++p)
             if (pst[p] != GBP_OK && st == GBP_OK) st = fail(pst[p], "sampler sub-block: %s", perr[p].c_str());
         const hipError_t le = hipGetLastError();
@@ -3535,7 +3226,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
         }
         // fm_dlogc at the remapped models whose structure changed (Model.py:383-384): prediction and Jacobian in one pass
         if ((st = fm_dlogc(c->nl_a, c->sigma_r, c->height, c->pred_r, c->J_r, main_q, 0)) != GBP_OK) return st;
-        if ((st = rj_newton_launch(o, c, iter, one_stage_launch(B, td != nullptr), stream)) != GBP_OK) return st;
+        if ((st = gbp_rj_newton(o, c, iter, stream)) != GBP_OK) return st;
         if (fork) {
             GBP_HIP(hipEventRecord(ss->fork, main_q));
             GBP_HIP(hipStreamWaitEvent(ss->q, ss->fork, 0));
@@ -3558,7 +3249,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
             GBP_HIP(hipEventRecord(ss->join, ss->q));
             GBP_HIP(hipStreamWaitEvent(main_q, ss->join, 0));
         }
-        if ((st = rj_accept_launch(o, c, iter, accumulate, one_stage_launch(B, td != nullptr), stream)) != GBP_OK) return st;
+        if ((st = gbp_rj_accept(o, c, iter, accumulate, stream)) != GBP_OK) return st;
         if (moving) {
             hipLaunchKernelGGL(rj::k_td_moves_accept, dim3((B + 63) / 64), dim3(64), 0, main_q, rj::extend(*o), *c, td->moves, td->mix.n_weights, N);
             GBP_HIP(hipGetLastError());

@@ -1,6 +1,8 @@
 #!/bin/bash
-# A/B builds of the library for same-box comparisons: scripts/build_ab.sh NAME [-Dflag ...]  ->  scripts/ab/NAME.so
-# (measurement only: the product loads geobipy_amd/csrc/libgeobipy_amd.so, built by geobipy_amd/build.py with no -D flags)
+# A copy of the library for same-box A/B comparisons: scripts/build_ab.sh NAME [hipcc argument ...]  ->  scripts/ab/NAME.so
+# It builds the tree as it stands with the product's flags (geobipy_amd/build.py), so `scripts/build_ab.sh parent` before a change
+# keeps the parent's library for scripts/ab_bits.py and scripts/ab_rj.py (GBP_AB_LIB).  Measurement only: the product loads
+# geobipy_amd/csrc/libgeobipy_amd.so.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

@@ -180,7 +180,7 @@ def propose_angles(moves, seed, b, it, current, centre):
 
 
 def newton(o, seed, b, it, vp, edges_r, sigma_r, J, pred, data, rel, add, add_scale=1.0, groups=None):
-    """k_rj_newton for one chain: (log_prop, C) with precision = C C'."""
+    """newton_body for one chain: (log_prop, C) with precision = C C'."""
     k = sigma_r.size
     std = channel_std(data, rel, add, add_scale, groups)
     a = data > 0.0
@@ -196,7 +196,7 @@ def newton(o, seed, b, it, vp, edges_r, sigma_r, J, pred, data, rel, add, add_sc
 
 def accept(o, seed, b, it, sp, vp, action, edges_r, sigma_r, log_prop, C, J_p, pred_p, data, rel_p, add_p, like_p, prior, like,
            add_scale=1.0, groups=None, prior_const=0.0):
-    """k_rj_accept for one chain: (log_ratio, accepted, prior_p).  prior_const: the density of the uniform height prior, when the
+    """accept_body for one chain: (log_ratio, accepted, prior_p).  prior_const: the density of the uniform height prior, when the
     height is sampled (its proposals are inside the prior by construction)."""
     prop = np.exp(log_prop)
     prior_p = rjmcmc.model_log_prior(sp, vp, edges_r, prop) + levels_log_prior(rel_p, o["rel_min"], o["rel_max"])
