@@ -1321,6 +1321,42 @@ extern "C" gbp_status gbp_hitmap_products(int B, int nv, int nz, const int32_t* 
     return GBP_OK;
 }
 
+// Class probabilities of B hit maps [B, nv, nz] for K classes in log10 conductivity (means / scales: host arrays of K values, scale the
+// standard deviation) -> prob [B, K, nz], best [B, nz] (the most probable class) and best_p [B, nz] (its probability)
+extern "C" gbp_status gbp_hitmap_classes(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width, int K,
+                                         const double* means, const double* scales, double* prob, int32_t* best, double* best_p, void* stream)
+{
+    if (B < 0 || nv < 1 || nz < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: negative or zero size%s");
+    if (K < 1 || K > hitmap::MAX_CLASSES) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: K outside 1 .. 16%s");
+    if (!means || !scales) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: means / scales NULL%s");
+    hitmap::Classes cl = {};
+    cl.n = K;
+    for (int k = 0; k < K; ++k) {
+        if (!std::isfinite(means[k])) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: every class mean must be finite%s");
+        if (!(std::isfinite(scales[k]) && scales[k] > 0.0))
+            return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: every class scale must be finite and positive%s");
+        cl.mean[k] = means[k];
+        cl.scale[k] = scales[k];
+    }
+    const int64_t lds = (int64_t)K * nv * (int64_t)sizeof(double);
+    if (lds > 65536) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: the class table (K * n_value * 8 B) exceeds 64 KiB of LDS%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!hitmap || !log_mean_prior || !prob || !best || !best_p) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: NULL pointer%s");
+    if ((int64_t)B * nz > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: B * n_depth out of range%s");
+    const dim3 grid(B, (nz + 255) / 256);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)lds, (hipStream_t)stream, nv, nz, hitmap, log_mean_prior, half_width, cl, prob, best,
+                           best_p);
+    };
+    if (K <= 1) launch(hitmap::k_hitmap_classes<1>);
+    else if (K <= 2) launch(hitmap::k_hitmap_classes<2>);
+    else if (K <= 4) launch(hitmap::k_hitmap_classes<4>);
+    else if (K <= 8) launch(hitmap::k_hitmap_classes<8>);
+    else launch(hitmap::k_hitmap_classes<16>);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 // The hit maps' rows (M = nv * nz cells each) as runs.  Call with start == NULL to COUNT (counts[B] <- runs per row), build the
 // exclusive prefix ptr[B + 1] of the counts, allocate ptr[B] entries, then call again with ptr / start / value to WRITE.
 extern "C" gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t* hitmap, int64_t* counts, const int64_t* ptr, int32_t* start,

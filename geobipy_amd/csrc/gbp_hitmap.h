@@ -106,6 +106,85 @@ __global__ __launch_bounds__(256) void k_hitmap_products(int nv, int nz, const i
         if (k < qs.n) q_idx[k * plane + o] = iq[k] < nv - 1 ? iq[k] : nv - 1;
 }
 
+// Up to 16 classes in log10 conductivity, passed by value (kernel arguments: no device copy).  scale[k] > 0 is the standard deviation.
+constexpr int MAX_CLASSES = 16;
+struct Classes {
+    double mean[MAX_CLASSES];
+    double scale[MAX_CLASSES];
+    int n;
+};
+
+// Class (lithology) probabilities of every column (Minsley, Foks & Bedrosian 2020; the reference's RectilinearMesh2D._compute_probability
+// with log=10 along the value axis), one workgroup per (sounding, 256 depth cells) as k_hitmap_stats, thread z walking its column once:
+//   x_v = k_hitmap_stats's centre of value cell v + log_mean_prior[b] / ln 10,  w[v][k] = norm.pdf(x_v, mean_k, scale_k) (scipy's form);
+//   S_k = sum_v c_v w[v][k] (v ascending);  prob[b, k, z] = S_k / sum_k' S_k' (0 / 0 = NaN: an empty column, or every term underflows);
+//   best[b, z] = the first k of the largest probability (numpy argmax: a NaN wins, an all-NaN column gives 0);
+//   best_p[b, z] = its probability.
+// The prologue builds the sounding's table w [nv][K] in fp64 in LDS (K nv exps per workgroup, the device libm exp: subnormals kept);
+// in the column loop every lane of a wave reads the same table row, a broadcast.  KB is the class bucket (K <= KB): accumulators of
+// unused classes cost neither registers nor FMAs beyond the bucket.  A wave whose 64 cells of a value row are all empty skips the row.
+template <int KB>
+__global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const int* __restrict__ hm, const double* __restrict__ log_mean_prior,
+                                                         double half_width, Classes cl, double* __restrict__ prob, int* __restrict__ best,
+                                                         double* __restrict__ best_p)
+{
+    extern __shared__ double wt[];                 // [nv][K]
+    const int b = blockIdx.x, z = blockIdx.y * 256 + threadIdx.x, K = cl.n;
+    const double shift = log_mean_prior[b] / 2.302585092994046;
+    const double w = 2.0 * half_width;
+    for (int i = threadIdx.x; i < nv * K; i += 256) {
+        const int v = i / K, k = i - v * K;
+        const double x = ((((double)v + 0.5) / (double)nv) * w - half_width) + shift;
+        const double y = (x - cl.mean[k]) / cl.scale[k];
+        wt[i] = exp(-y * y / 2.0) / 2.5066282746310002 / cl.scale[k];      // scipy: _norm_pdf((x - loc) / scale) / scale
+    }
+    __syncthreads();
+    if (z >= nz) return;
+    const int* col = hm + (size_t)b * nv * nz + z;
+    double acc[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) acc[k] = 0.0;
+    auto add = [&](int h, int v) {
+        if (h != 0) {
+            const double c = (double)h;
+            const double* row = wt + v * K;
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (k < KB / 2 || k < K) acc[k] += c * row[k];    // (the lower half of a bucket is always in use: K > KB / 2)
+        }
+    };
+    constexpr int U = 10;                          // ten loads in flight per wave, issued before the rows they feed
+    int v0 = 0;
+    for (; v0 + U <= nv; v0 += U) {
+        int h[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) h[u] = col[(size_t)(v0 + u) * nz];
+#pragma unroll
+        for (int u = 0; u < U; ++u) add(h[u], v0 + u);
+    }
+    for (; v0 < nv; ++v0) add(col[(size_t)v0 * nz], v0);
+    double tot = 0.0;
+#pragma unroll
+    for (int k = 0; k < KB; ++k)
+        if (k < KB / 2 || k < K) tot += acc[k];
+    const size_t o = (size_t)b * nz + z, plane = (size_t)nz;
+    double* pb = prob + (size_t)b * K * nz + z;
+    int ib = 0;
+    double pbest = 0.0;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        if (k < KB / 2 || k < K) {
+            const double p = acc[k] / tot;
+            pb[k * plane] = p;
+            const bool take = k == 0 || (pbest == pbest && (p > pbest || p != p));
+            ib = take ? k : ib;
+            pbest = take ? p : pbest;
+        }
+    }
+    best[o] = ib;
+    best_p[o] = pbest;
+}
+
 // Runs of a row's flattened cells: a run starts at cell 0 and wherever the count differs from the cell before.
 // Pass 1 (WRITE = false): counts[b] = number of runs.  Pass 2 (WRITE = true): start / value at ptr[b] + (rank of the run in the row).
 // One workgroup per row walks it in tiles of 1024 cells (4 per thread, coalesced); the ranks inside a tile come from a wave ballot

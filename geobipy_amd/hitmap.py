@@ -102,3 +102,35 @@ def products(hitmap, log_mean_prior, half_width, percentiles=(5, 50, 95), credib
     out["entropy"] = entropy_bits(m["total"], m["s1"], dz * (2.0 * float(half_width) / nv))
     out["total"], out["s1"] = m["total"], m["s1"]
     return out
+
+
+def class_probability(hitmap, log_mean_prior, half_width, means, scales):
+    """Class (lithology) probabilities of the hit maps [B, n_value, n_depth] in one kernel (gbp_hitmap_classes), on the maps' device: K
+    classes in log10 conductivity (S/m), class k weighting value cell v by norm.pdf(x_v, means[k], scales[k]) at the cell's centre x_v
+    (the centres of ``statistics``), normalised over the classes per depth cell -- the reference's ``compute_probability(MvNormal(means,
+    variance), log=10, axis=0)`` (mesh/RectilinearMesh2D.py _compute_probability), whose "variance" reaches scipy as the scale: here
+    ``scales`` are standard deviations.  Every class has the same prior weight.  Returns ``probability`` [B, K, n_depth] (NaN where every
+    term is 0, e.g. an empty column), ``highest_marginal`` [B, n_depth] int32 (the first most probable class; numpy's argmax over the
+    class axis, 0 for a NaN column) and ``probability_of_highest_marginal`` [B, n_depth] (its probability, NaN for a NaN column).
+    1 <= K <= 16, and K n_value fp64 weights must fit in 64 KiB (gbp_hitmap_classes refuses the rest)."""
+    if hitmap.device.type != "cuda":
+        raise _lib.NativeLibraryError("hitmap.class_probability runs on the device (gbp_hitmap_classes); there is no host fallback")
+    B, nv, nz = hitmap.shape
+    hm = hitmap.contiguous()
+    assert hm.dtype == torch.int32
+    dev = hm.device
+    mu = [float(m) for m in means]
+    sd = [float(s) for s in scales]
+    if len(mu) != len(sd):
+        raise ValueError("class_probability: %d means but %d scales" % (len(mu), len(sd)))
+    K = len(mu)
+    lmp = log_mean_prior.to(device=dev, dtype=torch.float64).contiguous()
+    ma = (ctypes.c_double * max(K, 1))(*mu)
+    sa = (ctypes.c_double * max(K, 1))(*sd)
+    prob = torch.empty((B, K, nz), dtype=torch.float64, device=dev)
+    best = torch.empty((B, nz), dtype=torch.int32, device=dev)
+    best_p = torch.empty((B, nz), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gbp_hitmap_classes(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), K, ma, sa, prob.data_ptr(),
+                                                  best.data_ptr(), best_p.data_ptr(), _stream(dev)))
+    return dict(probability=prob, highest_marginal=best, probability_of_highest_marginal=best_p)

@@ -1,17 +1,21 @@
 """Posterior line products of a flight line's results container: the mean, median and mode models, percentiles and the credible interval,
 entropy, opacity, depth of investigation (DOI) and interface probability -- what the reference's ``Inference2D`` derives from the hit maps
 (inversion/Inference2D.py: compute_mean/median/mode_parameter, percentile, credible_interval, compute_opacity, compute_doi, entropy,
-interface_probability).
+interface_probability) -- and, for K classes defined in log10 conductivity, the class (lithology) probabilities of every depth cell and
+the most probable class (Inference2D.compute_probability, highestMarginal, probability_of_highest_marginal; Minsley, Foks & Bedrosian 2020).
 
 The work splits in two.  Per sounding, one streaming kernel reduces every (sounding, depth cell) column of the int32 hit maps to a few
 moments -- total, sum c ln c, the mode's cell, the quantiles' cells, the mean (csrc/gbp_hitmap.h: k_hitmap_products, through
-``hitmap.products``); the maps go up a block at a time and never leave the device.  Per line, the small functions below finish on
-[N, n_depth] arrays: they run on whichever device their tensors are on (the CPU tier tests them without a GPU).  Everything is log10
-conductivity (S/m) except entropy (bits), opacity (0 - 1) and the depths (m).
+``hitmap.products``); the maps go up a block at a time and never leave the device.  With classes, a second kernel reduces the same
+uploaded block to the K class probabilities (k_hitmap_classes, through ``hitmap.class_probability``).  Per line, the small functions
+below finish on [N, n_depth] arrays: they run on whichever device their tensors are on (the CPU tier tests them without a GPU).
+Everything is log10 conductivity (S/m) except entropy (bits), opacity and probabilities (0 - 1) and the depths (m).
 
     python -m geobipy_amd.line_products <container or directory> [--credible 90] [--doi 67] [--percentiles 5 50 95]
+                                        [--class-means M1 M2 ... --class-scales S1 S2 ...]
 
-writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.
+writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.  The class means and scales (standard deviations)
+are in log10 S/m; they come together, 1 to 16 of each.
 """
 import argparse
 import glob
@@ -24,6 +28,7 @@ import torch
 
 LN10 = 2.302585092994046
 MAX_QUANTILES = 8
+MAX_CLASSES = 16
 
 VALUES = "/model/values/posterior"            # the conductivity-depth hit maps [N, n_value, n_depth] and their mesh
 INTERFACES = "/model/mesh/y/edges/posterior"  # the interface-depth hit counts [N, n_depth]
@@ -145,7 +150,18 @@ def _key(arrays, *names):
     return None
 
 
-def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0):
+def check_classes(means, scales):
+    """(means, scales) as float64 arrays of 1 to 16 classes in log10 S/m: equal lengths, finite means, finite positive scales."""
+    mu = np.asarray(means, dtype=np.float64).reshape(-1)
+    sd = np.asarray(scales, dtype=np.float64).reshape(-1)
+    if mu.size != sd.size or not 1 <= mu.size <= MAX_CLASSES:
+        raise ValueError("classes: 1 to %d means and as many scales, got %d and %d" % (MAX_CLASSES, mu.size, sd.size))
+    if not np.all(np.isfinite(mu)) or not np.all(np.isfinite(sd) & (sd > 0.0)):
+        raise ValueError("classes: the means must be finite and the scales finite and positive")
+    return mu, sd
+
+
+def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0, classes=None):
     """{name: numpy array} of the line products of the results container at ``path`` (``<line>.h5`` or the ``.results[.npz]`` stand-in,
     read through ``hdf.load_results``; the reference's own files where they hold this layout).  The hit maps go to ``device`` (default
     cuda:0) ``block`` soundings at a time.  Per sounding [N, n_depth] (log10 S/m): mean, median, mode, percentile_<p>, credible_low /
@@ -155,10 +171,18 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     The reference's DOI is ``mesh.y_centres`` at the index of the walk, and its mesh flips depth to height relative to the data's
     elevation (Inference2D.mesh: y edges negated, relative_to = elevation), so y_centres = elevation - depth centre.  ``doi_depth`` is
     the depth centre below the surface (m, positive down); ``doi_elevation`` = elevation - doi_depth is the reference's value, present
-    where the container has /data/elevation."""
+    where the container has /data/elevation.
+
+    ``classes`` = (means, scales), 1 to 16 classes in log10 S/m (scales: standard deviations; ``hitmap.class_probability``), adds
+    ``class_probability`` [N, K, n_depth] (the layout of the reference's ``probabilities``), ``highest_marginal`` [N, n_depth] (int32),
+    ``probability_of_highest_marginal`` [N, n_depth], ``class_means`` and ``class_scales``, from the blocks the products were computed
+    on (no second upload).  The reference takes its argmax over the last axis of a [N, K, n_depth] array in Inference3D but over the
+    class axis in Inference2D; here it is over the class axis."""
     from . import hdf, hitmap
     if not 0.0 < float(credible) < 100.0:
         raise ValueError("credible must lie in (0, 100)")
+    if classes is not None:
+        cmeans, cscales = check_classes(*classes)
     arrays, _ = hdf.load_results(path)
     hm_all = _key(arrays, VALUES + "/values/data", VALUES + "/values")
     if hm_all is None or hm_all.ndim != 3:
@@ -178,6 +202,10 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
         hm = torch.as_tensor(np.ascontiguousarray(hm_all[b0:b1], dtype=np.int32)).to(dev)
         lmp = torch.as_tensor(rel[b0:b1] * LN10, dtype=torch.float64, device=dev)
         p = hitmap.products(hm, lmp, hw, percentiles=percentiles, credible=credible, depth_edges=d_edges)
+        if classes is not None:
+            c = hitmap.class_probability(hm, lmp, hw, cmeans, cscales)
+            p.update(class_probability=c["probability"], highest_marginal=c["highest_marginal"],
+                     probability_of_highest_marginal=c["probability_of_highest_marginal"])
         parts.append({k: v.cpu() for k, v in p.items()})
     keys = parts[0].keys() if parts else []
     out = {k: torch.cat([p_[k] for p_ in parts]).numpy() for k in keys}
@@ -206,6 +234,12 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     if fid is not None:
         out["fiducial"] = np.asarray(fid)
     out["credible"], out["doi_percent"] = np.float64(credible), np.float64(doi)
+    if classes is not None:
+        if not N:
+            K = cmeans.size
+            out.update(class_probability=np.zeros((0, K, nz)), highest_marginal=np.zeros((0, nz), dtype=np.int32),
+                       probability_of_highest_marginal=np.zeros((0, nz)))
+        out["class_means"], out["class_scales"] = cmeans, cscales
     return out
 
 
@@ -241,18 +275,24 @@ def containers(path):
 def parser():
     ap = argparse.ArgumentParser(prog="python -m geobipy_amd.line_products",
                                  description="Posterior line products (mean, median, mode, percentiles, credible range, entropy, opacity, "
-                                             "DOI, interface probability) of GeoBIPy results containers, written to <line>.products.npz.")
+                                             "DOI, interface probability and, with --class-means / --class-scales, class probabilities and "
+                                             "the most probable class) of GeoBIPy results containers, written to <line>.products.npz.")
     ap.add_argument("paths", nargs="+", help="results containers (<line>.h5, <line>.results.npz) or directories holding them")
     ap.add_argument("--credible", type=float, default=90.0, help="credible interval of the opacity, percent (default 90)")
     ap.add_argument("--doi", type=float, default=67.0, help="opacity level of the depth of investigation, percent (default 67)")
     ap.add_argument("--percentiles", type=float, nargs="+", default=[5.0, 50.0, 95.0], help="percentiles to write (default 5 50 95)")
+    ap.add_argument("--class-means", type=float, nargs="+", default=None, metavar="M",
+                    help="means of 1 to 16 classes (lithologies) in log10 S/m; with --class-scales")
+    ap.add_argument("--class-scales", type=float, nargs="+", default=None, metavar="S",
+                    help="standard deviations of the classes in log10 S/m, one per mean, positive")
     ap.add_argument("--block", type=int, default=4096, help="soundings per upload (default 4096)")
     ap.add_argument("--device", default=None, help="torch device of the kernel (default cuda:0)")
     return ap
 
 
 def parse_args(argv=None):
-    """The command line's arguments, checked: percents in (0, 100), at most 8 distinct quantiles per pass, a positive block."""
+    """The command line's arguments, checked: percents in (0, 100), at most 8 distinct quantiles per pass, a positive block, class means
+    and scales together, 1 to 16 of each, equal counts, positive scales."""
     ap = parser()
     a = ap.parse_args(argv)
     for name, v in (("--credible", a.credible), ("--doi", a.doi)):
@@ -266,6 +306,13 @@ def parse_args(argv=None):
         ap.error(str(e))
     if a.block < 1:
         ap.error("--block must be positive")
+    if (a.class_means is None) != (a.class_scales is None):
+        ap.error("--class-means and --class-scales come together")
+    if a.class_means is not None:
+        try:
+            check_classes(a.class_means, a.class_scales)
+        except ValueError as e:
+            ap.error("--class-means / --class-scales: " + str(e))
     return a
 
 
@@ -276,7 +323,9 @@ def main(argv=None):
         print("no results containers under %s" % " ".join(a.paths), file=sys.stderr)
         return 1
     for f in files:
-        out = from_results(f, device=a.device, block=a.block, percentiles=tuple(a.percentiles), credible=a.credible, doi=a.doi)
+        classes = None if a.class_means is None else (a.class_means, a.class_scales)
+        out = from_results(f, device=a.device, block=a.block, percentiles=tuple(a.percentiles), credible=a.credible, doi=a.doi,
+                           classes=classes)
         dst = save(out, output_path(f))
         print("%s -> %s (%d soundings)" % (f, dst, out["mean"].shape[0]))
     return 0

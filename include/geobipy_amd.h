@@ -606,6 +606,17 @@ gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t *hitmap, int64_t *cou
 gbp_status gbp_hitmap_products(int B, int n_value, int n_depth, const int32_t *hitmap, const double *log_mean_prior, double half_width,
                                int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                void *stream);
+/* gbp_hitmap_classes -- class (lithology) probabilities of every column for K classes in log10 conductivity (S/m), the reference's
+ * Histogram.compute_probability(MvNormal(mean, variance), log=10, axis=0) (mesh/RectilinearMesh2D.py _compute_probability): with x_v the
+ * bin centres of gbp_hitmap_statistics and w_k(x) = exp(-((x - means[k]) / scales[k])^2 / 2) / (sqrt(2 pi) scales[k]) (scipy's
+ * norm.pdf -- scales[k] is a STANDARD DEVIATION: the reference hands the number it calls variance to scipy as scale),
+ * prob[b, k, z] = sum_v c_v w_k(x_v) / sum_k' sum_v c_v w_k'(x_v) ([B, K, n_depth]; NaN where every term is 0, an empty column among
+ * them); best[b, z] = the first class of the largest probability (numpy argmax; an all-NaN column: 0) and best_p[b, z] its probability
+ * ([B, n_depth]).  means / scales: HOST arrays of K values, 1 <= K <= 16, means finite, scales finite and > 0; the table of K * n_value
+ * fp64 weights lives in LDS and must fit in 64 KiB.  GBP_ERR_INVALID_ARG for bad sizes or classes, NULL pointers or B * n_depth beyond
+ * int32, every check before any launch; B == 0 launches nothing. */
+gbp_status gbp_hitmap_classes(int B, int n_value, int n_depth, const int32_t *hitmap, const double *log_mean_prior, double half_width, int K,
+                              const double *means, const double *scales, double *prob, int32_t *best, double *best_p, void *stream);
 
 /* [host] Results containers (geobipy_amd/h5lite.py; no reference counterpart -- the reference stores its hit maps dense): the rows of
  * a conductivity-depth hit map held as runs (row r owns runs ptr[r] .. ptr[r + 1] - 1; run q holds value[q] from cell start[q] of the row
