@@ -4,7 +4,8 @@ Scope: the 1-D layered-earth FDEM and TDEM forward solves,
 Gaussian data misfit / log-likelihood evaluated at every rjMCMC proposal, behind the reference's
 ``FdemSystem / TdemSystem / Model / FdemDataPoint / TdemDataPoint`` interface, plus batched device-resident
 entry points (``FdemBatch``, ``TdemBatch``) and the rjMCMC step around them (``Inference1D`` with the reference's random
-streams, ``DeviceChains`` resident on the GPU).
+streams, ``DeviceChains`` resident on the GPU), the posterior line products (``line_products``) and their gridding into survey volumes
+(``gridding.SibsonPlan``, ``survey_volume``).
 All arithmetic runs in hand-written HIP kernels (geobipy_amd/csrc); importing the classes works on
 a CPU-only machine, evaluating anything needs the built library and a GPU -- there is no fallback.
 """
@@ -15,7 +16,8 @@ from .batch import FdemBatch
 from .tdem import TdemBatch, TdemDataPoint, TdemDeviceChains, TdemSystem, TempestDataPoint
 from .inference import BatchedInference, Inference1D
 from .rjmcmc_gpu import DeviceChains
-from . import rjmcmc, survey, synthetic
+from .gridding import SibsonPlan
+from . import gridding, rjmcmc, survey, survey_volume, synthetic
 
 __all__ = ["CircularLoop", "FdemSystem", "Model", "RectilinearMesh1D", "FdemDataPoint", "FdemBatch", "TdemSystem", "TdemDataPoint", "TempestDataPoint", "TdemBatch", "TdemDeviceChains",
-           "Inference1D", "BatchedInference", "DeviceChains", "rjmcmc", "survey", "synthetic"]
+           "Inference1D", "BatchedInference", "DeviceChains", "SibsonPlan", "gridding", "rjmcmc", "survey", "survey_volume", "synthetic"]

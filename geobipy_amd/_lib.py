@@ -128,6 +128,12 @@ SIGNATURES = {
                            + [c_void_p]),
     "gbp_hitmap_runs": (c_int, [c_int, ctypes.c_int64] + [c_void_p] * 5 + [c_void_p]),
     "gbp_runs_to_zlib": (c_int, [c_int, ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_void_p]),
+    "gbp_sibson_plan_create": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, ctypes.POINTER(c_void_p)]),
+    "gbp_sibson_plan_create_ex": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_int64, c_void_p,
+                                          ctypes.POINTER(c_void_p)]),
+    "gbp_sibson_plan_destroy": (None, [c_void_p]),
+    "gbp_sibson_plan_query": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int64), c_void_p]),
+    "gbp_sibson_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gbp_debug_math": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_bench_time_forward_loglike": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p, c_int,
                                                                                         ctypes.POINTER(ctypes.c_float)]),

@@ -1398,3 +1398,198 @@ extern "C" gbp_status gbp_runs_to_zlib(int n_rows, int64_t cells_per_row, const 
     }
     return GBP_OK;
 }
+
+#include "gbp_grid.h"
+
+// Discrete Sibson gridding (gbp_grid.h): the plan holds the geometry of one grid -- nearest sounding, D, n, and per destination pixel the
+// list of the soundings its covering pixels point at, in row-major order of those pixels -- in bands of destination rows.  One band
+// (the lists fit the budget): they are written once, here.  Several: the plan keeps one band's room and gbp_sibson_apply rewrites it
+// band by band, so the sums and their order are the same either way.
+struct gbp_sibson_plan {
+    struct Band { int row0, row1, tile0, ntiles; long long base, len; };
+    int device = 0, N = 0, nx = 0, ny = 0, nseg = 0;
+    double max_d2 = 0.0;
+    int *d_index = nullptr, *d_D = nullptr, *d_n = nullptr, *d_segmax = nullptr, *d_rowmax = nullptr, *d_order = nullptr, *d_list = nullptr;
+    long long* d_ptr = nullptr;
+    long long total = 0, longest = 0, capacity = 0;
+    std::vector<Band> bands;
+};
+
+namespace {
+
+const int64_t GBP_SIBSON_DEFAULT_BUDGET = (int64_t)4 << 30;
+
+gbp_status sibson_fill(const gbp_sibson_plan* p, const gbp_sibson_plan::Band& b, hipStream_t stream)
+{
+    const long long cells = (long long)(b.row1 - b.row0) * p->nx;
+    hipLaunchKernelGGL(grid::k_cover_walk<true>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p->nx, p->ny, p->nseg, b.row0, b.row1,
+                       p->d_D, p->d_segmax, p->d_rowmax, p->d_index, (int*)nullptr, p->d_ptr, b.base, p->d_list);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" void gbp_sibson_plan_destroy(gbp_sibson_plan* p)
+{
+    if (!p) return;
+    for (void* d : {(void*)p->d_index, (void*)p->d_D, (void*)p->d_n, (void*)p->d_segmax, (void*)p->d_rowmax, (void*)p->d_order, (void*)p->d_list,
+                    (void*)p->d_ptr})
+        if (d) (void)hipFree(d);
+    delete p;
+}
+
+extern "C" gbp_status gbp_sibson_plan_create_ex(int N, const double* px, const double* py, int nx, int ny, double max_distance_px2,
+                                                int64_t list_budget_bytes, void* stream, gbp_sibson_plan** out)
+{
+    if (!out) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: out is NULL%s");
+    *out = nullptr;
+    if (N < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: N must be >= 1%s");
+    if (nx < 1 || ny < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: nx and ny must be >= 1%s");
+    if ((int64_t)nx * ny > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: nx * ny out of range (int32 pixel index)%s");
+    if (!px || !py) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: NULL pointer%s");
+    if (max_distance_px2 != max_distance_px2) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: max_distance_px2 is NaN (+inf for no mask)%s");
+    if (list_budget_bytes < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: negative list budget%s");
+    const int64_t budget = (list_budget_bytes ? list_budget_bytes : GBP_SIBSON_DEFAULT_BUDGET) / (int64_t)sizeof(int);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> h((size_t)2 * N);
+    GBP_HIP(hipMemcpyAsync(h.data(), px, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    GBP_HIP(hipMemcpyAsync(h.data() + N, py, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    GBP_HIP(hipStreamSynchronize(st));
+    for (double v : h)
+        if (!std::isfinite(v)) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: non-finite pixel coordinate%s");
+
+    gbp_sibson_plan* p = new (std::nothrow) gbp_sibson_plan();
+    if (!p) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: out of host memory%s");
+    const size_t P = (size_t)nx * ny;
+    p->N = N; p->nx = nx; p->ny = ny; p->nseg = (nx + grid::SEG - 1) / grid::SEG; p->max_d2 = max_distance_px2;
+    const int tiles_per_row = p->nseg;
+    const size_t ntiles = (size_t)tiles_per_row * ny;
+    std::vector<int> hn;
+    std::vector<long long> hptr;
+    std::vector<int> order;
+    hipError_t e = hipGetDevice(&p->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_index, P * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_D, P * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_n, P * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_segmax, ntiles * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_rowmax, (size_t)ny * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_order, ntiles * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_ptr, (P + 1) * sizeof(long long));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(grid::k_grid_nearest, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, N, px, py, nx, ny, p->d_index, p->d_D);
+        hipLaunchKernelGGL(grid::k_grid_segmax, dim3(ny), dim3(64), 0, st, nx, ny, p->nseg, p->d_D, p->d_segmax, p->d_rowmax);
+        hipLaunchKernelGGL(grid::k_cover_walk<false>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, nx, ny, p->nseg, 0, ny, p->d_D,
+                           p->d_segmax, p->d_rowmax, p->d_index, p->d_n, (const long long*)nullptr, 0LL, (int*)nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hn.resize(P);
+        e = hipMemcpyAsync(hn.data(), p->d_n, P * sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        gbp_sibson_plan_destroy(p);
+        return fail(GBP_ERR_HIP, "gbp_sibson_plan_create: %s", hipGetErrorString(e));
+    }
+    // exclusive prefix over the whole grid, bands of rows within the budget, tiles of a band longest first
+    hptr.resize(P + 1);
+    hptr[0] = 0;
+    for (size_t q = 0; q < P; ++q) {
+        hptr[q + 1] = hptr[q] + hn[q];
+        p->longest = std::max(p->longest, (long long)hn[q]);
+    }
+    p->total = hptr[P];
+    auto add_band = [&](int r0, int r1) {
+        gbp_sibson_plan::Band b = {r0, r1, r0 * tiles_per_row, (r1 - r0) * tiles_per_row, hptr[(size_t)r0 * nx], 0};
+        b.len = hptr[(size_t)r1 * nx] - b.base;
+        p->bands.push_back(b);
+        p->capacity = std::max(p->capacity, b.len);
+    };
+    int row0 = 0;
+    long long held = 0;
+    for (int i = 0; i < ny; ++i) {
+        const long long row = hptr[(size_t)(i + 1) * nx] - hptr[(size_t)i * nx];
+        if (row > budget) {
+            gbp_sibson_plan_destroy(p);
+            return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_create: one destination row's lists exceed the list budget%s");
+        }
+        if (i > row0 && held + row > budget) {
+            add_band(row0, i);
+            row0 = i;
+            held = 0;
+        }
+        held += row;
+    }
+    add_band(row0, ny);
+    order.resize(ntiles);
+    std::vector<long long> work(ntiles);
+    long long wmax = 1;
+    for (size_t t = 0; t < ntiles; ++t) {
+        const size_t r = t / tiles_per_row, j0 = (t % tiles_per_row) * grid::SEG, j1 = std::min((size_t)nx, j0 + grid::SEG);
+        work[t] = hptr[r * nx + j1] - hptr[r * nx + j0];
+        wmax = std::max(wmax, work[t]);
+        order[t] = (int)t;
+    }
+    for (const auto& b : p->bands)                 // sixteen classes of work; neighbours stay neighbours inside a class
+        std::stable_sort(order.begin() + b.tile0, order.begin() + b.tile0 + b.ntiles,
+                         [&](int a, int c) { return work[a] * 16 / wmax > work[c] * 16 / wmax; });
+    e = hipMalloc((void**)&p->d_list, (size_t)std::max(p->capacity, 1LL) * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_ptr, hptr.data(), (P + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_order, order.data(), ntiles * sizeof(int), hipMemcpyHostToDevice, st);
+    gbp_status rc = GBP_OK;
+    if (e == hipSuccess && p->bands.size() == 1) rc = sibson_fill(p, p->bands[0], st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the host arrays of the uploads die with this call)
+    if (e != hipSuccess || rc != GBP_OK) {
+        gbp_sibson_plan_destroy(p);
+        return e != hipSuccess ? fail(GBP_ERR_HIP, "gbp_sibson_plan_create: %s", hipGetErrorString(e)) : rc;
+    }
+    *out = p;
+    return GBP_OK;
+}
+
+extern "C" gbp_status gbp_sibson_plan_create(int N, const double* px, const double* py, int nx, int ny, double max_distance_px2, void* stream,
+                                             gbp_sibson_plan** out)
+{
+    return gbp_sibson_plan_create_ex(N, px, py, nx, ny, max_distance_px2, 0, stream, out);
+}
+
+extern "C" gbp_status gbp_sibson_plan_query(const gbp_sibson_plan* p, int32_t* index, int32_t* distance, int32_t* count, int64_t* info, void* stream)
+{
+    if (!p) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_plan_query: plan is NULL%s");
+    const size_t bytes = (size_t)p->nx * p->ny * sizeof(int);
+    hipStream_t st = (hipStream_t)stream;
+    if (index) GBP_HIP(hipMemcpyAsync(index, p->d_index, bytes, hipMemcpyDeviceToDevice, st));
+    if (distance) GBP_HIP(hipMemcpyAsync(distance, p->d_D, bytes, hipMemcpyDeviceToDevice, st));
+    if (count) GBP_HIP(hipMemcpyAsync(count, p->d_n, bytes, hipMemcpyDeviceToDevice, st));
+    if (info) {
+        const int64_t P = (int64_t)p->nx * p->ny, ntiles = (int64_t)p->nseg * p->ny;
+        info[0] = p->total;
+        info[1] = p->longest;
+        info[2] = (int64_t)p->bands.size();
+        info[3] = 3 * P * 4 + 2 * ntiles * 4 + (int64_t)p->ny * 4 + (P + 1) * 8 + std::max(p->capacity, 1LL) * 4;
+    }
+    return GBP_OK;
+}
+
+extern "C" gbp_status gbp_sibson_apply(const gbp_sibson_plan* p, int C, const double* values, double* out, void* stream)
+{
+    if (!p) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_apply: plan is NULL%s");
+    if (C < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_apply: C must be >= 1%s");
+    if (!values || !out) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_apply: NULL pointer%s");
+    const int64_t P = (int64_t)p->nx * p->ny, lim = 0x7fffffffffffffffLL / 8;
+    const int cblocks = (C + grid::COLS - 1) / grid::COLS;
+    if (cblocks > 65535 || (int64_t)C > lim / P || (int64_t)C > lim / p->N)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_apply: C * nx * ny or N * C out of range%s");
+    hipStream_t st = (hipStream_t)stream;
+    for (const auto& b : p->bands) {
+        if (p->bands.size() > 1) {
+            gbp_status rc = sibson_fill(p, b, st);
+            if (rc != GBP_OK) return rc;
+        }
+        hipLaunchKernelGGL(grid::k_sibson_gather, dim3(b.ntiles, cblocks), dim3(256), 0, st, C, p->nx, p->ny, p->nseg, p->d_order, b.tile0, p->d_ptr,
+                           b.base, p->d_list, p->d_D, p->max_d2, values, out);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}

@@ -1,0 +1,236 @@
+"""Survey volumes: the line products of ALL flight lines of a survey on one regular x-y grid, depth cell by depth cell -- depth-slice
+maps and 3-D volumes, what the reference's ``Inference3D.interpolate_3d`` / ``map_depth_slice`` / ``interpolate_marginal_3d`` build
+through ``Point.interpolate(method='sibson')`` (inversion/Inference3D.py -> pointcloud/Point.py -> base/interpolation.py).
+
+The reference grids one depth cell of one variable at a time, each a full sweep of the raster.  Here the soundings of every line are
+concatenated in line order, ONE ``gridding.SibsonPlan`` holds the geometry of the grid, and the plan is applied to ``[N, columns]`` blocks
+of each variable (columns = depth cells; ``class_probability`` [N, K, n_depth] goes through as K n_depth columns).  The grid is the
+reference's centred mesh over the soundings' bounding box (``gridding.centred_mesh``); the depth axis is the first line's, and every
+other line must share it (the reference takes ``lines[0].mesh.y`` for all, ``Inference3D.zGrid``).  ``elevation`` [ny, nx] is the
+soundings' elevation through the same plan -- the reference's ``mesh3d`` drapes its surface with ``Point.interpolate``'s default
+method (minimum curvature); this one is the Sibson surface.
+
+    python -m geobipy_amd.survey_volume <directory> --dx DX --dy DY [--variables mean percentile_5 ...] [--mask MAX_DISTANCE]
+                                        [--depth D | --depth-cells I0 I1] [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
+
+reads the directory's line containers and their ``<line>.products.npz`` (computed where absent: ``line_products.from_results``) and writes
+``survey_volume.npz`` (x_edges, y_edges, depth_edges, elevation, count, nearest_distance, the variables' names) and one
+``survey_volume.<variable>.npy`` [n_depth, ny, nx] per variable, filled column block by column block through a memory map: a volume is
+n_depth ny nx 8 bytes (440 x 1 000 x 1 000: 3.5 GB) and is never held in memory whole.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import gridding, line_products
+
+AXES_FILE = "survey_volume.npz"
+
+
+def volume_path(directory, variable):
+    return os.path.join(str(directory), "survey_volume.%s.npy" % variable)
+
+
+def depth_cells(depth, depth_edges):
+    """The depth cells ``depth`` selects, as a slice (``Inference2D._z_slice``): None -> all; an int -> that cell; a float -> the cell
+    holding that depth (m); a slice -> itself; a pair of ints -> cells i0 .. i1 inclusive; a pair of floats -> the cells holding both
+    depths and those between."""
+    e = np.asarray(depth_edges, dtype=np.float64)
+    nz = e.size - 1
+
+    def cell(d):
+        if not e[0] <= float(d) < e[-1]:
+            raise ValueError("depth %g is outside the depth axis [%g, %g)" % (d, e[0], e[-1]))
+        return int(np.searchsorted(e, float(d), side="right")) - 1
+
+    def index(i):
+        if not -nz <= int(i) < nz:
+            raise ValueError("depth cell %d is outside 0 .. %d" % (i, nz - 1))
+        return int(i) % nz
+
+    if depth is None:
+        return slice(0, nz)
+    if isinstance(depth, slice):
+        return slice(*depth.indices(nz))
+    if isinstance(depth, (int, np.integer)):
+        return slice(index(depth), index(depth) + 1)
+    if np.size(depth) == 1:
+        c = cell(np.asarray(depth).reshape(-1)[0])
+        return slice(c, c + 1)
+    if np.size(depth) != 2:
+        raise ValueError("depth must be a cell, a depth, a slice or a pair")
+    a, b = depth
+    ints = all(isinstance(v, (int, np.integer)) for v in (a, b))
+    lo, hi = sorted((index(a), index(b)) if ints else (cell(a), cell(b)))
+    return slice(lo, hi + 1)
+
+
+def load_line(path, device=None, block=4096):
+    """(x, y, elevation, products) of one line container: the soundings' coordinates from /data/x, /data/y, /data/elevation and the line
+    products from ``<line>.products.npz`` where present, else computed (``line_products.from_results``)."""
+    from . import hdf
+    arrays, _ = hdf.load_results(path)
+    x = line_products._key(arrays, "/data/x/data", "/data/x")
+    y = line_products._key(arrays, "/data/y/data", "/data/y")
+    if x is None or y is None:
+        raise ValueError("%s holds no /data/x and /data/y" % path)
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    elev = line_products._key(arrays, "/data/elevation/data", "/data/elevation")
+    elev = np.zeros_like(x) if elev is None else np.asarray(elev, dtype=np.float64).reshape(-1)
+    saved = line_products.output_path(path)
+    if os.path.exists(saved):
+        with np.load(saved) as z:
+            prod = {k: z[k] for k in z.files}
+    else:
+        prod = line_products.from_results(path, device=device, block=block)
+    if prod["mean"].shape[0] != x.size or elev.size != x.size:
+        raise ValueError("%s: %d soundings but products for %d" % (path, x.size, prod["mean"].shape[0]))
+    return x, y, elev, prod
+
+
+def _columns(prod_per_line, name, n_depth):
+    """([N, K, n_depth], whether the variable has a class axis) of variable ``name`` over all lines, line after line (K = 1 for the
+    [N, n_depth] variables)."""
+    parts, ndim = [], set()
+    for path, prod in prod_per_line:
+        if name not in prod:
+            raise ValueError("%s: the line products hold no %r (present: %s)" % (path, name, ", ".join(sorted(prod))))
+        a = np.asarray(prod[name], dtype=np.float64)
+        if a.ndim not in (2, 3) or a.shape[-1] != n_depth:
+            raise ValueError("%s: %r is not a per-depth-cell variable (shape %r)" % (path, name, a.shape))
+        parts.append(a.reshape(a.shape[0], -1, n_depth))
+        ndim.add(a.ndim)
+    if len({p.shape[1] for p in parts}) != 1 or len(ndim) != 1:
+        raise ValueError("%r has a different number of classes from line to line" % name)
+    return np.concatenate(parts), ndim == {3}
+
+
+def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None, block=256, device=None, out=None,
+               list_budget_bytes=0):
+    """Grid the line products of the containers ``paths`` (a directory, a container or a list of them; the lines in sorted order).
+
+    Returns a dict: ``x_edges``, ``y_edges`` (``gridding.centred_mesh`` of all soundings at spacing ``dx``, ``dy``), ``depth_edges``
+    (of the selected cells), ``elevation`` [ny, nx], ``count`` (n, the number of pixels covering a pixel) and ``nearest_distance`` (D,
+    pixels) [ny, nx], ``x``, ``y`` (the soundings), and per variable an array [n_depth, ny, nx] ([K, n_depth, ny, nx] for
+    ``class_probability``; [ny, nx] / [K, ny, nx] when ``depth`` selects one cell).  ``depth``: see ``depth_cells``.
+    ``max_distance`` (m) masks the pixels far from any sounding (``gridding``).  ``block`` columns go through the device at a time.
+    With ``out`` (a directory) the axes go to ``survey_volume.npz`` and each variable to ``survey_volume.<variable>.npy`` through a
+    memory map, and the returned arrays of the variables are those maps."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    files = [f for p in paths for f in line_products.containers(str(p))]
+    if not files:
+        raise ValueError("no results containers under %s" % " ".join(str(p) for p in paths))
+    if int(block) < 1:
+        raise ValueError("block must be positive")
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    lines = [(f,) + load_line(f, device=dev) for f in files]
+    d_edges = np.asarray(lines[0][4]["depth_edges"], dtype=np.float64)
+    for f, _, _, _, prod in lines[1:]:
+        if not np.array_equal(np.asarray(prod["depth_edges"], dtype=np.float64), d_edges):
+            raise ValueError("%s does not share the depth mesh of %s" % (f, lines[0][0]))
+    nz = d_edges.size - 1
+    cells = depth_cells(depth, d_edges)
+    single = depth is not None and not isinstance(depth, slice) and np.size(depth) == 1
+    x = np.concatenate([ln[1] for ln in lines])
+    y = np.concatenate([ln[2] for ln in lines])
+    elev = np.concatenate([ln[3] for ln in lines])
+    x_edges, y_edges = gridding.centred_mesh(x, y, dx, dy)
+    plan = gridding.SibsonPlan(x, y, x_edges, y_edges, max_distance=max_distance, device=dev, list_budget_bytes=list_budget_bytes)
+    try:
+        ny, nx = plan.ny, plan.nx
+        res = dict(x_edges=x_edges, y_edges=y_edges, depth_edges=d_edges[cells.start:cells.stop + 1], x=x, y=y,
+                   elevation=plan.apply(torch.as_tensor(elev).to(plan.device)).cpu().numpy(), count=plan.count.cpu().numpy(),
+                   nearest_distance=plan.distance.cpu().numpy(), variables=np.array(list(variables)))
+        if out is not None:
+            os.makedirs(str(out), exist_ok=True)
+            np.savez(os.path.join(str(out), AXES_FILE), **res)
+        ncell = cells.stop - cells.start
+        for name in variables:
+            cols, with_classes = _columns([(ln[0], ln[4]) for ln in lines], name, nz)
+            cols = cols[:, :, cells]                                                             # [N, K, cells]
+            K = cols.shape[1]
+            shape = ((K,) if with_classes else ()) + (() if single else (ncell,)) + (ny, nx)
+            if out is not None:
+                vol = np.lib.format.open_memmap(volume_path(out, name), mode="w+", dtype=np.float64, shape=shape)
+            else:
+                vol = np.empty(shape, dtype=np.float64)
+            flat = vol.reshape(K * ncell, ny, nx)
+            flat_cols = cols.reshape(cols.shape[0], K * ncell)
+            for c0 in range(0, K * ncell, int(block)):
+                c1 = min(K * ncell, c0 + int(block))
+                v = torch.as_tensor(np.ascontiguousarray(flat_cols[:, c0:c1])).to(plan.device)
+                flat[c0:c1] = plan.apply(v).cpu().numpy()
+            if out is not None:
+                vol.flush()
+            res[name] = vol
+    finally:
+        torch.cuda.synchronize(plan.device)
+        plan.close()
+    return res
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="python -m geobipy_amd.survey_volume",
+                                 description="Grid the line products of a directory of GeoBIPy results containers onto a regular x-y "
+                                             "raster by discrete Sibson interpolation, depth cell by depth cell: survey_volume.npz (axes, "
+                                             "elevation, count, nearest_distance) and survey_volume.<variable>.npy per variable.")
+    ap.add_argument("paths", nargs="+", help="directories holding <line>.h5 / <line>.results.npz, or such containers")
+    ap.add_argument("--dx", type=float, required=True, help="grid spacing in x (m)")
+    ap.add_argument("--dy", type=float, required=True, help="grid spacing in y (m)")
+    ap.add_argument("--variables", nargs="+", default=["mean"], metavar="NAME",
+                    help="line products to grid (default mean): mean median mode percentile_<p> credible_range entropy opacity "
+                         "interface_probability class_probability ...")
+    ap.add_argument("--mask", type=float, default=None, metavar="MAX_DISTANCE", help="mask pixels farther than this from any sounding (m)")
+    ap.add_argument("--depth", type=float, default=None, metavar="D", help="one map: the depth cell holding depth D (m)")
+    ap.add_argument("--depth-cells", type=int, nargs=2, default=None, metavar=("I0", "I1"), help="the depth cells I0 .. I1 (inclusive) only")
+    ap.add_argument("--block", type=int, default=256, help="columns per pass through the device (default 256)")
+    ap.add_argument("--device", default=None, help="torch device of the kernels (default cuda:0)")
+    ap.add_argument("--out", default=None, help="directory of the outputs (default: the first path's directory)")
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line's arguments, checked: positive spacings, mask and block, --depth or --depth-cells but not both, 0 <= I0 <= I1."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    for name, v in (("--dx", a.dx), ("--dy", a.dy)):
+        if not (v > 0.0 and np.isfinite(v)):
+            ap.error("%s must be positive and finite, got %g" % (name, v))
+    if a.mask is not None and not (a.mask > 0.0 and np.isfinite(a.mask)):
+        ap.error("--mask must be positive and finite")
+    if a.depth is not None and a.depth_cells is not None:
+        ap.error("--depth and --depth-cells exclude each other")
+    if a.depth is not None and not np.isfinite(a.depth):
+        ap.error("--depth must be finite")
+    if a.depth_cells is not None and not 0 <= a.depth_cells[0] <= a.depth_cells[1]:
+        ap.error("--depth-cells needs 0 <= I0 <= I1")
+    if a.block < 1:
+        ap.error("--block must be positive")
+    if len(set(a.variables)) != len(a.variables):
+        ap.error("--variables holds a name twice")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    depth = a.depth if a.depth is not None else (None if a.depth_cells is None else slice(a.depth_cells[0], a.depth_cells[1] + 1))
+    out = a.out if a.out is not None else (a.paths[0] if os.path.isdir(a.paths[0]) else os.path.dirname(os.path.abspath(a.paths[0])))
+    try:
+        r = from_lines(a.paths, a.dx, a.dy, variables=tuple(a.variables), max_distance=a.mask, depth=depth, block=a.block, device=a.device,
+                       out=out)
+    except ValueError as e:
+        print("survey_volume: %s" % e, file=sys.stderr)
+        return 1
+    print("%d soundings -> %d x %d pixels, %d depth cells: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
+                                                                  r["depth_edges"].size - 1, os.path.join(out, AXES_FILE)))
+    for name in a.variables:
+        print("  %s %r" % (volume_path(out, name), tuple(r[name].shape)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -625,6 +625,30 @@ gbp_status gbp_hitmap_classes(int B, int n_value, int n_depth, const int32_t *hi
 gbp_status gbp_runs_to_zlib(int n_rows, int64_t cells_per_row, const int64_t *ptr, const int32_t *start, const int32_t *value,
                             uint8_t *out, int64_t out_capacity, int64_t *out_ptr);
 
+/* Survey volumes: discrete Sibson (natural-neighbour) gridding of per-sounding columns onto a regular x-y raster (csrc/gbp_grid.h), the
+ * reference's method='sibson' (base/interpolation.py __sibson_2d_inner), split into a plan (geometry, once per grid) and an apply (once
+ * per block of columns).  px / py [N]: DEVICE arrays of the soundings' pixel coordinates ((x - x_edges[0]) / dx, (y - y_edges[0]) / dy).
+ * Pixel (i, j), 0 <= i < ny, 0 <= j < nx: index = the sounding nearest to the node (j, i) (lowest index on a tie),
+ * D = int(ceil(sqrt((j - px)^2 + (i - py)^2))) (capped at 2^30); it covers pixel (i_s, j_s) iff i - D <= i_s < i + D, j - D <= j_s < j + D
+ * and (i_s - i)^2 + (j_s - j)^2 <= D^2 + 0.25; n = the number of pixels covering a pixel.
+ * gbp_sibson_apply: out[c, i_s, j_s] = (sum of values[index[i, j], c] over the covering (i, j) in row-major order, from 0.0) / n
+ * (n = 0: NaN), NaN where the pixel's own D^2 + 0.25 > max_distance_px2 (+inf: no mask); values [N, C] row-major and out [C, ny, nx]
+ * on the plan's device, fp64.  The order of the sum is fixed, so results are bitwise reproducible.
+ * The lists hold sum(n) int32 entries.  Beyond list_budget_bytes (0: 4 GiB) the plan keeps room for one band of destination rows
+ * and gbp_sibson_apply rewrites it band by band (same results; such a plan serves one apply at a time).
+ * gbp_sibson_plan_create synchronises the stream.  gbp_sibson_plan_query copies index / distance / count ([ny, nx] int32 DEVICE arrays,
+ * each may be NULL) on the stream and fills the HOST array info[4] (may be NULL) = {sum(n), max(n), number of bands, device bytes held}.
+ * GBP_ERR_INVALID_ARG: N < 1, nx or ny < 1, nx * ny beyond int32, NULL pointers, a non-finite pixel coordinate, NaN max_distance_px2,
+ * a row of lists beyond the budget, C < 1, C * nx * ny or N * C out of range. */
+typedef struct gbp_sibson_plan gbp_sibson_plan;
+gbp_status gbp_sibson_plan_create(int N, const double *px, const double *py, int nx, int ny, double max_distance_px2, void *stream,
+                                  gbp_sibson_plan **out);
+gbp_status gbp_sibson_plan_create_ex(int N, const double *px, const double *py, int nx, int ny, double max_distance_px2,
+                                     int64_t list_budget_bytes, void *stream, gbp_sibson_plan **out);
+void gbp_sibson_plan_destroy(gbp_sibson_plan *plan);
+gbp_status gbp_sibson_plan_query(const gbp_sibson_plan *plan, int32_t *index, int32_t *distance, int32_t *count, int64_t *info, void *stream);
+gbp_status gbp_sibson_apply(const gbp_sibson_plan *plan, int C, const double *values, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
