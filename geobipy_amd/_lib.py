@@ -118,6 +118,9 @@ SIGNATURES = {
     "gbp_gauss_loglike_std": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "gbp_fdem_forward_loglike": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p]),
     "gbp_fdem_forward_loglike_ex": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
+    "gbp_gauss_prepare": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
+    "gbp_fdem_forward_loglike_prepared": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p]),
+    "gbp_fdem_forward_loglike_prepared_ex": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
     "gbp_fdem_sensitivity": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "gbp_fdem_sensitivity_ex": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "gbp_fdem_fm_dlogc": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p]),
@@ -137,6 +140,8 @@ SIGNATURES = {
     "gbp_debug_math": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_bench_time_forward_loglike": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p, c_int,
                                                                                         ctypes.POINTER(ctypes.c_float)]),
+    "gbp_bench_time_forward_loglike_prepared": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p, c_int,
+                                                                                                 ctypes.POINTER(ctypes.c_float)]),
 }
 
 _lib = None

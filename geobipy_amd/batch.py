@@ -9,6 +9,7 @@ HBM layout (all C-contiguous, fp64 unless noted):
     nlayers int32[B]      sigma[B, Lmax]   thk[B, Lmax]   height[B]
     data[B, 2F]           relative_error[B]               additive_error[B]
     predicted[B, 2F]      chi2[B]          logL[B]        (outputs, allocated once and reused)
+    weight[B, 2F]         c0[B]            (the likelihood's model-independent terms, prepared on first use: ``_prepared``)
 PyTorch is only the allocator / stream provider here; all arithmetic happens in libgeobipy_amd.so.
 """
 import numpy as np
@@ -87,6 +88,9 @@ class FdemBatch:
         self.chi2 = torch.empty(self.B, dtype=torch.float64, device=self.device)
         self._max_layers = None
         self.logL = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        self._prep = None           # (weight, c0) of the fused likelihood, see _prepared()
+        self._prep_key = self._prep_src = None
+        self.n_prepare_launches = 0
 
     def validate(self):
         """The reference's host asserts (FD/fdem1d.py:29, DP/FdemDataPoint.py:541) plus sigma, thk > 0, evaluated on the
@@ -123,17 +127,62 @@ class FdemBatch:
                                                out.data_ptr(), self.waves, _stream_ptr(self.device)))
         return out
 
-    def forward_loglike(self, want_pred=True):
+    def _prepared(self):
+        """(weight[B, 2F], c0[B]): what the likelihood needs of ``data``, ``relative_error`` and ``additive_error`` -- 1 / std
+        per channel and the sounding's ``-(Na/2) ln 2pi - sum ln std`` -- from one small launch (``gbp_gauss_prepare``) on first
+        use.  They are reused while the three attributes are the same tensors in the same state, and prepared again after any of
+        them was replaced or edited in place (torch's version counter; ``invalidate_prepared()`` after a write torch cannot
+        see, such as a native kernel's through ``data_ptr()``)."""
+        src = (self.data, self.relative_error, self.additive_error)
+        if any(t is None for t in src):
+            raise AssertionError(ValueError("data, relative_error and additive_error are needed for the likelihood"))
+        key = tuple((id(t), t.data_ptr(), t._version) for t in src)
+        if self._prep is None or key != self._prep_key:
+            if tuple(self.data.shape) != (self.B, 2 * self.F) or self.relative_error.numel() != self.B or self.additive_error.numel() != self.B:
+                raise AssertionError(ValueError("data must have shape [B, 2F], relative_error and additive_error B elements"))
+            if any(t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() for t in src):
+                raise AssertionError(ValueError("data and error levels must be contiguous fp64 tensors on the batch's device"))
+            if self._prep is None:
+                self._prep = (torch.empty((self.B, 2 * self.F), dtype=torch.float64, device=self.device),
+                              torch.empty(self.B, dtype=torch.float64, device=self.device))
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().gbp_gauss_prepare(self.B, 2 * self.F, self.data.data_ptr(), self.relative_error.data_ptr(),
+                                                         self.additive_error.data_ptr(), self._prep[0].data_ptr(),
+                                                         self._prep[1].data_ptr(), _stream_ptr(self.device)))
+            self.n_prepare_launches += 1
+            self._prep_key = key
+            self._prep_src = src     # keeps the tensors alive: their id() cannot be handed to another object meanwhile
+        return self._prep
+
+    def invalidate_prepared(self):
+        """Forget the prepared likelihood terms (the next ``forward_loglike`` prepares them again)."""
+        self._prep_key = None
+
+    def forward_loglike(self, want_pred=True, prepared=True):
         """Fused forward + chi^2 + log-likelihood: returns (chi2[B], logL[B]); ``self.predicted`` is
-        refreshed when ``want_pred``."""
-        assert self.data is not None and self.relative_error is not None and self.additive_error is not None, \
-            ValueError("data, relative_error and additive_error are needed for the likelihood")
+        refreshed when ``want_pred``.  The terms that depend on the data and error levels alone are prepared on the first call
+        (``_prepared``) and reused by the following ones -- the loop over proposal rounds on one batch; the values are those of
+        ``gbp_fdem_forward_loglike_ex``, bit for bit.  ``prepared=False`` launches that plain entry instead: for a batch that is
+        evaluated once (``find_best_halfspace``) preparing would be a second launch and a [B, 2F] array for nothing.
+        Under ``torch.cuda.graph`` capture the prepared arrays are baked into the graph: capture after the first call, and capture
+        again after data or error levels change (a replay cannot notice an edit)."""
         lib = _lib.load()
+        if not prepared:
+            assert self.data is not None and self.relative_error is not None and self.additive_error is not None, \
+                ValueError("data, relative_error and additive_error are needed for the likelihood")
+            with torch.cuda.device(self.device):
+                _lib.check(lib.gbp_fdem_forward_loglike_ex(
+                    self._h.ptr, self.B, self.Lmax, self.nlayers.data_ptr(), self.sigma.data_ptr(), self.thk.data_ptr(),
+                    self.height.data_ptr(), self.data.data_ptr(), self.relative_error.data_ptr(),
+                    self.additive_error.data_ptr(), self.predicted.data_ptr() if want_pred else None,
+                    self.chi2.data_ptr(), self.logL.data_ptr(), self.waves, _stream_ptr(self.device)))
+            return self.chi2, self.logL
+        weight, c0 = self._prepared()
         with torch.cuda.device(self.device):
-            _lib.check(lib.gbp_fdem_forward_loglike_ex(
+            _lib.check(lib.gbp_fdem_forward_loglike_prepared_ex(
                 self._h.ptr, self.B, self.Lmax, self.nlayers.data_ptr(), self.sigma.data_ptr(), self.thk.data_ptr(),
-                self.height.data_ptr(), self.data.data_ptr(), self.relative_error.data_ptr(),
-                self.additive_error.data_ptr(), self.predicted.data_ptr() if want_pred else None,
+                self.height.data_ptr(), self.data.data_ptr(), weight.data_ptr(), c0.data_ptr(),
+                self.predicted.data_ptr() if want_pred else None,
                 self.chi2.data_ptr(), self.logL.data_ptr(), self.waves, _stream_ptr(self.device)))
         return self.chi2, self.logL
 
@@ -212,7 +261,7 @@ class FdemBatch:
                           torch.zeros((n, 1), dtype=torch.float64), rep(self.height), data=rep(self.data),
                           relative_error=rep(self.relative_error), additive_error=rep(self.additive_error),
                           device=self.device)
-        chi2, _ = trial.forward_loglike(want_pred=False)
+        chi2, _ = trial.forward_loglike(want_pred=False, prepared=False)     # evaluated once: nothing to reuse
         chi2 = chi2.view(self.B, nSamples)
         best = torch.argmin(chi2, dim=1)          # first minimum, like numpy.argmin in the reference
         return c[best], chi2.gather(1, best[:, None])[:, 0]
@@ -220,12 +269,13 @@ class FdemBatch:
     def time_forward_loglike(self, reps, want_pred=False):
         """Average kernel time in ms over ``reps`` launches, measured with hipEvents on the launch stream."""
         import ctypes
+        weight, c0 = self._prepared()
         lib = _lib.load()
         ms = ctypes.c_float()
         with torch.cuda.device(self.device):
-            _lib.check(lib.gbp_bench_time_forward_loglike(
+            _lib.check(lib.gbp_bench_time_forward_loglike_prepared(
                 self._h.ptr, self.B, self.Lmax, self.nlayers.data_ptr(), self.sigma.data_ptr(), self.thk.data_ptr(),
-                self.height.data_ptr(), self.data.data_ptr(), self.relative_error.data_ptr(),
-                self.additive_error.data_ptr(), self.predicted.data_ptr() if want_pred else None,
+                self.height.data_ptr(), self.data.data_ptr(), weight.data_ptr(), c0.data_ptr(),
+                self.predicted.data_ptr() if want_pred else None,
                 self.chi2.data_ptr(), self.logL.data_ptr(), _stream_ptr(self.device), int(reps), ctypes.byref(ms)))
         return float(ms.value)

@@ -108,10 +108,10 @@ struct MathLds {
 };
 // SYNC = false: the caller's next workgroup barrier (the one behind the layer-thickness fill of forward_body / sens_body) is the tables'
 // too -- the sampler's physics kernel fills them first thing, while its chain's move and layer count are still on their way
-template <bool SYNC = true>
+template <bool SYNC = true, bool ONE_WAVE = false>   // ONE_WAVE: the workgroup is one wave (lane i fills entry i)
 __device__ __forceinline__ gbp::MathCtx math_setup(MathLds& lds)
 {
-    for (int i = threadIdx.x; i < 64; i += blockDim.x) {
+    for (int i = threadIdx.x; i < 64; i += ONE_WAVE ? 64 : (int)blockDim.x) {
         lds.exp2_64[i] = GBP_EXP2_64[i];
         lds.sincos_64[i].s = GBP_SINCOS_64[2 * i];
         lds.sincos_64[i].c = GBP_SINCOS_64[2 * i + 1];
@@ -347,9 +347,22 @@ __device__ __forceinline__ void forward_passes_1f(const gbp::MathCtx& M, const C
                                                   cplx* sh_part)
 {
     cplx prev = gbp::mk(0.0, 0.0);
+    // setup_layers for up to 64 layers (wave-uniform): lane k keeps sigma_k in a register for all passes and writes layer k's
+    // constants with one predicated statement -- no loop, no pointer stepping, no load of sigma in every pass; the same products
+    const bool lane_per_layer = L <= 64;
+    const double sig_k = (lane_per_layer && lane < L) ? sig[lane] : 0.0;
     for (int p = p0; p < p1; ++p) {
         const Channel cc = chan[p];
-        setup_layers(sh_lay, cc.wmu, sig, L, lane);
+        if (lane_per_layer) {
+            if (lane < L) {
+                const double b = cc.wmu * sig_k;
+                sh_lay[lane].b2 = b * b;
+                sh_lay[lane].bc = b * 0.70710678118654752440;
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            setup_layers(sh_lay, cc.wmu, sig, L, lane);
+        }
         const double hD = cc.hd0 - 2.0 * alt;
         const gbp::Point pt = gbp::load_point_u(pts, P, (unsigned)(64 * p + lane));
         cplx num, den;
@@ -393,6 +406,39 @@ __device__ __forceinline__ void loglike_wave(int N, const double* p, const doubl
     if (lane == 63) *logL = -(0.5 * na) * 1.8378770664093453 - 0.5 * mine - 0.5 * other;
 }
 
+// Sum of v by the tree wave_sum_pair runs on its first argument: lanes 60 - 63 return the bits lane 62 of wave_sum_pair(v, .) returns
+// (there the even lanes carry v's partial sums from the first exchange on and meet even lanes only; here every lane does).
+__device__ __forceinline__ double wave_sum_tail(double v)
+{
+    v += dpp_get<0xB1>(v);
+    v += dpp_get<0x4E>(v);
+    v += dpp_get<0x114>(v);
+    v += dpp_get<0x118>(v);
+    v = row_pair_sum<16>(v);
+    v = row_pair_sum<32>(v);
+    return v;
+}
+
+// loglike_wave with the terms that do not depend on the model prepared once per batch (k_gauss_prepare): w[i] = 1 / sqrt(var_i) of
+// the active channels and c0 = -(0.5 na) ln 2pi - 0.5 logdet, the value loglike_wave holds before it subtracts 0.5 chi^2.  A channel is
+// inactive by the rule of loglike_wave, read from the data themselves (the residual needs them anyway): its weight is never touched.
+__device__ __forceinline__ void loglike_wave_prepared(int N, const double* p, const double* __restrict__ obs,
+                                                      const double* __restrict__ w, const double* __restrict__ c0, int lane,
+                                                      double* chi2, double* logL)
+{
+    double s2 = 0.0;
+    for (int i = lane; i < N; i += 64) {
+        const double o = obs[i];
+        if (o > 0.0) {
+            const double r = (p[i] - o) * w[i];
+            s2 += r * r;
+        }
+    }
+    s2 = wave_sum_tail(s2);
+    if (lane == 62) *chi2 = s2;
+    if (lane == 63) *logL = *c0 - 0.5 * s2;
+}
+
 // Forward solve (+ chi^2 / logL) of ONE sounding by the calling workgroup: the body of k_fdem_forward, also called once per
 // iteration by the persistent sampler kernel (gbp_rjmcmc.h).  Every thread of the workgroup must call it (it contains
 // workgroup barriers); `sh_out` holds 2 * GBP_MAX_FREQ doubles, `sh_dyn` dyn_lds_bytes(nwaves, Lmax, passes) bytes:
@@ -401,25 +447,29 @@ __device__ __forceinline__ void loglike_wave(int N, const double* p, const doubl
 // does not depend on nw_use (see forward_passes).
 // ONE_PER_PASS (the plain forward kernel): the table set's frequencies are one pass each when `one_per_pass` (BinDesc) is set, and
 // forward_passes_1f runs them; the sampler's kernels instantiate the general path only.
-template <bool LIKE, bool ONE_PER_PASS = false>
+// PREPARED (k_fdem_forward_prepared): the likelihood from prepared terms, `rel_b` / `add_b` unused, `w_row`, `c0_b` instead.
+// ONE_WAVE (its one-wave-per-sounding instance): the workgroup IS one wave, known at compile time.
+template <bool LIKE, bool ONE_PER_PASS = false, bool PREPARED = false, bool ONE_WAVE = false>
 __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_out, unsigned char* sh_dyn,
                                              const Channel* __restrict__ chan, const double* __restrict__ pts, int npts_total,
                                              int F, int Lmax, int L, const double* __restrict__ sig,
                                              const double* __restrict__ th, double alt, const double* __restrict__ obs_row,
                                              double rel_b, double add_b, double* __restrict__ pred_row, double* chi2_b,
                                              double* logL_b, double sigma_direct, int nw_use, double row_scale = 1.0,
-                                             bool one_per_pass = false)
+                                             bool one_per_pass = false, const double* __restrict__ w_row = nullptr,
+                                             const double* __restrict__ c0_b = nullptr)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nwaves = nw_use;
+    const int wave = ONE_WAVE ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwaves = ONE_WAVE ? 1 : nw_use;
+    const unsigned tid = ONE_WAVE ? (unsigned)lane : threadIdx.x, nth = ONE_WAVE ? 64u : blockDim.x;
     const int npass = (npts_total + 63) >> 6;
     // every layer conductive enough for the select-free complex sqrt (all but displacement-current dominated models)
     const bool direct = wave_min_sigma(sig, L, lane) >= sigma_direct;   // workgroup-uniform
     gbp::LayerK* sh_lay = reinterpret_cast<gbp::LayerK*>(sh_dyn) + (size_t)wave * 2 * Lmax;
     cplx* sh_part = reinterpret_cast<cplx*>(sh_dyn + (size_t)nwaves * 2 * Lmax * sizeof(gbp::LayerK));
     double* sh_t2 = reinterpret_cast<double*>(sh_part + (size_t)2 * npass);
-    for (int k = threadIdx.x; k < L - 1; k += blockDim.x) sh_t2[k] = -2.0 * th[k];
+    for (int k = tid; k < L - 1; k += nth) sh_t2[k] = -2.0 * th[k];
     __syncthreads();
 
     if (wave < nwaves) {
@@ -440,7 +490,7 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
     __syncthreads();
 
     // out_f = 1e6 * scale * (H - H0) / H0 = g_f * sum of the frequency's per-pass partials in pass order
-    for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    for (int f = tid; f < F; f += nth) {
         const Channel ch = chan[f];
         double sr = 0.0, si = 0.0;
         for (int p = ch.off >> 6; 64 * p < ch.off + ch.npts; ++p) {
@@ -454,8 +504,13 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
 
     const int N = 2 * F;
     if (pred_row != nullptr)
-        for (int i = threadIdx.x; i < N; i += blockDim.x) pred_row[i] = sh_out[i];
-    if (LIKE && wave == 0) loglike_wave(N, sh_out, obs_row, rel_b, add_b, lane, chi2_b, logL_b);
+        for (int i = tid; i < N; i += nth) pred_row[i] = sh_out[i];
+    if (LIKE && wave == 0) {
+        if (PREPARED)
+            loglike_wave_prepared(N, sh_out, obs_row, w_row, c0_b, lane, chi2_b, logL_b);
+        else
+            loglike_wave(N, sh_out, obs_row, rel_b, add_b, lane, chi2_b, logL_b);
+    }
 }
 
 template <bool LIKE, bool SCALED = false>   // SCALED: the rows carry a distance scale (gbp_fdem_forward_rows_scaled); the plain kernels do not pay for it (4 VGPRs, 36 B of scratch)
@@ -502,6 +557,56 @@ __global__ __launch_bounds__(1024) void k_fdem_forward(const Channel* __restrict
                                 height[b], LIKE ? obs + (size_t)b * 2 * F : nullptr, LIKE ? rel[b] : 0.0, LIKE ? add[b] : 0.0,
                                 pred != nullptr ? pred + (size_t)b * 2 * F : nullptr, LIKE ? chi2 + b : nullptr, LIKE ? logL + b : nullptr,
                                 sigma_direct, (int)(blockDim.x >> 6), (SCALED && row_scale != nullptr) ? row_scale[b] : 1.0, one_per_pass);
+}
+
+// k_fdem_forward<true> with the likelihood's model-independent terms prepared (gbp_gauss_prepare): `weight`[B, 2F] and `c0`[B] in
+// place of rel / add, no per-row table set and no distance scale (the likelihood entries have neither).  ONE_WAVE is the launch with
+// one wave per sounding (pick_waves from 8 192 soundings up): the workgroup size is a compile-time 64.
+template <bool ONE_WAVE>
+__global__ __launch_bounds__(ONE_WAVE ? 64 : 1024) void k_fdem_forward_prepared(const Channel* __restrict__ chan,
+                                                                                const double* __restrict__ pts, int npts_total, int F,
+                                                                                int Lmax, const int* __restrict__ nlayers,
+                                                                                const double* __restrict__ sigma,
+                                                                                const double* __restrict__ thk,
+                                                                                const double* __restrict__ height,
+                                                                                const double* __restrict__ obs,
+                                                                                const double* __restrict__ weight,
+                                                                                const double* __restrict__ c0, double* __restrict__ pred,
+                                                                                double* __restrict__ chi2, double* __restrict__ logL,
+                                                                                double sigma_direct, const BinDesc* __restrict__ bins,
+                                                                                int bin0, int n_bins, const Channel* __restrict__ bin_chan,
+                                                                                const double* __restrict__ bin_pts)
+{
+    __shared__ double sh_out[2 * GBP_MAX_FREQ];
+    __shared__ MathLds sh_math;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
+    const int b = blockIdx.x;
+    const int tid = ONE_WAVE ? (int)(threadIdx.x & 63) : (int)threadIdx.x, nth = ONE_WAVE ? 64 : (int)blockDim.x;
+    bool one_per_pass = false;
+    if (bins != nullptr) {                                  // this sounding's abscissa window (see k_fdem_forward)
+        const int slot = table_slot(height[b], 0, bin0, n_bins);
+        if (slot >= 0) {
+            const BinDesc d = bins[slot];
+            chan = bin_chan + d.chan_off;
+            pts = bin_pts + d.pts_off;
+            npts_total = d.npts_total;
+            one_per_pass = d.one_per_pass != 0;
+        }
+    }
+    const int L = nlayers[b];
+    if (L <= 0) return;   // as k_fdem_forward: a skipped sounding's outputs are not written, a bad row's are NaN
+    if (L > Lmax) {
+        const double qnan = __builtin_nan("");
+        if (pred != nullptr)
+            for (int i = tid; i < 2 * F; i += nth) pred[(size_t)b * 2 * F + i] = qnan;
+        if (tid == 0) { chi2[b] = qnan; logL[b] = qnan; }
+        return;
+    }
+    const gbp::MathCtx M = math_setup<true, ONE_WAVE>(sh_math);
+    forward_body<true, true, true, ONE_WAVE>(M, sh_out, sh_dyn, chan, pts, npts_total, F, Lmax, L, sigma + (size_t)b * Lmax,
+                                             thk + (size_t)b * Lmax, height[b], obs + (size_t)b * 2 * F, 0.0, 0.0,
+                                             pred != nullptr ? pred + (size_t)b * 2 * F : nullptr, chi2 + b, logL + b, sigma_direct,
+                                             ONE_WAVE ? 1 : (int)(blockDim.x >> 6), 1.0, one_per_pass, weight + (size_t)b * 2 * F, c0 + b);
 }
 
 // Jacobian (+ prediction) of ONE sounding by the first `nw_use` waves of the calling workgroup: the body of k_fdem_sens, also
@@ -679,6 +784,37 @@ __global__ void k_gauss_loglike(int B, int N, const double* __restrict__ pred, c
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= B) return;
     loglike_wave(N, pred + (size_t)b * N, obs + (size_t)b * N, rel[b], add[b], lane, chi2 + b, logL + b);
+}
+
+// The model-independent terms of loglike_wave, once per batch of data and error levels (gbp_gauss_prepare): per channel the factor
+// 1 / sqrt(var) by loglike_wave's own expression (0 for an inactive channel, which loglike_wave_prepared never reads), per sounding
+// c0 = -(0.5 na) ln 2pi - 0.5 logdet with na and logdet summed by loglike_wave's trees (wave_sum; lane 63 of wave_sum_pair).
+__global__ void k_gauss_prepare(int B, int N, const double* __restrict__ obs, const double* __restrict__ rel,
+                                const double* __restrict__ add, double* __restrict__ weight, double* __restrict__ c0)
+{
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const double* o_row = obs + (size_t)b * N;
+    double* w_row = weight + (size_t)b * N;
+    const double rel_b = rel[b], add_b = add[b];
+    double logdet = 0.0, na = 0.0;
+    for (int i = lane; i < N; i += 64) {
+        const double o = o_row[i];
+        const bool active = o > 0.0;
+        const double ro = rel_b * o;
+        const double var = ro * ro + add_b * add_b;
+        double w = 0.0;
+        if (active) {
+            w = 1.0 / sqrt(var);
+            logdet += log(var);
+            na += 1.0;
+        }
+        w_row[i] = w;
+    }
+    const double mine = wave_sum_pair(0.0, logdet, lane);
+    na = wave_sum(na);
+    if (lane == 63) c0[b] = -(0.5 * na) * 1.8378770664093453 - 0.5 * mine;
 }
 
 // Per-sounding input / output status word (SURVEY 8b "Errors": validate, flag per sounding, never abort the batch).
@@ -1145,6 +1281,47 @@ gbp_status gbp_fdem_forward_loglike_ex(const gbp_fdem_system* sys, int B, int Lm
     return GBP_OK;
 }
 
+gbp_status gbp_gauss_prepare(int B, int N, const double* obs, const double* rel, const double* add, double* weight, double* c0,
+                             void* stream)
+{
+    if (B < 0 || N < 1) return fail(GBP_ERR_INVALID_ARG, "B must be >= 0 and N >= 1%s");
+    if (B == 0) return GBP_OK;
+    if (!obs || !rel || !add || !weight || !c0) return fail(GBP_ERR_INVALID_ARG, "NULL device pointer%s");
+    const int wpb = 4;
+    hipLaunchKernelGGL(k_gauss_prepare, dim3((B + wpb - 1) / wpb), dim3(64 * wpb), 0, (hipStream_t)stream, B, N, obs, rel, add,
+                       weight, c0);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+gbp_status gbp_fdem_forward_loglike_prepared(const gbp_fdem_system* sys, int B, int Lmax, const int32_t* nlayers,
+                                             const double* sigma, const double* thk, const double* height,
+                                             const double* obs, const double* weight, const double* c0, double* pred,
+                                             double* chi2, double* logL, void* stream)
+{
+    return gbp_fdem_forward_loglike_prepared_ex(sys, B, Lmax, nlayers, sigma, thk, height, obs, weight, c0, pred, chi2, logL, 0, stream);
+}
+
+gbp_status gbp_fdem_forward_loglike_prepared_ex(const gbp_fdem_system* sys, int B, int Lmax, const int32_t* nlayers,
+                                                const double* sigma, const double* thk, const double* height,
+                                                const double* obs, const double* weight, const double* c0, double* pred,
+                                                double* chi2, double* logL, int waves, void* stream)
+{
+    gbp_status st = check_batch(sys, B, Lmax, nlayers, sigma, thk, height);
+    if (st != GBP_OK) return st;
+    if (waves < 0 || waves > 16) return fail(GBP_ERR_INVALID_ARG, "waves must be in [0, 16]%s");
+    if (B == 0) return GBP_OK;
+    if (!obs || !weight || !c0 || !chi2 || !logL) return fail(GBP_ERR_INVALID_ARG, "NULL device pointer%s");
+    const int passes = (sys->t.npts + 63) / 64;
+    const int nw = pick_waves(B, sys->t.nF, Lmax, passes, waves);
+    auto kernel = nw == 1 ? k_fdem_forward_prepared<true> : k_fdem_forward_prepared<false>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * nw), dyn_lds_bytes(nw, Lmax, passes), (hipStream_t)stream, sys->d_chan, sys->d_pts,
+                       sys->t.npts, sys->t.nF, Lmax, nlayers, sigma, thk, height, obs, weight, c0, pred, chi2, logL, sys->sigma_direct,
+                       sys->d_bins, sys->bin0, sys->n_bins, sys->d_bin_chan, sys->d_bin_pts);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 gbp_status gbp_fdem_validate(int B, int Lmax, int N, const int32_t* nlayers, const double* sigma, const double* thk,
                              const double* height, const double* pred, int32_t* status, void* stream)
 {
@@ -1157,28 +1334,46 @@ gbp_status gbp_fdem_validate(int B, int Lmax, int N, const int32_t* nlayers, con
     return GBP_OK;
 }
 
-gbp_status gbp_bench_time_forward_loglike(const gbp_fdem_system* sys, int B, int Lmax, const int32_t* nlayers,
-                                         const double* sigma, const double* thk, const double* height,
-                                         const double* obs, const double* rel, const double* add, double* pred,
-                                         double* chi2, double* logL, void* stream, int reps, float* avg_ms)
+// average time of `reps` launches of `launch` on `stream`, by two events around them
+extern "C++" template <class Launch>
+static gbp_status time_launches(void* stream, int reps, float* avg_ms, Launch launch)
 {
     if (!avg_ms || reps < 1) return fail(GBP_ERR_INVALID_ARG, "avg_ms NULL or reps < 1%s");
     hipEvent_t e0, e1;
     GBP_HIP(hipEventCreate(&e0));
     GBP_HIP(hipEventCreate(&e1));
-    GBP_HIP(hipEventRecord(e0, (hipStream_t)stream));
     gbp_status st = GBP_OK;
-    for (int i = 0; i < reps && st == GBP_OK; ++i)
-        st = gbp_fdem_forward_loglike(sys, B, Lmax, nlayers, sigma, thk, height, obs, rel, add, pred, chi2, logL,
-                                      stream);
-    GBP_HIP(hipEventRecord(e1, (hipStream_t)stream));
-    GBP_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
-    GBP_HIP(hipEventElapsedTime(&ms, e0, e1));
+    hipError_t e = hipEventRecord(e0, (hipStream_t)stream);
+    for (int i = 0; i < reps && st == GBP_OK && e == hipSuccess; ++i) st = launch();
+    if (e == hipSuccess) e = hipEventRecord(e1, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    if (e != hipSuccess) return fail(GBP_ERR_HIP, "timing events: %s", hipGetErrorString(e));
     *avg_ms = ms / reps;
     return st;
+}
+
+gbp_status gbp_bench_time_forward_loglike(const gbp_fdem_system* sys, int B, int Lmax, const int32_t* nlayers,
+                                         const double* sigma, const double* thk, const double* height,
+                                         const double* obs, const double* rel, const double* add, double* pred,
+                                         double* chi2, double* logL, void* stream, int reps, float* avg_ms)
+{
+    return time_launches(stream, reps, avg_ms, [&] {
+        return gbp_fdem_forward_loglike(sys, B, Lmax, nlayers, sigma, thk, height, obs, rel, add, pred, chi2, logL, stream);
+    });
+}
+
+gbp_status gbp_bench_time_forward_loglike_prepared(const gbp_fdem_system* sys, int B, int Lmax, const int32_t* nlayers,
+                                                  const double* sigma, const double* thk, const double* height,
+                                                  const double* obs, const double* weight, const double* c0, double* pred,
+                                                  double* chi2, double* logL, void* stream, int reps, float* avg_ms)
+{
+    return time_launches(stream, reps, avg_ms, [&] {
+        return gbp_fdem_forward_loglike_prepared(sys, B, Lmax, nlayers, sigma, thk, height, obs, weight, c0, pred, chi2, logL, stream);
+    });
 }
 
 gbp_status gbp_debug_math(int op, int n, const double* x, const double* y, double* out0, double* out1, void* stream)

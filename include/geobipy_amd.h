@@ -213,6 +213,27 @@ gbp_status gbp_fdem_forward_loglike_ex(const gbp_fdem_system *sys, int B, int Lm
                                        double *pred, double *chi2, double *logL, int waves, void *stream);
 
 /*
+ * The same launch with the likelihood's model-independent terms prepared once, for callers that evaluate many models against
+ * data and error levels that stay put (proposal rounds over one batch); a single evaluation is cheaper through the plain entry.
+ *   gbp_gauss_prepare: obs [dev] f64[B, N], rel, add [dev] f64[B] -> weight [dev] f64[B, N] out (1 / std_i of the active
+ *   channels, 0 elsewhere) and c0 [dev] f64[B] out (-(Na/2) ln 2pi - sum_active ln std).  Prepare again whenever obs, rel or add change.
+ *   gbp_fdem_forward_loglike_prepared[_ex]: as gbp_fdem_forward_loglike[_ex] with weight, c0 in place of rel, add; chi2, logL and
+ *   pred carry the same bits (logL = c0 - chi2/2, every sum in the order of the plain entry).
+ */
+gbp_status gbp_gauss_prepare(int B, int N, const double *obs, const double *rel, const double *add, double *weight,
+                             double *c0, void *stream);
+
+gbp_status gbp_fdem_forward_loglike_prepared(const gbp_fdem_system *sys, int B, int Lmax, const int32_t *nlayers,
+                                             const double *sigma, const double *thk, const double *height,
+                                             const double *obs, const double *weight, const double *c0,
+                                             double *pred, double *chi2, double *logL, void *stream);
+
+gbp_status gbp_fdem_forward_loglike_prepared_ex(const gbp_fdem_system *sys, int B, int Lmax, const int32_t *nlayers,
+                                                const double *sigma, const double *thk, const double *height,
+                                                const double *obs, const double *weight, const double *c0,
+                                                double *pred, double *chi2, double *logL, int waves, void *stream);
+
+/*
  * Batched Jacobian d pred / d ln(sigma_k) (ppm).  Replaces FdemDataPoint.sensitivity -> fdem1dsen ->
  * nbFdem1dsen.   J [dev] f64[B, 2*nF, Lmax] out (columns >= nlayers[b] are set to 0);
  * rows [0,nF) real part, [nF,2nF) imaginary part (FdemDataPoint.py:553-557).
@@ -275,6 +296,12 @@ gbp_status gbp_bench_time_forward_loglike(const gbp_fdem_system *sys, int B, int
                                          const double *obs, const double *rel, const double *add,
                                          double *pred, double *chi2, double *logL, void *stream,
                                          int reps, float *avg_ms);
+
+gbp_status gbp_bench_time_forward_loglike_prepared(const gbp_fdem_system *sys, int B, int Lmax, const int32_t *nlayers,
+                                                  const double *sigma, const double *thk, const double *height,
+                                                  const double *obs, const double *weight, const double *c0,
+                                                  double *pred, double *chi2, double *logL, void *stream,
+                                                  int reps, float *avg_ms);
 
 /* Test hook: element-wise evaluation of the device math kernels (geobipy_amd/csrc/gbp_math.h) on
  * [dev] arrays of length n.  op: 0 exp_neg(x), 1 sincos(x) -> (sin, cos), 2 csqrt(x + i y) -> (re, im),

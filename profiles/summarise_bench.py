@@ -4,12 +4,12 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r2"
 rnd = sys.argv[2] if len(sys.argv) > 2 else tag
 src = os.path.join(R, "gpurun_out", "prof", tag)
-KERNEL = "k_fdem_forward<true"          # (round 4: <true, false> -- the row-scale template argument)
+KERNELS = ("k_fdem_forward_prepared<true", "k_fdem_forward<true")   # the headline's launch: the prepared kernel from r8 on, up to r7 the plain one
 B, L, F = 65536, 8, 10
 
 
 def rows(path):
-    return [r for r in csv.DictReader(open(path)) if KERNEL in r["Kernel_Name"]]
+    return [r for r in csv.DictReader(open(path)) if any(k in r["Kernel_Name"] for k in KERNELS)]
 
 
 trace = rows(os.path.join(src, "kt", "kt_kernel_trace.csv"))
@@ -32,7 +32,7 @@ label = ("label unknown (bench line without config.abscissa_points_*)" if pts is
          "default path: per-sounding abscissa window, eps = %g ppm, %.1f of %d abscissa points per sounding (batch mean)" % (cfg.get("hankel_eps_ppm"), pts, pts_all))
 out = {
     "command": "python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-windowed --no-rjmcmc --no-extras (under rocprofv3, profiles/run_profile.sh; reduced by profiles/summarise_bench.py)",
-    "kernel": KERNEL,
+    "kernel": sorted({r["Kernel_Name"] for r in trace})[0] if trace else KERNELS[0],
     "workload": "65536 soundings x 10 zz freq x 8 layers, 1 GPU (%s)" % label,
     "kernel_trace": {"calls": len(dur), "avg_ns": sum(dur) / len(dur), "min_ns": min(dur), "max_ns": max(dur),
                      "timed_region_avg_ns": sum(timed) / len(timed),
