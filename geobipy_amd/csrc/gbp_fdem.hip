@@ -1788,3 +1788,34 @@ extern "C" gbp_status gbp_sibson_apply(const gbp_sibson_plan* p, int C, const do
     }
     return GBP_OK;
 }
+
+#include "gbp_elev.h"
+
+// Elevation slices (gbp_elev.h): rows on the depth axis onto levels or cells of an elevation axis, one launch per call.
+extern "C" gbp_status gbp_elevation_resample(int mode, int R, int K, int n_depth, const double* values, const double* surface,
+                                             const double* depth_edges, int E, const double* axis, int c0, int c1, double* out, void* stream)
+{
+    if (mode != GBP_ELEVATION_LEVELS && mode != GBP_ELEVATION_INTERVALS)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: mode must be GBP_ELEVATION_LEVELS or GBP_ELEVATION_INTERVALS%s");
+    if (R < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: R must be >= 1%s");
+    if (K < 1 || R % K != 0) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: K must be >= 1 and divide R%s");
+    if (n_depth < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: n_depth must be >= 1%s");
+    if (n_depth > elev::MAX_DEPTH_CELLS) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: n_depth out of range (at most 8191 depth cells)%s");
+    if (E < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: E must be >= 1%s");
+    if (c0 < 0 || c1 > E || c0 >= c1) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: the column window needs 0 <= c0 < c1 <= E%s");
+    if (!values || !surface || !depth_edges || !axis || !out) return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: NULL pointer%s");
+    const int ncols = c1 - c0;
+    const int64_t lim = 0x7fffffffffffffffLL / 8;
+    const int cblocks = (ncols + elev::COLS - 1) / elev::COLS;
+    if (cblocks > 65535 || (int64_t)R > lim / n_depth || (int64_t)R > lim / ncols)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_elevation_resample: R * n_depth or R * columns out of range%s");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 blocks((unsigned)(((int64_t)R + elev::ROWS - 1) / elev::ROWS), (unsigned)cblocks);
+    const size_t lds = (size_t)(n_depth + 1) * sizeof(double);
+    if (mode == GBP_ELEVATION_INTERVALS)
+        hipLaunchKernelGGL(elev::k_elevation_resample<true>, blocks, dim3(256), lds, st, R, K, n_depth, values, surface, depth_edges, axis, c0, ncols, out);
+    else
+        hipLaunchKernelGGL(elev::k_elevation_resample<false>, blocks, dim3(256), lds, st, R, K, n_depth, values, surface, depth_edges, axis, c0, ncols, out);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}

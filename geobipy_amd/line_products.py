@@ -12,10 +12,11 @@ below finish on [N, n_depth] arrays: they run on whichever device their tensors 
 Everything is log10 conductivity (S/m) except entropy (bits), opacity and probabilities (0 - 1) and the depths (m).
 
     python -m geobipy_amd.line_products <container or directory> [--credible 90] [--doi 67] [--percentiles 5 50 95]
-                                        [--class-means M1 M2 ... --class-scales S1 S2 ...]
+                                        [--class-means M1 M2 ... --class-scales S1 S2 ...] [--elevation-axis DZ [TOP BOTTOM]]
 
 writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.  The class means and scales (standard deviations)
-are in log10 S/m; they come together, 1 to 16 of each.
+are in log10 S/m; they come together, 1 to 16 of each.  With ``--elevation-axis`` the per-depth-cell products also go onto a regular
+elevation axis (``on_elevation``, ``elevation.regular_axis``), written to ``<line>.products_elevation.npz`` beside the first file.
 """
 import argparse
 import glob
@@ -243,6 +244,46 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     return out
 
 
+def on_elevation(products, surface, edges=None, levels=None, device=None):
+    """The per-depth-cell entries of ``products`` (``from_results``) on an elevation axis (``elevation.resample``, on ``device``, default
+    cuda:0): every entry shaped [N, n_depth] or [N, K, n_depth] over ``products['depth_edges']`` becomes [N, E] / [N, K, E] -- the mean
+    over each cell of the ascending ``edges`` [E + 1], or the value at each of ``levels`` [E]; exactly one of the two.  ``surface`` [N]:
+    the soundings' surface elevation (the container's /data/elevation).  Integer entries (class indices: ``highest_marginal``) are never
+    averaged: with ``edges`` they are taken at the centre of each cell.  Everything else (the per-sounding and per-line entries, the
+    depth axes, ``interface_probability`` where it has a depth mesh of its own) passes through, and the result also carries
+    ``elevation_edges`` (and ``elevation_centres``) or ``elevation_levels``, and ``surface``."""
+    from . import _lib, elevation
+    mode, axis, _ = elevation.check_axis(levels=levels, edges=edges)
+    if "depth_edges" not in products:
+        raise ValueError("the products hold no depth_edges")
+    d_edges = elevation.check_depth_edges(products["depth_edges"])
+    nz = d_edges.size - 1
+    s = np.asarray(surface, dtype=np.float64).reshape(-1)
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    if dev.type != "cuda":
+        raise _lib.NativeLibraryError("line_products.on_elevation runs on the device (gbp_elevation_resample); there is no host fallback")
+    centres = 0.5 * (axis[1:] + axis[:-1]) if mode == elevation.INTERVALS else None
+    out = {}
+    for k, v in products.items():
+        a = np.asarray(v)
+        own_mesh = k == "interface_probability" and not np.array_equal(np.asarray(products.get("interface_depth_edges", d_edges)), d_edges)
+        if a.ndim not in (2, 3) or a.shape[-1] != nz or a.shape[0] != s.size or a.size == 0 or own_mesh or a.dtype.kind not in "fiub":
+            out[k] = v
+            continue
+        t = torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+        if a.dtype.kind == "f":
+            r = elevation.resample(t.to(torch.float64), s, d_edges, levels=levels, edges=edges)
+        else:
+            r = elevation.resample(t, s, d_edges, levels=axis if centres is None else centres)
+        out[k] = r.cpu().numpy()
+    if centres is None:
+        out["elevation_levels"] = axis
+    else:
+        out["elevation_edges"], out["elevation_centres"] = axis, centres
+    out["surface"] = s
+    return out
+
+
 def save(products, path):
     """Write ``products`` ({name: array}) to ``path`` (``<line>.products.npz``) with np.savez_compressed; returns the path."""
     np.savez_compressed(path, **{k: np.asarray(v) for k, v in products.items()})
@@ -258,6 +299,11 @@ def output_path(container):
         if container.endswith(s):
             return container[:-len(s)] + ".products.npz"
     return container + ".products.npz"
+
+
+def elevation_output_path(container):
+    """``<line>.products_elevation.npz`` next to the container."""
+    return output_path(container)[:-len(".products.npz")] + ".products_elevation.npz"
 
 
 def containers(path):
@@ -285,6 +331,10 @@ def parser():
                     help="means of 1 to 16 classes (lithologies) in log10 S/m; with --class-scales")
     ap.add_argument("--class-scales", type=float, nargs="+", default=None, metavar="S",
                     help="standard deviations of the classes in log10 S/m, one per mean, positive")
+    ap.add_argument("--elevation-axis", type=float, nargs="+", default=None, metavar="DZ [TOP BOTTOM]",
+                    help="also write <line>.products_elevation.npz: the per-depth-cell products averaged over the cells of a regular "
+                         "elevation axis of DZ m, from BOTTOM to TOP (default: everything the line's soundings reach), snapped outward "
+                         "to multiples of DZ")
     ap.add_argument("--block", type=int, default=4096, help="soundings per upload (default 4096)")
     ap.add_argument("--device", default=None, help="torch device of the kernel (default cuda:0)")
     return ap
@@ -292,7 +342,7 @@ def parser():
 
 def parse_args(argv=None):
     """The command line's arguments, checked: percents in (0, 100), at most 8 distinct quantiles per pass, a positive block, class means
-    and scales together, 1 to 16 of each, equal counts, positive scales."""
+    and scales together, 1 to 16 of each, equal counts, positive scales, --elevation-axis DZ or DZ TOP BOTTOM with DZ > 0 and BOTTOM < TOP."""
     ap = parser()
     a = ap.parse_args(argv)
     for name, v in (("--credible", a.credible), ("--doi", a.doi)):
@@ -313,7 +363,24 @@ def parse_args(argv=None):
             check_classes(a.class_means, a.class_scales)
         except ValueError as e:
             ap.error("--class-means / --class-scales: " + str(e))
+    if a.elevation_axis is not None:
+        try:
+            elevation_axis_arguments(a.elevation_axis)
+        except ValueError as e:
+            ap.error("--elevation-axis: " + str(e))
     return a
+
+
+def elevation_axis_arguments(values):
+    """(dz, top, bottom) of the command lines' ``--elevation-axis DZ [TOP BOTTOM]`` (top and bottom None where left out), checked."""
+    v = [float(x) for x in values]
+    if len(v) not in (1, 3):
+        raise ValueError("DZ, or DZ TOP BOTTOM")
+    if not all(np.isfinite(v)) or not v[0] > 0.0:
+        raise ValueError("DZ must be positive, everything finite")
+    if len(v) == 3 and not v[2] < v[1]:
+        raise ValueError("BOTTOM must lie below TOP")
+    return (v[0], None, None) if len(v) == 1 else (v[0], v[1], v[2])
 
 
 def main(argv=None):
@@ -328,6 +395,21 @@ def main(argv=None):
                            classes=classes)
         dst = save(out, output_path(f))
         print("%s -> %s (%d soundings)" % (f, dst, out["mean"].shape[0]))
+        if a.elevation_axis is not None:
+            from . import elevation, hdf
+            arrays, _ = hdf.load_results(f)
+            surface = _key(arrays, "/data/elevation/data", "/data/elevation")
+            if surface is None or np.asarray(surface).size != out["mean"].shape[0]:
+                print("%s holds no /data/elevation to hang an elevation axis on" % f, file=sys.stderr)
+                return 1
+            dz, top, bottom = elevation_axis_arguments(a.elevation_axis)
+            try:
+                edges = elevation.regular_axis(surface, out["depth_edges"], dz, top=top, bottom=bottom)
+                dst = save(on_elevation(out, surface, edges=edges, device=a.device), elevation_output_path(f))
+            except ValueError as e:
+                print("line_products: %s: %s" % (f, e), file=sys.stderr)
+                return 1
+            print("%s -> %s (%d elevation cells of %g m, %g .. %g m)" % (f, dst, edges.size - 1, dz, edges[0], edges[-1]))
     return 0
 
 

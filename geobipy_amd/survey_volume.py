@@ -11,20 +11,33 @@ soundings' elevation through the same plan -- the reference's ``mesh3d`` drapes 
 method (minimum curvature); this one is the Sibson surface.
 
     python -m geobipy_amd.survey_volume <directory> --dx DX --dy DY [--variables mean percentile_5 ...] [--mask MAX_DISTANCE]
-                                        [--depth D | --depth-cells I0 I1] [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
+                                        [--depth D | --depth-cells I0 I1 | --elevation-axis DZ [TOP BOTTOM] | --elevation E]
+                                        [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
 
 reads the directory's line containers and their ``<line>.products.npz`` (computed where absent: ``line_products.from_results``) and writes
 ``survey_volume.npz`` (x_edges, y_edges, depth_edges, elevation, count, nearest_distance, the variables' names) and one
 ``survey_volume.<variable>.npy`` [n_depth, ny, nx] per variable, filled column block by column block through a memory map: a volume is
 n_depth ny nx 8 bytes (440 x 1 000 x 1 000: 3.5 GB) and is never held in memory whole.
+
+Those volumes hang under the terrain: index 0 is the first depth cell below ``elevation`` [ny, nx], another horizon at every pixel.  With
+``--elevation-axis`` (``from_lines(elevation_edges=...)``) every sounding's column is first resampled from its depth cells onto ONE
+elevation axis (``elevation.resample``, csrc/gbp_elev.h: the reference's ``Inference2D.elevationSlice``), block of elevation cells by
+block on the device, and then gridded by the same plan: ``survey_volume.<variable>.npy`` is [n_elev, ny, nx] with index 0 the LOWEST
+cell and a regular z axis (``elevation_edges`` in ``survey_volume.npz``), a voxel model as it stands.  ``--elevation E`` is one
+horizontal slice [ny, nx] at that elevation.  The reference slices first and grids afterwards, and so does this: a sounding that is
+outside its own mesh at a level (above its surface, below its last depth edge) is NaN there, NaN propagates through the Sibson sum, and
+so a pixel is NaN at a level wherever ANY sounding that contributes to it is outside its mesh -- the volume's top follows the terrain
+from below and its bottom the deepest common reach.
 """
 import argparse
+import functools
 import os
 import sys
 
 import numpy as np
 import torch
 
+from . import elevation as elevation_axis
 from . import gridding, line_products
 
 AXES_FILE = "survey_volume.npz"
@@ -108,8 +121,35 @@ def _columns(prod_per_line, name, n_depth):
     return np.concatenate(parts), ndim == {3}
 
 
+def _on_elevation(plan, lines, name, surface, d_edges, mode, axis, block, out):
+    """The volume of variable ``name`` on the elevation axis (``mode``, ``axis``: ``elevation.check_axis``): [n_elev, ny, nx] for
+    cells, [ny, nx] for the one level, a leading class axis where the variable has one; a memory map under ``out``."""
+    if mode == elevation_axis.INTERVALS:
+        for ln in lines:
+            if name in ln[4] and np.asarray(ln[4][name]).dtype.kind in "iub":
+                raise ValueError("%s: %r holds integers (class indices), and their mean over elevation cells means nothing: take one "
+                                 "level (elevation=...) or grid class_probability" % (ln[0], name))
+    cols, with_classes = _columns([(ln[0], ln[4]) for ln in lines], name, d_edges.size - 1)     # [N, K, n_depth]
+    K, n_elev, ny, nx = cols.shape[1], axis.size - (mode == elevation_axis.INTERVALS), plan.ny, plan.nx
+    shape = ((K,) if with_classes else ()) + ((n_elev,) if mode == elevation_axis.INTERVALS else ()) + (ny, nx)
+    if out is not None:
+        vol = np.lib.format.open_memmap(volume_path(out, name), mode="w+", dtype=np.float64, shape=shape)
+    else:
+        vol = np.empty(shape, dtype=np.float64)
+    cube = vol.reshape(K, n_elev, ny, nx)
+    v = torch.as_tensor(cols).to(plan.device)                                                    # once per variable
+    key = "edges" if mode == elevation_axis.INTERVALS else "levels"
+    for c0 in range(0, n_elev, block):
+        c1 = min(n_elev, c0 + block)
+        r = elevation_axis.resample(v, surface, d_edges, columns=(c0, c1), **{key: axis})       # [N, K, c1 - c0]
+        cube[:, c0:c1] = plan.apply(r.reshape(r.shape[0], K * (c1 - c0))).reshape(K, c1 - c0, ny, nx).cpu().numpy()
+    if out is not None:
+        vol.flush()
+    return vol
+
+
 def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None, block=256, device=None, out=None,
-               list_budget_bytes=0):
+               list_budget_bytes=0, elevation_edges=None, elevation=None):
     """Grid the line products of the containers ``paths`` (a directory, a container or a list of them; the lines in sorted order).
 
     Returns a dict: ``x_edges``, ``y_edges`` (``gridding.centred_mesh`` of all soundings at spacing ``dx``, ``dy``), ``depth_edges``
@@ -118,7 +158,28 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
     ``class_probability``; [ny, nx] / [K, ny, nx] when ``depth`` selects one cell).  ``depth``: see ``depth_cells``.
     ``max_distance`` (m) masks the pixels far from any sounding (``gridding``).  ``block`` columns go through the device at a time.
     With ``out`` (a directory) the axes go to ``survey_volume.npz`` and each variable to ``survey_volume.<variable>.npy`` through a
-    memory map, and the returned arrays of the variables are those maps."""
+    memory map, and the returned arrays of the variables are those maps.
+
+    ``elevation_edges`` (ascending edges [n_elev + 1] in m, or a function (surface elevations [N], depth_edges) -> such edges, e.g.
+    ``functools.partial(elevation.regular_axis, dz=2.0)``) puts the volumes on that elevation axis instead of the depth axis: every
+    variable goes to the device once as [N, K, n_depth], ``block`` elevation cells at a time are resampled there
+    (``elevation.resample``: the mean of the depth cells each elevation cell overlaps, per sounding under its own surface elevation) and
+    put through the plan.  The variables come back as [n_elev, ny, nx] ([K, n_elev, ny, nx] with classes), index 0 the lowest cell, and
+    the result gains ``elevation_edges``.  ``elevation`` (a number, m) is one horizontal slice, the value of the depth cell holding that
+    level under each sounding: [ny, nx] ([K, ny, nx]), and the result gains ``elevation_level``.  Both exclude ``depth`` and each
+    other; ``depth_edges`` (whole) and the draped ``elevation`` surface stay in the result.  The reference slices, then grids
+    (``Inference2D.elevationSlice``, then ``Point.interpolate``), so a pixel is NaN at a level wherever any sounding contributing to it
+    is outside its own mesh there: NaN propagates through the Sibson sum.  Integer line products (class indices) are refused on an
+    elevation axis -- their mean means nothing; a single ``elevation`` level takes them."""
+    on_axis, on_level = elevation_edges is not None, elevation is not None
+    if on_axis and on_level:
+        raise ValueError("elevation_edges and elevation exclude each other")
+    if (on_axis or on_level) and depth is not None:
+        raise ValueError("elevation_edges / elevation and depth exclude each other")
+    if on_level and not (np.size(elevation) == 1 and np.isfinite(float(np.asarray(elevation).reshape(-1)[0]))):
+        raise ValueError("elevation must be one finite level (m)")
+    if on_axis and not callable(elevation_edges):
+        elevation_axis.check_axis(edges=elevation_edges)
     if isinstance(paths, (str, os.PathLike)):
         paths = [paths]
     files = [f for p in paths for f in line_products.containers(str(p))]
@@ -145,11 +206,21 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
         res = dict(x_edges=x_edges, y_edges=y_edges, depth_edges=d_edges[cells.start:cells.stop + 1], x=x, y=y,
                    elevation=plan.apply(torch.as_tensor(elev).to(plan.device)).cpu().numpy(), count=plan.count.cpu().numpy(),
                    nearest_distance=plan.distance.cpu().numpy(), variables=np.array(list(variables)))
+        if on_axis:
+            mode, axis, _ = elevation_axis.check_axis(edges=elevation_edges(elev, d_edges) if callable(elevation_edges) else elevation_edges)
+            res["elevation_edges"] = axis
+        elif on_level:
+            mode, axis, _ = elevation_axis.check_axis(levels=[float(np.asarray(elevation).reshape(-1)[0])])
+            res["elevation_level"] = np.float64(axis[0])
         if out is not None:
             os.makedirs(str(out), exist_ok=True)
             np.savez(os.path.join(str(out), AXES_FILE), **res)
         ncell = cells.stop - cells.start
+        surface = torch.as_tensor(elev).to(plan.device) if (on_axis or on_level) else None
         for name in variables:
+            if surface is not None:
+                res[name] = _on_elevation(plan, lines, name, surface, d_edges, mode, axis, int(block), out)
+                continue
             cols, with_classes = _columns([(ln[0], ln[4]) for ln in lines], name, nz)
             cols = cols[:, :, cells]                                                             # [N, K, cells]
             K = cols.shape[1]
@@ -187,6 +258,10 @@ def parser():
     ap.add_argument("--mask", type=float, default=None, metavar="MAX_DISTANCE", help="mask pixels farther than this from any sounding (m)")
     ap.add_argument("--depth", type=float, default=None, metavar="D", help="one map: the depth cell holding depth D (m)")
     ap.add_argument("--depth-cells", type=int, nargs=2, default=None, metavar=("I0", "I1"), help="the depth cells I0 .. I1 (inclusive) only")
+    ap.add_argument("--elevation-axis", type=float, nargs="+", default=None, metavar="DZ [TOP BOTTOM]",
+                    help="volumes on a regular elevation axis of DZ m instead of the depth axis, from BOTTOM to TOP (default: everything "
+                         "the soundings reach), snapped outward to multiples of DZ; index 0 is the lowest cell")
+    ap.add_argument("--elevation", type=float, default=None, metavar="E", help="one map: the horizontal slice at elevation E (m)")
     ap.add_argument("--block", type=int, default=256, help="columns per pass through the device (default 256)")
     ap.add_argument("--device", default=None, help="torch device of the kernels (default cuda:0)")
     ap.add_argument("--out", default=None, help="directory of the outputs (default: the first path's directory)")
@@ -194,7 +269,8 @@ def parser():
 
 
 def parse_args(argv=None):
-    """The command line's arguments, checked: positive spacings, mask and block, --depth or --depth-cells but not both, 0 <= I0 <= I1."""
+    """The command line's arguments, checked: positive spacings, mask and block, at most one of --depth, --depth-cells, --elevation-axis
+    and --elevation, 0 <= I0 <= I1, DZ > 0 and BOTTOM < TOP."""
     ap = parser()
     a = ap.parse_args(argv)
     for name, v in (("--dx", a.dx), ("--dy", a.dy)):
@@ -204,6 +280,15 @@ def parse_args(argv=None):
         ap.error("--mask must be positive and finite")
     if a.depth is not None and a.depth_cells is not None:
         ap.error("--depth and --depth-cells exclude each other")
+    if sum(v is not None for v in (a.depth, a.depth_cells, a.elevation_axis, a.elevation)) > 1:
+        ap.error("--depth, --depth-cells, --elevation-axis and --elevation exclude one another")
+    if a.elevation is not None and not np.isfinite(a.elevation):
+        ap.error("--elevation must be finite")
+    if a.elevation_axis is not None:
+        try:
+            line_products.elevation_axis_arguments(a.elevation_axis)
+        except ValueError as e:
+            ap.error("--elevation-axis: " + str(e))
     if a.depth is not None and not np.isfinite(a.depth):
         ap.error("--depth must be finite")
     if a.depth_cells is not None and not 0 <= a.depth_cells[0] <= a.depth_cells[1]:
@@ -219,14 +304,26 @@ def main(argv=None):
     a = parse_args(argv)
     depth = a.depth if a.depth is not None else (None if a.depth_cells is None else slice(a.depth_cells[0], a.depth_cells[1] + 1))
     out = a.out if a.out is not None else (a.paths[0] if os.path.isdir(a.paths[0]) else os.path.dirname(os.path.abspath(a.paths[0])))
+    edges = None
+    if a.elevation_axis is not None:
+        dz, top, bottom = line_products.elevation_axis_arguments(a.elevation_axis)
+        edges = functools.partial(elevation_axis.regular_axis, dz=dz, top=top, bottom=bottom)
     try:
         r = from_lines(a.paths, a.dx, a.dy, variables=tuple(a.variables), max_distance=a.mask, depth=depth, block=a.block, device=a.device,
-                       out=out)
+                       out=out, elevation_edges=edges, elevation=a.elevation)
     except ValueError as e:
         print("survey_volume: %s" % e, file=sys.stderr)
         return 1
-    print("%d soundings -> %d x %d pixels, %d depth cells: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
-                                                                  r["depth_edges"].size - 1, os.path.join(out, AXES_FILE)))
+    if "elevation_edges" in r:
+        print("%d soundings -> %d x %d pixels, %d elevation cells %g .. %g m: %s" % (
+            r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1, r["elevation_edges"].size - 1, r["elevation_edges"][0],
+            r["elevation_edges"][-1], os.path.join(out, AXES_FILE)))
+    elif "elevation_level" in r:
+        print("%d soundings -> %d x %d pixels at elevation %g m: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
+                                                                        r["elevation_level"], os.path.join(out, AXES_FILE)))
+    else:
+        print("%d soundings -> %d x %d pixels, %d depth cells: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
+                                                                      r["depth_edges"].size - 1, os.path.join(out, AXES_FILE)))
     for name in a.variables:
         print("  %s %r" % (volume_path(out, name), tuple(r[name].shape)))
     return 0

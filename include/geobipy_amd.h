@@ -676,6 +676,25 @@ void gbp_sibson_plan_destroy(gbp_sibson_plan *plan);
 gbp_status gbp_sibson_plan_query(const gbp_sibson_plan *plan, int32_t *index, int32_t *distance, int32_t *count, int64_t *info, void *stream);
 gbp_status gbp_sibson_apply(const gbp_sibson_plan *plan, int C, const double *values, double *out, void *stream);
 
+/* Elevation slices: rows on the depth-below-surface axis resampled onto an elevation axis (csrc/gbp_elev.h), the reference's
+ * Inference2D.elevationSlice for every row and every elevation at once.  values [R, n_depth] row-major, surface [R / K] (row r belongs
+ * to sounding r / K: [N, K, n_depth] class probabilities pass as R = N K rows), depth_edges [n_depth + 1] increasing, all fp64 DEVICE
+ * arrays.  cell(d) = clamp(upper_bound(depth_edges, d) - 1, 0, n_depth - 1).
+ * GBP_ELEVATION_LEVELS: axis = levels [E]; d = surface - level; out = values[cell(d)] when depth_edges[0] < d < depth_edges[n_depth]
+ * (both strict), else NaN.  GBP_ELEVATION_INTERVALS: axis = edges [E + 1], cell k = (edges[k], edges[k + 1]); d0 = surface - edges[k],
+ * d1 = surface - edges[k + 1]; out = the mean of values[cell(d1) .. cell(d0)] when d1 < depth_edges[n_depth] and d0 > depth_edges[0]
+ * (an interval that only overlaps the mesh averages the cells it overlaps), NaN otherwise and for an empty range.  The mean is
+ * sum / count with the sum in numpy's pairwise order (blocks of at most 128 terms on eight accumulators, halves split at multiples of
+ * eight), so results equal the reference's in every bit and are reproducible.  A NaN surface gives NaN; NaN values propagate.
+ * out [R, c1 - c0] row-major holds the columns c0 <= k < c1 of the axis: the [N, C] layout gbp_sibson_apply reads.
+ * The axes are not read on the host: whether they are finite and increasing is the caller's to check.
+ * GBP_ERR_INVALID_ARG: an unknown mode, R < 1, K < 1 or R % K != 0, n_depth < 1 or > 8191, E < 1, a window outside 0 <= c0 < c1 <= E,
+ * NULL pointers, R * n_depth or R * (c1 - c0) out of range. */
+#define GBP_ELEVATION_LEVELS 0
+#define GBP_ELEVATION_INTERVALS 1
+gbp_status gbp_elevation_resample(int mode, int R, int K, int n_depth, const double *values, const double *surface,
+                                  const double *depth_edges, int E, const double *axis, int c0, int c1, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
