@@ -1492,10 +1492,10 @@ extern "C" gbp_status gbp_hitmap_statistics(int B, int nv, int nz, const int32_t
 }
 
 // Per-column moments of B hit maps [B, nv, nz] for the line products: mean (as gbp_hitmap_statistics), mode index, n_q quantile indices
-// (q: host array, 0 < q < 1, n_q <= 8), total and sum c ln c -> [B, nz] arrays ([n_q, B, nz] for q_idx)
-extern "C" gbp_status gbp_hitmap_products(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width,
-                                          int n_q, const double* q, double* mean, int32_t* mode_idx, int32_t* q_idx, int64_t* total,
-                                          double* s1, void* stream)
+// (q: host array, 0 < q < 1, n_q <= 8), total and sum c ln c -> [B, nz] arrays ([n_q, B, nz] for q_idx).  T: the maps' count type.
+template <typename T>
+static gbp_status hitmap_products(int B, int nv, int nz, const T* hitmap, const double* log_mean_prior, double half_width, int n_q,
+                                  const double* q, double* mean, int32_t* mode_idx, int32_t* q_idx, int64_t* total, double* s1, void* stream)
 {
     if (B < 0 || nv < 1 || nz < 1 || n_q < 0 || n_q > 8 || (n_q > 0 && !q))
         return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: non-positive size, n_q outside 0 .. 8 or q NULL%s");
@@ -1510,16 +1510,33 @@ extern "C" gbp_status gbp_hitmap_products(int B, int nv, int nz, const int32_t* 
         return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: NULL pointer%s");
     if ((int64_t)B * nz > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_products: B * n_depth out of range%s");
     static_assert(sizeof(long long) == sizeof(int64_t), "int64_t is long long here");
-    hipLaunchKernelGGL(hitmap::k_hitmap_products, dim3(B, (nz + 255) / 256), dim3(256), 0, (hipStream_t)stream, nv, nz, hitmap, log_mean_prior,
+    hipLaunchKernelGGL(hitmap::k_hitmap_products<T>, dim3(B, (nz + 255) / 256), dim3(256), 0, (hipStream_t)stream, nv, nz, hitmap, log_mean_prior,
                        half_width, qs, mean, mode_idx, q_idx, (long long*)total, s1);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
 
+extern "C" gbp_status gbp_hitmap_products(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width,
+                                          int n_q, const double* q, double* mean, int32_t* mode_idx, int32_t* q_idx, int64_t* total,
+                                          double* s1, void* stream)
+{
+    return hitmap_products<int>(B, nv, nz, hitmap, log_mean_prior, half_width, n_q, q, mean, mode_idx, q_idx, total, s1, stream);
+}
+
+// The same over int64 maps [B, nv, nz] (interval marginals: gbp_hitmap_intervals)
+extern "C" gbp_status gbp_hitmap_products_i64(int B, int nv, int nz, const int64_t* hitmap, const double* log_mean_prior, double half_width,
+                                              int n_q, const double* q, double* mean, int32_t* mode_idx, int32_t* q_idx, int64_t* total,
+                                              double* s1, void* stream)
+{
+    return hitmap_products<long long>(B, nv, nz, (const long long*)hitmap, log_mean_prior, half_width, n_q, q, mean, mode_idx, q_idx, total, s1,
+                                      stream);
+}
+
 // Class probabilities of B hit maps [B, nv, nz] for K classes in log10 conductivity (means / scales: host arrays of K values, scale the
 // standard deviation) -> prob [B, K, nz], best [B, nz] (the most probable class) and best_p [B, nz] (its probability)
-extern "C" gbp_status gbp_hitmap_classes(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width, int K,
-                                         const double* means, const double* scales, double* prob, int32_t* best, double* best_p, void* stream)
+template <typename T>
+static gbp_status hitmap_classes(int B, int nv, int nz, const T* hitmap, const double* log_mean_prior, double half_width, int K,
+                                 const double* means, const double* scales, double* prob, int32_t* best, double* best_p, void* stream)
 {
     if (B < 0 || nv < 1 || nz < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: negative or zero size%s");
     if (K < 1 || K > hitmap::MAX_CLASSES) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_classes: K outside 1 .. 16%s");
@@ -1543,11 +1560,50 @@ extern "C" gbp_status gbp_hitmap_classes(int B, int nv, int nz, const int32_t* h
         hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)lds, (hipStream_t)stream, nv, nz, hitmap, log_mean_prior, half_width, cl, prob, best,
                            best_p);
     };
-    if (K <= 1) launch(hitmap::k_hitmap_classes<1>);
-    else if (K <= 2) launch(hitmap::k_hitmap_classes<2>);
-    else if (K <= 4) launch(hitmap::k_hitmap_classes<4>);
-    else if (K <= 8) launch(hitmap::k_hitmap_classes<8>);
-    else launch(hitmap::k_hitmap_classes<16>);
+    if (K <= 1) launch(hitmap::k_hitmap_classes<1, T>);
+    else if (K <= 2) launch(hitmap::k_hitmap_classes<2, T>);
+    else if (K <= 4) launch(hitmap::k_hitmap_classes<4, T>);
+    else if (K <= 8) launch(hitmap::k_hitmap_classes<8, T>);
+    else launch(hitmap::k_hitmap_classes<16, T>);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+extern "C" gbp_status gbp_hitmap_classes(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width, int K,
+                                         const double* means, const double* scales, double* prob, int32_t* best, double* best_p, void* stream)
+{
+    return hitmap_classes<int>(B, nv, nz, hitmap, log_mean_prior, half_width, K, means, scales, prob, best, best_p, stream);
+}
+
+// The same over int64 maps [B, nv, nz] (interval marginals: gbp_hitmap_intervals)
+extern "C" gbp_status gbp_hitmap_classes_i64(int B, int nv, int nz, const int64_t* hitmap, const double* log_mean_prior, double half_width,
+                                             int K, const double* means, const double* scales, double* prob, int32_t* best, double* best_p,
+                                             void* stream)
+{
+    return hitmap_classes<long long>(B, nv, nz, (const long long*)hitmap, log_mean_prior, half_width, K, means, scales, prob, best, best_p, stream);
+}
+
+// Interval marginals of B hit maps [B, nv, nz]: out[b, v, m] = sum of hitmap[b, v, z] over lo[b, m] <= z < hi[b, m] (int64 [B, nv, M];
+// lo / hi: DEVICE int32 [B, M], clamped to [0, nz] by the kernel; hi <= lo: no cells).  1 <= M <= 4096, nz <= 1024.
+extern "C" gbp_status gbp_hitmap_intervals(int B, int nv, int nz, int M, const int32_t* hitmap, const int32_t* lo, const int32_t* hi,
+                                           int64_t* out, void* stream)
+{
+    if (B < 0 || nv < 1 || nz < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_intervals: negative or zero size%s");
+    if (M < 1 || M > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_intervals: M outside 1 .. 4096%s");
+    if (nz > 1024) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_intervals: n_depth beyond 1024 (the row prefix lives in LDS)%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!hitmap || !lo || !hi || !out) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_intervals: NULL pointer%s");
+    const int rows = (nv + hitmap::INTERVAL_ROWS - 1) / hitmap::INTERVAL_ROWS;
+    if (rows > 65535) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_intervals: n_value out of range%s");
+    const bool aligned = nz % 4 == 0 && ((uintptr_t)hitmap & 15) == 0;
+    const int G = nz <= 256 ? 1 : (nz <= 512 ? 2 : 4);
+    const size_t lds = (size_t)(256 * G + 1) * sizeof(long long) + (size_t)2 * M * sizeof(int);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(B, rows), dim3(64), lds, (hipStream_t)stream, nv, nz, M, hitmap, lo, hi, (long long*)out);
+    };
+    if (G == 1) { if (aligned) launch(hitmap::k_hitmap_intervals<1, true>); else launch(hitmap::k_hitmap_intervals<1, false>); }
+    else if (G == 2) { if (aligned) launch(hitmap::k_hitmap_intervals<2, true>); else launch(hitmap::k_hitmap_intervals<2, false>); }
+    else { if (aligned) launch(hitmap::k_hitmap_intervals<4, true>); else launch(hitmap::k_hitmap_intervals<4, false>); }
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }

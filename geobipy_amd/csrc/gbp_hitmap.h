@@ -63,21 +63,25 @@ struct Quantiles {
 //   total[b, z] = sum_v c_v (int64);  mean[b, z] = k_hitmap_stats's mean (same expression, same order: the same bits);
 //   mode_idx[b, z] = first v of max_v c_v (numpy argmax; an empty column: 0);  s1[b, z] = sum_v c_v ln c_v (0 ln 0 = 0; gbp::log_pos);
 //   q_idx[k, b, z] = #{v : cumsum_v / max(total, 1) < q_k} clamped to nv - 1 (mesh/Mesh.py _percentile's searchsorted).
-__global__ __launch_bounds__(256) void k_hitmap_products(int nv, int nz, const int* __restrict__ hm, const double* __restrict__ log_mean_prior,
+// T is the count type: int for the maps themselves, long long for interval marginals (k_hitmap_intervals), whose counts stay below
+// 2^31 n_depth < 2^53, so that every conversion to fp64 is exact and the two instances give the same bits on the same counts.
+template <typename T>
+__global__ __launch_bounds__(256) void k_hitmap_products(int nv, int nz, const T* __restrict__ hm, const double* __restrict__ log_mean_prior,
                                                           double half_width, Quantiles qs, double* __restrict__ mean, int* __restrict__ mode_idx,
                                                           int* __restrict__ q_idx, long long* __restrict__ total, double* __restrict__ s1)
 {
     const int b = blockIdx.x, z = blockIdx.y * 256 + threadIdx.x;
     if (z >= nz) return;
-    const int* col = hm + (size_t)b * nv * nz + z;
+    const T* col = hm + (size_t)b * nv * nz + z;
     const double shift = log_mean_prior[b] / 2.302585092994046;
     const double w = 2.0 * half_width;
     long long tot = 0;
     double wsum = 0.0, slog = 0.0;
-    int best = col[0], ibest = 0;
+    T best = col[0];
+    int ibest = 0;
 #pragma unroll 10
     for (int v = 0; v < nv; ++v) {
-        const int h = col[(size_t)v * nz];
+        const T h = col[(size_t)v * nz];
         tot += h;
         wsum += (double)h * ((((double)v + 0.5) / (double)nv) * w - half_width);
         if (h > 0) slog += (double)h * gbp::log_pos((double)h);      // (a branch: a wave whose 64 cells are empty skips the logarithm)
@@ -123,8 +127,8 @@ struct Classes {
 // The prologue builds the sounding's table w [nv][K] in fp64 in LDS (K nv exps per workgroup, the device libm exp: subnormals kept);
 // in the column loop every lane of a wave reads the same table row, a broadcast.  KB is the class bucket (K <= KB): accumulators of
 // unused classes cost neither registers nor FMAs beyond the bucket.  A wave whose 64 cells of a value row are all empty skips the row.
-template <int KB>
-__global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const int* __restrict__ hm, const double* __restrict__ log_mean_prior,
+template <int KB, typename T>
+__global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const T* __restrict__ hm, const double* __restrict__ log_mean_prior,
                                                          double half_width, Classes cl, double* __restrict__ prob, int* __restrict__ best,
                                                          double* __restrict__ best_p)
 {
@@ -140,11 +144,11 @@ __global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const in
     }
     __syncthreads();
     if (z >= nz) return;
-    const int* col = hm + (size_t)b * nv * nz + z;
+    const T* col = hm + (size_t)b * nv * nz + z;
     double acc[KB];
 #pragma unroll
     for (int k = 0; k < KB; ++k) acc[k] = 0.0;
-    auto add = [&](int h, int v) {
+    auto add = [&](T h, int v) {
         if (h != 0) {
             const double c = (double)h;
             const double* row = wt + v * K;
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const in
     constexpr int U = 10;                          // ten loads in flight per wave, issued before the rows they feed
     int v0 = 0;
     for (; v0 + U <= nv; v0 += U) {
-        int h[U];
+        T h[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) h[u] = col[(size_t)(v0 + u) * nz];
 #pragma unroll
@@ -235,6 +239,110 @@ __global__ __launch_bounds__(256) void k_hitmap_runs(long long M, const int* __r
         base += rank0;
     }
     if (!WRITE && threadIdx.x == 0) counts[b] = base;
+}
+
+// Inclusive sum over the 64 lanes of a wave in int64, in the vector ALU alone (DPP: row_shr 1 2 4 8 inside the rows of 16 lanes, then
+// row_bcast 15 and 31 across them -- the sequence of LLVM's own wave scan for gfx9); lanes without a source add 0.  Every lane of the
+// wave must be active.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ long long dpp_or_zero(long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(unsigned long long)v, CTRL, ROWS, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)v >> 32), CTRL, ROWS, 0xf, false);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+__device__ __forceinline__ long long wave_inclusive_sum(long long x)
+{
+    x += dpp_or_zero<0x111, 0xf>(x);               // row_shr:1
+    x += dpp_or_zero<0x112, 0xf>(x);               // row_shr:2
+    x += dpp_or_zero<0x114, 0xf>(x);               // row_shr:4
+    x += dpp_or_zero<0x118, 0xf>(x);               // row_shr:8
+    x += dpp_or_zero<0x142, 0xa>(x);               // row_bcast:15 into rows 1 and 3
+    x += dpp_or_zero<0x143, 0xc>(x);               // row_bcast:31 into rows 2 and 3
+    return x;
+}
+
+__device__ __forceinline__ long long wave_read_lane(long long v, int lane)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)v, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), lane);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// Interval marginals: out[b, v, m] = sum of hm[b, v, z] over the depth cells lo[b, m] <= z < hi[b, m] (int64; the ranges clamped to
+// [0, nz], hi <= lo: no cells, 0) -- the reference's Histogram[:, lo:hi].marginalize(axis=1) for M ranges at once, which may overlap
+// and differ from sounding to sounding.  One wave per workgroup takes ROWS value rows of one sounding, a row at a time: lane l holds the
+// four consecutive cells 256 g + 4 l .. + 3 of group g (ALIGNED: one 16-byte load each, the row read once and coalesced; rows that are
+// not 16-byte aligned take four 4-byte loads), sums them, the lane sums are scanned across the wave (wave_inclusive_sum: no LDS), and
+// each lane writes the exclusive prefix P of its cells to LDS in int64 (P[z] = sum of the cells before z, P[256 G] = the row's sum).
+// Then lane m writes P[hi_m] - P[lo_m], M / 64 coalesced stores.  The next row's loads are issued before the current row is worked on.
+// Integer sums: exact in any order.  No atomics, no scratch.  LDS: (256 G + 1) 8 B of prefix + 2 M 4 B of ranges.
+constexpr int INTERVAL_ROWS = 32;
+template <int G, bool ALIGNED>
+__global__ __launch_bounds__(64) void k_hitmap_intervals(int nv, int nz, int M, const int* __restrict__ hm, const int* __restrict__ lo,
+                                                         const int* __restrict__ hi, long long* __restrict__ out)
+{
+    extern __shared__ long long interval_lds[];
+    long long* P = interval_lds;                                   // [256 G + 1]
+    int* slo = reinterpret_cast<int*>(interval_lds + 256 * G + 1); // [M]
+    int* shi = slo + M;                                            // [M]
+    const int b = blockIdx.x, lane = threadIdx.x;
+    for (int m = lane; m < M; m += 64) {
+        int l = lo[(size_t)b * M + m], h = hi[(size_t)b * M + m];
+        l = l < 0 ? 0 : (l > nz ? nz : l);
+        h = h < 0 ? 0 : (h > nz ? nz : h);
+        slo[m] = l;
+        shi[m] = h > l ? h : l;                                    // (no cells: P[l] - P[l])
+    }
+    const int v0 = blockIdx.y * INTERVAL_ROWS, v1 = v0 + INTERVAL_ROWS < nv ? v0 + INTERVAL_ROWS : nv;
+    const int* map = hm + (size_t)b * nv * nz;
+    auto load = [&](int v, int (&x)[G][4]) {
+        const int* row = map + (size_t)v * nz;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int z = 256 * g + 4 * lane;
+            if (ALIGNED) {                                         // nz % 4 == 0: a group of four is inside the row or outside it
+                int4 q = make_int4(0, 0, 0, 0);
+                if (z < nz) q = *reinterpret_cast<const int4*>(row + z);
+                x[g][0] = q.x; x[g][1] = q.y; x[g][2] = q.z; x[g][3] = q.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[g][j] = z + j < nz ? row[z + j] : 0;
+            }
+        }
+    };
+    int cur[G][4] = {}, nxt[G][4] = {};
+    if (v0 < v1) load(v0, cur);
+    __syncthreads();                                               // (the ranges are in LDS)
+    const int lo0 = lane < M ? slo[lane] : 0, hi0 = lane < M ? shi[lane] : 0;
+    for (int v = v0; v < v1; ++v) {
+        if (v + 1 < v1) load(v + 1, nxt);
+        long long base = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const long long s = (long long)cur[g][0] + cur[g][1] + cur[g][2] + cur[g][3];
+            const long long inc = wave_inclusive_sum(s);
+            long long p = base + inc - s;                          // exclusive prefix of this lane's first cell
+            long long* dst = P + 256 * g + 4 * lane;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                dst[j] = p;
+                p += cur[g][j];
+            }
+            base += wave_read_lane(inc, 63);
+        }
+        if (lane == 0) P[256 * G] = base;
+        __syncthreads();                                           // (one wave: the prefix is complete)
+        long long* dst = out + ((size_t)b * nv + v) * M;
+        if (lane < M) dst[lane] = P[hi0] - P[lo0];
+        for (int m = lane + 64; m < M; m += 64) dst[m] = P[shi[m]] - P[slo[m]];
+        __syncthreads();                                           // (read before the next row overwrites it)
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cur[g][j] = nxt[g][j];
+    }
 }
 
 }  // namespace hitmap

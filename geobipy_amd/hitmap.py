@@ -17,6 +17,15 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
+def _entry(hm, name):
+    """The C entry ``name`` for int32 maps, ``name``_i64 for int64 ones; other count types are refused."""
+    if hm.dtype == torch.int32:
+        return getattr(_lib.load(), name)
+    if hm.dtype == torch.int64:
+        return getattr(_lib.load(), name + "_i64")
+    raise TypeError("hit maps are int32 (or int64 interval marginals), not %s" % hm.dtype)
+
+
 def statistics(hitmap, log_mean_prior, half_width):
     """Mean and 5 / 50 / 95 % points of log10 conductivity per depth cell from the hit maps [B, n_value, n_depth] (value-major, depth
     fastest) in one kernel (gbp_hitmap_statistics): sum(count x cell centre) / total + the prior mean, and the centre of the first cell
@@ -59,12 +68,13 @@ def runs(hitmap):
 
 def moments(hitmap, log_mean_prior, half_width, q):
     """The per-column moments of the hit maps [B, n_value, n_depth] in one kernel (gbp_hitmap_products): mean (log10, the bits of
-    ``statistics``), mode_idx, q_idx [len(q), B, n_depth], total (int64) and s1 = sum c ln c, on the maps' device."""
+    ``statistics``), mode_idx, q_idx [len(q), B, n_depth], total (int64) and s1 = sum c ln c, on the maps' device.  int32 maps, or
+    int64 ones (``interval_marginals``: gbp_hitmap_products_i64, the same kernel on the other count type)."""
     if hitmap.device.type != "cuda":
         raise _lib.NativeLibraryError("hitmap.moments runs on the device (gbp_hitmap_products); there is no host fallback")
     B, nv, nz = hitmap.shape
     hm = hitmap.contiguous()
-    assert hm.dtype == torch.int32
+    entry = _entry(hm, "gbp_hitmap_products")
     dev = hm.device
     lmp = log_mean_prior.to(device=dev, dtype=torch.float64).contiguous()
     qa = (ctypes.c_double * max(len(q), 1))(*q)
@@ -74,8 +84,8 @@ def moments(hitmap, log_mean_prior, half_width, q):
     mode_idx = torch.empty((B, nz), dtype=torch.int32, device=dev)
     q_idx = torch.empty((len(q), B, nz), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().gbp_hitmap_products(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), len(q), qa, mean.data_ptr(),
-                                                   mode_idx.data_ptr(), q_idx.data_ptr(), total.data_ptr(), s1.data_ptr(), _stream(dev)))
+        _lib.check(entry(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), len(q), qa, mean.data_ptr(), mode_idx.data_ptr(),
+                         q_idx.data_ptr(), total.data_ptr(), s1.data_ptr(), _stream(dev)))
     return dict(mean=mean, mode_idx=mode_idx, q_idx=q_idx, total=total, s1=s1)
 
 
@@ -112,12 +122,13 @@ def class_probability(hitmap, log_mean_prior, half_width, means, scales):
     ``scales`` are standard deviations.  Every class has the same prior weight.  Returns ``probability`` [B, K, n_depth] (NaN where every
     term is 0, e.g. an empty column), ``highest_marginal`` [B, n_depth] int32 (the first most probable class; numpy's argmax over the
     class axis, 0 for a NaN column) and ``probability_of_highest_marginal`` [B, n_depth] (its probability, NaN for a NaN column).
-    1 <= K <= 16, and K n_value fp64 weights must fit in 64 KiB (gbp_hitmap_classes refuses the rest)."""
+    1 <= K <= 16, and K n_value fp64 weights must fit in 64 KiB (gbp_hitmap_classes refuses the rest).  int32 maps, or int64 ones
+    (``interval_marginals``: gbp_hitmap_classes_i64)."""
     if hitmap.device.type != "cuda":
         raise _lib.NativeLibraryError("hitmap.class_probability runs on the device (gbp_hitmap_classes); there is no host fallback")
     B, nv, nz = hitmap.shape
     hm = hitmap.contiguous()
-    assert hm.dtype == torch.int32
+    entry = _entry(hm, "gbp_hitmap_classes")
     dev = hm.device
     mu = [float(m) for m in means]
     sd = [float(s) for s in scales]
@@ -131,6 +142,42 @@ def class_probability(hitmap, log_mean_prior, half_width, means, scales):
     best = torch.empty((B, nz), dtype=torch.int32, device=dev)
     best_p = torch.empty((B, nz), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().gbp_hitmap_classes(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), K, ma, sa, prob.data_ptr(),
-                                                  best.data_ptr(), best_p.data_ptr(), _stream(dev)))
+        _lib.check(entry(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), K, ma, sa, prob.data_ptr(), best.data_ptr(),
+                         best_p.data_ptr(), _stream(dev)))
     return dict(probability=prob, highest_marginal=best, probability_of_highest_marginal=best_p)
+
+
+def interval_marginals(hitmap, lo, hi):
+    """Interval marginals of the hit maps [B, n_value, n_depth] (int32) in one kernel (gbp_hitmap_intervals), on the maps' device:
+    int64 [B, n_value, M], the counts summed over the depth cells ``lo <= cell < hi`` of each of M ranges (``intervals.depth_ranges``
+    and its siblings) -- the reference's ``Histogram[:, lo:hi].marginalize(axis=1)``.  ``lo`` / ``hi``: [M] (every sounding the same)
+    or [B, M], integers; clamped to [0, n_depth] by the kernel, ``hi <= lo``: no cells, zeros.  Ranges may overlap.  int64 because a few
+    cells of a long chain's map sum beyond 2^31.  ``products`` / ``class_probability`` take the result as they take the maps."""
+    if hitmap.device.type != "cuda":
+        raise _lib.NativeLibraryError("hitmap.interval_marginals runs on the device (gbp_hitmap_intervals); there is no host fallback")
+    B, nv, nz = hitmap.shape
+    hm = hitmap.contiguous()
+    if hm.dtype != torch.int32:
+        raise TypeError("hit maps are int32, not %s" % hm.dtype)
+    dev = hm.device
+
+    def ranges(r):
+        r = torch.as_tensor(r)
+        if r.dtype.is_floating_point or r.dtype == torch.bool or r.ndim not in (1, 2):
+            raise ValueError("interval ranges are integers [M] or [B, M]")
+        r = r.clamp(-1, nz + 1).to(device=dev, dtype=torch.int32)
+        if r.ndim == 1:
+            r = r[None, :].expand(B, -1)
+        if r.shape[0] != B:
+            raise ValueError("interval ranges for %d soundings, the block has %d" % (r.shape[0], B))
+        return r.contiguous()
+
+    lo_d, hi_d = ranges(lo), ranges(hi)
+    if lo_d.shape != hi_d.shape:
+        raise ValueError("lo and hi differ in shape: %r, %r" % (tuple(lo_d.shape), tuple(hi_d.shape)))
+    M = lo_d.shape[1]
+    out = torch.empty((B, nv, M), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gbp_hitmap_intervals(B, nv, nz, M, hm.data_ptr(), lo_d.data_ptr(), hi_d.data_ptr(), out.data_ptr(),
+                                                    _stream(dev)))
+    return out

@@ -13,10 +13,13 @@ Everything is log10 conductivity (S/m) except entropy (bits), opacity and probab
 
     python -m geobipy_amd.line_products <container or directory> [--credible 90] [--doi 67] [--percentiles 5 50 95]
                                         [--class-means M1 M2 ... --class-scales S1 S2 ...] [--elevation-axis DZ [TOP BOTTOM]]
+                                        [--depth-intervals E0 E1 ... | --elevation-intervals E0 E1 ...]
 
 writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.  The class means and scales (standard deviations)
 are in log10 S/m; they come together, 1 to 16 of each.  With ``--elevation-axis`` the per-depth-cell products also go onto a regular
 elevation axis (``on_elevation``, ``elevation.regular_axis``), written to ``<line>.products_elevation.npz`` beside the first file.
+With ``--depth-intervals`` / ``--elevation-intervals`` the file also holds the products of the units between those edges (``interval_*``:
+the statistics of each unit's marginal posterior, ``from_results(intervals=...)``, geobipy_amd/intervals.py).
 """
 import argparse
 import glob
@@ -162,7 +165,34 @@ def check_classes(means, scales):
     return mu, sd
 
 
-def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0, classes=None):
+INTERVAL_DROPPED = ("entropy", "s1")          # (the reference's density is over the sounding's 2-D mesh: not defined for a unit)
+
+
+def interval_products(hm, lmp, half_width, lo, hi, percentiles=(5, 50, 95), credible=90.0, classes=None):
+    """The ``interval_*`` entries of a block of hit maps on the device: ``hitmap.interval_marginals`` over the ranges ``lo`` / ``hi``
+    [B, M], then ``hitmap.products`` (and ``hitmap.class_probability`` for ``classes`` = (means, scales)) along the value axis of the
+    int64 marginals [B, n_value, M]: mean, median, mode, percentile_<p>, credible_low / high / range, total (int64) [B, M] and, with
+    classes, class_probability [B, K, M], highest_marginal, probability_of_highest_marginal; float entries NaN where a range has no
+    cells.  Torch tensors on the maps' device."""
+    from . import hitmap
+    marg = hitmap.interval_marginals(hm, lo, hi)
+    nz = hm.shape[2]
+    empty = (torch.as_tensor(hi).clamp(0, nz) <= torch.as_tensor(lo).clamp(0, nz)).to(marg.device)      # (as the kernel clamps them)
+    empty = empty[None, :].expand(marg.shape[0], -1) if empty.ndim == 1 else empty
+    p = hitmap.products(marg, lmp, half_width, percentiles=percentiles, credible=credible)
+    out = {"interval_" + k: v for k, v in p.items() if k not in INTERVAL_DROPPED}
+    if classes is not None:
+        c = hitmap.class_probability(marg, lmp, half_width, *classes)
+        out.update(interval_class_probability=c["probability"], interval_highest_marginal=c["highest_marginal"],
+                   interval_probability_of_highest_marginal=c["probability_of_highest_marginal"])
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=marg.device)
+    for k, v in out.items():
+        if v.dtype.is_floating_point:
+            out[k] = torch.where(empty[:, None, :] if v.ndim == 3 else empty, nan, v)
+    return out
+
+
+def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0, classes=None, intervals=None):
     """{name: numpy array} of the line products of the results container at ``path`` (``<line>.h5`` or the ``.results[.npz]`` stand-in,
     read through ``hdf.load_results``; the reference's own files where they hold this layout).  The hit maps go to ``device`` (default
     cuda:0) ``block`` soundings at a time.  Per sounding [N, n_depth] (log10 S/m): mean, median, mode, percentile_<p>, credible_low /
@@ -178,8 +208,20 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     ``class_probability`` [N, K, n_depth] (the layout of the reference's ``probabilities``), ``highest_marginal`` [N, n_depth] (int32),
     ``probability_of_highest_marginal`` [N, n_depth], ``class_means`` and ``class_scales``, from the blocks the products were computed
     on (no second upload).  The reference takes its argmax over the last axis of a [N, K, n_depth] array in Inference3D but over the
-    class axis in Inference2D; here it is over the class axis."""
+    class axis in Inference2D; here it is over the class axis.
+
+    ``intervals`` = a spec (``intervals.check_spec``: {"kind": "depth", "edges": [...]}, {"kind": "pairs", "pairs": [[d0, d1], ...]},
+    {"kind": "elevation", "edges": [...]} under the container's /data/elevation, or {"kind": "horizons", "top": ..., "bottom": ...})
+    adds the products of M depth or elevation UNITS, each the statistic of the unit's marginal posterior -- the hit map's counts summed
+    over the unit's depth cells (``hitmap.interval_marginals``), not a mean over per-cell products: ``interval_mean`` / ``_median`` /
+    ``_mode`` / ``_percentile_<p>`` / ``_credible_low`` / ``_high`` / ``_range`` [N, M] (NaN where a unit has no cells under a sounding),
+    ``interval_total`` (int64) and ``interval_cells`` (int32) [N, M], ``interval_lo`` / ``interval_hi`` (the cell ranges), with classes
+    ``interval_class_probability`` [N, K, M], ``interval_highest_marginal`` and ``interval_probability_of_highest_marginal``, and the
+    spec itself (``interval_kind``, ``interval_edges`` / ``interval_pairs`` / ``interval_top``, ``interval_bottom``).  The ranges are
+    computed once per line on the host; the marginals come from the blocks the products are computed on.  Entropy, opacity and DOI are
+    not defined for units."""
     from . import hdf, hitmap
+    from . import intervals as iv
     if not 0.0 < float(credible) < 100.0:
         raise ValueError("credible must lie in (0, 100)")
     if classes is not None:
@@ -197,12 +239,20 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     hw = _uniform_half_width(v_edges)
     rel = np.zeros(N) if rel is None else np.broadcast_to(np.asarray(rel, dtype=np.float64).reshape(-1), (N,))
     dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    elev = _key(arrays, "/data/elevation/data", "/data/elevation")
+    if intervals is not None:
+        spec = iv.check_spec(intervals)
+        surface = None if elev is None or np.asarray(elev).size != N else np.asarray(elev, dtype=np.float64).reshape(-1)
+        rng = iv.ranges(spec, d_edges, N, surface=surface)
     parts = []
     for b0 in range(0, N, int(block)):
         b1 = min(N, b0 + int(block))
         hm = torch.as_tensor(np.ascontiguousarray(hm_all[b0:b1], dtype=np.int32)).to(dev)
         lmp = torch.as_tensor(rel[b0:b1] * LN10, dtype=torch.float64, device=dev)
         p = hitmap.products(hm, lmp, hw, percentiles=percentiles, credible=credible, depth_edges=d_edges)
+        if intervals is not None:
+            p.update(interval_products(hm, lmp, hw, torch.as_tensor(rng.lo[b0:b1]), torch.as_tensor(rng.hi[b0:b1]), percentiles=percentiles,
+                                       credible=credible, classes=None if classes is None else (cmeans, cscales)))
         if classes is not None:
             c = hitmap.class_probability(hm, lmp, hw, cmeans, cscales)
             p.update(class_probability=c["probability"], highest_marginal=c["highest_marginal"],
@@ -220,7 +270,6 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     depth_centres = 0.5 * (d_edges[1:] + d_edges[:-1])
     out["doi_index"] = j
     out["doi_depth"] = depth_centres[j]
-    elev = _key(arrays, "/data/elevation/data", "/data/elevation")
     if elev is not None and np.asarray(elev).size == N:
         out["doi_elevation"] = np.asarray(elev, dtype=np.float64).reshape(-1) - out["doi_depth"]
     ic = _key(arrays, INTERFACES + "/values/data")
@@ -241,6 +290,17 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
             out.update(class_probability=np.zeros((0, K, nz)), highest_marginal=np.zeros((0, nz), dtype=np.int32),
                        probability_of_highest_marginal=np.zeros((0, nz)))
         out["class_means"], out["class_scales"] = cmeans, cscales
+    if intervals is not None:
+        if not N:
+            M = iv.n_intervals(spec)
+            names = ["mean", "median", "mode", "credible_low", "credible_high", "credible_range"] + ["percentile_%g" % float(p) for p in percentiles]
+            out.update({"interval_" + k: np.zeros((0, M)) for k in names})
+            out["interval_total"] = np.zeros((0, M), dtype=np.int64)
+            if classes is not None:
+                out.update(interval_class_probability=np.zeros((0, cmeans.size, M)), interval_highest_marginal=np.zeros((0, M), dtype=np.int32),
+                           interval_probability_of_highest_marginal=np.zeros((0, M)))
+        out["interval_cells"], out["interval_lo"], out["interval_hi"] = rng.n_cells, rng.lo, rng.hi
+        out.update(iv.describe(spec))
     return out
 
 
@@ -250,7 +310,8 @@ def on_elevation(products, surface, edges=None, levels=None, device=None):
     over each cell of the ascending ``edges`` [E + 1], or the value at each of ``levels`` [E]; exactly one of the two.  ``surface`` [N]:
     the soundings' surface elevation (the container's /data/elevation).  Integer entries (class indices: ``highest_marginal``) are never
     averaged: with ``edges`` they are taken at the centre of each cell.  Everything else (the per-sounding and per-line entries, the
-    depth axes, ``interface_probability`` where it has a depth mesh of its own) passes through, and the result also carries
+    depth axes, the ``interval_*`` entries, which are over units and not over depth cells however many there are,
+    ``interface_probability`` where it has a depth mesh of its own) passes through, and the result also carries
     ``elevation_edges`` (and ``elevation_centres``) or ``elevation_levels``, and ``surface``."""
     from . import _lib, elevation
     mode, axis, _ = elevation.check_axis(levels=levels, edges=edges)
@@ -267,7 +328,8 @@ def on_elevation(products, surface, edges=None, levels=None, device=None):
     for k, v in products.items():
         a = np.asarray(v)
         own_mesh = k == "interface_probability" and not np.array_equal(np.asarray(products.get("interface_depth_edges", d_edges)), d_edges)
-        if a.ndim not in (2, 3) or a.shape[-1] != nz or a.shape[0] != s.size or a.size == 0 or own_mesh or a.dtype.kind not in "fiub":
+        if (k.startswith("interval_") or a.ndim not in (2, 3) or a.shape[-1] != nz or a.shape[0] != s.size or a.size == 0 or own_mesh
+                or a.dtype.kind not in "fiub"):                             # (interval_*: over units, not depth cells, whatever their count)
             out[k] = v
             continue
         t = torch.as_tensor(np.ascontiguousarray(a)).to(dev)
@@ -335,9 +397,38 @@ def parser():
                     help="also write <line>.products_elevation.npz: the per-depth-cell products averaged over the cells of a regular "
                          "elevation axis of DZ m, from BOTTOM to TOP (default: everything the line's soundings reach), snapped outward "
                          "to multiples of DZ")
+    add_interval_arguments(ap)
     ap.add_argument("--block", type=int, default=4096, help="soundings per upload (default 4096)")
     ap.add_argument("--device", default=None, help="torch device of the kernel (default cuda:0)")
     return ap
+
+
+def add_interval_arguments(ap):
+    """``--depth-intervals`` / ``--elevation-intervals E0 E1 ...`` of the command lines."""
+    ap.add_argument("--depth-intervals", type=float, nargs="+", default=None, metavar="E",
+                    help="also the products of the depth units between these edges (m below the surface; at least two, ascending): "
+                         "each the statistic of the unit's marginal posterior, written as interval_* entries")
+    ap.add_argument("--elevation-intervals", type=float, nargs="+", default=None, metavar="E",
+                    help="the same for the elevation units between these edges (m; at least two, ascending; unit 0 the lowest), under "
+                         "each sounding's own surface elevation")
+
+
+def interval_arguments(ap, a, selectors):
+    """The interval spec of parsed arguments ``a`` (None without one), checked: one of the two flags, none of ``selectors`` (names of
+    the depth / elevation selectors of the command line) beside it, at least two finite ascending edges."""
+    from . import intervals as iv
+    given = [(n, v) for n, v in (("depth", a.depth_intervals), ("elevation", a.elevation_intervals)) if v is not None]
+    if not given:
+        return None
+    if len(given) > 1:
+        ap.error("--depth-intervals and --elevation-intervals exclude each other")
+    for name in selectors:
+        if getattr(a, name.lstrip("-").replace("-", "_")) is not None:
+            ap.error("--%s-intervals and %s exclude each other" % (given[0][0], name))
+    try:
+        return dict(kind=given[0][0], edges=iv.edges_argument(given[0][1]))
+    except ValueError as e:
+        ap.error("--%s-intervals: %s" % (given[0][0], e))
 
 
 def parse_args(argv=None):
@@ -368,6 +459,7 @@ def parse_args(argv=None):
             elevation_axis_arguments(a.elevation_axis)
         except ValueError as e:
             ap.error("--elevation-axis: " + str(e))
+    a.intervals = interval_arguments(ap, a, ("--elevation-axis",))
     return a
 
 
@@ -392,7 +484,7 @@ def main(argv=None):
     for f in files:
         classes = None if a.class_means is None else (a.class_means, a.class_scales)
         out = from_results(f, device=a.device, block=a.block, percentiles=tuple(a.percentiles), credible=a.credible, doi=a.doi,
-                           classes=classes)
+                           classes=classes, intervals=a.intervals)
         dst = save(out, output_path(f))
         print("%s -> %s (%d soundings)" % (f, dst, out["mean"].shape[0]))
         if a.elevation_axis is not None:

@@ -11,7 +11,8 @@ soundings' elevation through the same plan -- the reference's ``mesh3d`` drapes 
 method (minimum curvature); this one is the Sibson surface.
 
     python -m geobipy_amd.survey_volume <directory> --dx DX --dy DY [--variables mean percentile_5 ...] [--mask MAX_DISTANCE]
-                                        [--depth D | --depth-cells I0 I1 | --elevation-axis DZ [TOP BOTTOM] | --elevation E]
+                                        [--depth D | --depth-cells I0 I1 | --elevation-axis DZ [TOP BOTTOM] | --elevation E
+                                         | --depth-intervals E0 E1 ... | --elevation-intervals E0 E1 ...]
                                         [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
 
 reads the directory's line containers and their ``<line>.products.npz`` (computed where absent: ``line_products.from_results``) and writes
@@ -28,6 +29,10 @@ horizontal slice [ny, nx] at that elevation.  The reference slices first and gri
 outside its own mesh at a level (above its surface, below its last depth edge) is NaN there, NaN propagates through the Sibson sum, and
 so a pixel is NaN at a level wherever ANY sounding that contributes to it is outside its mesh -- the volume's top follows the terrain
 from below and its bottom the deepest common reach.
+
+With ``--depth-intervals`` / ``--elevation-intervals`` (``from_lines(intervals=...)``) the maps are of UNITS: per variable [M, ny, nx],
+map m the statistic of the marginal posterior of the unit between edges m and m + 1 (the lines' ``interval_*`` products,
+geobipy_amd/intervals.py), in ``survey_volume.intervals.<variable>.npy`` beside ``survey_volume.intervals.npz``.
 """
 import argparse
 import functools
@@ -41,10 +46,16 @@ from . import elevation as elevation_axis
 from . import gridding, line_products
 
 AXES_FILE = "survey_volume.npz"
+INTERVALS_AXES_FILE = "survey_volume.intervals.npz"
 
 
 def volume_path(directory, variable):
     return os.path.join(str(directory), "survey_volume.%s.npy" % variable)
+
+
+def intervals_volume_path(directory, variable):
+    """The file of a variable's interval maps [M, ny, nx]: it carries ``intervals``, these maps have no depth axis."""
+    return os.path.join(str(directory), "survey_volume.intervals.%s.npy" % variable)
 
 
 def depth_cells(depth, depth_edges):
@@ -81,10 +92,14 @@ def depth_cells(depth, depth_edges):
     return slice(lo, hi + 1)
 
 
-def load_line(path, device=None, block=4096):
+def load_line(path, device=None, block=4096, intervals=None, classes=None, variables=()):
     """(x, y, elevation, products) of one line container: the soundings' coordinates from /data/x, /data/y, /data/elevation and the line
-    products from ``<line>.products.npz`` where present, else computed (``line_products.from_results``)."""
+    products from ``<line>.products.npz`` where present, else computed (``line_products.from_results``).  With ``intervals`` (a checked
+    spec, ``intervals.check_spec``) the saved file is used only if it holds interval entries for the identical spec; otherwise the line
+    and every one of ``variables`` as ``interval_<variable>``; otherwise the line is computed from its container, with ``classes``
+    where given."""
     from . import hdf
+    from . import intervals as iv
     arrays, _ = hdf.load_results(path)
     x = line_products._key(arrays, "/data/x/data", "/data/x")
     y = line_products._key(arrays, "/data/y/data", "/data/y")
@@ -94,11 +109,14 @@ def load_line(path, device=None, block=4096):
     elev = line_products._key(arrays, "/data/elevation/data", "/data/elevation")
     elev = np.zeros_like(x) if elev is None else np.asarray(elev, dtype=np.float64).reshape(-1)
     saved = line_products.output_path(path)
+    prod = None
     if os.path.exists(saved):
         with np.load(saved) as z:
             prod = {k: z[k] for k in z.files}
-    else:
-        prod = line_products.from_results(path, device=device, block=block)
+        if intervals is not None and not (iv.same_spec(prod, intervals) and all("interval_" + v in prod for v in variables)):
+            prod = None
+    if prod is None:
+        prod = line_products.from_results(path, device=device, block=block, intervals=intervals, classes=classes)
     if prod["mean"].shape[0] != x.size or elev.size != x.size:
         raise ValueError("%s: %d soundings but products for %d" % (path, x.size, prod["mean"].shape[0]))
     return x, y, elev, prod
@@ -107,6 +125,8 @@ def load_line(path, device=None, block=4096):
 def _columns(prod_per_line, name, n_depth):
     """([N, K, n_depth], whether the variable has a class axis) of variable ``name`` over all lines, line after line (K = 1 for the
     [N, n_depth] variables)."""
+    if name.startswith("interval_"):
+        raise ValueError("%r is a variable of units, not of depth cells: grid it with intervals=..." % name)
     parts, ndim = [], set()
     for path, prod in prod_per_line:
         if name not in prod:
@@ -148,8 +168,25 @@ def _on_elevation(plan, lines, name, surface, d_edges, mode, axis, block, out):
     return vol
 
 
+def _interval_columns(prod_per_line, name, M):
+    """([N, K, M], whether the variable has a class axis) of the unit variable ``interval_<name>`` over all lines."""
+    key = "interval_" + name
+    parts, ndim = [], set()
+    for path, prod in prod_per_line:
+        if key not in prod:
+            raise ValueError("%s: the line products hold no %r (present: %s)" % (path, key, ", ".join(sorted(k for k in prod if k.startswith("interval_")))))
+        a = np.asarray(prod[key], dtype=np.float64)
+        if a.ndim not in (2, 3) or a.shape[-1] != M:
+            raise ValueError("%s: %r is not a per-unit variable (shape %r)" % (path, key, a.shape))
+        parts.append(a.reshape(a.shape[0], -1, M))
+        ndim.add(a.ndim)
+    if len({p.shape[1] for p in parts}) != 1 or len(ndim) != 1:
+        raise ValueError("%r has a different number of classes from line to line" % key)
+    return np.concatenate(parts), ndim == {3}
+
+
 def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None, block=256, device=None, out=None,
-               list_budget_bytes=0, elevation_edges=None, elevation=None):
+               list_budget_bytes=0, elevation_edges=None, elevation=None, intervals=None, classes=None):
     """Grid the line products of the containers ``paths`` (a directory, a container or a list of them; the lines in sorted order).
 
     Returns a dict: ``x_edges``, ``y_edges`` (``gridding.centred_mesh`` of all soundings at spacing ``dx``, ``dy``), ``depth_edges``
@@ -170,8 +207,24 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
     other; ``depth_edges`` (whole) and the draped ``elevation`` surface stay in the result.  The reference slices, then grids
     (``Inference2D.elevationSlice``, then ``Point.interpolate``), so a pixel is NaN at a level wherever any sounding contributing to it
     is outside its own mesh there: NaN propagates through the Sibson sum.  Integer line products (class indices) are refused on an
-    elevation axis -- their mean means nothing; a single ``elevation`` level takes them."""
+    elevation axis -- their mean means nothing; a single ``elevation`` level takes them.
+
+    ``intervals`` (a spec of kind depth, pairs or elevation: ``line_products.from_results``, geobipy_amd/intervals.py) grids the
+    products of M UNITS instead of depth cells: variable ``mean`` is the lines' ``interval_mean`` [N, M] (the statistic of each unit's
+    marginal posterior), and comes back as [M, ny, nx] ([K, M, ny, nx] for ``class_probability``) through the same plan, with the
+    spec (``interval_kind``, ``interval_edges`` / ``interval_pairs``) in the result; the files are ``survey_volume.intervals.npz`` and
+    ``survey_volume.intervals.<variable>.npy``.  It excludes ``depth``, ``elevation_edges`` and ``elevation``.  A line's saved products
+    are used only if they hold interval entries for the identical spec; otherwise the line is computed from its container (``classes``
+    = (means, scales) where ``class_probability`` is asked for).  A pixel is NaN for a unit wherever any contributing sounding has no
+    cell of the unit.  Horizons differ from line to line: compute them per line (``from_results``)."""
     on_axis, on_level = elevation_edges is not None, elevation is not None
+    if intervals is not None:
+        from . import intervals as iv
+        if on_axis or on_level or depth is not None:
+            raise ValueError("intervals excludes depth, elevation_edges and elevation")
+        intervals = iv.check_spec(intervals)
+        if intervals["kind"] == "horizons" or "surface" in intervals:
+            raise ValueError("intervals over several lines: kind depth, pairs or elevation, the surface from each line's container")
     if on_axis and on_level:
         raise ValueError("elevation_edges and elevation exclude each other")
     if (on_axis or on_level) and depth is not None:
@@ -188,7 +241,7 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
     if int(block) < 1:
         raise ValueError("block must be positive")
     dev = torch.device(device) if device is not None else torch.device("cuda", 0)
-    lines = [(f,) + load_line(f, device=dev) for f in files]
+    lines = [(f,) + load_line(f, device=dev, intervals=intervals, classes=classes, variables=tuple(variables)) for f in files]
     d_edges = np.asarray(lines[0][4]["depth_edges"], dtype=np.float64)
     for f, _, _, _, prod in lines[1:]:
         if not np.array_equal(np.asarray(prod["depth_edges"], dtype=np.float64), d_edges):
@@ -212,21 +265,27 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
         elif on_level:
             mode, axis, _ = elevation_axis.check_axis(levels=[float(np.asarray(elevation).reshape(-1)[0])])
             res["elevation_level"] = np.float64(axis[0])
+        if intervals is not None:
+            res.update(iv.describe(intervals))
         if out is not None:
             os.makedirs(str(out), exist_ok=True)
-            np.savez(os.path.join(str(out), AXES_FILE), **res)
-        ncell = cells.stop - cells.start
+            np.savez(os.path.join(str(out), AXES_FILE if intervals is None else INTERVALS_AXES_FILE), **res)
+        ncell = cells.stop - cells.start if intervals is None else iv.n_intervals(intervals)
         surface = torch.as_tensor(elev).to(plan.device) if (on_axis or on_level) else None
         for name in variables:
             if surface is not None:
                 res[name] = _on_elevation(plan, lines, name, surface, d_edges, mode, axis, int(block), out)
                 continue
-            cols, with_classes = _columns([(ln[0], ln[4]) for ln in lines], name, nz)
-            cols = cols[:, :, cells]                                                             # [N, K, cells]
+            if intervals is not None:
+                cols, with_classes = _interval_columns([(ln[0], ln[4]) for ln in lines], name, ncell)   # [N, K, M]
+            else:
+                cols, with_classes = _columns([(ln[0], ln[4]) for ln in lines], name, nz)
+                cols = cols[:, :, cells]                                                         # [N, K, cells]
             K = cols.shape[1]
             shape = ((K,) if with_classes else ()) + (() if single else (ncell,)) + (ny, nx)
             if out is not None:
-                vol = np.lib.format.open_memmap(volume_path(out, name), mode="w+", dtype=np.float64, shape=shape)
+                vol = np.lib.format.open_memmap((volume_path if intervals is None else intervals_volume_path)(out, name), mode="w+",
+                                                dtype=np.float64, shape=shape)
             else:
                 vol = np.empty(shape, dtype=np.float64)
             flat = vol.reshape(K * ncell, ny, nx)
@@ -262,6 +321,7 @@ def parser():
                     help="volumes on a regular elevation axis of DZ m instead of the depth axis, from BOTTOM to TOP (default: everything "
                          "the soundings reach), snapped outward to multiples of DZ; index 0 is the lowest cell")
     ap.add_argument("--elevation", type=float, default=None, metavar="E", help="one map: the horizontal slice at elevation E (m)")
+    line_products.add_interval_arguments(ap)
     ap.add_argument("--block", type=int, default=256, help="columns per pass through the device (default 256)")
     ap.add_argument("--device", default=None, help="torch device of the kernels (default cuda:0)")
     ap.add_argument("--out", default=None, help="directory of the outputs (default: the first path's directory)")
@@ -297,6 +357,7 @@ def parse_args(argv=None):
         ap.error("--block must be positive")
     if len(set(a.variables)) != len(a.variables):
         ap.error("--variables holds a name twice")
+    a.intervals = line_products.interval_arguments(ap, a, ("--depth", "--depth-cells", "--elevation-axis", "--elevation"))
     return a
 
 
@@ -310,10 +371,17 @@ def main(argv=None):
         edges = functools.partial(elevation_axis.regular_axis, dz=dz, top=top, bottom=bottom)
     try:
         r = from_lines(a.paths, a.dx, a.dy, variables=tuple(a.variables), max_distance=a.mask, depth=depth, block=a.block, device=a.device,
-                       out=out, elevation_edges=edges, elevation=a.elevation)
+                       out=out, elevation_edges=edges, elevation=a.elevation, intervals=a.intervals)
     except ValueError as e:
         print("survey_volume: %s" % e, file=sys.stderr)
         return 1
+    if a.intervals is not None:
+        print("%d soundings -> %d x %d pixels, %d %s units: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
+                                                                  r["interval_edges"].size - 1, a.intervals["kind"],
+                                                                  os.path.join(out, INTERVALS_AXES_FILE)))
+        for name in a.variables:
+            print("  %s %r" % (intervals_volume_path(out, name), tuple(r[name].shape)))
+        return 0
     if "elevation_edges" in r:
         print("%d soundings -> %d x %d pixels, %d elevation cells %g .. %g m: %s" % (
             r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1, r["elevation_edges"].size - 1, r["elevation_edges"][0],

@@ -644,6 +644,22 @@ gbp_status gbp_hitmap_products(int B, int n_value, int n_depth, const int32_t *h
  * int32, every check before any launch; B == 0 launches nothing. */
 gbp_status gbp_hitmap_classes(int B, int n_value, int n_depth, const int32_t *hitmap, const double *log_mean_prior, double half_width, int K,
                               const double *means, const double *scales, double *prob, int32_t *best, double *best_p, void *stream);
+/* gbp_hitmap_intervals -- interval marginals: out[b, v, m] = sum of hitmap[b, v, z] over the depth cells lo[b, m] <= z < hi[b, m], int64
+ * [B, n_value, M] -- the reference's Histogram[:, lo:hi].marginalize(axis=1) (statistics/Histogram.py), the marginal posterior of a depth
+ * or elevation unit, for M ranges at once.  lo / hi: DEVICE int32 [B, M], half-open, clamped to [0, n_depth] by the kernel, hi <= lo: no
+ * cells (0); ranges may overlap and differ from sounding to sounding.  int64 because ten cells of a long chain's map sum beyond 2^31.
+ * One streaming read of the maps; no atomics.  1 <= M <= 4096 and n_depth <= 1024 (the row prefix and the ranges live in LDS);
+ * GBP_ERR_INVALID_ARG for the rest, for bad sizes and NULL pointers, every check before any launch; B == 0 launches nothing.
+ * gbp_hitmap_products_i64 / gbp_hitmap_classes_i64 -- gbp_hitmap_products / gbp_hitmap_classes over int64 maps (such marginals, with
+ * M in the place of n_depth): the same kernels instantiated on the count type, the same bits on the same counts (counts < 2^53). */
+gbp_status gbp_hitmap_intervals(int B, int n_value, int n_depth, int M, const int32_t *hitmap, const int32_t *lo, const int32_t *hi,
+                                int64_t *out, void *stream);
+gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
+                                   int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
+                                   void *stream);
+gbp_status gbp_hitmap_classes_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
+                                  int K, const double *means, const double *scales, double *prob, int32_t *best, double *best_p,
+                                  void *stream);
 
 /* [host] Results containers (geobipy_amd/h5lite.py; no reference counterpart -- the reference stores its hit maps dense): the rows of
  * a conductivity-depth hit map held as runs (row r owns runs ptr[r] .. ptr[r + 1] - 1; run q holds value[q] from cell start[q] of the row
