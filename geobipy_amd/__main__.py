@@ -45,7 +45,29 @@ def parse(argv=None):
     p.add_argument("--traces", default="1",
                    help="per-iteration misfit / acceptance traces of the containers: 1 = the reference's arrays in full (2 n_markov_chains "
                         "columns), an integer stride > 1 or 'auto' (at most 4096 entries per sounding) keeps every stride-th entry, 0 = none")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--units-depth", type=float, nargs="+", default=None, metavar="E",
+                   help="sampled unit posteriors (conductance, transverse resistance: unit_* in the summaries) of the units between these depths, m")
+    g.add_argument("--units-elevation", type=float, nargs="+", default=None, metavar="E",
+                   help="the same for the units between these elevations (m) under each sounding's surface")
+    p.add_argument("--unit-kinds", nargs="+", choices=("arithmetic", "harmonic"), default=["arithmetic", "harmonic"],
+                   help="unit means to accumulate (default both)")
+    p.add_argument("--first-above", type=float, nargs="+", default=[], metavar="S",
+                   help="posterior of the depth to the first layer at or above these conductivities, S/m (first_depth_* in the summaries)")
+    p.add_argument("--first-below", type=float, nargs="+", default=[], metavar="S", help="... at or below these conductivities, S/m")
     a = p.parse_args(argv)
+    a.units = None
+    if a.units_depth is not None or a.units_elevation is not None:
+        from .intervals import edges_argument
+        try:
+            a.units = (dict(kind="depth", edges=edges_argument(a.units_depth)) if a.units_depth is not None
+                       else dict(kind="elevation", edges=edges_argument(a.units_elevation)))
+        except ValueError as e:
+            p.error(str(e))
+    if len(a.first_above) + len(a.first_below) > 4 or any(not (v > 0.0 and v < float("inf")) for v in a.first_above + a.first_below):
+        p.error("--first-above / --first-below: at most 4 thresholds in all, each finite and positive (S/m)")
+    if (a.units is not None or a.first_above or a.first_below) and a.no_hitmap:
+        p.error("--units-* / --first-* need the hit map (drop --no-hitmap)")
     a.traces = "auto" if a.traces == "auto" else (int(a.traces) or None)
     if a.seed is not None:
         a.seed = int(a.seed)
@@ -76,7 +98,8 @@ def main(argv=None):
     res = survey.infer(a.options_file, seed=a.seed, index=a.index, fiducial=a.fiducial, line_number=a.line_number,
                        exact_jacobian=a.exact_jacobian, hitmap=not a.no_hitmap, hankel_eps=a.hankel_eps, schedule=a.schedule, chunk=a.chunk, traces=a.traces, results_directory=containers,
                        container=None if a.container == "auto" else a.container, data_directory=a.data_directory,
-                       data_filename=a.data_filename)
+                       data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
+                       first_below=tuple(a.first_below))
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

@@ -1170,6 +1170,81 @@ __device__ inline void hitmap_add(const RjOpt& o, int32_t* hm, const double* ec,
     }
 }
 
+// Sampled unit posteriors (gbp_rj_options.n_units / n_first; include/geobipy_amd.h states the rule): `weight` counts of model
+// (ec, sc, kc) added to chain b's unit histograms and depth-to-threshold histograms.  Lane i of the chain's W lanes owns units
+// i, i + W, ... and thresholds likewise and walks the layers serially, so a count has one owner and plain adds suffice (as in
+// hitmap_add8: the counters are also zeroed with plain stores by the same wave, in program order).  Called where the hit map is
+// settled, with the same dwell.  Not inlined: with the feature off the callers keep the registers they had.
+__device__ inline bool units_on(const gbp_rj_chains& c) { return c.unit_hist != nullptr || c.first_hist != nullptr; }
+
+template <int W>
+__device__ __noinline__ void units_add(const RjOpt& o, const gbp_rj_chains& c, size_t b, const double* ec, const double* sc, int kc,
+                                       double lmp, int i, int weight)
+{
+    const double inv_ln10 = 0.43429448190325182765, Wd = o.value_half_width;
+    const int M = o.n_units, nv = o.n_value_bins;
+    if (c.unit_hist != nullptr) {
+        const int Q = (o.unit_kinds & 1) + ((o.unit_kinds >> 1) & 1);
+        for (int m = i; m < M; m += W) {
+            const double z0 = c.unit_z[(b * M + m) * 2], z1 = c.unit_z[(b * M + m) * 2 + 1];
+            const double dz = z1 - z0;
+            if (!(dz > 0.0)) continue;                           // an empty unit has no posterior
+            double S = 0.0, T = 0.0, top = 0.0;
+            for (int l = 0; l < kc && top < z1; ++l) {
+                const double bot = l < kc - 1 ? ec[l] : INF;
+                const double ov = fmax(0.0, fmin(bot, z1) - fmax(top, z0));
+                if (ov > 0.0) {
+                    const double sl = sc[l];
+                    S = __dadd_rn(S, __dmul_rn(sl, ov));
+                    T = __dadd_rn(T, __ddiv_rn(ov, sl));
+                }
+                top = bot;
+            }
+            int q = 0;
+#pragma unroll
+            for (int kind = 0; kind < 2; ++kind) {
+                if (!((o.unit_kinds >> kind) & 1)) continue;
+                const double x = kind == 0 ? __ddiv_rn(S, dz) : __ddiv_rn(dz, T);
+                const double v = (rj_log(x) - lmp) * inv_ln10;
+                const int bin = min(max((int)floor((v + Wd) / (2.0 * Wd) * (double)nv), 0), nv - 1);
+                c.unit_hist[((b * Q + q) * nv + bin) * M + m] += weight;
+                ++q;
+            }
+        }
+    }
+    if (c.first_hist != nullptr) {
+        const int nf = o.n_first, nd = o.n_depth_bins;
+        for (int q = i; q < nf; q += W) {
+            const double t = o.first_threshold[q];
+            const bool above = o.first_direction[q] > 0;
+            double top = 0.0;
+            int l = 0;
+            for (; l < kc; ++l) {
+                const double sl = sc[l];
+                if (above ? sl >= t : sl <= t) break;
+                top = l < kc - 1 ? ec[l] : INF;
+            }
+            if (l < kc) c.first_hist[(b * nf + q) * nd + min(max((int)floor(top / o.depth_bin_width), 0), nd - 1)] += weight;
+            else c.first_none[b * nf + q] += weight;
+        }
+    }
+}
+
+// (burn-in reset, W lanes of chain b)
+template <int W>
+__device__ __noinline__ void units_zero(const RjOpt& o, const gbp_rj_chains& c, size_t b, int i)
+{
+    if (c.unit_hist != nullptr) {
+        const size_t n = (size_t)((o.unit_kinds & 1) + ((o.unit_kinds >> 1) & 1)) * o.n_value_bins * o.n_units;
+        for (size_t q = i; q < n; q += W) c.unit_hist[b * n + q] = 0;
+    }
+    if (c.first_hist != nullptr) {
+        const size_t n = (size_t)o.n_first * o.n_depth_bins;
+        for (size_t q = i; q < n; q += W) c.first_hist[b * n + q] = 0;
+        for (int q = i; q < o.n_first; q += W) c.first_none[b * o.n_first + q] = 0;
+    }
+}
+
 __device__ inline double group_sum8(double v)
 {
     // (the pairs of the xor butterfly: lane ^ 1, lane ^ 2, then the other quad -- whose four lanes hold one value)
@@ -1183,7 +1258,8 @@ __device__ inline double group_sum8(double v)
 // all lanes of a chain sit in one wave, so program order is the only ordering needed between them.
 // (have_regs, W == 8: entry i of the post-step rows is in e_now / s_now -- the interface histogram then costs no loads, and the counters
 //  are atomic adds whose result nobody waits for: the stage is a latency chain, every read-modify-write was a trip to memory)
-template <int W>
+// (UNITS: the sampled unit posteriors are compiled in -- the instantiations without them are the code they were before the feature)
+template <int W, bool UNITS = false>
 __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32_t iter, int accumulate, size_t b, int i,
                                    int kc, const double* ec, const double* sc, double post, double best_prev, double misfit_now,
                                    const Levels& lev, double lmp, int dwell, double height_now, bool accepted, bool have_regs = false,
@@ -1222,6 +1298,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
                 if (c.hitmap != nullptr) {
                     for (size_t q = i; q < nh; q += W) c.hitmap[b * nh + q] = 0;
                     dwell = 0;
+                    if (UNITS && units_on(c)) units_zero<W>(o, c, b, i);
                 }
                 if (i == 0) c.burned_in_iteration[b] = bi;
             }
@@ -1269,6 +1346,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
         if (accumulate) dwell += 1;
         if (finished && dwell > 0) {                             // the chain stops here: settle its last model
             hitmap_add<W>(o, c.hitmap + b * nh, ec, sc, kc, lmp, i, dwell);
+            if (UNITS && units_on(c)) units_add<W>(o, c, b, ec, sc, kc, lmp, i, dwell);
             dwell = 0;
         }
         if (i == 0) c.hit_dwell[b] = dwell;
@@ -1286,6 +1364,7 @@ struct StepState {
     int status;
 };
 
+template <bool UNITS = false>
 __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains& c, uint32_t iter, int accumulate, int min_k, int b,
                                             int lane, unsigned char* sh_dyn, StepState* st = nullptr)
 {   // one wave per chain; chains whose current and proposed models both have at most min_k layers are left to accept8_body
@@ -1400,6 +1479,7 @@ __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains&
     int dwell = c.hitmap != nullptr ? c.hit_dwell[b] : 0;        // iterations the current model is still owed to the hit map
     if (accept && dwell > 0) {                                   // the model changes: settle the old one first
         hitmap_add<64>(o, c.hitmap + (size_t)b * nh, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
+        if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
         dwell = 0;
         wave_sync();
     }
@@ -1428,7 +1508,7 @@ __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains&
             if (o.solve_height) const_cast<double*>(c.height)[b] = height_now;
         }
     }
-    const int bk = bookkeeping<64>(o, c, iter, accumulate, (size_t)b, lane, accept ? k : k_prev, accept ? e : c.edges + (size_t)b * K,
+    const int bk = bookkeeping<64, UNITS>(o, c, iter, accumulate, (size_t)b, lane, accept ? k : k_prev, accept ? e : c.edges + (size_t)b * K,
                                    accept ? c.sigma_p + (size_t)b * K : c.sigma + (size_t)b * K, accept ? prior_p + like_p : prior_c + like_c,
                                    best_prev, accept ? misfit_p : misfit_c, select_levels(accept, lev_p, lev_c), lmp, dwell, height_now, accept);
     if (lane == 0 && c.step_flags != nullptr) c.step_flags[b] = (accept ? 1 : 0) | (bk & 15);
@@ -1579,7 +1659,7 @@ __device__ __forceinline__ double accept8_reverse(const RjOpt& o, const gbp_rj_c
 }
 
 // `b`: the chain of this lane's 8-lane group, or >= c.B for an idle group; sh_dyn: PR[8][N]
-template <bool TRIPS>
+template <bool TRIPS, bool UNITS = false>
 __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains& c, uint32_t iter, int accumulate, int lane, int b,
                                              unsigned char* sh_dyn, int b_idle = 0, StepState* st = nullptr)
 {
@@ -1759,6 +1839,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
     if (c.hitmap != nullptr) {                       // the model changes: settle the old one in the hit map first
         const bool on = accept && dwell > 0;
         hitmap_add8(o, c.hitmap + bb * nh, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, base, dwell, on);
+        if (UNITS && on && units_on(c)) units_add<8>(o, c, bb, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, dwell);
         if (on) dwell = 0;
     }
     if (accept && one_trip) {
@@ -1800,7 +1881,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
             if (o.solve_height) const_cast<double*>(c.height)[bb] = height_now;
         }
     }
-    const int bk = bookkeeping<8>(o, c, iter, accumulate, bb, i, accept ? k : k_prev, accept ? e : c.edges + bb * K,
+    const int bk = bookkeeping<8, UNITS>(o, c, iter, accumulate, bb, i, accept ? k : k_prev, accept ? e : c.edges + bb * K,
                                   accept ? c.sigma_p + bb * K : c.sigma + bb * K, accept ? prior_p + like_p : prior_c + like_c, best_prev,
                                   accept ? misfit_p : misfit_c, select_levels(accept, lev_p, lev_c), lmp, dwell, height_now, accept, one_trip,
                                   accept ? pre.e_i : pre.ce_i, accept ? sp_ic : pre.cs_i);
@@ -1808,16 +1889,17 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
     if (i == 0 && c.step_flags != nullptr) c.step_flags[bb] = (accept ? 1 : 0) | (bk & 15);
 }
 
+template <bool UNITS>
 __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_accept8(RjOpt o, gbp_rj_chains c, uint32_t iter, int accumulate, int n_packed)
 {   // (workgroups as in k_rj_newton8)
     GBP_RJ_RAISE_PRIO();
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_dyn[];
     if ((int)blockIdx.x >= n_packed) {                 // (the deep chains' scanning workgroups)
         const int g = (int)blockIdx.x - n_packed;
-        for_deep_chains(g, accept_is_deep(c, g * 64 + (int)threadIdx.x, 8), [&](int bb) { accept_body(o, c, iter, accumulate, 8, bb, threadIdx.x, sh_dyn); });
+        for_deep_chains(g, accept_is_deep(c, g * 64 + (int)threadIdx.x, 8), [&](int bb) { accept_body<UNITS>(o, c, iter, accumulate, 8, bb, threadIdx.x, sh_dyn); });
         return;
     }
-    accept8_body<true>(o, c, iter, accumulate, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
+    accept8_body<true, UNITS>(o, c, iter, accumulate, threadIdx.x, blockIdx.x * 8 + (threadIdx.x >> 3), sh_dyn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1832,6 +1914,7 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_accept8(RjOpt o
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t step_is_deep(int k_now, int kr) { return max(k_now, kr) > 8 ? 1 : 0; }
 
+template <bool UNITS>
 __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_step8(RjOpt o, gbp_rj_chains c, uint32_t iter, int accumulate, int n_packed,
                                                  const int32_t* __restrict__ deep_cur, int32_t* __restrict__ deep_next)
 {
@@ -1844,7 +1927,7 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_step8(RjOpt o, 
             StepState st{};
             const int k_before = c.k[bb];
             const bool frozen = o.schedule == 1 && c.status[bb] != 0;
-            accept_body(o, c, iter, accumulate, 0, bb, lane, sh_dyn, &st);
+            accept_body<UNITS>(o, c, iter, accumulate, 0, bb, lane, sh_dyn, &st);
             if (frozen) { st.accepted = false; st.k_now = k_before; }
             wave_sync();
             const double* e_row = (st.accepted ? c.edges_r : c.edges) + (size_t)bb * K;
@@ -1863,7 +1946,7 @@ __global__ __launch_bounds__(64) GBP_RJ_LATENCY_KERNEL void k_rj_step8(RjOpt o, 
     const bool frozen = o.schedule == 1 && c.status[bq] != 0;
     // (a chain flagged deep belongs to a scanning workgroup of this launch, which rewrites k_r and the move for iteration + 1 while
     //  this group may still be reading them: a group acts on its chain only when deep_cur says so -- idle groups get chain index c.B)
-    accept8_body<true>(o, c, iter, accumulate, lane, mine ? b : c.B, sh_dyn, 0, &st);
+    accept8_body<true, UNITS>(o, c, iter, accumulate, lane, mine ? b : c.B, sh_dyn, 0, &st);
     if (frozen) { st.accepted = false; st.k_now = k_before; }
     wave_sync();
     if (mine) {                                        // (group-uniform; the reads inside stay within the chain's own 8 lanes)
@@ -1901,6 +1984,7 @@ __global__ __launch_bounds__(1024) void k_rj_order_by_layers(gbp_rj_chains c, in
 }
 
 // Settles what the chains' current models are still owed in the hit map (call before reading it).
+template <bool UNITS>
 __global__ __launch_bounds__(64) void k_rj_flush(RjOpt o, gbp_rj_chains c)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -1909,6 +1993,7 @@ __global__ __launch_bounds__(64) void k_rj_flush(RjOpt o, gbp_rj_chains c)
     const int K = o.max_layers;
     hitmap_add<64>(o, c.hitmap + (size_t)b * o.n_depth_bins * o.n_value_bins, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b],
                    c.log_mean_prior[b], lane, dwell);
+    if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b], c.log_mean_prior[b], lane, dwell);
     __syncthreads();
     if (lane == 0) c.hit_dwell[b] = 0;
 }
@@ -2307,6 +2392,16 @@ __device__ GBP_STAGE_ATTR void stage_accept(const PersistentCtx* x, uint32_t ite
     else accept_body(*x->o, c, iter, accumulate, 8, x->b, lane, x->sh_dyn);
 }
 
+// (the same with the sampled unit posteriors: a stage of its own, chosen by a uniform branch, so that chains without them run the stage
+//  they always ran -- as template parameters of the kernel, the two extra instantiations moved the register allocation of the OTHER stages)
+__device__ GBP_STAGE_ATTR void stage_accept_units(const PersistentCtx* x, uint32_t iter, int accumulate, int lane)
+{
+    const gbp_rj_chains& c = *x->c;
+    const int kr = c.k_r[x->b], kp = c.k[x->b];
+    if ((kr > kp ? kr : kp) <= 8) accept8_body<false, true>(*x->o, c, iter, accumulate, lane, lane < 8 ? x->b : c.B, x->sh_dyn, x->b);
+    else accept_body<true>(*x->o, c, iter, accumulate, 8, x->b, lane, x->sh_dyn);
+}
+
 // (launch bound 1024 although 64 ... 256 threads are launched: it caps the kernel AND the stage functions it calls at 128 VGPRs,
 //  the budget the same code has in the lock-step kernels; without it every stage takes ~250 registers: one wave per SIMD)
 // Stage clock of chain 0 (s_memtime ticks of the 100 MHz constant clock, accumulated over the launches since the last reset):
@@ -2437,7 +2532,7 @@ __global__ GBP_RJ_PERSISTENT_BOUNDS void k_rj_persistent(RjOpt o_arg, gbp_rj_cha
         else stage_forward(&sh_x);                                // Inference1D.py:572-597: forward + chi^2 + logL of the proposal
         __syncthreads();
         tick(3);
-        if (wave == 0) { GBP_RJ_SERIAL_PRIO(GBP_RJ_PERSISTENT_PRIO); stage_accept(&sh_x, iter, accumulate, lane); GBP_RJ_SERIAL_PRIO(0); }
+        if (wave == 0) { GBP_RJ_SERIAL_PRIO(GBP_RJ_PERSISTENT_PRIO); if (units_on(c_arg)) stage_accept_units(&sh_x, iter, accumulate, lane); else stage_accept(&sh_x, iter, accumulate, lane); GBP_RJ_SERIAL_PRIO(0); }
         __syncthreads();
         tick(4);
         if (clocked) GBP_RJ_TICKS[5] += 1;
@@ -2642,6 +2737,8 @@ gbp_rj_chains slice_chains(const gbp_rj_options& o, const gbp_rj_chains& c, int 
     GBP_OFF(best_rel, Gr) GBP_OFF(best_add, Ga) GBP_OFF(iteration0, 1)
     GBP_OFF(height_p, 1) GBP_OFF(height0, 1) GBP_OFF(height_hist, nb) GBP_OFF(best_height, 1) GBP_OFF(step_flags, 1)
     GBP_OFF(trace_misfit, (size_t)o.trace_length) GBP_OFF(trace_accept, (size_t)o.trace_length) GBP_OFF(best_iteration, 1)
+    const size_t nu = (size_t)o.n_units, nq = (size_t)((o.unit_kinds & 1) + ((o.unit_kinds >> 1) & 1)), nf = (size_t)o.n_first;
+    GBP_OFF(unit_z, nu * 2) GBP_OFF(unit_hist, nq * nv * nu) GBP_OFF(first_hist, nf * nd) GBP_OFF(first_none, nf)
 #undef GBP_OFF
     return s;
 }
@@ -2670,6 +2767,19 @@ gbp_status rj_check(const gbp_rj_options* o, const gbp_rj_chains* c)
         return fail(GBP_ERR_INVALID_ARG, "trace_misfit and trace_accept come together, with trace_every >= 1 and trace_length >= 1%s");
     if ((c->rel_hist != nullptr) != (c->add_hist != nullptr) || (c->rel_hist && o->n_error_bins < 1))
         return fail(GBP_ERR_INVALID_ARG, "rel_hist and add_hist come together, with n_error_bins >= 1%s");
+    // sampled unit posteriors: settled and zeroed with the hit map (they share hit_dwell)
+    if (o->n_units < 0 || o->n_units > 16 || o->n_first < 0 || o->n_first > 4) return fail(GBP_ERR_INVALID_ARG, "n_units must be in [0, 16], n_first in [0, 4]%s");
+    if ((o->n_units > 0) != (c->unit_hist != nullptr) || (c->unit_hist != nullptr) != (c->unit_z != nullptr))
+        return fail(GBP_ERR_INVALID_ARG, "unit_z and unit_hist come together, with n_units >= 1%s");
+    if ((o->n_first > 0) != (c->first_hist != nullptr) || (c->first_hist != nullptr) != (c->first_none != nullptr))
+        return fail(GBP_ERR_INVALID_ARG, "first_hist and first_none come together, with n_first >= 1%s");
+    if ((c->unit_hist || c->first_hist) && !c->hitmap)
+        return fail(GBP_ERR_INVALID_ARG, "unit posteriors (unit_hist / first_hist) need the hit map: they are settled with its dwell times%s");
+    if (o->n_units > 0 && (o->unit_kinds < 1 || o->unit_kinds > 3)) return fail(GBP_ERR_INVALID_ARG, "unit_kinds must be 1 (arithmetic), 2 (harmonic) or 3 (both)%s");
+    for (int q = 0; q < o->n_first; ++q) {
+        if (!(std::isfinite(o->first_threshold[q]) && o->first_threshold[q] > 0.0)) return fail(GBP_ERR_INVALID_ARG, "first_threshold must be finite and positive%s");
+        if (o->first_direction[q] != 1 && o->first_direction[q] != -1) return fail(GBP_ERR_INVALID_ARG, "first_direction must be +1 or -1%s");
+    }
     const void* need[] = {c->data, c->height, c->log_mean_prior, c->k, c->edges, c->sigma, c->rel, c->add, c->pred, c->J, c->prior,
                           c->like, c->misfit, c->action, c->k_r, c->nl_a, c->nl_b, c->nl_c, c->edges_r, c->sigma_r, c->thk_r, c->rel_p,
                           c->add_p, c->pred_r, c->J_r, c->chol, c->log_prop, c->sigma_p, c->pred_p, c->misfit_p, c->like_p,
@@ -2749,8 +2859,9 @@ gbp_status gbp_rj_accept(const gbp_rj_options* o, const gbp_rj_chains* c, int64_
     if (st != GBP_OK || c->B == 0) return st;
     const int n_packed = (c->B + 7) / 8, n_deep = o->max_layers > 8 ? (c->B + 63) / 64 : 0;      // (deep: scanning workgroups of 64 chains)
     const size_t lds8 = (size_t)8 * o->n_channels * sizeof(double), lds_deep = rj::Lds::bytes(o->max_layers, o->n_channels);
-    hipLaunchKernelGGL(rj::k_rj_accept8, dim3(n_packed + n_deep), dim3(64), n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream,
-                       rj::extend(*o), *c, (uint32_t)iteration, accumulate, n_packed);
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr;     // (their code is in instantiations of its own)
+    hipLaunchKernelGGL(units ? rj::k_rj_accept8<true> : rj::k_rj_accept8<false>, dim3(n_packed + n_deep), dim3(64),
+                       n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, accumulate, n_packed);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
@@ -3168,8 +3279,9 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
                 const size_t lds = std::max((size_t)8 * o->n_channels * sizeof(double), n_deep ? rj::Lds::bytes(K, o->n_channels) : (size_t)0);
                 const int32_t* cur = t.flags + (size_t)(it & 1) * nB;
                 int32_t* nxt = t.flags + (size_t)((it + 1) & 1) * nB;
-                hipLaunchKernelGGL(rj::k_rj_step8, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o), t.c, (uint32_t)iter, accumulate,
-                                   n_packed, cur, nxt);
+                const bool units = t.c.unit_hist != nullptr || t.c.first_hist != nullptr;
+                hipLaunchKernelGGL(units ? rj::k_rj_step8<true> : rj::k_rj_step8<false>, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o),
+                                   t.c, (uint32_t)iter, accumulate, n_packed, cur, nxt);
                 return GBP_OK;
             }
             return gbp_rj_accept(&t.o, &t.c, iter, accumulate, t.q);
@@ -3300,7 +3412,8 @@ gbp_status gbp_rj_flush_posteriors(const gbp_rj_options* o, const gbp_rj_chains*
 {
     gbp_status st = rj_check(o, c);
     if (st != GBP_OK || c->B == 0 || !c->hitmap) return st;
-    hipLaunchKernelGGL(rj::k_rj_flush, dim3(c->B), dim3(64), 0, (hipStream_t)stream, rj::extend(*o), *c);
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr;
+    hipLaunchKernelGGL(units ? rj::k_rj_flush<true> : rj::k_rj_flush<false>, dim3(c->B), dim3(64), 0, (hipStream_t)stream, rj::extend(*o), *c);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }

@@ -10,6 +10,8 @@ kernels.  With the reference's seed it reproduces the reference's chain decision
 batches their kernel calls: one forward launch and one Jacobian launch per phase instead of one per sounding.
 Posterior hit-maps / HDF output of the reference (row f-4) are not part of this module.
 """
+import math
+
 import numpy as np
 
 from . import rjmcmc
@@ -163,6 +165,83 @@ def initial_state(engine, data, o, error_model=None, z_move=None, geom_moves=Non
     return (sp, vp, rp, ap), rjmcmc.ChainState(none, sigma, rel, add, pred, J, prior, like, misfit, None if z_move is None else z_move.z0, geom)
 
 
+UNIT_KINDS = ("arithmetic", "harmonic")
+
+
+def unit_kind_bits(kinds):
+    """("arithmetic", "harmonic") -> gbp_rj_options.unit_kinds (bit 0 arithmetic, bit 1 harmonic); an int 1 .. 3 passes through."""
+    if isinstance(kinds, (int, np.integer)):
+        bits = int(kinds)
+    else:
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        if any(k not in UNIT_KINDS for k in kinds):
+            raise ValueError("unit_kinds: each of %s, got %r" % (" / ".join(UNIT_KINDS), kinds))
+        bits = sum(1 << UNIT_KINDS.index(k) for k in set(kinds))
+    if bits < 1 or bits > 3:
+        raise ValueError("unit_kinds must name arithmetic, harmonic or both")
+    return bits
+
+
+def unit_kind_names(bits):
+    return tuple(n for i, n in enumerate(UNIT_KINDS) if bits >> i & 1)
+
+
+def check_unit_bounds(units):
+    """Unit bounds [..., M, 2] as float64, refused unless 0 <= top <= bottom, finite, 1 <= M <= 16."""
+    z = np.asarray(units, dtype=np.float64)
+    if z.ndim < 2 or z.shape[-1] != 2 or not 1 <= z.shape[-2] <= 16:
+        raise ValueError("units must be [M, 2] (top, bottom) with 1 <= M <= 16")
+    if not np.all(np.isfinite(z)) or np.any(z[..., 0] < 0.0) or np.any(z[..., 1] < z[..., 0]):
+        raise ValueError("unit bounds must be finite with 0 <= top <= bottom (metres below the surface)")
+    return z
+
+
+def check_first(thresholds, directions):
+    """Thresholds (S/m, finite and positive) and directions (+1: first layer at or above, -1: at or below), at most 4."""
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    d = np.asarray(directions, dtype=np.int64).reshape(-1)
+    if t.size != d.size or t.size > 4:
+        raise ValueError("first: as many directions as thresholds, at most 4")
+    if not np.all(np.isfinite(t) & (t > 0.0)):
+        raise ValueError("first: every threshold must be finite and positive (S/m)")
+    if not np.all(np.abs(d) == 1):
+        raise ValueError("first: every direction must be +1 or -1")
+    return t, d
+
+
+def unit_means(edges, values, z0, z1):
+    """(dz, S, T) of the unit [z0, z1] of the model (interior interface depths ``edges`` ascending, layer conductivities ``values``):
+    layer l spans [top_l, bot_l) with top_0 = 0, bot_{k-1} = +inf; ov_l = max(0, min(bot_l, z1) - max(top_l, z0)); conductance
+    S = sum_l s_l ov_l and transverse resistance T = sum_l ov_l / s_l over the layers with ov_l > 0, l ascending, one rounded
+    multiply / divide and one rounded add per term (numpy float64 scalars: no fused multiply-add).  The arithmetic unit mean is S / dz,
+    the harmonic one dz / T.  The device sampler evaluates the same expressions in the same order."""
+    f = np.float64
+    z0, z1 = f(z0), f(z1)
+    S, T, top = f(0.0), f(0.0), f(0.0)
+    k = len(values)
+    for l in range(k):
+        if not top < z1:
+            break
+        bot = f(edges[l]) if l < k - 1 else f(np.inf)
+        ov = max(f(0.0), min(bot, z1) - max(top, z0))
+        if ov > 0.0:
+            s = f(values[l])
+            S = S + s * ov
+            T = T + ov / s
+        top = bot
+    return z1 - z0, S, T
+
+
+def first_layer(edges, values, threshold, direction):
+    """Depth of the top of the shallowest layer with conductivity >= ``threshold`` (direction +1) or <= it (-1); None: no such layer."""
+    top = 0.0
+    for l, s in enumerate(values):
+        if (s >= threshold) if direction > 0 else (s <= threshold):
+            return top
+        top = float(edges[l]) if l < len(values) - 1 else float("inf")
+    return None
+
+
 class Posteriors:
     """The posteriors Inference1D.update accumulates every iteration (Model.update_posteriors, model/Model.py:810-847;
     RectilinearMesh1D.update_posteriors, mesh/RectilinearMesh1D.py:1595-1610), on the reference's grids
@@ -173,7 +252,11 @@ class Posteriors:
     (tests/test_rjmcmc.py)."""
 
     def __init__(self, max_cells, max_edge, min_width, value_mean, factor=10.0, n_value_bins=250, ratio=0.5,
-                 relative_error_bounds=None, additive_error_bounds=None, n_error_bins=99, height_edges=None, geometry_edges=None):
+                 relative_error_bounds=None, additive_error_bounds=None, n_error_bins=99, height_edges=None, geometry_edges=None,
+                 units=None, unit_kinds=("arithmetic", "harmonic"), first=None):
+        """``units`` [M, 2] (top, bottom; m below the surface), ``unit_kinds`` and ``first`` = (thresholds S/m, directions +-1): the sampled
+        unit posteriors (``unit_means`` / ``first_layer`` state the rule) -- ``unit_hist`` [Q, n_value_bins, M], ``first_hist``
+        [T, n_depth_bins], ``first_none`` [T]."""
         self.ratio = ratio
         # height (Point.set_z_posterior :1010-1017): the cells of the uniform prior, when the height is sampled
         self.height_edges = None if height_edges is None else np.asarray(height_edges, dtype=np.float64)
@@ -196,10 +279,52 @@ class Posteriors:
         self.n_cells = np.zeros(int(max_cells) + 1, dtype=np.int64)
         self.edges = np.zeros(self.depth_centres.size, dtype=np.int64)
         self.values = np.zeros((n_value_bins, self.depth_centres.size), dtype=np.int64)
+        # sampled unit posteriors: the device's expressions (csrc/gbp_rjmcmc.h units_add), value axis as the device's hit map bins it
+        self.units = None if units is None else check_unit_bounds(units)
+        self.unit_kinds = unit_kind_bits(unit_kinds) if self.units is not None else 0
+        self.log_mean_prior = np.log(np.float64(value_mean))
+        self.value_half_width = np.float64(4.0 * math.log(1.0 + factor) / math.log(10.0))
+        self.depth_bin_width = np.float64(0.5 * min_width)
+        n_q = (self.unit_kinds & 1) + (self.unit_kinds >> 1 & 1)
+        self.unit_hist = np.zeros((n_q, n_value_bins, 0 if self.units is None else self.units.shape[0]), dtype=np.int64)
+        self.first_threshold, self.first_direction = check_first(*(first if first is not None else ((), ())))
+        self.first_hist = np.zeros((self.first_threshold.size, self.depth_centres.size), dtype=np.int64)
+        self.first_none = np.zeros(self.first_threshold.size, dtype=np.int64)
+        self.unit_edge_distance = []          # |fractional bin position - nearest integer| of every value binned: (kind row, unit, distance)
 
     def reset(self):
-        for a in (self.n_cells, self.edges, self.values, self.relative_error, self.additive_error, self.height) + tuple(self.geometry.values()):
+        for a in (self.n_cells, self.edges, self.values, self.relative_error, self.additive_error, self.height, self.unit_hist,
+                  self.first_hist, self.first_none) + tuple(self.geometry.values()):
             a[:] = 0
+        del self.unit_edge_distance[:]
+
+    def value_bin(self, x):
+        """Bin of conductivity ``x`` on the value axis, the device's expression; also the fractional position it was floored from."""
+        v = (np.log(np.float64(x)) - self.log_mean_prior) * np.float64(0.43429448190325182765)
+        n = self.unit_hist.shape[1]
+        pos = (v + self.value_half_width) / (np.float64(2.0) * self.value_half_width) * np.float64(n)
+        return int(min(max(math.floor(pos), 0), n - 1)), float(pos)
+
+    def update_units(self, edges, values, weight=1):
+        """Adds one sampled model to the unit posteriors (``update`` calls it)."""
+        if self.units is not None:
+            for m, (z0, z1) in enumerate(self.units):
+                dz, S, T = unit_means(edges, values, z0, z1)
+                if not dz > 0.0:
+                    continue
+                q = 0
+                for kind in range(2):
+                    if self.unit_kinds >> kind & 1:
+                        b, pos = self.value_bin(S / dz if kind == 0 else dz / T)
+                        self.unit_hist[q, b, m] += weight
+                        self.unit_edge_distance.append((q, m, abs(pos - round(pos))))
+                        q += 1
+        for q, (t, d) in enumerate(zip(self.first_threshold, self.first_direction)):
+            top = first_layer(edges, values, t, d)
+            if top is None:
+                self.first_none[q] += weight
+            else:
+                self.first_hist[q, int(min(max(math.floor(np.float64(top) / self.depth_bin_width), 0), self.first_hist.shape[1] - 1))] += weight
 
     def update(self, edges, values, rel=None, add=None, z=None, geom=None):
         """``edges``: interior interface depths; ``values``: layer conductivities; ``rel`` / ``add``: error levels; ``z``: height;
@@ -219,6 +344,8 @@ class Posteriors:
                         hist[g_, np.clip(np.searchsorted(grid[g_], np.log10(xv), side="right") - 1, 0, hist.shape[1] - 1)] += 1
         k = values.size
         self.n_cells[k] += 1
+        if self.units is not None or self.first_threshold.size:
+            self.update_units(edges, values)
         if k > 1:
             r = np.exp(np.diff(np.log(values)))
             d = edges[(r <= 1.0 - self.ratio) | (r >= 1.0 + self.ratio)]
@@ -304,7 +431,9 @@ class Inference1D:
                                      relative_error_bounds=(o["minimum_relative_error"], o["maximum_relative_error"]),
                                      additive_error_bounds=(o["minimum_additive_error"], o["maximum_additive_error"]),
                                      height_edges=None if self.z_move is None else self.z_move.edges,
-                                     geometry_edges={m.name: m.edges for m in self.geom_moves})
+                                     geometry_edges={m.name: m.edges for m in self.geom_moves},
+                                     # sampled unit posteriors (options units / unit_kinds / first: DeviceChains' keywords)
+                                     units=o.get("units"), unit_kinds=o.get("unit_kinds") or UNIT_KINDS, first=o.get("first"))
 
     # the quantities the reference exposes on its Inference1D
     @property

@@ -186,6 +186,50 @@ def ranges(spec, depth_edges, n_soundings, surface=None):
     return Ranges(*(np.broadcast_to(a, (N, a.size)).copy() for a in r))
 
 
+def unit_bounds(spec, n_soundings, surface=None, max_depth=None):
+    """Exact bounds [N, M, 2] (top, bottom; m below the surface) of the units of a ``spec`` -- what the SAMPLED unit posteriors
+    integrate over (``rjmcmc_gpu.DeviceChains(units=...)``, ``inference.Posteriors(units=...)``), where ``ranges`` gives whole cells of
+    the depth mesh.  ``depth``: the intervals between the edges; ``elevation``: between the edges under each sounding's ``surface`` [N],
+    lowest unit first as ``elevation_ranges`` orders them; ``horizons``: top / bottom as depths, or as elevations when the spec asks for
+    a surface; ``pairs`` of depths (floats).  Bounds are clipped to [0, ``max_depth``] (no ``max_depth``: to [0, inf) -- give one, the
+    sampler wants finite bounds); a unit wholly above the ground or below ``max_depth``, a NaN horizon or a bottom not below its top
+    gives top == bottom: the unit has no posterior."""
+    spec = check_spec(spec)
+    kind, N = spec["kind"], int(n_soundings)
+    own = spec.get("surface")
+    s = None
+    if kind == "elevation" or (kind == "horizons" and own is not None):
+        s = surface if (own is None or own is True) else own
+        if s is None or np.asarray(s).size != N:
+            raise ValueError("intervals: %s units need %d surface elevations" % (kind, N))
+        s = np.asarray(s, dtype=np.float64).reshape(-1)
+        if not np.all(np.isfinite(s)):
+            raise ValueError("the surface elevations must be finite")
+    if kind == "depth":
+        x = spec["edges"]
+        z0, z1 = np.broadcast_to(x[:-1], (N, x.size - 1)), np.broadcast_to(x[1:], (N, x.size - 1))
+    elif kind == "pairs":
+        if spec["pairs"].dtype.kind != "f":
+            raise ValueError("intervals: unit bounds need pairs of depths, not of cells")
+        pr = np.sort(spec["pairs"], axis=1)
+        z0, z1 = np.broadcast_to(pr[:, 0], (N, pr.shape[0])), np.broadcast_to(pr[:, 1], (N, pr.shape[0]))
+    elif kind == "elevation":
+        x = spec["edges"]
+        z0, z1 = s[:, None] - x[None, 1:], s[:, None] - x[None, :-1]
+    else:
+        t, b = spec["top"], spec["bottom"]
+        t, b = (t[:, None], b[:, None]) if t.ndim == 1 else (t, b)
+        if t.shape[0] != N:
+            raise ValueError("intervals: horizons for %d soundings, the line has %d" % (t.shape[0], N))
+        z0, z1 = (t, b) if s is None else (s[:, None] - t, s[:, None] - b)
+    top = None if max_depth is None else float(max_depth)
+    z0, z1 = np.array(z0, dtype=np.float64), np.array(z1, dtype=np.float64)
+    bad = ~(np.isfinite(z0) & np.isfinite(z1))
+    z0, z1 = np.where(bad, 0.0, z0), np.where(bad, 0.0, z1)
+    z0, z1 = np.clip(z0, 0.0, top), np.clip(z1, 0.0, top)
+    return np.stack([z0, np.maximum(z1, z0)], axis=2)
+
+
 def describe(spec):
     """The spec as ``interval_*`` entries of the products: ``interval_kind`` and its arrays."""
     out = {"interval_kind": np.array(spec["kind"])}

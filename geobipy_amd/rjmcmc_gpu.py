@@ -86,7 +86,8 @@ class DeviceChains:
     def __init__(self, system, heights, data, seed=0, exact_jacobian=False, device=None, hitmap=False, n_value_bins=250,
                  first_chain=0, forward_waves=2, reference_schedule=False, burn_in_min_iterations=5000, hankel_eps_ppm=None,
                  min_altitude=None, add_scale=None, rel_group=None, add_group=None, chain_id=None, extra_log_prior=0.0,
-                 additive_independent=False, trace_every=0, trace_length=None, ignore_likelihood=False, **options):
+                 additive_independent=False, trace_every=0, trace_length=None, ignore_likelihood=False, units=None,
+                 unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), surface=None, **options):
         """``ignore_likelihood``: sample the PRIOR alone (the reference's option of that name, Inference1D.py:394, 519, 551, 596: no data
         term in the stochastic-Newton step, likelihood constant).  The reference's own run of it ends at the first birth or death, where
         Model.proposal_probabilities calls ``observation.sensitivity`` on None (model/Model.py:619); here the observation is left out
@@ -99,7 +100,16 @@ class DeviceChains:
         ``trace_every`` > 0: keep every ``trace_every``-th entry of the reference's per-iteration arrays ``data_misfit_v`` /
         ``acceptance_v`` (Inference1D.py:408, 414) on the device -- ``trace_misfit`` [B, trace_length] (NaN = not reached),
         ``trace_accept`` uint8 [B, trace_length]; ``trace_length`` defaults to the reference's 2 n_markov_chains / trace_every (needs
-        n_markov_chains).  1 = the reference's arrays in full."""
+        n_markov_chains).  1 = the reference's arrays in full.
+
+        Sampled unit posteriors (need ``hitmap=True``; ``unit_posteriors.products`` turns them into statistics).  ``units``: an interval
+        spec (``intervals.check_spec``: depth edges, elevation edges under ``surface`` [B], horizons) or the bounds themselves, [M, 2] or
+        [B, M, 2] metres below the surface, M <= 16 -- every replaced model adds its dwell time to the histogram of the unit's
+        arithmetic mean conductivity (conductance / thickness) and / or harmonic mean (thickness / transverse resistance) on the hit map's
+        value axis: ``unit_hist`` int32 [B, Q, n_value_bins, M], ``unit_kinds`` in file order arithmetic, harmonic.  ``first_above`` /
+        ``first_below``: up to 4 conductivities (S/m) in all -- ``first_hist`` int32 [B, T, n_depth_bins] is the posterior of the depth
+        to the top of the shallowest layer at or above / at or below each (thresholds in the order above, then below), ``first_none``
+        [B, T] counts the samples without such a layer."""
         from .inference import OPTION_DEFAULTS
         o = dict(OPTION_DEFAULTS)
         o.update({k: v for k, v in options.items() if v is not None})
@@ -195,6 +205,27 @@ class DeviceChains:
                 trace_length = -(-2 * ro.n_markov_chains // self.trace_every)
             ro.trace_every, ro.trace_length = self.trace_every, int(trace_length)
         self.trace_length = int(ro.trace_length)
+        # sampled unit posteriors (gbp_rj_options.n_units ...; the host rule: inference.Posteriors(units=..., first=...))
+        from .inference import check_first, check_unit_bounds, unit_kind_bits, unit_kind_names
+        self.unit_bounds = None
+        if units is not None:
+            if isinstance(units, dict) or hasattr(units, "kind"):
+                from .intervals import unit_bounds
+                units = unit_bounds(units, self.B, surface=surface, max_depth=1.1 * self.max_edge)
+            z = check_unit_bounds(units)
+            if z.ndim not in (2, 3) or (z.ndim == 3 and z.shape[0] != self.B):
+                raise ValueError("units must be [M, 2] or [B, M, 2]")
+            self.unit_bounds = np.array(np.broadcast_to(z, (self.B,) + z.shape[-2:]))      # (a writable copy)
+            ro.n_units, ro.unit_kinds = self.unit_bounds.shape[1], unit_kind_bits(unit_kinds)
+        self.unit_kinds = unit_kind_names(int(ro.unit_kinds))
+        th, di = check_first(list(first_above) + list(first_below), [1] * len(first_above) + [-1] * len(first_below))
+        self.first_threshold, self.first_direction = th, di
+        ro.n_first = th.size
+        ro.first_threshold = (ctypes.c_double * 4)(*(list(th) + [1.0] * (4 - th.size)))
+        ro.first_direction = (ctypes.c_int32 * 4)(*(list(di) + [1] * (4 - th.size)))
+        if (ro.n_units or ro.n_first) and not hitmap:
+            raise ValueError("units / first_above / first_below need hitmap=True: the unit posteriors are settled with the hit map's dwell times")
+        M_, Q_, T_ = int(ro.n_units), len(self.unit_kinds), int(ro.n_first)
         self._o = ro
         B, N, dev = self.B, self.N, self.device
         z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
@@ -220,7 +251,9 @@ class DeviceChains:
             step_flags=z(B, dt=i32),
             trace_misfit=torch.full((B, self.trace_length), float("nan"), dtype=torch.float64, device=dev) if self.trace_every > 0 else None,
             trace_accept=z(B, self.trace_length, dt=torch.uint8) if self.trace_every > 0 else None,
-            best_iteration=z(B, dt=i32))
+            best_iteration=z(B, dt=i32),
+            unit_z=f64(self.unit_bounds) if M_ else None, unit_hist=z(B, Q_, self.n_value_bins, M_, dt=i32) if M_ else None,
+            first_hist=z(B, T_, self.n_depth_bins, dt=i32) if T_ else None, first_none=z(B, T_, dt=i32) if T_ else None)
         self._bind()
         self.iteration = 0
         self.forward_waves = int(forward_waves)      # also passed explicitly to the forward calls of the initialisation
@@ -262,7 +295,7 @@ class DeviceChains:
     def __getattr__(self, name):              # chain state by the names of gbp_rj_chains
         t = self.__dict__.get("t")
         if t is not None and name in t:
-            if name == "hitmap" and t["hitmap"] is not None:
+            if name in ("hitmap", "unit_hist", "first_hist", "first_none") and t[name] is not None:
                 # a model enters the hit map with its dwell time when it is replaced; settle the current models first
                 with torch.cuda.device(self.device):
                     _lib.check(_lib.load().gbp_rj_flush_posteriors(self._o, self._c, self._stream()))
@@ -451,7 +484,8 @@ class DeviceChains:
         t["J"][r, :, 0] = t["init_J0"][r]
         for name in ("prior", "like", "misfit"):
             t[name][r] = t["init_" + name][r]
-        for name in ("n_accepted", "acc_mark", "n_zero", "k_hist", "edge_hist", "rel_hist", "add_hist", "hitmap", "hit_dwell", "height_hist"):
+        for name in ("n_accepted", "acc_mark", "n_zero", "k_hist", "edge_hist", "rel_hist", "add_hist", "hitmap", "hit_dwell", "height_hist", "unit_hist",
+                     "first_hist", "first_none"):
             if t.get(name) is not None:
                 t[name][r] = 0
         if self.solve_height:

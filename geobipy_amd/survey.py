@@ -477,7 +477,8 @@ BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device bloc
 
 def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min_iterations=5000, check_every=1000,
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
-          chunk=None, results_directory=None, timings=None, traces=1, container=None, **overrides):
+          chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
+          first_above=(), first_below=(), **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -504,6 +505,11 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     index by iteration; an int > 1 or "auto" (opt-in: the smallest stride with at most 4 096 entries per sounding): every stride-th
     entry side by side, ceil(2 n_markov_chains / stride) columns with the stride as the datasets' attribute ``trace_every`` -- NOT the
     reference's shapes; None: none.
+    ``units`` (an interval spec, ``intervals.check_spec``: depth edges, elevation edges under the data file's elevations, horizons),
+    ``unit_kinds``, ``first_above`` / ``first_below`` (S/m): the SAMPLED unit posteriors (``DeviceChains(units=...)``) -- the statistics of
+    ``unit_posteriors.products`` are computed per block on the device and join the per-sounding summaries: ``unit_<kind>_*``,
+    ``unit_conductance_*``, ``unit_resistance_*``, ``unit_thickness`` [S, M], ``first_depth_*``, ``first_probability`` [S, T] (statistics
+    only: the histograms, 8 KB per kind and sounding, stay on the device).  Need the hit map.  The containers are not touched.
     ``timings``: a dict that receives the wall time by phase (the device is synchronised at the phase borders then; bench.py).
     ``index`` / ``fiducial`` + ``line_number`` / ``line_number``: the reference's single-point and single-line switches.
     ``exact_jacobian``: use the true derivative of the forward model in the proposals instead of the reference's
@@ -582,6 +588,15 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
         if hitmap and results_directory is not None:
             per += 440 * 1024                                                                 # (the hit map's usual size; exact: DeviceChains)
         return limit if per == 0 else int(max(256, min(limit, BLOCK_PAYLOAD_BUDGET // per)))
+    # sampled unit posteriors: exact bounds of every sounding's units, metres below its surface, cut at the end of the depth axis
+    unit_z = None
+    if units is not None or len(first_above) or len(first_below):
+        if not hitmap:
+            raise ValueError("units / first_above / first_below need the hit map (they are settled with its dwell times)")
+        common.update(first_above=tuple(float(v) for v in first_above), first_below=tuple(float(v) for v in first_below), unit_kinds=unit_kinds)
+        if units is not None:
+            from .intervals import unit_bounds
+            unit_z = unit_bounds(units, ds.nPoints, surface=ds.elevation, max_depth=1.1 * float(o["maximum_depth"]))
     if time_domain and hankel_eps is not None:
         common.update(hankel_eps=float(hankel_eps))
     elif not time_domain and hankel_eps is not None:
@@ -609,6 +624,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     def run_block(idx, offset=None):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])])."""
         kw = dict(common)
+        if unit_z is not None:
+            kw["units"] = unit_z[idx]
         if idx.size != n or idx[0] != start:        # a selection of the shard: key every chain by its own row of the data file
             kw.pop("first_chain")
             kw["chain_id"] = int(rows[0]) + idx
@@ -644,6 +661,10 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
             with _Phase("hitmap_statistics"):
                 mean, pct = _hitmap_statistics(dc.hitmap, t["log_mean_prior"], dc.value_half_width)     # (attribute access settles dwell times)
             named += [("mean_log10_conductivity", mean)] + [("log10_conductivity_" + q, p) for q, p in zip(("p05", "p50", "p95"), pct)]
+        if t.get("unit_hist") is not None or t.get("first_hist") is not None:
+            from . import unit_posteriors
+            with _Phase("unit_posteriors"):
+                named += [(k_, f64(v_)) for k_, v_ in unit_posteriors.products(dc).items()]
         return dc, named
 
     state = dict(iterations=0, dc=None, named=None)

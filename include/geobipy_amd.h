@@ -383,6 +383,19 @@ typedef struct gbp_rj_options {
                                     after update j * trace_every + 1) and acceptance_v[j * trace_every] (the decision of update j *
                                     trace_every), updates counted from the chain's (re)start.  trace_every = 1, trace_length = 2 *
                                     n_markov_chains: the reference's arrays in full.  0: no traces                                  */
+    /* Sampled unit posteriors (chains->unit_z ...): properties of a depth unit [z0, z1] of every SAMPLED model, binned where the hit
+     * map is settled and with the same dwell weight.  Layer l spans [top_l, bot_l), top_0 = 0, bot_{k-1} = +inf; its overlap with the
+     * unit is ov_l = max(0, min(bot_l, z1) - max(top_l, z0)); layers with ov_l = 0 are skipped, l ascending, one rounded multiply /
+     * divide and one rounded add per term (no fused multiply-add):
+     *   arithmetic mean  a = (sum_l sigma_l ov_l) / dz   (conductance over thickness)
+     *   harmonic mean    h = dz / (sum_l ov_l / sigma_l) (thickness over transverse resistance)
+     * each binned on the hit map's value axis of its chain.  Depth to a threshold: top_l of the shallowest layer with sigma_l >= t
+     * (direction +1) or sigma_l <= t (-1), binned on the depth axis as edge_hist bins an interface; no such layer: first_none. */
+    int32_t n_units;             /* M, 0 .. 16 units per chain; 0: off                                                    */
+    int32_t unit_kinds;          /* bit 0 arithmetic, bit 1 harmonic (1 .. 3 when n_units > 0)                            */
+    int32_t n_first;             /* 0 .. 4 thresholds                                                                     */
+    double first_threshold[4];   /* S/m, finite and positive                                                              */
+    int32_t first_direction[4];  /* +1: first layer at or above the threshold, -1: at or below                            */
 } gbp_rj_options;
 
 typedef struct gbp_rj_chains {
@@ -445,6 +458,13 @@ typedef struct gbp_rj_chains {
     uint8_t *trace_accept;         /* [B, trace_length] or NULL  decimated accept / reject decisions (both traces or neither)      */
     int32_t *best_iteration;       /* [B] or NULL  the update (1-based, from the chain's (re)start) that produced the highest-posterior
                                       state (Inference1D.best_iteration :733, 743)                                                */
+    /* sampled unit posteriors (opt->n_units / n_first; need hitmap: they share hit_dwell and are zeroed where it is; all NULL: off) */
+    const double *unit_z;          /* [B, n_units, 2]  top and bottom of every unit, metres below the surface, 0 <= z0 <= z1 finite;
+                                      z1 == z0: the unit has no posterior (its column stays 0)                              */
+    int32_t *unit_hist;            /* [B, Q, n_value_bins, n_units]  Q = set bits of unit_kinds, arithmetic first; unit fastest:
+                                      the layout of the interval marginals (gbp_hitmap_intervals), int32                    */
+    int32_t *first_hist;           /* [B, n_first, n_depth_bins]  depth to the first layer beyond each threshold            */
+    int32_t *first_none;           /* [B, n_first]  samples without such a layer                                            */
 } gbp_rj_chains;
 
 /* The three host-logic stages of one iteration, exposed separately for the tests ... */
