@@ -55,7 +55,14 @@ def parse(argv=None):
     p.add_argument("--first-above", type=float, nargs="+", default=[], metavar="S",
                    help="posterior of the depth to the first layer at or above these conductivities, S/m (first_depth_* in the summaries)")
     p.add_argument("--first-below", type=float, nargs="+", default=[], metavar="S", help="... at or below these conductivities, S/m")
+    p.add_argument("--replicates", type=int, default=1, metavar="C",
+                   help="chains per sounding, 1 .. 8 (frequency-domain data): the posteriors are pooled over the chains that burned in and the "
+                        "summaries gain per-depth-cell convergence maps (rhat, jsd, n_used, ...)")
     a = p.parse_args(argv)
+    if not 1 <= a.replicates <= 8:
+        p.error("--replicates: 1 .. 8 chains per sounding")
+    if a.replicates > 1 and a.no_hitmap:
+        p.error("--replicates needs the hit map (drop --no-hitmap)")
     a.units = None
     if a.units_depth is not None or a.units_elevation is not None:
         from .intervals import edges_argument
@@ -99,7 +106,7 @@ def main(argv=None):
                        exact_jacobian=a.exact_jacobian, hitmap=not a.no_hitmap, hankel_eps=a.hankel_eps, schedule=a.schedule, chunk=a.chunk, traces=a.traces, results_directory=containers,
                        container=None if a.container == "auto" else a.container, data_directory=a.data_directory,
                        data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
-                       first_below=tuple(a.first_below))
+                       first_below=tuple(a.first_below), replicates=a.replicates)
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

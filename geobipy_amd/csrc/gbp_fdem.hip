@@ -1608,6 +1608,31 @@ extern "C" gbp_status gbp_hitmap_intervals(int B, int nv, int nz, int M, const i
     return GBP_OK;
 }
 
+// Replicate chains: the S * C hit maps [S * C, nv, nz] (row s * C + c: replicate c of sounding s) pooled over the chains with
+// use[s, c] != 0 (DEVICE int32 [S, C]) -> pooled [S, nv, nz], and per depth cell n_used, chain_mean [S, C, nz], rhat and jsd [S, nz]
+// (csrc/gbp_hitmap.h k_hitmap_pool).  2 <= C <= 8.
+extern "C" gbp_status gbp_hitmap_pool(int S, int C, int nv, int nz, const int32_t* hitmap, const int32_t* use, double half_width,
+                                      int32_t* pooled, int32_t* n_used, double* chain_mean, double* rhat, double* jsd, void* stream)
+{
+    if (S < 0 || nv < 1 || nz < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_pool: negative or zero size%s");
+    if (C < 2 || C > 8) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_pool: C outside 2 .. 8%s");
+    if (S == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!hitmap || !use || !pooled || !n_used || !chain_mean || !rhat || !jsd)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_pool: NULL pointer%s");
+    if ((int64_t)S * nz > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_pool: S * n_depth out of range%s");
+    if ((nz + 255) / 256 > 65535) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_pool: n_depth out of range%s");
+    const dim3 grid(S, (nz + 255) / 256);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, C, nv, nz, hitmap, use, half_width, pooled, n_used, chain_mean, rhat,
+                           jsd);
+    };
+    if (C <= 2) launch(hitmap::k_hitmap_pool<2>);
+    else if (C <= 4) launch(hitmap::k_hitmap_pool<4>);
+    else launch(hitmap::k_hitmap_pool<8>);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 // The hit maps' rows (M = nv * nz cells each) as runs.  Call with start == NULL to COUNT (counts[B] <- runs per row), build the
 // exclusive prefix ptr[B + 1] of the counts, allocate ptr[B] entries, then call again with ptr / start / value to WRITE.
 extern "C" gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t* hitmap, int64_t* counts, const int64_t* ptr, int32_t* start,

@@ -189,6 +189,128 @@ __global__ __launch_bounds__(256) void k_hitmap_classes(int nv, int nz, const T*
     best_p[o] = pbest;
 }
 
+// Replicate chains: the C hit maps of a sounding (rows s C + c of hm) pooled into one, and per depth cell the agreement of the chains
+// (no reference counterpart -- the host statement of the rule is geobipy_amd/replicates.py pool_reference).  One
+// workgroup per (sounding, 256 depth cells) as k_hitmap_stats; thread z walks the value cells once, the chains inside: per chain c
+//   n_c = sum_v h (int64), a_c = sum_v h x_v, q_c = sum_v (h x_v) x_v, e_c = sum_{h > 0} h ln h    (x_v: k_hitmap_stats's centre, no shift;
+//   fp64, v ascending) and, of the pooled cell hp[v] = sum_{c: use} h_c[v] -- written as it is formed --, e_p = sum_{hp > 0} hp ln hp.
+// P = {c: use[s, c] != 0 and n_c > 0}, m = |P|:  n_used = m;  chain_mean[s, c, z] = a_c / n_c (NaN outside P);
+//   rhat = sqrt(((nbar - 1) / nbar W + Bn) / W), W the mean of the chains' variances max(0, (q_c - a_c m_c) / (n_c - 1)) (0: n_c < 2),
+//   Bn = sum_P (m_c - mbar)^2 / (m - 1), nbar = N_P / m  (W == 0: 1 when Bn == 0, else +inf);
+//   jsd = max(0, [(ln N_P - e_p / N_P) - sum_P (n_c / N_P)(ln n_c - e_c / n_c)] / ln 2) bits;  both NaN when m < 2.
+// CB is the chain bucket (CB / 2 < C <= CB, C = 2: CB = 2): chains beyond C and chains switched off by `use` (uniform over the
+// workgroup) cost no loads.  U value rows of every chain are loaded before the rows they feed (10 .. 16 loads in flight per wave).
+// A wave whose 64 cells of a value row are empty in every chain skips the logarithms.
+template <int CB>
+__global__ __launch_bounds__(256) void k_hitmap_pool(int C, int nv, int nz, const int* __restrict__ hm, const int* __restrict__ use,
+                                                      double half_width, int* __restrict__ pooled, int* __restrict__ n_used,
+                                                      double* __restrict__ chain_mean, double* __restrict__ rhat, double* __restrict__ jsd)
+{
+    const int s = blockIdx.x, z = blockIdx.y * 256 + threadIdx.x;
+    if (z >= nz) return;
+    const size_t map = (size_t)nv * nz;
+    const int* col = hm + (size_t)s * C * map + z;
+    int* out = pooled + (size_t)s * map + z;
+    const double w = 2.0 * half_width;
+    bool on[CB];
+    long long n[CB];
+    double a[CB], q[CB], e[CB], ep = 0.0;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        on[c] = (c < CB / 2 || c < C) && use[(size_t)s * C + (c < C ? c : 0)] != 0;
+        n[c] = 0;
+        a[c] = q[c] = e[c] = 0.0;
+    }
+    auto add = [&](const int (&h)[CB], int v) {
+        const double x = (((double)v + 0.5) / (double)nv) * w - half_width;
+        int hp = 0;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) hp += h[c];
+        out[(size_t)v * nz] = hp;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) {
+            if (on[c]) {
+                const double hx = (double)h[c] * x;
+                n[c] += h[c];
+                a[c] += hx;
+                q[c] += hx * x;
+            }
+        }
+        if (hp > 0) {                              // (a branch: a wave whose 64 cells are empty in every chain skips the logarithms)
+#pragma unroll
+            for (int c = 0; c < CB; ++c)
+                if (on[c] && h[c] > 0) e[c] += (double)h[c] * gbp::log_pos((double)h[c]);
+            ep += (double)hp * gbp::log_pos((double)hp);
+        }
+    };
+    constexpr int U = CB == 2 ? 5 : (CB == 4 ? 3 : 2);
+    int v0 = 0;
+    for (; v0 + U <= nv; v0 += U) {
+        int h[U][CB];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < CB; ++c) h[u][c] = on[c] ? col[c * map + (size_t)(v0 + u) * nz] : 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) add(h[u], v0 + u);
+    }
+    for (; v0 < nv; ++v0) {
+        int h[CB];
+#pragma unroll
+        for (int c = 0; c < CB; ++c) h[c] = on[c] ? col[c * map + (size_t)v0 * nz] : 0;
+        add(h, v0);
+    }
+    // the diagnostics: sums over P in ascending c
+    const double nan = __builtin_nan("");
+    int m = 0;
+    long long NP = 0;
+    bool in[CB];
+    double mc[CB], sw = 0.0, sm = 0.0;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        in[c] = on[c] && n[c] > 0;
+        mc[c] = nan;
+        if (in[c]) {
+            const double nc = (double)n[c];
+            mc[c] = a[c] / nc;
+            double s2 = 0.0;
+            if (n[c] >= 2) {
+                s2 = (q[c] - a[c] * mc[c]) / (double)(n[c] - 1);
+                s2 = s2 > 0.0 ? s2 : 0.0;
+            }
+            sw += s2;
+            sm += mc[c];
+            NP += n[c];
+            ++m;
+        }
+        if (c < CB / 2 || c < C) chain_mean[((size_t)s * C + c) * nz + z] = mc[c];
+    }
+    double r = nan, j = nan;
+    if (m >= 2) {
+        const double md = (double)m, W = sw / md, mbar = sm / md, Nd = (double)NP;
+        double sb = 0.0;
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+            if (in[c]) sb += (mc[c] - mbar) * (mc[c] - mbar);
+        const double Bn = sb / (double)(m - 1), nbar = Nd / md;
+        if (W == 0.0) r = Bn == 0.0 ? 1.0 : __builtin_inf();
+        else r = sqrt(((nbar - 1.0) / nbar * W + Bn) / W);
+        double sj = 0.0;
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+            if (in[c]) {
+                const double nc = (double)n[c];
+                sj += (nc / Nd) * (gbp::log_pos(nc) - e[c] / nc);
+            }
+        j = ((gbp::log_pos(Nd) - ep / Nd) - sj) / 0.6931471805599453;
+        j = j > 0.0 ? j : 0.0;
+    }
+    const size_t o = (size_t)s * nz + z;
+    n_used[o] = m;
+    rhat[o] = r;
+    jsd[o] = j;
+}
+
 // Runs of a row's flattened cells: a run starts at cell 0 and wherever the count differs from the cell before.
 // Pass 1 (WRITE = false): counts[b] = number of runs.  Pass 2 (WRITE = true): start / value at ptr[b] + (rank of the run in the row).
 // One workgroup per row walks it in tiles of 1024 cells (4 per thread, coalesced); the ranks inside a tile come from a wave ballot

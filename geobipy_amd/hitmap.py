@@ -181,3 +181,58 @@ def interval_marginals(hitmap, lo, hi):
         _lib.check(_lib.load().gbp_hitmap_intervals(B, nv, nz, M, hm.data_ptr(), lo_d.data_ptr(), hi_d.data_ptr(), out.data_ptr(),
                                                     _stream(dev)))
     return out
+
+
+def _pool_arguments(maps, C, use, max_total=None):
+    """The checks of ``pool`` that need no device: (S, C, use as int32 [S, C] on the maps' device)."""
+    if not isinstance(maps, torch.Tensor) or maps.ndim != 3:
+        raise TypeError("replicate hit maps are a tensor [S * C, n_value, n_depth]")
+    if maps.dtype != torch.int32:
+        raise TypeError("hit maps are int32, not %s" % maps.dtype)
+    if not maps.is_contiguous():
+        raise ValueError("replicate hit maps must be contiguous (depth fastest)")
+    C = int(C)
+    if not 2 <= C <= 8:
+        raise ValueError("pool: C = %d replicate chains, 2 .. 8 are supported" % C)
+    if maps.shape[0] % C:
+        raise ValueError("pool: %d maps are not %d chains per sounding" % (maps.shape[0], C))
+    S = maps.shape[0] // C
+    if use is None:
+        use = torch.ones((S, C), dtype=torch.int32, device=maps.device)
+    else:
+        use = torch.as_tensor(use)
+        if tuple(use.shape) != (S, C):
+            raise ValueError("pool: use must be [%d, %d], not %r" % (S, C, tuple(use.shape)))
+        use = (use != 0).to(device=maps.device, dtype=torch.int32).contiguous()
+    # a pooled cell is at most C times the largest column total (a column's total is at most the chain's sample count); without a
+    # bound from the caller the totals are formed here: one more read of the maps and a host synchronisation
+    if max_total is None:
+        max_total = int(maps.sum(dim=1, dtype=torch.int64).max()) if maps.numel() else 0
+    if C * int(max_total) > 0x7fffffff:
+        raise ValueError("pool: %d chains of up to %d samples per column could pass 2^31 - 1 in a pooled int32 cell" % (C, int(max_total)))
+    return S, C, use
+
+
+def pool(maps, C, use=None, half_width=1.0, max_total=None):
+    """Replicate chains in one kernel (gbp_hitmap_pool): ``maps`` int32 [S * C, n_value, n_depth], row s * C + c the
+    replicate c of sounding s; ``use`` [S, C] (non-zero: the chain takes part; None: all).  Returns ``pooled`` int32 [S, n_value,
+    n_depth] (the sum over the used chains), ``n_used`` int32 [S, n_depth] (used chains with samples in the column), ``chain_mean``
+    [S, C, n_depth] (the chains' column means on the value axis WITHOUT the prior shift, NaN for a chain that takes no part), ``rhat``
+    [S, n_depth] (Gelman-Rubin potential scale reduction of the column means) and ``jsd`` [S, n_depth] (generalised Jensen-Shannon
+    divergence of the chains' columns, bits: 0 identical, log2 n_used disjoint); both NaN with fewer than two chains.  The axis is
+    generic: a histogram [S * C, cells] is ``maps[:, :, None]``.  A block whose pooled int32 cells could overflow is refused: C times
+    ``max_total``, an upper bound of every column's total that the caller knows (a chain's sample count), else the largest column
+    total, found by one more read of the maps.  The host statement of the rule is ``replicates.pool_reference``."""
+    S, C, use = _pool_arguments(maps, C, use, max_total)
+    if maps.device.type != "cuda":
+        raise _lib.NativeLibraryError("hitmap.pool runs on the device (gbp_hitmap_pool); there is no host fallback")
+    _, nv, nz = maps.shape
+    dev = maps.device
+    out = dict(pooled=torch.empty((S, nv, nz), dtype=torch.int32, device=dev), n_used=torch.empty((S, nz), dtype=torch.int32, device=dev),
+               chain_mean=torch.empty((S, C, nz), dtype=torch.float64, device=dev), rhat=torch.empty((S, nz), dtype=torch.float64, device=dev),
+               jsd=torch.empty((S, nz), dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gbp_hitmap_pool(S, C, nv, nz, maps.data_ptr(), use.data_ptr(), float(half_width), out["pooled"].data_ptr(),
+                                               out["n_used"].data_ptr(), out["chain_mean"].data_ptr(), out["rhat"].data_ptr(),
+                                               out["jsd"].data_ptr(), _stream(dev)))
+    return out

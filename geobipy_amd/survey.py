@@ -472,13 +472,16 @@ def select_soundings(ds, index=None, fiducial=None, line_number=None):
     return np.arange(ds.nPoints)
 
 
+# the per-sounding summaries a run with replicate chains adds, in the order of the result rows (replicates.Pooled.diagnostics)
+REPLICATE_SUMMARIES = ("rhat", "jsd", "n_used", "chain_mean", "rhat_layers", "jsd_layers", "rhat_interfaces", "rhat_max")
+
 BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device block may hold by default (infer's ``chunk``)
 
 
 def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min_iterations=5000, check_every=1000,
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
-          first_above=(), first_below=(), **overrides):
+          first_above=(), first_below=(), replicates=1, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -510,6 +513,12 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     ``unit_posteriors.products`` are computed per block on the device and join the per-sounding summaries: ``unit_<kind>_*``,
     ``unit_conductance_*``, ``unit_resistance_*``, ``unit_thickness`` [S, M], ``first_depth_*``, ``first_probability`` [S, T] (statistics
     only: the histograms, 8 KB per kind and sounding, stay on the device).  Need the hit map.  The containers are not touched.
+    ``replicates`` = C, 1 .. 8 (frequency-domain data): C chains per sounding that differ by their random streams alone
+    (``replicates.expand``: replicate 0 walks the chain the sounding walks alone); a block then holds C rows per sounding and is seen
+    through ``replicates.Pooled`` -- the containers and the posteriors of the summaries receive the sum over the chains that burned in,
+    per-chain rows come from the chain with the highest posterior, and the summaries gain ``rhat``, ``jsd``, ``n_used`` [S, n_depth],
+    ``chain_mean`` [S, C, n_depth], ``rhat_layers``, ``jsd_layers``, ``rhat_interfaces``, ``rhat_max`` and ``replicates_used`` [S]
+    (DESIGN.md 3.15).  Needs the hit map.  1 (default): one chain per sounding, nothing changes.
     ``timings``: a dict that receives the wall time by phase (the device is synchronised at the phase borders then; bench.py).
     ``index`` / ``fiducial`` + ``line_number`` / ``line_number``: the reference's single-point and single-line switches.
     ``exact_jacobian``: use the true derivative of the forward model in the proposals instead of the reference's
@@ -542,12 +551,21 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
         raise NotImplementedError("solve_z on time-domain data: the reference's forward takes the TRANSMITTER's z (system/Loop_pair.py:70), "
                                   "which the data point's z move never touches -- the key that would matter is solve_transmitter_z, and the "
                                   "geometry of the loop pair is not sampled")
+    C_rep = int(replicates)
+    if not 1 <= C_rep <= 8:
+        raise ValueError("replicates = {}: 1 .. 8 chains per sounding".format(replicates))
+    if C_rep > 1 and time_domain:
+        raise NotImplementedError("replicates > 1 on time-domain data: the system handle holds per-row state (table set, mixing weights), "
+                                  "which the pooled view would have to re-map for the best-model evaluation")
+    if C_rep > 1 and not hitmap:
+        raise ValueError("replicates > 1 needs the hit map (the convergence maps are computed from the chains' hit maps)")
     if data is not None:
         ds = data
     elif time_domain:
         ds = (TempestData if tempest else TdemData).read_csv(o["data_filename"], o["system_filename"])
     else:
         ds = FdemData.read_csv(o["data_filename"], o["system_filename"])
+    n_file = ds.nPoints                             # (replicate c of the sounding in row r of the data file: chain r + c n_file)
     rows = select_soundings(ds, index, fiducial, line_number)
     if rows.size != ds.nPoints:
         ds = ds.subset(rows)
@@ -587,7 +605,9 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
             per += -(-2 * int(o["n_markov_chains"]) // int(common["trace_every"])) * 9        # misfit f64 + acceptance u8 per kept entry
         if hitmap and results_directory is not None:
             per += 440 * 1024                                                                 # (the hit map's usual size; exact: DeviceChains)
-        return limit if per == 0 else int(max(256, min(limit, BLOCK_PAYLOAD_BUDGET // per)))
+        if C_rep > 1:                               # a sounding is C rows of the block
+            limit, per = max(1, limit // C_rep), per * C_rep
+        return limit if per == 0 else int(max(256 // C_rep, min(limit, BLOCK_PAYLOAD_BUDGET // per)))
     # sampled unit posteriors: exact bounds of every sounding's units, metres below its surface, cut at the end of the depth axis
     unit_z = None
     if units is not None or len(first_above) or len(first_below):
@@ -624,11 +644,18 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     def run_block(idx, offset=None):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])])."""
         kw = dict(common)
-        if unit_z is not None:
-            kw["units"] = unit_z[idx]
-        if idx.size != n or idx[0] != start:        # a selection of the shard: key every chain by its own row of the data file
+        if C_rep > 1:                               # C rows per sounding, sounding-major; every chain keyed by (row of the file, replicate)
+            from .replicates import Pooled, expand
+            if idx.size:
+                rep_rows, chain_id = expand(int(rows[0]) + idx, C_rep, n_file)
+                idx = rep_rows - int(rows[0])
+                kw.pop("first_chain")
+                kw["chain_id"] = chain_id
+        elif idx.size != n or idx[0] != start:      # a selection of the shard: key every chain by its own row of the data file
             kw.pop("first_chain")
             kw["chain_id"] = int(rows[0]) + idx
+        if unit_z is not None:
+            kw["units"] = unit_z[idx]                # (with replicates: the expanded rows)
         if time_domain:
             from .tdem import TdemDeviceChains
             if isinstance(ds, TempestData):
@@ -644,6 +671,10 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
                 dc = DeviceChains(ds.system, ds.z[idx], ds.data[idx], exact_jacobian=exact_jacobian, **kw)
         with _Phase("chains"):
             dc.infer(check_every=check_every)
+        if C_rep > 1:
+            with _Phase("pool_replicates"):
+                dc = Pooled(dc, C_rep)
+                diag = dc.diagnostics()
         t = dc.t
         named = [("status", col(t["status"])), ("burned_in_iteration", col(t["burned_in_iteration"])), ("n_accepted", col(t["n_accepted"])),
                  ("misfit", col(t["misfit"])), ("relative_error", t["rel"]), ("additive_error", t["add"]), ("n_layers", col(t["k"])),
@@ -665,6 +696,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
             from . import unit_posteriors
             with _Phase("unit_posteriors"):
                 named += [(k_, f64(v_)) for k_, v_ in unit_posteriors.products(dc).items()]
+        if C_rep > 1:
+            named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return dc, named
 
     state = dict(iterations=0, dc=None, named=None)
@@ -921,7 +954,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
                                depth_bin_width=np.float64(dc.depth_bin_width))
             c0 = 0
             ints = ("status", "burned_in_iteration", "n_layers", "best_n_layers", "layer_count_posterior", "interface_posterior",
-                    "relative_error_posterior", "additive_error_posterior", "height_posterior") + tuple(
+                    "relative_error_posterior", "additive_error_posterior", "height_posterior", "n_used", "replicates_used") + tuple(
                 n_ + "_posterior" for n_ in ("dx", "dy", "dz", "tx_z", "tx_pitch", "tx_roll", "tx_yaw", "rx_pitch", "rx_roll", "rx_yaw"))
             for name, v in named:
                 w = v.shape[1]
@@ -933,6 +966,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
             for name, G in (("relative_error_posterior", dc.n_rel_groups), ("additive_error_posterior", dc.n_add_groups)):
                 if G > 1:                                   # [S, groups, cells]; ne cells, uniform in log10 between the prior bounds
                     res[name] = res[name].reshape(-1, G, dc.n_error_bins)
+            if C_rep > 1:
+                res["chain_mean"] = res["chain_mean"].reshape(-1, C_rep, dc.n_depth_bins)
             n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze (infer :641-688)
             ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
             res["iterations"] = ran.astype(np.int64)

@@ -680,6 +680,22 @@ gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_
 gbp_status gbp_hitmap_classes_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                   int K, const double *means, const double *scales, double *prob, int32_t *best, double *best_p,
                                   void *stream);
+/* gbp_hitmap_pool -- replicate chains (no reference counterpart, the host statement of the rule is
+ * geobipy_amd/replicates.py pool_reference): hitmap holds S * C maps, row s * C + c the replicate c of sounding s; use: DEVICE int32
+ * [S, C], non-zero = the chain takes part.  With x_v the bin centres of gbp_hitmap_statistics WITHOUT the prior shift and per chain
+ * n_c = sum_v h (int64), a_c = sum_v h x_v, q_c = sum_v (h x_v) x_v, e_c = sum_{h > 0} h ln h (fp64, v ascending), per depth cell:
+ * pooled [S, n_value, n_depth] = sum_{c: use} h_c;  n_used [S, n_depth] = m = |P|, P = {c: use and n_c > 0};
+ * chain_mean [S, C, n_depth] = m_c = a_c / n_c (NaN outside P);
+ * rhat [S, n_depth] = sqrt(((nbar - 1) / nbar W + Bn) / W), the Gelman-Rubin potential scale reduction, with W = sum_P s2_c / m,
+ * s2_c = max(0, (q_c - a_c m_c) / (n_c - 1)) (0 when n_c < 2), Bn = sum_P (m_c - mbar)^2 / (m - 1), mbar = sum_P m_c / m,
+ * nbar = N_P / m, N_P = sum_P n_c; W == 0: 1 when Bn == 0, else +inf;
+ * jsd [S, n_depth] = max(0, [(ln N_P - e_p / N_P) - sum_P (n_c / N_P)(ln n_c - e_c / n_c)] / ln 2), e_p = sum_{hp > 0} hp ln hp of
+ * the pooled column: the generalised Jensen-Shannon divergence of the chains' columns in bits (0: identical, log2 m: disjoint).
+ * rhat and jsd are NaN when m < 2; sums over P run in ascending c.  The axis is generic: a [rows, cells] histogram is a map with
+ * n_depth = 1.  2 <= C <= 8; GBP_ERR_INVALID_ARG for the rest, for bad sizes, NULL pointers and S * n_depth beyond int32, every check
+ * before any launch; S == 0 launches nothing.  The caller keeps C times a column's total below 2^31. */
+gbp_status gbp_hitmap_pool(int S, int C, int n_value, int n_depth, const int32_t *hitmap, const int32_t *use, double half_width,
+                           int32_t *pooled, int32_t *n_used, double *chain_mean, double *rhat, double *jsd, void *stream);
 
 /* [host] Results containers (geobipy_amd/h5lite.py; no reference counterpart -- the reference stores its hit maps dense): the rows of
  * a conductivity-depth hit map held as runs (row r owns runs ptr[r] .. ptr[r + 1] - 1; run q holds value[q] from cell start[q] of the row
