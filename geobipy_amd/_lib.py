@@ -136,6 +136,9 @@ SIGNATURES = {
                                + [c_void_p]),
     "gbp_hitmap_intervals": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_hitmap_pool": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double] + [c_void_p] * 5 + [c_void_p]),
+    "gbp_hitmap_mixture": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
+    "gbp_hitmap_mixture_i64": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6
+                               + [c_void_p]),
     "gbp_hitmap_runs": (c_int, [c_int, ctypes.c_int64] + [c_void_p] * 5 + [c_void_p]),
     "gbp_runs_to_zlib": (c_int, [c_int, ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_void_p]),
     "gbp_sibson_plan_create": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, ctypes.POINTER(c_void_p)]),

@@ -1633,6 +1633,49 @@ extern "C" gbp_status gbp_hitmap_pool(int S, int C, int nv, int nz, const int32_
     return GBP_OK;
 }
 
+// Local mixture fits of B hit maps [B, nv, nz]: every stage K = 1 .. Kmax of the rule of DESIGN.md 3.16 for every column in one launch
+// (csrc/gbp_hitmap.h k_hitmap_mixture) -> weight / mean / sd [B, Kmax (Kmax + 1) / 2, nz], loglik / ll_change [B, Kmax, nz] and misfit
+// [B, Kmax, 2, nz].  T: the maps' count type.
+template <typename T>
+static gbp_status hitmap_mixture(int B, int nv, int nz, const T* hitmap, double half_width, int Kmax, int n_iter, double reg, double* weight,
+                                 double* mean, double* sd, double* loglik, double* ll_change, double* misfit, void* stream)
+{
+    if (B < 0 || nv < 1 || nz < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: negative or zero size%s");
+    if (nv > hitmap::MIXTURE_MAX_ROWS)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: n_value beyond 4096 (a wave's non-empty rows are a 64 x 64-bit mask)%s");
+    if (Kmax < 1 || Kmax > 4) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: Kmax outside 1 .. 4%s");
+    if (n_iter < 1 || n_iter > 10000) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: n_iter outside 1 .. 10000%s");
+    if (!(std::isfinite(reg) && reg > 0.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: reg must be finite and positive%s");
+    if (!(std::isfinite(half_width) && half_width > 0.0))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: half_width must be finite and positive%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!hitmap || !weight || !mean || !sd || !loglik || !ll_change || !misfit)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: NULL pointer%s");
+    if ((int64_t)B * nz > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: B * n_depth out of range%s");
+    if ((nz + 255) / 256 > 65535) return fail(GBP_ERR_INVALID_ARG, "gbp_hitmap_mixture: n_depth out of range%s");
+    const hitmap::MixtureOut out = {weight, mean, sd, loglik, ll_change, misfit};
+    hipLaunchKernelGGL(hitmap::k_hitmap_mixture<T>, dim3(B, (nz + 255) / 256), dim3(256), 0, (hipStream_t)stream, nv, nz, hitmap, half_width, Kmax,
+                       n_iter, reg, out);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+extern "C" gbp_status gbp_hitmap_mixture(int B, int nv, int nz, const int32_t* hitmap, double half_width, int Kmax, int n_iter, double reg,
+                                         double* weight, double* mean, double* sd, double* loglik, double* ll_change, double* misfit,
+                                         void* stream)
+{
+    return hitmap_mixture<int>(B, nv, nz, hitmap, half_width, Kmax, n_iter, reg, weight, mean, sd, loglik, ll_change, misfit, stream);
+}
+
+// The same over int64 maps [B, nv, nz] (interval marginals: gbp_hitmap_intervals)
+extern "C" gbp_status gbp_hitmap_mixture_i64(int B, int nv, int nz, const int64_t* hitmap, double half_width, int Kmax, int n_iter, double reg,
+                                             double* weight, double* mean, double* sd, double* loglik, double* ll_change, double* misfit,
+                                             void* stream)
+{
+    return hitmap_mixture<long long>(B, nv, nz, (const long long*)hitmap, half_width, Kmax, n_iter, reg, weight, mean, sd, loglik, ll_change,
+                                     misfit, stream);
+}
+
 // The hit maps' rows (M = nv * nz cells each) as runs.  Call with start == NULL to COUNT (counts[B] <- runs per row), build the
 // exclusive prefix ptr[B + 1] of the counts, allocate ptr[B] entries, then call again with ptr / start / value to WRITE.
 extern "C" gbp_status gbp_hitmap_runs(int B, int64_t M, const int32_t* hitmap, int64_t* counts, const int64_t* ptr, int32_t* start,

@@ -467,4 +467,234 @@ __global__ __launch_bounds__(64) void k_hitmap_intervals(int nv, int nz, int M, 
     }
 }
 
+// The value rows of a map in which some lane of the wave has a count, as a bit mask spread over the wave: lane l holds the bits of rows
+// 64 l .. 64 l + 63 (4 096 rows at most).  RowWalk hands out the set rows in ascending order; everything here is uniform over the wave
+// (the words come through v_readlane), so a walk is a scalar loop.  Every lane of the wave must be active.
+constexpr int MIXTURE_MAX_ROWS = 64 * 64;
+struct RowWalk {
+    long long mask;
+    unsigned long long word;
+    int wi, nwords;
+    __device__ __forceinline__ RowWalk(long long mask_, int nv) : mask(mask_), word(0), wi(-1), nwords((nv + 63) >> 6) {}
+    __device__ __forceinline__ int next()                            // the next set row, -1 when there is none
+    {
+        while (word == 0) {
+            if (++wi >= nwords) return -1;
+            word = (unsigned long long)wave_read_lane(mask, wi);
+        }
+        const int bit = __builtin_ctzll(word);
+        word &= word - 1;
+        return 64 * wi + bit;
+    }
+};
+
+// Where a lane's mixture fits go: weight / mean / sd [B, Kmax (Kmax + 1) / 2, nz] (stage K in slots K (K - 1) / 2 .. + K),
+// loglik / ll_change [B, Kmax, nz], misfit [B, Kmax, 2, nz]; depth fastest.
+struct MixtureOut {
+    double* weight;
+    double* mean;
+    double* sd;
+    double* loglik;
+    double* ll_change;
+    double* misfit;
+};
+
+// Stage K of the mixture rule for the lane's column (geobipy_amd/mixtures.py mixture_reference is the statement):
+// K Gaussians fitted to the binned column by n_iter EM iterations from the quantile start, then one closing pass over all nv cells.
+// col: the column (stride nz); rows: the WAVE's non-empty value rows (RowWalk's mask), uniform over the wave, so that a value row is
+// one coalesced load and the row loop is a scalar loop; the next row's load is issued before the current row's arithmetic.  Lanes
+// whose cell of a row is empty skip the row's arithmetic.  The libm exp / log.
+template <int K, typename T>
+__device__ __forceinline__ void mixture_stage(const T* __restrict__ col, int nv, int nz, long long rows, double half_width, double Nd,
+                                              double m, double V, const int* qi, int n_iter, double reg, bool store, const MixtureOut& o,
+                                              size_t b, int z, int Kmax)
+{
+    const double w2 = 2.0 * half_width, dx = w2 / (double)nv;
+    auto centre = [&](int v) { return (((double)v + 0.5) / (double)nv) * w2 - half_width; };
+    double wt[K], mu[K], s2[K];
+    double ll_prev = 0.0;
+    if (K == 1) {
+        wt[0] = 1.0;
+        mu[0] = m;
+        s2[0] = V + reg;
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            wt[j] = 1.0 / (double)K;
+            mu[j] = centre(qi[j]);
+            s2[j] = V / (double)(K * K) + reg;
+        }
+        for (int it = 0; it < n_iter; ++it) {
+            double a[K], h[K], sn[K], sa[K], sq[K], sl = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                a[j] = log(wt[j]) - 0.5 * log(6.283185307179586 * s2[j]);
+                h[j] = 2.0 * s2[j];
+                sn[j] = sa[j] = sq[j] = 0.0;
+            }
+            RowWalk walk(rows, nv);
+            int v = walk.next();
+            T cn = v >= 0 ? col[(size_t)v * nz] : (T)0;
+            while (v >= 0) {
+                const int vn = walk.next();
+                const T ci = cn;
+                if (vn >= 0) cn = col[(size_t)vn * nz];
+                if (ci > 0) {
+                    const double c = (double)ci, x = centre(v);
+                    double d[K], l[K], top;
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        d[j] = x - mu[j];
+                        l[j] = a[j] - d[j] * d[j] / h[j];
+                    }
+                    top = l[0];
+#pragma unroll
+                    for (int j = 1; j < K; ++j) top = l[j] > top ? l[j] : top;
+                    double se = 0.0;
+#pragma unroll
+                    for (int j = 0; j < K; ++j) se += exp(l[j] - top);
+                    const double L = top + log(se);
+                    sl += c * L;
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const double r = c * exp(l[j] - L);
+                        sn[j] += r;
+                        sa[j] += r * d[j];
+                        sq[j] += r * d[j] * d[j];
+                    }
+                }
+                v = vn;
+            }
+            double nt = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                sn[j] += 10.0 * 2.220446049250313e-16;
+                nt += sn[j];
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const double g = sa[j] / sn[j];
+                const double var = sq[j] / sn[j] - g * g;
+                mu[j] += g;
+                s2[j] = (var > 0.0 ? var : 0.0) + reg;
+                wt[j] = sn[j] / nt;
+            }
+            ll_prev = sl / Nd;
+        }
+    }
+    // the closing pass: every cell of the column
+    double a[K], h[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        a[j] = log(wt[j]) - 0.5 * log(6.283185307179586 * s2[j]);
+        h[j] = 2.0 * s2[j];
+    }
+    double sl = 0.0, emax = 0.0, pmax = 0.0, e2 = 0.0, p2 = 0.0;
+    T cn = col[0];
+    for (int v = 0; v < nv; ++v) {
+        const T ci = cn;
+        if (v + 1 < nv) cn = col[(size_t)(v + 1) * nz];
+        const double c = (double)ci, x = centre(v);
+        double l[K], top;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const double d = x - mu[j];
+            l[j] = a[j] - d * d / h[j];
+        }
+        top = l[0];
+#pragma unroll
+        for (int j = 1; j < K; ++j) top = l[j] > top ? l[j] : top;
+        double se = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) se += exp(l[j] - top);
+        const double L = top + log(se);
+        sl += c * L;
+        const double p = c / Nd, e = fabs(p - exp(L) * dx);
+        emax = e > emax ? e : emax;
+        pmax = p > pmax ? p : pmax;
+        e2 += e * e;
+        p2 += p * p;
+    }
+    if (!store) return;
+    const double nan = __builtin_nan("");
+    const bool some = Nd > 0.0;
+    const double loglik = sl / Nd;
+    const size_t S = (size_t)(Kmax * (Kmax + 1) / 2), slot = (size_t)(K * (K - 1) / 2);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const size_t i = (b * S + slot + j) * nz + z;
+        o.weight[i] = some ? wt[j] : nan;
+        o.mean[i] = some ? mu[j] : nan;
+        o.sd[i] = some ? sqrt(s2[j]) : nan;
+    }
+    const size_t i = (b * Kmax + (K - 1)) * nz + z;
+    o.loglik[i] = some ? loglik : nan;
+    o.ll_change[i] = some ? (K == 1 ? 0.0 : loglik - ll_prev) : nan;
+    o.misfit[(2 * (b * Kmax + (K - 1)) + 0) * nz + z] = some ? emax / pmax : nan;
+    o.misfit[(2 * (b * Kmax + (K - 1)) + 1) * nz + z] = some ? sqrt(e2) / sqrt(p2) : nan;
+}
+
+// Local mixture fits: all stages K = 1 .. Kmax of every (sounding, depth cell) column in one launch, one workgroup
+// per (sounding, 256 depth cells) and one lane per column as k_hitmap_stats.  Pass 1 walks the column: N (int64), sum c x, and the
+// wave's non-empty rows (a ballot per row; RowWalk's mask).  Pass 2 walks those rows: V = sum c (x - m)^2 / N and, for every stage
+// and component, the quantile start cell, the first v with 2 K cum_v >= (2 j + 1) N (int64, exact: the row at which the lane's
+// cumulative count crosses).  Then the stages (mixture_stage), whose EM passes walk the non-empty rows only.  The rows are re-read
+// from L1 / L2 in every pass (a wave's 10 .. 40 rows are 2.5 .. 10 KB; the arithmetic per row -- K exp, a log, K exp again -- outweighs
+// the load by two orders): no LDS.  Lanes beyond nz repeat the last column and store nothing, so that every lane of a wave takes part
+// in the ballots.  nv <= MIXTURE_MAX_ROWS.
+template <typename T>
+__global__ __launch_bounds__(256) void k_hitmap_mixture(int nv, int nz, const T* __restrict__ hm, double half_width, int Kmax, int n_iter,
+                                                         double reg, MixtureOut o)
+{
+    const int b = blockIdx.x, z = blockIdx.y * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool store = z < nz;
+    const int zc = store ? z : nz - 1;
+    const T* col = hm + (size_t)b * nv * nz + zc;
+    const double w2 = 2.0 * half_width;
+    long long tot = 0, rows = 0;
+    double wsum = 0.0;
+    auto add = [&](T h, int v) {
+        tot += h;
+        wsum += (double)h * ((((double)v + 0.5) / (double)nv) * w2 - half_width);
+        if (__ballot(h > 0) != 0 && lane == (v >> 6)) rows |= 1ll << (v & 63);
+    };
+    constexpr int U = 10;                          // ten loads in flight per wave, issued before the rows they feed
+    int v0 = 0;
+    for (; v0 + U <= nv; v0 += U) {
+        T h[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) h[u] = col[(size_t)(v0 + u) * nz];
+#pragma unroll
+        for (int u = 0; u < U; ++u) add(h[u], v0 + u);
+    }
+    for (; v0 < nv; ++v0) add(col[(size_t)v0 * nz], v0);
+    const double Nd = (double)tot, m = wsum / Nd;
+    // quantile start cells: stage K = 2 .. 4 at qi[K (K - 1) / 2 - 1 + j]
+    int qi[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) qi[i] = 0;
+    long long cum = 0;
+    double vsum = 0.0;
+    RowWalk walk(rows, nv);
+    for (int v = walk.next(); v >= 0; v = walk.next()) {
+        const T h = col[(size_t)v * nz];
+        const double d = ((((double)v + 0.5) / (double)nv) * w2 - half_width) - m;
+        vsum += (double)h * d * d;
+        const long long before = cum;
+        cum += h;
+#pragma unroll
+        for (int K = 2; K <= 4; ++K)
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const long long t = (2 * j + 1) * tot;
+                qi[K * (K - 1) / 2 - 1 + j] = (2 * K * before < t && 2 * K * cum >= t) ? v : qi[K * (K - 1) / 2 - 1 + j];
+            }
+    }
+    const double V = vsum / Nd;
+    mixture_stage<1, T>(col, nv, nz, rows, half_width, Nd, m, V, qi, n_iter, reg, store, o, (size_t)b, z, Kmax);
+    if (Kmax >= 2) mixture_stage<2, T>(col, nv, nz, rows, half_width, Nd, m, V, qi + 0, n_iter, reg, store, o, (size_t)b, z, Kmax);
+    if (Kmax >= 3) mixture_stage<3, T>(col, nv, nz, rows, half_width, Nd, m, V, qi + 2, n_iter, reg, store, o, (size_t)b, z, Kmax);
+    if (Kmax >= 4) mixture_stage<4, T>(col, nv, nz, rows, half_width, Nd, m, V, qi + 5, n_iter, reg, store, o, (size_t)b, z, Kmax);
+}
+
 }  // namespace hitmap

@@ -183,6 +183,44 @@ def interval_marginals(hitmap, lo, hi):
     return out
 
 
+def _mixture_arguments(maps, half_width, max_components, n_iter, reg):
+    """The checks of ``mixture`` that need no device: (Kmax, n_iter, reg), with the default reg = dx^2 / 12."""
+    if not isinstance(maps, torch.Tensor) or maps.ndim != 3:
+        raise TypeError("hit maps are a tensor [B, n_value, n_depth]")
+    if maps.dtype not in (torch.int32, torch.int64):
+        raise TypeError("hit maps are int32 (or int64 interval marginals), not %s" % maps.dtype)
+    if not maps.is_contiguous():
+        raise ValueError("hit maps must be contiguous (depth fastest)")
+    if maps.shape[1] < 1 or maps.shape[2] < 1:
+        raise ValueError("hit maps need at least one value cell and one depth cell, got %r" % (tuple(maps.shape),))
+    from . import mixtures
+    return mixtures.check_arguments(maps.shape[1], half_width, max_components, n_iter, reg)
+
+
+def mixture(maps, half_width, max_components=3, n_iter=50, reg=None):
+    """Local mixture fits in one kernel (gbp_hitmap_mixture): every stage K = 1 .. ``max_components`` (at most 4) of the
+    rule of ``mixtures.mixture_reference`` for every column of ``maps`` [B, n_value, n_depth] (int32, or int64 interval marginals:
+    gbp_hitmap_mixture_i64), K Gaussians fitted to the binned column by ``n_iter`` EM iterations from the quantile start; ``reg`` is
+    added to every variance (default dx^2 / 12, a value cell's own variance).  Returns the stages on the maps' device: ``weight`` /
+    ``mean`` / ``sd`` [B, Kmax (Kmax + 1) / 2, n_depth] (stage K in slots K (K - 1) / 2 .. + K; means WITHOUT the prior shift), ``loglik``
+    / ``ll_change`` [B, Kmax, n_depth] and ``misfit`` [B, Kmax, 2, n_depth] (the relative max and 2-norms of pmf minus fit); NaN for an
+    empty column.  ``mixtures.select`` picks a stage per column."""
+    K, n, reg = _mixture_arguments(maps, half_width, max_components, n_iter, reg)
+    if maps.device.type != "cuda":
+        raise _lib.NativeLibraryError("hitmap.mixture runs on the device (gbp_hitmap_mixture); there is no host fallback")
+    entry = _entry(maps, "gbp_hitmap_mixture")
+    B, nv, nz = maps.shape
+    dev = maps.device
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
+    S = K * (K + 1) // 2
+    out = dict(weight=f64(B, S, nz), mean=f64(B, S, nz), sd=f64(B, S, nz), loglik=f64(B, K, nz), ll_change=f64(B, K, nz),
+               misfit=f64(B, K, 2, nz))
+    with torch.cuda.device(dev):
+        _lib.check(entry(B, nv, nz, maps.data_ptr(), float(half_width), K, n, reg, out["weight"].data_ptr(), out["mean"].data_ptr(),
+                         out["sd"].data_ptr(), out["loglik"].data_ptr(), out["ll_change"].data_ptr(), out["misfit"].data_ptr(), _stream(dev)))
+    return out
+
+
 def _pool_arguments(maps, C, use, max_total=None):
     """The checks of ``pool`` that need no device: (S, C, use as int32 [S, C] on the maps' device)."""
     if not isinstance(maps, torch.Tensor) or maps.ndim != 3:

@@ -14,12 +14,15 @@ Everything is log10 conductivity (S/m) except entropy (bits), opacity and probab
     python -m geobipy_amd.line_products <container or directory> [--credible 90] [--doi 67] [--percentiles 5 50 95]
                                         [--class-means M1 M2 ... --class-scales S1 S2 ...] [--elevation-axis DZ [TOP BOTTOM]]
                                         [--depth-intervals E0 E1 ... | --elevation-intervals E0 E1 ...]
+                                        [--mixtures [KMAX] [--mixture-iterations N]]
 
 writes ``<line>.products.npz`` next to each ``<line>.h5`` / ``<line>.results.npz``.  The class means and scales (standard deviations)
 are in log10 S/m; they come together, 1 to 16 of each.  With ``--elevation-axis`` the per-depth-cell products also go onto a regular
 elevation axis (``on_elevation``, ``elevation.regular_axis``), written to ``<line>.products_elevation.npz`` beside the first file.
 With ``--depth-intervals`` / ``--elevation-intervals`` the file also holds the products of the units between those edges (``interval_*``:
-the statistics of each unit's marginal posterior, ``from_results(intervals=...)``, geobipy_amd/intervals.py).
+the statistics of each unit's marginal posterior, ``from_results(intervals=...)``, geobipy_amd/intervals.py).  With ``--mixtures`` it
+holds the local mixture fit of every depth cell's posterior (``mixture_*``, geobipy_amd/mixtures.py), from which
+``python -m geobipy_amd.mixtures`` derives global classes for ``--class-means`` / ``--class-scales``.
 """
 import argparse
 import glob
@@ -168,12 +171,40 @@ def check_classes(means, scales):
 INTERVAL_DROPPED = ("entropy", "s1")          # (the reference's density is over the sounding's 2-D mesh: not defined for a unit)
 
 
-def interval_products(hm, lmp, half_width, lo, hi, percentiles=(5, 50, 95), credible=90.0, classes=None):
+MIXTURE_OPTIONS = ("max_components", "n_iter", "reg", "epsilon", "mu")
+MIXTURE_ENTRIES = (("n", "n_components"), ("weight", "weight"), ("mean", "mean"), ("sd", "sd"), ("misfit", "misfit"), ("ll_change", "ll_change"))
+
+
+def check_mixtures(options, n_value, half_width):
+    """The ``mixtures=`` options of ``from_results`` as the keyword arguments of ``mixtures.fit``, checked (True / an empty dict: the
+    defaults)."""
+    from . import mixtures as mx
+    o = {} if options is True else dict(options)
+    if set(o) - set(MIXTURE_OPTIONS):
+        raise ValueError("mixtures: unknown options %r (known: %s)" % (sorted(set(o) - set(MIXTURE_OPTIONS)), ", ".join(MIXTURE_OPTIONS)))
+    K, n_iter, reg = mx.check_arguments(n_value, half_width, o.get("max_components", 3), o.get("n_iter", 50), o.get("reg"))
+    eps, mu = float(o.get("epsilon", 0.05)), float(o.get("mu", 0.1))
+    if not (math.isfinite(eps) and math.isfinite(mu) and eps >= 0.0 and mu >= 0.0):
+        raise ValueError("mixtures: epsilon and mu must be finite and not negative")
+    return dict(max_components=K, n_iter=n_iter, reg=reg, epsilon=eps, mu=mu)
+
+
+def mixture_products(hm, lmp, half_width, options, prefix="mixture_"):
+    """The ``mixture_*`` entries of a block of hit maps (or int64 interval marginals) on the device: ``mixtures.fit`` under ``options``
+    (``check_mixtures``) -> <prefix>n [B, n_depth] (int32), <prefix>weight / mean / sd [B, Kmax, n_depth], <prefix>misfit [B, 2,
+    n_depth] and <prefix>ll_change [B, n_depth]."""
+    from . import mixtures as mx
+    f = mx.fit(hm, lmp, half_width, **options)
+    return {prefix + a: f[b] for a, b in MIXTURE_ENTRIES}
+
+
+def interval_products(hm, lmp, half_width, lo, hi, percentiles=(5, 50, 95), credible=90.0, classes=None, mixtures=None):
     """The ``interval_*`` entries of a block of hit maps on the device: ``hitmap.interval_marginals`` over the ranges ``lo`` / ``hi``
     [B, M], then ``hitmap.products`` (and ``hitmap.class_probability`` for ``classes`` = (means, scales)) along the value axis of the
     int64 marginals [B, n_value, M]: mean, median, mode, percentile_<p>, credible_low / high / range, total (int64) [B, M] and, with
     classes, class_probability [B, K, M], highest_marginal, probability_of_highest_marginal; float entries NaN where a range has no
-    cells.  Torch tensors on the maps' device."""
+    cells.  With ``mixtures`` (the options of ``check_mixtures``) also the local mixture fits of the marginals, interval_mixture_*
+    (``mixture_products``).  Torch tensors on the maps' device."""
     from . import hitmap
     marg = hitmap.interval_marginals(hm, lo, hi)
     nz = hm.shape[2]
@@ -185,6 +216,8 @@ def interval_products(hm, lmp, half_width, lo, hi, percentiles=(5, 50, 95), cred
         c = hitmap.class_probability(marg, lmp, half_width, *classes)
         out.update(interval_class_probability=c["probability"], interval_highest_marginal=c["highest_marginal"],
                    interval_probability_of_highest_marginal=c["probability_of_highest_marginal"])
+    if mixtures is not None:
+        out.update(mixture_products(marg, lmp, half_width, mixtures, prefix="interval_mixture_"))
     nan = torch.full((), float("nan"), dtype=torch.float64, device=marg.device)
     for k, v in out.items():
         if v.dtype.is_floating_point:
@@ -192,7 +225,7 @@ def interval_products(hm, lmp, half_width, lo, hi, percentiles=(5, 50, 95), cred
     return out
 
 
-def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0, classes=None, intervals=None):
+def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credible=90.0, doi=67.0, classes=None, intervals=None, mixtures=None):
     """{name: numpy array} of the line products of the results container at ``path`` (``<line>.h5`` or the ``.results[.npz]`` stand-in,
     read through ``hdf.load_results``; the reference's own files where they hold this layout).  The hit maps go to ``device`` (default
     cuda:0) ``block`` soundings at a time.  Per sounding [N, n_depth] (log10 S/m): mean, median, mode, percentile_<p>, credible_low /
@@ -219,7 +252,15 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     ``interval_class_probability`` [N, K, M], ``interval_highest_marginal`` and ``interval_probability_of_highest_marginal``, and the
     spec itself (``interval_kind``, ``interval_edges`` / ``interval_pairs`` / ``interval_top``, ``interval_bottom``).  The ranges are
     computed once per line on the host; the marginals come from the blocks the products are computed on.  Entropy, opacity and DOI are
-    not defined for units."""
+    not defined for units.
+
+    ``mixtures`` = a dict of options (``max_components`` 1 .. 4, default 3; ``n_iter``, ``reg``, ``epsilon``, ``mu``: ``mixtures.fit``;
+    True for the defaults) adds the local mixture fit of every column from the same uploaded blocks (``hitmap.mixture``, DESIGN.md
+    3.16): ``mixture_n`` [N, n_depth] (int32, the number of components the stopping rule keeps; 0 for an empty column),
+    ``mixture_weight`` / ``mixture_mean`` / ``mixture_sd`` [N, Kmax, n_depth] (sorted by mean, NaN beyond mixture_n; means in log10
+    S/m), ``mixture_misfit`` [N, 2, n_depth] and ``mixture_ll_change`` [N, n_depth] (the log-likelihood's change over the last
+    iteration: whether n_iter was enough).  With ``intervals`` also ``interval_mixture_*`` [N, Kmax, M], the fits of the units'
+    marginal posteriors.  ``mixtures.global_classes`` turns the lines' fits into classes."""
     from . import hdf, hitmap
     from . import intervals as iv
     if not 0.0 < float(credible) < 100.0:
@@ -237,6 +278,8 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
     if v_edges is None or d_edges is None or v_edges.size != nv + 1 or d_edges.size != nz + 1:
         raise ValueError("%s: the hit maps' mesh (%s/mesh/y and /z edges) does not match their shape %r" % (path, VALUES, hm_all.shape))
     hw = _uniform_half_width(v_edges)
+    if mixtures is not None:
+        mixtures = check_mixtures(mixtures, nv, hw)
     rel = np.zeros(N) if rel is None else np.broadcast_to(np.asarray(rel, dtype=np.float64).reshape(-1), (N,))
     dev = torch.device(device) if device is not None else torch.device("cuda", 0)
     elev = _key(arrays, "/data/elevation/data", "/data/elevation")
@@ -252,7 +295,9 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
         p = hitmap.products(hm, lmp, hw, percentiles=percentiles, credible=credible, depth_edges=d_edges)
         if intervals is not None:
             p.update(interval_products(hm, lmp, hw, torch.as_tensor(rng.lo[b0:b1]), torch.as_tensor(rng.hi[b0:b1]), percentiles=percentiles,
-                                       credible=credible, classes=None if classes is None else (cmeans, cscales)))
+                                       credible=credible, classes=None if classes is None else (cmeans, cscales), mixtures=mixtures))
+        if mixtures is not None:
+            p.update(mixture_products(hm, lmp, hw, mixtures))
         if classes is not None:
             c = hitmap.class_probability(hm, lmp, hw, cmeans, cscales)
             p.update(class_probability=c["probability"], highest_marginal=c["highest_marginal"],
@@ -290,6 +335,12 @@ def from_results(path, device=None, block=4096, percentiles=(5, 50, 95), credibl
             out.update(class_probability=np.zeros((0, K, nz)), highest_marginal=np.zeros((0, nz), dtype=np.int32),
                        probability_of_highest_marginal=np.zeros((0, nz)))
         out["class_means"], out["class_scales"] = cmeans, cscales
+    if mixtures is not None and not N:
+        cells = [("mixture_", nz)] + ([("interval_mixture_", iv.n_intervals(spec))] if intervals is not None else [])
+        for prefix, n in cells:
+            out[prefix + "n"] = np.zeros((0, n), dtype=np.int32)
+            out.update({prefix + k: np.zeros((0, mixtures["max_components"], n)) for k in ("weight", "mean", "sd")})
+            out[prefix + "misfit"], out[prefix + "ll_change"] = np.zeros((0, 2, n)), np.zeros((0, n))
     if intervals is not None:
         if not N:
             M = iv.n_intervals(spec)
@@ -310,7 +361,8 @@ def on_elevation(products, surface, edges=None, levels=None, device=None):
     over each cell of the ascending ``edges`` [E + 1], or the value at each of ``levels`` [E]; exactly one of the two.  ``surface`` [N]:
     the soundings' surface elevation (the container's /data/elevation).  Integer entries (class indices: ``highest_marginal``) are never
     averaged: with ``edges`` they are taken at the centre of each cell.  Everything else (the per-sounding and per-line entries, the
-    depth axes, the ``interval_*`` entries, which are over units and not over depth cells however many there are,
+    depth axes, the ``interval_*`` entries, which are over units and not over depth cells however many there are, the ``mixture_*``
+    entries, whose components have no identity from one depth cell to the next that a mean over cells could keep,
     ``interface_probability`` where it has a depth mesh of its own) passes through, and the result also carries
     ``elevation_edges`` (and ``elevation_centres``) or ``elevation_levels``, and ``surface``."""
     from . import _lib, elevation
@@ -328,7 +380,7 @@ def on_elevation(products, surface, edges=None, levels=None, device=None):
     for k, v in products.items():
         a = np.asarray(v)
         own_mesh = k == "interface_probability" and not np.array_equal(np.asarray(products.get("interface_depth_edges", d_edges)), d_edges)
-        if (k.startswith("interval_") or a.ndim not in (2, 3) or a.shape[-1] != nz or a.shape[0] != s.size or a.size == 0 or own_mesh
+        if (k.startswith(("interval_", "mixture_")) or a.ndim not in (2, 3) or a.shape[-1] != nz or a.shape[0] != s.size or a.size == 0 or own_mesh
                 or a.dtype.kind not in "fiub"):                             # (interval_*: over units, not depth cells, whatever their count)
             out[k] = v
             continue
@@ -398,6 +450,10 @@ def parser():
                          "elevation axis of DZ m, from BOTTOM to TOP (default: everything the line's soundings reach), snapped outward "
                          "to multiples of DZ")
     add_interval_arguments(ap)
+    ap.add_argument("--mixtures", type=int, nargs="?", const=3, default=None, metavar="KMAX",
+                    help="also the local mixture fit of every depth cell's posterior (and of every unit's, with intervals): up to KMAX "
+                         "Gaussians, 1 to 4 (default 3), written as mixture_* entries")
+    ap.add_argument("--mixture-iterations", type=int, default=None, metavar="N", help="EM iterations of --mixtures (default 50)")
     ap.add_argument("--block", type=int, default=4096, help="soundings per upload (default 4096)")
     ap.add_argument("--device", default=None, help="torch device of the kernel (default cuda:0)")
     return ap
@@ -460,6 +516,15 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error("--elevation-axis: " + str(e))
     a.intervals = interval_arguments(ap, a, ("--elevation-axis",))
+    if a.mixtures is None and a.mixture_iterations is not None:
+        ap.error("--mixture-iterations comes with --mixtures")
+    if a.mixtures is not None:
+        if not 1 <= a.mixtures <= 4:
+            ap.error("--mixtures KMAX must lie in 1 .. 4")
+        n_iter = 50 if a.mixture_iterations is None else a.mixture_iterations
+        if not 1 <= n_iter <= 10000:
+            ap.error("--mixture-iterations must lie in 1 .. 10000")
+        a.mixtures = dict(max_components=a.mixtures, n_iter=n_iter)
     return a
 
 
@@ -484,7 +549,7 @@ def main(argv=None):
     for f in files:
         classes = None if a.class_means is None else (a.class_means, a.class_scales)
         out = from_results(f, device=a.device, block=a.block, percentiles=tuple(a.percentiles), credible=a.credible, doi=a.doi,
-                           classes=classes, intervals=a.intervals)
+                           classes=classes, intervals=a.intervals, mixtures=a.mixtures)
         dst = save(out, output_path(f))
         print("%s -> %s (%d soundings)" % (f, dst, out["mean"].shape[0]))
         if a.elevation_axis is not None:

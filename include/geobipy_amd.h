@@ -696,6 +696,23 @@ gbp_status gbp_hitmap_classes_i64(int B, int n_value, int n_depth, const int64_t
  * before any launch; S == 0 launches nothing.  The caller keeps C times a column's total below 2^31. */
 gbp_status gbp_hitmap_pool(int S, int C, int n_value, int n_depth, const int32_t *hitmap, const int32_t *use, double half_width,
                            int32_t *pooled, int32_t *n_used, double *chain_mean, double *rhat, double *jsd, void *stream);
+/* gbp_hitmap_mixture -- local mixture fits (the host statement of the rule is geobipy_amd/mixtures.py
+ * mixture_reference): for every column, every stage K = 1 .. Kmax in one launch -- K Gaussians fitted to the binned column (cell centres
+ * x_v of gbp_hitmap_statistics WITHOUT the prior shift, dx = 2 half_width / n_value) by n_iter EM iterations on the cells with counts,
+ * sums over v ascending: start w_j = 1 / K, mu_j = the centre of the first cell with 2 K cum_v >= (2 j + 1) N, s2_j = V / K^2 + reg (m, V
+ * the column's mean and variance); E-step l_vj = ln w_j - ln(2 pi s2_j) / 2 - (x_v - mu_j)^2 / (2 s2_j), L_v = logsumexp_j l_vj,
+ * r_vj = c_v exp(l_vj - L_v); M-step about the old mean d = x_v - mu_j: n_j = sum r + 10 * 2^-52, A = sum r d, Q = sum r d^2,
+ * mu_j += A / n_j, s2_j = max(Q / n_j - (A / n_j)^2, 0) + reg, w_j = n_j / sum_j n_j.  Stage 1 is the closed form (1, m, V + reg).
+ * A closing pass over ALL cells gives loglik = sum c_v L_v / N, ll_change = loglik minus that of the last E-step (0 at stage 1) and,
+ * with f_v = exp(L_v) dx and p_v = c_v / N, misfit = (max |p - f| / max p, ||p - f||_2 / ||p||_2).
+ * weight / mean / sd (= sqrt s2): [B, Kmax (Kmax + 1) / 2, n_depth], stage K in slots K (K - 1) / 2 .. + K; loglik / ll_change:
+ * [B, Kmax, n_depth]; misfit: [B, Kmax, 2, n_depth].  An empty column: NaN everywhere.  1 <= Kmax <= 4, 1 <= n_iter <= 10 000, reg and
+ * half_width finite and > 0, n_value <= 4096; GBP_ERR_INVALID_ARG for the rest, for bad sizes, NULL pointers and B * n_depth beyond int32, every check
+ * before any launch; B == 0 launches nothing.  gbp_hitmap_mixture_i64: the same over int64 maps (interval marginals). */
+gbp_status gbp_hitmap_mixture(int B, int n_value, int n_depth, const int32_t *hitmap, double half_width, int Kmax, int n_iter, double reg,
+                              double *weight, double *mean, double *sd, double *loglik, double *ll_change, double *misfit, void *stream);
+gbp_status gbp_hitmap_mixture_i64(int B, int n_value, int n_depth, const int64_t *hitmap, double half_width, int Kmax, int n_iter, double reg,
+                                  double *weight, double *mean, double *sd, double *loglik, double *ll_change, double *misfit, void *stream);
 
 /* [host] Results containers (geobipy_amd/h5lite.py; no reference counterpart -- the reference stores its hit maps dense): the rows of
  * a conductivity-depth hit map held as runs (row r owns runs ptr[r] .. ptr[r + 1] - 1; run q holds value[q] from cell start[q] of the row
