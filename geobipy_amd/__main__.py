@@ -58,7 +58,15 @@ def parse(argv=None):
     p.add_argument("--replicates", type=int, default=1, metavar="C",
                    help="chains per sounding, 1 .. 8 (frequency-domain data): the posteriors are pooled over the chains that burned in and the "
                         "summaries gain per-depth-cell convergence maps (rhat, jsd, n_used, ...)")
+    p.add_argument("--data-posteriors", type=int, nargs="?", const=64, default=None, metavar="N_BINS",
+                   help="data-space posteriors (residual of every channel's prediction, misfit: data_* / misfit_* in the summaries) on "
+                        "N_BINS cells (8 .. 256, default 64)")
     a = p.parse_args(argv)
+    if a.data_posteriors is not None:
+        if not 8 <= a.data_posteriors <= 256:
+            p.error("--data-posteriors: 8 .. 256 cells")
+        if a.no_hitmap:
+            p.error("--data-posteriors needs the hit map (drop --no-hitmap)")
     if not 1 <= a.replicates <= 8:
         p.error("--replicates: 1 .. 8 chains per sounding")
     if a.replicates > 1 and a.no_hitmap:
@@ -106,7 +114,8 @@ def main(argv=None):
                        exact_jacobian=a.exact_jacobian, hitmap=not a.no_hitmap, hankel_eps=a.hankel_eps, schedule=a.schedule, chunk=a.chunk, traces=a.traces, results_directory=containers,
                        container=None if a.container == "auto" else a.container, data_directory=a.data_directory,
                        data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
-                       first_below=tuple(a.first_below), replicates=a.replicates)
+                       first_below=tuple(a.first_below), replicates=a.replicates,
+                       data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors))
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

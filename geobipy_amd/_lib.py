@@ -31,7 +31,8 @@ class RjOptions(ctypes.Structure):
                    ("additive_independent", ctypes.c_int32), ("add_centre", ctypes.c_double * 4), ("extra_log_prior", ctypes.c_double),
                    ("trace_every", ctypes.c_int32), ("trace_length", ctypes.c_int32),
                    ("n_units", ctypes.c_int32), ("unit_kinds", ctypes.c_int32), ("n_first", ctypes.c_int32),
-                   ("first_threshold", ctypes.c_double * 4), ("first_direction", ctypes.c_int32 * 4)])
+                   ("first_threshold", ctypes.c_double * 4), ("first_direction", ctypes.c_int32 * 4),
+                   ("n_data_bins", ctypes.c_int32), ("data_half_width", ctypes.c_double), ("misfit_half_width", ctypes.c_double)])
 
 
 RJ_CHAIN_FIELDS = ("rel_group", "add_group", "add_scale", "chain_id", "data", "height", "log_mean_prior", "k", "edges", "sigma", "rel", "add", "pred", "J", "prior", "like", "misfit",
@@ -39,7 +40,7 @@ RJ_CHAIN_FIELDS = ("rel_group", "add_group", "add_scale", "chain_id", "data", "h
                    "log_prop", "sigma_p", "pred_p", "misfit_p", "like_p", "J_p", "log_ratio", "n_accepted", "k_hist", "edge_hist",
                    "rel_hist", "add_hist", "hitmap", "hit_dwell", "burned_in_iteration", "status", "best_posterior", "best_k", "best_edges", "best_sigma",
                    "best_rel", "best_add", "iteration0", "height_p", "height0", "height_hist", "best_height", "step_flags", "trace_misfit", "trace_accept",
-                   "best_iteration", "unit_z", "unit_hist", "first_hist", "first_none")
+                   "best_iteration", "unit_z", "unit_hist", "first_hist", "first_none", "data_scale", "data_hist", "misfit_scale", "misfit_hist")
 
 
 class RjChains(ctypes.Structure):

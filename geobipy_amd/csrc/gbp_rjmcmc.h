@@ -1245,6 +1245,48 @@ __device__ __noinline__ void units_zero(const RjOpt& o, const gbp_rj_chains& c, 
     }
 }
 
+// Data-space posteriors (gbp_rj_options.n_data_bins; include/geobipy_amd.h states the rule): `weight` counts of a state's prediction
+// `pred` [N] and misfit added to chain b's residual histograms and misfit histogram.  Lane i of the chain's W lanes owns channels
+// i, i + W, ... and lane 0 the misfit, so a count has one owner and plain adds suffice (as in units_add).  Every operation of the
+// cell position is rounded once (the intrinsics: the host's numpy expression gives the same bits); a non-finite position has no cell.
+// Called where the hit map is settled, with the same dwell: a chain's prediction and misfit change only when a proposal is accepted.
+__device__ inline bool data_on(const gbp_rj_chains& c) { return c.data_hist != nullptr; }
+__device__ inline bool extras_on(const gbp_rj_chains& c) { return units_on(c) || data_on(c); }
+
+__device__ inline int data_cell(double x, double H, int nb)
+{
+    const double pos = __dmul_rn(__ddiv_rn(__dadd_rn(x, H), __dmul_rn(2.0, H)), (double)nb);
+    if (!(fabs(pos) < INF)) return -1;
+    return (int)fmin(fmax(floor(pos), 0.0), (double)(nb - 1));
+}
+
+template <int W>
+__device__ __noinline__ void data_add(const RjOpt& o, const gbp_rj_chains& c, size_t b, const double* pred, double misfit, int i, int weight)
+{
+    const int N = o.n_channels, nb = o.n_data_bins;
+    for (int n = i; n < N; n += W) {
+        const double obs = c.data[b * N + n];
+        if (!(obs > 0.0)) continue;                              // inactive channels get no counts
+        const double r = __ddiv_rn(__dsub_rn(pred[n], obs), c.data_scale[b * N + n]);
+        const int bin = data_cell(r, o.data_half_width, nb);
+        if (bin >= 0) c.data_hist[(b * nb + bin) * N + n] += weight;
+    }
+    if (i == 0) {
+        const double inv_ln10 = 0.43429448190325182765;
+        const int bin = data_cell(__dmul_rn(rj_log(__ddiv_rn(misfit, c.misfit_scale[b])), inv_ln10), o.misfit_half_width, nb);
+        if (bin >= 0) c.misfit_hist[b * nb + bin] += weight;
+    }
+}
+
+// (burn-in reset, W lanes of chain b)
+template <int W>
+__device__ __noinline__ void data_zero(const RjOpt& o, const gbp_rj_chains& c, size_t b, int i)
+{
+    const size_t nb = (size_t)o.n_data_bins, n = nb * o.n_channels;
+    for (size_t q = i; q < n; q += W) c.data_hist[b * n + q] = 0;
+    for (size_t q = i; q < nb; q += W) c.misfit_hist[b * nb + q] = 0;
+}
+
 __device__ inline double group_sum8(double v)
 {
     // (the pairs of the xor butterfly: lane ^ 1, lane ^ 2, then the other quad -- whose four lanes hold one value)
@@ -1258,12 +1300,13 @@ __device__ inline double group_sum8(double v)
 // all lanes of a chain sit in one wave, so program order is the only ordering needed between them.
 // (have_regs, W == 8: entry i of the post-step rows is in e_now / s_now -- the interface histogram then costs no loads, and the counters
 //  are atomic adds whose result nobody waits for: the stage is a latency chain, every read-modify-write was a trip to memory)
-// (UNITS: the sampled unit posteriors are compiled in -- the instantiations without them are the code they were before the feature)
+// (UNITS: the sampled extras -- unit posteriors, data-space posteriors -- are compiled in, each guarded by its own pointer at run time;
+//  the instantiations without them are the code they were before the features.  pred_now: the post-step prediction, passed like ec / sc)
 template <int W, bool UNITS = false>
 __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32_t iter, int accumulate, size_t b, int i,
                                    int kc, const double* ec, const double* sc, double post, double best_prev, double misfit_now,
                                    const Levels& lev, double lmp, int dwell, double height_now, bool accepted, bool have_regs = false,
-                                   double e_now = 0.0, double s_now = 0.0)
+                                   double e_now = 0.0, double s_now = 0.0, const double* pred_now = nullptr)
 {
     const double s_dn_reg = (W == 8 && have_regs) ? lane_dn(s_now) : 0.0;      // (issued by every lane of the wave's live groups)
     const int K = o.max_layers, N = o.n_channels;
@@ -1299,6 +1342,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
                     for (size_t q = i; q < nh; q += W) c.hitmap[b * nh + q] = 0;
                     dwell = 0;
                     if (UNITS && units_on(c)) units_zero<W>(o, c, b, i);
+                    if (UNITS && data_on(c)) data_zero<W>(o, c, b, i);
                 }
                 if (i == 0) c.burned_in_iteration[b] = bi;
             }
@@ -1347,6 +1391,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
         if (finished && dwell > 0) {                             // the chain stops here: settle its last model
             hitmap_add<W>(o, c.hitmap + b * nh, ec, sc, kc, lmp, i, dwell);
             if (UNITS && units_on(c)) units_add<W>(o, c, b, ec, sc, kc, lmp, i, dwell);
+            if (UNITS && data_on(c)) data_add<W>(o, c, b, pred_now, misfit_now, i, dwell);
             dwell = 0;
         }
         if (i == 0) c.hit_dwell[b] = dwell;
@@ -1480,6 +1525,7 @@ __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains&
     if (accept && dwell > 0) {                                   // the model changes: settle the old one first
         hitmap_add<64>(o, c.hitmap + (size_t)b * nh, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
         if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
+        if (UNITS && data_on(c)) data_add<64>(o, c, (size_t)b, c.pred + (size_t)b * N, misfit_c, lane, dwell);      // (before pred is overwritten)
         dwell = 0;
         wave_sync();
     }
@@ -1510,7 +1556,8 @@ __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains&
     }
     const int bk = bookkeeping<64, UNITS>(o, c, iter, accumulate, (size_t)b, lane, accept ? k : k_prev, accept ? e : c.edges + (size_t)b * K,
                                    accept ? c.sigma_p + (size_t)b * K : c.sigma + (size_t)b * K, accept ? prior_p + like_p : prior_c + like_c,
-                                   best_prev, accept ? misfit_p : misfit_c, select_levels(accept, lev_p, lev_c), lmp, dwell, height_now, accept);
+                                   best_prev, accept ? misfit_p : misfit_c, select_levels(accept, lev_p, lev_c), lmp, dwell, height_now, accept,
+                                   false, 0.0, 0.0, UNITS ? (accept ? c.pred_p : c.pred) + (size_t)b * N : nullptr);
     if (lane == 0 && c.step_flags != nullptr) c.step_flags[b] = (accept ? 1 : 0) | (bk & 15);
 }
 
@@ -1840,6 +1887,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
         const bool on = accept && dwell > 0;
         hitmap_add8(o, c.hitmap + bb * nh, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, base, dwell, on);
         if (UNITS && on && units_on(c)) units_add<8>(o, c, bb, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, dwell);
+        if (UNITS && on && data_on(c)) data_add<8>(o, c, bb, c.pred + bb * N, misfit_c, i, dwell);      // (before pred is overwritten)
         if (on) dwell = 0;
     }
     if (accept && one_trip) {
@@ -1884,7 +1932,8 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
     const int bk = bookkeeping<8, UNITS>(o, c, iter, accumulate, bb, i, accept ? k : k_prev, accept ? e : c.edges + bb * K,
                                   accept ? c.sigma_p + bb * K : c.sigma + bb * K, accept ? prior_p + like_p : prior_c + like_c, best_prev,
                                   accept ? misfit_p : misfit_c, select_levels(accept, lev_p, lev_c), lmp, dwell, height_now, accept, one_trip,
-                                  accept ? pre.e_i : pre.ce_i, accept ? sp_ic : pre.cs_i);
+                                  accept ? pre.e_i : pre.ce_i, accept ? sp_ic : pre.cs_i,
+                                  UNITS ? (accept ? c.pred_p : c.pred) + bb * N : nullptr);
     if (st != nullptr && (bk & 16)) st->status = 1;             // (the chain stopped in this very iteration: its next proposal is the idle one)
     if (i == 0 && c.step_flags != nullptr) c.step_flags[bb] = (accept ? 1 : 0) | (bk & 15);
 }
@@ -1994,6 +2043,7 @@ __global__ __launch_bounds__(64) void k_rj_flush(RjOpt o, gbp_rj_chains c)
     hitmap_add<64>(o, c.hitmap + (size_t)b * o.n_depth_bins * o.n_value_bins, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b],
                    c.log_mean_prior[b], lane, dwell);
     if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b], c.log_mean_prior[b], lane, dwell);
+    if (UNITS && data_on(c)) data_add<64>(o, c, (size_t)b, c.pred + (size_t)b * o.n_channels, c.misfit[b], lane, dwell);
     __syncthreads();
     if (lane == 0) c.hit_dwell[b] = 0;
 }
@@ -2392,7 +2442,7 @@ __device__ GBP_STAGE_ATTR void stage_accept(const PersistentCtx* x, uint32_t ite
     else accept_body(*x->o, c, iter, accumulate, 8, x->b, lane, x->sh_dyn);
 }
 
-// (the same with the sampled unit posteriors: a stage of its own, chosen by a uniform branch, so that chains without them run the stage
+// (the same with the sampled extras -- unit posteriors, data-space posteriors: a stage of its own, chosen by a uniform branch, so that chains without them run the stage
 //  they always ran -- as template parameters of the kernel, the two extra instantiations moved the register allocation of the OTHER stages)
 __device__ GBP_STAGE_ATTR void stage_accept_units(const PersistentCtx* x, uint32_t iter, int accumulate, int lane)
 {
@@ -2532,7 +2582,7 @@ __global__ GBP_RJ_PERSISTENT_BOUNDS void k_rj_persistent(RjOpt o_arg, gbp_rj_cha
         else stage_forward(&sh_x);                                // Inference1D.py:572-597: forward + chi^2 + logL of the proposal
         __syncthreads();
         tick(3);
-        if (wave == 0) { GBP_RJ_SERIAL_PRIO(GBP_RJ_PERSISTENT_PRIO); if (units_on(c_arg)) stage_accept_units(&sh_x, iter, accumulate, lane); else stage_accept(&sh_x, iter, accumulate, lane); GBP_RJ_SERIAL_PRIO(0); }
+        if (wave == 0) { GBP_RJ_SERIAL_PRIO(GBP_RJ_PERSISTENT_PRIO); if (extras_on(c_arg)) stage_accept_units(&sh_x, iter, accumulate, lane); else stage_accept(&sh_x, iter, accumulate, lane); GBP_RJ_SERIAL_PRIO(0); }
         __syncthreads();
         tick(4);
         if (clocked) GBP_RJ_TICKS[5] += 1;
@@ -2739,6 +2789,8 @@ gbp_rj_chains slice_chains(const gbp_rj_options& o, const gbp_rj_chains& c, int 
     GBP_OFF(trace_misfit, (size_t)o.trace_length) GBP_OFF(trace_accept, (size_t)o.trace_length) GBP_OFF(best_iteration, 1)
     const size_t nu = (size_t)o.n_units, nq = (size_t)((o.unit_kinds & 1) + ((o.unit_kinds >> 1) & 1)), nf = (size_t)o.n_first;
     GBP_OFF(unit_z, nu * 2) GBP_OFF(unit_hist, nq * nv * nu) GBP_OFF(first_hist, nf * nd) GBP_OFF(first_none, nf)
+    const size_t ndb = (size_t)o.n_data_bins;
+    GBP_OFF(data_scale, N) GBP_OFF(data_hist, ndb * N) GBP_OFF(misfit_scale, 1) GBP_OFF(misfit_hist, ndb)
 #undef GBP_OFF
     return s;
 }
@@ -2779,6 +2831,17 @@ gbp_status rj_check(const gbp_rj_options* o, const gbp_rj_chains* c)
     for (int q = 0; q < o->n_first; ++q) {
         if (!(std::isfinite(o->first_threshold[q]) && o->first_threshold[q] > 0.0)) return fail(GBP_ERR_INVALID_ARG, "first_threshold must be finite and positive%s");
         if (o->first_direction[q] != 1 && o->first_direction[q] != -1) return fail(GBP_ERR_INVALID_ARG, "first_direction must be +1 or -1%s");
+    }
+    // data-space posteriors: settled and zeroed with the hit map too
+    const bool data_any = c->data_hist || c->misfit_hist || c->data_scale || c->misfit_scale;
+    if (o->n_data_bins != 0 || data_any) {
+        if (o->n_data_bins < 8 || o->n_data_bins > 256) return fail(GBP_ERR_INVALID_ARG, "n_data_bins must be 0 (off) or in [8, 256]%s");
+        if (!(std::isfinite(o->data_half_width) && o->data_half_width > 0.0) || !(std::isfinite(o->misfit_half_width) && o->misfit_half_width > 0.0))
+            return fail(GBP_ERR_INVALID_ARG, "data_half_width and misfit_half_width must be finite and positive%s");
+        if (!c->data_hist || !c->misfit_hist) return fail(GBP_ERR_INVALID_ARG, "data_hist and misfit_hist come together, with n_data_bins >= 8%s");
+        if (!c->hitmap)
+            return fail(GBP_ERR_INVALID_ARG, "data posteriors (data_hist / misfit_hist) need the hit map: they are settled with its dwell times%s");
+        if (!c->data_scale || !c->misfit_scale) return fail(GBP_ERR_INVALID_ARG, "data_hist needs data_scale, misfit_hist needs misfit_scale%s");
     }
     const void* need[] = {c->data, c->height, c->log_mean_prior, c->k, c->edges, c->sigma, c->rel, c->add, c->pred, c->J, c->prior,
                           c->like, c->misfit, c->action, c->k_r, c->nl_a, c->nl_b, c->nl_c, c->edges_r, c->sigma_r, c->thk_r, c->rel_p,
@@ -2859,7 +2922,7 @@ gbp_status gbp_rj_accept(const gbp_rj_options* o, const gbp_rj_chains* c, int64_
     if (st != GBP_OK || c->B == 0) return st;
     const int n_packed = (c->B + 7) / 8, n_deep = o->max_layers > 8 ? (c->B + 63) / 64 : 0;      // (deep: scanning workgroups of 64 chains)
     const size_t lds8 = (size_t)8 * o->n_channels * sizeof(double), lds_deep = rj::Lds::bytes(o->max_layers, o->n_channels);
-    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr;     // (their code is in instantiations of its own)
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr;     // (the extras' code is in instantiations of its own)
     hipLaunchKernelGGL(units ? rj::k_rj_accept8<true> : rj::k_rj_accept8<false>, dim3(n_packed + n_deep), dim3(64),
                        n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, accumulate, n_packed);
     GBP_HIP(hipGetLastError());
@@ -3279,7 +3342,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
                 const size_t lds = std::max((size_t)8 * o->n_channels * sizeof(double), n_deep ? rj::Lds::bytes(K, o->n_channels) : (size_t)0);
                 const int32_t* cur = t.flags + (size_t)(it & 1) * nB;
                 int32_t* nxt = t.flags + (size_t)((it + 1) & 1) * nB;
-                const bool units = t.c.unit_hist != nullptr || t.c.first_hist != nullptr;
+                const bool units = t.c.unit_hist != nullptr || t.c.first_hist != nullptr || t.c.data_hist != nullptr;
                 hipLaunchKernelGGL(units ? rj::k_rj_step8<true> : rj::k_rj_step8<false>, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o),
                                    t.c, (uint32_t)iter, accumulate, n_packed, cur, nxt);
                 return GBP_OK;
@@ -3412,7 +3475,7 @@ gbp_status gbp_rj_flush_posteriors(const gbp_rj_options* o, const gbp_rj_chains*
 {
     gbp_status st = rj_check(o, c);
     if (st != GBP_OK || c->B == 0 || !c->hitmap) return st;
-    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr;
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr;
     hipLaunchKernelGGL(units ? rj::k_rj_flush<true> : rj::k_rj_flush<false>, dim3(c->B), dim3(64), 0, (hipStream_t)stream, rj::extend(*o), *c);
     GBP_HIP(hipGetLastError());
     return GBP_OK;

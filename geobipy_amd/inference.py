@@ -209,6 +209,29 @@ def check_first(thresholds, directions):
     return t, d
 
 
+def check_data_posteriors(n_bins, half_width, misfit_half_width):
+    """(n_bins, half_width, misfit_half_width) of the data-space posteriors, refused unless 8 <= n_bins <= 256 and both widths are
+    finite and positive (gbp_rj_options.n_data_bins ...)."""
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 8 <= int(n_bins) <= 256:
+        raise ValueError("data posteriors: n_bins must be an integer in [8, 256], got %r" % (n_bins,))
+    hw, mhw = float(half_width), float(misfit_half_width)
+    if not (math.isfinite(hw) and hw > 0.0) or not (math.isfinite(mhw) and mhw > 0.0):
+        raise ValueError("data posteriors: half_width and misfit_half_width must be finite and positive")
+    return int(n_bins), hw, mhw
+
+
+def data_posteriors_argument(arg):
+    """``data_posteriors`` keyword of the samplers -> None (off) or dict(n_bins, half_width, misfit_half_width, scale), checked."""
+    if arg is None or arg is False:
+        return None
+    d = {} if arg is True else dict(arg)
+    unknown = set(d) - {"n_bins", "half_width", "misfit_half_width", "scale"}
+    if unknown:
+        raise ValueError("data_posteriors: unknown keys %s" % sorted(unknown))
+    nb, hw, mhw = check_data_posteriors(d.get("n_bins", 64), d.get("half_width", 8.0), d.get("misfit_half_width", 2.0))
+    return dict(n_bins=nb, half_width=hw, misfit_half_width=mhw, scale=d.get("scale"))
+
+
 def unit_means(edges, values, z0, z1):
     """(dz, S, T) of the unit [z0, z1] of the model (interior interface depths ``edges`` ascending, layer conductivities ``values``):
     layer l spans [top_l, bot_l) with top_0 = 0, bot_{k-1} = +inf; ov_l = max(0, min(bot_l, z1) - max(top_l, z0)); conductance
@@ -253,10 +276,13 @@ class Posteriors:
 
     def __init__(self, max_cells, max_edge, min_width, value_mean, factor=10.0, n_value_bins=250, ratio=0.5,
                  relative_error_bounds=None, additive_error_bounds=None, n_error_bins=99, height_edges=None, geometry_edges=None,
-                 units=None, unit_kinds=("arithmetic", "harmonic"), first=None):
+                 units=None, unit_kinds=("arithmetic", "harmonic"), first=None, data=None):
         """``units`` [M, 2] (top, bottom; m below the surface), ``unit_kinds`` and ``first`` = (thresholds S/m, directions +-1): the sampled
         unit posteriors (``unit_means`` / ``first_layer`` state the rule) -- ``unit_hist`` [Q, n_value_bins, M], ``first_hist``
-        [T, n_depth_bins], ``first_none`` [T]."""
+        [T, n_depth_bins], ``first_none`` [T].
+
+        ``data`` = dict(observed [N], scale [N], n_bins=64, half_width=8.0, misfit_half_width=2.0): the data-space posteriors
+        (``update_data`` states the rule) -- ``data_hist`` [n_bins, N], ``misfit_hist`` [n_bins]; ``update(..., predicted=, misfit=)``."""
         self.ratio = ratio
         # height (Point.set_z_posterior :1010-1017): the cells of the uniform prior, when the height is sampled
         self.height_edges = None if height_edges is None else np.asarray(height_edges, dtype=np.float64)
@@ -291,12 +317,55 @@ class Posteriors:
         self.first_hist = np.zeros((self.first_threshold.size, self.depth_centres.size), dtype=np.int64)
         self.first_none = np.zeros(self.first_threshold.size, dtype=np.int64)
         self.unit_edge_distance = []          # |fractional bin position - nearest integer| of every value binned: (kind row, unit, distance)
+        # data-space posteriors: the device's expressions (csrc/gbp_rjmcmc.h data_add)
+        self.data_n_bins = 0
+        self.data_hist, self.misfit_hist = np.zeros((0, 0), dtype=np.int64), np.zeros(0, dtype=np.int64)
+        self.misfit_edge_distance = []        # |fractional cell position - nearest integer| of every misfit binned
+        if data is not None:
+            nb, hw, mhw = check_data_posteriors(data.get("n_bins", 64), data.get("half_width", 8.0), data.get("misfit_half_width", 2.0))
+            self.data_n_bins, self.data_half_width, self.misfit_half_width = nb, np.float64(hw), np.float64(mhw)
+            self.observed = np.asarray(data["observed"], dtype=np.float64).reshape(-1)
+            self.data_scale = np.broadcast_to(np.asarray(data["scale"], dtype=np.float64), self.observed.shape)
+            self.data_active = self.observed > 0.0                  # (the sampler's own rule; NaN is inactive)
+            if not np.all(np.isfinite(self.data_scale[self.data_active]) & (self.data_scale[self.data_active] > 0.0)):
+                raise ValueError("data posteriors: the scale must be finite and positive on every active channel")
+            self.misfit_scale = np.float64(self.data_active.sum())
+            self.data_hist = np.zeros((nb, self.observed.size), dtype=np.int64)
+            self.misfit_hist = np.zeros(nb, dtype=np.int64)
 
     def reset(self):
         for a in (self.n_cells, self.edges, self.values, self.relative_error, self.additive_error, self.height, self.unit_hist,
-                  self.first_hist, self.first_none) + tuple(self.geometry.values()):
+                  self.first_hist, self.first_none, self.data_hist, self.misfit_hist) + tuple(self.geometry.values()):
             a[:] = 0
         del self.unit_edge_distance[:]
+        del self.misfit_edge_distance[:]
+
+    def update_data(self, predicted=None, misfit=None, weight=1):
+        """Adds one sampled state to the data-space posteriors (``update`` calls it).  Channel n, active when observed[n] > 0, numpy
+        float64, every operation rounded once:  r = (predicted[n] - observed[n]) / scale[n];  pos = (r + H) / (2 H) * n_bins with
+        H = half_width;  data_hist[clamp(floor(pos), 0, n_bins - 1), n] += weight -- a non-finite pos goes to no cell, an inactive
+        channel gets nothing.  The misfit (chi^2):  v = ln(misfit / N_active) * 0.43429448190325182765, binned the same way on
+        +-misfit_half_width decades into misfit_hist.  The device sampler evaluates the same expressions in the same order."""
+        nb = self.data_n_bins
+        if nb == 0:
+            return
+        n64 = np.float64(nb)
+        with np.errstate(all="ignore"):
+            if predicted is not None:
+                H = self.data_half_width
+                r = (np.asarray(predicted, dtype=np.float64).reshape(-1) - self.observed) / self.data_scale
+                pos = (r + H) / (np.float64(2.0) * H) * n64
+                ok = self.data_active & np.isfinite(pos)
+                cell = np.clip(np.floor(np.where(ok, pos, 0.0)), 0.0, n64 - 1.0).astype(np.int64)
+                ch = np.nonzero(ok)[0]
+                self.data_hist[cell[ch], ch] += weight
+            if misfit is not None:
+                H = self.misfit_half_width
+                v = np.log(np.float64(misfit) / self.misfit_scale) * np.float64(0.43429448190325182765)
+                pos = (v + H) / (np.float64(2.0) * H) * n64
+                if np.isfinite(pos):
+                    self.misfit_hist[int(min(max(math.floor(pos), 0), nb - 1))] += weight
+                    self.misfit_edge_distance.append(float(abs(pos - np.round(pos))))
 
     def value_bin(self, x):
         """Bin of conductivity ``x`` on the value axis, the device's expression; also the fractional position it was floored from."""
@@ -326,9 +395,11 @@ class Posteriors:
             else:
                 self.first_hist[q, int(min(max(math.floor(np.float64(top) / self.depth_bin_width), 0), self.first_hist.shape[1] - 1))] += weight
 
-    def update(self, edges, values, rel=None, add=None, z=None, geom=None):
+    def update(self, edges, values, rel=None, add=None, z=None, geom=None, predicted=None, misfit=None):
         """``edges``: interior interface depths; ``values``: layer conductivities; ``rel`` / ``add``: error levels; ``z``: height;
-        ``geom``: sampled scalars of the loop pair."""
+        ``geom``: sampled scalars of the loop pair; ``predicted`` [N] / ``misfit``: the state's prediction and chi^2 (data-space posteriors)."""
+        if self.data_n_bins and (predicted is not None or misfit is not None):
+            self.update_data(predicted, misfit)
         for n_, v_ in (geom or {}).items():
             e_ = self.geometry_edges.get(n_)
             if e_ is not None and e_[0] <= v_ <= e_[-1]:

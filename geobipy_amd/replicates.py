@@ -14,12 +14,13 @@ import torch
 LN2 = 0.6931471805599453
 
 # histogram-type chain state: summed over the used chains (the hit map goes through the kernel, the rest are small)
-SUMMED = ("k_hist", "edge_hist", "rel_hist", "add_hist", "height_hist", "unit_hist", "first_hist", "first_none")
+SUMMED = ("k_hist", "edge_hist", "rel_hist", "add_hist", "height_hist", "unit_hist", "first_hist", "first_none",
+          "data_hist", "misfit_hist")
 # per-chain state [rows, ...] a pooled view shows, taken from the representative chain: what survey.infer's run_block / payload and
 # unit_posteriors.products read (the sampler's working state -- Jacobians, Cholesky factors, proposals -- is not part of the view)
 PER_CHAIN = ("chain_id", "data", "observed", "height", "height0", "best_height", "log_mean_prior", "k", "edges", "sigma", "rel", "add", "prior",
              "like", "misfit", "n_accepted", "burned_in_iteration", "status", "best_posterior", "best_k", "best_edges", "best_sigma", "best_rel",
-             "best_add", "best_iteration", "iteration0", "trace_misfit", "trace_accept", "unit_z")
+             "best_add", "best_iteration", "iteration0", "trace_misfit", "trace_accept", "unit_z", "data_scale", "misfit_scale")
 # chain state every row shares (not per chain: DeviceChains.infer's re-packing leaves them alone too)
 SHARED = ("add_scale", "rel_group", "add_group")
 
@@ -90,8 +91,8 @@ def pool_reference(maps, C, use=None, half_width=1.0):
 
 class Pooled:
     """A finished block of S * C chains (row s * C + c: replicate c of sounding s) seen as S soundings: the names ``survey.infer`` and
-    ``unit_posteriors.products`` read of a sampler -- ``t`` (the chain state by the names of gbp_rj_chains), ``hitmap``, ``unit_hist``,
-    ``first_hist``, ``first_none``, ``observed``, ``B`` -- and the sampler's own attributes for the rest.  ``t`` holds the names of
+    ``unit_posteriors.products`` / ``data_posteriors.products`` read of a sampler -- ``t`` (the chain state by the names of gbp_rj_chains),
+    ``hitmap``, ``unit_hist``, ``first_hist``, ``first_none``, ``data_hist``, ``misfit_hist``, ``observed``, ``B`` -- and the sampler's own attributes for the rest.  ``t`` holds the names of
     ``PER_CHAIN``, ``SUMMED`` and ``SHARED`` (None where the sampler has none), not the sampler's working state.
 
     ``use`` [S, C]: the chain burned in -- under the reference's schedule its status is not "failed" (2); without the schedule every

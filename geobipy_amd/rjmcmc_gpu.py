@@ -87,7 +87,7 @@ class DeviceChains:
                  first_chain=0, forward_waves=2, reference_schedule=False, burn_in_min_iterations=5000, hankel_eps_ppm=None,
                  min_altitude=None, add_scale=None, rel_group=None, add_group=None, chain_id=None, extra_log_prior=0.0,
                  additive_independent=False, trace_every=0, trace_length=None, ignore_likelihood=False, units=None,
-                 unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), surface=None, **options):
+                 unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), surface=None, data_posteriors=None, **options):
         """``ignore_likelihood``: sample the PRIOR alone (the reference's option of that name, Inference1D.py:394, 519, 551, 596: no data
         term in the stochastic-Newton step, likelihood constant).  The reference's own run of it ends at the first birth or death, where
         Model.proposal_probabilities calls ``observation.sensitivity`` on None (model/Model.py:619); here the observation is left out
@@ -109,11 +109,31 @@ class DeviceChains:
         value axis: ``unit_hist`` int32 [B, Q, n_value_bins, M], ``unit_kinds`` in file order arithmetic, harmonic.  ``first_above`` /
         ``first_below``: up to 4 conductivities (S/m) in all -- ``first_hist`` int32 [B, T, n_depth_bins] is the posterior of the depth
         to the top of the shallowest layer at or above / at or below each (thresholds in the order above, then below), ``first_none``
-        [B, T] counts the samples without such a layer."""
-        from .inference import OPTION_DEFAULTS
+        [B, T] counts the samples without such a layer.
+
+        Data-space posteriors (need ``hitmap=True``; ``data_posteriors.products`` turns them into statistics).  ``data_posteriors``:
+        True or dict(n_bins=64, half_width=8.0, misfit_half_width=2.0, scale=None) -- every replaced state adds its dwell time to the
+        histogram of every active channel's residual (predicted - observed) / scale on +-half_width, ``data_hist`` int32
+        [B, n_bins, N], and to the histogram of log10(chi^2 / active channels) on +-misfit_half_width decades, ``misfit_hist`` int32
+        [B, n_bins]; the end cells hold what lies beyond.  ``scale`` [B, N] (or [N]): the unit of the residual axis, default each
+        channel's standard deviation at the chain's INITIAL error levels (``channel_std``: what the starting misfit is computed with)."""
+        from .inference import OPTION_DEFAULTS, data_posteriors_argument
         o = dict(OPTION_DEFAULTS)
         o.update({k: v for k, v in options.items() if v is not None})
         self.o = o
+        # data-space posteriors: refused here, before anything touches the device
+        dp = data_posteriors_argument(data_posteriors)
+        self._data_scale_given = None
+        if dp is not None:
+            if not hitmap:
+                raise ValueError("data_posteriors need hitmap=True: they are settled with the hit map's dwell times")
+            if ignore_likelihood or o.get("ignore_likelihood", False):
+                raise ValueError("data_posteriors with ignore_likelihood: chains that sample the prior alone have no active channel")
+            if dp["scale"] is not None:
+                sc_, shape = np.asarray(dp["scale"], dtype=np.float64), tuple(np.shape(data))
+                if len(shape) != 2 or sc_.shape not in (shape[1:], shape):
+                    raise ValueError("data_posteriors: scale must be [N] or [B, N]")
+                self._data_scale_given = np.array(np.broadcast_to(sc_, shape))
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.system = system
         f64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64).to(self.device).contiguous()
@@ -226,6 +246,11 @@ class DeviceChains:
         if (ro.n_units or ro.n_first) and not hitmap:
             raise ValueError("units / first_above / first_below need hitmap=True: the unit posteriors are settled with the hit map's dwell times")
         M_, Q_, T_ = int(ro.n_units), len(self.unit_kinds), int(ro.n_first)
+        # data-space posteriors (gbp_rj_options.n_data_bins ...; the host rule: inference.Posteriors(data=...))
+        if dp is not None:
+            ro.n_data_bins, ro.data_half_width, ro.misfit_half_width = dp["n_bins"], dp["half_width"], dp["misfit_half_width"]
+        D_ = int(ro.n_data_bins)
+        self.n_data_bins, self.data_half_width, self.misfit_half_width = D_, float(ro.data_half_width), float(ro.misfit_half_width)
         self._o = ro
         B, N, dev = self.B, self.N, self.device
         z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
@@ -253,7 +278,10 @@ class DeviceChains:
             trace_accept=z(B, self.trace_length, dt=torch.uint8) if self.trace_every > 0 else None,
             best_iteration=z(B, dt=i32),
             unit_z=f64(self.unit_bounds) if M_ else None, unit_hist=z(B, Q_, self.n_value_bins, M_, dt=i32) if M_ else None,
-            first_hist=z(B, T_, self.n_depth_bins, dt=i32) if T_ else None, first_none=z(B, T_, dt=i32) if T_ else None)
+            first_hist=z(B, T_, self.n_depth_bins, dt=i32) if T_ else None, first_none=z(B, T_, dt=i32) if T_ else None,
+            data_scale=(torch.ones(B, N, dtype=torch.float64, device=dev) if self._data_scale_given is None else f64(self._data_scale_given)) if D_ else None,
+            data_hist=z(B, D_, N, dt=i32) if D_ else None, misfit_scale=torch.ones(B, dtype=torch.float64, device=dev) if D_ else None,
+            misfit_hist=z(B, D_, dt=i32) if D_ else None)
         self._bind()
         self.iteration = 0
         self.forward_waves = int(forward_waves)      # also passed explicitly to the forward calls of the initialisation
@@ -295,7 +323,7 @@ class DeviceChains:
     def __getattr__(self, name):              # chain state by the names of gbp_rj_chains
         t = self.__dict__.get("t")
         if t is not None and name in t:
-            if name in ("hitmap", "unit_hist", "first_hist", "first_none") and t[name] is not None:
+            if name in ("hitmap", "unit_hist", "first_hist", "first_none", "data_hist", "misfit_hist") and t[name] is not None:
                 # a model enters the hit map with its dwell time when it is replaced; settle the current models first
                 with torch.cuda.device(self.device):
                     _lib.check(_lib.load().gbp_rj_flush_posteriors(self._o, self._c, self._stream()))
@@ -368,6 +396,12 @@ class DeviceChains:
         t.update(init_sigma=t["sigma"][:, 0].clone(), init_pred=t["pred"].clone(), init_J0=t["J"][:, :, 0].clone(),
                  init_prior=t["prior"].clone(), init_like=t["like"].clone(), init_misfit=t["misfit"].clone(),
                  acc_mark=zi(torch.int64), n_zero=zi(torch.int32), n_resets=zi(torch.int32), limited=zi(torch.int32))
+        if t.get("data_hist") is not None:
+            # data-space posteriors: the residual axis in units of the channels' standard deviations at the INITIAL error levels (the
+            # expression of the starting misfit above), the misfit axis about the number of active channels
+            if self._data_scale_given is None:
+                t["data_scale"].copy_(self.channel_std(t["data"], t["rel"], t["add"]))
+            t["misfit_scale"].copy_((t["data"] > 0.0).sum(dim=1).to(torch.float64))
 
     # the two evaluations the initialisation needs, through the same entries the sampler uses (overridden for time-domain data)
     def _eval_loglike(self, k, sigma, thk, height, data, rel, add, pred, chi2, logl):
@@ -485,7 +519,7 @@ class DeviceChains:
         for name in ("prior", "like", "misfit"):
             t[name][r] = t["init_" + name][r]
         for name in ("n_accepted", "acc_mark", "n_zero", "k_hist", "edge_hist", "rel_hist", "add_hist", "hitmap", "hit_dwell", "height_hist", "unit_hist",
-                     "first_hist", "first_none"):
+                     "first_hist", "first_none", "data_hist", "misfit_hist"):
             if t.get(name) is not None:
                 t[name][r] = 0
         if self.solve_height:

@@ -481,7 +481,7 @@ BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device bloc
 def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min_iterations=5000, check_every=1000,
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
-          first_above=(), first_below=(), replicates=1, **overrides):
+          first_above=(), first_below=(), replicates=1, data_posteriors=None, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -513,6 +513,10 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     ``unit_posteriors.products`` are computed per block on the device and join the per-sounding summaries: ``unit_<kind>_*``,
     ``unit_conductance_*``, ``unit_resistance_*``, ``unit_thickness`` [S, M], ``first_depth_*``, ``first_probability`` [S, T] (statistics
     only: the histograms, 8 KB per kind and sounding, stay on the device).  Need the hit map.  The containers are not touched.
+    ``data_posteriors`` (True or dict(n_bins, half_width, misfit_half_width)): the DATA-SPACE posteriors
+    (``DeviceChains(data_posteriors=...)``) -- the statistics of ``data_posteriors.products`` join the per-sounding summaries the same
+    way: ``data_residual_*``, ``data_predicted_*``, ``data_exceedance``, ``data_outside``, ``data_total`` [S, N] and ``misfit_median``,
+    ``misfit_percentile_<p>``, ``misfit_share_below_one``, ``misfit_outside``, ``misfit_total`` [S].  Need the hit map too.
     ``replicates`` = C, 1 .. 8 (frequency-domain data): C chains per sounding that differ by their random streams alone
     (``replicates.expand``: replicate 0 walks the chain the sounding walks alone); a block then holds C rows per sounding and is seen
     through ``replicates.Pooled`` -- the containers and the posteriors of the summaries receive the sum over the chains that burned in,
@@ -617,6 +621,14 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
         if units is not None:
             from .intervals import unit_bounds
             unit_z = unit_bounds(units, ds.nPoints, surface=ds.elevation, max_depth=1.1 * float(o["maximum_depth"]))
+    if data_posteriors is not None and data_posteriors is not False:
+        from .inference import data_posteriors_argument
+        dp = data_posteriors_argument(data_posteriors)
+        if not hitmap:
+            raise ValueError("data_posteriors need the hit map (they are settled with its dwell times)")
+        if dp["scale"] is not None:
+            raise ValueError("data_posteriors: survey.infer takes no scale (each channel's standard deviation at the initial error levels)")
+        common.update(data_posteriors={k_: dp[k_] for k_ in ("n_bins", "half_width", "misfit_half_width")})
     if time_domain and hankel_eps is not None:
         common.update(hankel_eps=float(hankel_eps))
     elif not time_domain and hankel_eps is not None:
@@ -696,6 +708,10 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
             from . import unit_posteriors
             with _Phase("unit_posteriors"):
                 named += [(k_, f64(v_)) for k_, v_ in unit_posteriors.products(dc).items()]
+        if t.get("data_hist") is not None:
+            from . import data_posteriors as data_posteriors_
+            with _Phase("data_posteriors"):
+                named += [(k_, f64(v_) if v_.ndim > 1 else col(v_)) for k_, v_ in data_posteriors_.products(dc).items()]
         if C_rep > 1:
             named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return dc, named

@@ -396,6 +396,23 @@ typedef struct gbp_rj_options {
     int32_t n_first;             /* 0 .. 4 thresholds                                                                     */
     double first_threshold[4];   /* S/m, finite and positive                                                              */
     int32_t first_direction[4];  /* +1: first layer at or above the threshold, -1: at or below                            */
+    /* Data-space posteriors (chains->data_hist, misfit_hist): the prediction and the misfit of every SAMPLED model, binned where the
+     * hit map is settled and with the same dwell weight (a chain's prediction and misfit change only when a proposal is accepted).
+     * Channel n of chain b, active when obs = data[b, n] > 0 (inactive channels get no counts), every operation rounded once, in
+     * this order (no fused multiply-add):
+     *   r   = (pred[n] - obs) / data_scale[b, n]              the residual in scale units
+     *   pos = (r + H) / (2 H) * n_data_bins                   H = data_half_width
+     *   data_hist[b, clamp(floor(pos), 0, n_data_bins - 1), n] += dwell      (a non-finite pos goes to no cell)
+     * and once per chain, with H = misfit_half_width decades:
+     *   v   = ln(misfit / misfit_scale[b]) * 0.43429448190325182765          (the sampler's own ln; misfit = chi^2)
+     *   pos = (v + H) / (2 H) * n_data_bins
+     *   misfit_hist[b, clamp(floor(pos), 0, n_data_bins - 1)] += dwell
+     * The end cells hold everything beyond +-H.  The entry points refuse n_data_bins outside 8 .. 256, a half width that is not
+     * positive and finite, histograms without hitmap (they share hit_dwell and are zeroed where it is), a histogram without its
+     * scale or without the other histogram.  A block that samples the prior alone has no active channel: its data_hist stays 0. */
+    int32_t n_data_bins;         /* 0: off; otherwise 8 .. 256 cells of both axes                                        */
+    double data_half_width;      /* > 0 and finite: the residual axis spans +-data_half_width scale units                */
+    double misfit_half_width;    /* > 0 and finite: the misfit axis spans +-misfit_half_width decades about misfit_scale */
 } gbp_rj_options;
 
 typedef struct gbp_rj_chains {
@@ -465,6 +482,13 @@ typedef struct gbp_rj_chains {
                                       the layout of the interval marginals (gbp_hitmap_intervals), int32                    */
     int32_t *first_hist;           /* [B, n_first, n_depth_bins]  depth to the first layer beyond each threshold            */
     int32_t *first_none;           /* [B, n_first]  samples without such a layer                                            */
+    /* data-space posteriors (opt->n_data_bins; need hitmap: they share hit_dwell and are zeroed where it is; all NULL: off) */
+    const double *data_scale;      /* [B, N]  unit of the residual axis of every channel, > 0 and finite on active channels (the
+                                      channel's standard deviation at the chain's initial error levels, say)                */
+    int32_t *data_hist;            /* [B, n_data_bins, N]  residuals of the sampled predictions; channel fastest: the value-major
+                                      layout of the interval marginals, int32                                               */
+    const double *misfit_scale;    /* [B]  > 0: what the misfit is divided by (the chain's number of active channels)       */
+    int32_t *misfit_hist;          /* [B, n_data_bins]  log10(misfit / misfit_scale) of the sampled models                  */
 } gbp_rj_chains;
 
 /* The three host-logic stages of one iteration, exposed separately for the tests ... */
