@@ -901,7 +901,7 @@ class LineSpec:
         self.trace_every = int(trace_every or 1)       # stride of the per-iteration traces the device block kept (1: the reference's arrays)
 
 
-# per-sounding fields of a finished block, as survey.infer ships them to the writing rank: (name, columns, kind)
+# per-sounding fields of a finished block, as survey_run.SurveyRun.payload packs and the line writer reads them: (name, columns)
 def device_row_fields(N, K, n_depth, n_value, n_err=99, hitmap=True, n_rel=1, n_add=1, time_domain=False, n_primary=0, height=False,
                       angles=(), trace_length=0):
     """``n_rel`` / ``n_add``: error levels per sounding (time-domain data: one relative level per system x component, one additive

@@ -16,7 +16,7 @@ LN2 = 0.6931471805599453
 # histogram-type chain state: summed over the used chains (the hit map goes through the kernel, the rest are small)
 SUMMED = ("k_hist", "edge_hist", "rel_hist", "add_hist", "height_hist", "unit_hist", "first_hist", "first_none",
           "data_hist", "misfit_hist")
-# per-chain state [rows, ...] a pooled view shows, taken from the representative chain: what survey.infer's run_block / payload and
+# per-chain state [rows, ...] a pooled view shows, taken from the representative chain: what survey_run.SurveyRun's run_block / summaries / payload and
 # unit_posteriors.products read (the sampler's working state -- Jacobians, Cholesky factors, proposals -- is not part of the view)
 PER_CHAIN = ("chain_id", "data", "observed", "height", "height0", "best_height", "log_mean_prior", "k", "edges", "sigma", "rel", "add", "prior",
              "like", "misfit", "n_accepted", "burned_in_iteration", "status", "best_posterior", "best_k", "best_edges", "best_sigma", "best_rel",
@@ -90,7 +90,7 @@ def pool_reference(maps, C, use=None, half_width=1.0):
 
 
 class Pooled:
-    """A finished block of S * C chains (row s * C + c: replicate c of sounding s) seen as S soundings: the names ``survey.infer`` and
+    """A finished block of S * C chains (row s * C + c: replicate c of sounding s) seen as S soundings: the names ``survey_run.SurveyRun`` (run_block, summaries, payload) and
     ``unit_posteriors.products`` / ``data_posteriors.products`` read of a sampler -- ``t`` (the chain state by the names of gbp_rj_chains),
     ``hitmap``, ``unit_hist``, ``first_hist``, ``first_none``, ``data_hist``, ``misfit_hist``, ``observed``, ``B`` -- and the sampler's own attributes for the rest.  ``t`` holds the names of
     ``PER_CHAIN``, ``SUMMED`` and ``SHARED`` (None where the sampler has none), not the sampler's working state.

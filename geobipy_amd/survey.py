@@ -322,6 +322,20 @@ def _container_kind(ds):
     return "tempest" if isinstance(ds, TempestData) else ("tdem" if isinstance(ds, TdemData) else "fdem")
 
 
+def _row_fields(ds, dc, hitmap):
+    """The columns of a finished block's device rows for this data set and sampler: hdf.device_row_fields' two lists [(name, width)],
+    float64 and int32, and the keyword arguments they were asked with.  The one place that decides them: survey_run's payload packs the
+    rows in this order and _LineWriter reads them in it (``hitmap`` False: the hit maps travel apart, as runs)."""
+    from . import hdf
+    td = _container_kind(ds) != "fdem"
+    fkw = dict(hitmap=hitmap, n_rel=dc.n_rel_groups, n_add=dc.n_add_groups, time_domain=td,
+               n_primary=(ds.primary_field.shape[1] if getattr(ds, "primary_field", None) is not None else 0) if td else 0,
+               height=bool(getattr(dc, "solve_height", False)), angles=tuple((m_[0], m_[5]) for m_ in (getattr(dc, "_moves", None) or ())),
+               trace_length=int(getattr(dc, "trace_length", 0) or 0))
+    ff, fi = hdf.device_row_fields(dc.N, dc.K, dc.n_depth_bins, dc.n_value_bins, **fkw)
+    return ff, fi, fkw
+
+
 class _LineWriter:
     """Fills one results container per flight line (geobipy_amd.hdf) from chunks of device rows; a line's container is compressed and
     written out by a writer thread, and dropped, as soon as its last sounding has arrived -- what is held is the open lines."""
@@ -334,14 +348,9 @@ class _LineWriter:
         self.container = hdf.container_type(container)        # "hdf5" (<line>.h5) | "npz" (<line>.results.npz + .attrs.json)
         self.K, self.N, self.nd, self.nv = dc.K, dc.N, dc.n_depth_bins, dc.n_value_bins
         kind = self.kind = _container_kind(ds)
-        td = kind != "fdem"
-        n_primary = (ds.primary_field.shape[1] if getattr(ds, "primary_field", None) is not None else 0) if td else 0
-        height = bool(getattr(dc, "solve_height", False))
-        angles = tuple((m_[0], m_[5]) for m_ in (getattr(dc, "_moves", None) or ()))
-        self.trace_every, self.trace_length = int(getattr(dc, "trace_every", 0) or 0), int(getattr(dc, "trace_length", 0) or 0)
-        fkw = dict(hitmap=hitmap, n_rel=dc.n_rel_groups, n_add=dc.n_add_groups, time_domain=td, n_primary=n_primary, height=height, angles=angles,
-                   trace_length=self.trace_length)
-        ff, fi = hdf.device_row_fields(self.N, self.K, self.nd, self.nv, **fkw)
+        ff, fi, fkw = _row_fields(ds, dc, hitmap)
+        n_primary, height, angles = fkw["n_primary"], fkw["height"], fkw["angles"]
+        self.trace_every, self.trace_length = int(getattr(dc, "trace_every", 0) or 0), fkw["trace_length"]
         # int32 rows come with dense hit-map columns (wi_dense: rows streamed from other ranks) or without (wi: the hit maps travel as
         # their non-zero entries); hm_tail = the columns after the hit map's
         self.wf, self.wi_dense = sum(w for _, w in ff), sum(w for _, w in fi)
@@ -351,7 +360,7 @@ class _LineWriter:
         self.line_col = [n_ for n_, _ in ff].index("line_number")
         self.fid_col = [n_ for n_, _ in ff].index("fiducial")
         self.wkw = dict(hitmap=hitmap, kind=kind, n_rel=dc.n_rel_groups, n_add=dc.n_add_groups, n_primary=n_primary,
-                        loop_radius=ds.system[0].loopRadius() if td else 0.0,
+                        loop_radius=ds.system[0].loopRadius() if fkw["time_domain"] else 0.0,
                         channel_additive=o.get("initial_additive_error") if kind == "tempest" else None, height=height, angles=angles,
                         trace_length=self.trace_length)
         self.lines, self.paths = {}, []
@@ -412,7 +421,7 @@ class _LineWriter:
                 self._close(ln)
 
     def add_block(self, block):
-        """One finished block of this process: payload() -- (rows, float64 rows, int32 rows) on the host with dense hit-map columns,
+        """One finished block of this process: survey_run's payload() -- (rows, float64 rows, int32 rows) on the host with dense hit-map columns,
         taken 64 rows at a time, or (rows, float64 rows, int32 rows, (ptr, index, value)) with the hit maps as their non-zero
         entries, taken whole (the rows of a line are then one slice of each array)."""
         f_b, i_b = block[1], block[2]
@@ -475,6 +484,11 @@ def select_soundings(ds, index=None, fiducial=None, line_number=None):
 # the per-sounding summaries a run with replicate chains adds, in the order of the result rows (replicates.Pooled.diagnostics)
 REPLICATE_SUMMARIES = ("rhat", "jsd", "n_used", "chain_mean", "rhat_layers", "jsd_layers", "rhat_interfaces", "rhat_max")
 
+# the per-sounding summaries that are counts: int64 in the SurveyResult (the result rows travel as float64)
+INTEGER_SUMMARIES = ("status", "burned_in_iteration", "n_layers", "best_n_layers", "layer_count_posterior", "interface_posterior",
+                     "relative_error_posterior", "additive_error_posterior", "height_posterior", "n_used", "replicates_used") + tuple(
+    n_ + "_posterior" for n_ in ("dx", "dy", "dz", "tx_z", "tx_pitch", "tx_roll", "tx_yaw", "rx_pitch", "rx_roll", "rx_yaw"))
+
 BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device block may hold by default (infer's ``chunk``)
 
 
@@ -529,478 +543,115 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     expression.  ``hankel_eps``: accuracy-budgeted window of the Hankel filter abscissae.  Frequency domain: ppm, per
     sounding, default 1e-10 (``DeviceChains(hankel_eps_ppm=...)``; 0 = all abscissae).  Time domain: relative to the
     inductive-limit value of every nodal sum, per sounding, default 1e-12 (``TdemDeviceChains(hankel_eps=...)``; 0 = all)."""
+    import threading
     import torch
     import torch.distributed as dist
+    from . import survey_run
     from .distributed import shard
-    from .rjmcmc_gpu import DeviceChains
 
+    # check
     o = read_options(options, **overrides) if isinstance(options, str) else dict(options)
-    tempest = o["data_type"] in ("TempestData", "Tempest_datapoint")
-    time_domain = tempest or o["data_type"] in ("TdemData", "TdemDataPoint")
-    if not time_domain and o["data_type"] not in ("FdemData", "FdemDataPoint"):
-        raise NotImplementedError("the device sampler handles FdemData, TdemData and TempestData; {} is not supported".format(o["data_type"]))
-    geometry_keys = [k_ for k_ in o if (k_.startswith("solve_transmitter_") or k_.startswith("solve_receiver_")) and o[k_]]
-    if geometry_keys and not time_domain:
-        raise NotImplementedError(geometry_keys[0] + ": frequency-domain data points have no loop pair to sample")
-    # (time-domain data: the loops' attitude angles are sampled on the device, gbp_td_moves; position moves raise in TdemDeviceChains)
-    if o.get("solve_calibration"):
-        raise NotImplementedError("solve_calibration is not supported by the device sampler")
-    if o.get("ignore_likelihood") and time_domain:
-        raise NotImplementedError("ignore_likelihood (prior-only sampling) on time-domain data is not supported by the device sampler")
-    # (frequency-domain data: DeviceChains(ignore_likelihood=True) -- the prior alone, Inference1D.py:394, 519, 551, 596)
-    # solve_height: the reference's datapoint only moves its height for the keys solve_z / maximum_z_change /
-    # z_proposal_variance (pointcloud/Point.py:949-983), which its options files never set -- with the files as shipped the height
-    # stays fixed there too.  An options file that DOES carry solve_z = True gets the move (frequency-domain data; DeviceChains).
-    if time_domain and o.get("solve_z"):
-        raise NotImplementedError("solve_z on time-domain data: the reference's forward takes the TRANSMITTER's z (system/Loop_pair.py:70), "
-                                  "which the data point's z move never touches -- the key that would matter is solve_transmitter_z, and the "
-                                  "geometry of the loop pair is not sampled")
-    C_rep = int(replicates)
-    if not 1 <= C_rep <= 8:
-        raise ValueError("replicates = {}: 1 .. 8 chains per sounding".format(replicates))
-    if C_rep > 1 and time_domain:
-        raise NotImplementedError("replicates > 1 on time-domain data: the system handle holds per-row state (table set, mixing weights), "
-                                  "which the pooled view would have to re-map for the best-model evaluation")
-    if C_rep > 1 and not hitmap:
-        raise ValueError("replicates > 1 needs the hit map (the convergence maps are computed from the chains' hit maps)")
+    tempest, time_domain, C_rep = survey_run.check_request(o, hitmap, replicates)
+    # read
     if data is not None:
         ds = data
     elif time_domain:
         ds = (TempestData if tempest else TdemData).read_csv(o["data_filename"], o["system_filename"])
     else:
         ds = FdemData.read_csv(o["data_filename"], o["system_filename"])
-    n_file = ds.nPoints                             # (replicate c of the sounding in row r of the data file: chain r + c n_file)
+    n_file = ds.nPoints
     rows = select_soundings(ds, index, fiducial, line_number)
     if rows.size != ds.nPoints:
         ds = ds.subset(rows)
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     start, n = shard(ds.nPoints, rank, world)
-    sl = slice(start, start + n)
-    seed = o.get("seed", 0) if seed is None else seed
-    keys = ("ignore_likelihood", "n_markov_chains", "solve_gradient", "solve_parameter", "solve_relative_error", "solve_additive_error", "maximum_number_of_layers",
-            "minimum_depth", "maximum_depth", "minimum_thickness", "initial_relative_error", "minimum_relative_error",
-            "maximum_relative_error", "initial_additive_error", "minimum_additive_error", "maximum_additive_error",
-            "relative_error_proposal_variance", "additive_error_proposal_variance", "probability_of_birth",
-            "probability_of_death", "probability_of_perturb", "probability_of_no_change", "factor",
-            "gradient_standard_deviation", "covariance_scaling", "parameter_limits", "update_plot_every", "reset_limit",
-            "solve_z", "maximum_z_change", "z_proposal_variance")
-    if time_domain:
-        from .tdem_geometry import LOOP_PAIR_SCALARS
-        keys = keys + tuple(k_ for _, stem, _ in LOOP_PAIR_SCALARS for k_ in ("solve_" + stem, "maximum_" + stem + "_change", stem + "_proposal_variance"))
     # chains are keyed by the sounding's row in the data file, so a sounding inverted alone walks the chain it walks in the
     # full survey
     assert rows.size == 1 or np.all(np.diff(rows) == 1), "selected soundings must be contiguous rows"
-    common = dict(seed=int(seed) % (1 << 64), device=device, hitmap=hitmap, first_chain=int(rows[0]) + start, reference_schedule=True,
-                  burn_in_min_iterations=burn_in_min_iterations, **{k: o[k] for k in keys if o.get(k) is not None})
-    # per-iteration traces for the containers' `phids` / `acceptance_rate` (Inference1D.data_misfit_v / acceptance_v): kept on the
-    # device at a stride -- "auto": the smallest stride with at most 4 096 entries per sounding (32 + 4 KB per sounding beside a
-    # 440 KB hit map; the reference's full arrays are 2 n_markov_chains x 9 bytes = 1.8 MB at its default 100 000); an int: that
-    # stride (1 = the reference's arrays in full); None / 0: no traces (the two datasets stay at their fill values)
-    if results_directory is not None and traces:
-        n_mc2 = 2 * int(o["n_markov_chains"])
-        common.update(trace_every=max(1, -(-n_mc2 // 4096)) if traces == "auto" else int(traces))
-    # Default block size: 16 384 soundings, less when a sounding's posterior payload on the device is large -- full-length traces at the
-    # reference's default n_markov_chains = 100 000 are 1.8 MB per sounding (29.5 GB for 16 384, plus their host copies): the default
-    # block keeps traces + hit maps under BLOCK_PAYLOAD_BUDGET.  Chains are keyed by row, so the block size never changes a result.
-    def default_block(limit=16384):
-        per = 0
-        if common.get("trace_every"):
-            per += -(-2 * int(o["n_markov_chains"]) // int(common["trace_every"])) * 9        # misfit f64 + acceptance u8 per kept entry
-        if hitmap and results_directory is not None:
-            per += 440 * 1024                                                                 # (the hit map's usual size; exact: DeviceChains)
-        if C_rep > 1:                               # a sounding is C rows of the block
-            limit, per = max(1, limit // C_rep), per * C_rep
-        return limit if per == 0 else int(max(256 // C_rep, min(limit, BLOCK_PAYLOAD_BUDGET // per)))
-    # sampled unit posteriors: exact bounds of every sounding's units, metres below its surface, cut at the end of the depth axis
-    unit_z = None
-    if units is not None or len(first_above) or len(first_below):
-        if not hitmap:
-            raise ValueError("units / first_above / first_below need the hit map (they are settled with its dwell times)")
-        common.update(first_above=tuple(float(v) for v in first_above), first_below=tuple(float(v) for v in first_below), unit_kinds=unit_kinds)
-        if units is not None:
-            from .intervals import unit_bounds
-            unit_z = unit_bounds(units, ds.nPoints, surface=ds.elevation, max_depth=1.1 * float(o["maximum_depth"]))
-    if data_posteriors is not None and data_posteriors is not False:
-        from .inference import data_posteriors_argument
-        dp = data_posteriors_argument(data_posteriors)
-        if not hitmap:
-            raise ValueError("data_posteriors need the hit map (they are settled with its dwell times)")
-        if dp["scale"] is not None:
-            raise ValueError("data_posteriors: survey.infer takes no scale (each channel's standard deviation at the initial error levels)")
-        common.update(data_posteriors={k_: dp[k_] for k_ in ("n_bins", "half_width", "misfit_half_width")})
-    if time_domain and hankel_eps is not None:
-        common.update(hankel_eps=float(hankel_eps))
-    elif not time_domain and hankel_eps is not None:
-        common.update(hankel_eps_ppm=float(hankel_eps))
-    f64 = lambda x: x.to(torch.float64)
-    col = lambda x: f64(x)[:, None]
-    # wall time by phase (device-synchronised at the phase borders only when a caller asks for it with timings={}: bench.py's
-    # ``survey`` object; a normal run never synchronises for this)
-    import time as _time
-
-    class _Phase:
-        def __init__(self, name):
-            self.name = name
-        def __enter__(self):
-            if timings is not None:
-                if torch.cuda.is_available():
-                    torch.cuda.synchronize()
-                self.t0 = _time.perf_counter()
-        def __exit__(self, *a):
-            if timings is not None:
-                if torch.cuda.is_available():
-                    torch.cuda.synchronize()
-                timings[self.name] = timings.get(self.name, 0.0) + _time.perf_counter() - self.t0
-
-    def run_block(idx, offset=None):
-        """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])])."""
-        kw = dict(common)
-        if C_rep > 1:                               # C rows per sounding, sounding-major; every chain keyed by (row of the file, replicate)
-            from .replicates import Pooled, expand
-            if idx.size:
-                rep_rows, chain_id = expand(int(rows[0]) + idx, C_rep, n_file)
-                idx = rep_rows - int(rows[0])
-                kw.pop("first_chain")
-                kw["chain_id"] = chain_id
-        elif idx.size != n or idx[0] != start:      # a selection of the shard: key every chain by its own row of the data file
-            kw.pop("first_chain")
-            kw["chain_id"] = int(rows[0]) + idx
-        if unit_z is not None:
-            kw["units"] = unit_z[idx]                # (with replicates: the expanded rows)
-        if time_domain:
-            from .tdem import TdemDeviceChains
-            if isinstance(ds, TempestData):
-                # Tempest_datapoint (data/datapoint/Tempest_datapoint.py:106-123, 161-176): the channels hold primary + secondary
-                # field, the options file's additive errors are per channel and the sampled level is their multiplier per component
-                nc = ds.system[0].n_components
-                kw.update(channel_additive=np.asarray(o["initial_additive_error"], dtype=np.float64), initial_additive_error=[1.0] * nc,
-                          primary_field=ds.primary_field[idx] if ds.primary_field is not None else None)
-            dc = TdemDeviceChains(ds.system, ds.z[idx], ds.total_field(idx) if isinstance(ds, TempestData) else ds.data[idx], offset,
-                                  attitude=ds.attitude[idx] if idx.size else None, **kw)
-        else:
-            with _Phase("upload_and_initialise"):
-                dc = DeviceChains(ds.system, ds.z[idx], ds.data[idx], exact_jacobian=exact_jacobian, **kw)
-        with _Phase("chains"):
-            dc.infer(check_every=check_every)
-        if C_rep > 1:
-            with _Phase("pool_replicates"):
-                dc = Pooled(dc, C_rep)
-                diag = dc.diagnostics()
-        t = dc.t
-        named = [("status", col(t["status"])), ("burned_in_iteration", col(t["burned_in_iteration"])), ("n_accepted", col(t["n_accepted"])),
-                 ("misfit", col(t["misfit"])), ("relative_error", t["rel"]), ("additive_error", t["add"]), ("n_layers", col(t["k"])),
-                 ("best_n_layers", col(t["best_k"])), ("best_posterior", col(t["best_posterior"])), ("best_edges", t["best_edges"]),
-                 ("best_conductivity", t["best_sigma"]), ("layer_count_posterior", f64(t["k_hist"])),
-                 ("interface_posterior", f64(t["edge_hist"])), ("relative_error_posterior", f64(t["rel_hist"]).flatten(1)),
-                 ("additive_error_posterior", f64(t["add_hist"]).flatten(1))]
-        if getattr(dc, "_moves", None):            # sampled attitude angles (the loops' own convention): final, highest-posterior, posterior
-            cur, best = dc.sampled_angles("geom"), dc.sampled_angles("best_geom")
-            for q, m_ in enumerate(dc._moves):
-                named += [(m_[0], col(cur[m_[0]])), ("best_" + m_[0], col(best[m_[0]])), (m_[0] + "_posterior", f64(t["geom_hist"][:, q, :m_[5]]))]
-        if getattr(dc, "solve_height", False):     # the sampled height: final and highest-posterior values, posterior on the prior's 99 cells
-            named += [("height", col(t["height"])), ("best_height", col(t["best_height"])), ("height_posterior", f64(t["height_hist"]))]
-        if hitmap:
-            with _Phase("hitmap_statistics"):
-                mean, pct = _hitmap_statistics(dc.hitmap, t["log_mean_prior"], dc.value_half_width)     # (attribute access settles dwell times)
-            named += [("mean_log10_conductivity", mean)] + [("log10_conductivity_" + q, p) for q, p in zip(("p05", "p50", "p95"), pct)]
-        if t.get("unit_hist") is not None or t.get("first_hist") is not None:
-            from . import unit_posteriors
-            with _Phase("unit_posteriors"):
-                named += [(k_, f64(v_)) for k_, v_ in unit_posteriors.products(dc).items()]
-        if t.get("data_hist") is not None:
-            from . import data_posteriors as data_posteriors_
-            with _Phase("data_posteriors"):
-                named += [(k_, f64(v_) if v_.ndim > 1 else col(v_)) for k_, v_ in data_posteriors_.products(dc).items()]
-        if C_rep > 1:
-            named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
-        return dc, named
-
-    state = dict(iterations=0, dc=None, named=None)
-    shipped = []                                   # per block: (rows, float64 block, int32 block) of hdf.device_row_fields, on the HOST
-
-    def payload(dc, idx, sparse=False):
-        """The rows of hdf.device_row_fields for a finished block, moved to host memory at once (the hit maps are 440 KB per
-        sounding: what stays on the GPU is the running block, not every block a rank has finished).  ``sparse``: the hit maps leave
-        the device in run-length form (per row: the flat positions value_bin * n_depth + depth cell at which the count changes, and
-        the counts; hdf._Dataset.write_run_rows) instead of dense int32 columns -- depth is the fast axis and a layer fills a run of
-        cells with one count: a few thousand runs against 110 000 cells -- for a process that fills its own containers."""
-        from .rjmcmc_gpu import layer_widths
-        t, dev = dc.t, dc.device
-        n_mc = int(o["n_markov_chains"])
-        none = t["best_k"] < 1                      # (a chain that never recorded a best model: its current one)
-        bk = torch.where(none, t["k"], t["best_k"])
-        be = torch.where(none[:, None], t["edges"], t["best_edges"])
-        bs = torch.where(none[:, None], t["sigma"], t["best_sigma"])
-        # the error levels of the highest-posterior state, like Inference1D.writeHdf's best data point (:1076-1088)
-        brel = torch.where(none[:, None], t["rel"], t["best_rel"]).contiguous()
-        badd = torch.where(none[:, None], t["add"], t["best_add"]).contiguous()
-        observed = dc.observed                     # (the measured data: t["data"] unless the chains sampled the prior alone)
-        pred = torch.empty_like(observed)
-        chi2, logl = torch.empty_like(t["misfit"]), torch.empty_like(t["misfit"])
-        # sampled attitude angles: the best data point's OWN geometry -- the prediction and the predicted primary field of the
-        # highest-posterior angles, not of the chain's last state / the measured geometry (Inference1D.writeHdf :1076-1088 writes
-        # the best data point: predicted_secondary_field = predictedData - predicted_primary_field there)
-        best_mix = {}
-        best_primary = None
-        eval_height = t["best_height"] if t.get("best_height") is not None else t["height"]
-        if getattr(dc, "_moves", None):
-            bw, boff, best_primary = dc.mix_for_geometry(torch.where(none[:, None], t["geom"], t["best_geom"]))
-            best_mix = dict(weights=bw, offset=boff)
-            extra = dc.geometry_rows_extra()       # sampled positions: the best state's distance scale and effective height
-            if extra is not None:
-                best_mix["scale"], eval_height = extra["scale"], extra["height"]
-        with torch.cuda.device(dev):                # one batched forward at the best models, through the sampler's own entry
-            dc._eval_loglike(bk.contiguous(), bs.contiguous(), layer_widths(be, bk.to(torch.int64)).contiguous(),
-                             eval_height, observed, brel, badd, pred, chi2, logl, **best_mix)
-        host = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)[idx], device=dev).reshape(idx.size, -1)
-        cols_f = [host(ds.x), host(ds.y), host(ds.z), host(ds.elevation), host(ds.lineNumber), host(ds.fiducial), observed, pred,
-                  brel, badd, t["log_mean_prior"][:, None], be, bs]
-        if time_domain:
-            n_pf = ds.primary_field.shape[1] if ds.primary_field is not None else 0
-            cols_f += [dc.channel_std(observed, brel, badd), host(ds.offsets), host(ds.loop_angles)]
-            if n_pf:
-                cols_f += [host(ds.primary_field),
-                           torch.as_tensor(dc.predicted_primary() if best_primary is None else best_primary, device=dev).reshape(idx.size, -1)]
-        if getattr(dc, "solve_height", False):
-            cols_f += [t["best_height"][:, None], t["height0"][:, None]]
-        if getattr(dc, "_moves", None):
-            bst, ctr = dc.sampled_angles("best_geom"), dc.sampled_angles("geom0")
-            for m_ in dc._moves:
-                cols_f += [bst[m_[0]][:, None], ctr[m_[0]][:, None]]
-        if getattr(dc, "trace_every", 0):
-            cols_f.append(t["trace_misfit"])
-        f64_block = torch.cat(cols_f, dim=1).contiguous()
-        st, bi = t["status"].to(torch.int32), t["burned_in_iteration"].to(torch.int32)
-        ran = torch.where(st == 1, bi + n_mc + 1, torch.where(st == 2, torch.full_like(bi, n_mc), torch.full_like(bi, dc.iteration)))
-        cols = [st[:, None], bi[:, None], ran[:, None], bk.to(torch.int32)[:, None], t["best_iteration"][:, None], t["k_hist"], t["edge_hist"], t["rel_hist"].flatten(1),
-                t["add_hist"].flatten(1)]
-        csr = None
-        if hitmap and sparse:
-            from .hitmap import runs                # run starts: a row's first cell and every change of value (csrc/gbp_hitmap.h)
-            ptr, start_, val_ = runs(dc.hitmap)     # (attribute access settles the dwell times)
-            csr = (ptr.cpu().numpy(), start_.cpu().numpy(), val_.cpu().numpy())
-            del start_, val_
-        elif hitmap:
-            cols.append(dc.hitmap.flatten(1))       # (attribute access settles the dwell times)
-        if getattr(dc, "solve_height", False):
-            cols.append(t["height_hist"])
-        for q_, m_ in enumerate(getattr(dc, "_moves", None) or ()):
-            cols.append(t["geom_hist"][:, q_, :m_[5]])
-        if getattr(dc, "trace_every", 0):
-            cols.append(t["trace_accept"])
-        to_host = lambda x: x.cpu()
-        out = (torch.as_tensor(np.asarray(idx), dtype=torch.int64), to_host(f64_block),
-               to_host(torch.cat([c_.to(torch.int32) for c_ in cols], dim=1).contiguous()))
-        return out + (csr,) if sparse else out
-
-    def fill_containers(background=False):
-        """The finished block's rows -> host -> line containers.  ``background``: on a host thread with a device stream of its own, while
-        the caller's thread runs the NEXT block's chains (the block's sampler stays alive until its rows have left the device; one block is
-        in flight at a time, so the containers receive the blocks in order) -- 65 536 soundings: the rows of three of the four blocks no
-        longer stand between two blocks' chains.  The phase clocks of a background fill are host wall time, overlapped with "chains"."""
-        join_fill()
-        if state.get("unfilled") is None:
-            return
-        dc_, idx_ = state.pop("unfilled")
-        if state.get("writer") is None:
-            state["writer"] = _LineWriter(results_directory, ds, o, dc_, hitmap, container)
-        if idx_.size == 0:                          # (a rank that got no flight line: nothing to hand over)
-            return
-        if not background or dc_.device.type != "cuda":
-            with _Phase("rows_to_host"):
-                pl = payload(dc_, idx_, sparse=True)
-            with _Phase("container_fill"):
-                state["writer"].add_block(pl)
-            return
-        import threading
-        side = state.get("fill_stream")
-        if side is None:
-            side = state["fill_stream"] = torch.cuda.Stream(device=dc_.device)
-        side.wait_stream(torch.cuda.current_stream(dc_.device))      # (the block's chains have ended: infer() read their status flags)
-        failed = state.setdefault("fill_failed", [])
-
-        def work():
-            try:
-                t0_ = _time.perf_counter()
-                with torch.cuda.device(dc_.device), torch.cuda.stream(side):
-                    pl = payload(dc_, idx_, sparse=True)
-                t1_ = _time.perf_counter()
-                state["writer"].add_block(pl)
-                if timings is not None:
-                    timings["rows_to_host_overlapped"] = timings.get("rows_to_host_overlapped", 0.0) + t1_ - t0_
-                    timings["container_fill_overlapped"] = timings.get("container_fill_overlapped", 0.0) + _time.perf_counter() - t1_
-            except BaseException as e:               # (handed to the caller's thread by join_fill)
-                failed.append(e)
-        th = state["fill_thread"] = threading.Thread(target=work)
-        th.start()
-
-    def join_fill():
-        th = state.pop("fill_thread", None)
-        if th is not None:
-            th.join()
-        if state.get("fill_failed"):
-            raise state["fill_failed"].pop(0)
-
-    def process(first, count):
-        """Result rows [count, width] of the soundings first .. first + count - 1 (count >= 0)."""
-        span = np.arange(first, first + count)
-        if time_domain:
-            # the Hankel tables depend on the horizontal transmitter-receiver distance and dz: the block's handle holds one table
-            # set per distinct pair and every chain runs with its own; azimuth and attitude are per-chain mixing weights
-            # (TdemDeviceChains(offset=[n, 3], attitude=[n, 6])) -- one block whatever the geometry
-            n_off = np.unique(np.c_[np.hypot(ds.offsets[span, 0], ds.offsets[span, 1]), ds.offsets[span, 2]], axis=0).shape[0] if count > 0 else 1
-            if n_off > TdemData.MAX_OFFSET_SETS:
-                raise NotImplementedError("{} distinct (horizontal distance, dz) receiver offsets in {} soundings: the device sampler holds one "
-                                          "set of Hankel tables (~0.15 MB x (1 + altitude bins)) per pair -- bin the offsets (e.g. to 0.1 m) first".format(n_off, count))
-            blocks = [(ds.offsets[span] if count > 0 else (0.0, 0.0, 0.0), span)]
-        else:
-            blocks = [(None, span)]
-        out = None
-        for off, idx in blocks:
-            fill_containers(background=True)        # (the block before this one, if any: its rows leave while this block's chains run)
-            dc, named = run_block(idx, off)
-            if results_directory is not None and (world == 1 or schedule == "lines"):
-                # one process: the block's rows go to the line containers and are dropped (host memory holds the open lines, not the
-                # survey's hit maps) -- at the start of the next block, or, for the last one, once the summary file's thread is running
-                state["unfilled"] = (dc, idx)
-            elif results_directory is not None and idx.size:      # (a rank that drew no chunk ships nothing)
-                shipped.append(payload(dc, idx))
-            part = torch.cat([v for _, v in named], dim=1).contiguous()
-            state.update(iterations=max(state["iterations"], dc.iteration), dc=dc, named=named)
-            if len(blocks) == 1:
-                return part
-            if out is None:
-                out = torch.empty((count, part.shape[1]), dtype=torch.float64, device=part.device)
-            out[torch.as_tensor(idx - first, device=part.device)] = part
-        return out
-
+    containers = results_directory is not None
+    common = survey_run.sampler_arguments(o, time_domain, seed=seed, device=device, hitmap=hitmap, first_chain=int(rows[0]) + start,
+                                          burn_in_min_iterations=burn_in_min_iterations, containers=containers, traces=traces,
+                                          units=units is not None, unit_kinds=unit_kinds, first_above=first_above, first_below=first_below,
+                                          data_posteriors=data_posteriors, hankel_eps=hankel_eps)
+    unit_z = None                                   # sampled unit posteriors: exact bounds of every sounding's units, metres below its
+    if units is not None:                           # surface, cut at the end of the depth axis
+        from .intervals import unit_bounds
+        unit_z = unit_bounds(units, ds.nPoints, surface=ds.elevation, max_depth=1.1 * float(o["maximum_depth"]))
+    # plan
     assert schedule in ("auto", "static", "dynamic", "lines"), ValueError("schedule must be 'auto', 'static', 'dynamic' or 'lines'")
     if schedule == "auto":
-        # more than one rank: whole lines per rank -- every rank writes its own containers and the job's only exchange is the gather of the
-        # one-row summaries (all_gather_into_tensor; the posterior rows of "static" / "dynamic" travel point to point, which has run over
-        # gloo only) -- whenever the data file allows it (every flight line one run of consecutive rows)
-        change_ = np.flatnonzero(np.diff(ds.lineNumber) != 0) + 1
-        firsts_ = np.r_[0, change_] if ds.nPoints else np.zeros(0, dtype=np.int64)
-        lines_ok = bool(world > 1 and results_directory is not None and ds.nPoints and np.unique(ds.lineNumber[firsts_]).size == firsts_.size
-                        and firsts_.size >= world)
-        if lines_ok:
-            # ... and only when whole lines balance: the most loaded rank within 1.2 x the mean (a survey with fewer lines than ranks,
-            # or one dominant line, would leave GPUs idle where "static" uses all of them); without containers "lines" buys nothing
-            from .distributed import assign_lines as _assign
-            counts_ = np.diff(np.r_[firsts_, ds.nPoints])
-            loads = [int(sum(counts_[i] for i in mine_)) for mine_ in _assign(counts_, world)]
-            lines_ok = max(loads) <= 1.2 * ds.nPoints / world
-        schedule = "lines" if lines_ok else "static"
-    if schedule == "lines":
-        # whole flight lines per rank: every rank fills and writes the results files of its own lines (as the reference's ranks write
-        # their own rows, Inference3D.py:586-635), only the one-row summaries are gathered
-        from .distributed import assign_lines, gather_rows
-        change = np.flatnonzero(np.diff(ds.lineNumber) != 0) + 1
-        firsts = np.r_[0, change] if ds.nPoints else np.zeros(0, dtype=np.int64)
-        counts = np.diff(np.r_[firsts, ds.nPoints])
-        if np.unique(ds.lineNumber[firsts]).size != firsts.size:
-            raise ValueError("schedule='lines' needs every flight line in one run of consecutive rows of the data file (use 'static' or 'dynamic')")
-        n = -1                                      # (every block is a selection: chains keyed by chain_id)
-        size = int(chunk) if chunk else default_block()   # a long line goes through the device in pieces of this many soundings
-        done_rows, done_vals = [], []
-        for li in assign_lines(counts, world)[rank]:
-            for first in range(int(firsts[li]), int(firsts[li] + counts[li]), size):
-                count = min(size, int(firsts[li] + counts[li]) - first)
-                done_vals.append(process(first, count))
-                done_rows.append(torch.arange(first, first + count, dtype=torch.int64, device=done_vals[-1].device))
-        if not done_vals:                           # more ranks than lines: an empty block fixes the row width and the device
-            done_vals.append(process(0, 0))
-            done_rows.append(torch.zeros(0, dtype=torch.int64, device=done_vals[-1].device))
-        gathered = gather_rows(torch.cat(done_rows), torch.cat(done_vals), ds.nPoints)
-    elif schedule == "static":
-        # a rank's block goes through the device in pieces of `chunk` soundings (default 16 384): the posteriors of a piece (440 KB of hit
-        # map per sounding) leave the GPU, and with one process the host, before the next piece runs -- 65 536 soundings: 19.6 s and 16 GB
-        # of host memory in pieces against 24.7 s and 38 GB in one block (scripts/bench_survey.py); the chains are keyed by row either way
-        piece = int(chunk) if chunk else default_block()
-        if n > piece:
-            local = torch.cat([process(first, min(piece, start + n - first)) for first in range(start, start + n, piece)])
+        schedule = survey_run.auto_schedule(ds.lineNumber, world, containers)
+    block = lambda limit=16384: int(chunk) if chunk else survey_run.default_block(
+        o["n_markov_chains"], common.get("trace_every"), hitmap and containers, C_rep, limit)
+    # wall time by phase (device-synchronised at the phase borders only when a caller asks for it with timings={}: bench.py's
+    # ``survey`` object; a normal run never synchronises for this)
+    clock = survey_run.PhaseClock(timings)
+    run = survey_run.SurveyRun(ds=ds, o=o, common=common, rows=rows, n_file=n_file, rank=rank, C_rep=C_rep,
+                               time_domain=time_domain, hitmap=hitmap, exact_jacobian=exact_jacobian, check_every=check_every,
+                               results_directory=results_directory, container=container,
+                               own_containers=containers and (world == 1 or schedule == "lines"), unit_z=unit_z, clock=clock)
+    filler = survey_run.ContainerFiller(lambda dc, idx: run.payload(dc, idx, sparse=True),
+                                        lambda dc: _LineWriter(results_directory, ds, o, dc, hitmap, container), clock)
+    # the blocks, one after the other; a block's rows leave for the containers while the next block's chains run
+    with filler:
+        if schedule == "lines":
+            # whole flight lines per rank: every rank fills and writes the results files of its own lines (as the reference's ranks
+            # write their own rows, Inference3D.py:586-635), only the one-row summaries are gathered
+            from .distributed import assign_lines
+            firsts, counts, one_run_per_line = survey_run.line_runs(ds.lineNumber)
+            if not one_run_per_line:
+                raise ValueError("schedule='lines' needs every flight line in one run of consecutive rows of the data file (use 'static' or 'dynamic')")
+            size = block()                          # a long line goes through the device in pieces of this many soundings
+            ends = firsts + counts
+            gathered = run.gather_pieces(((first, min(size, int(ends[li]) - first)) for li in assign_lines(counts, world)[rank]
+                                          for first in range(int(firsts[li]), int(ends[li]), size)), filler)
+        elif schedule == "static":
+            # a rank's block goes through the device in pieces of `chunk` soundings (default 16 384): the posteriors of a piece (440 KB of
+            # hit map per sounding) leave the GPU, and with one process the host, before the next piece runs -- 65 536 soundings: 19.6 s
+            # and 16 GB of host memory in pieces against 24.7 s and 38 GB in one block (scripts/bench_survey.py); the chains are keyed by
+            # row either way (a piece by every chain's own row, the whole shard by its first)
+            piece = block()
+            if n > piece:
+                local = torch.cat([run.process(first, min(piece, start + n - first), filler) for first in range(start, start + n, piece)])
+            else:
+                local = run.process(start, n, filler, key_by_row=False)
+            if world > 1:                           # the one exchange of the job: per-sounding result rows to rank 0
+                from .distributed import SummaryGather
+                g = SummaryGather(ds.nPoints, local.shape[1], local.device)
+                gathered = g.finish(g.launch(*[local[:, i] for i in range(local.shape[1])]))
+            else:
+                gathered = local
         else:
-            local = process(start, n)
-        if world > 1:                               # the one exchange of the job: per-sounding result rows to rank 0
-            from .distributed import SummaryGather
-            g = SummaryGather(ds.nPoints, local.shape[1], local.device)
-            gathered = g.finish(g.launch(*[local[:, i] for i in range(local.shape[1])]))
-        else:
-            gathered = local
-    else:
-        from .distributed import ChunkQueue, gather_rows
-        n = -1                                      # (every block is a selection: chains keyed by chain_id)
-        size = int(chunk) if chunk else default_block(max(256, -(-ds.nPoints // (16 * world))))
-        done_rows, done_vals = [], []
-        for first, count in ChunkQueue(ds.nPoints, size):
-            done_vals.append(process(first, count))
-            done_rows.append(torch.arange(first, first + count, dtype=torch.int64, device=done_vals[-1].device))
-        if not done_vals:                           # this rank got no chunk: an empty block fixes the row width and the device
-            done_vals.append(process(0, 0))
-            done_rows.append(torch.zeros(0, dtype=torch.int64, device=done_vals[-1].device))
-        gathered = gather_rows(torch.cat(done_rows), torch.cat(done_vals), ds.nPoints)
-    iterations_run, dc, named = state["iterations"], state["dc"], state["named"]
+            from .distributed import ChunkQueue
+            gathered = run.gather_pieces(ChunkQueue(ds.nPoints, block(max(256, -(-ds.nPoints // (16 * world))))), filler)
+    iterations_run = run.iterations
     if world > 1:                                   # an unfinished chain's count is the longest run of any rank
-        it = torch.tensor([iterations_run], dtype=torch.int64, device=dc.device)
+        it = torch.tensor([iterations_run], dtype=torch.int64, device=run.dc.device)
         dist.all_reduce(it, op=dist.ReduceOp.MAX)
         iterations_run = int(it)
-    def finish_containers():
-        if results_directory is not None and (world == 1 or schedule == "lines"):
-            fill_containers()
-            if state.get("writer") is None:         # (no sounding at all: the empty set of containers)
-                state["writer"] = _LineWriter(results_directory, ds, o, dc, hitmap, container)
-            with _Phase("compress_and_write_tail"):
-                state["writer"].finish()
-        elif results_directory is not None:
-            _write_line_containers(results_directory, ds, o, dc, shipped, hitmap, rank, container)
     if rank != 0:
-        finish_containers()
+        run.write_containers(filler)
         return None
-    with _Phase("summaries_to_host"):
+    with clock.phase("summaries_to_host"):
         r = gathered.cpu().numpy()
     # the result is put together and the summary file compressed on a thread of its own while this one fills the line containers and
     # their writer threads finish (numpy's conversions and zlib release the interpreter lock)
-    import threading
     failed, made = [], []
 
     def assemble_and_save():
         try:
-            res = SurveyResult(line=ds.lineNumber, fiducial=ds.fiducial, x=ds.x, y=ds.y, z=ds.z, elevation=ds.elevation,
-                               depth_bin_width=np.float64(dc.depth_bin_width))
-            c0 = 0
-            ints = ("status", "burned_in_iteration", "n_layers", "best_n_layers", "layer_count_posterior", "interface_posterior",
-                    "relative_error_posterior", "additive_error_posterior", "height_posterior", "n_used", "replicates_used") + tuple(
-                n_ + "_posterior" for n_ in ("dx", "dy", "dz", "tx_z", "tx_pitch", "tx_roll", "tx_yaw", "rx_pitch", "rx_roll", "rx_yaw"))
-            for name, v in named:
-                w = v.shape[1]
-                block = r[:, c0:c0 + w]
-                c0 += w
-                if name in ints:
-                    block = block.astype(np.int64)
-                res[name] = block[:, 0] if w == 1 else block
-            for name, G in (("relative_error_posterior", dc.n_rel_groups), ("additive_error_posterior", dc.n_add_groups)):
-                if G > 1:                                   # [S, groups, cells]; ne cells, uniform in log10 between the prior bounds
-                    res[name] = res[name].reshape(-1, G, dc.n_error_bins)
-            if C_rep > 1:
-                res["chain_mean"] = res["chain_mean"].reshape(-1, C_rep, dc.n_depth_bins)
-            n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze (infer :641-688)
-            ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
-            res["iterations"] = ran.astype(np.int64)
-            res["acceptance"] = res.pop("n_accepted") / np.maximum(1, ran)
-            for k_ in ("status", "burned_in_iteration", "n_layers", "best_n_layers"):
-                res[k_] = res[k_].astype(np.int32)
-            made.append(res)
+            made.append(survey_run.assemble_result(ds, o, run.dc, run.named, r, C_rep, iterations_run))
             if output is not None:
-                res.save(output)
+                made[0].save(output)
         except BaseException as e:                       # (handed to the caller's thread below)
             failed.append(e)
     saver = threading.Thread(target=assemble_and_save)
     saver.start()
     try:
-        finish_containers()
+        run.write_containers(filler)
     finally:
-        with _Phase("summary_file_tail"):
+        with clock.phase("summary_file_tail"):
             saver.join()
     if failed:
         raise failed[0]

@@ -72,19 +72,35 @@ def test_select_soundings_and_cli_arguments():
 
 def test_default_block_and_schedule_follow_the_payload_and_the_lines():
     """ADVICE r5: the default device block shrinks when full-length traces of a large n_markov_chains would not fit the payload budget;
-    --schedule auto takes whole lines per rank only when containers are written and the lines balance (checked through the pieces of
-    survey.infer that decide it: the budget constant and distributed.assign_lines)."""
-    from geobipy_amd.distributed import assign_lines
+    --schedule auto takes whole lines per rank only when containers are written and the lines balance (the functions survey.infer
+    decides with: survey_run.default_block, line_runs, auto_schedule)."""
+    from geobipy_amd import survey_run
     per = -(-2 * 100000 // 1) * 9 + 440 * 1024                    # bytes per sounding: full traces at the reference's default + a hit map
-    assert 256 <= survey.BLOCK_PAYLOAD_BUDGET // per < 16384 and (survey.BLOCK_PAYLOAD_BUDGET // per) * per <= survey.BLOCK_PAYLOAD_BUDGET
-    per_small = -(-2 * 2000 // 1) * 9 + 440 * 1024
-    assert survey.BLOCK_PAYLOAD_BUDGET // per_small >= 16384      # the bench's surveys keep blocks of 16 384
-    counts = np.array([1000, 10, 10, 10])                        # one dominant line over four ranks: "lines" would idle three of them
-    loads = [int(sum(counts[i] for i in mine)) for mine in assign_lines(counts, 4)]
-    assert max(loads) > 1.2 * counts.sum() / 4
-    counts = np.full(16, 512)
-    loads = [int(sum(counts[i] for i in mine)) for mine in assign_lines(counts, 8)]
-    assert max(loads) <= 1.2 * counts.sum() / 8
+    block = survey_run.default_block(100000, 1, True, 1)
+    assert 256 <= block < 16384 and block == survey.BLOCK_PAYLOAD_BUDGET // per and block * per <= survey.BLOCK_PAYLOAD_BUDGET
+    assert survey_run.default_block(2000, 1, True, 1) == 16384    # the bench's surveys keep blocks of 16 384
+    assert survey_run.default_block(100000, None, False, 1) == 16384 and survey_run.default_block(100000, None, False, 1, limit=300) == 300
+    assert survey_run.default_block(10 ** 7, 1, True, 1) == 256   # never fewer than 256 chains
+    # replicates=4: a sounding is 4 rows of the block -- the limit and the per-sounding payload both scale by 4
+    assert survey_run.default_block(2000, 1, True, 4) == 16384 // 4 and survey_run.default_block(100000, None, False, 4) == 16384 // 4
+    assert survey_run.default_block(100000, 1, True, 4) == survey.BLOCK_PAYLOAD_BUDGET // (4 * per) < 16384 // 4
+    assert survey_run.default_block(10 ** 7, 1, True, 4) == 256 // 4
+    lines = lambda counts: np.repeat(100.0 + np.arange(len(counts)), counts)
+    firsts, counts, one_run = survey_run.line_runs(lines([1000, 10, 10, 10]))
+    assert firsts.tolist() == [0, 1000, 1010, 1020] and counts.tolist() == [1000, 10, 10, 10] and one_run
+    assert [a.tolist() for a in survey_run.line_runs(np.zeros(0))[:2]] == [[], []] and survey_run.line_runs(np.zeros(0))[2]
+    # one dominant line over four ranks: "lines" would idle three of them
+    assert survey_run.auto_schedule(lines([1000, 10, 10, 10]), 4, True) == "static"
+    even = lines([512] * 16)
+    assert survey_run.auto_schedule(even, 8, True) == "lines"
+    assert survey_run.auto_schedule(even, 8, False) == "static"   # no containers: "lines" buys nothing
+    assert survey_run.auto_schedule(even, 1, True) == "static"    # one rank
+    assert survey_run.auto_schedule(lines([512] * 4), 8, True) == "static"       # fewer lines than ranks
+    assert survey_run.auto_schedule(np.zeros(0), 2, True) == "static"
+    split = even.copy()
+    split[-256:] = even[0]                                       # the first line comes back at the end of the file: two runs
+    assert not survey_run.line_runs(split)[2] and survey_run.line_runs(split)[0].size == 17
+    assert survey_run.auto_schedule(split, 8, True) == "static"
 
 
 def test_read_time_domain_csv_and_options():
@@ -425,6 +441,37 @@ def test_ranks_that_own_whole_lines_write_their_own_files(tmp_path):
     ds.lineNumber[70:] = 10.0
     with pytest.raises(ValueError, match="one run"):
         survey.infer(OPTIONS, data=ds, schedule="lines")
+
+
+@pytest.mark.gpu
+def test_background_fill_writes_the_files_a_foreground_fill_writes(tmp_path):
+    """Twelve soundings in blocks of five: the first two blocks' rows leave on the fill thread (its own device stream) while the next
+    block's chains run, the last block's in the foreground -- the containers and the summaries of the one-block run, whose rows all
+    leave in the foreground; and the phase clocks say which way the rows went."""
+    from geobipy_amd import survey_run
+    o = survey.read_options(OPTIONS)
+    ds = survey.FdemData.read_csv(o["data_filename"], o["system_filename"]).subset(np.arange(12))
+    kw = dict(data=ds, n_markov_chains=300, burn_in_min_iterations=100, check_every=100, exact_jacobian=True, container="npz")
+    one, three = tmp_path / "one", tmp_path / "three"
+    t_one, t_three = {}, {}
+    whole = survey.infer(OPTIONS, results_directory=str(one), timings=t_one, **kw)
+    pieces = survey.infer(OPTIONS, results_directory=str(three), timings=t_three, chunk=5, **kw)
+    assert set(whole) == set(pieces)
+    for k in whole:
+        assert np.array_equal(np.asarray(whole[k]), np.asarray(pieces[k]), equal_nan=True), k
+    names = sorted(os.listdir(one))
+    assert names == sorted(os.listdir(three)) == ["0.0.results.attrs.json", "0.0.results.npz"]
+    assert open(one / names[0]).read() == open(three / names[0]).read()
+    from geobipy_amd import hdf
+    a, b = hdf.load_npz(str(one / names[1])), hdf.load_npz(str(three / names[1]))
+    assert sorted(a) == sorted(b) and a["/model/values/posterior/values/data"].shape[0] == 12 and a["/phids/data"].shape == (12, 600)
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    print("phases, one block:", t_one, "three blocks:", t_three)
+    assert {"rows_to_host_overlapped", "container_fill_overlapped", "rows_to_host", "container_fill"} <= set(t_three)
+    assert {"rows_to_host", "container_fill"} <= set(t_one) and not {"rows_to_host_overlapped", "container_fill_overlapped"} & set(t_one)
+    assert set(t_one) <= set(survey_run.PHASES) and set(t_three) <= set(survey_run.PHASES)
+    assert {"upload_and_initialise", "chains", "hitmap_statistics", "compress_and_write_tail", "summaries_to_host", "summary_file_tail"} <= set(t_one) & set(t_three)
 
 
 @pytest.mark.gpu
