@@ -176,7 +176,9 @@ __device__ __forceinline__ double wave_sum(double v)
 #error "geobipy_amd builds for gfx950 (MI355X) only: hipcc --offload-arch=gfx950"
 #endif
 // v[lane] + v[lane ^ W] for W = 16, 32 in every lane, by gfx950's row swaps (v_permlane16_swap / v_permlane32_swap exchange the odd
-// 16- / 32-lane rows of one register with the even rows of another: VALU moves, where a shuffle would wait for the LDS crossbar)
+// 16- / 32-lane rows of one register with the even rows of another: VALU moves, where a shuffle would wait for the LDS crossbar;
+// ds_swizzle / ds_bpermute for every exchange of wave_sum_store2 and wave_sum_tail were measured in the VALU-bound headline kernel and
+// were no faster, docs/notes_r9.md)
 template <int W>
 __device__ __forceinline__ void row_pair(double v, double& x, double& y)     // {x, y} = {v[lane], v[lane ^ W]} in some order
 {
@@ -340,41 +342,69 @@ __device__ __forceinline__ void forward_passes(const gbp::MathCtx& M, const Chan
 // pass p is frequency p, so there is no frequency cursor, no second layer slot, no straddle and no ragged tail.  Each pair of passes
 // goes through one reduction tree (wave_sum_store2); the partials are the ones forward_passes stores, bit for bit.  The plain forward
 // kernel's path (no row scale).
+// The wave's share of the layer tables is used as LayerRec rec[Lmax] here (the bytes of LayerK lay[2][Lmax]): -2 thk_k sits in layer k's
+// record, written once per sounding, and the recursion reads the records from ONE base address held in a VGPR (rte_num_den_rec), where
+// separate tables at run-time distances cost two address copies per layer.
+typedef const __attribute__((address_space(3))) gbp::LayerRec* lds_rec_cp;
+// gbp::hankel_term with the exponent clamped by ONE v_max_f64: the argument is a product, hence canonical already, which the compiler
+// does not see through fmax (it puts a canonicalising v_max_f64 v, v in front).  The clamp's result is fmax's for every input, NaN included.
+__device__ __forceinline__ double clamp_exp_arg(double x)
+{
+    double r;
+    const double lo = -800.0;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "s"(lo));
+    return r;
+}
+__device__ __forceinline__ cplx hankel_term_1f(const gbp::MathCtx& M, cplx num, cplx den, cplx ue, double hD, cplx coef, bool real_ue)
+{
+    const double x = clamp_exp_arg(ue.re * hD);
+    if (real_ue) return gbp::cdiv(num * (coef * gbp::exp_neg_clamped(M, x)), den);
+    const cplx E = gbp::cexp_neg_clamped(M, x, ue.im * hD);
+    return gbp::cdiv(num * (E * coef), den);
+}
 template <bool DIRECT>
 __device__ __forceinline__ void forward_passes_1f(const gbp::MathCtx& M, const Channel* __restrict__ chan,
                                                   const double* __restrict__ pts, int P, int L, const double* __restrict__ sig,
-                                                  const double* sh_t2, gbp::LayerK* sh_lay, double alt, int p0, int p1, int lane,
-                                                  cplx* sh_part)
+                                                  const double* __restrict__ th, gbp::LayerRec* sh_rec, double alt, int p0, int p1,
+                                                  int lane, cplx* sh_part)
 {
     cplx prev = gbp::mk(0.0, 0.0);
     // setup_layers for up to 64 layers (wave-uniform): lane k keeps sigma_k in a register for all passes and writes layer k's
     // constants with one predicated statement -- no loop, no pointer stepping, no load of sigma in every pass; the same products
     const bool lane_per_layer = L <= 64;
     const double sig_k = (lane_per_layer && lane < L) ? sig[lane] : 0.0;
+    for (int k = lane; k < L - 1; k += 64) sh_rec[k].t2 = -2.0 * th[k];
+    // the records' LDS address, opaque and in a VGPR: every ds_read of the recursion is this register plus an immediate
+    unsigned rec_at = (unsigned)(size_t)(lds_rec_cp)sh_rec;
+    asm volatile("" : "+v"(rec_at));
+    const lds_rec_cp rec = (lds_rec_cp)(size_t)rec_at;
     for (int p = p0; p < p1; ++p) {
         const Channel cc = chan[p];
         if (lane_per_layer) {
             if (lane < L) {
                 const double b = cc.wmu * sig_k;
-                sh_lay[lane].b2 = b * b;
-                sh_lay[lane].bc = b * 0.70710678118654752440;
+                sh_rec[lane].b2 = b * b;
+                sh_rec[lane].bc = b * 0.70710678118654752440;
             }
-            __builtin_amdgcn_wave_barrier();
         } else {
-            setup_layers(sh_lay, cc.wmu, sig, L, lane);
+            for (int k = lane; k < L; k += 64) {
+                const double b = cc.wmu * sig[k];
+                sh_rec[k].b2 = b * b;
+                sh_rec[k].bc = b * 0.70710678118654752440;
+            }
         }
+        __builtin_amdgcn_wave_barrier();
         const double hD = cc.hd0 - 2.0 * alt;
         const gbp::Point pt = gbp::load_point_u(pts, P, (unsigned)(64 * p + lane));
         cplx num, den;
-        gbp::rte_num_den<DIRECT>(M, pt.a, L, sh_lay, sh_t2, pt.u0, num, den);
+        gbp::rte_num_den_rec<DIRECT>(M, pt.a, L, rec, pt.u0, num, den);
         const bool real_ue = __ballot(pt.ue.im != 0.0) == 0ull;            // (wave-uniform: see hankel_term)
-        const cplx t = gbp::hankel_term(M, num, den, pt.ue, hD, pt.coef, real_ue);
+        const cplx t = hankel_term_1f(M, num, den, pt.ue, hD, pt.coef, real_ue);
         if ((p - p0) & 1)
             wave_sum_store2(prev.re, prev.im, t.re, t.im, lane, sh_part + 2 * (p - 1));
-        else if (p + 1 < p1)
-            prev = t;
-        else
+        else if (p + 1 == p1)
             wave_sum_store(t.re, t.im, lane, sh_part + 2 * p);
+        prev = t;
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -443,6 +473,7 @@ __device__ __forceinline__ void loglike_wave_prepared(int N, const double* p, co
 // iteration by the persistent sampler kernel (gbp_rjmcmc.h).  Every thread of the workgroup must call it (it contains
 // workgroup barriers); `sh_out` holds 2 * GBP_MAX_FREQ doubles, `sh_dyn` dyn_lds_bytes(nwaves, Lmax, passes) bytes:
 //   LayerK lay[nwaves][2][Lmax] | cplx part[passes][2] | double t2[Lmax]
+// (forward_passes_1f keeps LayerRec rec[nwaves][Lmax] in the bytes of `lay` and leaves `t2` alone)
 // The passes are shared by the first `nw_use` waves of the workgroup (the others only take part in the barriers); the result
 // does not depend on nw_use (see forward_passes).
 // ONE_PER_PASS (the plain forward kernel): the table set's frequencies are one pass each when `one_per_pass` (BinDesc) is set, and
@@ -469,18 +500,21 @@ __device__ __forceinline__ void forward_body(const gbp::MathCtx& M, double* sh_o
     gbp::LayerK* sh_lay = reinterpret_cast<gbp::LayerK*>(sh_dyn) + (size_t)wave * 2 * Lmax;
     cplx* sh_part = reinterpret_cast<cplx*>(sh_dyn + (size_t)nwaves * 2 * Lmax * sizeof(gbp::LayerK));
     double* sh_t2 = reinterpret_cast<double*>(sh_part + (size_t)2 * npass);
-    for (int k = tid; k < L - 1; k += nth) sh_t2[k] = -2.0 * th[k];
+    const bool records = ONE_PER_PASS && one_per_pass;     // (workgroup-uniform: the sounding's own table set)
+    if (!records)
+        for (int k = tid; k < L - 1; k += nth) sh_t2[k] = -2.0 * th[k];
     __syncthreads();
 
     if (wave < nwaves) {
         const int per = (npass + nwaves - 1) / nwaves;
         const int p0 = wave * per;
         const int p1 = min(npass, p0 + per);
-        if (ONE_PER_PASS && one_per_pass) {     // (workgroup-uniform: the sounding's own table set)
+        if (records) {
+            gbp::LayerRec* sh_rec = reinterpret_cast<gbp::LayerRec*>(sh_lay);
             if (direct)
-                forward_passes_1f<true>(M, chan, pts, npts_total, L, sig, sh_t2, sh_lay, alt, p0, p1, lane, sh_part);
+                forward_passes_1f<true>(M, chan, pts, npts_total, L, sig, th, sh_rec, alt, p0, p1, lane, sh_part);
             else
-                forward_passes_1f<false>(M, chan, pts, npts_total, L, sig, sh_t2, sh_lay, alt, p0, p1, lane, sh_part);
+                forward_passes_1f<false>(M, chan, pts, npts_total, L, sig, th, sh_rec, alt, p0, p1, lane, sh_part);
         } else if (direct) {
             forward_passes<true>(M, chan, pts, npts_total, F, L, sig, sh_t2, sh_lay, Lmax, alt, p0, p1, lane, sh_part, row_scale);
         } else {

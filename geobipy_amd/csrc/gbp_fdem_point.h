@@ -121,6 +121,67 @@ GBP_HD void rte_num_den(const MathCtx& M, double a, int L, const LayerK* __restr
     den = uD + N;
 }
 
+// ---- the same recursion for callers that keep a layer's constants and its t2 in ONE record at a compile-time distance from a base
+// (forward_passes_1f): the fp64 operations of rte_num_den, in its order, so the bits are rte_num_den's ----
+struct alignas(16) LayerRec {
+    double b2, bc;  // LayerK
+    double t2;      // -2 thk_k (never read for the basement)
+    double spare;
+};
+GBP_HD void rte_renorm(cplx& N, cplx& D)
+{
+    int s = -frexp_exp(__builtin_fmax(__builtin_fabs(D.re), __builtin_fabs(D.im)));
+    N = mk(ldexp_i(N.re, s), ldexp_i(N.im, s));
+    D = mk(ldexp_i(D.re, s), ldexp_i(D.im, s));
+}
+// One layer.  FIRST: the step above the basement, where D = (1, 0) and u * D is u exactly -- fma(u.re, 1, -(u.im * 0)) = u.re and
+// fma(u.re, 0, u.im * 1) = u.im for finite u with u.re > 0, which csqrt_upper2 returns for every finite positive conductivity (a
+// non-finite one gives NaN here as there) --, so D is neither materialised nor multiplied.
+template <bool DIRECT, bool FIRST, bool RENORM>
+GBP_HD void rte_layer(const MathCtx& M, double a, double b2, double bc, double tk, cplx& N, cplx& D)
+{
+    const cplx u = csqrt_upper2<DIRECT>(a, b2, bc);
+    const cplx e = cexp_neg(M, tk * u.re, tk * u.im);
+    const cplx uD = FIRST ? u : u * D;
+    const cplx A = uD + N, B = uD - N;
+    const cplx eB = e * B;
+    N = u * (A - eB);
+    D = A + eB;
+    if (RENORM) rte_renorm(N, D);
+}
+// rte_num_den over records: REC is a pointer to LayerRec (on the device one into LDS whose base sits in a VGPR, so that rec[k] of a
+// compile-time k is that register plus an immediate offset and the layer costs no address arithmetic).  The step above the basement is
+// peeled; the layers below GBP_RTE_CHAIN are an unrolled chain of wave-uniform branches, entered at the sounding's depth, with the
+// renormalisation of k = 7 resolved at compile time; deeper models walk down to the chain's top in a loop first.
+#define GBP_RTE_CHAIN 8
+template <bool DIRECT, typename REC>
+GBP_HD void rte_num_den_rec(const MathCtx& M, double a, int L, REC rec, cplx u0, cplx& num, cplx& den)
+{
+    cplx N = csqrt_upper2<DIRECT>(a, rec[L - 1].b2, rec[L - 1].bc);  // basement: Yh_L = u_L
+    // half-space: D = (1, 0), and u0 * D is u0 up to the sign of a zero, which the sums with N (both parts > 0) absorb: no product
+    cplx D, uD = u0;
+    int k = L - 2;
+    if (k >= 0) {
+        rte_layer<DIRECT, true, false>(M, a, rec[k].b2, rec[k].bc, rec[k].t2, N, D);
+        if ((k & 7) == 7) rte_renorm(N, D);
+        for (--k; k >= GBP_RTE_CHAIN; --k) {
+            rte_layer<DIRECT, false, false>(M, a, rec[k].b2, rec[k].bc, rec[k].t2, N, D);
+            if ((k & 7) == 7) rte_renorm(N, D);
+        }
+        if (k >= 7) rte_layer<DIRECT, false, true>(M, a, rec[7].b2, rec[7].bc, rec[7].t2, N, D);
+        if (k >= 6) rte_layer<DIRECT, false, false>(M, a, rec[6].b2, rec[6].bc, rec[6].t2, N, D);
+        if (k >= 5) rte_layer<DIRECT, false, false>(M, a, rec[5].b2, rec[5].bc, rec[5].t2, N, D);
+        if (k >= 4) rte_layer<DIRECT, false, false>(M, a, rec[4].b2, rec[4].bc, rec[4].t2, N, D);
+        if (k >= 3) rte_layer<DIRECT, false, false>(M, a, rec[3].b2, rec[3].bc, rec[3].t2, N, D);
+        if (k >= 2) rte_layer<DIRECT, false, false>(M, a, rec[2].b2, rec[2].bc, rec[2].t2, N, D);
+        if (k >= 1) rte_layer<DIRECT, false, false>(M, a, rec[1].b2, rec[1].bc, rec[1].t2, N, D);
+        if (k >= 0) rte_layer<DIRECT, false, false>(M, a, rec[0].b2, rec[0].bc, rec[0].t2, N, D);
+        uD = u0 * D;
+    }
+    num = uD - N;
+    den = uD + N;
+}
+
 // One term of H - H0: rTE * exp(ue * hD) * coef
 // `real_ue` (wave-uniform, decided by the caller): ue.im == 0 for every lane of the pass -- the abscissae above the free-space wavenumber,
 // i.e. every point of an abscissa window at survey altitudes, and every point of a raw (time-domain) handle.  cexp_neg(x, 0) is

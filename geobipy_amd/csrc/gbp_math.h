@@ -179,9 +179,9 @@ GBP_HD double round_mul(double x, double inv, int& k)
     return t - MAGIC;
 }
 
-GBP_HD double exp_neg(const MathCtx& M, double x)
+// (exp_neg_clamped: the same for a caller that has clamped xx to >= -800 itself)
+GBP_HD double exp_neg_clamped(const MathCtx& M, double xx)
 {
-    double xx = __builtin_fmax(x, -800.0);
     int k;
     double kf = round_mul(xx, M.k.inv_ln2_64, k);
     double r = __builtin_fma(-kf, M.k.ln2_64_hi, xx);
@@ -194,6 +194,7 @@ GBP_HD double exp_neg(const MathCtx& M, double x)
     double t = M.exp2_64[k & 63];
     return ldexp_i(t * p, k >> 6);
 }
+GBP_HD double exp_neg(const MathCtx& M, double x) { return exp_neg_clamped(M, __builtin_fmax(x, -800.0)); }
 
 // sin and cos of x for |x| < ~2e8 (beyond that the caller's exp factor has long underflowed).
 //   x = k pi/32 + r, |r| <= pi/64: angle addition with the tabulated sin/cos of k pi/32 and degree-7/8
@@ -220,6 +221,13 @@ GBP_HD void sincos_tab(const MathCtx& M, double x, double& s, double& c)
 GBP_HD cplx cexp_neg(const MathCtx& M, double x, double t)
 {
     double e = exp_neg(M, x);
+    double s, c;
+    sincos_tab(M, t, s, c);
+    return mk(e * c, e * s);
+}
+GBP_HD cplx cexp_neg_clamped(const MathCtx& M, double xx, double t)
+{
+    double e = exp_neg_clamped(M, xx);
     double s, c;
     sincos_tab(M, t, s, c);
     return mk(e * c, e * s);
