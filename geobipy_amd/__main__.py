@@ -61,7 +61,18 @@ def parse(argv=None):
     p.add_argument("--data-posteriors", type=int, nargs="?", const=64, default=None, metavar="N_BINS",
                    help="data-space posteriors (residual of every channel's prediction, misfit: data_* / misfit_* in the summaries) on "
                         "N_BINS cells (8 .. 256, default 64)")
+    p.add_argument("--ensemble", type=int, nargs="*", default=None, metavar="N",
+                   help="keep a posterior ensemble: N_KEEP [THIN] -- every THIN-th sampled model of every sounding, up to N_KEEP (1 .. 4096, "
+                        "default 64; THIN defaults to ceil(n_markov_chains / N_KEEP)): ensemble_* in the summaries")
     a = p.parse_args(argv)
+    if a.ensemble is not None:
+        if len(a.ensemble) > 2:
+            p.error("--ensemble: at most N_KEEP and THIN")
+        a.ensemble = dict(n_keep=a.ensemble[0] if a.ensemble else 64, thin=a.ensemble[1] if len(a.ensemble) > 1 else None)
+        if not 1 <= a.ensemble["n_keep"] <= 4096 or (a.ensemble["thin"] is not None and a.ensemble["thin"] < 1):
+            p.error("--ensemble: N_KEEP in 1 .. 4096, THIN >= 1")
+        if a.no_hitmap:
+            p.error("--ensemble needs the hit map (drop --no-hitmap)")
     if a.data_posteriors is not None:
         if not 8 <= a.data_posteriors <= 256:
             p.error("--data-posteriors: 8 .. 256 cells")
@@ -115,7 +126,7 @@ def main(argv=None):
                        container=None if a.container == "auto" else a.container, data_directory=a.data_directory,
                        data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
                        first_below=tuple(a.first_below), replicates=a.replicates,
-                       data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors))
+                       data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble)
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

@@ -32,7 +32,8 @@ class RjOptions(ctypes.Structure):
                    ("trace_every", ctypes.c_int32), ("trace_length", ctypes.c_int32),
                    ("n_units", ctypes.c_int32), ("unit_kinds", ctypes.c_int32), ("n_first", ctypes.c_int32),
                    ("first_threshold", ctypes.c_double * 4), ("first_direction", ctypes.c_int32 * 4),
-                   ("n_data_bins", ctypes.c_int32), ("data_half_width", ctypes.c_double), ("misfit_half_width", ctypes.c_double)])
+                   ("n_data_bins", ctypes.c_int32), ("data_half_width", ctypes.c_double), ("misfit_half_width", ctypes.c_double),
+                   ("n_ensemble", ctypes.c_int32), ("ensemble_thin", ctypes.c_int32)])
 
 
 RJ_CHAIN_FIELDS = ("rel_group", "add_group", "add_scale", "chain_id", "data", "height", "log_mean_prior", "k", "edges", "sigma", "rel", "add", "pred", "J", "prior", "like", "misfit",
@@ -40,7 +41,8 @@ RJ_CHAIN_FIELDS = ("rel_group", "add_group", "add_scale", "chain_id", "data", "h
                    "log_prop", "sigma_p", "pred_p", "misfit_p", "like_p", "J_p", "log_ratio", "n_accepted", "k_hist", "edge_hist",
                    "rel_hist", "add_hist", "hitmap", "hit_dwell", "burned_in_iteration", "status", "best_posterior", "best_k", "best_edges", "best_sigma",
                    "best_rel", "best_add", "iteration0", "height_p", "height0", "height_hist", "best_height", "step_flags", "trace_misfit", "trace_accept",
-                   "best_iteration", "unit_z", "unit_hist", "first_hist", "first_none", "data_scale", "data_hist", "misfit_scale", "misfit_hist")
+                   "best_iteration", "unit_z", "unit_hist", "first_hist", "first_none", "data_scale", "data_hist", "misfit_scale", "misfit_hist",
+                   "ens_k", "ens_edges", "ens_sigma", "ens_misfit", "ens_seen")
 
 
 class RjChains(ctypes.Structure):
@@ -136,6 +138,9 @@ SIGNATURES = {
     "gbp_hitmap_classes_i64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_int, c_double_p, c_double_p] + [c_void_p] * 3
                                + [c_void_p]),
     "gbp_hitmap_intervals": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
+    "gbp_ensemble_raster": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gbp_ensemble_rebin": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, c_int, ctypes.c_double,
+                                   c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_double_p, c_int32_p, c_void_p, c_void_p, c_void_p]),
     "gbp_hitmap_pool": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double] + [c_void_p] * 5 + [c_void_p]),
     "gbp_hitmap_mixture": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
     "gbp_hitmap_mixture_i64": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6

@@ -1511,6 +1511,7 @@ static gbp_status fm_dlogc_launch(const gbp_fdem_system* sys, int B, int Lmax, c
 #include "gbp_tdem.h"
 #include "gbp_hostpack.h"
 #include "gbp_hitmap.h"
+#include "gbp_ensemble.h"
 
 // Per-depth mean and 5 / 50 / 95 % points of log10 conductivity of B hit maps [B, nv, nz] (depth fastest) -> four [B, nz] arrays
 extern "C" gbp_status gbp_hitmap_statistics(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width,
@@ -1749,6 +1750,83 @@ extern "C" gbp_status gbp_runs_to_zlib(int n_rows, int64_t cells_per_row, const 
         pos += (int64_t)n;
         out_ptr[r + 1] = pos;
     }
+    return GBP_OK;
+}
+
+// Realisations of a posterior ensemble on a depth axis (csrc/gbp_ensemble.h k_ensemble_raster): out[b, r, c] = the conductivity of the
+// layer of slot slots[r] of chain b that holds z[c] -- layer = #{l < k - 1 : edges[l] <= z[c]}, the hit map's rule; the stored double
+// bit for bit; a row of NaN for an empty slot (or one outside 0 .. n_ensemble - 1).  slots: DEVICE int32 [R], any order, repeats
+// allowed; z: DEVICE [n_depth].  K <= 64 (a slot's rows sit one entry per lane).
+extern "C" gbp_status gbp_ensemble_raster(int B, int n_ensemble, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                          int R, const int32_t* slots, int n_depth, const double* z, double* out, void* stream)
+{
+    if (B < 0 || n_ensemble < 1 || R < 1 || n_depth < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_raster: negative or zero size%s");
+    if (n_ensemble > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_raster: n_ensemble outside 1 .. 4096%s");
+    if (K < 1 || K > 64) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_raster: K outside 1 .. 64%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!ens_k || !ens_edges || !ens_sigma || !slots || !z || !out) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_raster: NULL pointer%s");
+    const int64_t rows = (int64_t)B * R;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_raster: B * R out of range%s");
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, (long long)rows, n_ensemble, K, R, n_depth, ens_k, ens_edges, ens_sigma,
+                           slots, z, out);
+    };
+    if (n_depth <= 64) launch(ensemble::k_ensemble_raster<1>);
+    else if (n_depth <= 128) launch(ensemble::k_ensemble_raster<2>);
+    else launch(ensemble::k_ensemble_raster<4>);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+// Any posterior the sampler could have binned, after the fact (csrc/gbp_ensemble.h k_ensemble_rebin): every filled slot of every chain
+// is added with weight 1 by the sampler's own accumulators to outputs this entry zeroes first -- hitmap int32 [B, n_value, n_depth]
+// (NULL: none) on the axes given, unit_hist int32 [B, Q, n_value, n_units] for unit_z [B, n_units, 2] (n_units == 0: none), first_hist
+// int32 [B, n_first, n_depth] and first_none [B, n_first] (n_first == 0: none; thresholds / directions: HOST arrays).
+extern "C" gbp_status gbp_ensemble_rebin(int B, int n_ensemble, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                         const double* log_mean_prior, int n_value, double value_half_width, int n_depth, double depth_bin_width,
+                                         int32_t* hitmap, int n_units, int unit_kinds, const double* unit_z, int32_t* unit_hist, int n_first,
+                                         const double* first_threshold, const int32_t* first_direction, int32_t* first_hist,
+                                         int32_t* first_none, void* stream)
+{
+    if (B < 0 || n_ensemble < 1 || n_value < 1 || n_depth < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: negative or zero size%s");
+    if (n_ensemble > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: n_ensemble outside 1 .. 4096%s");
+    if (K < 1 || K > 64) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: K outside 1 .. 64%s");
+    if (!(std::isfinite(value_half_width) && value_half_width > 0.0) || !(std::isfinite(depth_bin_width) && depth_bin_width > 0.0))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: value_half_width and depth_bin_width must be finite and positive%s");
+    if (n_units < 0 || n_units > 16 || n_first < 0 || n_first > 4) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: n_units outside 0 .. 16 or n_first outside 0 .. 4%s");
+    if (n_units > 0 && (unit_kinds < 1 || unit_kinds > 3)) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: unit_kinds must be 1, 2 or 3%s");
+    if (n_first > 0 && (!first_threshold || !first_direction)) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: first_threshold / first_direction NULL%s");
+    for (int q = 0; q < n_first; ++q) {
+        if (!(std::isfinite(first_threshold[q]) && first_threshold[q] > 0.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: first_threshold must be finite and positive%s");
+        if (first_direction[q] != 1 && first_direction[q] != -1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: first_direction must be +1 or -1%s");
+    }
+    if (!hitmap && n_units == 0 && n_first == 0) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: nothing to compute (no hitmap, no units, no thresholds)%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!ens_k || !ens_edges || !ens_sigma || !log_mean_prior || (n_units > 0 && (!unit_z || !unit_hist)) || (n_first > 0 && (!first_hist || !first_none)))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_rebin: NULL pointer%s");
+    gbp_rj_options o = {};
+    o.max_layers = K; o.n_ensemble = n_ensemble; o.ensemble_thin = 1;
+    o.n_value_bins = n_value; o.value_half_width = value_half_width; o.n_depth_bins = n_depth; o.depth_bin_width = depth_bin_width;
+    o.n_units = n_units; o.unit_kinds = n_units > 0 ? unit_kinds : 0; o.n_first = n_first;
+    for (int q = 0; q < n_first; ++q) { o.first_threshold[q] = first_threshold[q]; o.first_direction[q] = first_direction[q]; }
+    rj::RjOpt x = {};                              // (the logarithms of extend() belong to the moves: the accumulators read none)
+    static_cast<gbp_rj_options&>(x) = o;
+    gbp_rj_chains c = {};
+    c.B = B; c.log_mean_prior = log_mean_prior;
+    c.ens_k = const_cast<int32_t*>(ens_k); c.ens_edges = const_cast<double*>(ens_edges); c.ens_sigma = const_cast<double*>(ens_sigma);
+    c.hitmap = hitmap;
+    if (n_units > 0) { c.unit_z = unit_z; c.unit_hist = unit_hist; }
+    if (n_first > 0) { c.first_hist = first_hist; c.first_none = first_none; }
+    const size_t nq = (size_t)((o.unit_kinds & 1) + ((o.unit_kinds >> 1) & 1));
+    if (hitmap) GBP_HIP(hipMemsetAsync(hitmap, 0, (size_t)B * n_value * n_depth * sizeof(int32_t), (hipStream_t)stream));
+    if (n_units > 0) GBP_HIP(hipMemsetAsync(unit_hist, 0, (size_t)B * nq * n_value * n_units * sizeof(int32_t), (hipStream_t)stream));
+    if (n_first > 0) {
+        GBP_HIP(hipMemsetAsync(first_hist, 0, (size_t)B * n_first * n_depth * sizeof(int32_t), (hipStream_t)stream));
+        GBP_HIP(hipMemsetAsync(first_none, 0, (size_t)B * n_first * sizeof(int32_t), (hipStream_t)stream));
+    }
+    hipLaunchKernelGGL(ensemble::k_ensemble_rebin, dim3(B), dim3(64), 0, (hipStream_t)stream, x, c);
+    GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
 

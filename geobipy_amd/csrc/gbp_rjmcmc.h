@@ -1251,7 +1251,8 @@ __device__ __noinline__ void units_zero(const RjOpt& o, const gbp_rj_chains& c, 
 // cell position is rounded once (the intrinsics: the host's numpy expression gives the same bits); a non-finite position has no cell.
 // Called where the hit map is settled, with the same dwell: a chain's prediction and misfit change only when a proposal is accepted.
 __device__ inline bool data_on(const gbp_rj_chains& c) { return c.data_hist != nullptr; }
-__device__ inline bool extras_on(const gbp_rj_chains& c) { return units_on(c) || data_on(c); }
+__device__ inline bool ensemble_on(const gbp_rj_chains& c) { return c.ens_k != nullptr; }
+__device__ inline bool extras_on(const gbp_rj_chains& c) { return units_on(c) || data_on(c) || ensemble_on(c); }
 
 __device__ inline int data_cell(double x, double H, int nb)
 {
@@ -1287,6 +1288,39 @@ __device__ __noinline__ void data_zero(const RjOpt& o, const gbp_rj_chains& c, s
     for (size_t q = i; q < nb; q += W) c.misfit_hist[b * nb + q] = 0;
 }
 
+// Posterior ensemble (gbp_rj_options.n_ensemble; include/geobipy_amd.h states the rule): a settle of model (ec, sc, kc) with `weight`
+// = its dwell covers the samples ens_seen .. ens_seen + weight - 1 of chain b; every ensemble_thin-th of them, up to n_ensemble, is
+// kept -- slot n / thin receives the model, in chain order, and samples past the last slot are dropped.  Lane i of the chain's W lanes
+// writes entries i, i + W, ... of a row; lane 0 the layer count, the misfit and, after every lane has read it, ens_seen (the lanes of a
+// chain sit in one wave: program order is the ordering, as for the histograms).  Called where the hit map is settled, with its dwell.
+template <int W>
+__device__ __noinline__ void ensemble_add(const RjOpt& o, const gbp_rj_chains& c, size_t b, const double* ec, const double* sc, int kc,
+                                          double misfit, int i, int weight)
+{
+    const int ne = o.n_ensemble, thin = o.ensemble_thin, K = o.max_layers;
+    const int seen = c.ens_seen[b];
+    if (weight <= 0 || seen < 0) return;                         // (nothing to settle; a counter nobody zeroed writes nowhere)
+    const long long first = ((long long)seen + thin - 1) / thin, last = min(((long long)seen + weight - 1) / thin, (long long)ne - 1);
+    for (long long s = first; s <= last; ++s) {
+        const size_t row = b * (size_t)ne + (size_t)s;
+        for (int j = i; j < K; j += W) {
+            c.ens_edges[row * K + j] = j < kc - 1 ? ec[j] : INF;
+            c.ens_sigma[row * K + j] = j < kc ? sc[j] : __longlong_as_double(0x7ff8000000000000ll);
+        }
+        if (i == 0) { c.ens_k[row] = kc; c.ens_misfit[row] = misfit; }
+    }
+    if (i == 0) c.ens_seen[b] = seen + weight;
+}
+
+// (burn-in reset, W lanes of chain b: an empty slot is one with ens_k == 0, its rows are never read)
+template <int W>
+__device__ __noinline__ void ensemble_zero(const RjOpt& o, const gbp_rj_chains& c, size_t b, int i)
+{
+    const size_t ne = (size_t)o.n_ensemble;
+    for (size_t q = i; q < ne; q += W) c.ens_k[b * ne + q] = 0;
+    if (i == 0) c.ens_seen[b] = 0;
+}
+
 __device__ inline double group_sum8(double v)
 {
     // (the pairs of the xor butterfly: lane ^ 1, lane ^ 2, then the other quad -- whose four lanes hold one value)
@@ -1300,7 +1334,7 @@ __device__ inline double group_sum8(double v)
 // all lanes of a chain sit in one wave, so program order is the only ordering needed between them.
 // (have_regs, W == 8: entry i of the post-step rows is in e_now / s_now -- the interface histogram then costs no loads, and the counters
 //  are atomic adds whose result nobody waits for: the stage is a latency chain, every read-modify-write was a trip to memory)
-// (UNITS: the sampled extras -- unit posteriors, data-space posteriors -- are compiled in, each guarded by its own pointer at run time;
+// (UNITS: the sampled extras -- unit posteriors, data-space posteriors, the posterior ensemble -- are compiled in, each guarded by its own pointer at run time;
 //  the instantiations without them are the code they were before the features.  pred_now: the post-step prediction, passed like ec / sc)
 template <int W, bool UNITS = false>
 __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32_t iter, int accumulate, size_t b, int i,
@@ -1343,6 +1377,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
                     dwell = 0;
                     if (UNITS && units_on(c)) units_zero<W>(o, c, b, i);
                     if (UNITS && data_on(c)) data_zero<W>(o, c, b, i);
+                    if (UNITS && ensemble_on(c)) ensemble_zero<W>(o, c, b, i);
                 }
                 if (i == 0) c.burned_in_iteration[b] = bi;
             }
@@ -1392,6 +1427,7 @@ __device__ inline int bookkeeping(const RjOpt& o, const gbp_rj_chains& c, uint32
             hitmap_add<W>(o, c.hitmap + b * nh, ec, sc, kc, lmp, i, dwell);
             if (UNITS && units_on(c)) units_add<W>(o, c, b, ec, sc, kc, lmp, i, dwell);
             if (UNITS && data_on(c)) data_add<W>(o, c, b, pred_now, misfit_now, i, dwell);
+            if (UNITS && ensemble_on(c)) ensemble_add<W>(o, c, b, ec, sc, kc, misfit_now, i, dwell);
             dwell = 0;
         }
         if (i == 0) c.hit_dwell[b] = dwell;
@@ -1526,6 +1562,7 @@ __device__ __forceinline__ void accept_body(const RjOpt& o, const gbp_rj_chains&
         hitmap_add<64>(o, c.hitmap + (size_t)b * nh, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
         if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, lmp, lane, dwell);
         if (UNITS && data_on(c)) data_add<64>(o, c, (size_t)b, c.pred + (size_t)b * N, misfit_c, lane, dwell);      // (before pred is overwritten)
+        if (UNITS && ensemble_on(c)) ensemble_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, k_prev, misfit_c, lane, dwell);
         dwell = 0;
         wave_sync();
     }
@@ -1888,6 +1925,7 @@ __device__ __forceinline__ void accept8_body(const RjOpt& o, const gbp_rj_chains
         hitmap_add8(o, c.hitmap + bb * nh, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, base, dwell, on);
         if (UNITS && on && units_on(c)) units_add<8>(o, c, bb, c.edges + bb * K, c.sigma + bb * K, k_prev, lmp, i, dwell);
         if (UNITS && on && data_on(c)) data_add<8>(o, c, bb, c.pred + bb * N, misfit_c, i, dwell);      // (before pred is overwritten)
+        if (UNITS && on && ensemble_on(c)) ensemble_add<8>(o, c, bb, c.edges + bb * K, c.sigma + bb * K, k_prev, misfit_c, i, dwell);
         if (on) dwell = 0;
     }
     if (accept && one_trip) {
@@ -2044,6 +2082,7 @@ __global__ __launch_bounds__(64) void k_rj_flush(RjOpt o, gbp_rj_chains c)
                    c.log_mean_prior[b], lane, dwell);
     if (UNITS && units_on(c)) units_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b], c.log_mean_prior[b], lane, dwell);
     if (UNITS && data_on(c)) data_add<64>(o, c, (size_t)b, c.pred + (size_t)b * o.n_channels, c.misfit[b], lane, dwell);
+    if (UNITS && ensemble_on(c)) ensemble_add<64>(o, c, (size_t)b, c.edges + (size_t)b * K, c.sigma + (size_t)b * K, c.k[b], c.misfit[b], lane, dwell);
     __syncthreads();
     if (lane == 0) c.hit_dwell[b] = 0;
 }
@@ -2791,6 +2830,8 @@ gbp_rj_chains slice_chains(const gbp_rj_options& o, const gbp_rj_chains& c, int 
     GBP_OFF(unit_z, nu * 2) GBP_OFF(unit_hist, nq * nv * nu) GBP_OFF(first_hist, nf * nd) GBP_OFF(first_none, nf)
     const size_t ndb = (size_t)o.n_data_bins;
     GBP_OFF(data_scale, N) GBP_OFF(data_hist, ndb * N) GBP_OFF(misfit_scale, 1) GBP_OFF(misfit_hist, ndb)
+    const size_t ne = (size_t)o.n_ensemble;
+    GBP_OFF(ens_k, ne) GBP_OFF(ens_edges, ne * K) GBP_OFF(ens_sigma, ne * K) GBP_OFF(ens_misfit, ne) GBP_OFF(ens_seen, 1)
 #undef GBP_OFF
     return s;
 }
@@ -2842,6 +2883,16 @@ gbp_status rj_check(const gbp_rj_options* o, const gbp_rj_chains* c)
         if (!c->hitmap)
             return fail(GBP_ERR_INVALID_ARG, "data posteriors (data_hist / misfit_hist) need the hit map: they are settled with its dwell times%s");
         if (!c->data_scale || !c->misfit_scale) return fail(GBP_ERR_INVALID_ARG, "data_hist needs data_scale, misfit_hist needs misfit_scale%s");
+    }
+    // posterior ensemble: settled and zeroed with the hit map too
+    const bool ens_any = c->ens_k || c->ens_edges || c->ens_sigma || c->ens_misfit || c->ens_seen;
+    if (o->n_ensemble != 0 || o->ensemble_thin != 0 || ens_any) {
+        if (o->n_ensemble < 1 || o->n_ensemble > 4096) return fail(GBP_ERR_INVALID_ARG, "n_ensemble must be 0 (off) or in [1, 4096]%s");
+        if (o->ensemble_thin < 1) return fail(GBP_ERR_INVALID_ARG, "ensemble_thin must be >= 1%s");
+        if (!c->ens_k || !c->ens_edges || !c->ens_sigma || !c->ens_misfit || !c->ens_seen)
+            return fail(GBP_ERR_INVALID_ARG, "ens_k, ens_edges, ens_sigma, ens_misfit and ens_seen come together, with n_ensemble >= 1%s");
+        if (!c->hitmap)
+            return fail(GBP_ERR_INVALID_ARG, "the ensemble (ens_k ...) needs the hit map: it is settled with its dwell times%s");
     }
     const void* need[] = {c->data, c->height, c->log_mean_prior, c->k, c->edges, c->sigma, c->rel, c->add, c->pred, c->J, c->prior,
                           c->like, c->misfit, c->action, c->k_r, c->nl_a, c->nl_b, c->nl_c, c->edges_r, c->sigma_r, c->thk_r, c->rel_p,
@@ -2922,7 +2973,7 @@ gbp_status gbp_rj_accept(const gbp_rj_options* o, const gbp_rj_chains* c, int64_
     if (st != GBP_OK || c->B == 0) return st;
     const int n_packed = (c->B + 7) / 8, n_deep = o->max_layers > 8 ? (c->B + 63) / 64 : 0;      // (deep: scanning workgroups of 64 chains)
     const size_t lds8 = (size_t)8 * o->n_channels * sizeof(double), lds_deep = rj::Lds::bytes(o->max_layers, o->n_channels);
-    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr;     // (the extras' code is in instantiations of its own)
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr || c->ens_k != nullptr;     // (the extras' code is in instantiations of its own)
     hipLaunchKernelGGL(units ? rj::k_rj_accept8<true> : rj::k_rj_accept8<false>, dim3(n_packed + n_deep), dim3(64),
                        n_deep ? std::max(lds8, lds_deep) : lds8, (hipStream_t)stream, rj::extend(*o), *c, (uint32_t)iteration, accumulate, n_packed);
     GBP_HIP(hipGetLastError());
@@ -3342,7 +3393,7 @@ static gbp_status rj_run_lockstep(const gbp_fdem_system* sys, const gbp_td_opera
                 const size_t lds = std::max((size_t)8 * o->n_channels * sizeof(double), n_deep ? rj::Lds::bytes(K, o->n_channels) : (size_t)0);
                 const int32_t* cur = t.flags + (size_t)(it & 1) * nB;
                 int32_t* nxt = t.flags + (size_t)((it + 1) & 1) * nB;
-                const bool units = t.c.unit_hist != nullptr || t.c.first_hist != nullptr || t.c.data_hist != nullptr;
+                const bool units = t.c.unit_hist != nullptr || t.c.first_hist != nullptr || t.c.data_hist != nullptr || t.c.ens_k != nullptr;
                 hipLaunchKernelGGL(units ? rj::k_rj_step8<true> : rj::k_rj_step8<false>, dim3(n_packed + n_deep), dim3(64), lds, t.q, rj::extend(t.o),
                                    t.c, (uint32_t)iter, accumulate, n_packed, cur, nxt);
                 return GBP_OK;
@@ -3475,7 +3526,7 @@ gbp_status gbp_rj_flush_posteriors(const gbp_rj_options* o, const gbp_rj_chains*
 {
     gbp_status st = rj_check(o, c);
     if (st != GBP_OK || c->B == 0 || !c->hitmap) return st;
-    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr;
+    const bool units = c->unit_hist != nullptr || c->first_hist != nullptr || c->data_hist != nullptr || c->ens_k != nullptr;
     hipLaunchKernelGGL(units ? rj::k_rj_flush<true> : rj::k_rj_flush<false>, dim3(c->B), dim3(64), 0, (hipStream_t)stream, rj::extend(*o), *c);
     GBP_HIP(hipGetLastError());
     return GBP_OK;

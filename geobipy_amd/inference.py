@@ -232,6 +232,52 @@ def data_posteriors_argument(arg):
     return dict(n_bins=nb, half_width=hw, misfit_half_width=mhw, scale=d.get("scale"))
 
 
+def check_ensemble(n_keep, thin):
+    """(n_keep, thin) of the posterior ensemble, refused unless 1 <= n_keep <= 4096 and thin >= 1, both integers
+    (gbp_rj_options.n_ensemble, ensemble_thin)."""
+    if isinstance(n_keep, bool) or not isinstance(n_keep, (int, np.integer)) or not 1 <= int(n_keep) <= 4096:
+        raise ValueError("ensemble: n_keep must be an integer in [1, 4096], got %r" % (n_keep,))
+    if isinstance(thin, bool) or not isinstance(thin, (int, np.integer)) or not 1 <= int(thin) <= 0x7fffffff:
+        raise ValueError("ensemble: thin must be an integer >= 1, got %r" % (thin,))
+    return int(n_keep), int(thin)
+
+
+def ensemble_argument(arg, n_markov_chains=None, reference_schedule=False):
+    """``ensemble`` keyword of the samplers -> None (off) or dict(n_keep, thin), checked.  ``arg``: N (= n_keep) or
+    dict(n_keep=256, thin=None); ``thin=None`` is ceil(n_markov_chains / n_keep) under the reference's schedule (the ensemble then
+    spans the whole chain) and refused otherwise: without the schedule nobody knows how many samples will be taken."""
+    if arg is None or arg is False:
+        return None
+    if isinstance(arg, dict):
+        unknown = set(arg) - {"n_keep", "thin"}
+        if unknown:
+            raise ValueError("ensemble: unknown keys %s" % sorted(unknown))
+        n_keep, thin = arg.get("n_keep", 256), arg.get("thin")
+    else:
+        n_keep, thin = arg, None
+    n_keep, _ = check_ensemble(n_keep, 1)
+    if thin is None:
+        if not reference_schedule or not n_markov_chains or int(n_markov_chains) < 1:
+            raise ValueError("ensemble: thin is required without reference_schedule (and n_markov_chains)")
+        thin = -(-int(n_markov_chains) // n_keep)
+    n_keep, thin = check_ensemble(n_keep, thin)
+    return dict(n_keep=n_keep, thin=thin)
+
+
+def ensemble_slots(seen, dwell, thin, n_keep):
+    """The slots one settle fills: a model settled with weight ``dwell`` after ``seen`` samples covers the samples seen .. seen +
+    dwell - 1; sample n is kept iff n % thin == 0 and n // thin < n_keep, in slot n // thin.  Returns range(first, last + 1) with
+    first = ceil(seen / thin), last = min(n_keep - 1, (seen + dwell - 1) // thin) -- empty when dwell == 0 or nothing is kept (the
+    device sampler's arithmetic, csrc/gbp_rjmcmc.h ensemble_add)."""
+    seen, dwell, thin, n_keep = int(seen), int(dwell), int(thin), int(n_keep)
+    if seen < 0 or dwell < 0 or thin < 1 or n_keep < 1:
+        raise ValueError("ensemble_slots: need seen >= 0, dwell >= 0, thin >= 1, n_keep >= 1")
+    if dwell == 0:
+        return range(0)
+    first, last = -(-seen // thin), min(n_keep - 1, (seen + dwell - 1) // thin)
+    return range(first, max(first, last + 1))
+
+
 def unit_means(edges, values, z0, z1):
     """(dz, S, T) of the unit [z0, z1] of the model (interior interface depths ``edges`` ascending, layer conductivities ``values``):
     layer l spans [top_l, bot_l) with top_0 = 0, bot_{k-1} = +inf; ov_l = max(0, min(bot_l, z1) - max(top_l, z0)); conductance
@@ -276,13 +322,17 @@ class Posteriors:
 
     def __init__(self, max_cells, max_edge, min_width, value_mean, factor=10.0, n_value_bins=250, ratio=0.5,
                  relative_error_bounds=None, additive_error_bounds=None, n_error_bins=99, height_edges=None, geometry_edges=None,
-                 units=None, unit_kinds=("arithmetic", "harmonic"), first=None, data=None):
+                 units=None, unit_kinds=("arithmetic", "harmonic"), first=None, data=None, ensemble=None):
         """``units`` [M, 2] (top, bottom; m below the surface), ``unit_kinds`` and ``first`` = (thresholds S/m, directions +-1): the sampled
         unit posteriors (``unit_means`` / ``first_layer`` state the rule) -- ``unit_hist`` [Q, n_value_bins, M], ``first_hist``
         [T, n_depth_bins], ``first_none`` [T].
 
         ``data`` = dict(observed [N], scale [N], n_bins=64, half_width=8.0, misfit_half_width=2.0): the data-space posteriors
-        (``update_data`` states the rule) -- ``data_hist`` [n_bins, N], ``misfit_hist`` [n_bins]; ``update(..., predicted=, misfit=)``."""
+        (``update_data`` states the rule) -- ``data_hist`` [n_bins, N], ``misfit_hist`` [n_bins]; ``update(..., predicted=, misfit=)``.
+
+        ``ensemble`` = dict(n_keep=, thin=): the posterior ensemble, recorded per ITERATION (``update_ensemble`` states the rule) --
+        ``ens_k`` [n_keep] (0: empty), ``ens_edges`` / ``ens_sigma`` [n_keep, max_cells] (+inf / NaN padded), ``ens_misfit``
+        [n_keep], ``ens_seen``."""
         self.ratio = ratio
         # height (Point.set_z_posterior :1010-1017): the cells of the uniform prior, when the height is sampled
         self.height_edges = None if height_edges is None else np.asarray(height_edges, dtype=np.float64)
@@ -333,7 +383,33 @@ class Posteriors:
             self.data_hist = np.zeros((nb, self.observed.size), dtype=np.int64)
             self.misfit_hist = np.zeros(nb, dtype=np.int64)
 
+        # posterior ensemble: every thin-th update, in order, up to n_keep (csrc/gbp_rjmcmc.h ensemble_add in run lengths)
+        self.ens_n_keep, self.ens_thin, self.ens_seen = 0, 1, 0
+        if ensemble is not None:
+            self.ens_n_keep, self.ens_thin = check_ensemble(ensemble["n_keep"], ensemble["thin"])
+        self.ens_k = np.zeros(self.ens_n_keep, dtype=np.int64)
+        self.ens_edges = np.full((self.ens_n_keep, int(max_cells)), np.inf)
+        self.ens_sigma = np.full((self.ens_n_keep, int(max_cells)), np.nan)
+        self.ens_misfit = np.zeros(self.ens_n_keep)
+
+    def update_ensemble(self, edges, values, misfit=None):
+        """Adds one sampled model (weight 1) to the ensemble: sample n = ens_seen is kept iff n % thin == 0 and n // thin < n_keep, in
+        slot n // thin -- its k = len(values), its k - 1 interface depths then +inf, its k conductivities then NaN, its misfit."""
+        if self.ens_n_keep == 0:
+            return
+        n = self.ens_seen
+        if n % self.ens_thin == 0 and n // self.ens_thin < self.ens_n_keep:
+            s, k = n // self.ens_thin, len(values)
+            self.ens_k[s] = k
+            self.ens_edges[s], self.ens_sigma[s] = np.inf, np.nan
+            self.ens_edges[s, :k - 1] = np.asarray(edges, dtype=np.float64)[:k - 1]
+            self.ens_sigma[s, :k] = values
+            self.ens_misfit[s] = 0.0 if misfit is None else misfit
+        self.ens_seen = n + 1
+
     def reset(self):
+        self.ens_k[:] = 0
+        self.ens_seen = 0
         for a in (self.n_cells, self.edges, self.values, self.relative_error, self.additive_error, self.height, self.unit_hist,
                   self.first_hist, self.first_none, self.data_hist, self.misfit_hist) + tuple(self.geometry.values()):
             a[:] = 0
@@ -400,6 +476,8 @@ class Posteriors:
         ``geom``: sampled scalars of the loop pair; ``predicted`` [N] / ``misfit``: the state's prediction and chi^2 (data-space posteriors)."""
         if self.data_n_bins and (predicted is not None or misfit is not None):
             self.update_data(predicted, misfit)
+        if self.ens_n_keep:
+            self.update_ensemble(edges, values, misfit)
         for n_, v_ in (geom or {}).items():
             e_ = self.geometry_edges.get(n_)
             if e_ is not None and e_[0] <= v_ <= e_[-1]:

@@ -15,7 +15,10 @@ LN2 = 0.6931471805599453
 
 # histogram-type chain state: summed over the used chains (the hit map goes through the kernel, the rest are small)
 SUMMED = ("k_hist", "edge_hist", "rel_hist", "add_hist", "height_hist", "unit_hist", "first_hist", "first_none",
-          "data_hist", "misfit_hist")
+          "data_hist", "misfit_hist", "ens_seen")
+# the posterior ensemble [rows, n_keep, ...]: a sounding's is the concatenation over its C chains, [S, C * n_keep, ...] in chain order,
+# with ens_k = 0 (empty) in the slots of the chains that are not used
+ENSEMBLE = ("ens_k", "ens_edges", "ens_sigma", "ens_misfit")
 # per-chain state [rows, ...] a pooled view shows, taken from the representative chain: what survey_run.SurveyRun's run_block / summaries / payload and
 # unit_posteriors.products read (the sampler's working state -- Jacobians, Cholesky factors, proposals -- is not part of the view)
 PER_CHAIN = ("chain_id", "data", "observed", "height", "height0", "best_height", "log_mean_prior", "k", "edges", "sigma", "rel", "add", "prior",
@@ -92,7 +95,7 @@ def pool_reference(maps, C, use=None, half_width=1.0):
 class Pooled:
     """A finished block of S * C chains (row s * C + c: replicate c of sounding s) seen as S soundings: the names ``survey_run.SurveyRun`` (run_block, summaries, payload) and
     ``unit_posteriors.products`` / ``data_posteriors.products`` read of a sampler -- ``t`` (the chain state by the names of gbp_rj_chains),
-    ``hitmap``, ``unit_hist``, ``first_hist``, ``first_none``, ``data_hist``, ``misfit_hist``, ``observed``, ``B`` -- and the sampler's own attributes for the rest.  ``t`` holds the names of
+    ``hitmap``, ``unit_hist``, ``first_hist``, ``first_none``, ``data_hist``, ``misfit_hist``, ``ens_k`` ... (``ENSEMBLE``), ``observed``, ``B`` -- and the sampler's own attributes for the rest.  ``t`` holds the names of
     ``PER_CHAIN``, ``SUMMED`` and ``SHARED`` (None where the sampler has none), not the sampler's working state.
 
     ``use`` [S, C]: the chain burned in -- under the reference's schedule its status is not "failed" (2); without the schedule every
@@ -127,6 +130,13 @@ class Pooled:
         self.half_width = float(dc.value_half_width if sampler else t.get("value_half_width", 1.0))
         self._pool, self._diagnostics = None, None
         out = {}
+        for name in ENSEMBLE:
+            v = t.get(name)
+            if v is not None:
+                v = v.view((S, C * v.shape[1]) + tuple(v.shape[2:]))
+                if name == "ens_k":
+                    v = v * use.to(v.dtype).repeat_interleave(v.shape[1] // C, dim=1)
+            out[name] = v
         for name in PER_CHAIN + SUMMED + SHARED + ("hitmap",):
             v = t.get(name)
             if v is None or name in SHARED:

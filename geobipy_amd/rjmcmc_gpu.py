@@ -87,7 +87,8 @@ class DeviceChains:
                  first_chain=0, forward_waves=2, reference_schedule=False, burn_in_min_iterations=5000, hankel_eps_ppm=None,
                  min_altitude=None, add_scale=None, rel_group=None, add_group=None, chain_id=None, extra_log_prior=0.0,
                  additive_independent=False, trace_every=0, trace_length=None, ignore_likelihood=False, units=None,
-                 unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), surface=None, data_posteriors=None, **options):
+                 unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), surface=None, data_posteriors=None, ensemble=None,
+                 **options):
         """``ignore_likelihood``: sample the PRIOR alone (the reference's option of that name, Inference1D.py:394, 519, 551, 596: no data
         term in the stochastic-Newton step, likelihood constant).  The reference's own run of it ends at the first birth or death, where
         Model.proposal_probabilities calls ``observation.sensitivity`` on None (model/Model.py:619); here the observation is left out
@@ -116,8 +117,14 @@ class DeviceChains:
         histogram of every active channel's residual (predicted - observed) / scale on +-half_width, ``data_hist`` int32
         [B, n_bins, N], and to the histogram of log10(chi^2 / active channels) on +-misfit_half_width decades, ``misfit_hist`` int32
         [B, n_bins]; the end cells hold what lies beyond.  ``scale`` [B, N] (or [N]): the unit of the residual axis, default each
-        channel's standard deviation at the chain's INITIAL error levels (``channel_std``: what the starting misfit is computed with)."""
-        from .inference import OPTION_DEFAULTS, data_posteriors_argument
+        channel's standard deviation at the chain's INITIAL error levels (``channel_std``: what the starting misfit is computed with).
+
+        Posterior ensemble (needs ``hitmap=True``; ``ensembles.from_chains`` reads it).  ``ensemble``: N or dict(n_keep=256, thin=None) --
+        every ``thin``-th accumulated sample of every chain is kept on the device, in chain order, up to ``n_keep`` (1 .. 4096) per
+        chain: ``ens_k`` int32 [B, n_keep] (0: empty slot), ``ens_edges`` / ``ens_sigma`` [B, n_keep, K] (padded with +inf / NaN),
+        ``ens_misfit`` [B, n_keep], ``ens_seen`` int32 [B] (include/geobipy_amd.h states the rule).  ``thin=None``:
+        ceil(n_markov_chains / n_keep) under ``reference_schedule``, required otherwise."""
+        from .inference import OPTION_DEFAULTS, data_posteriors_argument, ensemble_argument
         o = dict(OPTION_DEFAULTS)
         o.update({k: v for k, v in options.items() if v is not None})
         self.o = o
@@ -134,6 +141,10 @@ class DeviceChains:
                 if len(shape) != 2 or sc_.shape not in (shape[1:], shape):
                     raise ValueError("data_posteriors: scale must be [N] or [B, N]")
                 self._data_scale_given = np.array(np.broadcast_to(sc_, shape))
+        # posterior ensemble: refused here too
+        ens = ensemble_argument(ensemble, n_markov_chains=o.get("n_markov_chains"), reference_schedule=reference_schedule)
+        if ens is not None and not hitmap:
+            raise ValueError("ensemble needs hitmap=True: it is settled with the hit map's dwell times")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.system = system
         f64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64).to(self.device).contiguous()
@@ -251,6 +262,11 @@ class DeviceChains:
             ro.n_data_bins, ro.data_half_width, ro.misfit_half_width = dp["n_bins"], dp["half_width"], dp["misfit_half_width"]
         D_ = int(ro.n_data_bins)
         self.n_data_bins, self.data_half_width, self.misfit_half_width = D_, float(ro.data_half_width), float(ro.misfit_half_width)
+        # posterior ensemble (gbp_rj_options.n_ensemble, ensemble_thin; the host rule: inference.Posteriors(ensemble=...))
+        if ens is not None:
+            ro.n_ensemble, ro.ensemble_thin = ens["n_keep"], ens["thin"]
+        E_ = int(ro.n_ensemble)
+        self.n_ensemble, self.ensemble_thin = E_, int(ro.ensemble_thin)
         self._o = ro
         B, N, dev = self.B, self.N, self.device
         z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
@@ -281,7 +297,9 @@ class DeviceChains:
             first_hist=z(B, T_, self.n_depth_bins, dt=i32) if T_ else None, first_none=z(B, T_, dt=i32) if T_ else None,
             data_scale=(torch.ones(B, N, dtype=torch.float64, device=dev) if self._data_scale_given is None else f64(self._data_scale_given)) if D_ else None,
             data_hist=z(B, D_, N, dt=i32) if D_ else None, misfit_scale=torch.ones(B, dtype=torch.float64, device=dev) if D_ else None,
-            misfit_hist=z(B, D_, dt=i32) if D_ else None)
+            misfit_hist=z(B, D_, dt=i32) if D_ else None,
+            ens_k=z(B, E_, dt=i32) if E_ else None, ens_edges=z(B, E_, K) if E_ else None, ens_sigma=z(B, E_, K) if E_ else None,
+            ens_misfit=z(B, E_) if E_ else None, ens_seen=z(B, dt=i32) if E_ else None)
         self._bind()
         self.iteration = 0
         self.forward_waves = int(forward_waves)      # also passed explicitly to the forward calls of the initialisation
@@ -323,7 +341,8 @@ class DeviceChains:
     def __getattr__(self, name):              # chain state by the names of gbp_rj_chains
         t = self.__dict__.get("t")
         if t is not None and name in t:
-            if name in ("hitmap", "unit_hist", "first_hist", "first_none", "data_hist", "misfit_hist") and t[name] is not None:
+            if name in ("hitmap", "unit_hist", "first_hist", "first_none", "data_hist", "misfit_hist", "ens_k", "ens_edges", "ens_sigma",
+                        "ens_misfit", "ens_seen") and t[name] is not None:
                 # a model enters the hit map with its dwell time when it is replaced; settle the current models first
                 with torch.cuda.device(self.device):
                     _lib.check(_lib.load().gbp_rj_flush_posteriors(self._o, self._c, self._stream()))
@@ -519,7 +538,7 @@ class DeviceChains:
         for name in ("prior", "like", "misfit"):
             t[name][r] = t["init_" + name][r]
         for name in ("n_accepted", "acc_mark", "n_zero", "k_hist", "edge_hist", "rel_hist", "add_hist", "hitmap", "hit_dwell", "height_hist", "unit_hist",
-                     "first_hist", "first_none", "data_hist", "misfit_hist"):
+                     "first_hist", "first_none", "data_hist", "misfit_hist", "ens_k", "ens_seen"):
             if t.get(name) is not None:
                 t[name][r] = 0
         if self.solve_height:

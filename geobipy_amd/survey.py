@@ -495,7 +495,7 @@ BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device bloc
 def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min_iterations=5000, check_every=1000,
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
-          first_above=(), first_below=(), replicates=1, data_posteriors=None, **overrides):
+          first_above=(), first_below=(), replicates=1, data_posteriors=None, ensemble=None, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -531,6 +531,11 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     (``DeviceChains(data_posteriors=...)``) -- the statistics of ``data_posteriors.products`` join the per-sounding summaries the same
     way: ``data_residual_*``, ``data_predicted_*``, ``data_exceedance``, ``data_outside``, ``data_total`` [S, N] and ``misfit_median``,
     ``misfit_percentile_<p>``, ``misfit_share_below_one``, ``misfit_outside``, ``misfit_total`` [S].  Need the hit map too.
+    ``ensemble`` (N or dict(n_keep, thin)): the POSTERIOR ENSEMBLE (``DeviceChains(ensemble=...)``; thin defaults to
+    ceil(n_markov_chains / n_keep)) -- the kept models themselves join the per-sounding summaries: ``ensemble_k`` int32 [S, n_keep]
+    (0: empty slot), ``ensemble_edges`` / ``ensemble_sigma`` [S, n_keep, K] (+inf / NaN padded), ``ensemble_misfit`` [S, n_keep] and
+    ``ensemble_thin`` [S]; ``ensembles.realisations`` / ``ensembles.rebin`` take them from there.  Needs the hit map; counted in the
+    default block's payload budget.  The containers are not touched.
     ``replicates`` = C, 1 .. 8 (frequency-domain data): C chains per sounding that differ by their random streams alone
     (``replicates.expand``: replicate 0 walks the chain the sounding walks alone); a block then holds C rows per sounding and is seen
     through ``replicates.Pooled`` -- the containers and the posteriors of the summaries receive the sum over the chains that burned in,
@@ -573,7 +578,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     common = survey_run.sampler_arguments(o, time_domain, seed=seed, device=device, hitmap=hitmap, first_chain=int(rows[0]) + start,
                                           burn_in_min_iterations=burn_in_min_iterations, containers=containers, traces=traces,
                                           units=units is not None, unit_kinds=unit_kinds, first_above=first_above, first_below=first_below,
-                                          data_posteriors=data_posteriors, hankel_eps=hankel_eps)
+                                          data_posteriors=data_posteriors, hankel_eps=hankel_eps, ensemble=ensemble)
+    ens_bytes = survey_run.ensemble_bytes(common["ensemble"]["n_keep"], o["maximum_number_of_layers"]) if "ensemble" in common else 0
     unit_z = None                                   # sampled unit posteriors: exact bounds of every sounding's units, metres below its
     if units is not None:                           # surface, cut at the end of the depth axis
         from .intervals import unit_bounds
@@ -583,7 +589,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     if schedule == "auto":
         schedule = survey_run.auto_schedule(ds.lineNumber, world, containers)
     block = lambda limit=16384: int(chunk) if chunk else survey_run.default_block(
-        o["n_markov_chains"], common.get("trace_every"), hitmap and containers, C_rep, limit)
+        o["n_markov_chains"], common.get("trace_every"), hitmap and containers, C_rep, limit, ensemble_bytes=ens_bytes)
     # wall time by phase (device-synchronised at the phase borders only when a caller asks for it with timings={}: bench.py's
     # ``survey`` object; a normal run never synchronises for this)
     clock = survey_run.PhaseClock(timings)

@@ -13,7 +13,7 @@ from .survey import (BLOCK_PAYLOAD_BUDGET, INTEGER_SUMMARIES, REPLICATE_SUMMARIE
                      _row_fields, _write_line_containers)
 
 # the phase clock's names (bench.py reads them from survey.infer(timings={}))
-PHASES = ("upload_and_initialise", "chains", "pool_replicates", "hitmap_statistics", "unit_posteriors", "data_posteriors", "rows_to_host",
+PHASES = ("upload_and_initialise", "chains", "pool_replicates", "hitmap_statistics", "unit_posteriors", "data_posteriors", "ensemble", "rows_to_host",
           "container_fill", "rows_to_host_overlapped", "container_fill_overlapped", "compress_and_write_tail", "summaries_to_host",
           "summary_file_tail")
 
@@ -64,7 +64,7 @@ def check_request(o, hitmap, replicates):
 
 def sampler_arguments(o, time_domain, seed=None, device=None, hitmap=True, first_chain=0, burn_in_min_iterations=5000, containers=False,
                       traces=1, units=False, unit_kinds=("arithmetic", "harmonic"), first_above=(), first_below=(), data_posteriors=None,
-                      hankel_eps=None):
+                      hankel_eps=None, ensemble=None):
     """The keyword arguments every block's DeviceChains / TdemDeviceChains gets, from the options ``o`` and infer's own arguments
     (``containers``: results containers are written; ``units``: a unit spec was given -- its bounds are per block, SurveyRun.unit_z).
     Touches no device."""
@@ -94,19 +94,31 @@ def sampler_arguments(o, time_domain, seed=None, device=None, hitmap=True, first
         if dp["scale"] is not None:
             raise ValueError("data_posteriors: survey.infer takes no scale (each channel's standard deviation at the initial error levels)")
         common.update(data_posteriors={k_: dp[k_] for k_ in ("n_bins", "half_width", "misfit_half_width")})
+    if ensemble is not None and ensemble is not False:
+        from .inference import ensemble_argument
+        if not hitmap:
+            raise ValueError("ensemble needs the hit map (it is settled with its dwell times)")
+        common.update(ensemble=ensemble_argument(ensemble, n_markov_chains=o.get("n_markov_chains"), reference_schedule=True))
     if hankel_eps is not None:
         common.update({"hankel_eps" if time_domain else "hankel_eps_ppm": float(hankel_eps)})
     return common
 
 
+def ensemble_bytes(n_keep, max_layers):
+    """Bytes of device memory one chain's posterior ensemble takes: n_keep slots of 2 K doubles, a misfit and a layer count, and the
+    chain's sample counter -- n_keep (16 K + 12) + 4 (126 KB at n_keep = 256, K = 30, beside the hit map's 440 KB)."""
+    return int(n_keep) * (16 * int(max_layers) + 12) + 4
+
+
 # ---- block size and schedule --------------------------------------------------------------------------------------------------------
 
-def default_block(n_markov_chains, trace_every, payload_hitmap, replicates, limit=16384):
+def default_block(n_markov_chains, trace_every, payload_hitmap, replicates, limit=16384, ensemble_bytes=0):
     """Default block size: ``limit`` soundings, less when a sounding's posterior payload on the device is large -- full-length traces at
     the reference's default n_markov_chains = 100 000 are 1.8 MB per sounding (29.5 GB for 16 384, plus their host copies): the default
     block keeps traces + hit maps under BLOCK_PAYLOAD_BUDGET.  Chains are keyed by row, so the block size never changes a result.
-    ``trace_every``: the traces' stride (None / 0: none kept); ``payload_hitmap``: the hit maps leave the device for the containers."""
-    per = 0
+    ``trace_every``: the traces' stride (None / 0: none kept); ``payload_hitmap``: the hit maps leave the device for the containers;
+    ``ensemble_bytes``: a chain's posterior ensemble (``ensemble_bytes()``; 0: none kept), counted in the same budget."""
+    per = int(ensemble_bytes)
     if trace_every:
         per += -(-2 * int(n_markov_chains) // int(trace_every)) * 9        # misfit f64 + acceptance u8 per kept entry
     if payload_hitmap:
@@ -286,6 +298,12 @@ class SurveyRun:
             from . import data_posteriors
             with clock.phase("data_posteriors"):
                 named += [(k_, f64(v_) if v_.ndim > 1 else col(v_)) for k_, v_ in data_posteriors.products(dc).items()]
+        if t.get("ens_k") is not None:
+            from . import ensembles
+            with clock.phase("ensemble"):
+                ens = ensembles.from_chains(dc)
+                named += [("ensemble_k", f64(ens.k)), ("ensemble_edges", ens.edges.flatten(1)), ("ensemble_sigma", ens.sigma.flatten(1)),
+                          ("ensemble_misfit", ens.misfit), ("ensemble_thin", col(torch.full_like(t["k"], ens.thin)))]
         if diag is not None:
             named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return named
@@ -530,6 +548,13 @@ def assemble_result(ds, o, dc, named, r, C_rep, iterations_run):
             res[name] = res[name].reshape(-1, G, dc.n_error_bins)
     if C_rep > 1:
         res["chain_mean"] = res["chain_mean"].reshape(-1, C_rep, dc.n_depth_bins)
+    if "ensemble_k" in res:                      # [S, slots] and [S, slots, K]; with replicates the chains' slots one after the other
+        slots = int(dc.n_ensemble) * C_rep
+        res["ensemble_k"] = res["ensemble_k"].reshape(-1, slots).astype(np.int32)
+        res["ensemble_misfit"] = res["ensemble_misfit"].reshape(-1, slots)
+        res["ensemble_thin"] = res["ensemble_thin"].astype(np.int32)
+        for k_ in ("ensemble_edges", "ensemble_sigma"):
+            res[k_] = res[k_].reshape(-1, slots, dc.K)
     n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze
     ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
     res["iterations"] = ran.astype(np.int64)

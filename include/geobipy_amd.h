@@ -413,6 +413,17 @@ typedef struct gbp_rj_options {
     int32_t n_data_bins;         /* 0: off; otherwise 8 .. 256 cells of both axes                                        */
     double data_half_width;      /* > 0 and finite: the residual axis spans +-data_half_width scale units                */
     double misfit_half_width;    /* > 0 and finite: the misfit axis spans +-misfit_half_width decades about misfit_scale */
+    /* Posterior ensemble (chains->ens_k ...): the SAMPLED MODELS themselves, thinned, kept per chain in chain order.  The samples a
+     * chain accumulates are numbered from 0 where its posteriors last started (ens_seen counts them).  A settle of model m with weight
+     * d (its dwell: where the hit map is settled, with the same weight) covers the samples n = ens_seen .. ens_seen + d - 1.  Sample n
+     * is kept iff n % ensemble_thin == 0 and n / ensemble_thin < n_ensemble, and goes to slot n / ensemble_thin.  One settle therefore
+     * writes m into the slots ceil(ens_seen / thin) .. min(n_ensemble - 1, floor((ens_seen + d - 1) / thin)); then ens_seen += d.
+     * Samples past the last slot are dropped: no ring, no replacement.  After gbp_rj_flush_posteriors ens_seen equals the sum of
+     * k_hist, and min(n_ensemble, ceil(ens_seen / thin)) slots are filled.  The burn-in reset zeroes ens_k and ens_seen.  The entry
+     * points refuse n_ensemble outside 1 .. 4096, ensemble_thin < 1, the arrays without hitmap (they share hit_dwell), and one
+     * array without the others. */
+    int32_t n_ensemble;          /* 0: off; otherwise 1 .. 4096 slots per chain                                          */
+    int32_t ensemble_thin;       /* >= 1: every ensemble_thin-th sample is kept                                          */
 } gbp_rj_options;
 
 typedef struct gbp_rj_chains {
@@ -489,6 +500,12 @@ typedef struct gbp_rj_chains {
                                       layout of the interval marginals, int32                                               */
     const double *misfit_scale;    /* [B]  > 0: what the misfit is divided by (the chain's number of active channels)       */
     int32_t *misfit_hist;          /* [B, n_data_bins]  log10(misfit / misfit_scale) of the sampled models                  */
+    /* posterior ensemble (opt->n_ensemble, ensemble_thin; needs hitmap: it shares hit_dwell and is zeroed where it is; all NULL: off) */
+    int32_t *ens_k;                /* [B, n_ensemble]  layer count of the slot's model; 0: the slot is empty                */
+    double *ens_edges;             /* [B, n_ensemble, K]  the k - 1 interface depths of the slot's model, then +inf         */
+    double *ens_sigma;             /* [B, n_ensemble, K]  its k conductivities, then NaN                                    */
+    double *ens_misfit;            /* [B, n_ensemble]  its misfit (chi^2: what the data-space posteriors bin at the same site) */
+    int32_t *ens_seen;             /* [B]  accumulated samples already settled since the posteriors last started            */
 } gbp_rj_chains;
 
 /* The three host-logic stages of one iteration, exposed separately for the tests ... */
@@ -698,6 +715,25 @@ gbp_status gbp_hitmap_classes(int B, int n_value, int n_depth, const int32_t *hi
  * M in the place of n_depth): the same kernels instantiated on the count type, the same bits on the same counts (counts < 2^53). */
 gbp_status gbp_hitmap_intervals(int B, int n_value, int n_depth, int M, const int32_t *hitmap, const int32_t *lo, const int32_t *hi,
                                 int64_t *out, void *stream);
+/* Two kernels on a finished posterior ensemble (gbp_rj_chains.ens_k, ens_edges, ens_sigma; csrc/gbp_ensemble.h):
+ * gbp_ensemble_raster -- realisations on a depth axis: out[b, r, c] (f64 [B, R, n_depth]) = the conductivity of the layer of slot
+ * slots[r] of chain b that holds z[c], layer = #{l < k - 1 : edges[l] <= z[c]} (the hit map's rule: an interface exactly at a cell
+ * centre gives the layer below); a pure gather -- the stored double bit for bit; a whole row is NaN for an empty slot (ens_k == 0) or
+ * a slot outside 0 .. n_ensemble - 1.  slots: DEVICE int32 [R], any order, repeats allowed; z: DEVICE [n_depth], the cell centres.
+ * gbp_ensemble_rebin -- any posterior the sampler could have binned, after the fact: every filled slot, in order, with weight 1,
+ * through the sampler's own accumulators (the same bits), into outputs the entry zeroes first: hitmap int32 [B, n_value, n_depth] on
+ * the axes given (depth cell c spans [c, c + 1) depth_bin_width; NULL: none), unit_hist int32 [B, Q, n_value, n_units] of unit_z
+ * [B, n_units, 2] (DEVICE), unit_kinds the bits of gbp_rj_options.unit_kinds; n_units == 0: none, first_hist int32 [B, n_first, n_depth] and first_none
+ * [B, n_first] of first_threshold / first_direction (HOST arrays of n_first values; 0: none).  log_mean_prior: DEVICE [B].
+ * Both: 1 <= n_ensemble <= 4096, 1 <= K <= 64; GBP_ERR_INVALID_ARG for bad sizes, axes, units or thresholds and NULL pointers, every
+ * check before any launch; B == 0 launches nothing. */
+gbp_status gbp_ensemble_raster(int B, int n_ensemble, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma, int R,
+                               const int32_t *slots, int n_depth, const double *z, double *out, void *stream);
+gbp_status gbp_ensemble_rebin(int B, int n_ensemble, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                              const double *log_mean_prior, int n_value, double value_half_width, int n_depth, double depth_bin_width,
+                              int32_t *hitmap, int n_units, int unit_kinds, const double *unit_z, int32_t *unit_hist, int n_first,
+                              const double *first_threshold, const int32_t *first_direction, int32_t *first_hist, int32_t *first_none,
+                              void *stream);
 gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                    int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                    void *stream);
