@@ -153,6 +153,7 @@ SIGNATURES = {
     "gbp_sibson_plan_destroy": (None, [c_void_p]),
     "gbp_sibson_plan_query": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int64), c_void_p]),
     "gbp_sibson_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gbp_sibson_pool": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "gbp_elevation_resample": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                        c_void_p]),
     "gbp_debug_math": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_void_p]),

@@ -2025,6 +2025,35 @@ extern "C" gbp_status gbp_sibson_apply(const gbp_sibson_plan* p, int C, const do
     return GBP_OK;
 }
 
+// Pixel posteriors (k_sibson_pool): the hit maps of each listed pixel's cover list summed, a neighbour's value axis moved onto the nearest
+// sounding's.  Every refusal comes before the launch; the pooled cells are int32, so the longest list times the caller's bound of a
+// column's total must stay inside it.
+extern "C" gbp_status gbp_sibson_pool(const gbp_sibson_plan* p, int n_pixels, const int32_t* pixels, int n_value, int n_depth,
+                                      const int32_t* maps, const double* u, int64_t max_total, int32_t* pooled, int64_t* clipped, void* stream)
+{
+    if (n_pixels < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: n_pixels must be >= 0%s");
+    if (n_value < 1 || n_depth < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: n_value and n_depth must be >= 1%s");
+    if (n_depth > (1 << 29)) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: n_depth out of range (a row's bytes are a 32-bit lane offset)%s");
+    if (max_total < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: max_total must be >= 0%s");
+    if (n_pixels == 0) return GBP_OK;
+    if (!p) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: plan is NULL%s");
+    if (!pixels || !maps || !pooled) return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: NULL pointer%s");
+    if (p->bands.size() > 1)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: the plan is banded (its lists exceed the list budget); pooling needs the lists of one band%s");
+    if (max_total > 0 && p->longest > 0x7fffffffLL / max_total)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: longest list times max_total exceeds 2^31 - 1, a pooled int32 cell could overflow%s");
+    const int cpl = n_depth > 64 ? 2 : 1;
+    const int64_t tiles = ((int64_t)n_depth + 64 * cpl - 1) / (64 * cpl), lim = 0x7fffffffffffffffLL / 8;
+    if ((int64_t)n_pixels * tiles > 0x7fffffffLL || (int64_t)n_value > lim / n_depth / std::max(p->N, n_pixels))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_sibson_pool: n_pixels * depth tiles or the maps' size out of range%s");
+    hipStream_t st = (hipStream_t)stream;
+    auto kernel = cpl == 2 ? grid::k_sibson_pool<2> : grid::k_sibson_pool<1>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_pixels * tiles)), dim3(256), 0, st, n_pixels, pixels, p->nx, p->ny, n_value, n_depth, (int)tiles,
+                       p->d_ptr, p->d_list, p->d_index, p->d_D, p->max_d2, maps, u, pooled, (long long*)clipped);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 #include "gbp_elev.h"
 
 // Elevation slices (gbp_elev.h): rows on the depth axis onto levels or cells of an elevation axis, one launch per call.

@@ -15,6 +15,9 @@
 //                    destination's own D^2 + 0.25 exceeds max_distance.  The lanes of a wave hold 64 consecutive columns of one
 //                    row of `values` (512 contiguous bytes per load); the list entry is wave-uniform.  A workgroup owns 32
 //                    destinations consecutive in x and 64 columns and transposes through LDS, so the stores run along x.
+//   k_sibson_pool    pixel posteriors: pooled[i, v, c] = the sum over the list of pixel pixels[i] of the int32 hit maps
+//                    maps[list[e], v - d_e, c], each neighbour's value axis moved by whole cells onto the nearest sounding's, and the
+//                    counts that fell off the axis.  Integers: exact whatever the order.  Described at the kernel.
 // The order of every sum is the list's order and nothing else: no atomics on the sums, no partial sums.
 #pragma once
 
@@ -147,6 +150,129 @@ __global__ __launch_bounds__(256) void k_sibson_gather(int C, int nx, int ny, in
 #pragma unroll
         for (int c = g; c < COLS; c += 8)
             if (c0 + c < C) out[(size_t)(c0 + c) * P + o] = tile[c][d];
+    }
+}
+
+// Pixel posteriors: the linear pool of the hit maps of a pixel's list, pooled[i, v, c] = sum over the entries e of maps[s_e, v - d_e, c],
+// for the pixels of a caller's list (any order, repeats allowed).  d_e = (int) rint(u[s_e] - u[r]) clamped to +-n_value, r the pixel's
+// nearest sounding (every sounding's value axis is centred on its own prior mean: u is that centre in value cells), 0 without u.
+// clipped[i, c] = the counts of the rows that fell outside 0 <= v < n_value.  A masked pixel, an empty list and a pixel number outside
+// the raster give zeros.  Integers only: the result does not depend on the order of anything.
+//
+// Workgroup blockIdx.x = i * tiles + t: pixel pixels[i], depth cells 64 CPL t .. + 64 CPL - 1, the depth tile fastest so that the
+// workgroups in flight belong to few neighbouring pixels, which share most of their sources.  Lane l owns the cells c0 + 64 k + l,
+// k < CPL: a (sounding, value row) load is CPL contiguous runs of 256 bytes.  The waves split the value rows in chunks of POOL_ROWS
+// register accumulators and walk the list once per chunk; the entry and its shift are wave-uniform, and a chunk's loads of one entry
+// are issued together (a row outside the axis is loaded from the nearest row inside and not added).  A lane past the last depth cell
+// loads the last cell and stores nothing.  The last wave also sums the clipped rows, lane-local in int64.
+constexpr int POOL_ROWS = 32;
+
+__device__ __forceinline__ int pool_shift(const double* __restrict__ u, double ur, int s, int n_value)
+{
+    if (!u) return 0;
+    const double t = rint(u[s] - ur), lim = (double)n_value;
+    return __builtin_amdgcn_readfirstlane((int)fmin(fmax(t, -lim), lim));    // (wave-uniform: the row addresses stay scalar)
+}
+
+template <int CPL>
+__global__ __launch_bounds__(256) void k_sibson_pool(int n_pixels, const int* __restrict__ pixels, int nx, int ny, int n_value, int n_depth,
+                                                      int tiles, const long long* __restrict__ ptr, const int* __restrict__ list,
+                                                      const int* __restrict__ index, const int* __restrict__ D, double max_d2,
+                                                      const int* __restrict__ maps, const double* __restrict__ u, int* __restrict__ pooled,
+                                                      long long* __restrict__ clipped)
+{
+    const int i = blockIdx.x / tiles, c0 = (blockIdx.x % tiles) * (64 * CPL);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int p = pixels[i];
+    const int* l = list;
+    long long len = 0;
+    double ur = 0.0;
+    if (p >= 0 && p < nx * ny) {
+        const double d = (double)D[p];
+        if (!(d * d + 0.25 > max_d2)) {
+            l = list + ptr[p];
+            len = ptr[p + 1] - ptr[p];
+        }
+        if (u) ur = u[index[p]];
+    }
+    unsigned c[CPL];
+    bool live[CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const int cell = c0 + 64 * k + lane;
+        live[k] = cell < n_depth;
+        c[k] = 4u * (unsigned)min(cell, n_depth - 1);          // (bytes: a 32-bit lane offset beside a scalar row address)
+    }
+    const size_t map_cells = (size_t)n_value * n_depth, row_bytes = (size_t)n_depth * sizeof(int);
+    for (int v0 = wave * POOL_ROWS; v0 < n_value; v0 += 4 * POOL_ROWS) {
+        int acc[POOL_ROWS][CPL];
+#pragma unroll
+        for (int j = 0; j < POOL_ROWS; ++j)
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) acc[j][k] = 0;
+        for (long long e = 0; e < len; ++e) {
+            const int s = l[e];
+            const int lo = v0 - pool_shift(u, ur, s, n_value);            // the source row of the chunk's first row
+            if (lo + POOL_ROWS <= 0 || lo >= n_value) continue;
+            const int* m = maps + (size_t)s * map_cells;
+            int val[POOL_ROWS][CPL];
+            if (lo >= 0 && lo + POOL_ROWS <= n_value) {                  // every row inside the axis: addresses by increments
+                const char* a[CPL];
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) a[k] = (const char*)(m + (size_t)lo * n_depth) + c[k];
+#pragma unroll
+                for (int j = 0; j < POOL_ROWS; ++j)
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) {
+                        val[j][k] = *(const int*)a[k];
+                        a[k] += row_bytes;
+                    }
+#pragma unroll
+                for (int j = 0; j < POOL_ROWS; ++j)
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) acc[j][k] += val[j][k];
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < POOL_ROWS; ++j) {
+                const int* row = m + (size_t)min(max(lo + j, 0), n_value - 1) * n_depth;
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) val[j][k] = *(const int*)((const char*)row + c[k]);
+            }
+#pragma unroll
+            for (int j = 0; j < POOL_ROWS; ++j) {
+                const bool inside = lo + j >= 0 && lo + j < n_value;
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) acc[j][k] += inside ? val[j][k] : 0;
+            }
+        }
+        int* out = pooled + ((size_t)i * n_value + v0) * n_depth;
+#pragma unroll
+        for (int j = 0; j < POOL_ROWS; ++j)
+            if (v0 + j < n_value) {
+#pragma unroll
+                for (int k = 0; k < CPL; ++k)
+                    if (live[k]) *(int*)((char*)(out + (size_t)j * n_depth) + c[k]) = acc[j][k];
+            }
+    }
+    if (wave == 3 && clipped) {
+        long long lost[CPL];
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) lost[k] = 0;
+        if (u)
+            for (long long e = 0; e < len; ++e) {
+                const int s = l[e];
+                const int d = pool_shift(u, ur, s, n_value);
+                if (d == 0) continue;
+                const int a = d > 0 ? n_value - d : 0, b = d > 0 ? n_value : -d;   // source rows a .. b - 1 land outside (|d| <= n_value)
+                const int* m = maps + (size_t)s * map_cells;
+                for (int v = a; v < b; ++v)
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) lost[k] += *(const int*)((const char*)(m + (size_t)v * n_depth) + c[k]);
+            }
+#pragma unroll
+        for (int k = 0; k < CPL; ++k)
+            if (live[k]) clipped[(size_t)i * n_depth + c[k] / 4] = lost[k];
     }
 }
 

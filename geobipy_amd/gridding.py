@@ -69,6 +69,59 @@ def _host(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
+def axis_offsets(log_mean_prior, half_width, n_value):
+    """u [N] float64: the soundings' axis offsets in value cells, ``log10_shift(log_mean_prior) / w`` with w = 2 half_width / n_value,
+    computed once by numpy on the host so that the device only subtracts and rounds."""
+    from .line_products import log10_shift
+    w = 2.0 * float(half_width) / int(n_value)
+    return log10_shift(np.asarray(log_mean_prior, dtype=np.float64)).numpy() / w
+
+
+def _pool_arguments(plan, maps, pixels, log_mean_prior, half_width, max_total, out=None):
+    """The checks of ``SibsonPlan.pool`` that need no device: (pixels int64 [P], u float64 [N] or None, log_mean_prior float64 [N] or
+    None), all on the host."""
+    if not isinstance(maps, torch.Tensor) or maps.ndim != 3:
+        raise TypeError("gbp_sibson_pool: hit maps are a tensor [N, n_value, n_depth]")
+    if maps.dtype != torch.int32:
+        raise TypeError("gbp_sibson_pool: hit maps are int32, not %s" % maps.dtype)
+    if not maps.is_contiguous():
+        raise ValueError("gbp_sibson_pool: hit maps must be contiguous (depth fastest)")
+    N, nv, nz = maps.shape
+    if N != plan.n_soundings or nv < 1 or nz < 1:
+        raise ValueError("gbp_sibson_pool: maps of %d soundings with at least one value and one depth cell are needed, got %r" % (
+            plan.n_soundings, tuple(maps.shape)))
+    P = plan.nx * plan.ny
+    if pixels is None:
+        pix = np.arange(P, dtype=np.int64)
+    else:
+        pix = _host(pixels)
+        if pix.dtype.kind not in "iu" or pix.ndim != 1:
+            raise TypeError("gbp_sibson_pool: pixels are a list [P] of integers (flat pixel numbers), got %s %r" % (pix.dtype, pix.shape))
+        pix = pix.astype(np.int64)
+        if pix.size and (pix.min() < 0 or pix.max() >= P):
+            raise ValueError("gbp_sibson_pool: pixel %d is outside the raster of %d x %d pixels" % (
+                pix[(pix < 0) | (pix >= P)][0], plan.ny, plan.nx))
+    if (log_mean_prior is None) != (half_width is None):
+        raise ValueError("gbp_sibson_pool: log_mean_prior and half_width come together")
+    u = lmp = None
+    if log_mean_prior is not None:
+        lmp = np.array(_host(log_mean_prior), dtype=np.float64)
+        if lmp.shape != (N,) or not np.all(np.isfinite(lmp)):
+            raise ValueError("gbp_sibson_pool: log_mean_prior must hold %d finite values" % N)
+        if not (np.isfinite(float(half_width)) and float(half_width) > 0.0):
+            raise ValueError("gbp_sibson_pool: half_width must be finite and positive")
+        u = axis_offsets(lmp, half_width, nv)
+    if max_total is not None and (int(max_total) != max_total or int(max_total) < 0):
+        raise ValueError("gbp_sibson_pool: max_total is a count, got %r" % (max_total,))
+    if out is not None:
+        for k, shape, dt in (("pooled", (nv, nz), torch.int32), ("clipped", (nz,), torch.int64)):
+            b = out[k]
+            if b.dtype != dt or tuple(b.shape[1:]) != shape or b.shape[0] < pix.size or not b.is_contiguous() or b.device != maps.device:
+                raise ValueError("gbp_sibson_pool: out[%r] must be a contiguous %s buffer [>= %d, %s] beside the maps" % (
+                    k, dt, pix.size, ", ".join(str(s) for s in shape)))
+    return pix, u, lmp
+
+
 class SibsonPlan:
     """The geometry of one grid and one set of soundings: ``index`` (the nearest sounding of every pixel's node), ``distance`` (D) and
     ``count`` (n, the number of pixels covering a pixel), each an int32 ``[ny, nx]`` tensor on the device, and the cover lists the
@@ -128,6 +181,47 @@ class SibsonPlan:
             _lib.check(_lib.load().gbp_sibson_apply(self._handle, C, v.data_ptr(), out.data_ptr(),
                                                     torch.cuda.current_stream(self.device).cuda_stream))
         return out[0] if values.dim() == 1 else out
+
+    def pool(self, maps, pixels=None, log_mean_prior=None, half_width=None, max_total=None, out=None):
+        """Pixel posteriors (gbp_sibson_pool; DESIGN.md 3.19, the host statement of the rule is ``pixel_posteriors.pool_reference``):
+        ``maps`` int32 [N, n_value, n_depth] on the plan's device -> dict(``pooled`` int32 [P, n_value, n_depth], the sum of the maps
+        of each pixel's list; ``clipped`` int64 [P, n_depth], the counts that fell off the value axis; ``log_mean_prior`` [P], the
+        pixel's axis = its nearest sounding's (None without one); ``count`` int32 [P], the entries pooled: the list's length, 0 under
+        the mask).  ``pixels``: flat pixel numbers i * nx + j in any order, repeats allowed; None: every pixel in row-major order.
+        ``log_mean_prior`` [N] (ln S/m, as ``hitmap.products`` takes it) and ``half_width`` come together: every sounding's value
+        axis is centred on its own prior mean, and a neighbour's counts are moved by the nearest whole number of value cells onto the
+        axis of the pixel's nearest sounding, whose own counts are never moved; without them nothing moves.  An entry adds its
+        sounding's counts as they are: a sounding with more samples weighs more, one that never burned in (an empty map) weighs
+        nothing.  ``max_total``: a bound of every column's total the caller knows (a chain's sample count), else found by one more
+        read of the maps; a plan whose longest list times it could pass 2^31 - 1 in a pooled int32 cell is refused, and so is a
+        banded plan.  ``out``: a dict(pooled, clipped) of buffers with room for P pixels to write into (views of them come back)."""
+        pix, u, lmp = _pool_arguments(self, maps, pixels, log_mean_prior, half_width, max_total, out)
+        if maps.device.type != "cuda":
+            raise _lib.NativeLibraryError("SibsonPlan.pool runs on the device (gbp_sibson_pool); there is no host fallback")
+        if maps.device != self.device:
+            raise ValueError("gbp_sibson_pool: the maps are on %s, the plan on %s" % (maps.device, self.device))
+        dev = self.device
+        _, nv, nz = maps.shape
+        P = pix.size
+        if max_total is None:
+            max_total = int(maps.sum(dim=1, dtype=torch.int64).max()) if maps.numel() else 0
+        with torch.cuda.device(dev):
+            pix_d = torch.as_tensor(pix.astype(np.int32)).to(dev)
+            u_d = None if u is None else torch.as_tensor(u).to(dev)
+            if out is None:
+                pooled = torch.empty((P, nv, nz), dtype=torch.int32, device=dev)
+                clipped = torch.empty((P, nz), dtype=torch.int64, device=dev)
+            else:
+                pooled, clipped = out["pooled"][:P], out["clipped"][:P]
+            _lib.check(_lib.load().gbp_sibson_pool(self._handle, P, pix_d.data_ptr(), nv, nz, maps.data_ptr(),
+                                                   None if u_d is None else u_d.data_ptr(), int(max_total), pooled.data_ptr(),
+                                                   clipped.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            where = pix_d.long()
+            near = self.index.reshape(-1)[where].long()
+            d = self.distance.reshape(-1)[where].to(torch.float64)
+            count = torch.where(d * d + 0.25 > self.max_distance_px2, torch.zeros_like(where, dtype=torch.int32), self.count.reshape(-1)[where])
+            lmp_p = None if lmp is None else torch.as_tensor(lmp).to(dev)[near]
+        return dict(pooled=pooled, clipped=clipped, log_mean_prior=lmp_p, count=count)
 
     def close(self):
         if getattr(self, "_handle", None):

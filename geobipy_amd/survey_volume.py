@@ -13,7 +13,7 @@ method (minimum curvature); this one is the Sibson surface.
     python -m geobipy_amd.survey_volume <directory> --dx DX --dy DY [--variables mean percentile_5 ...] [--mask MAX_DISTANCE]
                                         [--depth D | --depth-cells I0 I1 | --elevation-axis DZ [TOP BOTTOM] | --elevation E
                                          | --depth-intervals E0 E1 ... | --elevation-intervals E0 E1 ...]
-                                        [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
+                                        [--pooled] [--block COLUMNS] [--device cuda:0] [--out DIRECTORY]
 
 reads the directory's line containers and their ``<line>.products.npz`` (computed where absent: ``line_products.from_results``) and writes
 ``survey_volume.npz`` (x_edges, y_edges, depth_edges, elevation, count, nearest_distance, the variables' names) and one
@@ -33,6 +33,10 @@ from below and its bottom the deepest common reach.
 With ``--depth-intervals`` / ``--elevation-intervals`` (``from_lines(intervals=...)``) the maps are of UNITS: per variable [M, ny, nx],
 map m the statistic of the marginal posterior of the unit between edges m and m + 1 (the lines' ``interval_*`` products,
 geobipy_amd/intervals.py), in ``survey_volume.intervals.<variable>.npy`` beside ``survey_volume.intervals.npz``.
+
+With ``--pooled`` (``from_lines(pooled=True)``) nothing is gridded: every pixel gets a posterior of its own, the pool of its natural
+neighbours' hit maps through the same plan (geobipy_amd/pixel_posteriors.py), and the variables are the products of that posterior, in
+``survey_volume.pooled.<variable>.npy`` [n_depth, ny, nx].
 """
 import argparse
 import functools
@@ -51,6 +55,11 @@ INTERVALS_AXES_FILE = "survey_volume.intervals.npz"
 
 def volume_path(directory, variable):
     return os.path.join(str(directory), "survey_volume.%s.npy" % variable)
+
+
+def pooled_volume_path(directory, variable):
+    """The file of a variable taken from the pixel posteriors (``from_lines(pooled=True)``): it carries ``pooled``."""
+    return os.path.join(str(directory), "survey_volume.pooled.%s.npy" % variable)
 
 
 def intervals_volume_path(directory, variable):
@@ -185,8 +194,133 @@ def _interval_columns(prod_per_line, name, M):
     return np.concatenate(parts), ndim == {3}
 
 
+def load_maps(path):
+    """(x, y, elevation, hit maps int32 [N, n_value, n_depth], log_mean_prior [N] (ln S/m), half_width, depth_edges) of one line
+    container, on the host: what ``line_products.from_results`` uploads block by block."""
+    from . import hdf
+    arrays, _ = hdf.load_results(path)
+    x = line_products._key(arrays, "/data/x/data", "/data/x")
+    y = line_products._key(arrays, "/data/y/data", "/data/y")
+    if x is None or y is None:
+        raise ValueError("%s holds no /data/x and /data/y" % path)
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    elev = line_products._key(arrays, "/data/elevation/data", "/data/elevation")
+    elev = np.zeros_like(x) if elev is None else np.asarray(elev, dtype=np.float64).reshape(-1)
+    V = line_products.VALUES
+    hm = line_products._key(arrays, V + "/values/data", V + "/values")
+    if hm is None or hm.ndim != 3:
+        raise ValueError("%s holds no conductivity-depth hit maps [N, n_value, n_depth] at %s" % (path, V))
+    v_edges = line_products._key(arrays, V + "/mesh/y/edges/data")
+    d_edges = line_products._key(arrays, V + "/mesh/z/edges/data")
+    rel = line_products._key(arrays, V + "/mesh/y/relative_to/data")
+    N, nv, nz = hm.shape
+    if v_edges is None or d_edges is None or v_edges.size != nv + 1 or d_edges.size != nz + 1:
+        raise ValueError("%s: the hit maps' mesh (%s/mesh/y and /z edges) does not match their shape %r" % (path, V, hm.shape))
+    if x.size != N or elev.size != N:
+        raise ValueError("%s: %d soundings but hit maps for %d" % (path, x.size, N))
+    hw = line_products._uniform_half_width(v_edges)
+    rel = np.zeros(N) if rel is None else np.broadcast_to(np.asarray(rel, dtype=np.float64).reshape(-1), (N,))
+    return x, y, elev, hm, rel * line_products.LN10, hw, np.asarray(d_edges, dtype=np.float64)
+
+
+def pooled_variables(variables, classes=None):
+    """(names, percentiles) of the ``variables`` a pooled volume may hold, checked by name: ``pixel_posteriors.VARIABLES`` and
+    percentile_<p>; the percentiles to ask ``pixel_posteriors.products`` for."""
+    from . import pixel_posteriors as pp
+    pct = []
+    for name in variables:
+        if name.startswith("percentile_"):
+            try:
+                p = float(name[len("percentile_"):])
+            except ValueError:
+                p = float("nan")
+            if not 0.0 < p < 100.0 or pp.percentile_name(p) != name:
+                raise ValueError("%r is not percentile_<p> with p in (0, 100), written as %%g writes it" % name)
+            pct.append(p)
+        elif name not in pp.VARIABLES:
+            raise ValueError("%r cannot be taken from the pixel posteriors (pooled): %s or percentile_<p>" % (name, ", ".join(pp.VARIABLES)))
+        elif name in ("class_probability", "highest_marginal") and classes is None:
+            raise ValueError("%r needs classes=(means, scales)" % name)
+    return list(variables), tuple(pct) if pct else (50.0,)
+
+
+def _pooled_from_lines(paths, dx, dy, variables, max_distance, depth, block, device, out, list_budget_bytes, classes):
+    """``from_lines(pooled=True)``: the variables from the pixel posteriors (geobipy_amd/pixel_posteriors.py), block of pixels by block."""
+    from . import pixel_posteriors as pp
+    names, pct = pooled_variables(variables, classes)
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    files = [f for p in paths for f in line_products.containers(str(p))]
+    if not files:
+        raise ValueError("no results containers under %s" % " ".join(str(p) for p in paths))
+    if int(block) < 1:
+        raise ValueError("block must be positive")
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    lines = [(f,) + load_maps(f) for f in files]
+    d_edges, hw, shape = lines[0][7], lines[0][6], lines[0][4].shape[1:]
+    for ln in lines[1:]:
+        if not np.array_equal(ln[7], d_edges):
+            raise ValueError("%s does not share the depth mesh of %s" % (ln[0], lines[0][0]))
+        if ln[4].shape[1:] != shape or ln[6] != hw:
+            raise ValueError("%s does not share the value axis of %s (%r cells of half width %g)" % (ln[0], lines[0][0], shape[0], hw))
+    nv, nz = shape
+    cells = depth_cells(depth, d_edges)
+    single = depth is not None and not isinstance(depth, slice) and np.size(depth) == 1
+    x, y, elev = (np.concatenate([ln[k] for ln in lines]) for k in (1, 2, 3))
+    lmp = np.concatenate([ln[5] for ln in lines])
+    need = x.size * nv * nz * 4
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free:
+        raise ValueError("pooled: the hit maps of all lines must be resident at once, %d soundings x %d x %d cells x 4 bytes = %d bytes, "
+                         "and the device has %d bytes free" % (x.size, nv, nz, need, free))
+    x_edges, y_edges = gridding.centred_mesh(x, y, dx, dy)
+    plan = gridding.SibsonPlan(x, y, x_edges, y_edges, max_distance=max_distance, device=dev, list_budget_bytes=list_budget_bytes)
+    try:
+        if plan.n_bands > 1:
+            raise ValueError("pooled: the plan is banded (%d bands under list_budget_bytes), and pooling needs every list resident" % plan.n_bands)
+        ny, nx = plan.ny, plan.nx
+        res = dict(x_edges=x_edges, y_edges=y_edges, depth_edges=d_edges[cells.start:cells.stop + 1], x=x, y=y,
+                   elevation=plan.apply(torch.as_tensor(elev).to(plan.device)).cpu().numpy(), count=plan.count.cpu().numpy(),
+                   nearest_distance=plan.distance.cpu().numpy(), variables=np.array(names), pooled=np.bool_(True))
+        if out is not None:
+            os.makedirs(str(out), exist_ok=True)
+            np.savez(os.path.join(str(out), AXES_FILE), **res)
+        maps = torch.cat([torch.as_tensor(np.ascontiguousarray(ln[4], dtype=np.int32)).to(dev) for ln in lines])
+        ncell, P = cells.stop - cells.start, nx * ny
+        flats = {}
+        for name in names:
+            K = () if name != "class_probability" else (len(classes[0]),)
+            shape = K + (() if single else (ncell,)) + (ny, nx)
+            dtype = np.int32 if name == "highest_marginal" else np.float64
+            if out is not None:
+                res[name] = np.lib.format.open_memmap(pooled_volume_path(out, name), mode="w+", dtype=dtype, shape=shape)
+            else:
+                res[name] = np.empty(shape, dtype=dtype)
+            flats[name] = res[name].reshape(K + (ncell, P))
+        moments = None                                                                       # total, s1 of every pixel: the entropy's
+        if "entropy" in names:
+            moments = (torch.empty((P, nz), dtype=torch.int64, device=dev), torch.empty((P, nz), dtype=torch.float64, device=dev))
+        for p0, _, r in pp.blocks(plan, maps, lmp, hw, block=int(block), percentiles=pct, credible=90.0, classes=classes, depth_edges=d_edges):
+            b = r["total"].shape[0]
+            if moments is not None:
+                moments[0][p0:p0 + b], moments[1][p0:p0 + b] = r["total"], r["s1"]
+            for name in names:
+                if name != "entropy":
+                    v = r[name][..., cells].cpu().numpy()                                    # [b, cells] or [b, K, cells]
+                    flats[name][..., p0:p0 + b] = np.moveaxis(v, 0, -1)
+        if moments is not None:
+            flats["entropy"][:] = pp.entropy(moments[0], moments[1], nv, hw, d_edges)[:, cells].cpu().numpy().T
+        if out is not None:
+            for name in names:
+                res[name].flush()
+    finally:
+        torch.cuda.synchronize(plan.device)
+        plan.close()
+    return res
+
+
 def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None, block=256, device=None, out=None,
-               list_budget_bytes=0, elevation_edges=None, elevation=None, intervals=None, classes=None):
+               list_budget_bytes=0, elevation_edges=None, elevation=None, intervals=None, classes=None, pooled=False):
     """Grid the line products of the containers ``paths`` (a directory, a container or a list of them; the lines in sorted order).
 
     Returns a dict: ``x_edges``, ``y_edges`` (``gridding.centred_mesh`` of all soundings at spacing ``dx``, ``dy``), ``depth_edges``
@@ -216,7 +350,23 @@ def from_lines(paths, dx, dy, variables=("mean",), max_distance=None, depth=None
     ``survey_volume.intervals.<variable>.npy``.  It excludes ``depth``, ``elevation_edges`` and ``elevation``.  A line's saved products
     are used only if they hold interval entries for the identical spec; otherwise the line is computed from its container (``classes``
     = (means, scales) where ``class_probability`` is asked for).  A pixel is NaN for a unit wherever any contributing sounding has no
-    cell of the unit.  Horizons differ from line to line: compute them per line (``from_results``)."""
+    cell of the unit.  Horizons differ from line to line: compute them per line (``from_results``).
+
+    ``pooled=True`` takes the variables from the PIXEL POSTERIORS instead of gridding them (geobipy_amd/pixel_posteriors.py, DESIGN.md
+    3.19): every pixel's posterior is the pool of its natural neighbours' hit maps through the same plan, and ``mean``, ``median``,
+    ``mode``, ``percentile_<p>``, ``credible_low`` / ``_high`` / ``_range`` (90 %), ``entropy``, ``class_probability`` and
+    ``highest_marginal`` (with ``classes``) and ``clipped_share`` are the products of that posterior; any other name is refused.  The
+    hit maps of all lines are read from the containers and must be resident on the device at once (refused with the figure
+    otherwise); ``block`` PIXELS go through at a time; the files are ``survey_volume.pooled.<variable>.npy`` [n_depth, ny, nx] and
+    ``survey_volume.npz`` holds ``pooled`` = True.  ``depth`` selects cells as above (the entropy stays that of the whole column, and
+    asking for it keeps two more [pixels, n_depth] arrays on the device).  A
+    masked pixel holds what an empty column gives, not NaN.  ``elevation_edges``, ``elevation``, ``intervals`` and a banded plan are
+    refused together with it."""
+    if pooled:
+        if elevation_edges is not None or elevation is not None or intervals is not None:
+            raise ValueError("pooled excludes elevation_edges, elevation and intervals")
+        return _pooled_from_lines(paths, dx, dy, variables, max_distance, depth, block, device, out, list_budget_bytes,
+                                  None if classes is None else line_products.check_classes(*classes))
     on_axis, on_level = elevation_edges is not None, elevation is not None
     if intervals is not None:
         from . import intervals as iv
@@ -322,6 +472,10 @@ def parser():
                          "the soundings reach), snapped outward to multiples of DZ; index 0 is the lowest cell")
     ap.add_argument("--elevation", type=float, default=None, metavar="E", help="one map: the horizontal slice at elevation E (m)")
     line_products.add_interval_arguments(ap)
+    ap.add_argument("--pooled", action="store_true",
+                    help="take the variables from the pixel posteriors (every pixel's pool of its natural neighbours' hit maps) instead of "
+                         "gridding them: survey_volume.pooled.<variable>.npy; mean median mode percentile_<p> credible_low credible_high "
+                         "credible_range entropy clipped_share; --block is then in pixels")
     ap.add_argument("--block", type=int, default=256, help="columns per pass through the device (default 256)")
     ap.add_argument("--device", default=None, help="torch device of the kernels (default cuda:0)")
     ap.add_argument("--out", default=None, help="directory of the outputs (default: the first path's directory)")
@@ -358,6 +512,15 @@ def parse_args(argv=None):
     if len(set(a.variables)) != len(a.variables):
         ap.error("--variables holds a name twice")
     a.intervals = line_products.interval_arguments(ap, a, ("--depth", "--depth-cells", "--elevation-axis", "--elevation"))
+    if a.pooled:
+        for name, v in (("--elevation-axis", a.elevation_axis), ("--elevation", a.elevation), ("--depth-intervals", a.depth_intervals),
+                        ("--elevation-intervals", a.elevation_intervals)):
+            if v is not None:
+                ap.error("--pooled and %s exclude each other" % name)
+        try:
+            pooled_variables(a.variables, classes=None)
+        except ValueError as e:
+            ap.error("--pooled: " + str(e))
     return a
 
 
@@ -371,7 +534,7 @@ def main(argv=None):
         edges = functools.partial(elevation_axis.regular_axis, dz=dz, top=top, bottom=bottom)
     try:
         r = from_lines(a.paths, a.dx, a.dy, variables=tuple(a.variables), max_distance=a.mask, depth=depth, block=a.block, device=a.device,
-                       out=out, elevation_edges=edges, elevation=a.elevation, intervals=a.intervals)
+                       out=out, elevation_edges=edges, elevation=a.elevation, intervals=a.intervals, **({"pooled": True} if a.pooled else {}))
     except ValueError as e:
         print("survey_volume: %s" % e, file=sys.stderr)
         return 1
@@ -393,7 +556,7 @@ def main(argv=None):
         print("%d soundings -> %d x %d pixels, %d depth cells: %s" % (r["x"].size, r["x_edges"].size - 1, r["y_edges"].size - 1,
                                                                       r["depth_edges"].size - 1, os.path.join(out, AXES_FILE)))
     for name in a.variables:
-        print("  %s %r" % (volume_path(out, name), tuple(r[name].shape)))
+        print("  %s %r" % ((pooled_volume_path if a.pooled else volume_path)(out, name), tuple(r[name].shape)))
     return 0
 
 

@@ -805,6 +805,25 @@ void gbp_sibson_plan_destroy(gbp_sibson_plan *plan);
 gbp_status gbp_sibson_plan_query(const gbp_sibson_plan *plan, int32_t *index, int32_t *distance, int32_t *count, int64_t *info, void *stream);
 gbp_status gbp_sibson_apply(const gbp_sibson_plan *plan, int C, const double *values, double *out, void *stream);
 
+/* Pixel posteriors (csrc/gbp_grid.h k_sibson_pool; no reference counterpart: the reference grids finished products): the linear pool
+ * of the hit maps of each listed pixel's natural neighbours, with the plan's lists as they are.  pixels [n_pixels] int32 flat pixel
+ * numbers (i * nx + j; any order, repeats allowed), maps [N, n_value, n_depth] int32 (N the plan's soundings, depth fastest), u [N] fp64
+ * or NULL, pooled [n_pixels, n_value, n_depth] int32, clipped [n_pixels, n_depth] int64 or NULL: DEVICE arrays on the plan's device.
+ * For pixel p = pixels[i] with nearest sounding r = index[p] and list entries s_e:
+ *   d_e = 0 without u, else (int) rint(u[s_e] - u[r]) (one fp64 subtraction, round half to even, clamped to +-n_value): u is a
+ *   sounding's axis offset in value cells, so a neighbour's counts move by whole cells onto the nearest sounding's axis;
+ *   pooled[i, v, c] = sum over e of maps[s_e, v - d_e, c] where 0 <= v - d_e < n_value;
+ *   clipped[i, c] = sum over e of the counts of maps[s_e, :, c] whose row fell outside that range.
+ * A pixel under the plan's mask (D^2 + 0.25 > max_distance_px2) or with an empty list gives zeros in both.  An entry adds its
+ * sounding's counts as they are: more samples weigh more, an empty map weighs nothing.  Integer sums: exact, whatever the order.
+ * The caller guarantees 0 <= pixels[i] < nx * ny (the list is not read on the host; the kernel gives zeros for a number outside).
+ * max_total: the caller's bound of the largest column total of any map; a pooled cell is at most (longest list) * max_total.
+ * GBP_ERR_INVALID_ARG, before any launch: n_pixels < 0, n_value or n_depth < 1, n_depth > 2^29, max_total < 0, a NULL plan, NULL
+ * pixels / maps / pooled, a banded plan (n_bands > 1: its lists are not resident), (longest list) * max_total > 2^31 - 1, sizes out
+ * of range.  n_pixels == 0 launches nothing. */
+gbp_status gbp_sibson_pool(const gbp_sibson_plan *plan, int n_pixels, const int32_t *pixels, int n_value, int n_depth, const int32_t *maps,
+                           const double *u, int64_t max_total, int32_t *pooled, int64_t *clipped, void *stream);
+
 /* Elevation slices: rows on the depth-below-surface axis resampled onto an elevation axis (csrc/gbp_elev.h), the reference's
  * Inference2D.elevationSlice for every row and every elevation at once.  values [R, n_depth] row-major, surface [R / K] (row r belongs
  * to sounding r / K: [N, K, n_depth] class probabilities pass as R = N K rows), depth_edges [n_depth + 1] increasing, all fp64 DEVICE
