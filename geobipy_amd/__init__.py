@@ -17,7 +17,7 @@ from .tdem import TdemBatch, TdemDataPoint, TdemDeviceChains, TdemSystem, Tempes
 from .inference import BatchedInference, Inference1D
 from .rjmcmc_gpu import DeviceChains
 from .gridding import SibsonPlan
-from . import gridding, rjmcmc, survey, survey_volume, synthetic
+from . import gridding, horizons, rjmcmc, survey, survey_volume, synthetic
 
 __all__ = ["CircularLoop", "FdemSystem", "Model", "RectilinearMesh1D", "FdemDataPoint", "FdemBatch", "TdemSystem", "TdemDataPoint", "TempestDataPoint", "TdemBatch", "TdemDeviceChains",
-           "Inference1D", "BatchedInference", "DeviceChains", "SibsonPlan", "gridding", "rjmcmc", "survey", "survey_volume", "synthetic"]
+           "Inference1D", "BatchedInference", "DeviceChains", "SibsonPlan", "gridding", "horizons", "rjmcmc", "survey", "survey_volume", "synthetic"]

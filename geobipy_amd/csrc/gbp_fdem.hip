@@ -2084,3 +2084,71 @@ extern "C" gbp_status gbp_elevation_resample(int mode, int R, int K, int n_depth
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
+
+#include "gbp_horizon.h"
+
+// Horizon tracking (gbp_horizon.h): one workgroup per sequence walks its Markov chain; the Viterbi launch always, the forward-backward
+// launch only when the marginals are asked for.  Every refusal comes before any launch; ptr is not read on the host.
+namespace {
+
+template <int NJ>
+gbp_status horizon_launch(int L, const int64_t* ptr, int S, double dz, const double* score, const double* absent_score, const double* g,
+                          const double* d, double sw, uint16_t* back, int32_t* cell, double* log_score, double* marginal,
+                          double* log_partition, double* scale, hipStream_t st)
+{
+    const size_t lds = horizon::lds_doubles(S) * sizeof(double);
+    const int has_absent = absent_score ? 1 : 0;
+    if (lds > 48 * 1024) {                                                  // (above the default limit of a launch's dynamic LDS)
+        (void)hipFuncSetAttribute((const void*)horizon::k_horizon_viterbi<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)horizon::k_horizon_marginals<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL(horizon::k_horizon_viterbi<NJ>, dim3((unsigned)L), dim3(horizon::THREADS), lds, st, (const long long*)ptr, S, has_absent, dz,
+                       score, absent_score, g, d, sw, (unsigned short*)back, (int*)cell, log_score);
+    GBP_HIP(hipGetLastError());
+    if (marginal) {
+        hipLaunchKernelGGL(horizon::k_horizon_marginals<NJ>, dim3((unsigned)L), dim3(horizon::THREADS), lds, st, (const long long*)ptr, S, has_absent,
+                           dz, score, absent_score, g, d, sw, marginal, log_partition, scale);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" gbp_status gbp_horizon_track(int L, const int64_t* ptr, int64_t total_n, int max_n, int S, double dz, const double* score,
+                                        const double* absent_score, const double* g, const double* d, double switch_cost, uint16_t* back,
+                                        int32_t* cell, double* log_score, double* marginal, double* log_partition, double* scale, void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: L must be >= 0%s");
+    if (S < 1 || S > horizon::MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: S must lie in 1 .. 2048 (the states live in LDS)%s");
+    if (!(dz > 0.0) || !std::isfinite(dz)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: dz must be positive and finite%s");
+    if (!(switch_cost >= 0.0) || !std::isfinite(switch_cost)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: switch must be >= 0 and finite%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < L || max_n < 1 || max_n > total_n || total_n > (int64_t)max_n * L)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: total_n and max_n do not fit L sequences of at least one sounding%s");
+    if (total_n > 0x7fffffffffffffffLL / 8 / (S + 1))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: total_n * (S + 1) out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: ptr is NULL%s");
+    if (!score || !g || !d) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: NULL pointer (score, g, d)%s");
+    if (!back) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: the back workspace is NULL%s");
+    if (!cell || !log_score) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: NULL pointer (cell, log_score)%s");
+    if ((marginal != nullptr) != (log_partition != nullptr) || (marginal != nullptr) != (scale != nullptr))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_track: marginal, log_partition and scale go together (all, or all NULL)%s");
+    hipStream_t st = (hipStream_t)stream;
+#define GBP_HORIZON_CASE(nj) \
+    case nj: return horizon_launch<nj>(L, ptr, S, dz, score, absent_score, g, d, switch_cost, back, cell, log_score, marginal, log_partition, scale, st)
+    switch ((S + 1 + horizon::THREADS - 1) / horizon::THREADS) {
+        GBP_HORIZON_CASE(1);
+        GBP_HORIZON_CASE(2);
+        GBP_HORIZON_CASE(3);
+        GBP_HORIZON_CASE(4);
+        GBP_HORIZON_CASE(5);
+        GBP_HORIZON_CASE(6);
+        GBP_HORIZON_CASE(7);
+        GBP_HORIZON_CASE(8);
+        default: return horizon_launch<horizon::MAX_OWNED>(L, ptr, S, dz, score, absent_score, g, d, switch_cost, back, cell, log_score, marginal,
+                                                           log_partition, scale, st);
+    }
+#undef GBP_HORIZON_CASE
+}

@@ -843,6 +843,36 @@ gbp_status gbp_sibson_pool(const gbp_sibson_plan *plan, int n_pixels, const int3
 gbp_status gbp_elevation_resample(int mode, int R, int K, int n_depth, const double *values, const double *surface,
                                   const double *depth_edges, int E, const double *axis, int c0, int c1, double *out, void *stream);
 
+/* Horizon tracking along lines (csrc/gbp_horizon.h k_horizon_viterbi, k_horizon_marginals; no reference counterpart: the rule is
+ * stated in numpy as horizons.track_reference): the most probable path and the smoothed marginals of a Markov chain over the S depth
+ * cells of a window (uniform width dz, ascending depth) and, where absent_score is given, the extra state "absent" (index S).
+ * L sequences (a line, or a line x a horizon) are concatenated: ptr [L + 1] int64, sequence l holds the rows ptr[l] .. ptr[l + 1] - 1.
+ * score [total_n, S], absent_score [total_n] or NULL (no absent state), g, d [total_n] (of the step n -> n + 1; the entry of a
+ * sequence's last row is unused), all fp64 and finite; DEVICE arrays, ptr included: it is not read on the host, the caller passes
+ * total_n = ptr[L] and max_n = the longest sequence, and guarantees that ptr starts at 0 and grows by at least 1.
+ *   T_n[k] = g[n] * fabs(d[n] - (double)k * dz), k = c' - c: cell c under row n to cell c' under row n + 1; cell <-> absent costs
+ *   switch_cost >= 0; absent -> absent costs 0.
+ *   Viterbi: V_0 = score[0] (and absent_score[0]); V_{n+1}[c'] = score[n + 1, c'] + max(max_c (V_n[c] - T_n[c' - c]), V_n[S] -
+ *   switch_cost); V_{n+1}[S] = absent_score[n + 1] + max(max_c (V_n[c] - switch_cost), V_n[S]).  The maximiser is the first maximum in
+ *   the order c = 0 .. S - 1, then absent (strict > replaces) and is kept as a back-pointer; the path ends at the first maximum of
+ *   V_{N-1} in the same order.  Every operation is one fp64 add, subtract, multiply or compare as written, so cell and log_score
+ *   equal the numpy rule's in every bit.  cell [total_n] int32 (S: absent), log_score [L].
+ *   Marginals (only when marginal, log_partition and scale are given: otherwise the second kernel is not launched): w = exp(score),
+ *   K_n[k] = exp(-T_n[k]), ks = exp(-switch_cost); alpha_0 = w_0 / s_0; alpha_{n+1}[c'] = w[n + 1, c'] (sum_c alpha_n[c] K_n[c' - c]
+ *   + alpha_n[S] ks), c ascending, the absent row sum_c alpha_n[c] ks + alpha_n[S], each normalised by its sum s_{n+1};
+ *   beta_{N-1} = 1, beta_n = K_n (w_{n+1} o beta_{n+1}) / s_{n+1}; marginal [total_n, S + 1 or S] = alpha_n o beta_n renormalised
+ *   (the absent state last, present only with absent_score); scale [total_n] = s_n; log_partition [L] = sum_n ln s_n.  The device's
+ *   exp and the order of its normalising sums differ from numpy's: a few ulp.  Where every transition of a step underflows the
+ *   marginals of the sequence are NaN (the path is not affected).
+ * back: a workspace of total_n * (S + 1) uint16 (the back-pointers; followed on the device).  One 256-thread workgroup per sequence;
+ * LDS: (4 S + 6) doubles.
+ * GBP_ERR_INVALID_ARG, before any launch: L < 0, S < 1 or S > 2048, dz not positive, switch_cost negative or not finite, total_n <
+ * L, max_n < 1 or > total_n, L * max_n < total_n, sizes out of range, a NULL ptr / score / g / d / back / cell / log_score, marginal,
+ * log_partition and scale not all given or all NULL.  L == 0 launches nothing. */
+gbp_status gbp_horizon_track(int L, const int64_t *ptr, int64_t total_n, int max_n, int S, double dz, const double *score,
+                             const double *absent_score, const double *g, const double *d, double switch_cost, uint16_t *back,
+                             int32_t *cell, double *log_score, double *marginal, double *log_partition, double *scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
