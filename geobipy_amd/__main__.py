@@ -64,7 +64,16 @@ def parse(argv=None):
     p.add_argument("--ensemble", type=int, nargs="*", default=None, metavar="N",
                    help="keep a posterior ensemble: N_KEEP [THIN] -- every THIN-th sampled model of every sounding, up to N_KEEP (1 .. 4096, "
                         "default 64; THIN defaults to ceil(n_markov_chains / N_KEEP)): ensemble_* in the summaries")
+    p.add_argument("--ensemble-diagnostics", type=int, nargs="?", const=255, default=None, metavar="MAX_LAG",
+                   help="chain diagnostics of the ensemble (needs --ensemble): effective sample size, split R-hat, autocorrelation time and "
+                        "Monte-Carlo standard error per depth cell, lags up to MAX_LAG (1 .. 255, default 255): ensemble_ess, ensemble_rhat, "
+                        "... in the summaries")
     a = p.parse_args(argv)
+    if a.ensemble_diagnostics is not None:
+        if a.ensemble is None:
+            p.error("--ensemble-diagnostics needs --ensemble")
+        if not 1 <= a.ensemble_diagnostics <= 255:
+            p.error("--ensemble-diagnostics: MAX_LAG in 1 .. 255")
     if a.ensemble is not None:
         if len(a.ensemble) > 2:
             p.error("--ensemble: at most N_KEEP and THIN")
@@ -126,7 +135,8 @@ def main(argv=None):
                        container=None if a.container == "auto" else a.container, data_directory=a.data_directory,
                        data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
                        first_below=tuple(a.first_below), replicates=a.replicates,
-                       data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble)
+                       data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble,
+                       ensemble_diagnostics=False if a.ensemble_diagnostics is None else dict(max_lag=a.ensemble_diagnostics))
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -1512,6 +1513,7 @@ static gbp_status fm_dlogc_launch(const gbp_fdem_system* sys, int B, int Lmax, c
 #include "gbp_hostpack.h"
 #include "gbp_hitmap.h"
 #include "gbp_ensemble.h"
+#include "gbp_ensemble_diag.h"
 
 // Per-depth mean and 5 / 50 / 95 % points of log10 conductivity of B hit maps [B, nv, nz] (depth fastest) -> four [B, nz] arrays
 extern "C" gbp_status gbp_hitmap_statistics(int B, int nv, int nz, const int32_t* hitmap, const double* log_mean_prior, double half_width,
@@ -1828,6 +1830,55 @@ extern "C" gbp_status gbp_ensemble_rebin(int B, int n_ensemble, int K, const int
     hipLaunchKernelGGL(ensemble::k_ensemble_rebin, dim3(B), dim3(64), 0, (hipStream_t)stream, x, c);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
+}
+
+// Chain diagnostics (csrc/gbp_ensemble_diag.h k_series_diagnostics; the rule: include/geobipy_amd.h): one workgroup per (sounding, 64
+// variables).  The checks the two entries share; `entry` names the caller in gbp_last_error.
+static gbp_status series_diagnostics_launch(const char* entry, int source, int B, ensemble::DiagArgs a, bool pointers, void* stream)
+{
+    if (B < 0 || a.n_rows < 1 || a.V < 1) return fail(GBP_ERR_INVALID_ARG, "%s: negative or zero size", entry);
+    if (a.n_rows > 32768) return fail(GBP_ERR_INVALID_ARG, "%s: more than 32 768 rows", entry);
+    if (a.max_lag < 1 || a.max_lag > 255) return fail(GBP_ERR_INVALID_ARG, "%s: max_lag outside 1 .. 255", entry);
+    if (a.M_max < 1 || a.M_max > ensemble::DIAG_MAX_M) return fail(GBP_ERR_INVALID_ARG, "%s: M_max outside 1 .. 16", entry);
+    if (source == ensemble::DIAG_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!pointers || !a.seg_start || !a.seg_m || !a.seg_n || !a.stats || !a.pairs) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    const int64_t blocks = (int64_t)B * ((a.V + 63) / 64);
+    if (blocks > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "%s: B * tiles out of range", entry);
+    const int lds = (int)ensemble::DIAG_LDS_BYTES;
+    auto launch = [&](auto kern) -> gbp_status {
+        static std::atomic<bool> allowed[64];      // per instantiation (the lambda's body is one per kernel) and device: asked for once
+        int dev = 0;
+        GBP_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !allowed[dev].load(std::memory_order_acquire)) {
+            GBP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_release);
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(ensemble::DIAG_WAVES * 64), (size_t)lds, (hipStream_t)stream, a);
+        GBP_HIP(hipGetLastError());
+        return GBP_OK;
+    };
+    return source == ensemble::DIAG_RASTER ? launch(ensemble::k_series_diagnostics<ensemble::DIAG_RASTER>)
+                                           : launch(ensemble::k_series_diagnostics<ensemble::DIAG_PLAIN>);
+}
+
+extern "C" gbp_status gbp_series_diagnostics(int B, int n_rows, int V, const double* x, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                             const int32_t* seg_n, int max_lag, double* stats, int32_t* pairs, double* rho, void* stream)
+{
+    ensemble::DiagArgs a = {};
+    a.n_rows = n_rows; a.V = V; a.x = x; a.M_max = M_max; a.max_lag = max_lag;
+    a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.pairs = pairs; a.rho = rho;
+    return series_diagnostics_launch("gbp_series_diagnostics", ensemble::DIAG_PLAIN, B, a, x != nullptr, stream);
+}
+
+extern "C" gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                               int n_depth, const double* z, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                               const int32_t* seg_n, int max_lag, double* stats, int32_t* pairs, double* rho, void* stream)
+{
+    ensemble::DiagArgs a = {};
+    a.n_rows = n_slots; a.V = n_depth; a.K = K; a.ens_k = ens_k; a.ens_edges = ens_edges; a.ens_sigma = ens_sigma; a.z = z;
+    a.M_max = M_max; a.max_lag = max_lag; a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.pairs = pairs; a.rho = rho;
+    return series_diagnostics_launch("gbp_ensemble_diagnostics", ensemble::DIAG_RASTER, B, a, ens_k && ens_edges && ens_sigma && z, stream);
 }
 
 #include "gbp_grid.h"

@@ -11,7 +11,13 @@ every ``thin``-th sampled model of every chain, in chain order, up to ``n_keep``
                    chosen afterwards (gbp_ensemble_rebin: the sampler's own accumulators with weight 1); the outputs have the shapes
                    ``hitmap.products``, ``hitmap.interval_marginals`` and ``unit_posteriors.products`` take.
 
-There is no host fallback: both refuse tensors that are not on the device (``realisations_reference`` states the raster's rule in numpy).
+``diagnostics``    did the chain run long enough: per depth cell (and for the layer count and the misfit) the integrated
+                   autocorrelation time, the effective sample size, the Monte-Carlo standard error of the posterior mean and a split
+                   R-hat that works with one chain (gbp_ensemble_diagnostics / gbp_series_diagnostics).
+                   ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH`` writes them for a saved ensemble.
+
+There is no host fallback: all refuse tensors that are not on the device (``realisations_reference`` states the raster's rule in numpy,
+``diagnostics_reference`` that of the diagnostics).
 """
 import ctypes
 from collections import namedtuple
@@ -186,6 +192,261 @@ def rebin(ens, n_value_bins, value_half_width, depth, units=None, unit_kinds=("a
     return out
 
 
+STAT_NAMES = ("mean", "sd", "rhat", "tau", "ess", "mcse")
+MAX_LAG, MAX_SEGMENTS, MIN_CHAIN_COUNT = 255, 16, 8
+
+
+def check_max_lag(max_lag):
+    """``max_lag`` (None: 255) as an int in 1 .. 255."""
+    if max_lag is None:
+        return MAX_LAG
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 1 <= int(max_lag) <= MAX_LAG:
+        raise ValueError("max_lag must be an integer in 1 .. %d" % MAX_LAG)
+    return int(max_lag)
+
+
+def lag_count(n, max_lag):
+    """L of segments of length ``n`` (array or int): min(max_lag, n - 1), lowered by one if even, so lags 0 .. L form whole pairs."""
+    L = np.minimum(int(max_lag), np.asarray(n, dtype=np.int64) - 1)
+    return L - (1 - L % 2)
+
+
+def diagnostics_reference(x, seg_start, n, max_lag, dtype=np.float64):
+    """The rule of the chain diagnostics for one sounding, in numpy: ``x`` [n_rows, V], M = len(seg_start) segments of ``n`` rows each
+    (segment m: rows seg_start[m] .. seg_start[m] + n - 1), evaluated in ``dtype``.  Returns {mean, sd, rhat, tau, ess, mcse [V], pairs
+    int32 [V], rho [max_lag + 1, V] (NaN beyond L), pair_sums [(L + 1) / 2, V] (the P_k the walk compares with 0), L}.
+
+    L = min(max_lag, n - 1), lowered by one if even.  Per variable, sums over a segment's rows: mean_m, d = x - mean_m, acov_m(l) =
+    (1/n) sum_{t < n - l} d_t d_{t+l} (biased); W = (1/M) sum_m acov_m(0) n/(n-1); gm = (1/M) sum_m mean_m; Bn = sum_m (mean_m - gm)^2 /
+    (M - 1) (0 when M = 1); vp = W (n-1)/n + Bn; rho_0 = 1, rho_l = 1 - (W - (1/M) sum_m acov_m(l) n/(n-1)) / vp.  Geyer's initial
+    monotone sequence on the pairs P_k = rho_2k + rho_2k+1: S = prev = P_0, pairs = 1; for k = 1, 2, ...: stop unless P_k > 0, else
+    prev = min(prev, P_k), S += prev, pairs += 1.  tau = max(2 S - 1, 1 / log10(M n)), ess = M n / tau, rhat = sqrt(vp / W), sd =
+    sqrt(vp), mcse = sqrt(vp / ess), mean = gm; pairs == (L + 1) / 2: the sum ran into the lag cap.  M == 0 or n < 4: everything NaN,
+    pairs 0.  A variable whose used samples are all one value (compared as stored): mean = it, sd = 0, the rest NaN, pairs 0; one with
+    a non-finite used sample: all NaN, pairs 0."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("diagnostics_reference: x [n_rows, V]")
+    max_lag = check_max_lag(max_lag)
+    starts = [int(q) for q in np.asarray(seg_start).reshape(-1)]
+    M, N, V = len(starts), int(n), x.shape[1]
+    if M > MAX_SEGMENTS:
+        raise ValueError("diagnostics_reference: at most %d segments" % MAX_SEGMENTS)
+    out = {name: np.full(V, np.nan, dtype=dtype) for name in STAT_NAMES}
+    out.update(pairs=np.zeros(V, dtype=np.int32), rho=np.full((max_lag + 1, V), np.nan, dtype=dtype), pair_sums=np.zeros((0, V), dtype=dtype), L=0)
+    if M == 0 or N < 4:
+        return out
+    if min(starts) < 0 or max(starts) + N > x.shape[0]:
+        raise ValueError("diagnostics_reference: a segment leaves the rows 0 .. %d" % (x.shape[0] - 1))
+    L = int(lag_count(N, max_lag))
+    stored = np.stack([x[q:q + N] for q in starts])                    # [M, N, V]
+    xs = stored.astype(dtype)
+    Nf, Mf, one = dtype(N), dtype(M), dtype(1)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        mean_m = xs.sum(axis=1) / Nf                                   # [M, V]
+        d = xs - mean_m[:, None, :]
+        acov = np.stack([(d[:, :N - l] * d[:, l:]).sum(axis=1) / Nf for l in range(L + 1)], axis=1)    # [M, L + 1, V]
+        bessel = Nf / (Nf - one)
+        A = acov.sum(axis=0) / Mf * bessel                             # [L + 1, V]
+        W = A[0]
+        gm = mean_m.sum(axis=0) / Mf
+        Bn = ((mean_m - gm) ** 2).sum(axis=0) / (Mf - one) if M > 1 else np.zeros(V, dtype=dtype)
+        vp = W * (Nf - one) / Nf + Bn
+        rho = one - (W - A) / vp
+        rho[0] = one
+        P = rho[0::2] + rho[1::2]                                      # [(L + 1) / 2, V]
+        S, prev = P[0].copy(), P[0].copy()
+        pairs, open_ = np.ones(V, dtype=np.int32), np.ones(V, dtype=bool)
+        for k in range(1, P.shape[0]):
+            open_ &= P[k] > 0
+            prev = np.where(open_, np.minimum(prev, P[k]), prev)
+            S = np.where(open_, S + prev, S)
+            pairs += open_
+        total = Mf * Nf
+        tau = np.maximum(dtype(2) * S - one, one / np.log10(total))
+        ess = total / tau
+        stats = dict(mean=gm, sd=np.sqrt(vp), rhat=np.sqrt(vp / W), tau=tau, ess=ess, mcse=np.sqrt(vp / ess))
+    flat = stored.reshape(M * N, V)
+    bad = ~np.all(np.isfinite(flat), axis=0)
+    with np.errstate(invalid="ignore"):
+        const = ~bad & (flat.min(axis=0) == flat.max(axis=0))
+    for name in STAT_NAMES:
+        a = np.array(stats[name], dtype=dtype)
+        a[bad | const] = np.nan
+        out[name] = a
+    out["mean"][const] = flat[0, const].astype(dtype)
+    out["sd"][const] = 0
+    pairs[bad | const] = 0
+    rho[:, bad | const] = np.nan
+    out["pairs"], out["pair_sums"], out["L"] = pairs, P, L
+    out["rho"][:L + 1] = rho
+    return out
+
+
+def segments(count_per_chain, slots_per_chain):
+    """Split-chain segments from the filled-slot counts [B, C] of C chains whose ensembles lie one after the other, ``slots_per_chain``
+    slots each (the chains' filled slots are their first ones).  Chains with fewer than 8 filled slots are left out; with C_used >= 1
+    chains left n = min count, N = n // 2, M = 2 C_used, and chain c gives the segments that start at its slots 0 and N (an odd n
+    leaves the last slot unused).  Returns numpy (seg_start int32 [B, 2 C], seg_m int32 [B], seg_n int32 [B], n_chains_used int32 [B]);
+    C_used == 0: M = N = 0."""
+    cnt = np.asarray(count_per_chain)
+    if cnt.ndim != 2 or cnt.shape[1] < 1 or cnt.dtype.kind not in "iu":
+        raise ValueError("segments: integer counts [B, C]")
+    B, C = cnt.shape
+    per = int(slots_per_chain)
+    if per < 1 or 2 * C > MAX_SEGMENTS:
+        raise ValueError("segments: slots_per_chain >= 1 and at most %d chains" % (MAX_SEGMENTS // 2))
+    if cnt.size and (cnt.min() < 0 or cnt.max() > per):
+        raise ValueError("segments: every count must lie in 0 .. slots_per_chain")
+    used = cnt >= MIN_CHAIN_COUNT
+    n_used = used.sum(axis=1).astype(np.int32)
+    n = np.where(used, cnt, np.iinfo(np.int64).max).min(axis=1, initial=np.iinfo(np.int64).max)
+    N = np.where(n_used > 0, n // 2, 0).astype(np.int32)
+    start = np.zeros((B, 2 * C), dtype=np.int32)
+    for b in range(B):
+        chains = np.nonzero(used[b])[0]
+        start[b, 0:2 * chains.size:2] = chains * per
+        start[b, 1:2 * chains.size:2] = chains * per + N[b]
+    return start, (2 * n_used).astype(np.int32), N, n_used
+
+
+def _on_device(tensors, what, entry):
+    """The last check of an entry: shapes, dtypes and values are refused first, whatever device the tensors are on."""
+    for a in tensors:
+        if a.device.type != "cuda":
+            raise _lib.NativeLibraryError("ensembles.%s runs on the device (%s); there is no host fallback" % (what, entry))
+
+
+def _are_tensors(tensors, what, entry):
+    for a in tensors:
+        if not torch.is_tensor(a):
+            raise _lib.NativeLibraryError("ensembles.%s takes torch tensors on the device (%s); there is no host fallback" % (what, entry))
+
+
+def _check_segments(seg_start, seg_m, seg_n, B, n_rows, what):
+    """dtype, shapes and values of a caller's segment lists (the kernel reads seg_start[b, :seg_m[b]] and the rows they name: these
+    checks are what keeps it inside its arrays); any device."""
+    for a in (seg_start, seg_m, seg_n):
+        if a.dtype != torch.int32:
+            raise TypeError("%s: seg_start, seg_m and seg_n are int32" % what)
+    if seg_start.ndim != 2 or seg_start.shape[0] != B or not 1 <= seg_start.shape[1] <= MAX_SEGMENTS or seg_m.shape != (B,) or seg_n.shape != (B,):
+        raise ValueError("%s: seg_start [B, M_max] with 1 <= M_max <= %d, seg_m and seg_n [B]" % (what, MAX_SEGMENTS))
+    if not (seg_start.device == seg_m.device == seg_n.device):
+        raise ValueError("%s: seg_start, seg_m and seg_n live on one device" % what)
+    if B > 0:
+        M_max = seg_start.shape[1]
+        live = torch.arange(M_max, device=seg_start.device)[None, :] < seg_m[:, None]
+        ok = (seg_m >= 0).all() & (seg_m <= M_max).all() & (seg_n >= 0).all() & (~live | ((seg_start >= 0) & (seg_start + seg_n[:, None] <= n_rows))).all()
+        if not bool(ok):
+            raise ValueError("%s: a segment leaves the rows 0 .. %d (or seg_m is outside 0 .. M_max)" % (what, n_rows - 1))
+    return seg_start.contiguous(), seg_m.contiguous(), seg_n.contiguous()
+
+
+def _unpack(stats, pairs, rho, seg_n, max_lag):
+    out = {name: stats[:, i] for i, name in enumerate(STAT_NAMES)}
+    L = torch.clamp(seg_n.to(torch.int64) - 1, max=max_lag)
+    L = L - (1 - L % 2)
+    out["pairs"] = pairs
+    out["truncated"] = (pairs > 0) & (pairs == ((L + 1) // 2)[:, None])
+    if rho is not None:
+        out["rho"] = rho
+    return out
+
+
+def series_diagnostics(x, seg_start, seg_m, seg_n, max_lag=255, return_rho=False):
+    """The chain diagnostics (``diagnostics_reference`` states the rule) of the series ``x`` f64 [B, n_rows, V] on the device: sounding
+    b has seg_m[b] segments of seg_n[b] rows that start at seg_start[b, :seg_m[b]] (int32 device tensors, [B, M_max] and [B]).  Returns
+    {mean, sd, rhat, tau, ess, mcse f64 [B, V], pairs int32 [B, V], truncated bool [B, V] (the sum ran into the lag cap: ess is an
+    over-estimate)} and, with ``return_rho``, rho f64 [B, max_lag + 1, V].  One kernel (gbp_series_diagnostics)."""
+    max_lag = check_max_lag(max_lag)
+    _are_tensors((x, seg_start, seg_m, seg_n), "series_diagnostics", "gbp_series_diagnostics")
+    if x.dtype != torch.float64:
+        raise TypeError("series_diagnostics: x is float64")
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
+        raise ValueError("series_diagnostics: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1")
+    B, n_rows, V = x.shape
+    seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, B, n_rows, "series_diagnostics")
+    _on_device((x, seg_start, seg_m, seg_n), "series_diagnostics", "gbp_series_diagnostics")
+    x, dev = x.contiguous(), x.device
+    stats = torch.empty((B, 6, V), dtype=torch.float64, device=dev)
+    pairs = torch.empty((B, V), dtype=torch.int32, device=dev)
+    rho = torch.empty((B, max_lag + 1, V), dtype=torch.float64, device=dev) if return_rho else None
+    if B > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gbp_series_diagnostics(B, n_rows, V, x.data_ptr(), int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(),
+                                                          seg_n.data_ptr(), max_lag, stats.data_ptr(), pairs.data_ptr(),
+                                                          None if rho is None else rho.data_ptr(), _stream(dev)))
+    return _unpack(stats, pairs, rho, seg_n, max_lag)
+
+
+def check_chains(chains, n_slots):
+    """``chains`` as an int in 1 .. 8 that divides the slot axis."""
+    if isinstance(chains, bool) or not isinstance(chains, (int, np.integer)) or not 1 <= int(chains) <= MAX_SEGMENTS // 2:
+        raise ValueError("chains must be an integer in 1 .. %d" % (MAX_SEGMENTS // 2))
+    if n_slots % int(chains) != 0:
+        raise ValueError("chains = %d does not divide the slot axis (%d slots)" % (int(chains), n_slots))
+    return int(chains)
+
+
+def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho=False):
+    """Did the chains run long enough?  Per sounding and cell of ``depth_edges`` [n_depth + 1] the diagnostics of the series log10
+    conductivity at the cell centre over the kept models (``diagnostics_reference`` states the rule, ``segments`` the split of every
+    chain into two halves; ``chains`` = C: the slot axis holds C chains' ensembles one after the other, as ``replicates.Pooled`` yields
+    them), the series never written to memory (gbp_ensemble_diagnostics).  Returns mean, sd, rhat, tau, ess, mcse f64 [B, n_depth],
+    pairs int32 and truncated bool [B, n_depth], tau_iterations = tau * ens.thin; the same names with the suffixes ``_k`` (the layer
+    count) and ``_misfit`` (log10 of the misfit) [B]; n_chains_used, segment_length, n_segments int32 [B]; ess_min [B], the smallest
+    finite ess over the cells (NaN: none); with ``return_rho`` rho [B, max_lag + 1, n_depth].  ``block``: soundings per launch (None:
+    all).  A cell no interface reached is constant: sd = 0, the rest NaN."""
+    max_lag = check_max_lag(max_lag)
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2:
+        check_chains(chains, ens.k.shape[1])
+    z_np = centres(depth_edges)
+    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
+        raise ValueError("diagnostics: block must be a positive integer")
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    _are_tensors((k, edges, sigma, ens.misfit), "diagnostics", "gbp_ensemble_diagnostics")
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape) or ens.misfit.shape != k.shape:
+        raise ValueError("ensemble: k and misfit [B, n_slots], edges and sigma [B, n_slots, K]")
+    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or not ens.misfit.dtype.is_floating_point:
+        raise TypeError("ensemble: k is int32, edges and sigma are float64, misfit is floating point")
+    B, ns, K = edges.shape
+    C = check_chains(chains, ns)
+    if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
+        raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
+    _on_device((k, edges, sigma, ens.misfit), "diagnostics", "gbp_ensemble_diagnostics")
+    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
+    nd = int(z_np.size)
+    count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
+    start_np, m_np, n_np, used_np = segments(count, ns // C)
+    start, seg_m, seg_n = (torch.as_tensor(a).to(dev) for a in (start_np, m_np, n_np))
+    stats = torch.empty((B, 6, nd), dtype=torch.float64, device=dev)
+    pairs = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    rho = torch.empty((B, max_lag + 1, nd), dtype=torch.float64, device=dev) if return_rho else None
+    if B > 0:
+        z = torch.as_tensor(z_np).to(dev)
+        step = B if block is None else int(block)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, step):
+                s = slice(b0, min(B, b0 + step))
+                _lib.check(lib.gbp_ensemble_diagnostics(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
+                                                        z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), max_lag,
+                                                        stats[s].data_ptr(), pairs[s].data_ptr(), None if rho is None else rho[s].data_ptr(),
+                                                        _stream(dev)))
+    out = _unpack(stats, pairs, rho, seg_n, max_lag)
+    scalars = torch.stack((k.to(torch.float64), torch.log10(ens.misfit.to(torch.float64))), dim=2)
+    two = series_diagnostics(scalars, start, seg_m, seg_n, max_lag=max_lag)
+    for name in STAT_NAMES + ("pairs", "truncated"):
+        out[name + "_k"], out[name + "_misfit"] = two[name][:, 0], two[name][:, 1]
+    thin = int(ens.thin)
+    out["tau_iterations"], out["tau_iterations_k"], out["tau_iterations_misfit"] = out["tau"] * thin, out["tau_k"] * thin, out["tau_misfit"] * thin
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = torch.as_tensor(used_np).to(dev), seg_n, seg_m
+    ess = out["ess"]
+    lowest = torch.where(torch.isfinite(ess), ess, torch.full_like(ess, float("inf"))).min(dim=1).values if nd else torch.full((B,), float("inf"), device=dev)
+    out["ess_min"] = torch.where(torch.isfinite(lowest), lowest, torch.full_like(lowest, float("nan")))
+    return out
+
+
 def save(ens, path):
     """Write an ``Ensemble`` to ``path`` with np.savez_compressed; returns the path."""
     np.savez_compressed(path, **{n: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for n, v in ens._asdict().items()})
@@ -200,3 +461,60 @@ def load(path, device=None):
     if device is not None:
         d = {n: (torch.as_tensor(v).to(device) if n != "thin" else v) for n, v in d.items()}
     return Ensemble(**d)
+
+
+def _parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m geobipy_amd.ensembles",
+                                description="Chain diagnostics (ESS, autocorrelation time, split R-hat) of a saved ensemble; writes <name>.diagnostics.npz")
+    p.add_argument("ensemble", help="an ensemble written by ensembles.save (.npz)")
+    axis = p.add_mutually_exclusive_group(required=True)
+    axis.add_argument("--depth-edges", type=float, nargs="+", metavar="EDGE", help="ascending cell edges [n_depth + 1]")
+    axis.add_argument("--depth-axis", nargs=2, metavar=("N", "WIDTH"), help="N uniform cells of WIDTH starting at 0")
+    p.add_argument("--chains", type=int, default=1, help="replicate chains on the slot axis (default 1)")
+    p.add_argument("--max-lag", type=int, default=None, help="largest lag, 1 .. 255 (default 255)")
+    p.add_argument("--device", default="cuda:0")
+    return p
+
+
+def parse_args(argv=None):
+    """The command line of ``python -m geobipy_amd.ensembles`` as (path, depth_edges, chains, max_lag, device); refuses before any device work."""
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.depth_axis is not None:
+        try:
+            n, w = int(a.depth_axis[0]), float(a.depth_axis[1])
+        except ValueError:
+            p.error("--depth-axis N WIDTH: an integer and a number")
+        if n < 1 or not (np.isfinite(w) and w > 0.0):
+            p.error("--depth-axis: N >= 1 and a finite, positive WIDTH")
+        edges = np.arange(n + 1, dtype=np.float64) * w
+    else:
+        edges = np.asarray(a.depth_edges, dtype=np.float64)
+    try:
+        centres(edges)
+        max_lag = check_max_lag(a.max_lag)
+        if not 1 <= a.chains <= MAX_SEGMENTS // 2:
+            raise ValueError("--chains must be in 1 .. %d" % (MAX_SEGMENTS // 2))
+    except ValueError as e:
+        p.error(str(e))
+    return a.ensemble, edges, a.chains, max_lag, a.device
+
+
+def diagnostics_path(path):
+    """<name>.diagnostics.npz beside the ensemble <name>.npz."""
+    return (path[:-4] if path.endswith(".npz") else path) + ".diagnostics.npz"
+
+
+def main(argv=None):
+    path, edges, chains, max_lag, device = parse_args(argv)
+    ens = load(path, device=device)
+    d = diagnostics(ens, edges, chains=chains, max_lag=max_lag)
+    out = diagnostics_path(path)
+    np.savez_compressed(out, depth_edges=edges, thin=ens.thin, **{n: v.cpu().numpy() for n, v in d.items()})
+    print("wrote", out)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -495,7 +495,7 @@ BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device bloc
 def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min_iterations=5000, check_every=1000,
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
-          first_above=(), first_below=(), replicates=1, data_posteriors=None, ensemble=None, **overrides):
+          first_above=(), first_below=(), replicates=1, data_posteriors=None, ensemble=None, ensemble_diagnostics=False, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -536,6 +536,11 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     (0: empty slot), ``ensemble_edges`` / ``ensemble_sigma`` [S, n_keep, K] (+inf / NaN padded), ``ensemble_misfit`` [S, n_keep] and
     ``ensemble_thin`` [S]; ``ensembles.realisations`` / ``ensembles.rebin`` take them from there.  Needs the hit map; counted in the
     default block's payload budget.  The containers are not touched.
+    ``ensemble_diagnostics`` (True or dict(max_lag=1 .. 255); needs ``ensemble``): did the chains run long enough -- the chain
+    diagnostics of the kept models (``ensembles.diagnostics``) join the summaries: ``ensemble_ess``, ``ensemble_rhat``
+    (split R-hat: it works with one chain), ``ensemble_tau_iterations``, ``ensemble_mcse`` [S, n_depth] on the hit map's depth axis and
+    ``ensemble_ess_k``, ``ensemble_ess_misfit``, ``ensemble_rhat_k``, ``ensemble_rhat_misfit``, ``ensemble_ess_min`` [S]; with
+    ``replicates`` = C every chain of a sounding gives two segments.  The containers are not touched.
     ``replicates`` = C, 1 .. 8 (frequency-domain data): C chains per sounding that differ by their random streams alone
     (``replicates.expand``: replicate 0 walks the chain the sounding walks alone); a block then holds C rows per sounding and is seen
     through ``replicates.Pooled`` -- the containers and the posteriors of the summaries receive the sum over the chains that burned in,
@@ -555,6 +560,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     from .distributed import shard
 
     # check
+    ens_diag = survey_run.ensemble_diagnostics_argument(ensemble_diagnostics, ensemble)
     o = read_options(options, **overrides) if isinstance(options, str) else dict(options)
     tempest, time_domain, C_rep = survey_run.check_request(o, hitmap, replicates)
     # read
@@ -596,7 +602,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     run = survey_run.SurveyRun(ds=ds, o=o, common=common, rows=rows, n_file=n_file, rank=rank, C_rep=C_rep,
                                time_domain=time_domain, hitmap=hitmap, exact_jacobian=exact_jacobian, check_every=check_every,
                                results_directory=results_directory, container=container,
-                               own_containers=containers and (world == 1 or schedule == "lines"), unit_z=unit_z, clock=clock)
+                               own_containers=containers and (world == 1 or schedule == "lines"), unit_z=unit_z, clock=clock,
+                               ensemble_diagnostics=ens_diag)
     filler = survey_run.ContainerFiller(lambda dc, idx: run.payload(dc, idx, sparse=True),
                                         lambda dc: _LineWriter(results_directory, ds, o, dc, hitmap, container), clock)
     # the blocks, one after the other; a block's rows leave for the containers while the next block's chains run

@@ -104,6 +104,21 @@ def sampler_arguments(o, time_domain, seed=None, device=None, hitmap=True, first
     return common
 
 
+def ensemble_diagnostics_argument(ensemble_diagnostics, ensemble):
+    """infer's ``ensemble_diagnostics`` (False / None: off; True; dict(max_lag=)) as None or dict(max_lag=int in 1 .. 255).  Refuses
+    the diagnostics without an ensemble.  Touches no device."""
+    if ensemble_diagnostics is None or ensemble_diagnostics is False:
+        return None
+    from .ensembles import check_max_lag
+    if ensemble_diagnostics is True:
+        ensemble_diagnostics = {}
+    if not isinstance(ensemble_diagnostics, dict) or set(ensemble_diagnostics) - {"max_lag"}:
+        raise ValueError("ensemble_diagnostics: False, True or dict(max_lag=)")
+    if ensemble is None or ensemble is False:
+        raise ValueError("ensemble_diagnostics needs ensemble= (the diagnostics are computed from the kept models)")
+    return dict(max_lag=check_max_lag(ensemble_diagnostics.get("max_lag")))
+
+
 def ensemble_bytes(n_keep, max_layers):
     """Bytes of device memory one chain's posterior ensemble takes: n_keep slots of 2 K doubles, a misfit and a layer count, and the
     chain's sample counter -- n_keep (16 K + 12) + 4 (126 KB at n_keep = 256, K = 30, beside the hit map's 440 KB)."""
@@ -224,6 +239,7 @@ class SurveyRun:
     named: list = None                  # its summaries [(name, [rows, width])]: the layout of every block's result rows
     iterations: int = 0                 # the largest iteration count of any block
     shipped: list = field(default_factory=list)     # per block: payload() on the HOST, for the rank that writes (not own_containers)
+    ensemble_diagnostics: object = None     # None, or dict(max_lag): the chain diagnostics of the ensemble join the summaries
 
     def run_block(self, idx, offset=None, key_by_row=True):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])]).  ``key_by_row``:
@@ -304,6 +320,11 @@ class SurveyRun:
                 ens = ensembles.from_chains(dc)
                 named += [("ensemble_k", f64(ens.k)), ("ensemble_edges", ens.edges.flatten(1)), ("ensemble_sigma", ens.sigma.flatten(1)),
                           ("ensemble_misfit", ens.misfit), ("ensemble_thin", col(torch.full_like(t["k"], ens.thin)))]
+                if self.ensemble_diagnostics is not None:
+                    d = ensembles.diagnostics(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
+                                              max_lag=self.ensemble_diagnostics["max_lag"])
+                    named += [("ensemble_" + k_, d[k_]) for k_ in ("ess", "rhat", "tau_iterations", "mcse")]
+                    named += [("ensemble_" + k_, col(d[k_])) for k_ in ("ess_k", "ess_misfit", "rhat_k", "rhat_misfit", "ess_min")]
         if diag is not None:
             named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return named

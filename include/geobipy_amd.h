@@ -734,6 +734,26 @@ gbp_status gbp_ensemble_rebin(int B, int n_ensemble, int K, const int32_t *ens_k
                               int32_t *hitmap, int n_units, int unit_kinds, const double *unit_z, int32_t *unit_hist, int n_first,
                               const double *first_threshold, const int32_t *first_direction, int32_t *first_hist, int32_t *first_none,
                               void *stream);
+/* Chain diagnostics of regularly spaced series (csrc/gbp_ensemble_diag.h): did the chain run long enough, and how many independent
+ * samples stand behind a posterior mean.  Per sounding b: M = seg_m[b] segments of equal length N = seg_n[b]; segment m covers rows
+ * seg_start[b, m] .. seg_start[b, m] + N - 1 (inside 0 .. n_rows - 1: the caller's duty).  L = min(max_lag, N - 1), lowered by one if
+ * even.  Per variable, with sums over a segment's rows: mean_m, d = x - mean_m, acov_m(l) = (1/N) sum_{t < N - l} d_t d_{t+l} (l = 0 .. L);
+ * W = (1/M) sum_m acov_m(0) N/(N-1); gm = (1/M) sum_m mean_m; Bn = sum_m (mean_m - gm)^2 / (M - 1) (0 when M = 1); vp = W (N-1)/N + Bn;
+ * rho_0 = 1, rho_l = 1 - (W - (1/M) sum_m acov_m(l) N/(N-1)) / vp; Geyer's initial monotone sequence on the pairs P_k = rho_2k + rho_2k+1:
+ * S = prev = P_0, pairs = 1, then for k = 1 .. (L-1)/2 stop unless P_k > 0, else prev = min(prev, P_k), S += prev, pairs += 1;
+ * tau = max(2 S - 1, 1 / log10(M N)); ess = M N / tau; rhat = sqrt(vp / W); sd = sqrt(vp); mcse = sqrt(vp / ess); mean = gm.
+ * stats f64 [B, 6, V]: mean, sd, rhat, tau, ess, mcse; pairs int32 [B, V] (== (L + 1) / 2: the sum ran into the lag cap); rho NULL or
+ * f64 [B, max_lag + 1, V], NaN beyond L.  M = 0 or N < 4: every output of the sounding NaN, pairs 0.  A variable whose used samples
+ * are all one value (compared as stored): mean = it, sd = 0, the rest NaN, pairs 0; one with a non-finite used sample: all NaN, pairs 0.
+ * gbp_series_diagnostics reads x f64 [B, n_rows, V]; gbp_ensemble_diagnostics rasters x[t, c] = log10 of the conductivity of the
+ * layer of slot t that holds z[c] (the rule of gbp_ensemble_raster) on the fly.  1 <= max_lag <= 255, 1 <= M_max <= 16, n_rows and
+ * n_slots <= 32 768, 1 <= K <= 64; GBP_ERR_INVALID_ARG for these and NULL pointers, every check before any launch, the entry named in
+ * gbp_last_error; B == 0 launches nothing.  No atomics, one order of addition: a call repeats its own bits. */
+gbp_status gbp_series_diagnostics(int B, int n_rows, int V, const double *x, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                                  const int32_t *seg_n, int max_lag, double *stats, int32_t *pairs, double *rho, void *stream);
+gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                                    int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                                    const int32_t *seg_n, int max_lag, double *stats, int32_t *pairs, double *rho, void *stream);
 gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                    int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                    void *stream);
