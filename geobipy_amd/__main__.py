@@ -68,7 +68,24 @@ def parse(argv=None):
                    help="chain diagnostics of the ensemble (needs --ensemble): effective sample size, split R-hat, autocorrelation time and "
                         "Monte-Carlo standard error per depth cell, lags up to MAX_LAG (1 .. 255, default 255): ensemble_ess, ensemble_rhat, "
                         "... in the summaries")
+    p.add_argument("--ensemble-correlation", nargs="*", default=None, metavar="BAND [THRESHOLD]",
+                   help="vertical resolution from the ensemble (needs --ensemble): the posterior correlation between depth cells up to BAND "
+                        "cells apart (>= 0, default 64) and the thickness over which it stays >= THRESHOLD (0 < THRESHOLD < 1, default 0.5): "
+                        "ensemble_resolution_length, ensemble_resolution_cells, ensemble_resolution_closed in the summaries")
     a = p.parse_args(argv)
+    if a.ensemble_correlation is not None:
+        if a.ensemble is None:
+            p.error("--ensemble-correlation needs --ensemble")
+        if len(a.ensemble_correlation) > 2:
+            p.error("--ensemble-correlation: at most BAND and THRESHOLD")
+        try:
+            band = int(a.ensemble_correlation[0]) if a.ensemble_correlation else 64
+            threshold = float(a.ensemble_correlation[1]) if len(a.ensemble_correlation) > 1 else 0.5
+        except ValueError:
+            p.error("--ensemble-correlation: BAND is an integer, THRESHOLD a number")
+        if band < 0 or not 0.0 < threshold < 1.0:
+            p.error("--ensemble-correlation: BAND >= 0 and 0 < THRESHOLD < 1")
+        a.ensemble_correlation = dict(band=band, threshold=threshold)
     if a.ensemble_diagnostics is not None:
         if a.ensemble is None:
             p.error("--ensemble-diagnostics needs --ensemble")
@@ -136,7 +153,8 @@ def main(argv=None):
                        data_filename=a.data_filename, units=a.units, unit_kinds=tuple(a.unit_kinds), first_above=tuple(a.first_above),
                        first_below=tuple(a.first_below), replicates=a.replicates,
                        data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble,
-                       ensemble_diagnostics=False if a.ensemble_diagnostics is None else dict(max_lag=a.ensemble_diagnostics))
+                       ensemble_diagnostics=False if a.ensemble_diagnostics is None else dict(max_lag=a.ensemble_diagnostics),
+                       ensemble_correlation=False if a.ensemble_correlation is None else a.ensemble_correlation)
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

@@ -1881,6 +1881,78 @@ extern "C" gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const 
     return series_diagnostics_launch("gbp_ensemble_diagnostics", ensemble::DIAG_RASTER, B, a, ens_k && ens_edges && ens_sigma && z, stream);
 }
 
+#include "gbp_ensemble_corr.h"
+
+// Correlation between variables (csrc/gbp_ensemble_corr.h; the rule: include/geobipy_amd.h): the moments, the MFMA kernel, then the two
+// streaming kernels of the finish, in stream order.  The checks the two entries share; `entry` names the caller in gbp_last_error.
+static gbp_status series_correlation_launch(const char* entry, int source, int B, ensemble::CorrArgs a, int normalise, bool pointers, void* stream)
+{
+    using namespace ensemble;
+    if (B < 0 || a.n_rows < 1 || a.V < 1) return fail(GBP_ERR_INVALID_ARG, "%s: negative or zero size", entry);
+    if (a.n_rows > 32768) return fail(GBP_ERR_INVALID_ARG, "%s: more than 32 768 rows", entry);
+    if (a.W < 0 || a.W > a.V - 1) return fail(GBP_ERR_INVALID_ARG, "%s: band_width outside 0 .. V - 1", entry);
+    if (a.M_max < 1 || a.M_max > DIAG_MAX_M) return fail(GBP_ERR_INVALID_ARG, "%s: M_max outside 1 .. 16", entry);
+    if (source == DIAG_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!pointers || !a.seg_start || !a.seg_m || !a.seg_n || !a.stats || !a.band) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    const int ntiles = (a.V + 15) / 16, nstrips = (ntiles + CORR_WAVES - 1) / CORR_WAVES;
+    const int DJ = (a.W + 15) / 16 + 1, npanels = (DJ + CORR_NACC - 1) / CORR_NACC;
+    const int64_t moment_blocks = (int64_t)B * ((a.V + 63) / 64), blocks = (int64_t)B * nstrips * npanels;
+    const int64_t entries = (int64_t)B * a.V * (a.W + 1), finish_blocks = (entries + 255) / 256;
+    if (moment_blocks > 0x7fffffffLL || blocks > 0x7fffffffLL || finish_blocks > 0x7fffffffLL)
+        return fail(GBP_ERR_INVALID_ARG, "%s: B * V * (band_width + 1) out of range", entry);
+    const int ncol = (std::min(DJ, CORR_NACC) + CORR_WAVES - 1) * 16 + (npanels > 1 ? CORR_WAVES * 16 : 0);      // the widest staged row
+    const size_t lds = (size_t)CORR_CH * (ncol + ((ncol & 31) == 0 ? 16 : 0)) * sizeof(double);                    // <= CORR_LDS_BYTES < 64 KiB
+    hipStream_t s = (hipStream_t)stream;
+    if (source == DIAG_RASTER) {
+        hipLaunchKernelGGL(k_series_moments<DIAG_RASTER>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
+        hipLaunchKernelGGL(k_series_correlation<DIAG_RASTER>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
+    } else {
+        hipLaunchKernelGGL(k_series_moments<DIAG_PLAIN>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
+        hipLaunchKernelGGL(k_series_correlation<DIAG_PLAIN>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
+    }
+    const size_t cells = (size_t)B * a.V;
+    hipLaunchKernelGGL(k_correlation_sd, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, cells, a.V, a.W, a.band, a.stats);
+    hipLaunchKernelGGL(k_correlation_finish, dim3((unsigned)finish_blocks), dim3(256), 0, s, (size_t)entries, a.V, a.W, normalise, a.stats, a.band);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+extern "C" gbp_status gbp_series_correlation(int B, int n_rows, int V, const double* x, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                             const int32_t* seg_n, int band_width, int normalise, double* stats, double* band, void* stream)
+{
+    ensemble::CorrArgs a = {};
+    a.n_rows = n_rows; a.V = V; a.x = x; a.M_max = M_max; a.W = band_width;
+    a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.band = band;
+    return series_correlation_launch("gbp_series_correlation", ensemble::DIAG_PLAIN, B, a, normalise, x != nullptr, stream);
+}
+
+extern "C" gbp_status gbp_ensemble_correlation(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                               int n_depth, const double* z, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                               const int32_t* seg_n, int band_width, int normalise, double* stats, double* band, void* stream)
+{
+    ensemble::CorrArgs a = {};
+    a.n_rows = n_slots; a.V = n_depth; a.K = K; a.ens_k = ens_k; a.ens_edges = ens_edges; a.ens_sigma = ens_sigma; a.z = z;
+    a.M_max = M_max; a.W = band_width; a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.band = band;
+    return series_correlation_launch("gbp_ensemble_correlation", ensemble::DIAG_RASTER, B, a, normalise, ens_k && ens_edges && ens_sigma && z, stream);
+}
+
+extern "C" gbp_status gbp_band_runs(int B, int V, int band_width, const double* band, double threshold, int32_t* up, int32_t* down,
+                                    uint8_t* closed, void* stream)
+{
+    if (B < 0 || V < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_band_runs: negative or zero size%s");
+    if (band_width < 0 || band_width > V - 1) return fail(GBP_ERR_INVALID_ARG, "gbp_band_runs: band_width outside 0 .. V - 1%s");
+    if (threshold != threshold) return fail(GBP_ERR_INVALID_ARG, "gbp_band_runs: threshold is NaN%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!band || !up || !down || !closed) return fail(GBP_ERR_INVALID_ARG, "gbp_band_runs: NULL pointer%s");
+    const size_t cells = (size_t)B * V;
+    if ((cells + 255) / 256 > 0x7fffffffull) return fail(GBP_ERR_INVALID_ARG, "gbp_band_runs: B * V out of range%s");
+    hipLaunchKernelGGL(ensemble::k_band_runs, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cells, V, band_width, band,
+                       threshold, up, down, closed);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 #include "gbp_grid.h"
 
 // Discrete Sibson gridding (gbp_grid.h): the plan holds the geometry of one grid -- nearest sounding, D, n, and per destination pixel the

@@ -16,8 +16,13 @@ every ``thin``-th sampled model of every chain, in chain order, up to ``n_keep``
                    R-hat that works with one chain (gbp_ensemble_diagnostics / gbp_series_diagnostics).
                    ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH`` writes them for a saved ensemble.
 
+``correlation``    what is the vertical resolution: the posterior correlation between depth cells in a band R(c, c + j), j = 0 .. W, and
+                   from it the thickness of the run of cells that move with a cell (``resolution_length``, metres) -- centred products on
+                   the fp64 matrix cores, the series never written (gbp_ensemble_correlation / gbp_series_correlation / gbp_band_runs;
+                   DESIGN.md 3.22).  ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH --correlation [BAND]``.
+
 There is no host fallback: all refuse tensors that are not on the device (``realisations_reference`` states the raster's rule in numpy,
-``diagnostics_reference`` that of the diagnostics).
+``diagnostics_reference`` that of the diagnostics, ``correlation_reference`` and ``correlation_runs_reference`` those of the correlation).
 """
 import ctypes
 from collections import namedtuple
@@ -447,6 +452,259 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
     return out
 
 
+def correlation_reference(x, seg_start, n, band, dtype=np.float64, normalise=True):
+    """The rule of the correlation between variables for one sounding, in numpy: ``x`` [n_rows, V], M = len(seg_start) segments of
+    ``n`` rows each (the lists ``segments`` builds: the used samples are the ones the diagnostics use), evaluated in ``dtype``.
+    Returns {mean, sd [V], band [V, W + 1]} with W = ``band`` (0 .. V - 1).
+
+    With n_used = M n used rows: mu_v = (1/n_used) sum_t x_tv, d = x - mu, C(u, v) = (1/(n_used - 1)) sum_t d_tu d_tv (the pooled sample
+    covariance), sd_v = sqrt(C(v, v)), R(u, v) = C(u, v) / (sd_u sd_v); band[c, j] = R(c, c + j) (``normalise=False``: C(c, c + j)), NaN
+    where c + j >= V.  M == 0 or n_used < 4: everything NaN.  A variable whose used samples are all one value (compared as stored):
+    mean = it, sd = 0, every band entry that involves it NaN, its own diagonal included; one with a non-finite used sample: mean, sd
+    and its entries NaN; no other entry is touched by either.  R of a live variable with itself is 1 exactly.
+
+    ``sd`` is the POOLED sample standard deviation (one mean for all segments, divisor n_used - 1); the diagnostics' sd = sqrt(vp)
+    (within-segment variance (n - 1)/n W plus the variance of the segment means) differs from it by O(1/n) for segments whose means
+    agree to O(sd / sqrt(n)): the spread of the segment means enters the two with weights 1/M and 1/(M - 1)."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("correlation_reference: x [n_rows, V]")
+    V = x.shape[1]
+    if isinstance(band, bool) or int(band) != band or not 0 <= int(band) <= V - 1:
+        raise ValueError("correlation_reference: band must be an integer in 0 .. V - 1")
+    W = int(band)
+    starts = [int(q) for q in np.asarray(seg_start).reshape(-1)]
+    M, N = len(starts), int(n)
+    if M > MAX_SEGMENTS:
+        raise ValueError("correlation_reference: at most %d segments" % MAX_SEGMENTS)
+    out = dict(mean=np.full(V, np.nan, dtype=dtype), sd=np.full(V, np.nan, dtype=dtype), band=np.full((V, W + 1), np.nan, dtype=dtype))
+    if M == 0 or M * N < 4:
+        return out
+    if min(starts) < 0 or max(starts) + N > x.shape[0]:
+        raise ValueError("correlation_reference: a segment leaves the rows 0 .. %d" % (x.shape[0] - 1))
+    stored = np.concatenate([x[q:q + N] for q in starts])               # [n_used, V]
+    xs = stored.astype(dtype)
+    nu = dtype(M * N)
+    bad = ~np.all(np.isfinite(stored), axis=0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        const = ~bad & (stored.min(axis=0) == stored.max(axis=0))
+        dead = bad | const
+        mu = xs.sum(axis=0) / nu
+        d = np.where(dead[None, :], dtype(0), xs - mu[None, :])
+        var = (d * d).sum(axis=0) / (nu - dtype(1))
+        sd = np.sqrt(var)
+        for j in range(W + 1):
+            c = (d[:, :V - j] * d[:, j:]).sum(axis=0) / (nu - dtype(1))
+            if normalise:
+                c = c / (sd[:V - j] * sd[j:]) if j else np.ones(V, dtype=dtype)
+            c[dead[:V - j] | dead[j:]] = np.nan
+            out["band"][:V - j, j] = c
+    mu[const] = stored[0, const].astype(dtype)
+    mu[bad] = np.nan
+    sd[const] = 0
+    sd[bad] = np.nan
+    out["mean"], out["sd"] = mu, sd
+    return out
+
+
+def band_to_matrix(band):
+    """The symmetric matrix [..., V, V] of a band [..., V, W + 1] (band[..., c, j] = entry (c, c + j)); NaN outside the band.  Torch or
+    numpy, as given."""
+    if band.ndim < 2 or not 1 <= band.shape[-1] <= band.shape[-2]:
+        raise ValueError("band_to_matrix: band [..., V, W + 1] with 0 <= W <= V - 1")
+    V, W1 = band.shape[-2], band.shape[-1]
+    if torch.is_tensor(band):
+        out = torch.full(tuple(band.shape[:-1]) + (V,), float("nan"), dtype=band.dtype, device=band.device)
+    else:
+        out = np.full(band.shape[:-1] + (V,), np.nan, dtype=band.dtype)
+    for j in range(W1):
+        c = np.arange(V - j)
+        out[..., c, c + j] = band[..., :V - j, j]
+        out[..., c + j, c] = band[..., :V - j, j]
+    return out
+
+
+def check_threshold(threshold):
+    """``threshold`` as a float strictly between 0 and 1."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0.0 < float(threshold) < 1.0:
+        raise ValueError("threshold must be a number with 0 < threshold < 1")
+    return float(threshold)
+
+
+def correlation_runs_reference(band, threshold):
+    """The runs of a band [V, W + 1] above ``threshold``, in numpy: for cell c, ``down[c]`` = the number of consecutive j = 1, 2, ...
+    with j <= W, c + j <= V - 1 and band[c, j] >= threshold (NaN compares false and ends the run), ``up[c]`` the same with
+    band[c - j, j] and c - j >= 0; ``closed_down[c]`` / ``closed_up[c]``: the walk ended at an entry that is not >= threshold (False:
+    it ended at j = W or at the end of the axis, so the run is a lower bound).  A cell whose diagonal is NaN: up = down = 0, both
+    flags False.  Returns {up, down int32 [V], closed_up, closed_down bool [V]}."""
+    band = np.asarray(band)
+    if band.ndim != 2 or not 1 <= band.shape[1] <= band.shape[0]:
+        raise ValueError("correlation_runs_reference: band [V, W + 1] with 0 <= W <= V - 1")
+    V, W = band.shape[0], band.shape[1] - 1
+    up, down = np.zeros(V, dtype=np.int32), np.zeros(V, dtype=np.int32)
+    cu, cd = np.zeros(V, dtype=bool), np.zeros(V, dtype=bool)
+    for c in range(V):
+        if np.isnan(band[c, 0]):
+            continue
+        j = 1
+        while j <= W and c + j <= V - 1:
+            if not band[c, j] >= threshold:
+                cd[c] = True
+                break
+            down[c] += 1
+            j += 1
+        j = 1
+        while j <= W and c - j >= 0:
+            if not band[c - j, j] >= threshold:
+                cu[c] = True
+                break
+            up[c] += 1
+            j += 1
+    return dict(up=up, down=down, closed_up=cu, closed_down=cd)
+
+
+def resolution_length(up, down, depth_edges, live=None):
+    """edges[c + down + 1] - edges[c - up] in metres: the thickness of the run of cells that move with cell c (at least the cell's own
+    thickness).  ``up`` / ``down`` int [..., V] (torch or numpy), ``depth_edges`` [V + 1]; ``live`` bool [..., V] (None: everything):
+    NaN where it is False (the cells whose diagonal is NaN)."""
+    centres(depth_edges)
+    e = np.asarray(depth_edges, dtype=np.float64).reshape(-1)
+    V = e.size - 1
+    if up.shape != down.shape or up.shape[-1] != V:
+        raise ValueError("resolution_length: up and down [..., V] for depth_edges [V + 1]")
+    if torch.is_tensor(up):
+        c = torch.arange(V, device=up.device)
+        et = torch.as_tensor(e).to(up.device)
+        out = et[(c + down.long() + 1).clamp(max=V)] - et[(c - up.long()).clamp(min=0)]
+        return out if live is None else torch.where(live, out, torch.full_like(out, float("nan")))
+    c = np.arange(V)
+    out = e[np.minimum(c + np.asarray(down, dtype=np.int64) + 1, V)] - e[np.maximum(c - np.asarray(up, dtype=np.int64), 0)]
+    return out if live is None else np.where(live, out, np.nan)
+
+
+def check_band(band, V):
+    """``band`` (None: V - 1) as an int >= 0, clipped to V - 1."""
+    if band is None:
+        return V - 1
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or int(band) < 0:
+        raise ValueError("band must be an integer >= 0")
+    return min(int(band), V - 1)
+
+
+def series_correlation(x, seg_start, seg_m, seg_n, band=None, normalise=True):
+    """The correlation between the variables (``correlation_reference`` states the rule) of the series ``x`` f64 [B, n_rows, V] on the
+    device, segments as ``series_diagnostics`` takes them.  Returns {mean, sd f64 [B, V], band f64 [B, V, W + 1]}: band[b, c, j] =
+    R(c, c + j) (``normalise=False``: the covariance), W = ``band`` clipped to V - 1 (None: V - 1, the whole matrix;
+    ``band_to_matrix`` unfolds it).  gbp_series_correlation: centred products on the fp64 matrix cores."""
+    _are_tensors((x, seg_start, seg_m, seg_n), "series_correlation", "gbp_series_correlation")
+    if x.dtype != torch.float64:
+        raise TypeError("series_correlation: x is float64")
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
+        raise ValueError("series_correlation: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1")
+    B, n_rows, V = x.shape
+    W = check_band(band, V)
+    seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, B, n_rows, "series_correlation")
+    _on_device((x, seg_start, seg_m, seg_n), "series_correlation", "gbp_series_correlation")
+    x, dev = x.contiguous(), x.device
+    stats = torch.empty((B, 2, V), dtype=torch.float64, device=dev)
+    out = torch.empty((B, V, W + 1), dtype=torch.float64, device=dev)
+    if B > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gbp_series_correlation(B, n_rows, V, x.data_ptr(), int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(),
+                                                          seg_n.data_ptr(), W, int(bool(normalise)), stats.data_ptr(), out.data_ptr(), _stream(dev)))
+    return dict(mean=stats[:, 0], sd=stats[:, 1], band=out)
+
+
+def correlation_runs(band, threshold):
+    """``correlation_runs_reference`` on a device band f64 [B, V, W + 1] (gbp_band_runs): {up, down int32 [B, V], closed_up,
+    closed_down bool [B, V]}.  ``threshold``: any number that is not NaN."""
+    _are_tensors((band,), "correlation_runs", "gbp_band_runs")
+    if band.dtype != torch.float64:
+        raise TypeError("correlation_runs: band is float64")
+    if band.ndim != 3 or not 1 <= band.shape[2] <= band.shape[1]:
+        raise ValueError("correlation_runs: band [B, V, W + 1] with 0 <= W <= V - 1")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("correlation_runs: threshold is NaN")
+    _on_device((band,), "correlation_runs", "gbp_band_runs")
+    band, dev = band.contiguous(), band.device
+    B, V, W1 = band.shape
+    up, down = (torch.empty((B, V), dtype=torch.int32, device=dev) for _ in range(2))
+    closed = torch.empty((B, 2, V), dtype=torch.uint8, device=dev)
+    if B > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gbp_band_runs(B, V, W1 - 1, band.data_ptr(), threshold, up.data_ptr(), down.data_ptr(), closed.data_ptr(), _stream(dev)))
+    return dict(up=up, down=down, closed_up=closed[:, 0].bool(), closed_down=closed[:, 1].bool())
+
+
+BAND_BLOCK_BYTES = 2 << 30
+
+
+def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=True, block=None, keep_band=True):
+    """What moves together, and over what thickness?  Per sounding the posterior correlation between the cells of ``depth_edges``
+    [n_depth + 1] of the series log10 conductivity at the cell centre over the kept models (``correlation_reference`` states the rule;
+    the used samples are those of ``diagnostics``: ``segments``, ``chains`` = C as there), the series never written to memory
+    (gbp_ensemble_correlation).  Returns mean, sd f64 [B, n_depth] (sd: the pooled sample standard deviation, O(1/N) from the
+    diagnostics' sd); ``band`` f64 [B, n_depth, W + 1], band[b, c, j] = R(c, c + j), W = ``band`` clipped to n_depth - 1
+    (``normalise=False``: covariances; dropped with ``keep_band=False``); the runs of entries >= ``threshold`` (0 < threshold < 1) up
+    and down from every cell (``correlation_runs_reference``): up, down int32, closed_up, closed_down bool [B, n_depth];
+    resolution_cells = up + down + 1; resolution_length f64 [B, n_depth] (``resolution_length``: metres, NaN for a cell that is
+    constant or non-finite) and resolution_closed = closed_up & closed_down (False: the length is a lower bound -- the run reached
+    the band's width or the end of the axis); n_chains_used, segment_length, n_segments int32 [B].  ``block``: soundings per launch
+    (None: as many as keep a block's band under 2 GiB)."""
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2:
+        check_chains(chains, ens.k.shape[1])
+    z_np = centres(depth_edges)
+    nd = int(z_np.size)
+    W = check_band(band, nd)
+    threshold = check_threshold(threshold)
+    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
+        raise ValueError("correlation: block must be a positive integer")
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    _are_tensors((k, edges, sigma), "correlation", "gbp_ensemble_correlation")
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
+        raise ValueError("ensemble: k [B, n_slots], edges and sigma [B, n_slots, K]")
+    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64:
+        raise TypeError("ensemble: k is int32, edges and sigma are float64")
+    B, ns, K = edges.shape
+    C = check_chains(chains, ns)
+    if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
+        raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
+    _on_device((k, edges, sigma), "correlation", "gbp_ensemble_correlation")
+    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
+    count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
+    start_np, m_np, n_np, used_np = segments(count, ns // C)
+    start, seg_m, seg_n = (torch.as_tensor(a).to(dev) for a in (start_np, m_np, n_np))
+    step = max(1, BAND_BLOCK_BYTES // (nd * (W + 1) * 8)) if block is None else int(block)
+    stats = torch.empty((B, 2, nd), dtype=torch.float64, device=dev)
+    full = torch.empty((B, nd, W + 1), dtype=torch.float64, device=dev) if keep_band else None
+    up, down = (torch.empty((B, nd), dtype=torch.int32, device=dev) for _ in range(2))
+    closed = torch.empty((B, 2, nd), dtype=torch.uint8, device=dev)
+    live = torch.empty((B, nd), dtype=torch.bool, device=dev)
+    if B > 0:
+        z = torch.as_tensor(z_np).to(dev)
+        lib = _lib.load()
+        work = None if keep_band else torch.empty((min(step, B), nd, W + 1), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            for b0 in range(0, B, step):
+                s = slice(b0, min(B, b0 + step))
+                part = full[s] if keep_band else work[:s.stop - s.start]
+                _lib.check(lib.gbp_ensemble_correlation(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
+                                                        z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), W,
+                                                        int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(), _stream(dev)))
+                _lib.check(lib.gbp_band_runs(s.stop - s.start, nd, W, part.data_ptr(), threshold, up[s].data_ptr(), down[s].data_ptr(),
+                                             closed[s].data_ptr(), _stream(dev)))
+                live[s] = ~torch.isnan(part[:, :, 0])
+    out = dict(mean=stats[:, 0], sd=stats[:, 1], up=up, down=down, closed_up=closed[:, 0].bool(), closed_down=closed[:, 1].bool())
+    if keep_band:
+        out["band"] = full
+    out["resolution_cells"] = up + down + 1
+    out["resolution_length"] = resolution_length(up, down, depth_edges, live=live)
+    out["resolution_closed"] = out["closed_up"] & out["closed_down"]
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = torch.as_tensor(used_np).to(dev), seg_n, seg_m
+    return out
+
+
 def save(ens, path):
     """Write an ``Ensemble`` to ``path`` with np.savez_compressed; returns the path."""
     np.savez_compressed(path, **{n: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for n, v in ens._asdict().items()})
@@ -473,6 +731,10 @@ def _parser():
     axis.add_argument("--depth-axis", nargs=2, metavar=("N", "WIDTH"), help="N uniform cells of WIDTH starting at 0")
     p.add_argument("--chains", type=int, default=1, help="replicate chains on the slot axis (default 1)")
     p.add_argument("--max-lag", type=int, default=None, help="largest lag, 1 .. 255 (default 255)")
+    p.add_argument("--correlation", type=int, nargs="?", const=64, default=None, metavar="BAND",
+                   help="instead of the diagnostics: the correlation between depth cells up to BAND cells apart (default 64) and the "
+                        "resolution length; writes <name>.correlation.npz")
+    p.add_argument("--threshold", type=float, default=None, metavar="T", help="with --correlation: cells move together while R >= T, 0 < T < 1 (default 0.5)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -506,8 +768,40 @@ def diagnostics_path(path):
     return (path[:-4] if path.endswith(".npz") else path) + ".diagnostics.npz"
 
 
+def parse_correlation(argv=None):
+    """``--correlation [BAND] [--threshold T]`` of the command line as (band, threshold), or None without ``--correlation``; refuses
+    before any device work."""
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.correlation is None:
+        if a.threshold is not None:
+            p.error("--threshold needs --correlation")
+        return None
+    if a.correlation < 0:
+        p.error("--correlation: BAND >= 0")
+    if a.max_lag is not None:
+        p.error("--max-lag belongs to the diagnostics (drop --correlation)")
+    try:
+        return a.correlation, check_threshold(0.5 if a.threshold is None else a.threshold)
+    except ValueError as e:
+        p.error("--threshold: " + str(e))
+
+
+def correlation_path(path):
+    """<name>.correlation.npz beside the ensemble <name>.npz."""
+    return (path[:-4] if path.endswith(".npz") else path) + ".correlation.npz"
+
+
 def main(argv=None):
     path, edges, chains, max_lag, device = parse_args(argv)
+    corr = parse_correlation(argv)
+    if corr is not None:
+        ens = load(path, device=device)
+        d = correlation(ens, edges, chains=chains, band=corr[0], threshold=corr[1])
+        out = correlation_path(path)
+        np.savez_compressed(out, depth_edges=edges, thin=ens.thin, threshold=corr[1], **{n: v.cpu().numpy() for n, v in d.items()})
+        print("wrote", out)
+        return out
     ens = load(path, device=device)
     d = diagnostics(ens, edges, chains=chains, max_lag=max_lag)
     out = diagnostics_path(path)

@@ -119,6 +119,27 @@ def ensemble_diagnostics_argument(ensemble_diagnostics, ensemble):
     return dict(max_lag=check_max_lag(ensemble_diagnostics.get("max_lag")))
 
 
+def ensemble_correlation_argument(ensemble_correlation, ensemble):
+    """infer's ``ensemble_correlation`` (False / None: off; True; dict(band=, threshold=, keep_band=)) as None or dict(band=int >= 0,
+    threshold=float in (0, 1), keep_band=bool).  Refuses the correlation without an ensemble.  Touches no device."""
+    if ensemble_correlation is None or ensemble_correlation is False:
+        return None
+    from .ensembles import check_threshold
+    if ensemble_correlation is True:
+        ensemble_correlation = {}
+    if not isinstance(ensemble_correlation, dict) or set(ensemble_correlation) - {"band", "threshold", "keep_band"}:
+        raise ValueError("ensemble_correlation: False, True or dict(band=, threshold=, keep_band=)")
+    if ensemble is None or ensemble is False:
+        raise ValueError("ensemble_correlation needs ensemble= (the correlation is computed from the kept models)")
+    band = ensemble_correlation.get("band", 64)
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or int(band) < 0:
+        raise ValueError("ensemble_correlation: band must be an integer >= 0")
+    keep = ensemble_correlation.get("keep_band", False)
+    if not isinstance(keep, (bool, np.bool_)):
+        raise ValueError("ensemble_correlation: keep_band is True or False")
+    return dict(band=int(band), threshold=check_threshold(ensemble_correlation.get("threshold", 0.5)), keep_band=bool(keep))
+
+
 def ensemble_bytes(n_keep, max_layers):
     """Bytes of device memory one chain's posterior ensemble takes: n_keep slots of 2 K doubles, a misfit and a layer count, and the
     chain's sample counter -- n_keep (16 K + 12) + 4 (126 KB at n_keep = 256, K = 30, beside the hit map's 440 KB)."""
@@ -240,6 +261,7 @@ class SurveyRun:
     iterations: int = 0                 # the largest iteration count of any block
     shipped: list = field(default_factory=list)     # per block: payload() on the HOST, for the rank that writes (not own_containers)
     ensemble_diagnostics: object = None     # None, or dict(max_lag): the chain diagnostics of the ensemble join the summaries
+    ensemble_correlation: object = None     # None, or dict(band, threshold, keep_band): the resolution length (and the band) join them
 
     def run_block(self, idx, offset=None, key_by_row=True):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])]).  ``key_by_row``:
@@ -325,6 +347,13 @@ class SurveyRun:
                                               max_lag=self.ensemble_diagnostics["max_lag"])
                     named += [("ensemble_" + k_, d[k_]) for k_ in ("ess", "rhat", "tau_iterations", "mcse")]
                     named += [("ensemble_" + k_, col(d[k_])) for k_ in ("ess_k", "ess_misfit", "rhat_k", "rhat_misfit", "ess_min")]
+                if self.ensemble_correlation is not None:
+                    ec = self.ensemble_correlation
+                    d = ensembles.correlation(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
+                                              band=ec["band"], threshold=ec["threshold"], keep_band=ec["keep_band"])
+                    named += [("ensemble_" + k_, f64(d[k_])) for k_ in ("resolution_length", "resolution_cells", "resolution_closed")]
+                    if ec["keep_band"]:
+                        named += [("ensemble_correlation_band", d["band"].flatten(1))]
         if diag is not None:
             named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return named
@@ -576,6 +605,13 @@ def assemble_result(ds, o, dc, named, r, C_rep, iterations_run):
         res["ensemble_thin"] = res["ensemble_thin"].astype(np.int32)
         for k_ in ("ensemble_edges", "ensemble_sigma"):
             res[k_] = res[k_].reshape(-1, slots, dc.K)
+    if "ensemble_resolution_length" in res:      # [S, n_depth], and the band [S, n_depth, W + 1]
+        nd = int(dc.n_depth_bins)
+        res["ensemble_resolution_length"] = res["ensemble_resolution_length"].reshape(-1, nd)
+        res["ensemble_resolution_cells"] = res["ensemble_resolution_cells"].reshape(-1, nd).astype(np.int32)
+        res["ensemble_resolution_closed"] = res["ensemble_resolution_closed"].reshape(-1, nd) != 0
+        if "ensemble_correlation_band" in res:
+            res["ensemble_correlation_band"] = res["ensemble_correlation_band"].reshape(res["status"].shape[0], nd, -1)
     n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze
     ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
     res["iterations"] = ran.astype(np.int64)

@@ -754,6 +754,30 @@ gbp_status gbp_series_diagnostics(int B, int n_rows, int V, const double *x, int
 gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
                                     int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
                                     const int32_t *seg_n, int max_lag, double *stats, int32_t *pairs, double *rho, void *stream);
+/* Correlation between the variables of such series (csrc/gbp_ensemble_corr.h): what moves together.  Per sounding b
+ * the used rows are those of its M = seg_m[b] segments of N = seg_n[b] rows (the lists of the diagnostics), n = M N of them:
+ * mu_v = (1/n) sum_t x_tv; d_tv = x_tv - mu_v; C(u, v) = (1/(n - 1)) sum_t d_tu d_tv (the pooled sample covariance); sd_v = sqrt(C(v, v));
+ * R(u, v) = C(u, v) / (sd_u sd_v).  stats f64 [B, 2, V]: mean, sd; band f64 [B, V, W + 1], W = band_width, j fastest:
+ * band[b, c, j] = R(c, c + j) (normalise != 0) or C(c, c + j) (normalise == 0), NaN where c + j >= V.  M = 0 or n < 4: everything NaN.
+ * A variable whose used samples are all one value (compared as stored): mean = it, sd = 0, every band entry that involves it NaN, its
+ * own diagonal included; one with a non-finite used sample: mean, sd and its entries NaN; no other entry is touched by either.  R of
+ * a live variable with itself is 1.0 exactly (written, not computed).  sd is the pooled sample standard deviation; the diagnostics'
+ * sd = sqrt(vp) differs from it by O(1/N).  The products are of centred values, accumulated in fp64 (v_mfma_f64_16x16x4_f64).
+ * gbp_series_correlation reads x f64 [B, n_rows, V]; gbp_ensemble_correlation rasters x[t, c] as gbp_ensemble_diagnostics does.
+ * gbp_band_runs: from a band and a threshold, per cell c, down[c] = the number of consecutive j = 1, 2, ... with j <= W, c + j <= V - 1
+ * and band[c, j] >= threshold (NaN compares false and ends the run); up[c] the same with band[c - j, j], c - j >= 0; closed uint8
+ * [B, 2, V] = closed_up, closed_down: 1 iff the walk ended at an entry not >= threshold (0: it ended at j = W or at the end of the
+ * axis).  A cell whose diagonal is NaN: up = down = 0, closed 0.
+ * 1 <= V, 0 <= band_width <= V - 1, n_rows and n_slots <= 32 768, 1 <= M_max <= 16, 1 <= K <= 64; GBP_ERR_INVALID_ARG for these and
+ * NULL pointers, every check before any launch, the entry named in gbp_last_error; B == 0 launches nothing.  A segment that leaves the
+ * rows is the caller's error: its rows are clamped.  No atomics, one order of addition: a call repeats its own bits. */
+gbp_status gbp_series_correlation(int B, int n_rows, int V, const double *x, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                                  const int32_t *seg_n, int band_width, int normalise, double *stats, double *band, void *stream);
+gbp_status gbp_ensemble_correlation(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                                    int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                                    const int32_t *seg_n, int band_width, int normalise, double *stats, double *band, void *stream);
+gbp_status gbp_band_runs(int B, int V, int band_width, const double *band, double threshold, int32_t *up, int32_t *down, uint8_t *closed,
+                         void *stream);
 gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                    int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                    void *stream);
