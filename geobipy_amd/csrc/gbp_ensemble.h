@@ -7,14 +7,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gbp_ensemble_series.h"
+
 namespace ensemble {
 
-// One wave per output row (chain b, list entry r): the slot's k - 1 interface depths and k conductivities sit one per lane (K <= 64),
-// read once.  A pass covers CELLS * 64 cells; lane i owns cells c0 + i + 64 j, so every store instruction of the wave writes one
-// contiguous 512-byte run.  The layer of a cell is the hit map's own count, #{l < k - 1 : edges[l] <= z}: edge l is broadcast from
-// its lane once per pass and compared with the CELLS centres a lane holds.  The conductivity then comes from the lane that holds it --
-// moved as two 32-bit halves, never through arithmetic, so the output is the stored double bit for bit.  A slot outside the
-// ensemble or an empty one (k == 0) gives a row of NaN.
+// One wave per output row (chain b, list entry r) loads its slot once (gbp_ensemble_series.h states the raster rule; the stored
+// doubles, so the output is the stored double bit for bit).  A pass covers CELLS * 64 cells; lane i owns cells c0 + i + 64 j, so every
+// store instruction of the wave writes one contiguous 512-byte run.  A slot outside the ensemble or an empty one (k == 0) gives a row
+// of NaN.
 template <int CELLS>
 __global__ __launch_bounds__(256) void k_ensemble_raster(long long rows, int ne, int K, int R, int nz, const int* __restrict__ ens_k,
                                                          const double* __restrict__ ens_edges, const double* __restrict__ ens_sigma,
@@ -27,32 +27,17 @@ __global__ __launch_bounds__(256) void k_ensemble_raster(long long rows, int ne,
     const long long b = row / R;
     const int slot = slots[(int)(row - b * R)];
     const bool inside = slot >= 0 && slot < ne;
-    const long long src = b * ne + (inside ? slot : 0);
-    const int k = __builtin_amdgcn_readfirstlane(inside ? min(max(ens_k[src], 0), K) : 0);
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double e = lane < k - 1 ? ens_edges[src * K + lane] : (double)INFINITY;
-    const double s = lane < k ? ens_sigma[src * K + lane] : qnan;
-    const int e_lo = __double2loint(e), e_hi = __double2hiint(e);
+    const Slot q = slot_load<false>(ens_k, ens_edges, ens_sigma, K, (size_t)(b * ne + (inside ? slot : 0)), inside, lane);
     double* __restrict__ o = out + row * nz;
     for (int c0 = 0; c0 < nz; c0 += 64 * CELLS) {
-        double zc[CELLS];
-        int layer[CELLS];
+        double zc[CELLS], v[CELLS];
+#pragma unroll
+        for (int j = 0; j < CELLS; ++j) zc[j] = z[min(c0 + lane + 64 * j, nz - 1)];
+        layers<CELLS>(q, zc, v);
 #pragma unroll
         for (int j = 0; j < CELLS; ++j) {
             const int c = c0 + lane + 64 * j;
-            zc[j] = z[min(c, nz - 1)];
-            layer[j] = 0;
-        }
-        for (int l = 0; l < k - 1; ++l) {
-            const double el = __hiloint2double(__builtin_amdgcn_readlane(e_hi, l), __builtin_amdgcn_readlane(e_lo, l));
-#pragma unroll
-            for (int j = 0; j < CELLS; ++j) layer[j] += el <= zc[j] ? 1 : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < CELLS; ++j) {
-            const int c = c0 + lane + 64 * j;
-            const double v = __shfl(s, layer[j], 64);             // (k == 0: every lane holds the NaN)
-            if (c < nz) o[c] = v;
+            if (c < nz) o[c] = v[j];
         }
     }
 }

@@ -1,10 +1,8 @@
 // Posterior correlation between the variables of regularly spaced series (the rule: include/geobipy_amd.h
 // gbp_series_correlation and geobipy_amd/ensembles.py correlation_reference): per sounding the band R(c, c + j), j = 0 .. W, of the
 // pooled sample correlation (or covariance) matrix of the used rows, and the runs of a band above a threshold.  Included by
-// gbp_fdem.hip after gbp_ensemble_diag.h.  The two sources of k_series_diagnostics:
-//   PLAIN    reads x[b, t, v] (f64 [B, n_rows, V], v contiguous)
-//   RASTER   builds x[t, cell] = log10 of the conductivity of the layer holding the cell centre from ens_k / ens_edges / ens_sigma on
-//            the fly (diag_fetch's rule; here the slot's edges and log10s are loaded once per row and serve every staged column)
+// gbp_fdem.hip after gbp_ensemble_diag.h.  SOURCE: the two sources of gbp_ensemble_series.h (RASTER: the log10 conductivity at the
+// cell centres, built on the fly; the slot is loaded once per row and serves every staged column).
 // Four launches, each a pure function of what the one before wrote -- no workgroup reads what another of its launch writes:
 //   k_series_moments<SOURCE>      one workgroup of 4 waves per (sounding, 64 variables): every used row once; stats[b, 0, v] = the mean
 //                                 (a constant's value as stored; NaN for a non-finite sample), stats[b, 1, v] = the flag 1 (live),
@@ -28,7 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "gbp_ensemble_diag.h"
+#include "gbp_ensemble_series.h"
 
 namespace ensemble {
 
@@ -39,59 +37,10 @@ static_assert(CORR_MAX_COLS <= 64 * CORR_MAX_GROUPS && CORR_MAX_COLS % 32 == 16,
 
 typedef double corr_double4 __attribute__((ext_vector_type(4)));
 
-struct CorrArgs {
-    int n_rows, V;                    // rows per sounding (PLAIN: of x; RASTER: slots), variables (RASTER: depth cells)
-    const double* x;                  // PLAIN
-    int K;                            // RASTER
-    const int* ens_k;
-    const double* ens_edges;
-    const double* ens_sigma;
-    const double* z;
-    int M_max, W;
-    const int* seg_start;             // [B, M_max]
-    const int* seg_m;                 // [B]
-    const int* seg_n;                 // [B]
+struct CorrArgs : SeriesArgs {           // reach: W
     double* stats;                    // [B, 2, V]: mean; flag, then sd
     double* band;                     // [B, V, W + 1]
 };
-
-// The row of sounding b that the used sample (segment m, time t) names, kept inside the rows (a segment outside them is the caller's
-// error: never a fault).
-__device__ __forceinline__ size_t corr_row(const CorrArgs& a, size_t b, int start, int t)
-{
-    return b * a.n_rows + (size_t)min(max(start + t, 0), a.n_rows - 1);
-}
-
-// RASTER: what a row's lanes hold -- its k - 1 edges (then +inf) and the log10 of its k conductivities (then NaN), one per lane.
-struct CorrSlot { int k, e_lo, e_hi; double s; };
-
-__device__ __forceinline__ CorrSlot corr_slot(const CorrArgs& a, size_t src, int lane)
-{
-    CorrSlot q;
-    q.k = __builtin_amdgcn_readfirstlane(min(max(a.ens_k[src], 0), a.K));
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double e = lane < q.k - 1 ? a.ens_edges[src * a.K + lane] : (double)INFINITY;
-    q.s = lane < q.k ? log10(a.ens_sigma[src * a.K + lane]) : qnan;
-    q.e_lo = __double2loint(e);
-    q.e_hi = __double2hiint(e);
-    return q;
-}
-
-// layer = #{l < k - 1 : edges[l] <= z} for G centres per lane at once (one readlane pair per edge serves them all)
-template <int G>
-__device__ __forceinline__ void corr_layers(const CorrSlot& q, const double (&zc)[G], double (&x)[G])
-{
-    int layer[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) layer[g] = 0;
-    for (int l = 0; l < q.k - 1; ++l) {
-        const double el = __hiloint2double(__builtin_amdgcn_readlane(q.e_hi, l), __builtin_amdgcn_readlane(q.e_lo, l));
-#pragma unroll
-        for (int g = 0; g < G; ++g) layer[g] += el <= zc[g] ? 1 : 0;
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) x[g] = __shfl(q.s, layer[g], 64);
-}
 
 template <int SOURCE>
 __global__ __launch_bounds__(CORR_WAVES * 64) void k_series_moments(CorrArgs a)
@@ -105,28 +54,28 @@ __global__ __launch_bounds__(CORR_WAVES * 64) void k_series_moments(CorrArgs a)
     const bool own = v < V;
     const int vc = min(v, V - 1);
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const int M = __builtin_amdgcn_readfirstlane(min(a.seg_m[b], a.M_max));
-    const int N = __builtin_amdgcn_readfirstlane(a.seg_n[b]);
+    const Segments seg = series_segments(a, b);
+    const int M = seg.M, N = seg.N;
     double* const st = a.stats + b * 2 * (size_t)V;
     if (M <= 0 || N <= 0 || (int64_t)M * N < 4) {
         if (w == 0 && own) st[v] = st[(size_t)V + v] = qnan;
         return;
     }
-    const int* const seg0 = a.seg_start + b * a.M_max;
-    double zc[1] = {SOURCE == DIAG_RASTER ? a.z[vc] : 0.0};
+    const int* const seg0 = series_starts(a, b);
+    const double zc = SOURCE == SERIES_RASTER ? a.z[vc] : 0.0;
     double s = 0.0, lo = (double)INFINITY, hi = -(double)INFINITY;
     int nf = 0;
     for (int m = 0; m < M; ++m) {
         const int r0 = __builtin_amdgcn_readfirstlane(seg0[m]);
         for (int t = w; t < N; t += CORR_WAVES) {
-            double x[1];
-            const size_t src = corr_row(a, b, r0, t);
-            if (SOURCE == DIAG_PLAIN) x[0] = a.x[src * (size_t)V + vc];
-            else corr_layers<1>(corr_slot(a, src, lane), zc, x);
-            s += x[0];
-            lo = fmin(lo, x[0]);
-            hi = fmax(hi, x[0]);
-            nf |= (__double2hiint(x[0]) & 0x7ff00000) == 0x7ff00000 ? 1 : 0;
+            double x;
+            const size_t src = series_row(a, b, r0 + t);
+            if (SOURCE == SERIES_PLAIN) x = a.x[src * (size_t)V + vc];
+            else layers<1>(slot_load(a, src, lane), &zc, &x);
+            s += x;
+            lo = fmin(lo, x);
+            hi = fmax(hi, x);
+            nf |= (__double2hiint(x) & 0x7ff00000) == 0x7ff00000 ? 1 : 0;
         }
     }
     red[0][w][lane] = s;
@@ -154,13 +103,13 @@ __global__ __launch_bounds__(CORR_WAVES * 64) void k_series_correlation(CorrArgs
     extern __shared__ __attribute__((aligned(16))) double corr_lds[];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int V = a.V, W = a.W, ntiles = (V + 15) / 16, nstrips = (ntiles + CORR_WAVES - 1) / CORR_WAVES;
+    const int V = a.V, W = a.reach, ntiles = (V + 15) / 16, nstrips = (ntiles + CORR_WAVES - 1) / CORR_WAVES;
     const int DJ = (W + 15) / 16 + 1;                                  // tile diagonals a tile row meets: J - I = 0 .. ceil(W / 16)
     const int panel = (int)(blockIdx.x % npanels);
     const int strip = (int)((blockIdx.x / npanels) % nstrips);
     const size_t b = blockIdx.x / npanels / nstrips;
-    const int M = __builtin_amdgcn_readfirstlane(min(a.seg_m[b], a.M_max));
-    const int N = __builtin_amdgcn_readfirstlane(a.seg_n[b]);
+    const Segments seg = series_segments(a, b);
+    const int M = seg.M, N = seg.N;
     if (M <= 0 || N <= 0 || (int64_t)M * N < 4) return;                // (the finish writes NaN: the flags say so)
     const int n = M * N;
     const int Jbase = strip * CORR_WAVES + CORR_NACC * panel;          // the panel's first B tile
@@ -187,9 +136,9 @@ __global__ __launch_bounds__(CORR_WAVES * 64) void k_series_correlation(CorrArgs
         vcol[g] = vc;
         live[g] = q < ncol && v < V && st[(size_t)V + vc] > 0.0;
         mean[g] = st[vc];
-        zc[g] = SOURCE == DIAG_RASTER ? a.z[vc] : 0.0;
+        zc[g] = SOURCE == SERIES_RASTER ? a.z[vc] : 0.0;
     }
-    const int* const seg0 = a.seg_start + b * a.M_max;
+    const int* const seg0 = series_starts(a, b);
     const int I = strip * CORR_WAVES + w;
     const int nq = I < ntiles ? min(min(CORR_NACC, DJ - CORR_NACC * panel), ntiles - (I + CORR_NACC * panel)) : 0;      // this wave's tiles (<= 0: none)
     corr_double4 acc[CORR_NACC];
@@ -203,22 +152,15 @@ __global__ __launch_bounds__(CORR_WAVES * 64) void k_series_correlation(CorrArgs
             double x[CORR_MAX_GROUPS] = {0.0, 0.0, 0.0, 0.0};
             if (r < n) {
                 const int m = r / N;
-                const size_t src = corr_row(a, b, __builtin_amdgcn_readfirstlane(seg0[m]), r - m * N);
-                if (SOURCE == DIAG_PLAIN) {
+                const size_t src = series_row(a, b, __builtin_amdgcn_readfirstlane(seg0[m]) + r - m * N);
+                if (SOURCE == SERIES_PLAIN) {
 #pragma unroll
                     for (int g = 0; g < CORR_MAX_GROUPS; ++g)
                         if (live[g]) x[g] = a.x[src * (size_t)V + vcol[g]];
                 } else {
-                    const CorrSlot slot = corr_slot(a, src, lane);
-                    if (ngroups <= 2) {
-                        const double z2[2] = {zc[0], zc[1]};
-                        double x2[2];
-                        corr_layers<2>(slot, z2, x2);
-                        x[0] = x2[0];
-                        x[1] = x2[1];
-                    } else {
-                        corr_layers<CORR_MAX_GROUPS>(slot, zc, x);
-                    }
+                    const Slot slot = slot_load(a, src, lane);
+                    if (ngroups <= 2) layers<2>(slot, zc, x);          // (the columns past 128 stay 0: not staged)
+                    else layers<CORR_MAX_GROUPS>(slot, zc, x);
                 }
             }
 #pragma unroll

@@ -1,9 +1,8 @@
 // Chain diagnostics of regularly spaced series (the rule: include/geobipy_amd.h gbp_series_diagnostics and
 // geobipy_amd/ensembles.py diagnostics_reference): per sounding and variable the split-chain autocovariances up to lag L, Geyer's
 // initial monotone sequence, tau, ESS, split R-hat and the Monte-Carlo standard error.  Included by gbp_fdem.hip after gbp_ensemble.h.
-//   k_series_diagnostics<PLAIN>    reads x[b, t, v] (f64 [B, n_rows, V], v contiguous)
-//   k_series_diagnostics<RASTER>   builds x[t, cell] = log10 of the conductivity of the layer holding the cell centre from ens_k /
-//                                  ens_edges / ens_sigma on the fly (the count of k_ensemble_raster); [B, n_slots, n_depth] never exists
+// k_series_diagnostics<SERIES_PLAIN / SERIES_RASTER>: the two sources of gbp_ensemble_series.h (RASTER: the log10 conductivity at the
+// cell centres, built on the fly).
 // One workgroup of 16 waves per (sounding, tile of 64 variables); a lane owns a variable, the waves share lags and times.
 //   pass 1   every used row once: per segment the sum (-> mean_m), over all segments min, max and a non-finite flag.  A tile whose 64
 //            variables are all constant or non-finite ends here (the deep cells of a depth axis).
@@ -22,59 +21,44 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gbp_ensemble_series.h"
+
 namespace ensemble {
 
-enum { DIAG_PLAIN = 0, DIAG_RASTER = 1 };
 constexpr int DIAG_WAVES = 16, DIAG_TB = 8, DIAG_LG = 16, DIAG_MIRROR = DIAG_TB + DIAG_LG - 2;       // 22: a run is at most 23 rows
-constexpr int DIAG_MAX_M = 16;
 constexpr int DIAG_RING_ROWS = 296;                                   // R + MIRROR <= 296: L = 255 leaves CH = 16
-constexpr size_t DIAG_LDS_BYTES = (size_t)(DIAG_MAX_M + DIAG_RING_ROWS) * 64 * sizeof(double);       // 159 744 B <= 160 KiB
+constexpr size_t DIAG_LDS_BYTES = (size_t)(SERIES_MAX_M + DIAG_RING_ROWS) * 64 * sizeof(double);     // 159 744 B <= 160 KiB
 
-struct DiagArgs {
-    int n_rows, V;                    // rows per sounding (PLAIN: of x; RASTER: slots), variables (RASTER: depth cells)
-    const double* x;                  // PLAIN
-    int K;                            // RASTER
-    const int* ens_k;
-    const double* ens_edges;
-    const double* ens_sigma;
-    const double* z;
-    int M_max, max_lag;
-    const int* seg_start;             // [B, M_max]
-    const int* seg_m;                 // [B]
-    const int* seg_n;                 // [B]
+struct DiagArgs : SeriesArgs {           // reach: max_lag
     double* stats;                    // [B, 6, V]
     int* pairs;                       // [B, V]
     double* rho;                      // NULL or [B, max_lag + 1, V]
 };
 
-// The value of variable v (this lane's) in row `row` of sounding b; one wave per row.  RASTER: the slot's edges and the log10 of its
-// conductivities sit one per lane; the layer is #{l < k - 1 : edges[l] <= z}, the log10 comes from the lane that holds the layer
-// (an empty slot: NaN in every lane).
+// The value of variable v (this lane's; RASTER: the centre zc) in row `row` of sounding b; one wave per row.  The row is clamped and
+// the one centre counted here, in the order this kernel always had: through series_row and layers<1> the same rule compiles to
+// other code.
 template <int SOURCE>
 __device__ __forceinline__ double diag_fetch(const DiagArgs& a, size_t b, int row, int v, int lane, double zc)
 {
-    row = min(max(row, 0), a.n_rows - 1);                              // (a segment outside the rows is the caller's error: never a fault)
-    if (SOURCE == DIAG_PLAIN) return a.x[(b * a.n_rows + row) * (size_t)a.V + v];
+    row = min(max(row, 0), a.n_rows - 1);                              // (series_row's clamp)
     const size_t src = b * a.n_rows + row;
-    const int k = __builtin_amdgcn_readfirstlane(min(max(a.ens_k[src], 0), a.K));
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const double e = lane < k - 1 ? a.ens_edges[src * a.K + lane] : (double)INFINITY;
-    const double s = lane < k ? log10(a.ens_sigma[src * a.K + lane]) : qnan;
-    const int e_lo = __double2loint(e), e_hi = __double2hiint(e);
-    int layer = 0;
-    for (int l = 0; l < k - 1; ++l) {
-        const double el = __hiloint2double(__builtin_amdgcn_readlane(e_hi, l), __builtin_amdgcn_readlane(e_lo, l));
+    if (SOURCE == SERIES_PLAIN) return a.x[src * (size_t)a.V + v];
+    const Slot q = slot_load(a, src, lane);
+    int layer = 0;                                                     // (layers<1>)
+    for (int l = 0; l < q.k - 1; ++l) {
+        const double el = __hiloint2double(__builtin_amdgcn_readlane(q.e_hi, l), __builtin_amdgcn_readlane(q.e_lo, l));
         layer += el <= zc ? 1 : 0;
     }
-    return __shfl(s, layer, 64);
+    return __shfl(q.s, layer, 64);
 }
 
 template <int SOURCE>
 __global__ __launch_bounds__(DIAG_WAVES * 64) void k_series_diagnostics(DiagArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double diag_lds[];
-    double* const sh_mean = diag_lds;                                  // [DIAG_MAX_M][64]
-    double* const ring = diag_lds + DIAG_MAX_M * 64;                   // [DIAG_RING_ROWS][64]; pass 1 and the finish use it as scratch
+    double* const sh_mean = diag_lds;                                  // [SERIES_MAX_M][64]
+    double* const ring = diag_lds + SERIES_MAX_M * 64;                 // [DIAG_RING_ROWS][64]; pass 1 and the finish use it as scratch
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int V = a.V, tiles = (V + 63) / 64;
@@ -83,8 +67,8 @@ __global__ __launch_bounds__(DIAG_WAVES * 64) void k_series_diagnostics(DiagArgs
     const bool own = v < V;
     const int vc = min(v, V - 1);
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    const int M = __builtin_amdgcn_readfirstlane(min(a.seg_m[b], a.M_max));
-    const int N = __builtin_amdgcn_readfirstlane(a.seg_n[b]);
+    const Segments seg = series_segments(a, b);
+    const int M = seg.M, N = seg.N;
     double* const st = a.stats + b * 6 * (size_t)V;
     if (M <= 0 || N < 4) {
         if (w == 0 && own) {
@@ -92,17 +76,17 @@ __global__ __launch_bounds__(DIAG_WAVES * 64) void k_series_diagnostics(DiagArgs
             a.pairs[b * V + v] = 0;
         }
         if (a.rho != nullptr && own)
-            for (int l = w; l <= a.max_lag; l += DIAG_WAVES) a.rho[(b * (a.max_lag + 1) + l) * (size_t)V + v] = qnan;
+            for (int l = w; l <= a.reach; l += DIAG_WAVES) a.rho[(b * (a.reach + 1) + l) * (size_t)V + v] = qnan;
         return;
     }
-    int L = min(a.max_lag, N - 1);
+    int L = min(a.reach, N - 1);
     L -= (L & 1) ? 0 : 1;
     const int nlg = (L + DIAG_LG) / DIAG_LG, LPAD = nlg * DIAG_LG, ntg = DIAG_WAVES / nlg;
     const int CH = min((DIAG_RING_ROWS - DIAG_MIRROR - LPAD) & ~(DIAG_TB - 1), DIAG_TB * ntg * 4);
     const int R = CH + LPAD;
     const int lg = w % nlg, tg = w / nlg;
-    const int* const seg0 = a.seg_start + b * a.M_max;
-    const double zc = SOURCE == DIAG_RASTER ? a.z[vc] : 0.0;
+    const int* const seg0 = series_starts(a, b);
+    const double zc = SOURCE == SERIES_RASTER ? a.z[vc] : 0.0;
 
     // ---- pass 1: sums, min, max, non-finite
     double mn = (double)INFINITY, mx = -(double)INFINITY, gsum = 0.0;
@@ -201,14 +185,14 @@ __global__ __launch_bounds__(DIAG_WAVES * 64) void k_series_diagnostics(DiagArgs
     __syncthreads();
     if (w != 0) {
         if (a.rho != nullptr && own)                                   // (beyond L: NaN; wave 0 writes 0 .. L)
-            for (int l = L + w; l <= a.max_lag; l += DIAG_WAVES - 1) a.rho[(b * (a.max_lag + 1) + l) * (size_t)V + v] = qnan;
+            for (int l = L + w; l <= a.reach; l += DIAG_WAVES - 1) a.rho[(b * (a.reach + 1) + l) * (size_t)V + v] = qnan;
         return;
     }
     const double dM = (double)M, dN = (double)N, bessel = dN / (dN - 1.0);
     const double gm = gsum / dM;
     double out[6];
     int np = 0;
-    double* const rho = a.rho != nullptr && own ? a.rho + b * (a.max_lag + 1) * (size_t)V + v : nullptr;
+    double* const rho = a.rho != nullptr && own ? a.rho + b * (a.reach + 1) * (size_t)V + v : nullptr;
     if (bad || constant) {
         out[0] = bad ? qnan : mn;
         out[1] = bad ? qnan : 0.0;

@@ -1832,17 +1832,28 @@ extern "C" gbp_status gbp_ensemble_rebin(int B, int n_ensemble, int K, const int
     return GBP_OK;
 }
 
-// Chain diagnostics (csrc/gbp_ensemble_diag.h k_series_diagnostics; the rule: include/geobipy_amd.h): one workgroup per (sounding, 64
-// variables).  The checks the two entries share; `entry` names the caller in gbp_last_error.
-static gbp_status series_diagnostics_launch(const char* entry, int source, int B, ensemble::DiagArgs a, bool pointers, void* stream)
+// The refusals the entries on a regularly spaced series share (csrc/gbp_ensemble_series.h), in the order a bad call meets them.  The
+// launcher's own: a.reach outside lo .. hi, refused with its literal `refusal` (one %s: the entry), and `outputs`, its output pointers
+// are there.  B == 0 passes before any pointer is looked at (an empty block: empty device arrays have no address): a launcher returns on it too.
+static gbp_status series_check(const char* entry, int source, int B, const ensemble::SeriesArgs& a, int lo, int hi, const char* refusal, bool outputs)
 {
     if (B < 0 || a.n_rows < 1 || a.V < 1) return fail(GBP_ERR_INVALID_ARG, "%s: negative or zero size", entry);
     if (a.n_rows > 32768) return fail(GBP_ERR_INVALID_ARG, "%s: more than 32 768 rows", entry);
-    if (a.max_lag < 1 || a.max_lag > 255) return fail(GBP_ERR_INVALID_ARG, "%s: max_lag outside 1 .. 255", entry);
-    if (a.M_max < 1 || a.M_max > ensemble::DIAG_MAX_M) return fail(GBP_ERR_INVALID_ARG, "%s: M_max outside 1 .. 16", entry);
-    if (source == ensemble::DIAG_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
-    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
-    if (!pointers || !a.seg_start || !a.seg_m || !a.seg_n || !a.stats || !a.pairs) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    if (a.reach < lo || a.reach > hi) return fail(GBP_ERR_INVALID_ARG, refusal, entry);
+    if (a.M_max < 1 || a.M_max > ensemble::SERIES_MAX_M) return fail(GBP_ERR_INVALID_ARG, "%s: M_max outside 1 .. 16", entry);
+    if (source == ensemble::SERIES_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
+    if (B == 0) return GBP_OK;
+    const bool inputs = source == ensemble::SERIES_RASTER ? a.ens_k && a.ens_edges && a.ens_sigma && a.z : a.x != nullptr;
+    if (!inputs || !outputs || !a.seg_start || !a.seg_m || !a.seg_n) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    return GBP_OK;
+}
+
+// Chain diagnostics (csrc/gbp_ensemble_diag.h k_series_diagnostics; the rule: include/geobipy_amd.h): one workgroup per (sounding, 64
+// variables).
+static gbp_status series_diagnostics_launch(const char* entry, int source, int B, ensemble::DiagArgs a, void* stream)
+{
+    const gbp_status status = series_check(entry, source, B, a, 1, 255, "%s: max_lag outside 1 .. 255", a.stats && a.pairs);
+    if (status != GBP_OK || B == 0) return status;
     const int64_t blocks = (int64_t)B * ((a.V + 63) / 64);
     if (blocks > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "%s: B * tiles out of range", entry);
     const int lds = (int)ensemble::DIAG_LDS_BYTES;
@@ -1858,62 +1869,54 @@ static gbp_status series_diagnostics_launch(const char* entry, int source, int B
         GBP_HIP(hipGetLastError());
         return GBP_OK;
     };
-    return source == ensemble::DIAG_RASTER ? launch(ensemble::k_series_diagnostics<ensemble::DIAG_RASTER>)
-                                           : launch(ensemble::k_series_diagnostics<ensemble::DIAG_PLAIN>);
+    return source == ensemble::SERIES_RASTER ? launch(ensemble::k_series_diagnostics<ensemble::SERIES_RASTER>)
+                                             : launch(ensemble::k_series_diagnostics<ensemble::SERIES_PLAIN>);
 }
 
 extern "C" gbp_status gbp_series_diagnostics(int B, int n_rows, int V, const double* x, int M_max, const int32_t* seg_start, const int32_t* seg_m,
                                              const int32_t* seg_n, int max_lag, double* stats, int32_t* pairs, double* rho, void* stream)
 {
-    ensemble::DiagArgs a = {};
-    a.n_rows = n_rows; a.V = V; a.x = x; a.M_max = M_max; a.max_lag = max_lag;
-    a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.pairs = pairs; a.rho = rho;
-    return series_diagnostics_launch("gbp_series_diagnostics", ensemble::DIAG_PLAIN, B, a, x != nullptr, stream);
+    const ensemble::DiagArgs a = {{n_rows, V, x, 0, nullptr, nullptr, nullptr, nullptr, M_max, max_lag, seg_start, seg_m, seg_n}, stats, pairs, rho};
+    return series_diagnostics_launch("gbp_series_diagnostics", ensemble::SERIES_PLAIN, B, a, stream);
 }
 
 extern "C" gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
                                                int n_depth, const double* z, int M_max, const int32_t* seg_start, const int32_t* seg_m,
                                                const int32_t* seg_n, int max_lag, double* stats, int32_t* pairs, double* rho, void* stream)
 {
-    ensemble::DiagArgs a = {};
-    a.n_rows = n_slots; a.V = n_depth; a.K = K; a.ens_k = ens_k; a.ens_edges = ens_edges; a.ens_sigma = ens_sigma; a.z = z;
-    a.M_max = M_max; a.max_lag = max_lag; a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.pairs = pairs; a.rho = rho;
-    return series_diagnostics_launch("gbp_ensemble_diagnostics", ensemble::DIAG_RASTER, B, a, ens_k && ens_edges && ens_sigma && z, stream);
+    const ensemble::DiagArgs a = {{n_slots, n_depth, nullptr, K, ens_k, ens_edges, ens_sigma, z, M_max, max_lag, seg_start, seg_m, seg_n}, stats, pairs, rho};
+    return series_diagnostics_launch("gbp_ensemble_diagnostics", ensemble::SERIES_RASTER, B, a, stream);
 }
 
 #include "gbp_ensemble_corr.h"
 
 // Correlation between variables (csrc/gbp_ensemble_corr.h; the rule: include/geobipy_amd.h): the moments, the MFMA kernel, then the two
-// streaming kernels of the finish, in stream order.  The checks the two entries share; `entry` names the caller in gbp_last_error.
-static gbp_status series_correlation_launch(const char* entry, int source, int B, ensemble::CorrArgs a, int normalise, bool pointers, void* stream)
+// streaming kernels of the finish, in stream order.
+static gbp_status series_correlation_launch(const char* entry, int source, int B, ensemble::CorrArgs a, int normalise, void* stream)
 {
     using namespace ensemble;
-    if (B < 0 || a.n_rows < 1 || a.V < 1) return fail(GBP_ERR_INVALID_ARG, "%s: negative or zero size", entry);
-    if (a.n_rows > 32768) return fail(GBP_ERR_INVALID_ARG, "%s: more than 32 768 rows", entry);
-    if (a.W < 0 || a.W > a.V - 1) return fail(GBP_ERR_INVALID_ARG, "%s: band_width outside 0 .. V - 1", entry);
-    if (a.M_max < 1 || a.M_max > DIAG_MAX_M) return fail(GBP_ERR_INVALID_ARG, "%s: M_max outside 1 .. 16", entry);
-    if (source == DIAG_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
-    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
-    if (!pointers || !a.seg_start || !a.seg_m || !a.seg_n || !a.stats || !a.band) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    const int W = a.reach;
+    const gbp_status status = series_check(entry, source, B, a, 0, a.V - 1, "%s: band_width outside 0 .. V - 1", a.stats && a.band);
+    if (status != GBP_OK || B == 0) return status;
     const int ntiles = (a.V + 15) / 16, nstrips = (ntiles + CORR_WAVES - 1) / CORR_WAVES;
-    const int DJ = (a.W + 15) / 16 + 1, npanels = (DJ + CORR_NACC - 1) / CORR_NACC;
+    const int DJ = (W + 15) / 16 + 1, npanels = (DJ + CORR_NACC - 1) / CORR_NACC;
     const int64_t moment_blocks = (int64_t)B * ((a.V + 63) / 64), blocks = (int64_t)B * nstrips * npanels;
-    const int64_t entries = (int64_t)B * a.V * (a.W + 1), finish_blocks = (entries + 255) / 256;
+    const int64_t entries = (int64_t)B * a.V * (W + 1), finish_blocks = (entries + 255) / 256;
     if (moment_blocks > 0x7fffffffLL || blocks > 0x7fffffffLL || finish_blocks > 0x7fffffffLL)
         return fail(GBP_ERR_INVALID_ARG, "%s: B * V * (band_width + 1) out of range", entry);
     const int ncol = (std::min(DJ, CORR_NACC) + CORR_WAVES - 1) * 16 + (npanels > 1 ? CORR_WAVES * 16 : 0);      // the widest staged row
     const size_t lds = (size_t)CORR_CH * (ncol + ((ncol & 31) == 0 ? 16 : 0)) * sizeof(double);                    // <= CORR_LDS_BYTES < 64 KiB
     hipStream_t s = (hipStream_t)stream;
-    if (source == DIAG_RASTER) {
-        hipLaunchKernelGGL(k_series_moments<DIAG_RASTER>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
-        hipLaunchKernelGGL(k_series_correlation<DIAG_RASTER>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
+    if (source == SERIES_RASTER) {
+        hipLaunchKernelGGL(k_series_moments<SERIES_RASTER>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
+        hipLaunchKernelGGL(k_series_correlation<SERIES_RASTER>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
     } else {
-        hipLaunchKernelGGL(k_series_moments<DIAG_PLAIN>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
-        hipLaunchKernelGGL(k_series_correlation<DIAG_PLAIN>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
+        hipLaunchKernelGGL(k_series_moments<SERIES_PLAIN>, dim3((unsigned)moment_blocks), dim3(CORR_WAVES * 64), 0, s, a);
+        hipLaunchKernelGGL(k_series_correlation<SERIES_PLAIN>, dim3((unsigned)blocks), dim3(CORR_WAVES * 64), lds, s, a, npanels);
     }
     const size_t cells = (size_t)B * a.V;
-    hipLaunchKernelGGL(k_correlation_sd, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, cells, a.V, a.W, a.band, a.stats);
-    hipLaunchKernelGGL(k_correlation_finish, dim3((unsigned)finish_blocks), dim3(256), 0, s, (size_t)entries, a.V, a.W, normalise, a.stats, a.band);
+    hipLaunchKernelGGL(k_correlation_sd, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, cells, a.V, W, a.band, a.stats);
+    hipLaunchKernelGGL(k_correlation_finish, dim3((unsigned)finish_blocks), dim3(256), 0, s, (size_t)entries, a.V, W, normalise, a.stats, a.band);
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
@@ -1921,20 +1924,16 @@ static gbp_status series_correlation_launch(const char* entry, int source, int B
 extern "C" gbp_status gbp_series_correlation(int B, int n_rows, int V, const double* x, int M_max, const int32_t* seg_start, const int32_t* seg_m,
                                              const int32_t* seg_n, int band_width, int normalise, double* stats, double* band, void* stream)
 {
-    ensemble::CorrArgs a = {};
-    a.n_rows = n_rows; a.V = V; a.x = x; a.M_max = M_max; a.W = band_width;
-    a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.band = band;
-    return series_correlation_launch("gbp_series_correlation", ensemble::DIAG_PLAIN, B, a, normalise, x != nullptr, stream);
+    const ensemble::CorrArgs a = {{n_rows, V, x, 0, nullptr, nullptr, nullptr, nullptr, M_max, band_width, seg_start, seg_m, seg_n}, stats, band};
+    return series_correlation_launch("gbp_series_correlation", ensemble::SERIES_PLAIN, B, a, normalise, stream);
 }
 
 extern "C" gbp_status gbp_ensemble_correlation(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
                                                int n_depth, const double* z, int M_max, const int32_t* seg_start, const int32_t* seg_m,
                                                const int32_t* seg_n, int band_width, int normalise, double* stats, double* band, void* stream)
 {
-    ensemble::CorrArgs a = {};
-    a.n_rows = n_slots; a.V = n_depth; a.K = K; a.ens_k = ens_k; a.ens_edges = ens_edges; a.ens_sigma = ens_sigma; a.z = z;
-    a.M_max = M_max; a.W = band_width; a.seg_start = seg_start; a.seg_m = seg_m; a.seg_n = seg_n; a.stats = stats; a.band = band;
-    return series_correlation_launch("gbp_ensemble_correlation", ensemble::DIAG_RASTER, B, a, normalise, ens_k && ens_edges && ens_sigma && z, stream);
+    const ensemble::CorrArgs a = {{n_slots, n_depth, nullptr, K, ens_k, ens_edges, ens_sigma, z, M_max, band_width, seg_start, seg_m, seg_n}, stats, band};
+    return series_correlation_launch("gbp_ensemble_correlation", ensemble::SERIES_RASTER, B, a, normalise, stream);
 }
 
 extern "C" gbp_status gbp_band_runs(int B, int V, int band_width, const double* band, double threshold, int32_t* up, int32_t* down,

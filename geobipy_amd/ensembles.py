@@ -347,6 +347,25 @@ def _check_segments(seg_start, seg_m, seg_n, B, n_rows, what):
     return seg_start.contiguous(), seg_m.contiguous(), seg_n.contiguous()
 
 
+def _check_series(x, seg_start, seg_m, seg_n, what, entry, check_v=lambda V: None):
+    """The checks ``series_diagnostics`` and ``series_correlation`` share, in their order: tensors, x, ``check_v(V)`` (the entry's own
+    check that needs V), the segment lists, and the device last.  Returns x and the lists, contiguous, and what ``check_v`` gave."""
+    _are_tensors((x, seg_start, seg_m, seg_n), what, entry)
+    if x.dtype != torch.float64:
+        raise TypeError("%s: x is float64" % what)
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
+        raise ValueError("%s: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1" % what)
+    own = check_v(x.shape[2])
+    seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, x.shape[0], x.shape[1], what)
+    _on_device((x, seg_start, seg_m, seg_n), what, entry)
+    return x.contiguous(), seg_start, seg_m, seg_n, own
+
+
+def _check_block(block, what):
+    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
+        raise ValueError("%s: block must be a positive integer" % what)
+
+
 def _unpack(stats, pairs, rho, seg_n, max_lag):
     out = {name: stats[:, i] for i, name in enumerate(STAT_NAMES)}
     L = torch.clamp(seg_n.to(torch.int64) - 1, max=max_lag)
@@ -364,15 +383,8 @@ def series_diagnostics(x, seg_start, seg_m, seg_n, max_lag=255, return_rho=False
     {mean, sd, rhat, tau, ess, mcse f64 [B, V], pairs int32 [B, V], truncated bool [B, V] (the sum ran into the lag cap: ess is an
     over-estimate)} and, with ``return_rho``, rho f64 [B, max_lag + 1, V].  One kernel (gbp_series_diagnostics)."""
     max_lag = check_max_lag(max_lag)
-    _are_tensors((x, seg_start, seg_m, seg_n), "series_diagnostics", "gbp_series_diagnostics")
-    if x.dtype != torch.float64:
-        raise TypeError("series_diagnostics: x is float64")
-    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
-        raise ValueError("series_diagnostics: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1")
-    B, n_rows, V = x.shape
-    seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, B, n_rows, "series_diagnostics")
-    _on_device((x, seg_start, seg_m, seg_n), "series_diagnostics", "gbp_series_diagnostics")
-    x, dev = x.contiguous(), x.device
+    x, seg_start, seg_m, seg_n, _ = _check_series(x, seg_start, seg_m, seg_n, "series_diagnostics", "gbp_series_diagnostics")
+    (B, n_rows, V), dev = x.shape, x.device
     stats = torch.empty((B, 6, V), dtype=torch.float64, device=dev)
     pairs = torch.empty((B, V), dtype=torch.int32, device=dev)
     rho = torch.empty((B, max_lag + 1, V), dtype=torch.float64, device=dev) if return_rho else None
@@ -393,6 +405,28 @@ def check_chains(chains, n_slots):
     return int(chains)
 
 
+def _check_chained(ens, chains, what, entry, misfit):
+    """What ``diagnostics`` and ``correlation`` ask of an ensemble whose slot axis holds ``chains`` chains (``misfit``: it takes part),
+    refused in this order: tensors, shapes, dtypes, sizes, and the device last.  Returns k, edges, sigma (contiguous), B, n_slots, K,
+    C, the lists of ``segments`` for the chains' filled slots on the device (seg_start, seg_m, seg_n) and n_chains_used."""
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    tensors = (k, edges, sigma, ens.misfit) if misfit else (k, edges, sigma)
+    _are_tensors(tensors, what, entry)
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape) or (misfit and ens.misfit.shape != k.shape):
+        raise ValueError("ensemble: %s [B, n_slots], edges and sigma [B, n_slots, K]" % ("k and misfit" if misfit else "k"))
+    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or (misfit and not ens.misfit.dtype.is_floating_point):
+        raise TypeError("ensemble: k is int32, edges and sigma are float64" + (", misfit is floating point" if misfit else ""))
+    B, ns, K = edges.shape
+    C = check_chains(chains, ns)
+    if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
+        raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
+    _on_device(tensors, what, entry)
+    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
+    count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
+    start, seg_m, seg_n, used = (torch.as_tensor(a).to(dev) for a in segments(count, ns // C))
+    return k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used
+
+
 def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho=False):
     """Did the chains run long enough?  Per sounding and cell of ``depth_edges`` [n_depth + 1] the diagnostics of the series log10
     conductivity at the cell centre over the kept models (``diagnostics_reference`` states the rule, ``segments`` the split of every
@@ -406,24 +440,9 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
     if torch.is_tensor(ens.k) and ens.k.ndim == 2:
         check_chains(chains, ens.k.shape[1])
     z_np = centres(depth_edges)
-    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
-        raise ValueError("diagnostics: block must be a positive integer")
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma, ens.misfit), "diagnostics", "gbp_ensemble_diagnostics")
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape) or ens.misfit.shape != k.shape:
-        raise ValueError("ensemble: k and misfit [B, n_slots], edges and sigma [B, n_slots, K]")
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or not ens.misfit.dtype.is_floating_point:
-        raise TypeError("ensemble: k is int32, edges and sigma are float64, misfit is floating point")
-    B, ns, K = edges.shape
-    C = check_chains(chains, ns)
-    if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
-        raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
-    _on_device((k, edges, sigma, ens.misfit), "diagnostics", "gbp_ensemble_diagnostics")
-    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
-    nd = int(z_np.size)
-    count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
-    start_np, m_np, n_np, used_np = segments(count, ns // C)
-    start, seg_m, seg_n = (torch.as_tensor(a).to(dev) for a in (start_np, m_np, n_np))
+    _check_block(block, "diagnostics")
+    k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "diagnostics", "gbp_ensemble_diagnostics", misfit=True)
+    nd, dev = int(z_np.size), k.device
     stats = torch.empty((B, 6, nd), dtype=torch.float64, device=dev)
     pairs = torch.empty((B, nd), dtype=torch.int32, device=dev)
     rho = torch.empty((B, max_lag + 1, nd), dtype=torch.float64, device=dev) if return_rho else None
@@ -445,7 +464,7 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
         out[name + "_k"], out[name + "_misfit"] = two[name][:, 0], two[name][:, 1]
     thin = int(ens.thin)
     out["tau_iterations"], out["tau_iterations_k"], out["tau_iterations_misfit"] = out["tau"] * thin, out["tau_k"] * thin, out["tau_misfit"] * thin
-    out["n_chains_used"], out["segment_length"], out["n_segments"] = torch.as_tensor(used_np).to(dev), seg_n, seg_m
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
     ess = out["ess"]
     lowest = torch.where(torch.isfinite(ess), ess, torch.full_like(ess, float("inf"))).min(dim=1).values if nd else torch.full((B,), float("inf"), device=dev)
     out["ess_min"] = torch.where(torch.isfinite(lowest), lowest, torch.full_like(lowest, float("nan")))
@@ -596,16 +615,9 @@ def series_correlation(x, seg_start, seg_m, seg_n, band=None, normalise=True):
     device, segments as ``series_diagnostics`` takes them.  Returns {mean, sd f64 [B, V], band f64 [B, V, W + 1]}: band[b, c, j] =
     R(c, c + j) (``normalise=False``: the covariance), W = ``band`` clipped to V - 1 (None: V - 1, the whole matrix;
     ``band_to_matrix`` unfolds it).  gbp_series_correlation: centred products on the fp64 matrix cores."""
-    _are_tensors((x, seg_start, seg_m, seg_n), "series_correlation", "gbp_series_correlation")
-    if x.dtype != torch.float64:
-        raise TypeError("series_correlation: x is float64")
-    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
-        raise ValueError("series_correlation: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1")
-    B, n_rows, V = x.shape
-    W = check_band(band, V)
-    seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, B, n_rows, "series_correlation")
-    _on_device((x, seg_start, seg_m, seg_n), "series_correlation", "gbp_series_correlation")
-    x, dev = x.contiguous(), x.device
+    x, seg_start, seg_m, seg_n, W = _check_series(x, seg_start, seg_m, seg_n, "series_correlation", "gbp_series_correlation",
+                                                  check_v=lambda V: check_band(band, V))
+    (B, n_rows, V), dev = x.shape, x.device
     stats = torch.empty((B, 2, V), dtype=torch.float64, device=dev)
     out = torch.empty((B, V, W + 1), dtype=torch.float64, device=dev)
     if B > 0:
@@ -658,23 +670,9 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     nd = int(z_np.size)
     W = check_band(band, nd)
     threshold = check_threshold(threshold)
-    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
-        raise ValueError("correlation: block must be a positive integer")
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma), "correlation", "gbp_ensemble_correlation")
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
-        raise ValueError("ensemble: k [B, n_slots], edges and sigma [B, n_slots, K]")
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64:
-        raise TypeError("ensemble: k is int32, edges and sigma are float64")
-    B, ns, K = edges.shape
-    C = check_chains(chains, ns)
-    if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
-        raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
-    _on_device((k, edges, sigma), "correlation", "gbp_ensemble_correlation")
-    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
-    count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
-    start_np, m_np, n_np, used_np = segments(count, ns // C)
-    start, seg_m, seg_n = (torch.as_tensor(a).to(dev) for a in (start_np, m_np, n_np))
+    _check_block(block, "correlation")
+    k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "correlation", "gbp_ensemble_correlation", misfit=False)
+    dev = k.device
     step = max(1, BAND_BLOCK_BYTES // (nd * (W + 1) * 8)) if block is None else int(block)
     stats = torch.empty((B, 2, nd), dtype=torch.float64, device=dev)
     full = torch.empty((B, nd, W + 1), dtype=torch.float64, device=dev) if keep_band else None
@@ -701,7 +699,7 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     out["resolution_cells"] = up + down + 1
     out["resolution_length"] = resolution_length(up, down, depth_edges, live=live)
     out["resolution_closed"] = out["closed_up"] & out["closed_down"]
-    out["n_chains_used"], out["segment_length"], out["n_segments"] = torch.as_tensor(used_np).to(dev), seg_n, seg_m
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
     return out
 
 

@@ -235,7 +235,7 @@ def test_raster_entry_against_the_rule(K, per, counts):
     exactly at a cell centre, 4 k = K in every slot and a deepest layer that never changes; counts 0 / 7 (no usable chain) / 8 / full."""
     dev = _dev()
     C = len(counts[0])
-    for n_depth, W in ((1, 0), (65, 64), (440, 20)):
+    for n_depth, W in ((1, 0), (65, 64), (130, 129), (440, 20)):        # 130, 129: two panels, and panel 0 stages 144 columns (three lane groups)
         rng = np.random.default_rng(1000 * K + 10 * C + n_depth)
         depth_edges = np.linspace(0.0, 110.0, n_depth + 1)
         z = ensembles.centres(depth_edges)
