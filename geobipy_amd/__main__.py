@@ -72,7 +72,16 @@ def parse(argv=None):
                    help="vertical resolution from the ensemble (needs --ensemble): the posterior correlation between depth cells up to BAND "
                         "cells apart (>= 0, default 64) and the thickness over which it stays >= THRESHOLD (0 < THRESHOLD < 1, default 0.5): "
                         "ensemble_resolution_length, ensemble_resolution_cells, ensemble_resolution_closed in the summaries")
+    p.add_argument("--ensemble-families", type=int, nargs="?", const=4, default=None, metavar="QMAX",
+                   help="model families from the ensemble (needs --ensemble): the representative (medoid) model of every sounding and up to "
+                        "QMAX families of kept models (1 .. 8, default 4): ensemble_central_*, ensemble_families_n, ensemble_family_* in the "
+                        "summaries")
     a = p.parse_args(argv)
+    if a.ensemble_families is not None:
+        if a.ensemble is None:
+            p.error("--ensemble-families needs --ensemble")
+        if not 1 <= a.ensemble_families <= 8:
+            p.error("--ensemble-families: QMAX in 1 .. 8")
     if a.ensemble_correlation is not None:
         if a.ensemble is None:
             p.error("--ensemble-correlation needs --ensemble")
@@ -154,7 +163,8 @@ def main(argv=None):
                        first_below=tuple(a.first_below), replicates=a.replicates,
                        data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble,
                        ensemble_diagnostics=False if a.ensemble_diagnostics is None else dict(max_lag=a.ensemble_diagnostics),
-                       ensemble_correlation=False if a.ensemble_correlation is None else a.ensemble_correlation)
+                       ensemble_correlation=False if a.ensemble_correlation is None else a.ensemble_correlation,
+                       ensemble_families=False if a.ensemble_families is None else dict(max_families=a.ensemble_families))
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

@@ -150,6 +150,9 @@ SIGNATURES = {
     "gbp_ensemble_correlation": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gbp_band_runs": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gbp_ensemble_distance": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_double, c_int, c_int,
+                                      c_int, c_void_p, c_void_p]),
+    "gbp_distance_families": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_void_p]),
     "gbp_hitmap_pool": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double] + [c_void_p] * 5 + [c_void_p]),
     "gbp_hitmap_mixture": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
     "gbp_hitmap_mixture_i64": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6

@@ -1952,6 +1952,55 @@ extern "C" gbp_status gbp_band_runs(int B, int V, int band_width, const double* 
     return GBP_OK;
 }
 
+#include "gbp_ensemble_families.h"
+
+// Families of kept models (csrc/gbp_ensemble_families.h; the rules: include/geobipy_amd.h): the distance between layered models ...
+extern "C" gbp_status gbp_ensemble_distance(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                            int n, const int32_t* rows, double z0, double z1, int measure, int log10, int squared, double* dist,
+                                            void* stream)
+{
+    using namespace ensemble;
+    if (B < 0 || n_slots < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: negative or zero size%s");
+    if (n < 1 || n > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: n outside 1 .. 4096%s");
+    if (K < 1 || K > 64) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: K outside 1 .. 64%s");
+    if (!std::isfinite(z0) || !std::isfinite(z1) || z0 < 0.0 || z1 <= z0)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: the window needs finite bounds with 0 <= z0 < z1%s");
+    if (measure != 0 && measure != 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: measure must be 0 (linear) or 1 (log)%s");
+    if (measure == 1 && z0 == 0.0) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: the log measure needs z0 > 0%s");
+    const int nt = (n + FAM_TILE - 1) / FAM_TILE, ntp = nt * (nt + 1) / 2;
+    if ((int64_t)B * ntp * FAM_THREADS > 0xffffffffLL)             // (a dispatch counts its work-items in 32 bits)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: B * tile pairs out of range (more than 2^32 - 1 threads)%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!ens_k || !ens_edges || !ens_sigma || !rows || !dist) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_distance: NULL pointer%s");
+    const double mu = measure == 1 ? std::log1p((z1 - z0) / z0) : z1 - z0;      // (ln(z1 / z0), as the kernel takes a segment's: a narrow deep window)
+    const DistanceArgs a = {n_slots, K, n, ens_k, ens_edges, ens_sigma, rows, z0, z1, 1.0 / mu, log10 ? 1 : 0, squared ? 1 : 0, ntp, dist};
+    const dim3 grid((unsigned)((int64_t)B * ntp));
+    if (measure == 1) hipLaunchKernelGGL(k_layered_distance<true>, grid, dim3(FAM_THREADS), distance_lds_bytes(K), (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_layered_distance<false>, grid, dim3(FAM_THREADS), distance_lds_bytes(K), (hipStream_t)stream, a);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+// ... and k-medoids on the distances, every stage of a sounding in one launch: one workgroup per sounding.
+extern "C" gbp_status gbp_distance_families(int B, int n, const double* dist, const int32_t* n_used, int q_max, int max_iter, int32_t* medoid,
+                                            int32_t* label, double* nearest, double* second, int32_t* iterations, uint8_t* converged,
+                                            int32_t* n_found, void* stream)
+{
+    using namespace ensemble;
+    if (B < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: negative size%s");
+    if (n < 1 || n > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: n outside 1 .. 4096%s");
+    if (q_max < 1 || q_max > FAM_MAX_Q) return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: q_max outside 1 .. 8%s");
+    if (max_iter < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: max_iter must be >= 0%s");
+    if ((int64_t)B * FAM_THREADS > 0xffffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: B out of range (more than 2^32 - 1 threads)%s");
+    if (B == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!dist || !n_used || !medoid || !label || !nearest || !second || !iterations || !converged || !n_found)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_distance_families: NULL pointer%s");
+    const FamilyArgs a = {n, q_max, max_iter, dist, n_used, medoid, label, nearest, second, iterations, converged, n_found};
+    hipLaunchKernelGGL(k_distance_families, dim3((unsigned)B), dim3(FAM_THREADS), families_lds_bytes(n), (hipStream_t)stream, a);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 #include "gbp_grid.h"
 
 // Discrete Sibson gridding (gbp_grid.h): the plan holds the geometry of one grid -- nearest sounding, D, n, and per destination pixel the

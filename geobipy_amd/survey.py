@@ -496,7 +496,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
           first_above=(), first_below=(), replicates=1, data_posteriors=None, ensemble=None, ensemble_diagnostics=False, ensemble_correlation=False,
-          **overrides):
+          ensemble_families=False, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -548,6 +548,14 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     ``ensemble_resolution_cells`` int32 and ``ensemble_resolution_closed`` bool (False: the length is a lower bound) [S, n_depth] on the
     hit map's depth axis; with ``keep_band`` also ``ensemble_correlation_band`` [S, n_depth, W + 1].  ``replicates`` = C as for the
     diagnostics.  The containers are not touched.
+    ``ensemble_families`` (True or dict(max_families=4, max_models=1024, measure="linear", min_silhouette=0.7); needs ``ensemble``): which
+    kept model is representative, and is the posterior one family of models or several (``families.families``) on the
+    window from the surface to the bottom of the hit map's depth axis: ``ensemble_central_k`` int32 [S], ``ensemble_central_edges`` /
+    ``ensemble_central_sigma`` [S, K] and ``ensemble_central_mean_distance`` [S] (the medoid of the kept models: a sampled layered
+    model, decades), ``ensemble_families_n`` int32 [S], ``ensemble_family_share`` and ``ensemble_family_silhouette`` [S, Q] (the shares
+    of the selected stage's families, largest first; the silhouette of every stage), ``ensemble_family_k`` int32 [S, Q] and
+    ``ensemble_family_edges`` / ``ensemble_family_sigma`` [S, Q, K] (the families' medoid models).  ``replicates`` = C as for the
+    diagnostics.  The containers are not touched.
     ``replicates`` = C, 1 .. 8 (frequency-domain data): C chains per sounding that differ by their random streams alone
     (``replicates.expand``: replicate 0 walks the chain the sounding walks alone); a block then holds C rows per sounding and is seen
     through ``replicates.Pooled`` -- the containers and the posteriors of the summaries receive the sum over the chains that burned in,
@@ -569,6 +577,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     # check
     ens_diag = survey_run.ensemble_diagnostics_argument(ensemble_diagnostics, ensemble)
     ens_corr = survey_run.ensemble_correlation_argument(ensemble_correlation, ensemble)
+    ens_fam = survey_run.ensemble_families_argument(ensemble_families, ensemble)
     o = read_options(options, **overrides) if isinstance(options, str) else dict(options)
     tempest, time_domain, C_rep = survey_run.check_request(o, hitmap, replicates)
     # read
@@ -611,7 +620,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
                                time_domain=time_domain, hitmap=hitmap, exact_jacobian=exact_jacobian, check_every=check_every,
                                results_directory=results_directory, container=container,
                                own_containers=containers and (world == 1 or schedule == "lines"), unit_z=unit_z, clock=clock,
-                               ensemble_diagnostics=ens_diag, ensemble_correlation=ens_corr)
+                               ensemble_diagnostics=ens_diag, ensemble_correlation=ens_corr, ensemble_families=ens_fam)
     filler = survey_run.ContainerFiller(lambda dc, idx: run.payload(dc, idx, sparse=True),
                                         lambda dc: _LineWriter(results_directory, ds, o, dc, hitmap, container), clock)
     # the blocks, one after the other; a block's rows leave for the containers while the next block's chains run

@@ -140,6 +140,37 @@ def ensemble_correlation_argument(ensemble_correlation, ensemble):
     return dict(band=int(band), threshold=check_threshold(ensemble_correlation.get("threshold", 0.5)), keep_band=bool(keep))
 
 
+def ensemble_families_argument(ensemble_families, ensemble):
+    """infer's ``ensemble_families`` (False / None: off; True; dict(max_families=, max_models=, measure=, min_silhouette=)) as None or
+    dict(max_families=int in 1 .. 8, max_models=int in 1 .. 4096, measure="linear" | "log", min_silhouette=float in [0, 1]).  Refuses
+    before any device work."""
+    if ensemble_families is None or ensemble_families is False:
+        return None
+    from .families import MAX_FAMILIES, MAX_MODELS, MEASURES
+    if ensemble_families is True:
+        ensemble_families = {}
+    if not isinstance(ensemble_families, dict) or set(ensemble_families) - {"max_families", "max_models", "measure", "min_silhouette"}:
+        raise ValueError("ensemble_families: False, True or dict(max_families=, max_models=, measure=, min_silhouette=)")
+    if ensemble is None:
+        raise ValueError("ensemble_families needs ensemble= (the families are made of the kept models)")
+    out = dict(max_families=ensemble_families.get("max_families", 4), max_models=ensemble_families.get("max_models", 1024),
+               measure=ensemble_families.get("measure", "linear"), min_silhouette=ensemble_families.get("min_silhouette", 0.7))
+    for name, hi in (("max_families", MAX_FAMILIES), ("max_models", MAX_MODELS)):
+        v = out[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+            raise ValueError("ensemble_families: %s must be an integer in 1 .. %d" % (name, hi))
+        out[name] = int(v)
+    if out["measure"] not in MEASURES:
+        raise ValueError("ensemble_families: measure must be 'linear' or 'log'")
+    if out["measure"] == "log":
+        raise ValueError("ensemble_families: the window starts at the surface (z0 = 0), which the log measure cannot weigh; use families.families")
+    v = out["min_silhouette"]
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError("ensemble_families: min_silhouette must be a number in [0, 1]")
+    out["min_silhouette"] = float(v)
+    return out
+
+
 def ensemble_bytes(n_keep, max_layers):
     """Bytes of device memory one chain's posterior ensemble takes: n_keep slots of 2 K doubles, a misfit and a layer count, and the
     chain's sample counter -- n_keep (16 K + 12) + 4 (126 KB at n_keep = 256, K = 30, beside the hit map's 440 KB)."""
@@ -262,6 +293,7 @@ class SurveyRun:
     shipped: list = field(default_factory=list)     # per block: payload() on the HOST, for the rank that writes (not own_containers)
     ensemble_diagnostics: object = None     # None, or dict(max_lag): the chain diagnostics of the ensemble join the summaries
     ensemble_correlation: object = None     # None, or dict(band, threshold, keep_band): the resolution length (and the band) join them
+    ensemble_families: object = None        # None, or dict(max_families, max_models, measure, min_silhouette): the model families join them
 
     def run_block(self, idx, offset=None, key_by_row=True):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])]).  ``key_by_row``:
@@ -354,6 +386,17 @@ class SurveyRun:
                     named += [("ensemble_" + k_, f64(d[k_])) for k_ in ("resolution_length", "resolution_cells", "resolution_closed")]
                     if ec["keep_band"]:
                         named += [("ensemble_correlation_band", d["band"].flatten(1))]
+                if self.ensemble_families is not None:
+                    from . import families
+                    ef = self.ensemble_families
+                    d = families.families(ens, float(int(dc.n_depth_bins) * float(dc.depth_bin_width)), z0=0.0, measure=ef["measure"],
+                                          chains=self.C_rep, max_families=ef["max_families"], max_models=ef["max_models"],
+                                          min_silhouette=ef["min_silhouette"])
+                    named += [("ensemble_families_n", col(d["n_families"])), ("ensemble_family_share", d["family_share"]),
+                              ("ensemble_family_silhouette", d["silhouette"]), ("ensemble_family_k", f64(d["family_k"])),
+                              ("ensemble_family_edges", d["family_edges"].flatten(1)), ("ensemble_family_sigma", d["family_sigma"].flatten(1)),
+                              ("ensemble_central_k", col(d["central_k"])), ("ensemble_central_edges", d["central_edges"]),
+                              ("ensemble_central_sigma", d["central_sigma"]), ("ensemble_central_mean_distance", col(d["central_mean_distance"]))]
         if diag is not None:
             named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
         return named
@@ -612,6 +655,19 @@ def assemble_result(ds, o, dc, named, r, C_rep, iterations_run):
         res["ensemble_resolution_closed"] = res["ensemble_resolution_closed"].reshape(-1, nd) != 0
         if "ensemble_correlation_band" in res:
             res["ensemble_correlation_band"] = res["ensemble_correlation_band"].reshape(res["status"].shape[0], nd, -1)
+    if "ensemble_families_n" in res:             # [S], [S, Q], [S, Q, K] and the central model [S], [S, K]
+        S = res["status"].shape[0]
+        res["ensemble_families_n"] = res["ensemble_families_n"].reshape(S).astype(np.int32)
+        res["ensemble_family_share"] = res["ensemble_family_share"].reshape(S, -1)
+        Q = res["ensemble_family_share"].shape[1]
+        res["ensemble_family_silhouette"] = res["ensemble_family_silhouette"].reshape(S, Q)
+        res["ensemble_family_k"] = res["ensemble_family_k"].reshape(S, Q).astype(np.int32)
+        res["ensemble_central_k"] = res["ensemble_central_k"].reshape(S).astype(np.int32)
+        res["ensemble_central_mean_distance"] = res["ensemble_central_mean_distance"].reshape(S)
+        for k_ in ("ensemble_family_edges", "ensemble_family_sigma"):
+            res[k_] = res[k_].reshape(S, Q, dc.K)
+        for k_ in ("ensemble_central_edges", "ensemble_central_sigma"):
+            res[k_] = res[k_].reshape(S, dc.K)
     n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze
     ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
     res["iterations"] = ran.astype(np.int64)

@@ -778,6 +778,39 @@ gbp_status gbp_ensemble_correlation(int B, int n_slots, int K, const int32_t *en
                                     const int32_t *seg_n, int band_width, int normalise, double *stats, double *band, void *stream);
 gbp_status gbp_band_runs(int B, int V, int band_width, const double *band, double threshold, int32_t *up, int32_t *down, uint8_t *closed,
                          void *stream);
+/* Families of kept models (csrc/gbp_ensemble_families.h; the host statements of the rules are geobipy_amd/families.py
+ * distance_reference and families_reference): which sampled model is representative, and is the posterior one family of models or several.
+ * gbp_ensemble_distance -- model u of sounding b is slot rows[b, u] of the ensemble (rows int32 [B, n]): k layers, interfaces e[0 .. k - 2]
+ * ascending, values a[l] = log10 sigma[l] (log10 != 0) or the stored doubles (log10 == 0); its value at depth z is that of layer
+ * #{l < k - 1 : e[l] <= z} (the count of gbp_ensemble_raster: an interface exactly at z gives the layer below).  On the window [z0, z1]
+ * with the measure mu([p, q]) = q - p (measure 0, linear) or ln(q / p) (measure 1, log; z0 > 0):
+ *   D2(u, v) = (1 / mu([z0, z1])) sum over the merged segments [p, q) of mu([p, q]) (a_u(p) - a_v(p))^2,  D = sqrt(D2),
+ * the breakpoints being z0, every interface of either model strictly inside (z0, z1) in ascending order, and z1: the exact integral of
+ * the squared difference of two piecewise-constant functions, O(k_u + k_v) per pair and no depth axis.  dist f64 [B, n, n] holds D
+ * (squared == 0) or D2; dist[b, u, v] and dist[b, v, u] are one value, bit for bit; the diagonal of a present model is 0.0 (written, not
+ * computed) and two slots that hold one model are exactly 0 apart.  A row outside 0 .. n_slots - 1 or a slot with k <= 0 is absent: its
+ * row, column and diagonal are NaN (the slot index is clamped before any load).
+ * gbp_distance_families -- k-medoids on dist, per sounding on its first m = n_used[b] models (clamped to 0 .. n), stages q = 1 .. q_max;
+ * every sum runs over j = 0 .. m - 1 in ascending order in fp64.  If an entry of dist[b, :m, :m] is non-finite or negative, or m == 0:
+ * n_found = 0 and every stage is not found.  Stage 1: the medoid is argmin_i sum_j dist[j, i].  Stage q > 1: stage q - 1's final medoids
+ * plus the candidate c with the greatest gain sum_j max(nearest[j] - dist[j, c], 0) against stage q - 1's final assignment; a greatest gain
+ * of 0.0 means fewer than q distinct models: this stage and the later ones are not found, n_found = q - 1.  Then at most max_iter times:
+ * assign every model j to the medoid c_p with the least dist[c_p, j] (ties to the medoid that joined first); per family the new medoid is
+ * the member i with the least sum_{j in the family} dist[j, i] (a family without a member keeps its medoid); no medoid changed:
+ * converged = 1, stop.  When the cap is reached the models are assigned once more to the current medoids and converged = 0.  iterations
+ * counts the updates.  Every argmin / argmax takes the lowest index among equals.  Per stage: medoid int32 [B, q_max, q_max] (indices into
+ * the model list; -1 beyond q), label int32 [B, q_max, n] (the medoid's position; -1 for j >= m), nearest and second f64 [B, q_max, n] (the
+ * distances to the nearest and the second-nearest medoid: copies of dist entries; second is NaN at stage 1), iterations int32 and converged
+ * uint8 [B, q_max]; n_found int32 [B].  A stage not found: -1, -1, NaN, NaN, 0, 0.  Every output is an integer or a copy of an input double.
+ * 1 <= n <= 4096, 1 <= K <= 64, 1 <= q_max <= 8, max_iter >= 0, finite 0 <= z0 < z1, z0 > 0 for the log measure; GBP_ERR_INVALID_ARG for
+ * these, for NULL pointers and for a launch of more than 2^32 - 1 threads (256 per tile pair, 256 per sounding), every check before any launch, the entry named in gbp_last_error;
+ * B == 0 launches nothing.  No atomics, one order of addition: a call repeats its own bits. */
+gbp_status gbp_ensemble_distance(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                                 int n, const int32_t *rows, double z0, double z1, int measure, int log10, int squared, double *dist,
+                                 void *stream);
+gbp_status gbp_distance_families(int B, int n, const double *dist, const int32_t *n_used, int q_max, int max_iter, int32_t *medoid,
+                                 int32_t *label, double *nearest, double *second, int32_t *iterations, uint8_t *converged, int32_t *n_found,
+                                 void *stream);
 gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                    int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                    void *stream);
