@@ -77,29 +77,25 @@ def parse(argv=None):
                         "QMAX families of kept models (1 .. 8, default 4): ensemble_central_*, ensemble_families_n, ensemble_family_* in the "
                         "summaries")
     a = p.parse_args(argv)
-    if a.ensemble_families is not None:
-        if a.ensemble is None:
-            p.error("--ensemble-families needs --ensemble")
-        if not 1 <= a.ensemble_families <= 8:
-            p.error("--ensemble-families: QMAX in 1 .. 8")
     if a.ensemble_correlation is not None:
-        if a.ensemble is None:
-            p.error("--ensemble-correlation needs --ensemble")
         if len(a.ensemble_correlation) > 2:
             p.error("--ensemble-correlation: at most BAND and THRESHOLD")
         try:
-            band = int(a.ensemble_correlation[0]) if a.ensemble_correlation else 64
-            threshold = float(a.ensemble_correlation[1]) if len(a.ensemble_correlation) > 1 else 0.5
+            a.ensemble_correlation = dict(band=int(a.ensemble_correlation[0]) if a.ensemble_correlation else 64,
+                                          threshold=float(a.ensemble_correlation[1]) if len(a.ensemble_correlation) > 1 else 0.5)
         except ValueError:
             p.error("--ensemble-correlation: BAND is an integer, THRESHOLD a number")
-        if band < 0 or not 0.0 < threshold < 1.0:
-            p.error("--ensemble-correlation: BAND >= 0 and 0 < THRESHOLD < 1")
-        a.ensemble_correlation = dict(band=band, threshold=threshold)
-    if a.ensemble_diagnostics is not None:
-        if a.ensemble is None:
-            p.error("--ensemble-diagnostics needs --ensemble")
-        if not 1 <= a.ensemble_diagnostics <= 255:
-            p.error("--ensemble-diagnostics: MAX_LAG in 1 .. 255")
+    # the ranges, and that each of the three needs --ensemble, are infer's own checks
+    from . import survey_run
+    try:
+        if a.ensemble_families is not None:
+            survey_run.ensemble_families_argument(dict(max_families=a.ensemble_families), a.ensemble)
+        if a.ensemble_correlation is not None:
+            survey_run.ensemble_correlation_argument(a.ensemble_correlation, a.ensemble)
+        if a.ensemble_diagnostics is not None:
+            survey_run.ensemble_diagnostics_argument(dict(max_lag=a.ensemble_diagnostics), a.ensemble)
+    except ValueError as e:
+        p.error(str(e))
     if a.ensemble is not None:
         if len(a.ensemble) > 2:
             p.error("--ensemble: at most N_KEEP and THIN")

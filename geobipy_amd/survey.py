@@ -484,11 +484,6 @@ def select_soundings(ds, index=None, fiducial=None, line_number=None):
 # the per-sounding summaries a run with replicate chains adds, in the order of the result rows (replicates.Pooled.diagnostics)
 REPLICATE_SUMMARIES = ("rhat", "jsd", "n_used", "chain_mean", "rhat_layers", "jsd_layers", "rhat_interfaces", "rhat_max")
 
-# the per-sounding summaries that are counts: int64 in the SurveyResult (the result rows travel as float64)
-INTEGER_SUMMARIES = ("status", "burned_in_iteration", "n_layers", "best_n_layers", "layer_count_posterior", "interface_posterior",
-                     "relative_error_posterior", "additive_error_posterior", "height_posterior", "n_used", "replicates_used") + tuple(
-    n_ + "_posterior" for n_ in ("dx", "dy", "dz", "tx_z", "tx_pitch", "tx_roll", "tx_yaw", "rx_pitch", "rx_roll", "rx_yaw"))
-
 BLOCK_PAYLOAD_BUDGET = 8 << 30      # bytes of traces + hit maps one device block may hold by default (infer's ``chunk``)
 
 
@@ -671,7 +666,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
 
     def assemble_and_save():
         try:
-            made.append(survey_run.assemble_result(ds, o, run.dc, run.named, r, C_rep, iterations_run))
+            made.append(survey_run.assemble_result(ds, o, run.dc, run.named, r, iterations_run))
             if output is not None:
                 made[0].save(output)
         except BaseException as e:                       # (handed to the caller's thread below)

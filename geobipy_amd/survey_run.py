@@ -2,14 +2,16 @@
 and the schedule, the run itself (one block's chains, its summaries, its device rows), the phase clock, the container filler and the
 assembly of the result.  ``survey.infer`` imports this module when it is called; nothing here is needed to read options or data."""
 import contextlib
+import math
 import threading
 import time
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from .survey import (BLOCK_PAYLOAD_BUDGET, INTEGER_SUMMARIES, REPLICATE_SUMMARIES, SurveyResult, TdemData, TempestData, _hitmap_statistics,
+from .survey import (BLOCK_PAYLOAD_BUDGET, REPLICATE_SUMMARIES, SurveyResult, TdemData, TempestData, _hitmap_statistics,
                      _row_fields, _write_line_containers)
 
 # the phase clock's names (bench.py reads them from survey.infer(timings={}))
@@ -104,33 +106,38 @@ def sampler_arguments(o, time_domain, seed=None, device=None, hitmap=True, first
     return common
 
 
+def _ensemble_product_argument(name, keys, value, ensemble, needs):
+    """What infer's ``ensemble_*`` arguments share: False / None -> None (off); True -> {}; a dict of ``keys`` -> that dict.  Anything
+    else is refused, and so is any of them without ``ensemble`` (``needs``: why the product needs it)."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict) or set(value) - set(keys):
+        raise ValueError("{}: False, True or dict({})".format(name, ", ".join(k_ + "=" for k_ in keys)))
+    if ensemble is None or ensemble is False:
+        raise ValueError("{} needs ensemble= ({})".format(name, needs))
+    return value
+
+
 def ensemble_diagnostics_argument(ensemble_diagnostics, ensemble):
     """infer's ``ensemble_diagnostics`` (False / None: off; True; dict(max_lag=)) as None or dict(max_lag=int in 1 .. 255).  Refuses
     the diagnostics without an ensemble.  Touches no device."""
-    if ensemble_diagnostics is None or ensemble_diagnostics is False:
+    given = _ensemble_product_argument("ensemble_diagnostics", ("max_lag",), ensemble_diagnostics, ensemble, "the diagnostics are computed from the kept models")
+    if given is None:
         return None
     from .ensembles import check_max_lag
-    if ensemble_diagnostics is True:
-        ensemble_diagnostics = {}
-    if not isinstance(ensemble_diagnostics, dict) or set(ensemble_diagnostics) - {"max_lag"}:
-        raise ValueError("ensemble_diagnostics: False, True or dict(max_lag=)")
-    if ensemble is None or ensemble is False:
-        raise ValueError("ensemble_diagnostics needs ensemble= (the diagnostics are computed from the kept models)")
-    return dict(max_lag=check_max_lag(ensemble_diagnostics.get("max_lag")))
+    return dict(max_lag=check_max_lag(given.get("max_lag")))
 
 
 def ensemble_correlation_argument(ensemble_correlation, ensemble):
     """infer's ``ensemble_correlation`` (False / None: off; True; dict(band=, threshold=, keep_band=)) as None or dict(band=int >= 0,
     threshold=float in (0, 1), keep_band=bool).  Refuses the correlation without an ensemble.  Touches no device."""
-    if ensemble_correlation is None or ensemble_correlation is False:
+    ensemble_correlation = _ensemble_product_argument("ensemble_correlation", ("band", "threshold", "keep_band"), ensemble_correlation, ensemble,
+                                                      "the correlation is computed from the kept models")
+    if ensemble_correlation is None:
         return None
     from .ensembles import check_threshold
-    if ensemble_correlation is True:
-        ensemble_correlation = {}
-    if not isinstance(ensemble_correlation, dict) or set(ensemble_correlation) - {"band", "threshold", "keep_band"}:
-        raise ValueError("ensemble_correlation: False, True or dict(band=, threshold=, keep_band=)")
-    if ensemble is None or ensemble is False:
-        raise ValueError("ensemble_correlation needs ensemble= (the correlation is computed from the kept models)")
     band = ensemble_correlation.get("band", 64)
     if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or int(band) < 0:
         raise ValueError("ensemble_correlation: band must be an integer >= 0")
@@ -144,15 +151,11 @@ def ensemble_families_argument(ensemble_families, ensemble):
     """infer's ``ensemble_families`` (False / None: off; True; dict(max_families=, max_models=, measure=, min_silhouette=)) as None or
     dict(max_families=int in 1 .. 8, max_models=int in 1 .. 4096, measure="linear" | "log", min_silhouette=float in [0, 1]).  Refuses
     before any device work."""
-    if ensemble_families is None or ensemble_families is False:
+    ensemble_families = _ensemble_product_argument("ensemble_families", ("max_families", "max_models", "measure", "min_silhouette"),
+                                                   ensemble_families, ensemble, "the families are made of the kept models")
+    if ensemble_families is None:
         return None
     from .families import MAX_FAMILIES, MAX_MODELS, MEASURES
-    if ensemble_families is True:
-        ensemble_families = {}
-    if not isinstance(ensemble_families, dict) or set(ensemble_families) - {"max_families", "max_models", "measure", "min_silhouette"}:
-        raise ValueError("ensemble_families: False, True or dict(max_families=, max_models=, measure=, min_silhouette=)")
-    if ensemble is None:
-        raise ValueError("ensemble_families needs ensemble= (the families are made of the kept models)")
     out = dict(max_families=ensemble_families.get("max_families", 4), max_models=ensemble_families.get("max_models", 1024),
                measure=ensemble_families.get("measure", "linear"), min_silhouette=ensemble_families.get("min_silhouette", 0.7))
     for name, hi in (("max_families", MAX_FAMILIES), ("max_models", MAX_MODELS)):
@@ -265,6 +268,42 @@ def pack_rows(fields, layout, dtype=None):
     return torch.cat(cols, dim=1).contiguous()
 
 
+# ---- the result rows of a block -----------------------------------------------------------------------------------------------------
+
+class Entry(NamedTuple):
+    """One per-sounding summary as ``SurveyRun.summaries`` holds it."""
+    name: str
+    tensor: object                      # [rows, ...], in the shape and dtype it has on the device
+    dtype: object = None                # the result's numpy dtype, where it is not the tensor's own (a floating tensor's: float64)
+    keep: bool = False                  # a single column stays [rows, 1] (default: it comes back [rows])
+
+
+def layout(entries):
+    """[(name, tail, dtype, squeeze)] of ``entries``, in their order: the result's shape after the soundings' axis, its numpy dtype, and
+    whether a single column comes back [rows].  Rows are not looked at, so an empty block gives the layout of a full one."""
+    own = lambda v: np.float64 if v.is_floating_point() else torch.empty(0, dtype=v.dtype).numpy().dtype      # noqa: E731
+    return tuple((e.name, tuple(e.tensor.shape[1:]), np.dtype(own(e.tensor) if e.dtype is None else e.dtype), not e.keep) for e in entries)
+
+
+def pack(entries):
+    """The float64 [rows, sum of widths] block of ``entries``, the columns in their order: what the ranks exchange (counts are 32-bit
+    on the device and flags 0 / 1, so float64 holds them exactly)."""
+    return torch.cat([e.tensor.to(torch.float64).reshape(e.tensor.shape[0], math.prod(e.tensor.shape[1:])) for e in entries], dim=1).contiguous()
+
+
+def unpack(columns, block):
+    """{name: array} from the host rows ``block`` (numpy float64 [rows, sum of widths], as ``pack`` laid them out) with the dtype and
+    shape ``columns`` (a ``layout``) gives every name; float64 columns are views of ``block``."""
+    out, c0 = {}, 0
+    for name, tail, dtype, squeeze in columns:
+        w = math.prod(tail)
+        v = block[:, c0:c0 + w]
+        v = v != 0 if dtype == np.bool_ else v.astype(dtype, copy=False)
+        out[name] = v[:, 0] if w == 1 and squeeze else v.reshape((block.shape[0],) + tail)
+        c0 += w
+    return out
+
+
 # ---- the run ------------------------------------------------------------------------------------------------------------------------
 
 @dataclass
@@ -288,7 +327,7 @@ class SurveyRun:
     clock: PhaseClock
     # what the blocks leave behind
     dc: object = None                   # the last block's sampler (referenced until infer returns)
-    named: list = None                  # its summaries [(name, [rows, width])]: the layout of every block's result rows
+    named: tuple = None                 # layout() of its summaries, which is that of every block's result rows
     iterations: int = 0                 # the largest iteration count of any block
     shipped: list = field(default_factory=list)     # per block: payload() on the HOST, for the rank that writes (not own_containers)
     ensemble_diagnostics: object = None     # None, or dict(max_lag): the chain diagnostics of the ensemble join the summaries
@@ -296,7 +335,7 @@ class SurveyRun:
     ensemble_families: object = None        # None, or dict(max_families, max_models, measure, min_silhouette): the model families join them
 
     def run_block(self, idx, offset=None, key_by_row=True):
-        """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, [(name, [len(idx), w])]).  ``key_by_row``:
+        """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, its ``summaries``).  ``key_by_row``:
         every chain is keyed by its own row of the data file (a selection of the shard); False: ``idx`` is the whole shard, keyed by
         its first row (``common["first_chain"]``)."""
         ds, o, C_rep, clock = self.ds, self.o, self.C_rep, self.clock
@@ -338,67 +377,66 @@ class SurveyRun:
         return dc, self.summaries(dc, diag)
 
     def summaries(self, dc, diag=None):
-        """The per-sounding summaries of a finished block, [(name, float64 [rows, width])] in the order of the result rows (``diag``:
-        Pooled.diagnostics() of a block with replicate chains)."""
+        """The per-sounding summaries of a finished block: [Entry] in the order of the result rows, every tensor as it stands on the device
+        (``diag``: Pooled.diagnostics() of a block with replicate chains); an error posterior is [rows, groups, cells] with more than one group."""
         clock = self.clock
-        f64 = lambda x: x.to(torch.float64)
-        col = lambda x: f64(x)[:, None]
+        E, i64, f64 = Entry, np.int64, np.float64
         t = dc.t
-        named = [("status", col(t["status"])), ("burned_in_iteration", col(t["burned_in_iteration"])), ("n_accepted", col(t["n_accepted"])),
-                 ("misfit", col(t["misfit"])), ("relative_error", t["rel"]), ("additive_error", t["add"]), ("n_layers", col(t["k"])),
-                 ("best_n_layers", col(t["best_k"])), ("best_posterior", col(t["best_posterior"])), ("best_edges", t["best_edges"]),
-                 ("best_conductivity", t["best_sigma"]), ("layer_count_posterior", f64(t["k_hist"])),
-                 ("interface_posterior", f64(t["edge_hist"])), ("relative_error_posterior", f64(t["rel_hist"]).flatten(1)),
-                 ("additive_error_posterior", f64(t["add_hist"]).flatten(1))]
+        named = [E("status", t["status"]), E("burned_in_iteration", t["burned_in_iteration"]), E("n_accepted", t["n_accepted"]),
+                 E("misfit", t["misfit"]), E("relative_error", t["rel"]), E("additive_error", t["add"]), E("n_layers", t["k"]),
+                 E("best_n_layers", t["best_k"]), E("best_posterior", t["best_posterior"]), E("best_edges", t["best_edges"]),
+                 E("best_conductivity", t["best_sigma"]), E("layer_count_posterior", t["k_hist"], i64),
+                 E("interface_posterior", t["edge_hist"], i64), E("relative_error_posterior", t["rel_hist"].squeeze(1), i64),
+                 E("additive_error_posterior", t["add_hist"].squeeze(1), i64)]
         if getattr(dc, "_moves", None):            # sampled attitude angles (the loops' own convention): final, highest-posterior, posterior
             cur, best = dc.sampled_angles("geom"), dc.sampled_angles("best_geom")
             for q, m_ in enumerate(dc._moves):
-                named += [(m_[0], col(cur[m_[0]])), ("best_" + m_[0], col(best[m_[0]])), (m_[0] + "_posterior", f64(t["geom_hist"][:, q, :m_[5]]))]
+                named += [E(m_[0], cur[m_[0]]), E("best_" + m_[0], best[m_[0]]), E(m_[0] + "_posterior", t["geom_hist"][:, q, :m_[5]], i64)]
         if getattr(dc, "solve_height", False):     # the sampled height: final and highest-posterior values, posterior on the prior's 99 cells
-            named += [("height", col(t["height"])), ("best_height", col(t["best_height"])), ("height_posterior", f64(t["height_hist"]))]
+            named += [E("height", t["height"]), E("best_height", t["best_height"]), E("height_posterior", t["height_hist"], i64)]
         if self.hitmap:
             with clock.phase("hitmap_statistics"):
                 mean, pct = _hitmap_statistics(dc.hitmap, t["log_mean_prior"], dc.value_half_width)     # (attribute access settles dwell times)
-            named += [("mean_log10_conductivity", mean)] + [("log10_conductivity_" + q, p) for q, p in zip(("p05", "p50", "p95"), pct)]
+            named += [E("mean_log10_conductivity", mean)] + [E("log10_conductivity_" + q, p) for q, p in zip(("p05", "p50", "p95"), pct)]
         if t.get("unit_hist") is not None or t.get("first_hist") is not None:
             from . import unit_posteriors
             with clock.phase("unit_posteriors"):
-                named += [(k_, f64(v_)) for k_, v_ in unit_posteriors.products(dc).items()]
+                named += [E(k_, v_, f64) for k_, v_ in unit_posteriors.products(dc).items()]
         if t.get("data_hist") is not None:
             from . import data_posteriors
             with clock.phase("data_posteriors"):
-                named += [(k_, f64(v_) if v_.ndim > 1 else col(v_)) for k_, v_ in data_posteriors.products(dc).items()]
-        if t.get("ens_k") is not None:
+                named += [E(k_, v_, f64) for k_, v_ in data_posteriors.products(dc).items()]
+        if t.get("ens_k") is not None:             # [rows, slots] and [rows, slots, K]; with replicates the chains' slots one after the other
             from . import ensembles
             with clock.phase("ensemble"):
                 ens = ensembles.from_chains(dc)
-                named += [("ensemble_k", f64(ens.k)), ("ensemble_edges", ens.edges.flatten(1)), ("ensemble_sigma", ens.sigma.flatten(1)),
-                          ("ensemble_misfit", ens.misfit), ("ensemble_thin", col(torch.full_like(t["k"], ens.thin)))]
+                named += [E("ensemble_k", ens.k, keep=True), E("ensemble_edges", ens.edges, keep=True), E("ensemble_sigma", ens.sigma, keep=True),
+                          E("ensemble_misfit", ens.misfit, keep=True), E("ensemble_thin", torch.full_like(t["k"], ens.thin))]
                 if self.ensemble_diagnostics is not None:
                     d = ensembles.diagnostics(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
                                               max_lag=self.ensemble_diagnostics["max_lag"])
-                    named += [("ensemble_" + k_, d[k_]) for k_ in ("ess", "rhat", "tau_iterations", "mcse")]
-                    named += [("ensemble_" + k_, col(d[k_])) for k_ in ("ess_k", "ess_misfit", "rhat_k", "rhat_misfit", "ess_min")]
+                    named += [E("ensemble_" + k_, d[k_]) for k_ in ("ess", "rhat", "tau_iterations", "mcse", "ess_k", "ess_misfit", "rhat_k", "rhat_misfit", "ess_min")]
                 if self.ensemble_correlation is not None:
                     ec = self.ensemble_correlation
                     d = ensembles.correlation(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
                                               band=ec["band"], threshold=ec["threshold"], keep_band=ec["keep_band"])
-                    named += [("ensemble_" + k_, f64(d[k_])) for k_ in ("resolution_length", "resolution_cells", "resolution_closed")]
+                    named += [E("ensemble_" + k_, d[k_], keep=True) for k_ in ("resolution_length", "resolution_cells", "resolution_closed")]
                     if ec["keep_band"]:
-                        named += [("ensemble_correlation_band", d["band"].flatten(1))]
+                        named += [E("ensemble_correlation_band", d["band"], keep=True)]
                 if self.ensemble_families is not None:
                     from . import families
                     ef = self.ensemble_families
                     d = families.families(ens, float(int(dc.n_depth_bins) * float(dc.depth_bin_width)), z0=0.0, measure=ef["measure"],
                                           chains=self.C_rep, max_families=ef["max_families"], max_models=ef["max_models"],
                                           min_silhouette=ef["min_silhouette"])
-                    named += [("ensemble_families_n", col(d["n_families"])), ("ensemble_family_share", d["family_share"]),
-                              ("ensemble_family_silhouette", d["silhouette"]), ("ensemble_family_k", f64(d["family_k"])),
-                              ("ensemble_family_edges", d["family_edges"].flatten(1)), ("ensemble_family_sigma", d["family_sigma"].flatten(1)),
-                              ("ensemble_central_k", col(d["central_k"])), ("ensemble_central_edges", d["central_edges"]),
-                              ("ensemble_central_sigma", d["central_sigma"]), ("ensemble_central_mean_distance", col(d["central_mean_distance"]))]
+                    named += [E("ensemble_families_n", d["n_families"]), E("ensemble_family_share", d["family_share"], keep=True),
+                              E("ensemble_family_silhouette", d["silhouette"], keep=True), E("ensemble_family_k", d["family_k"], keep=True),
+                              E("ensemble_family_edges", d["family_edges"], keep=True), E("ensemble_family_sigma", d["family_sigma"], keep=True),
+                              E("ensemble_central_k", d["central_k"]), E("ensemble_central_edges", d["central_edges"], keep=True),
+                              E("ensemble_central_sigma", d["central_sigma"], keep=True),
+                              E("ensemble_central_mean_distance", d["central_mean_distance"])]
         if diag is not None:
-            named += [(k_, f64(diag[k_]).reshape(dc.B, -1)) for k_ in REPLICATE_SUMMARIES] + [("replicates_used", col(dc.use.sum(dim=1)))]
+            named += [E(k_, diag[k_], i64 if k_ == "n_used" else f64, k_ == "chain_mean") for k_ in REPLICATE_SUMMARIES] + [E("replicates_used", dc.use.sum(dim=1))]
         return named
 
     def payload(self, dc, idx, sparse=False):
@@ -493,15 +531,18 @@ class SurveyRun:
                                           "set of Hankel tables (~0.15 MB x (1 + altitude bins)) per pair -- bin the offsets (e.g. to 0.1 m) first".format(n_off, count))
             offset = ds.offsets[span] if count > 0 else (0.0, 0.0, 0.0)
         filler.drain(background=True)
-        dc, named = self.run_block(span, offset, key_by_row)
+        dc, entries = self.run_block(span, offset, key_by_row)
         if self.own_containers:
             # the block's rows go to the line containers and are dropped (host memory holds the open lines, not the survey's hit
             # maps) -- at the start of the next block, or, for the last one, once the summary file's thread is running
             filler.hand_over(dc, span)
         elif self.results_directory is not None and span.size:      # (a rank that drew no chunk ships nothing)
             self.shipped.append(self.payload(dc, span))
-        self.iterations, self.dc, self.named = max(self.iterations, dc.iteration), dc, named
-        return torch.cat([v for _, v in named], dim=1).contiguous()
+        columns = layout(entries)
+        if self.named is not None and self.named != columns:
+            raise ValueError("result rows: this block's columns are not those of the block before it")
+        self.iterations, self.dc, self.named = max(self.iterations, dc.iteration), dc, columns
+        return pack(entries)
 
     def gather_pieces(self, pieces, filler):
         """The blocks ``pieces`` (an iterable of (first, count); every chain keyed by its own row) of this rank, one after the other,
@@ -623,55 +664,14 @@ class ContainerFiller:
 
 # ---- the result ---------------------------------------------------------------------------------------------------------------------
 
-def assemble_result(ds, o, dc, named, r, C_rep, iterations_run):
-    """The SurveyResult from the gathered result rows ``r`` (numpy [soundings, width], columns in the order of ``named``; ``dc``: any
-    block's sampler, for the axes' sizes; ``iterations_run``: the count of a chain that never finished)."""
+def assemble_result(ds, o, dc, columns, r, iterations_run):
+    """The SurveyResult from the gathered result rows ``r`` (numpy [soundings, width], laid out as ``columns``: SurveyRun.named; ``dc``:
+    any block's sampler, for the depth axis; ``iterations_run``: the count of a chain that never finished)."""
     res = SurveyResult(line=ds.lineNumber, fiducial=ds.fiducial, x=ds.x, y=ds.y, z=ds.z, elevation=ds.elevation,
                        depth_bin_width=np.float64(dc.depth_bin_width))
-    c0 = 0
-    for name, v in named:
-        w = v.shape[1]
-        block = r[:, c0:c0 + w]
-        c0 += w
-        if name in INTEGER_SUMMARIES:
-            block = block.astype(np.int64)
-        res[name] = block[:, 0] if w == 1 else block
-    for name, G in (("relative_error_posterior", dc.n_rel_groups), ("additive_error_posterior", dc.n_add_groups)):
-        if G > 1:                                   # [S, groups, cells]; ne cells, uniform in log10 between the prior bounds
-            res[name] = res[name].reshape(-1, G, dc.n_error_bins)
-    if C_rep > 1:
-        res["chain_mean"] = res["chain_mean"].reshape(-1, C_rep, dc.n_depth_bins)
-    if "ensemble_k" in res:                      # [S, slots] and [S, slots, K]; with replicates the chains' slots one after the other
-        slots = int(dc.n_ensemble) * C_rep
-        res["ensemble_k"] = res["ensemble_k"].reshape(-1, slots).astype(np.int32)
-        res["ensemble_misfit"] = res["ensemble_misfit"].reshape(-1, slots)
-        res["ensemble_thin"] = res["ensemble_thin"].astype(np.int32)
-        for k_ in ("ensemble_edges", "ensemble_sigma"):
-            res[k_] = res[k_].reshape(-1, slots, dc.K)
-    if "ensemble_resolution_length" in res:      # [S, n_depth], and the band [S, n_depth, W + 1]
-        nd = int(dc.n_depth_bins)
-        res["ensemble_resolution_length"] = res["ensemble_resolution_length"].reshape(-1, nd)
-        res["ensemble_resolution_cells"] = res["ensemble_resolution_cells"].reshape(-1, nd).astype(np.int32)
-        res["ensemble_resolution_closed"] = res["ensemble_resolution_closed"].reshape(-1, nd) != 0
-        if "ensemble_correlation_band" in res:
-            res["ensemble_correlation_band"] = res["ensemble_correlation_band"].reshape(res["status"].shape[0], nd, -1)
-    if "ensemble_families_n" in res:             # [S], [S, Q], [S, Q, K] and the central model [S], [S, K]
-        S = res["status"].shape[0]
-        res["ensemble_families_n"] = res["ensemble_families_n"].reshape(S).astype(np.int32)
-        res["ensemble_family_share"] = res["ensemble_family_share"].reshape(S, -1)
-        Q = res["ensemble_family_share"].shape[1]
-        res["ensemble_family_silhouette"] = res["ensemble_family_silhouette"].reshape(S, Q)
-        res["ensemble_family_k"] = res["ensemble_family_k"].reshape(S, Q).astype(np.int32)
-        res["ensemble_central_k"] = res["ensemble_central_k"].reshape(S).astype(np.int32)
-        res["ensemble_central_mean_distance"] = res["ensemble_central_mean_distance"].reshape(S)
-        for k_ in ("ensemble_family_edges", "ensemble_family_sigma"):
-            res[k_] = res[k_].reshape(S, Q, dc.K)
-        for k_ in ("ensemble_central_edges", "ensemble_central_sigma"):
-            res[k_] = res[k_].reshape(S, dc.K)
+    res.update(unpack(columns, r))
     n_mc = int(o["n_markov_chains"])             # iterations each chain ran before it froze
     ran = np.where(res["status"] == 1, res["burned_in_iteration"] + n_mc + 1, np.where(res["status"] == 2, n_mc, iterations_run))
     res["iterations"] = ran.astype(np.int64)
     res["acceptance"] = res.pop("n_accepted") / np.maximum(1, ran)
-    for k_ in ("status", "burned_in_iteration", "n_layers", "best_n_layers"):
-        res[k_] = res[k_].astype(np.int32)
     return res

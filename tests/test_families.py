@@ -399,8 +399,9 @@ def test_the_survey_driver_checks_the_keyword():
     assert check(False, None) is None and check(None, 16) is None
     assert check(True, 16) == dict(max_families=4, max_models=1024, measure="linear", min_silhouette=0.7)
     assert check(dict(max_families=2, min_silhouette=0.5), 16) == dict(max_families=2, max_models=1024, measure="linear", min_silhouette=0.5)
-    with pytest.raises(ValueError, match="needs ensemble"):
-        check(True, None)
+    for no_ensemble in (None, False):
+        with pytest.raises(ValueError, match="needs ensemble"):
+            check(True, no_ensemble)
     for bad in (3, "yes", dict(families=2), dict(max_families=0), dict(max_families=9), dict(max_families=2.0), dict(max_models=0),
                 dict(max_models=4097), dict(measure="cubic"), dict(measure="log"), dict(min_silhouette=1.5), dict(min_silhouette="high")):
         with pytest.raises(ValueError, match="ensemble_families"):

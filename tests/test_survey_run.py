@@ -258,19 +258,102 @@ def test_phase_clock_accumulates_only_when_asked():
     assert set(t) == {"chains", "rows_to_host_overlapped", "container_fill"} and t["rows_to_host_overlapped"] == 0.75 and t["chains"] >= 0.0
 
 
+def _entries(rows):
+    """Hand-made summaries: tails (), (1,) squeezed, (1,) kept, (3,), (2, 5) and (0,); results int32, int64, bool and float64 from
+    tensors of their own or of another dtype; NaN and the largest int32 among the values -> ([Entry], {name: the expected array})."""
+    E, big = survey_run.Entry, 2 ** 31 - 1
+    count = torch.arange(rows, dtype=torch.int32) * 3 - 1
+    if rows:
+        count[0] = big
+    real = torch.arange(rows * 10, dtype=torch.float64).reshape(rows, 2, 5) / 7.0
+    real[:1, 1, 2] = float("nan")
+    flag = (torch.arange(rows * 3).reshape(rows, 3) % 2) == 0
+    entries = [E("scalar", count), E("squeezed", real[:, 1, 2:3]), E("kept", real[:, :1, 0], keep=True), E("kept_count", count[:, None], np.int64, True),
+               E("flags", flag), E("cube", real), E("single", real[:, 0, :3].to(torch.float32)), E("nothing", real[:, 0, :0]),
+               E("wide_count", count[:, None].to(torch.int64) + torch.arange(2), np.float64), E("bytes", flag.to(torch.uint8), np.int32)]
+    expected = dict(scalar=count.numpy(), squeezed=real[:, 1, 2].numpy(), kept=real[:, :1, 0].numpy(), kept_count=count[:, None].numpy().astype(np.int64),
+                    flags=flag.numpy(), cube=real.numpy(), single=real[:, 0, :3].to(torch.float32).numpy().astype(np.float64), nothing=np.zeros((rows, 0)),
+                    wide_count=(count[:, None].to(torch.int64) + torch.arange(2)).numpy().astype(np.float64), bytes=flag.numpy().astype(np.int32))
+    return entries, expected
+
+
+@pytest.mark.parametrize("rows", [0, 4])
+def test_result_rows_pack_and_unpack_exactly(rows):
+    entries, expected = _entries(rows)
+    columns = survey_run.layout(entries)
+    assert [(name, tail, dtype.name, squeeze) for name, tail, dtype, squeeze in columns] == [
+        ("scalar", (), "int32", True), ("squeezed", (1,), "float64", True), ("kept", (1,), "float64", False), ("kept_count", (1,), "int64", False),
+        ("flags", (3,), "bool", True), ("cube", (2, 5), "float64", True), ("single", (3,), "float64", True), ("nothing", (0,), "float64", True),
+        ("wide_count", (2,), "float64", True), ("bytes", (3,), "int32", True)]
+    assert columns == survey_run.layout(_entries(4 - rows)[0])          # an empty block gives the layout of a full one
+    block = survey_run.pack(entries)
+    assert block.dtype == torch.float64 and block.shape == (rows, 1 + 1 + 1 + 1 + 3 + 10 + 3 + 0 + 2 + 3) and block.is_contiguous()
+    got = survey_run.unpack(columns, block.numpy())
+    assert list(got) == [e.name for e in entries]
+    for name, want in expected.items():
+        assert got[name].dtype == want.dtype and got[name].shape == want.shape and np.array_equal(got[name], want, equal_nan=want.dtype.kind == "f"), name
+    assert rows == 0 or (got["scalar"][0] == 2 ** 31 - 1 and np.isnan(got["squeezed"][0]) and np.isnan(got["cube"][0, 1, 2]))
+
+
+def test_the_column_order_belongs_to_the_layout():
+    entries, expected = _entries(4)
+    a, b = [entries[5], entries[0], entries[4]], [entries[4], entries[5], entries[0]]
+    la, lb = survey_run.layout(a), survey_run.layout(b)
+    assert [c[0] for c in la] == ["cube", "scalar", "flags"] and [c[0] for c in lb] == ["flags", "cube", "scalar"] and set(la) == set(lb)
+    pa, pb = survey_run.pack(a).numpy(), survey_run.pack(b).numpy()
+    assert pa.shape == pb.shape and np.array_equal(pa[:, 10], expected["scalar"]) and np.array_equal(pb[:, 13], expected["scalar"])
+    for lay, block in ((la, pa), (lb, pb)):
+        got = survey_run.unpack(lay, block)
+        assert list(got) == [c[0] for c in lay] and all(np.array_equal(got[k], expected[k], equal_nan=k == "cube") for k in got)
+    assert not np.array_equal(survey_run.unpack(lb, pa)["flags"], expected["flags"])        # rows of one order read with the other's layout
+
+
 def test_assemble_result_keeps_the_dtypes():
     ds = SimpleNamespace(lineNumber=np.zeros(3), fiducial=np.arange(3.0), x=np.zeros(3), y=np.zeros(3), z=np.zeros(3), elevation=np.zeros(3))
-    dc = SimpleNamespace(depth_bin_width=0.5, n_rel_groups=1, n_add_groups=2, n_error_bins=2, n_depth_bins=4)
-    widths = dict(status=1, burned_in_iteration=1, n_accepted=1, misfit=1, relative_error=1, additive_error=2, n_layers=1, best_n_layers=1,
-                  layer_count_posterior=3, additive_error_posterior=4, mean_log10_conductivity=4)
-    named = [(k, np.zeros((0, w))) for k, w in widths.items()]
-    r = np.zeros((3, sum(widths.values())))
+    dc = SimpleNamespace(depth_bin_width=0.5)
+    i32, i64, f64 = np.dtype(np.int32), np.dtype(np.int64), np.dtype(np.float64)
+    columns = [(k, tail, dtype, True) for k, tail, dtype in (
+        ("status", (), i32), ("burned_in_iteration", (), i32), ("n_accepted", (), i64), ("misfit", (), f64), ("relative_error", (1,), f64),
+        ("additive_error", (2,), f64), ("n_layers", (), i32), ("best_n_layers", (), i32), ("layer_count_posterior", (3,), i64),
+        ("additive_error_posterior", (2, 2), i64), ("mean_log10_conductivity", (4,), f64))]
+    r = np.zeros((3, 20))
     r[:, 0], r[:, 1], r[:, 2] = [1, 2, 0], [10, 0, 0], [50, 20, 30]
-    res = survey_run.assemble_result(ds, {"n_markov_chains": 100}, dc, named, r, 1, 77)
+    res = survey_run.assemble_result(ds, {"n_markov_chains": 100}, dc, columns, r, 77)
     assert res["iterations"].tolist() == [111, 100, 77] and res["iterations"].dtype == np.int64 and "n_accepted" not in res
     assert np.array_equal(res["acceptance"], [50 / 111, 0.2, 30 / 77])
     for k in ("status", "burned_in_iteration", "n_layers", "best_n_layers"):
         assert res[k].dtype == np.int32 and res[k].shape == (3,)
     assert res["layer_count_posterior"].dtype == np.int64 and res["additive_error_posterior"].shape == (3, 2, 2) and res["additive_error_posterior"].dtype == np.int64
     assert res["misfit"].dtype == np.float64 and res["mean_log10_conductivity"].shape == (3, 4) and res["depth_bin_width"] == 0.5
-    assert set(survey.INTEGER_SUMMARIES) >= {"status", "n_used", "replicates_used", "rx_pitch_posterior", "height_posterior"}
+
+
+def test_summaries_declare_what_the_result_holds():
+    """SurveyRun.summaries itself, on a stand-in sampler of host tensors (no hit map, so no kernel runs): sampled height and one sampled
+    angle, two error groups, two replicate chains -- the counts come back int32, the posteriors' counts and the replicates' counts
+    int64, through layout, pack and unpack."""
+    S, C, nd, K = 3, 2, 4, 3
+    z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt)
+    i32 = torch.int32
+    t = dict(status=z(S, dt=i32), burned_in_iteration=z(S, dt=i32), n_accepted=z(S, dt=torch.int64), misfit=z(S), rel=z(S, 1), add=z(S, 2),
+             k=z(S, dt=i32), best_k=z(S, dt=i32), best_posterior=z(S), best_edges=z(S, K), best_sigma=z(S, K), k_hist=z(S, K + 1, dt=i32),
+             edge_hist=z(S, nd, dt=i32), rel_hist=z(S, 1, 99, dt=i32), add_hist=z(S, 2, 99, dt=i32), geom_hist=z(S, 1, 199, dt=i32),
+             height=z(S), best_height=z(S), height_hist=z(S, 99, dt=i32))
+    dc = SimpleNamespace(t=t, _moves=[("rx_pitch", None, None, None, None, 7)], sampled_angles=lambda which: {"rx_pitch": z(S)},
+                         solve_height=True, use=torch.ones(S, C, dtype=torch.bool))
+    diag = dict(rhat=z(S, nd), jsd=z(S, nd), n_used=z(S, nd, dt=i32), chain_mean=z(S, C, nd), rhat_layers=z(S), jsd_layers=z(S),
+                rhat_interfaces=z(S), rhat_max=z(S))
+    run = SimpleNamespace(clock=survey_run.PhaseClock(None), hitmap=False, C_rep=C, ensemble_diagnostics=None, ensemble_correlation=None,
+                          ensemble_families=None)
+    entries = survey_run.SurveyRun.summaries(run, dc, diag)
+    res = survey_run.unpack(survey_run.layout(entries), survey_run.pack(entries).numpy())
+    assert list(res)[-len(survey.REPLICATE_SUMMARIES) - 1:] == list(survey.REPLICATE_SUMMARIES) + ["replicates_used"]
+    for k in ("status", "burned_in_iteration", "n_layers", "best_n_layers"):
+        assert res[k].dtype == np.int32 and res[k].shape == (S,)
+    for k, shape in (("n_used", (S, nd)), ("replicates_used", (S,)), ("rx_pitch_posterior", (S, 7)), ("height_posterior", (S, 99)),
+                     ("layer_count_posterior", (S, K + 1)), ("interface_posterior", (S, nd)), ("relative_error_posterior", (S, 99)),
+                     ("additive_error_posterior", (S, 2, 99))):
+        assert res[k].dtype == np.int64 and res[k].shape == shape, k
+    assert res["replicates_used"].tolist() == [C] * S
+    for k, shape in (("relative_error", (S,)), ("additive_error", (S, 2)), ("rx_pitch", (S,)), ("best_height", (S,)), ("chain_mean", (S, C, nd)),
+                     ("rhat", (S, nd)), ("rhat_max", (S,)), ("best_edges", (S, K))):
+        assert res[k].dtype == np.float64 and res[k].shape == shape, k
