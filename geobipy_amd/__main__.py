@@ -68,6 +68,10 @@ def parse(argv=None):
                    help="chain diagnostics of the ensemble (needs --ensemble): effective sample size, split R-hat, autocorrelation time and "
                         "Monte-Carlo standard error per depth cell, lags up to MAX_LAG (1 .. 255, default 255): ensemble_ess, ensemble_rhat, "
                         "... in the summaries")
+    p.add_argument("--ensemble-rank-diagnostics", type=int, nargs="?", const=255, default=None, metavar="MAX_LAG",
+                   help="rank diagnostics of the ensemble (needs --ensemble): rank-normalised and folded split R-hat, bulk and tail "
+                        "effective sample size per depth cell, lags up to MAX_LAG (1 .. 255, default 255): ensemble_rhat_rank, "
+                        "ensemble_ess_bulk, ensemble_ess_tail, ... in the summaries")
     p.add_argument("--ensemble-correlation", nargs="*", default=None, metavar="BAND [THRESHOLD]",
                    help="vertical resolution from the ensemble (needs --ensemble): the posterior correlation between depth cells up to BAND "
                         "cells apart (>= 0, default 64) and the thickness over which it stays >= THRESHOLD (0 < THRESHOLD < 1, default 0.5): "
@@ -85,7 +89,7 @@ def parse(argv=None):
                                           threshold=float(a.ensemble_correlation[1]) if len(a.ensemble_correlation) > 1 else 0.5)
         except ValueError:
             p.error("--ensemble-correlation: BAND is an integer, THRESHOLD a number")
-    # the ranges, and that each of the three needs --ensemble, are infer's own checks
+    # the ranges, and that each of the four needs --ensemble, are infer's own checks
     from . import survey_run
     try:
         if a.ensemble_families is not None:
@@ -94,6 +98,8 @@ def parse(argv=None):
             survey_run.ensemble_correlation_argument(a.ensemble_correlation, a.ensemble)
         if a.ensemble_diagnostics is not None:
             survey_run.ensemble_diagnostics_argument(dict(max_lag=a.ensemble_diagnostics), a.ensemble)
+        if a.ensemble_rank_diagnostics is not None:
+            survey_run.ensemble_rank_diagnostics_argument(dict(max_lag=a.ensemble_rank_diagnostics), a.ensemble)
     except ValueError as e:
         p.error(str(e))
     if a.ensemble is not None:
@@ -160,7 +166,8 @@ def main(argv=None):
                        data_posteriors=None if a.data_posteriors is None else dict(n_bins=a.data_posteriors), ensemble=a.ensemble,
                        ensemble_diagnostics=False if a.ensemble_diagnostics is None else dict(max_lag=a.ensemble_diagnostics),
                        ensemble_correlation=False if a.ensemble_correlation is None else a.ensemble_correlation,
-                       ensemble_families=False if a.ensemble_families is None else dict(max_families=a.ensemble_families))
+                       ensemble_families=False if a.ensemble_families is None else dict(max_families=a.ensemble_families),
+                       ensemble_rank_diagnostics=False if a.ensemble_rank_diagnostics is None else dict(max_lag=a.ensemble_rank_diagnostics))
     if rank == 0:
         paths = res.save_lines(a.output_directory)
         done, failed = int((res["status"] == 1).sum()), int((res["status"] == 2).sum())

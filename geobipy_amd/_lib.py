@@ -145,6 +145,10 @@ SIGNATURES = {
                                        c_void_p]),
     "gbp_ensemble_diagnostics": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gbp_series_ranks": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "gbp_ensemble_ranks": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_int, c_double_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gbp_series_correlation": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
     "gbp_ensemble_correlation": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

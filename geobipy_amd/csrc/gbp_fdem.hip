@@ -1888,6 +1888,66 @@ extern "C" gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const 
     return series_diagnostics_launch("gbp_ensemble_diagnostics", ensemble::SERIES_RASTER, B, a, stream);
 }
 
+#include "gbp_ensemble_ranks.h"
+
+// Ranks within columns (csrc/gbp_ensemble_ranks.h k_series_ranks; the rule: include/geobipy_amd.h): one workgroup per (sounding, tile
+// of T columns), T and the padded length P from n_rows.
+static gbp_status series_ranks_launch(const char* entry, int source, int B, ensemble::RankArgs a, int fold, const double* p, void* stream)
+{
+    using namespace ensemble;
+    const gbp_status status = series_check(entry, source, B, a, 0, RANK_MAX_P, "%s: n_p outside 0 .. 16", true);
+    if (status != GBP_OK) return status;
+    if (a.n_rows > RANK_MAX_ROWS) return fail(GBP_ERR_INVALID_ARG, "%s: more than 16 384 rows", entry);
+    if (a.reach > 0 && !p) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    for (int q = 0; q < a.reach; ++q) {
+        if (!(std::isfinite(p[q]) && p[q] >= 0.0 && p[q] <= 1.0)) return fail(GBP_ERR_INVALID_ARG, "%s: a probability outside [0, 1]", entry);
+        a.p[q] = p[q];
+    }
+    if ((a.less == nullptr) != (a.leq == nullptr)) return fail(GBP_ERR_INVALID_ARG, "%s: less and leq come as a pair", entry);
+    if (a.order != nullptr && a.reach == 0) a.order = nullptr;      // (nothing to write)
+    int P = 1;
+    while (P < a.n_rows) P <<= 1;
+    const int T = std::min(64, RANK_TILE_DOUBLES / P);
+    const int64_t blocks = (int64_t)B * ((a.V + T - 1) / T);
+    if (blocks * RANK_THREADS > 0xffffffffLL)                       // (a dispatch counts its work-items in 32 bits)
+        return fail(GBP_ERR_INVALID_ARG, "%s: B * column tiles out of range (more than 2^32 - 1 threads)", entry);
+    if (B == 0 || (!a.less && !a.order && !a.x_out)) return GBP_OK;
+    a.T = T;
+    a.P = P;
+    const size_t lds = rank_lds_bytes(T, P);
+    auto launch = [&](auto kern) -> gbp_status {
+        static std::atomic<bool> allowed[64];      // per instantiation and device: asked for once, for the largest tile
+        int dev = 0;
+        GBP_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !allowed[dev].load(std::memory_order_acquire)) {
+            GBP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_lds_bytes(64, RANK_TILE_DOUBLES / 64)));
+            if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_release);
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(RANK_THREADS), lds, (hipStream_t)stream, a);
+        GBP_HIP(hipGetLastError());
+        return GBP_OK;
+    };
+    if (source == SERIES_RASTER) return fold ? launch(k_series_ranks<SERIES_RASTER, true>) : launch(k_series_ranks<SERIES_RASTER, false>);
+    return fold ? launch(k_series_ranks<SERIES_PLAIN, true>) : launch(k_series_ranks<SERIES_PLAIN, false>);
+}
+
+extern "C" gbp_status gbp_series_ranks(int B, int n_rows, int V, const double* x, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                       const int32_t* seg_n, int fold, int n_p, const double* p, int32_t* less, int32_t* leq, double* order,
+                                       double* x_out, void* stream)
+{
+    const ensemble::RankArgs a = {{n_rows, V, x, 0, nullptr, nullptr, nullptr, nullptr, M_max, n_p, seg_start, seg_m, seg_n}, less, leq, order, x_out, 0, 0, {}};
+    return series_ranks_launch("gbp_series_ranks", ensemble::SERIES_PLAIN, B, a, fold, p, stream);
+}
+
+extern "C" gbp_status gbp_ensemble_ranks(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                         int n_depth, const double* z, int M_max, const int32_t* seg_start, const int32_t* seg_m,
+                                         const int32_t* seg_n, int fold, int n_p, const double* p, int32_t* less, int32_t* leq, double* order,
+                                         double* x_out, void* stream)
+{
+    const ensemble::RankArgs a = {{n_slots, n_depth, nullptr, K, ens_k, ens_edges, ens_sigma, z, M_max, n_p, seg_start, seg_m, seg_n}, less, leq, order, x_out, 0, 0, {}};
+    return series_ranks_launch("gbp_ensemble_ranks", ensemble::SERIES_RASTER, B, a, fold, p, stream);
+}
+
 #include "gbp_ensemble_corr.h"
 
 // Correlation between variables (csrc/gbp_ensemble_corr.h; the rule: include/geobipy_amd.h): the moments, the MFMA kernel, then the two

@@ -21,8 +21,14 @@ every ``thin``-th sampled model of every chain, in chain order, up to ``n_keep``
                    the fp64 matrix cores, the series never written (gbp_ensemble_correlation / gbp_series_correlation / gbp_band_runs;
                    DESIGN.md 3.22).  ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH --correlation [BAND]``.
 
+``rank_diagnostics``  the same question for what the project publishes, the percentiles: rank-normalised and folded split R-hat, bulk
+                   ESS, the ESS of the indicator I(x <= Q_p) behind every percentile and the tail ESS (Vehtari et al. 2021), built on the
+                   rank of every kept sample within its (sounding, cell) column (gbp_ensemble_ranks / gbp_series_ranks; DESIGN.md
+                   3.24); ``quantiles``: the exact sample quantiles of the kept models; ``correlation(rank=True)``: Spearman's.
+                   ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH --rank [--percentiles P ...]``.
+
 There is no host fallback: all refuse tensors that are not on the device (``realisations_reference`` states the raster's rule in numpy,
-``diagnostics_reference`` that of the diagnostics, ``correlation_reference`` and ``correlation_runs_reference`` those of the correlation).
+``diagnostics_reference`` that of the diagnostics, ``correlation_reference`` and ``correlation_runs_reference`` those of the correlation, ``rank_counts_reference`` that of the ranks).
 """
 import ctypes
 from collections import namedtuple
@@ -347,16 +353,21 @@ def _check_segments(seg_start, seg_m, seg_n, B, n_rows, what):
     return seg_start.contiguous(), seg_m.contiguous(), seg_n.contiguous()
 
 
-def _check_series(x, seg_start, seg_m, seg_n, what, entry, check_v=lambda V: None):
+def _check_series(x, seg_start, seg_m, seg_n, what, entry, check_v=lambda V: None, ranked=False):
     """The checks ``series_diagnostics`` and ``series_correlation`` share, in their order: tensors, x, ``check_v(V)`` (the entry's own
-    check that needs V), the segment lists, and the device last.  Returns x and the lists, contiguous, and what ``check_v`` gave."""
+    check that needs V), the segment lists, and the device last.  Returns x and the lists, contiguous, and what ``check_v`` gave.
+    ``ranked``: the columns are ranked too (``series_ranks``): at most 16 384 rows, and segments that do not overlap."""
     _are_tensors((x, seg_start, seg_m, seg_n), what, entry)
     if x.dtype != torch.float64:
         raise TypeError("%s: x is float64" % what)
     if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
         raise ValueError("%s: x is float64 [B, n_rows, V] with 1 <= n_rows <= 32768 and V >= 1" % what)
+    if ranked and x.shape[1] > RANK_MAX_ROWS:
+        raise ValueError("%s: at most %d rows where columns are ranked (a padded column lives in LDS); x has %d" % (what, RANK_MAX_ROWS, x.shape[1]))
     own = check_v(x.shape[2])
     seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, x.shape[0], x.shape[1], what)
+    if ranked and seg_m.numel() and bool((seg_m.to(torch.int64) * seg_n.to(torch.int64) > x.shape[1]).any()):
+        raise ValueError("%s: the segments overlap (seg_m * seg_n > n_rows)" % what)
     _on_device((x, seg_start, seg_m, seg_n), what, entry)
     return x.contiguous(), seg_start, seg_m, seg_n, own
 
@@ -468,6 +479,328 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
     ess = out["ess"]
     lowest = torch.where(torch.isfinite(ess), ess, torch.full_like(ess, float("inf"))).min(dim=1).values if nd else torch.full((B,), float("inf"), device=dev)
     out["ess_min"] = torch.where(torch.isfinite(lowest), lowest, torch.full_like(lowest, float("nan")))
+    return out
+
+
+RANK_MAX_ROWS, RANK_MAX_PROBABILITIES, RANK_BLOCK_BYTES = 16384, 16, 2 << 30
+
+
+def check_probabilities(probabilities):
+    """``probabilities`` (None: none) as a float64 numpy list of at most 16 finite numbers in [0, 1]."""
+    if probabilities is None:
+        return np.zeros(0, dtype=np.float64)
+    p = np.asarray(probabilities, dtype=np.float64)
+    if p.ndim != 1 or p.size > RANK_MAX_PROBABILITIES:
+        raise ValueError("probabilities: a list of at most %d numbers" % RANK_MAX_PROBABILITIES)
+    if not np.all(np.isfinite(p) & (p >= 0.0) & (p <= 1.0)):
+        raise ValueError("probabilities: every one finite and in [0, 1]")
+    return p
+
+
+def check_percentiles(percentiles):
+    """``percentiles`` as a tuple of 1 .. 16 distinct, ascending floats in [0, 100]."""
+    try:
+        q = np.asarray(percentiles, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("percentiles: a list of numbers in [0, 100]")
+    if q.ndim != 1 or not 1 <= q.size <= RANK_MAX_PROBABILITIES:
+        raise ValueError("percentiles: a list of 1 .. %d numbers" % RANK_MAX_PROBABILITIES)
+    if not np.all(np.isfinite(q) & (q >= 0.0) & (q <= 100.0)) or not np.all(np.diff(q) > 0.0):
+        raise ValueError("percentiles: distinct, ascending numbers in [0, 100]")
+    return tuple(float(v) for v in q)
+
+
+def percentile_name(q):
+    """'5' for 5.0, '2.5' for 2.5: what follows ``ess_percentile_`` and ``quantile_``."""
+    return "%g" % q
+
+
+def rank_counts_reference(x, seg_start, n, fold=False, probabilities=None):
+    """The rule of the ranks for one sounding, in numpy: ``x`` [n_rows, V], M = len(seg_start) segments of ``n`` rows each (the lists
+    ``segments`` builds); the used rows are r_j = seg_start[m] + t, j = m n + t, nu = M n of them.  Returns {less, leq int32
+    [n_rows, V], order f64 [Q, 2, V]} for Q = len(probabilities) <= 16 probabilities in [0, 1].
+
+    Per variable v with the column c_j = x[r_j, v] and s = c sorted ascending: lo_i = floor((nu - 1) p_i) (one fp64 product),
+    order[i, 0, v] = s[lo_i], order[i, 1, v] = s[min(lo_i + 1, nu - 1)] -- before any folding.  ``fold``: med = 0.5 (s[(nu - 1) // 2] +
+    s[nu // 2]), c_j <- |c_j - med| (one subtraction, then the absolute value; +inf ranks as the largest).  less[r_j] = #{i : c_i < c_j},
+    leq[r_j] = #{i : c_i <= c_j}: values compare as doubles (-0.0 equals +0.0), so 0 <= less < leq <= nu.  A row in no segment:
+    less = leq = -1.  M == 0 or n < 4: -1 everywhere and order NaN.  A variable with a non-finite used value: -1 at the used rows
+    too, its order NaN.  Segments that overlap (M n > n_rows) are refused."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("rank_counts_reference: x [n_rows, V]")
+    p = check_probabilities(probabilities)
+    starts = [int(q) for q in np.asarray(seg_start).reshape(-1)]
+    M, N, V = len(starts), int(n), x.shape[1]
+    if M > MAX_SEGMENTS:
+        raise ValueError("rank_counts_reference: at most %d segments" % MAX_SEGMENTS)
+    less, leq = np.full(x.shape, -1, dtype=np.int32), np.full(x.shape, -1, dtype=np.int32)
+    order = np.full((p.size, 2, V), np.nan)
+    out = dict(less=less, leq=leq, order=order)
+    if M == 0 or N < 4:
+        return out
+    if min(starts) < 0 or max(starts) + N > x.shape[0]:
+        raise ValueError("rank_counts_reference: a segment leaves the rows 0 .. %d" % (x.shape[0] - 1))
+    nu = M * N
+    if nu > x.shape[0]:
+        raise ValueError("rank_counts_reference: the segments overlap (M n > n_rows)")
+    rows = np.concatenate([np.arange(q, q + N) for q in starts])
+    lo = np.floor(np.float64(nu - 1) * p).astype(np.int64)
+    for v in range(V):
+        c = x[rows, v]
+        if not np.all(np.isfinite(c)):
+            continue
+        s = np.sort(c)
+        order[:, 0, v], order[:, 1, v] = s[lo], s[np.minimum(lo + 1, nu - 1)]
+        if fold:
+            with np.errstate(over="ignore"):
+                med = 0.5 * (s[(nu - 1) // 2] + s[nu // 2])
+                c = np.abs(c - med)
+            s = np.sort(c)
+        less[rows, v], leq[rows, v] = np.searchsorted(s, c, side="left"), np.searchsorted(s, c, side="right")
+    return out
+
+
+def _used_count(seg_m, seg_n, like):
+    """nu = M N per sounding as f64 shaped to broadcast against ``like`` [B, ...] (torch)."""
+    nu = seg_m.to(torch.float64) * seg_n.to(torch.float64)
+    return nu.reshape((-1,) + (1,) * (like.ndim - 1))
+
+
+def midranks(less, leq):
+    """(less + leq + 1) / 2 in f64 -- ``scipy.stats.rankdata(method="average")`` of the column; NaN where less < 0.  Torch."""
+    r = less.to(torch.float64)                                         # (in place: one f64 series beside the counts)
+    r += leq
+    r += 1.0
+    r /= 2.0
+    return r.masked_fill_(less < 0, float("nan"))
+
+
+def normal_scores(less, leq, nu):
+    """z = ndtri((r - 3/8) / (nu + 1/4)) of the midrank r (Blom's scores); nu broadcasts against less; NaN where less < 0.  Torch."""
+    r = midranks(less, leq)
+    r -= 0.375
+    r /= nu + 0.25
+    return torch.special.ndtri(r, out=r)
+
+
+def quantile_cells(nu, p):
+    """lo = floor((nu - 1) p) and g = (nu - 1) p - lo (f64 torch, shaped as nu): the cell of numpy's ``method="linear"``."""
+    h = (nu - 1.0) * float(p)
+    lo = torch.floor(h)
+    return lo, h - lo
+
+
+def indicators(less, nu, p):
+    """I_p = 1.0 where less <= floor((nu - 1) p), else 0.0 -- with ties exactly I(x <= Q_p).  Torch, f64."""
+    return (less.to(torch.float64) <= quantile_cells(nu, p)[0]).to(torch.float64)
+
+
+def sample_quantile(order, nu, i, p):
+    """order[..., i, 0, :] + g (order[..., i, 1, :] - order[..., i, 0, :]): numpy's ``method="linear"`` quantile.  Torch."""
+    o0, o1 = order[..., i, 0, :], order[..., i, 1, :]
+    g = quantile_cells(nu, p)[1]
+    return o0 + g.reshape(g.shape[:o0.ndim]) * (o1 - o0)
+
+
+def _truncated(pairs, L):
+    return (pairs > 0) & (pairs == (L + 1) // 2)
+
+
+def rank_products_reference(z, z_folded, indicator, seg_start, n, max_lag, dtype=np.float64):
+    """The rank products of one sounding from its derived series (numpy [n_rows, V]; ``indicator``: {percentile: series}), each
+    through ``diagnostics_reference`` in ``dtype``: rhat_bulk, ess_bulk, tau_bulk, truncated_bulk (z), rhat_folded (z_folded),
+    rhat_rank = max of the two, ess_percentile_<p> (I_p), ess_tail = min of the ESS of the lowest and the highest percentile; NaN
+    propagates through max and min."""
+    d = diagnostics_reference(z, seg_start, n, max_lag, dtype=dtype)
+    out = dict(rhat_bulk=d["rhat"], ess_bulk=d["ess"], tau_bulk=d["tau"], truncated_bulk=_truncated(d["pairs"], d["L"]))
+    out["rhat_folded"] = diagnostics_reference(z_folded, seg_start, n, max_lag, dtype=dtype)["rhat"]
+    out["rhat_rank"] = np.maximum(out["rhat_bulk"], out["rhat_folded"])
+    qs = sorted(indicator)
+    for q in qs:
+        out["ess_percentile_" + percentile_name(q)] = diagnostics_reference(indicator[q], seg_start, n, max_lag, dtype=dtype)["ess"]
+    out["ess_tail"] = np.minimum(out["ess_percentile_" + percentile_name(qs[0])], out["ess_percentile_" + percentile_name(qs[-1])])
+    return out
+
+
+def rank_diagnostics_reference(x, seg_start, n, max_lag, percentiles=(5, 50, 95), dtype=np.float64):
+    """The rule of the rank diagnostics for one sounding on the host: ``rank_counts_reference`` (unfolded with p = percentiles / 100,
+    and folded), the derived series by the expressions the device uses (``normal_scores``, ``indicators``, ``sample_quantile``, here
+    on CPU tensors), then ``rank_products_reference``; adds quantile_<p> [V]."""
+    qs = check_percentiles(percentiles)
+    x = np.asarray(x, dtype=np.float64)
+    starts = np.asarray(seg_start).reshape(-1)
+    plain = rank_counts_reference(x, starts, n, fold=False, probabilities=[q / 100.0 for q in qs])
+    folded = rank_counts_reference(x, starts, n, fold=True)
+    nu = torch.tensor(float(len(starts) * int(n)), dtype=torch.float64)
+    t = lambda a: torch.as_tensor(a)      # noqa: E731
+    z = normal_scores(t(plain["less"]), t(plain["leq"]), nu).numpy()
+    zf = normal_scores(t(folded["less"]), t(folded["leq"]), nu).numpy()
+    ind = {q: indicators(t(plain["less"]), nu, q / 100.0).numpy() for q in qs}
+    out = rank_products_reference(z, zf, ind, starts, n, max_lag, dtype=dtype)
+    for i, q in enumerate(qs):
+        out["quantile_" + percentile_name(q)] = sample_quantile(t(plain["order"]), nu, i, q / 100.0).numpy()
+    return out
+
+
+def _launch_ranks(entry, head, B, n_rows, V, dev, seg_start, seg_m, seg_n, fold, p, counts, order, values):
+    """One call of gbp_series_ranks / gbp_ensemble_ranks (``head``: the entry's arguments up to M_max) on fresh outputs: {less, leq
+    int32 [B, n_rows, V] (``counts``), order f64 [B, Q, 2, V] (``order``), x_out f64 [B, n_rows, V] (``values``)}."""
+    out = {}
+    if counts:
+        out["less"], out["leq"] = (torch.empty((B, n_rows, V), dtype=torch.int32, device=dev) for _ in range(2))
+    if order:
+        out["order"] = torch.empty((B, p.size, 2, V), dtype=torch.float64, device=dev)
+    if values:
+        out["x_out"] = torch.empty((B, n_rows, V), dtype=torch.float64, device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out and out[name].numel() else None      # noqa: E731
+    if B > 0:
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.load(), entry)(*head, int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(), seg_n.data_ptr(),
+                                                   int(bool(fold)), int(p.size), (ctypes.c_double * max(int(p.size), 1))(*p), ptr("less"),
+                                                   ptr("leq"), ptr("order"), ptr("x_out"), _stream(dev)))
+    return out
+
+
+def series_ranks(x, seg_start, seg_m, seg_n, fold=False, probabilities=None, counts=True, values=False):
+    """The ranks (``rank_counts_reference`` states the rule) within the columns of the series ``x`` f64 [B, n_rows, V] on the device,
+    n_rows <= 16 384, segments as ``series_diagnostics`` takes them (they may not overlap).  Returns {less, leq int32 [B, n_rows, V]
+    (``counts``), order f64 [B, Q, 2, V] (with ``probabilities``), x_out f64 [B, n_rows, V] (``values``: the ranked values at the used
+    rows, NaN elsewhere)}.  One kernel (gbp_series_ranks)."""
+    p = check_probabilities(probabilities)
+    x, seg_start, seg_m, seg_n, _ = _check_series(x, seg_start, seg_m, seg_n, "series_ranks", "gbp_series_ranks", ranked=True)
+    B, n_rows, V = x.shape
+    return _launch_ranks("gbp_series_ranks", (B, n_rows, V, x.data_ptr()), B, n_rows, V, x.device, seg_start, seg_m, seg_n, fold, p, counts,
+                         p.size > 0, values)
+
+
+def _rank_products(ranker, seg_start, seg_m, seg_n, max_lag, qs):
+    """The products of ``rank_products_reference`` and the quantiles on the device: ``ranker(fold, p)`` gives {less, leq, order} of
+    the series; the derived series exist one at a time."""
+    p = np.asarray([q / 100.0 for q in qs], dtype=np.float64)
+    r = ranker(False, p)
+    less = r["less"]
+    nu = _used_count(seg_m, seg_n, less)
+    d = series_diagnostics(normal_scores(less, r["leq"], nu), seg_start, seg_m, seg_n, max_lag=max_lag)
+    out = dict(rhat_bulk=d["rhat"], ess_bulk=d["ess"], tau_bulk=d["tau"], truncated_bulk=d["truncated"])
+    for i, q in enumerate(qs):
+        out["ess_percentile_" + percentile_name(q)] = series_diagnostics(indicators(less, nu, p[i]), seg_start, seg_m, seg_n, max_lag=max_lag)["ess"]
+        out["quantile_" + percentile_name(q)] = sample_quantile(r["order"], nu, i, p[i])
+    del r, less, d
+    f = ranker(True, np.zeros(0))
+    out["rhat_folded"] = series_diagnostics(normal_scores(f["less"], f["leq"], nu), seg_start, seg_m, seg_n, max_lag=max_lag)["rhat"]
+    out["rhat_rank"] = torch.maximum(out["rhat_bulk"], out["rhat_folded"])
+    out["ess_tail"] = torch.minimum(out["ess_percentile_" + percentile_name(qs[0])], out["ess_percentile_" + percentile_name(qs[-1])])
+    return out
+
+
+def series_rank_diagnostics(x, seg_start, seg_m, seg_n, max_lag=255, percentiles=(5, 50, 95)):
+    """The rank diagnostics (``rank_diagnostics_reference`` states the rule) of the series ``x`` f64 [B, n_rows, V] on the device:
+    rhat_bulk, ess_bulk, tau_bulk, rhat_folded, rhat_rank, ess_percentile_<p>, ess_tail, quantile_<p> f64 [B, V], truncated_bulk bool
+    [B, V].  gbp_series_ranks twice (unfolded, folded), the derived series through gbp_series_diagnostics."""
+    max_lag = check_max_lag(max_lag)
+    qs = check_percentiles(percentiles)
+    x, seg_start, seg_m, seg_n, _ = _check_series(x, seg_start, seg_m, seg_n, "series_rank_diagnostics", "gbp_series_ranks", ranked=True)
+    B, n_rows, V = x.shape
+    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, n_rows, V, x.data_ptr()), B, n_rows, V, x.device, seg_start, seg_m, seg_n,      # noqa: E731
+                                           fold, p, True, p.size > 0, False)
+    return _rank_products(ranker, seg_start, seg_m, seg_n, max_lag, qs)
+
+
+def _check_slots(ens, what):
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2 and ens.k.shape[1] > RANK_MAX_ROWS:
+        raise ValueError("%s: at most %d slots per sounding (a padded column lives in LDS); the ensemble has %d" % (what, RANK_MAX_ROWS, ens.k.shape[1]))
+
+
+def _ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s):
+    """``ranker(fold, p, counts=True, values=False)`` of soundings ``s`` (a slice) through gbp_ensemble_ranks."""
+    n = s.stop - s.start
+    head = (n, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd, z.data_ptr())
+    return lambda fold, p, counts=True, values=False: _launch_ranks("gbp_ensemble_ranks", head, n, ns, nd, k.device, start[s], seg_m[s], seg_n[s],
+                                                                    fold, p, counts, p.size > 0, values)
+
+
+def _rank_block(block, B, ns, nd):
+    """Soundings per launch: ``block``, or as many as keep less, leq and the derived series beside them (32 B a sample) under 2 GiB."""
+    return max(1, min(max(B, 1), RANK_BLOCK_BYTES // (32 * ns * nd))) if block is None else int(block)
+
+
+def ensemble_ranks(ens, depth_edges, chains=1, fold=False, probabilities=None, counts=True, values=False):
+    """``series_ranks`` of the series log10 conductivity at the centres of ``depth_edges`` [n_depth + 1] over the kept models, the
+    series never read from memory (gbp_ensemble_ranks; the used samples are those of ``diagnostics``); one launch, [B, n_slots,
+    n_depth] outputs.  ``values``: x_out, the values that were ranked."""
+    p = check_probabilities(probabilities)
+    _check_slots(ens, "ensemble_ranks")
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2:
+        check_chains(chains, ens.k.shape[1])
+    z_np = centres(depth_edges)
+    k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "ensemble_ranks", "gbp_ensemble_ranks", misfit=False)
+    z = torch.as_tensor(z_np).to(k.device)
+    out = _ensemble_ranker(k, edges, sigma, ns, K, C, z, int(z_np.size), start, seg_m, seg_n, slice(0, B))(fold, p, counts, values)
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
+    return out
+
+
+def rank_diagnostics(ens, depth_edges, chains=1, max_lag=None, percentiles=(5, 50, 95), block=None):
+    """Did the chains run long enough for the percentiles?  Per sounding and cell of ``depth_edges`` [n_depth + 1], on the series
+    and the used samples of ``diagnostics`` (``rank_diagnostics_reference`` states the rule): rhat_bulk, rhat_folded and rhat_rank =
+    their maximum (rank-normalised split R-hat: free of the variable's scale, and the folded one sees chains that differ in spread),
+    ess_bulk, tau_bulk, truncated_bulk, ess_percentile_<p> (the independent samples behind percentile p), ess_tail (the smaller of
+    the lowest and the highest percentile's; NaN where the percentile sits on the sample's extreme) and quantile_<p>, the exact
+    sample quantile, f64 [B, n_depth]; the same names with ``_k`` (the layer count) and ``_misfit`` (log10 of the misfit) [B];
+    ess_bulk_min [B], the smallest finite ess_bulk over the cells (NaN: none); n_chains_used, segment_length, n_segments int32 [B].
+    At most 16 384 slots.  ``block``: soundings per launch (None: as many as keep a block's counts and derived series under 2 GiB)."""
+    max_lag = check_max_lag(max_lag)
+    qs = check_percentiles(percentiles)
+    _check_slots(ens, "rank_diagnostics")
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2:
+        check_chains(chains, ens.k.shape[1])
+    z_np = centres(depth_edges)
+    _check_block(block, "rank_diagnostics")
+    k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "rank_diagnostics", "gbp_ensemble_ranks", misfit=True)
+    nd, dev = int(z_np.size), k.device
+    z = torch.as_tensor(z_np).to(dev)
+    step = _rank_block(block, B, ns, nd)
+    parts = []
+    for b0 in range(0, B, step):
+        s = slice(b0, min(B, b0 + step))
+        parts.append(_rank_products(_ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s), start[s], seg_m[s], seg_n[s], max_lag, qs))
+    if not parts:
+        parts.append(_rank_products(_ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, slice(0, 0)), start, seg_m, seg_n, max_lag, qs))
+    out = {name: torch.cat([q[name] for q in parts]) for name in parts[0]}
+    scalars = torch.stack((k.to(torch.float64), torch.log10(ens.misfit.to(torch.float64))), dim=2).contiguous()
+    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, ns, 2, scalars.data_ptr()), B, ns, 2, dev, start, seg_m, seg_n, fold, p, True,      # noqa: E731
+                                           p.size > 0, False)
+    two = _rank_products(ranker, start, seg_m, seg_n, max_lag, qs)
+    for name in list(two):
+        out[name + "_k"], out[name + "_misfit"] = two[name][:, 0], two[name][:, 1]
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
+    ess = out["ess_bulk"]
+    lowest = torch.where(torch.isfinite(ess), ess, torch.full_like(ess, float("inf"))).min(dim=1).values if nd else torch.full((B,), float("inf"), device=dev)
+    out["ess_bulk_min"] = torch.where(torch.isfinite(lowest), lowest, torch.full_like(lowest, float("nan")))
+    return out
+
+
+def quantiles(ens, depth_edges, percentiles, chains=1, block=None):
+    """The exact sample quantiles (numpy's ``method="linear"``) of log10 conductivity at the centres of ``depth_edges`` over the used
+    kept models -- not the hit map's 250 value cells: {quantile_<p> f64 [B, n_depth], n_chains_used, segment_length, n_segments}.  One
+    launch per block that writes no series (gbp_ensemble_ranks with no counts)."""
+    qs = check_percentiles(percentiles)
+    _check_slots(ens, "quantiles")
+    if torch.is_tensor(ens.k) and ens.k.ndim == 2:
+        check_chains(chains, ens.k.shape[1])
+    z_np = centres(depth_edges)
+    _check_block(block, "quantiles")
+    k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "quantiles", "gbp_ensemble_ranks", misfit=False)
+    nd, dev = int(z_np.size), k.device
+    z = torch.as_tensor(z_np).to(dev)
+    p = np.asarray([q / 100.0 for q in qs], dtype=np.float64)
+    step = max(B, 1) if block is None else int(block)
+    order = torch.cat([_ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, slice(b0, min(B, b0 + step)))(False, p, False)["order"]
+                       for b0 in range(0, max(B, 1), step)])
+    nu = _used_count(seg_m, seg_n, order[:, 0, 0])
+    out = {"quantile_" + percentile_name(q): sample_quantile(order, nu, i, p[i]) for i, q in enumerate(qs)}
+    out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
     return out
 
 
@@ -610,13 +943,17 @@ def check_band(band, V):
     return min(int(band), V - 1)
 
 
-def series_correlation(x, seg_start, seg_m, seg_n, band=None, normalise=True):
+def series_correlation(x, seg_start, seg_m, seg_n, band=None, normalise=True, rank=False):
     """The correlation between the variables (``correlation_reference`` states the rule) of the series ``x`` f64 [B, n_rows, V] on the
     device, segments as ``series_diagnostics`` takes them.  Returns {mean, sd f64 [B, V], band f64 [B, V, W + 1]}: band[b, c, j] =
     R(c, c + j) (``normalise=False``: the covariance), W = ``band`` clipped to V - 1 (None: V - 1, the whole matrix;
-    ``band_to_matrix`` unfolds it).  gbp_series_correlation: centred products on the fp64 matrix cores."""
+    ``band_to_matrix`` unfolds it).  gbp_series_correlation: centred products on the fp64 matrix cores.  ``rank``: Spearman's -- the
+    same on the midranks of every column (``series_ranks``: n_rows <= 16 384, disjoint segments); mean and sd are the midranks'."""
     x, seg_start, seg_m, seg_n, W = _check_series(x, seg_start, seg_m, seg_n, "series_correlation", "gbp_series_correlation",
-                                                  check_v=lambda V: check_band(band, V))
+                                                  check_v=lambda V: check_band(band, V), ranked=bool(rank))
+    if rank:
+        r = series_ranks(x, seg_start, seg_m, seg_n)
+        x = midranks(r["less"], r["leq"])
     (B, n_rows, V), dev = x.shape, x.device
     stats = torch.empty((B, 2, V), dtype=torch.float64, device=dev)
     out = torch.empty((B, V, W + 1), dtype=torch.float64, device=dev)
@@ -652,7 +989,7 @@ def correlation_runs(band, threshold):
 BAND_BLOCK_BYTES = 2 << 30
 
 
-def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=True, block=None, keep_band=True):
+def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=True, block=None, keep_band=True, rank=False):
     """What moves together, and over what thickness?  Per sounding the posterior correlation between the cells of ``depth_edges``
     [n_depth + 1] of the series log10 conductivity at the cell centre over the kept models (``correlation_reference`` states the rule;
     the used samples are those of ``diagnostics``: ``segments``, ``chains`` = C as there), the series never written to memory
@@ -663,7 +1000,11 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     resolution_cells = up + down + 1; resolution_length f64 [B, n_depth] (``resolution_length``: metres, NaN for a cell that is
     constant or non-finite) and resolution_closed = closed_up & closed_down (False: the length is a lower bound -- the run reached
     the band's width or the end of the axis); n_chains_used, segment_length, n_segments int32 [B].  ``block``: soundings per launch
-    (None: as many as keep a block's band under 2 GiB)."""
+    (None: as many as keep a block's band under 2 GiB).  ``rank``: Spearman's correlation -- per block the midranks of every column
+    (gbp_ensemble_ranks) are written as a series [block, n_slots, n_depth] and correlated through gbp_series_correlation; mean and
+    sd are then the midranks'; at most 16 384 slots, and None for ``block`` keeps that series under 2 GiB too."""
+    if rank:
+        _check_slots(ens, "correlation(rank=True)")
     if torch.is_tensor(ens.k) and ens.k.ndim == 2:
         check_chains(chains, ens.k.shape[1])
     z_np = centres(depth_edges)
@@ -674,6 +1015,8 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "correlation", "gbp_ensemble_correlation", misfit=False)
     dev = k.device
     step = max(1, BAND_BLOCK_BYTES // (nd * (W + 1) * 8)) if block is None else int(block)
+    if rank and block is None:
+        step = min(step, _rank_block(None, B, ns, nd))
     stats = torch.empty((B, 2, nd), dtype=torch.float64, device=dev)
     full = torch.empty((B, nd, W + 1), dtype=torch.float64, device=dev) if keep_band else None
     up, down = (torch.empty((B, nd), dtype=torch.int32, device=dev) for _ in range(2))
@@ -687,9 +1030,18 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
             for b0 in range(0, B, step):
                 s = slice(b0, min(B, b0 + step))
                 part = full[s] if keep_band else work[:s.stop - s.start]
-                _lib.check(lib.gbp_ensemble_correlation(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
-                                                        z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), W,
-                                                        int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(), _stream(dev)))
+                if rank:
+                    r = _ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s)(False, np.zeros(0))
+                    mid = midranks(r["less"], r["leq"])
+                    del r
+                    _lib.check(lib.gbp_series_correlation(s.stop - s.start, ns, nd, mid.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(),
+                                                          seg_n[s].data_ptr(), W, int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(),
+                                                          _stream(dev)))
+                    del mid
+                else:
+                    _lib.check(lib.gbp_ensemble_correlation(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
+                                                            z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), W,
+                                                            int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(), _stream(dev)))
                 _lib.check(lib.gbp_band_runs(s.stop - s.start, nd, W, part.data_ptr(), threshold, up[s].data_ptr(), down[s].data_ptr(),
                                              closed[s].data_ptr(), _stream(dev)))
                 live[s] = ~torch.isnan(part[:, :, 0])
@@ -733,6 +1085,11 @@ def _parser():
                    help="instead of the diagnostics: the correlation between depth cells up to BAND cells apart (default 64) and the "
                         "resolution length; writes <name>.correlation.npz")
     p.add_argument("--threshold", type=float, default=None, metavar="T", help="with --correlation: cells move together while R >= T, 0 < T < 1 (default 0.5)")
+    p.add_argument("--spearman", action="store_true", help="with --correlation: correlate the midranks of the columns (Spearman's correlation)")
+    p.add_argument("--rank", action="store_true",
+                   help="instead of the diagnostics: the rank diagnostics (rank-normalised and folded split R-hat, bulk and tail ESS, the ESS "
+                        "behind every percentile, exact sample quantiles); writes <name>.rank_diagnostics.npz")
+    p.add_argument("--percentiles", type=float, nargs="+", default=None, metavar="P", help="with --rank: ascending percentiles in [0, 100] (default 5 50 95)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -790,12 +1147,44 @@ def correlation_path(path):
     return (path[:-4] if path.endswith(".npz") else path) + ".correlation.npz"
 
 
+def parse_rank(argv=None):
+    """``--rank [--percentiles P ...]`` and ``--spearman`` of the command line as (percentiles or None without ``--rank``, spearman);
+    refuses before any device work."""
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.spearman and a.correlation is None:
+        p.error("--spearman needs --correlation")
+    if not a.rank:
+        if a.percentiles is not None:
+            p.error("--percentiles needs --rank")
+        return None, a.spearman
+    if a.correlation is not None:
+        p.error("--rank and --correlation are two runs")
+    try:
+        return check_percentiles((5, 50, 95) if a.percentiles is None else a.percentiles), False
+    except ValueError as e:
+        p.error("--" + str(e))
+
+
+def rank_diagnostics_path(path):
+    """<name>.rank_diagnostics.npz beside the ensemble <name>.npz."""
+    return (path[:-4] if path.endswith(".npz") else path) + ".rank_diagnostics.npz"
+
+
 def main(argv=None):
     path, edges, chains, max_lag, device = parse_args(argv)
     corr = parse_correlation(argv)
+    percentiles, spearman = parse_rank(argv)
+    if percentiles is not None:
+        ens = load(path, device=device)
+        d = rank_diagnostics(ens, edges, chains=chains, max_lag=max_lag, percentiles=percentiles)
+        out = rank_diagnostics_path(path)
+        np.savez_compressed(out, depth_edges=edges, thin=ens.thin, percentiles=np.asarray(percentiles), **{n: v.cpu().numpy() for n, v in d.items()})
+        print("wrote", out)
+        return out
     if corr is not None:
         ens = load(path, device=device)
-        d = correlation(ens, edges, chains=chains, band=corr[0], threshold=corr[1])
+        d = correlation(ens, edges, chains=chains, band=corr[0], threshold=corr[1], rank=spearman)
         out = correlation_path(path)
         np.savez_compressed(out, depth_edges=edges, thin=ens.thin, threshold=corr[1], **{n: v.cpu().numpy() for n, v in d.items()})
         print("wrote", out)

@@ -491,7 +491,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
           exact_jacobian=False, data=None, index=None, fiducial=None, line_number=None, hankel_eps=None, schedule="static",
           chunk=None, results_directory=None, timings=None, traces=1, container=None, units=None, unit_kinds=("arithmetic", "harmonic"),
           first_above=(), first_below=(), replicates=1, data_posteriors=None, ensemble=None, ensemble_diagnostics=False, ensemble_correlation=False,
-          ensemble_families=False, **overrides):
+          ensemble_families=False, ensemble_rank_diagnostics=False, **overrides):
     """Invert every sounding of the options file's data set.  One process per GPU: call from every rank of an initialised
     ``torch.distributed`` group to shard the soundings (``distributed.shard``); rank 0 returns the SurveyResult of the
     whole survey (and writes ``output`` if given), the other ranks return None.
@@ -537,6 +537,12 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     (split R-hat: it works with one chain), ``ensemble_tau_iterations``, ``ensemble_mcse`` [S, n_depth] on the hit map's depth axis and
     ``ensemble_ess_k``, ``ensemble_ess_misfit``, ``ensemble_rhat_k``, ``ensemble_rhat_misfit``, ``ensemble_ess_min`` [S]; with
     ``replicates`` = C every chain of a sounding gives two segments.  The containers are not touched.
+    ``ensemble_rank_diagnostics`` (True or dict(max_lag=1 .. 255, percentiles=(5, 50, 95)); needs ``ensemble``): did the chains run
+    long enough for the percentiles -- the rank diagnostics of the kept models (``ensembles.rank_diagnostics``) join
+    the summaries: ``ensemble_rhat_rank`` (the larger of the rank-normalised and the folded split R-hat), ``ensemble_ess_bulk`` and
+    ``ensemble_ess_tail`` (the independent samples behind the lowest and the highest percentile) [S, n_depth], the same three with
+    ``_k`` and ``_misfit`` [S] and ``ensemble_ess_bulk_min`` [S]; ``replicates`` = C as for the diagnostics.  The containers are not
+    touched.
     ``ensemble_correlation`` (True or dict(band=64, threshold=0.5, keep_band=False); needs ``ensemble``): the vertical resolution -- the
     posterior correlation between depth cells of the kept models (``ensembles.correlation``) up to ``band`` cells apart:
     ``ensemble_resolution_length`` f64 (metres: the thickness of the run of cells whose correlation with the cell stays >= threshold),
@@ -573,6 +579,7 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
     ens_diag = survey_run.ensemble_diagnostics_argument(ensemble_diagnostics, ensemble)
     ens_corr = survey_run.ensemble_correlation_argument(ensemble_correlation, ensemble)
     ens_fam = survey_run.ensemble_families_argument(ensemble_families, ensemble)
+    ens_rank = survey_run.ensemble_rank_diagnostics_argument(ensemble_rank_diagnostics, ensemble)
     o = read_options(options, **overrides) if isinstance(options, str) else dict(options)
     tempest, time_domain, C_rep = survey_run.check_request(o, hitmap, replicates)
     # read
@@ -615,7 +622,8 @@ def infer(options, output=None, seed=None, device=None, hitmap=True, burn_in_min
                                time_domain=time_domain, hitmap=hitmap, exact_jacobian=exact_jacobian, check_every=check_every,
                                results_directory=results_directory, container=container,
                                own_containers=containers and (world == 1 or schedule == "lines"), unit_z=unit_z, clock=clock,
-                               ensemble_diagnostics=ens_diag, ensemble_correlation=ens_corr, ensemble_families=ens_fam)
+                               ensemble_diagnostics=ens_diag, ensemble_correlation=ens_corr, ensemble_families=ens_fam,
+                               ensemble_rank_diagnostics=ens_rank)
     filler = survey_run.ContainerFiller(lambda dc, idx: run.payload(dc, idx, sparse=True),
                                         lambda dc: _LineWriter(results_directory, ds, o, dc, hitmap, container), clock)
     # the blocks, one after the other; a block's rows leave for the containers while the next block's chains run

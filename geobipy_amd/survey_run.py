@@ -130,6 +130,17 @@ def ensemble_diagnostics_argument(ensemble_diagnostics, ensemble):
     return dict(max_lag=check_max_lag(given.get("max_lag")))
 
 
+def ensemble_rank_diagnostics_argument(ensemble_rank_diagnostics, ensemble):
+    """infer's ``ensemble_rank_diagnostics`` (False / None: off; True; dict(max_lag=, percentiles=)) as None or dict(max_lag=int in
+    1 .. 255, percentiles=ascending floats in [0, 100]).  Refuses the rank diagnostics without an ensemble.  Touches no device."""
+    given = _ensemble_product_argument("ensemble_rank_diagnostics", ("max_lag", "percentiles"), ensemble_rank_diagnostics, ensemble,
+                                       "the ranks are those of the kept models")
+    if given is None:
+        return None
+    from .ensembles import check_max_lag, check_percentiles
+    return dict(max_lag=check_max_lag(given.get("max_lag")), percentiles=check_percentiles(given.get("percentiles", (5, 50, 95))))
+
+
 def ensemble_correlation_argument(ensemble_correlation, ensemble):
     """infer's ``ensemble_correlation`` (False / None: off; True; dict(band=, threshold=, keep_band=)) as None or dict(band=int >= 0,
     threshold=float in (0, 1), keep_band=bool).  Refuses the correlation without an ensemble.  Touches no device."""
@@ -333,6 +344,7 @@ class SurveyRun:
     ensemble_diagnostics: object = None     # None, or dict(max_lag): the chain diagnostics of the ensemble join the summaries
     ensemble_correlation: object = None     # None, or dict(band, threshold, keep_band): the resolution length (and the band) join them
     ensemble_families: object = None        # None, or dict(max_families, max_models, measure, min_silhouette): the model families join them
+    ensemble_rank_diagnostics: object = None    # None, or dict(max_lag, percentiles): the rank diagnostics of the ensemble join them
 
     def run_block(self, idx, offset=None, key_by_row=True):
         """Chains of the soundings ``idx`` (rows of ds, ascending) to completion -> (sampler, its ``summaries``).  ``key_by_row``:
@@ -416,6 +428,12 @@ class SurveyRun:
                     d = ensembles.diagnostics(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
                                               max_lag=self.ensemble_diagnostics["max_lag"])
                     named += [E("ensemble_" + k_, d[k_]) for k_ in ("ess", "rhat", "tau_iterations", "mcse", "ess_k", "ess_misfit", "rhat_k", "rhat_misfit", "ess_min")]
+                if self.ensemble_rank_diagnostics is not None:
+                    er = self.ensemble_rank_diagnostics
+                    d = ensembles.rank_diagnostics(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,
+                                                   max_lag=er["max_lag"], percentiles=er["percentiles"])
+                    named += [E("ensemble_" + k_ + s_, d[k_ + s_]) for s_ in ("", "_k", "_misfit") for k_ in ("rhat_rank", "ess_bulk", "ess_tail")]
+                    named += [E("ensemble_ess_bulk_min", d["ess_bulk_min"])]
                 if self.ensemble_correlation is not None:
                     ec = self.ensemble_correlation
                     d = ensembles.correlation(ens, np.arange(int(dc.n_depth_bins) + 1) * float(dc.depth_bin_width), chains=self.C_rep,

@@ -754,6 +754,31 @@ gbp_status gbp_series_diagnostics(int B, int n_rows, int V, const double *x, int
 gbp_status gbp_ensemble_diagnostics(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
                                     int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
                                     const int32_t *seg_n, int max_lag, double *stats, int32_t *pairs, double *rho, void *stream);
+/* Ranks within the columns of such series (csrc/gbp_ensemble_ranks.h; the host statement of the rule is
+ * geobipy_amd/ensembles.py rank_counts_reference): what rank-normalised R-hat, bulk / tail ESS, exact sample quantiles and Spearman's
+ * correlation are made of.  Per sounding b the used rows are r_j = seg_start[b, m] + t, j = m N + t, of its M = seg_m[b] segments of
+ * N = seg_n[b] rows (the lists of the diagnostics), n = M N of them; per variable v the column c_j = x[r_j, v]:
+ *   order[b, i, 0, v] = s[lo_i], order[b, i, 1, v] = s[min(lo_i + 1, n - 1)], s = c sorted ascending, lo_i = floor((n - 1) p[i]) (one
+ *   fp64 product) -- taken before any folding;
+ *   fold != 0: med = 0.5 (s[(n - 1) / 2] + s[n / 2]), c_j <- |c_j - med| (a folded value may be +inf: it ranks as the largest);
+ *   less[b, r_j, v] = #{i : c_i < c_j}, leq[b, r_j, v] = #{i : c_i <= c_j}: values compare as doubles (-0.0 equals +0.0), so
+ *   0 <= less < leq <= n, and (less + leq + 1) / 2 is the midrank.
+ * less, leq int32 [B, n_rows, V] (a pair), order f64 [B, n_p, 2, V], x_out f64 [B, n_rows, V]: the values that were ranked, before
+ * folding, at the used rows (gbp_ensemble_ranks: log10 of the stored conductivity of the layer that holds z[v], the value
+ * gbp_ensemble_diagnostics sees), NaN elsewhere; each of the three may be NULL and is then skipped.  A row in no segment: less = leq
+ * = -1.  M = 0, N < 4 or M N > n_rows (overlapping segments): less = leq = -1 everywhere, order NaN.  A variable with a non-finite used
+ * value: less = leq = -1 at the used rows, its order NaN.  p: HOST array of n_p probabilities.
+ * 0 <= n_p <= 16, every p finite in [0, 1], n_rows and n_slots <= 16 384 (a padded column of doubles lives in LDS), 1 <= M_max <= 16,
+ * 1 <= K <= 64, at most 2^32 - 1 threads; GBP_ERR_INVALID_ARG for these and NULL pointers, every check before any launch, the entry
+ * named in gbp_last_error; B == 0 launches nothing.  A segment that leaves the rows is the caller's error: its rows are clamped.  No
+ * atomics, every output has one writer: a call repeats its own bits. */
+gbp_status gbp_series_ranks(int B, int n_rows, int V, const double *x, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                            const int32_t *seg_n, int fold, int n_p, const double *p, int32_t *less, int32_t *leq, double *order,
+                            double *x_out, void *stream);
+gbp_status gbp_ensemble_ranks(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                              int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
+                              const int32_t *seg_n, int fold, int n_p, const double *p, int32_t *less, int32_t *leq, double *order,
+                              double *x_out, void *stream);
 /* Correlation between the variables of such series (csrc/gbp_ensemble_corr.h): what moves together.  Per sounding b
  * the used rows are those of its M = seg_m[b] segments of N = seg_n[b] rows (the lists of the diagnostics), n = M N of them:
  * mu_v = (1/n) sum_t x_tv; d_tv = x_tv - mu_v; C(u, v) = (1/(n - 1)) sum_t d_tu d_tv (the pooled sample covariance); sd_v = sqrt(C(v, v));
