@@ -157,6 +157,8 @@ SIGNATURES = {
     "gbp_ensemble_distance": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                       c_int, c_void_p, c_void_p]),
     "gbp_distance_families": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_void_p]),
+    "gbp_ensemble_cross_distance": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double,
+                                            ctypes.c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gbp_hitmap_pool": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double] + [c_void_p] * 5 + [c_void_p]),
     "gbp_hitmap_mixture": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
     "gbp_hitmap_mixture_i64": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, ctypes.c_double] + [c_void_p] * 6
@@ -174,6 +176,7 @@ SIGNATURES = {
                                        c_void_p]),
     "gbp_horizon_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                   ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
+    "gbp_section_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 10 + [c_void_p]),
     "gbp_debug_math": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_bench_time_forward_loglike": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p, c_int,
                                                                                         ctypes.POINTER(ctypes.c_float)]),

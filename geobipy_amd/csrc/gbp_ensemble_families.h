@@ -8,6 +8,11 @@
 //                             different bank pairs -- and each thread merges one pair with two pointers: O(k_i + k_j), no depth axis.
 //                             The thread writes its value to (u, v) and (v, u): symmetric bit for bit.  The diagonal of a present
 //                             model is written as 0.0; an absent model (row outside the slots, k <= 0) gives NaN.  LOG: mu = ln(q / p), as log1p((q - p) / p).
+//   k_layered_cross_distance<LOG>  the same distance (layered_pair: one merge for both kernels, the same bits) between the models of a
+//                             sounding and those of its partner sounding (gbp_ensemble_cross_distance).  The same
+//                             staging -- rows 0 .. 15 the sounding's models, 16 .. 31 the partner's -- over all nt x nt tiles: nothing is
+//                             symmetric, there is no diagonal, and identical models are 0.0 apart by arithmetic.  A partner outside
+//                             0 .. S - 1 gives a slab of NaN.  The kernel writes every entry.
 //   k_distance_families       k-medoids on a distance matrix, every stage q = 1 .. q_max of a sounding in one launch by one workgroup of
 //                             256 threads.  Thread t owns columns t, t + 256, ...: it walks j upward over row j's entry of its own
 //                             column (a wave reads 64 consecutive doubles) and its sum keeps the rule's order.  Labels and nearest
@@ -39,6 +44,31 @@ struct DistanceArgs {
     int log10, squared, ntp;          // tile pairs per sounding: nt (nt + 1) / 2
     double* dist;                     // [B, n, n]
 };
+
+// The distance of two staged models (rows of 2 K + 1 doubles: K edges, K values) with ki, kj >= 1 layers: the merge of the header's
+// rule, one order of the sum.  Both kernels call it, so a pair of models gives the same bits through either entry.
+template <bool LOG>
+__device__ __forceinline__ double layered_pair(const double* ei, const double* ej, int ki, int kj, int K, double z0, double z1, double inv_mu,
+                                               int squared)
+{
+    const double *ai = ei + K, *aj = ej + K;
+    int li = 0, lj = 0;
+    for (int l = 0; l < ki - 1; ++l) li += ei[l] <= z0 ? 1 : 0;
+    for (int l = 0; l < kj - 1; ++l) lj += ej[l] <= z0 ? 1 : 0;
+    double p = z0, acc = 0.0;
+    for (int step = 0; step < 2 * K + 2 && p < z1; ++step) {           // (at most k_i + k_j - 1 segments: the cap only guards malformed edges)
+        const double ni = li < ki - 1 ? ei[li] : (double)INFINITY, nj = lj < kj - 1 ? ej[lj] : (double)INFINITY;
+        const double q = fmin(fmin(ni, nj), z1);
+        const double d = ai[li] - aj[lj];
+        const double mu = LOG ? log1p((q - p) / p) : q - p;              // (ln(q / p), to a few U relative however thin the segment)
+        acc += mu * (d * d);
+        li += ni == q ? 1 : 0;
+        lj += nj == q ? 1 : 0;
+        p = q;
+    }
+    const double d2 = acc * inv_mu;
+    return squared ? d2 : sqrt(d2);
+}
 
 template <bool LOG>
 __global__ __launch_bounds__(FAM_THREADS) void k_layered_distance(DistanceArgs a)
@@ -77,30 +107,64 @@ __global__ __launch_bounds__(FAM_THREADS) void k_layered_distance(DistanceArgs a
     double value;
     if (ki == 0 || kj == 0) value = qnan;
     else if (u == v) value = 0.0;
-    else {
-        const double* const ei = fam_lds + i * S;
-        const double* const ej = fam_lds + (FAM_TILE + j) * S;
-        const double *ai = ei + K, *aj = ej + K;
-        const double z0 = a.z0, z1 = a.z1;
-        int li = 0, lj = 0;
-        for (int l = 0; l < ki - 1; ++l) li += ei[l] <= z0 ? 1 : 0;
-        for (int l = 0; l < kj - 1; ++l) lj += ej[l] <= z0 ? 1 : 0;
-        double p = z0, acc = 0.0;
-        for (int step = 0; step < 2 * K + 2 && p < z1; ++step) {       // (at most k_i + k_j - 1 segments: the cap only guards malformed edges)
-            const double ni = li < ki - 1 ? ei[li] : (double)INFINITY, nj = lj < kj - 1 ? ej[lj] : (double)INFINITY;
-            const double q = fmin(fmin(ni, nj), z1);
-            const double d = ai[li] - aj[lj];
-            const double mu = LOG ? log1p((q - p) / p) : q - p;          // (ln(q / p), to a few U relative however thin the segment)
-            acc += mu * (d * d);
-            li += ni == q ? 1 : 0;
-            lj += nj == q ? 1 : 0;
-            p = q;
-        }
-        const double d2 = acc * a.inv_mu;
-        value = a.squared ? d2 : sqrt(d2);
-    }
+    else value = layered_pair<LOG>(fam_lds + i * S, fam_lds + (FAM_TILE + j) * S, ki, kj, K, a.z0, a.z1, a.inv_mu, a.squared);
     out[(size_t)u * n + v] = value;
     if (u != v) out[(size_t)v * n + u] = value;
+}
+
+struct CrossDistanceArgs {
+    int S, n_slots, K, n;
+    const int* ens_k;
+    const double* ens_edges;
+    const double* ens_sigma;
+    const int* rows;                  // [S, n]
+    const int* partner;               // [S]
+    double z0, z1, inv_mu;
+    int log10, squared, nt2;          // tiles per sounding: nt * nt
+    double* dist;                     // [S, n, n]
+};
+
+template <bool LOG>
+__global__ __launch_bounds__(FAM_THREADS) void k_layered_cross_distance(CrossDistanceArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double fam_lds[];
+    __shared__ int sk[2 * FAM_TILE];
+    const int t = threadIdx.x, K = a.K, n = a.n, S = family_stride(K);
+    const int nt = (n + FAM_TILE - 1) / FAM_TILE;
+    const size_t b = blockIdx.x / (unsigned)a.nt2;
+    const int rem = (int)(blockIdx.x % (unsigned)a.nt2), tr = rem / nt, tc = rem - tr * nt;
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const int i = t >> 4, j = t & (FAM_TILE - 1);
+    const int u = tr * FAM_TILE + i, v = tc * FAM_TILE + j;
+    double* const out = a.dist + b * (size_t)n * n;
+    const int pb = a.partner[b];
+    if (pb < 0 || pb >= a.S) {                                         // (the same for the whole workgroup: nobody waits at the barrier)
+        if (u < n && v < n) out[(size_t)u * n + v] = qnan;
+        return;
+    }
+
+    // ---- stage: model m < 16 is tr * 16 + m of sounding b, model m >= 16 is tc * 16 + m - 16 of its partner
+    for (int idx = t; idx < 2 * FAM_TILE * K; idx += FAM_THREADS) {
+        const int m = idx / K, l = idx - m * K;
+        const int w = (m < FAM_TILE ? tr : tc) * FAM_TILE + (m & (FAM_TILE - 1));
+        const size_t sb = m < FAM_TILE ? b : (size_t)pb;
+        const int r = a.rows[sb * n + min(w, n - 1)];
+        const bool present = w < n && r >= 0 && r < a.n_slots;
+        const size_t src = sb * a.n_slots + (size_t)min(max(r, 0), a.n_slots - 1);     // (clamped before any load)
+        const int k = present ? min(max(a.ens_k[src], 0), K) : 0;
+        if (l == 0) sk[m] = k;
+        double* const row = fam_lds + m * S;
+        row[l] = l < k - 1 ? a.ens_edges[src * K + l] : (double)INFINITY;
+        const double s = l < k ? a.ens_sigma[src * K + l] : qnan;
+        row[K + l] = l < k && a.log10 ? log10(s) : s;
+    }
+    __syncthreads();
+
+    if (u >= n || v >= n) return;
+    const int ki = sk[i], kj = sk[FAM_TILE + j];
+    double value = qnan;
+    if (ki != 0 && kj != 0) value = layered_pair<LOG>(fam_lds + i * S, fam_lds + (FAM_TILE + j) * S, ki, kj, K, a.z0, a.z1, a.inv_mu, a.squared);
+    out[(size_t)u * n + v] = value;
 }
 
 struct FamilyArgs {

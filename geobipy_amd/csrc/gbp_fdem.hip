@@ -2041,6 +2041,35 @@ extern "C" gbp_status gbp_ensemble_distance(int B, int n_slots, int K, const int
     return GBP_OK;
 }
 
+// ... the same distance between the models of a sounding and those of its partner sounding: all nt x nt tiles ...
+extern "C" gbp_status gbp_ensemble_cross_distance(int S, int n_slots, int K, const int32_t* ens_k, const double* ens_edges,
+                                                  const double* ens_sigma, int n, const int32_t* rows, const int32_t* partner, double z0,
+                                                  double z1, int measure, int log10, int squared, double* dist, void* stream)
+{
+    using namespace ensemble;
+    if (S < 0 || n_slots < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: negative or zero size%s");
+    if (n < 1 || n > 4096) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: n outside 1 .. 4096%s");
+    if (K < 1 || K > 64) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: K outside 1 .. 64%s");
+    if (!std::isfinite(z0) || !std::isfinite(z1) || z0 < 0.0 || z1 <= z0)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: the window needs finite bounds with 0 <= z0 < z1%s");
+    if (measure != 0 && measure != 1) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: measure must be 0 (linear) or 1 (log)%s");
+    if (measure == 1 && z0 == 0.0) return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: the log measure needs z0 > 0%s");
+    const int nt = (n + FAM_TILE - 1) / FAM_TILE, nt2 = nt * nt;
+    if ((int64_t)S * nt2 * FAM_THREADS > 0xffffffffLL)             // (a dispatch counts its work-items in 32 bits)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: S * tiles out of range (more than 2^32 - 1 threads)%s");
+    if (S == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!ens_k || !ens_edges || !ens_sigma || !rows || !partner || !dist)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_ensemble_cross_distance: NULL pointer%s");
+    const double mu = measure == 1 ? std::log1p((z1 - z0) / z0) : z1 - z0;      // (as gbp_ensemble_distance takes it)
+    const CrossDistanceArgs a = {S, n_slots, K, n, ens_k, ens_edges, ens_sigma, rows, partner, z0, z1, 1.0 / mu, log10 ? 1 : 0, squared ? 1 : 0,
+                                 nt2, dist};
+    const dim3 grid((unsigned)((int64_t)S * nt2));
+    if (measure == 1) hipLaunchKernelGGL(k_layered_cross_distance<true>, grid, dim3(FAM_THREADS), distance_lds_bytes(K), (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_layered_cross_distance<false>, grid, dim3(FAM_THREADS), distance_lds_bytes(K), (hipStream_t)stream, a);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
 // ... and k-medoids on the distances, every stage of a sounding in one launch: one workgroup per sounding.
 extern "C" gbp_status gbp_distance_families(int B, int n, const double* dist, const int32_t* n_used, int q_max, int max_iter, int32_t* medoid,
                                             int32_t* label, double* nearest, double* second, int32_t* iterations, uint8_t* converged,
@@ -2382,4 +2411,56 @@ extern "C" gbp_status gbp_horizon_track(int L, const int64_t* ptr, int64_t total
                                                            log_partition, scale, st);
     }
 #undef GBP_HORIZON_CASE
+}
+
+#include "gbp_section.h"
+
+// Sections of sampled models (gbp_section.h): one workgroup per sequence walks the chain over the kept models; the Viterbi launch
+// always, the forward-backward launch only when the marginals are asked for.  Every refusal comes before any launch; ptr is not read
+// on the host.
+namespace {
+
+template <int NJ>
+gbp_status section_launch(int L, const int64_t* ptr, int n, const int32_t* n_used, const double* score, const double* g, const double* d2,
+                          uint16_t* back, int32_t* state, double* log_score, double* marginal, double* log_partition, double* scale,
+                          hipStream_t st)
+{
+    const size_t lds = section::lds_bytes(n);
+    const int W = n <= 64 ? 64 : n <= 128 ? 128 : section::THREADS;        // lanes that own a state; the other lane groups share the i range
+    hipLaunchKernelGGL(section::k_section_viterbi<NJ>, dim3((unsigned)L), dim3(section::THREADS), lds, st, (const long long*)ptr, n, W,
+                       (const int*)n_used, score, g, d2, (unsigned short*)back, (int*)state, log_score);
+    GBP_HIP(hipGetLastError());
+    if (marginal) {
+        hipLaunchKernelGGL(section::k_section_marginals<NJ>, dim3((unsigned)L), dim3(section::THREADS), lds, st, (const long long*)ptr, n,
+                           (const int*)n_used, score, g, d2, marginal, log_partition, scale);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" gbp_status gbp_section_track(int L, const int64_t* ptr, int64_t total_n, int n, const int32_t* n_used, const double* score,
+                                        const double* g, const double* d2, uint16_t* back, int32_t* state, double* log_score,
+                                        double* marginal, double* log_partition, double* scale, void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: L must be >= 0%s");
+    if (n < 1 || n > section::MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: n must lie in 1 .. 1024%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < L) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: total_n does not fit L sequences of at least one sounding%s");
+    if (total_n > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: total_n * n * n out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: ptr is NULL%s");
+    if (!n_used || !score || !g || !d2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: NULL pointer (n_used, score, g, d2)%s");
+    if (!back) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: the back workspace is NULL%s");
+    if (!state || !log_score) return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: NULL pointer (state, log_score)%s");
+    if ((marginal != nullptr) != (log_partition != nullptr) || (marginal != nullptr) != (scale != nullptr))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_track: marginal, log_partition and scale go together (all, or all NULL)%s");
+    hipStream_t st = (hipStream_t)stream;
+    switch ((n + section::THREADS - 1) / section::THREADS) {
+        case 1: return section_launch<1>(L, ptr, n, n_used, score, g, d2, back, state, log_score, marginal, log_partition, scale, st);
+        case 2: return section_launch<2>(L, ptr, n, n_used, score, g, d2, back, state, log_score, marginal, log_partition, scale, st);
+        case 3: return section_launch<3>(L, ptr, n, n_used, score, g, d2, back, state, log_score, marginal, log_partition, scale, st);
+        default: return section_launch<section::MAX_OWNED>(L, ptr, n, n_used, score, g, d2, back, state, log_score, marginal, log_partition,
+                                                           scale, st);
+    }
 }

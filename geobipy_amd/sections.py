@@ -1,0 +1,545 @@
+"""Laterally coherent sections of sampled models along flight lines (csrc/gbp_ensemble_families.h
+k_layered_cross_distance, csrc/gbp_section.h k_section_viterbi / k_section_marginals).
+
+``families`` hands on one kept model per sounding; where a posterior has two families of comparable share that pick jumps between them
+from one sounding to the next, and nothing per sounding can say which branch continues along the line.  Here one kept model per
+sounding is chosen JOINTLY along a line: the states of a Markov chain under sounding s are its kept models (``families.used_rows``),
+and the step s -> s + 1 from model i to model j costs g[s] D^2(i, j), D the RMS difference in decades of the two layered models over
+the depth window (the distance of ``families.distance``, between the models of two different soundings).
+
+``partners``        which sounding each sounding is paired with: the next of its sequence, -1 at a sequence's end and around soundings
+                    without models.
+``cross_distance``  D^2 (or D) f64 [S, n, n] between the models of every sounding and those of its partner, one kernel
+                    (gbp_ensemble_cross_distance; ``cross_distance_reference`` states the rule through ``families.distance_reference``).
+``steps``           g[s] = length / (2 tau^2 max(dx_s, min_distance)): the RMS difference between neighbouring models is taken as a
+                    random walk of standard deviation ``tau`` decades per ``length`` metres, so that -g D^2 is its Gaussian log
+                    density.  ``tau`` = 0.1 per 100 m and the 1 m floor are a documented convention, not fitted numbers.
+``track``           the most probable path (Viterbi) and the smoothed marginals (forward-backward) of that chain (gbp_section_track;
+                    ``track_reference`` states the rule in numpy: the device is held to it with ``==`` for the path and its score and to
+                    the rule's own rounding for the marginals).
+``sections``        all of the above for an ensemble, and the chosen models: a section made of models the sampler visited, as continuous
+                    along the line as the posteriors allow, with the weight every sounding's models get from their neighbours.
+``from_survey``     the same for a ``survey.SurveyResult`` (or its saved file) that carries the ensemble; sequences are the flight lines.
+
+The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L + 1]; m_r = n_used[r] in 1 .. n.
+  Viterbi: V_0[j] = score[r0, j] for j < m_0.  Per step r -> r + 1 and per j < m_{r+1}: best = -inf, arg = 0; for i = 0 .. m_r - 1
+  ascending cand = V[i] - g[r] * d2[r, i, j], replaced on strict cand > best (a NaN candidate never wins); V'[j] = score[r + 1, j] +
+  best, back[r + 1, j] = arg.  The path ends at the first maximum of V over j < m_last (``log_score``) and is walked back.
+  Marginals (scaled forward-backward): w = exp(score); alpha_0 = w_0 / s_0; u[j] = sum_i alpha[i] exp(-(g[r] d2[r, i, j])), i
+  ascending; u <- w_{r+1} u; s_{r+1} = sum u; alpha' = u / s_{r+1}; beta_last = 1, beta_r[i] = sum_j exp(-(g[r] d2[r, i, j])) w_{r+1}[j]
+  beta_{r+1}[j] / s_{r+1}; gamma = alpha beta normalised per sounding, 0 for the states >= m_r; log_partition = sum ln s.
+Nothing outside the prefixes i < m_r, j < m_{r+1} of d2 is read, nor the entry of a sequence's last sounding.
+
+``python -m geobipy_amd.sections <survey.npz> --depth Z1 [--from Z0] [--measure log] [--tau T] [--length L] [--max-models n]
+[--chains C] [--no-marginals]`` writes ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``, ``track`` and ``sections``
+refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
+after the run, like ``horizons.from_products``.  Left out on purpose: coupling across lines, carrying a sequence across launches,
+weighted re-binning of the hit maps by ``weight``, and learning ``tau`` (``log_partition`` is returned for whoever wants to scan it).
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .ensembles import Ensemble, check_chains
+from .families import MAX_K, MAX_MODELS, _check_block, _check_int, _stream, check_window, distance_reference, used_rows
+
+MAX_STATES = 1024
+OUTPUT_SUFFIX = ".sections.npz"
+
+
+def check_ptr(ptr, total):
+    """``ptr`` as int64 numpy [L + 1]: starts at 0, ends at ``total``, every sequence holds at least one sounding."""
+    p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr)
+    if p.ndim != 1 or p.size < 1 or p.dtype.kind not in "iu":
+        raise ValueError("sections: ptr must be a vector of L + 1 integers")
+    p = p.astype(np.int64)
+    if p[0] != 0 or p[-1] != total or np.any(np.diff(p) < 1):
+        raise ValueError("sections: ptr must start at 0, end at the number of soundings (%d) and give every sequence at least one" % total)
+    return p
+
+
+def _default_ptr(ptr, total):
+    """``ptr`` checked; None: one sequence of all the soundings (no sequence when there are none)."""
+    if ptr is None:
+        return np.array([0, total] if total else [0], dtype=np.int64)
+    return check_ptr(ptr, total)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def _check_number(v, what, positive=True):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or (positive and not v > 0):
+        raise ValueError("sections: %s must be a %s number" % (what, "positive finite" if positive else "finite"))
+    return float(v)
+
+
+# ---- which soundings follow which ---------------------------------------------------------------------------------------------------
+
+def partners(ptr, n_used):
+    """int32 [S] (numpy): the sounding that sounding s is paired with -- s + 1 within a sequence of ``ptr`` [L + 1] (None: one sequence),
+    -1 at a sequence's end.  Sequences are cut at soundings with ``n_used`` == 0: such a sounding, and the one before it, get -1."""
+    nu = _host(n_used).reshape(-1)
+    S = nu.size
+    p = _default_ptr(ptr, S)
+    out = np.arange(1, S + 1, dtype=np.int32)
+    out[p[1:] - 1] = -1
+    empty = nu <= 0
+    out[empty] = -1
+    out[:-1][empty[1:]] = -1
+    return out
+
+
+def pieces(ptr, n_used):
+    """The chains of a launch: (keep int64 [T], piece_ptr int64 [P + 1], owner int64 [P]) -- the soundings with models in their order,
+    the runs of them that ``partners`` connects as sequences over ``keep``, and the sequence of ``ptr`` every run belongs to."""
+    nu = _host(n_used).reshape(-1)
+    p = _default_ptr(ptr, nu.size)
+    partner = partners(p, nu)
+    keep = np.flatnonzero(nu > 0).astype(np.int64)
+    ends = np.flatnonzero(partner[keep] < 0)
+    piece_ptr = np.concatenate([[0], ends + 1]).astype(np.int64)
+    owner = (np.searchsorted(p, keep[piece_ptr[:-1]], side="right") - 1).astype(np.int64)
+    return keep, piece_ptr, owner
+
+
+# ---- the rules ----------------------------------------------------------------------------------------------------------------------
+
+def cross_distance_reference(k, edges, sigma, rows, partner, z0, z1, measure="linear", dtype=np.float64, stored=False, squared=True):
+    """The rule of ``cross_distance`` in numpy: ``k`` [S, n_slots], ``edges`` / ``sigma`` [S, n_slots, K], ``rows`` [S, n], ``partner``
+    [S].  Returns D^2 (``squared``) or D [S, n, n] in ``dtype``: the slots of sounding s and of its partner are stacked into one
+    sounding of 2 n_slots slots and the block [:n, n:] of ``families.distance_reference`` on the 2 n models is taken -- the same rule by
+    construction.  A row outside the slots or an empty slot gives NaN in its row or column; a partner outside 0 .. S - 1 a slab of NaN."""
+    k, edges, sigma, rows, partner = np.asarray(k), np.asarray(edges), np.asarray(sigma), np.asarray(rows), np.asarray(partner).reshape(-1)
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or edges.shape[:2] != k.shape or rows.ndim != 2 or rows.shape[0] != k.shape[0] \
+            or partner.size != k.shape[0]:
+        raise ValueError("cross_distance_reference: k [S, n_slots], edges and sigma [S, n_slots, K], rows [S, n], partner [S]")
+    S, ns = k.shape
+    n = rows.shape[1]
+    out = np.full((S, n, n), np.nan, dtype=dtype)
+    inside = lambda r: np.where((r >= 0) & (r < ns), r, -1).astype(np.int64)      # noqa: E731  (a row past the end must not name a partner's slot)
+    for s in range(S):
+        p = int(partner[s])
+        if not 0 <= p < S:
+            continue
+        mine, theirs = inside(rows[s]), inside(rows[p])
+        both = np.concatenate([mine, np.where(theirs >= 0, theirs + ns, -1)])
+        D = distance_reference(np.concatenate([k[s], k[p]]), np.concatenate([edges[s], edges[p]]), np.concatenate([sigma[s], sigma[p]]), both, z0, z1,
+                               measure=measure, dtype=dtype, stored=stored, squared=squared)
+        out[s] = D[:n, n:]
+    return out
+
+
+def steps(x, y, tau=0.1, length=100.0, min_distance=1.0, ptr=None):
+    """g float64 [S] (numpy) of the steps s -> s + 1 of soundings at ``x``, ``y`` (m): g[s] = length / (2 tau^2 max(dx_s, min_distance))
+    with dx_s the horizontal distance.  The RMS difference in decades between neighbouring models is taken as a random walk of standard
+    deviation ``tau`` per ``length`` metres: over dx its variance is tau^2 dx / length, and -g D^2 is the Gaussian log density of a
+    difference D.  ``tau`` = 0.1 decades per 100 m and the floor of 1 m are a documented convention, not fitted numbers;
+    on the planted line of the tests the path is the same for every tau in 0.05 .. 0.4.  The entry of a sequence's last sounding (of
+    ``ptr``; default one sequence) is unused and holds length / (2 tau^2 min_distance)."""
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != y.size:
+        raise ValueError("sections.steps: x and y must have one entry per sounding")
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError("sections.steps: x and y must be finite")
+    tau, length, min_distance = _check_number(tau, "tau"), _check_number(length, "length"), _check_number(min_distance, "min_distance")
+    S = x.size
+    dx = np.zeros(S)
+    if S > 1:
+        dx[:-1] = np.hypot(np.diff(x), np.diff(y))
+    if ptr is not None and S > 0:
+        dx[check_ptr(ptr, S)[1:] - 1] = 0.0
+    return length / (2.0 * tau * tau * np.maximum(dx, min_distance))
+
+
+def _check_chain(ptr, score, g, d2, n_used, what):
+    """The host checks ``track`` and ``track_reference`` share; returns ptr (numpy), n_used (numpy int64)."""
+    if d2.ndim != 3 or d2.shape[1] != d2.shape[2] or not 1 <= d2.shape[1] <= MAX_STATES:
+        raise ValueError("%s: d2 [T, n, n] with 1 <= n <= %d" % (what, MAX_STATES))
+    total, n = d2.shape[0], d2.shape[1]
+    ptr = check_ptr(ptr, total)
+    nu = _host(n_used).reshape(-1)
+    if nu.size != total or nu.dtype.kind not in "iu":
+        raise ValueError("%s: n_used must hold one integer per sounding" % what)
+    if np.any(nu < 1) or np.any(nu > n):
+        raise ValueError("%s: n_used must lie in 1 .. n (sequences are cut at soundings without models: sections.pieces)" % what)
+    if np.size(g) != total:
+        raise ValueError("%s: g must hold one entry per sounding" % what)
+    if score is not None and tuple(score.shape) != (total, n):
+        raise ValueError("%s: score must be [T, n]" % what)
+    return ptr, nu.astype(np.int64)
+
+
+def track_reference(ptr, score, g, d2, n_used, marginals=True, dtype=np.float64):
+    """The rule of the module's docstring in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the
+    yardstick of the rule's own rounding).  ``ptr`` [L + 1], ``score`` [T, n] or None (zeros), ``g`` [T], ``d2`` [T, n, n], ``n_used``
+    [T] in 1 .. n.  Returns ``state`` int32 [T], ``log_score`` [L], and with ``marginals`` ``marginal`` [T, n], ``log_partition`` [L] and
+    ``scale`` [T]."""
+    ft = np.dtype(dtype).type
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.track_reference")
+    total, n = d2.shape[0], d2.shape[1]
+    score = (np.zeros((total, n)) if score is None else score).astype(ft)
+    g = np.asarray(g, dtype=np.float64).reshape(-1).astype(ft)
+    L = ptr.size - 1
+    state, log_score = np.zeros(total, dtype=np.int32), np.zeros(L, dtype=ft)
+    out = dict(state=state, log_score=log_score)
+    if marginals:
+        gamma, log_partition, scale = np.zeros((total, n), dtype=ft), np.zeros(L, dtype=ft), np.zeros(total, dtype=ft)
+        out.update(marginal=gamma, log_partition=log_partition, scale=scale)
+    for l in range(L):
+        r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+        m = [int(v) for v in nu[r0:r0 + N]]
+        cost = [g[r0 + s] * d2[r0 + s, :m[s], :m[s + 1]].astype(ft) for s in range(N - 1)]      # one multiply per entry, prefixes only
+        # ---- Viterbi
+        V = score[r0, :m[0]]
+        back = [np.zeros(m[0], dtype=np.int64)]
+        for s in range(N - 1):
+            best, arg = np.full(m[s + 1], -np.inf, dtype=ft), np.zeros(m[s + 1], dtype=np.int64)
+            with np.errstate(invalid="ignore"):
+                for i in range(m[s]):                                        # i ascending
+                    cand = V[i] - cost[s][i]
+                    repl = cand > best                                       # strict: the first maximum stays, a NaN never wins
+                    best, arg = np.where(repl, cand, best), np.where(repl, i, arg)
+            V = score[r0 + s + 1, :m[s + 1]] + best
+            back.append(arg)
+        cur = _first_max(V)
+        log_score[l] = V[cur]
+        for s in range(N - 1, -1, -1):
+            state[r0 + s] = cur
+            cur = int(back[s][cur])
+        if not marginals:
+            continue
+        # ---- scaled forward-backward
+        w = [np.exp(score[r0 + s, :m[s]]) for s in range(N)]
+        E = [np.exp(-c) for c in cost]
+        alpha, sc = [None] * N, np.zeros(N, dtype=ft)
+        sc[0] = w[0].sum()
+        alpha[0] = w[0] / sc[0]
+        for s in range(N - 1):
+            u = np.zeros(m[s + 1], dtype=ft)
+            for i in range(m[s]):                                            # i ascending
+                u = u + alpha[s][i] * E[s][i]
+            u = w[s + 1] * u
+            sc[s + 1] = u.sum()
+            alpha[s + 1] = u / sc[s + 1]
+        beta = np.ones(m[N - 1], dtype=ft)
+        for s in range(N - 1, -1, -1):
+            if s < N - 1:
+                u = w[s + 1] * beta
+                b = np.zeros(m[s], dtype=ft)
+                for j in range(m[s + 1]):                                    # j ascending
+                    b = b + E[s][:, j] * u[j]
+                beta = b / sc[s + 1]
+            gm = alpha[s] * beta
+            gamma[r0 + s, :m[s]] = gm / gm.sum()
+        scale[r0:r0 + N] = sc
+        log_partition[l] = np.cumsum(np.log(sc))[-1]
+    return out
+
+
+def _first_max(v):
+    """The first maximum of a vector with strict > to replace, starting from v[0] (what the device's one lane does)."""
+    cur = 0
+    for j in range(1, v.size):
+        if v[j] > v[cur]:
+            cur = j
+    return cur
+
+
+# ---- the entries --------------------------------------------------------------------------------------------------------------------
+
+def _are_tensors(tensors, what, entry):
+    for a in tensors:
+        if not torch.is_tensor(a):
+            raise _lib.NativeLibraryError("sections.%s takes torch tensors on the device (%s); there is no host fallback" % (what, entry))
+
+
+def _on_device(tensors, what, entry):
+    """The last check of an entry: shapes, dtypes and values are refused first, whatever device the tensors are on."""
+    for a in tensors:
+        if a.device.type != "cuda":
+            raise _lib.NativeLibraryError("sections.%s runs on the device (%s); there is no host fallback" % (what, entry))
+
+
+def cross_distance(ens, rows, partner, z0, z1, measure="linear", squared=True, log10=True, block=None):
+    """D^2 (``squared``; else D) f64 [S, n, n] on the device: entry [s, i, j] is the distance of ``families.distance`` between model
+    ``rows[s, i]`` of sounding s and model ``rows[partner[s], j]`` of sounding ``partner[s]`` (``rows`` int32 [S, n] on the device;
+    ``partner`` int32 [S], what ``partners`` gives: numpy or torch) over the window [z0, z1].  An absent model gives NaN in its row or
+    column, a partner outside 0 .. S - 1 a slab of NaN (``cross_distance_reference`` states the rule).  ``block``: soundings per launch
+    (None: one launch unless it would exceed 2^32 - 1 threads); a block brings the partners outside it along, the bits are the same.
+    One kernel (gbp_ensemble_cross_distance)."""
+    entry = "gbp_ensemble_cross_distance"
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    _are_tensors((k, edges, sigma, rows), "cross_distance", entry)
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
+        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
+    if rows.ndim != 2 or rows.shape[0] != k.shape[0] or not 1 <= rows.shape[1] <= MAX_MODELS:
+        raise ValueError("cross_distance: rows [S, n] with 1 <= n <= %d" % MAX_MODELS)
+    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or rows.dtype != torch.int32:
+        raise TypeError("ensemble: k is int32, edges and sigma are float64; rows is int32")
+    S, ns, K = edges.shape
+    if ns < 1 or not 1 <= K <= MAX_K:
+        raise ValueError("ensemble: at least one slot and K in [1, %d]" % MAX_K)
+    pn = _host(partner)
+    if pn.shape != (S,) or pn.dtype.kind not in "iu":
+        raise ValueError("cross_distance: partner must hold one integer per sounding")
+    z0, z1, log = check_window(z0, z1, measure)
+    _check_block(block, "cross_distance")
+    _on_device((k, edges, sigma, rows), "cross_distance", entry)
+    k, edges, sigma, rows, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), rows.contiguous(), k.device
+    n = rows.shape[1]
+    out = torch.empty((S, n, n), dtype=torch.float64, device=dev)
+    if S == 0:
+        return out
+    tiles = (n + 15) // 16
+    step = (2 ** 32 - 1) // (256 * tiles * tiles) if block is None else int(block)      # soundings one launch takes: 256 threads per tile
+    lib = _lib.load()
+
+    def launch(k_, e_, s_, rows_, partner_, out_):
+        p_ = torch.as_tensor(np.ascontiguousarray(partner_, dtype=np.int32)).to(dev)
+        _lib.check(lib.gbp_ensemble_cross_distance(k_.shape[0], ns, K, k_.data_ptr(), e_.data_ptr(), s_.data_ptr(), n, rows_.data_ptr(), p_.data_ptr(),
+                                                   z0, z1, log, int(bool(log10)), int(bool(squared)), out_.data_ptr(), _stream(dev)))
+
+    with torch.cuda.device(dev):
+        if S <= step:
+            launch(k, edges, sigma, rows, pn, out)
+            return out
+        for b0 in range(0, S, step):
+            b1 = min(S, b0 + step)
+            p = pn[b0:b1].astype(np.int64)
+            valid = (p >= 0) & (p < S)
+            extra = np.unique(p[valid & ((p < b0) | (p >= b1))])                  # the partners outside the block come along, unpaired
+            local = np.where(valid, np.where((p >= b0) & (p < b1), p - b0, (b1 - b0) + np.searchsorted(extra, p)), -1)
+            idx = torch.as_tensor(np.concatenate([np.arange(b0, b1), extra])).to(dev)
+            part = torch.empty((idx.numel(), n, n), dtype=torch.float64, device=dev)
+            launch(k[idx], edges[idx], sigma[idx], rows[idx], np.concatenate([local, np.full(extra.size, -1)]), part)
+            out[b0:b1] = part[:b1 - b0]
+    return out
+
+
+def track(d2, g, ptr, n_used, score=None, marginals=True):
+    """The most probable path and the smoothed marginals of the chain of the module's docstring (gbp_section_track): ``d2`` f64
+    [T, n, n] on the device (what ``cross_distance`` gives for soundings in sequence order), ``g`` [T] (``steps``; host or device),
+    ``ptr`` [L + 1] (host), ``n_used`` [T] in 1 .. n (host or device), ``score`` f64 [T, n] on the device or None: zeros -- the kept
+    models are equally weighted samples.  Returns on the device ``state`` int32 [T], ``log_score`` [L], and with ``marginals``
+    ``marginal`` [T, n], ``log_partition`` [L] and ``scale`` [T]."""
+    entry = "gbp_section_track"
+    _are_tensors((d2,) + (() if score is None else (score,)), "track", entry)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.track")
+    if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
+        raise TypeError("sections.track: d2 and score are float64")
+    _on_device((d2,) + (() if score is None else (score,)), "track", entry)
+    dev = d2.device
+    total, n = d2.shape[0], d2.shape[1]
+    L = ptr.size - 1
+    f64 = dict(dtype=torch.float64, device=dev)
+    d2 = d2.contiguous()
+    score = torch.zeros((total, n), **f64) if score is None else score.contiguous()
+    t_ptr = torch.as_tensor(ptr, dtype=torch.int64).to(dev)
+    t_g = torch.as_tensor(_host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_nu = torch.as_tensor(nu.astype(np.int32)).to(dev)
+    back = torch.empty((total, n), dtype=torch.int16, device=dev)
+    out = dict(state=torch.empty(total, dtype=torch.int32, device=dev), log_score=torch.empty(L, **f64))
+    if marginals:
+        out.update(marginal=torch.empty((total, n), **f64), log_partition=torch.empty(L, **f64), scale=torch.empty(total, **f64))
+    p = lambda t: None if t is None else t.data_ptr()                         # noqa: E731
+    if L > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gbp_section_track(L, p(t_ptr), total, n, p(t_nu), p(score), p(t_g), p(d2), p(back), p(out["state"]),
+                                                     p(out["log_score"]), p(out.get("marginal")), p(out.get("log_partition")),
+                                                     p(out.get("scale")), _stream(dev)))
+    return out
+
+
+def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=128, tau=0.1, length=100.0, min_distance=1.0, score=None,
+             marginals=True, budget_bytes=4 << 30):
+    """One kept model per sounding, chosen jointly along every sequence of ``ptr`` [L + 1] (None: one sequence) for the ensemble
+    ``ens`` of soundings at ``x``, ``y`` [S] (host; m) over the depth window [z0, z1]: ``families.used_rows`` (``chains``,
+    ``max_models`` <= 1024), ``cross_distance`` (squared), ``steps`` (``tau``, ``length``, ``min_distance``), ``track`` and a gather.
+    ``score`` f64 [S, n] on the device: a log weight per used model (None: equal weights).  Sequences are cut at soundings without
+    models.  Whole sequences are grouped into launches whose d2 stays under ``budget_bytes``; a single sequence that does not fit is
+    refused (lower ``max_models`` or raise ``budget_bytes``): no state is carried between pieces.
+
+    Returns, on the device: ``state`` int32 [S] (the position in ``rows``; -1: no models), ``slot`` int32 [S] (the ensemble slot; -1),
+    ``rows`` int32 [S, n], ``n_used`` int32 [S], ``section_k`` int32 [S] (0: none), ``section_edges`` / ``section_sigma`` f64 [S, K]
+    (bit copies of the chosen slots; NaN: none), ``step_distance`` f64 [S] (D in decades between the chosen models of s and s + 1; NaN at
+    the end of a run), ``log_score`` f64 [L] (the sum over the sequence's runs; 0 for a sequence without models); with ``marginals``
+    ``weight`` f64 [S, n] (the smoothed marginal of every used model; NaN: no models), ``chosen_weight`` [S], ``n_effective`` [S] =
+    1 / sum w^2 (between 1 and n_used: how strongly the neighbours re-weight the sounding's samples) and ``log_partition`` [L]."""
+    z0, z1, _ = check_window(z0, z1, measure)
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    _are_tensors((k, edges, sigma), "sections", "gbp_ensemble_cross_distance")
+    if k.ndim != 2 or edges.ndim != 3:
+        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
+    C = check_chains(chains, k.shape[1])
+    max_models = _check_int(max_models, 1, MAX_STATES, "max_models")
+    budget_bytes = _check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
+    S, K = k.shape[0], edges.shape[2]
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != S or y.size != S:
+        raise ValueError("sections: x and y must hold one entry per sounding (%d)" % S)
+    p = _default_ptr(ptr, S)
+    g = steps(x, y, tau, length, min_distance, p)
+    rows, n_used, _ = used_rows(ens, chains=C, max_models=max_models)
+    n = rows.shape[1]
+    if score is not None:
+        _are_tensors((score,), "sections", "gbp_section_track")
+        if tuple(score.shape) != (S, n) or score.dtype != torch.float64:
+            raise ValueError("sections: score must be float64 [S, n] with n = %d, the width of used_rows" % n)
+    dev, L = k.device, p.size - 1
+    keep, piece_ptr, owner = pieces(p, n_used)
+    slab = n * n * 8
+    longest = int(np.diff(piece_ptr).max(initial=0))
+    if longest * slab > budget_bytes:
+        raise ValueError("sections: a sequence of %d soundings with %d models each needs %d bytes of distances, more than budget_bytes = %d; lower "
+                         "max_models or raise budget_bytes (no state is carried between pieces of a sequence)" % (longest, n, longest * slab, budget_bytes))
+    _on_device((k, edges, sigma) + (() if score is None else (score,)), "sections", "gbp_ensemble_cross_distance")
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    nan = float("nan")
+    state = torch.full((S,), -1, **i32)
+    step_distance = torch.full((S,), nan, **f64)
+    log_score = torch.zeros(L, **f64)
+    weight = torch.full((S, n), nan, **f64) if marginals else None
+    log_partition = torch.zeros(L, **f64) if marginals else None
+    P, p0 = piece_ptr.size - 1, 0
+    while p0 < P:
+        p1 = p0 + 1
+        while p1 < P and (piece_ptr[p1 + 1] - piece_ptr[p0]) * slab <= budget_bytes:
+            p1 += 1
+        idx_h = keep[piece_ptr[p0]:piece_ptr[p1]]
+        idx = torch.as_tensor(idx_h).to(dev)
+        local = piece_ptr[p0:p1 + 1] - piece_ptr[p0]
+        T = idx_h.size
+        partner = np.arange(1, T + 1, dtype=np.int32)
+        partner[local[1:] - 1] = -1
+        sub = Ensemble(k[idx], edges[idx], sigma[idx], None, None, ens.thin, None)
+        d2 = cross_distance(sub, rows[idx], partner, z0, z1, measure=measure, squared=True)
+        res = track(d2, g[idx_h], local, n_used[idx], score=None if score is None else score[idx], marginals=marginals)
+        st = res["state"].long()
+        state[idx] = res["state"]
+        t = torch.arange(T, device=dev)
+        nxt = torch.as_tensor(np.where(partner >= 0, partner, 0).astype(np.int64)).to(dev)
+        chosen = d2[t, st, st[nxt]]
+        step_distance[idx] = torch.where(torch.as_tensor(partner >= 0).to(dev), torch.sqrt(chosen), torch.full_like(chosen, nan))
+        own = torch.as_tensor(owner[p0:p1]).to(dev)
+        log_score.index_add_(0, own, res["log_score"])
+        if marginals:
+            weight[idx] = res["marginal"]
+            log_partition.index_add_(0, own, res["log_partition"])
+        del d2, res
+        p0 = p1
+    has = state >= 0
+    at = torch.arange(S, device=dev)
+    slot = torch.gather(rows.long(), 1, state.long().clamp(min=0)[:, None])[:, 0].clamp(min=0) if S else torch.zeros(0, dtype=torch.int64, device=dev)
+    nanv = torch.full((), nan, **f64)
+    out = dict(state=state, slot=torch.where(has, slot, torch.full_like(slot, -1)).to(torch.int32), rows=rows, n_used=n_used,
+               section_k=torch.where(has, k[at, slot], torch.zeros_like(k[at, slot])),
+               section_edges=torch.where(has[:, None], edges[at, slot], nanv), section_sigma=torch.where(has[:, None], sigma[at, slot], nanv),
+               step_distance=step_distance, log_score=log_score)
+    if marginals:
+        w = torch.where(has[:, None], weight, torch.zeros((), **f64))
+        out["weight"] = weight
+        out["chosen_weight"] = torch.where(has, torch.gather(w, 1, state.long().clamp(min=0)[:, None])[:, 0], nanv) if S else torch.zeros(0, **f64)
+        out["n_effective"] = torch.where(has, 1.0 / (w * w).sum(dim=1), nanv)
+        out["log_partition"] = log_partition
+    return out
+
+
+def line_ptr(line):
+    """ptr int64 [L + 1] of the runs of consecutive rows with equal ``line`` number."""
+    line = np.asarray(line).reshape(-1)
+    cut = np.flatnonzero(line[1:] != line[:-1]) + 1 if line.size else np.zeros(0, dtype=np.int64)
+    return np.concatenate([[0], cut, [line.size]]).astype(np.int64) if line.size else np.zeros(1, dtype=np.int64)
+
+
+def from_survey(result_or_path, z1, device=None, **kw):
+    """``sections`` for a ``survey.SurveyResult`` -- or the file its ``save`` wrote -- that carries the kept models (``survey.infer(...,
+    ensemble=...)``: ensemble_k / _edges / _sigma).  The sequences are the runs of consecutive rows with equal line number; ``kw``: the
+    keywords of ``sections`` but ``ptr``.  Returns its dictionary on ``device`` (default cuda:0) plus ``line``, ``fiducial``, ``x``, ``y``
+    (numpy, as stored)."""
+    from .survey import SurveyResult
+    res = SurveyResult.load(result_or_path) if isinstance(result_or_path, (str, bytes)) or hasattr(result_or_path, "__fspath__") else result_or_path
+    missing = [name for name in ("ensemble_k", "ensemble_edges", "ensemble_sigma", "line", "x", "y") if name not in res]
+    if missing:
+        raise ValueError("sections.from_survey: the survey result holds no %s (survey.infer(..., ensemble=n_keep) keeps the models)" % ", ".join(missing))
+    if "ptr" in kw:
+        raise ValueError("sections.from_survey: the sequences are the survey's lines; ptr is not taken")
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    k = torch.as_tensor(np.ascontiguousarray(res["ensemble_k"], dtype=np.int32))
+    e, s = (torch.as_tensor(np.ascontiguousarray(res[name], dtype=np.float64)) for name in ("ensemble_edges", "ensemble_sigma"))
+    if dev.type == "cuda":
+        k, e, s = k.to(dev), e.to(dev), s.to(dev)
+    ens = Ensemble(k, e, s, None, None, 1, None)
+    out = sections(ens, res["x"], res["y"], z1, ptr=line_ptr(res["line"]), **kw)
+    out.update(line=np.asarray(res["line"]), fiducial=np.asarray(res["fiducial"]) if "fiducial" in res else np.arange(k.shape[0]),
+               x=np.asarray(res["x"]), y=np.asarray(res["y"]))
+    return out
+
+
+def save(result, path):
+    """Write a result ({name: tensor or array}) to ``path`` (``<name>.sections.npz``) with np.savez_compressed; returns the path."""
+    np.savez_compressed(path, **{k: _host(v) for k, v in result.items()})
+    return path
+
+
+def load(path):
+    """{name: numpy array} of a file written by ``save``."""
+    with np.load(path) as f:
+        return {k: f[k] for k in f.files}
+
+
+def output_path(path):
+    """<name>.sections.npz beside the survey result <name>.npz."""
+    path = str(path)
+    return (path[:-4] if path.endswith(".npz") else path) + OUTPUT_SUFFIX
+
+
+# ---- the command line ---------------------------------------------------------------------------------------------------------------
+
+def _parser():
+    import argparse
+    from .families import MEASURES
+    p = argparse.ArgumentParser(prog="python -m geobipy_amd.sections",
+                                description="One kept model per sounding, chosen jointly along every flight line of a saved survey result that "
+                                            "carries its ensemble; writes <name>.sections.npz")
+    p.add_argument("survey", help="a survey result written by SurveyResult.save (.npz) with ensemble_k / _edges / _sigma")
+    p.add_argument("--depth", type=float, required=True, metavar="Z1", help="the bottom of the depth window (m)")
+    p.add_argument("--from", dest="z0", type=float, default=0.0, metavar="Z0", help="the top of the depth window (default 0)")
+    p.add_argument("--measure", choices=MEASURES, default="linear", help="weigh depth linearly or by its logarithm (log needs --from > 0)")
+    p.add_argument("--tau", type=float, default=0.1, metavar="T", help="decades of RMS difference per --length metres (default 0.1)")
+    p.add_argument("--length", type=float, default=100.0, metavar="L", help="the distance --tau refers to, m (default 100)")
+    p.add_argument("--max-models", type=int, default=128, metavar="n", help="the most models per sounding, 1 .. 1024 (default 128)")
+    p.add_argument("--chains", type=int, default=1, metavar="C", help="replicate chains on the slot axis (default 1)")
+    p.add_argument("--no-marginals", action="store_true", help="only the path: skip the forward-backward pass")
+    p.add_argument("--device", default="cuda:0")
+    return p
+
+
+def parse_args(argv=None):
+    """The command line as (path, keywords of ``from_survey``); refuses before any device work."""
+    p = _parser()
+    a = p.parse_args(argv)
+    try:
+        check_window(a.z0, a.depth, a.measure)
+        _check_number(a.tau, "--tau")
+        _check_number(a.length, "--length")
+        _check_int(a.chains, 1, 8, "--chains")
+        _check_int(a.max_models, 1, MAX_STATES, "--max-models")
+    except ValueError as e:
+        p.error(str(e))
+    return a.survey, dict(z1=a.depth, z0=a.z0, measure=a.measure, tau=a.tau, length=a.length, max_models=a.max_models, chains=a.chains,
+                          marginals=not a.no_marginals, device=a.device)
+
+
+def main(argv=None):
+    path, kw = parse_args(argv)
+    out = save(from_survey(path, **kw), output_path(path))
+    print("wrote", out)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -836,6 +836,19 @@ gbp_status gbp_ensemble_distance(int B, int n_slots, int K, const int32_t *ens_k
 gbp_status gbp_distance_families(int B, int n, const double *dist, const int32_t *n_used, int q_max, int max_iter, int32_t *medoid,
                                  int32_t *label, double *nearest, double *second, int32_t *iterations, uint8_t *converged, int32_t *n_found,
                                  void *stream);
+/* gbp_ensemble_cross_distance -- the distance of gbp_ensemble_distance, word for word (the same breakpoints, the same order of the sum,
+ * the same log1p: one device function serves both kernels, so a pair of models gives the same bits through either entry), between the
+ * models of DIFFERENT soundings (the host statement is geobipy_amd/sections.py cross_distance_reference).  rows int32
+ * [S, n] as above; partner int32 [S]: the sounding that sounding s is paired with, or -1.  dist f64 [S, n, n]: dist[s, i, j] is D (or
+ * D2) between model rows[s, i] of sounding s and model rows[partner[s], j] of sounding partner[s].  An absent model (a row outside
+ * 0 .. n_slots - 1, a slot with k <= 0) gives NaN in its row (i) or column (j); a sounding whose partner is -1 or otherwise outside
+ * 0 .. S - 1 gets a slab of NaN.  Every entry is written.  Nothing is symmetric and there is no diagonal: i and j are models of
+ * different soundings, and two identical models are exactly 0.0 apart by arithmetic.  One workgroup of 256 threads per (sounding,
+ * 16 x 16 tile), all nt x nt tiles.  The limits and refusals of gbp_ensemble_distance (256 threads per tile; a NULL partner); S == 0
+ * launches nothing.  No atomics: a call repeats its own bits. */
+gbp_status gbp_ensemble_cross_distance(int S, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                                       int n, const int32_t *rows, const int32_t *partner, double z0, double z1, int measure, int log10,
+                                       int squared, double *dist, void *stream);
 gbp_status gbp_hitmap_products_i64(int B, int n_value, int n_depth, const int64_t *hitmap, const double *log_mean_prior, double half_width,
                                    int n_q, const double *q, double *mean, int32_t *mode_idx, int32_t *q_idx, int64_t *total, double *s1,
                                    void *stream);
@@ -974,6 +987,29 @@ gbp_status gbp_elevation_resample(int mode, int R, int K, int n_depth, const dou
 gbp_status gbp_horizon_track(int L, const int64_t *ptr, int64_t total_n, int max_n, int S, double dz, const double *score,
                              const double *absent_score, const double *g, const double *d, double switch_cost, uint16_t *back,
                              int32_t *cell, double *log_score, double *marginal, double *log_partition, double *scale, void *stream);
+
+/* Sections of sampled models along lines (csrc/gbp_section.h k_section_viterbi, k_section_marginals; the rule is
+ * stated in numpy as sections.track_reference): the most probable path and the smoothed marginals of a Markov chain whose states
+ * under row r are the first m_r = n_used[r] (1 .. n) of n kept models and whose transition is a dense matrix per step.  The
+ * conventions of gbp_horizon_track: L sequences concatenated by ptr [L + 1] int64 (a sequence has >= 1 row), DEVICE arrays, ptr
+ * included; the caller passes total_n = ptr[L].  score f64 [total_n, n], g f64 [total_n], d2 f64 [total_n, n, n] of the step r ->
+ * r + 1 (the entry of a sequence's last row is never read; nothing outside the prefixes i < m_r, j < m_{r+1} is read).
+ *   Viterbi: V_0[j] = score[r0, j], j < m_0.  Per step and per j < m_{r+1}: best = -inf, arg = 0; for i = 0 .. m_r - 1 ascending
+ *   cand = V[i] - g[r] * d2[r, i, j] (one fp64 multiply, one subtract), replaced on strict cand > best -- a NaN never wins --;
+ *   V'[j] = score[r + 1, j] + best, back[r + 1, j] = arg.  The path ends at the first maximum of V over j < m_last: log_score [L]; the
+ *   walk back gives state int32 [total_n], every state < m_r.  state and log_score equal the numpy rule's in every bit.
+ *   Marginals (only when marginal, log_partition and scale are given): w = exp(score); alpha_0 = w_0 / s_0; u[j] = sum_i alpha[i]
+ *   exp(-(g[r] d2[r, i, j])), i ascending; u <- w_{r+1} o u; s_{r+1} = sum u; alpha' = u / s_{r+1}; beta_last = 1, beta_r[i] = sum_j
+ *   exp(-(g[r] d2[r, i, j])) w_{r+1}[j] beta_{r+1}[j] / s_{r+1}; marginal [total_n, n] = alpha o beta renormalised per row, 0.0 for
+ *   the states >= m_r; scale [total_n] = s; log_partition [L] = sum ln s.  The device's exp and the order of its normalising and
+ *   backward sums differ from numpy's: a few ulp.  Where every transition of a step underflows the marginals of the sequence are NaN
+ *   (the path is not affected).
+ * back: a workspace of total_n * n uint16.  One 256-thread workgroup per sequence; LDS: (2 n + 4) doubles, 3 KiB static.
+ * GBP_ERR_INVALID_ARG, before any launch: L < 0, n < 1 or n > 1024, total_n < L, sizes out of range, a NULL ptr / n_used / score / g /
+ * d2 / back / state / log_score, marginal, log_partition and scale not all given or all NULL.  L == 0 launches nothing. */
+gbp_status gbp_section_track(int L, const int64_t *ptr, int64_t total_n, int n, const int32_t *n_used, const double *score,
+                             const double *g, const double *d2, uint16_t *back, int32_t *state, double *log_score, double *marginal,
+                             double *log_partition, double *scale, void *stream);
 
 #ifdef __cplusplus
 }
