@@ -2464,3 +2464,49 @@ extern "C" gbp_status gbp_section_track(int L, const int64_t* ptr, int64_t total
                                                            scale, st);
     }
 }
+
+// Joint draws of sections (gbp_section.h k_section_filter, k_section_draw): the filter launch, one workgroup per sequence, then the
+// walks, one wave per (sequence, 64 realisations).  Every refusal comes before any launch; ptr is not read on the host.
+namespace {
+
+template <int NJ>
+gbp_status section_draw_launch(int L, const int64_t* ptr, int64_t total_n, int n, const int32_t* n_used, const double* score, const double* g,
+                               const double* d2, const int64_t* row_key, uint64_t seed, int n_draws, double* filtered, double* scale,
+                               int32_t* draw_state, hipStream_t st)
+{
+    hipLaunchKernelGGL(section::k_section_filter<NJ>, dim3((unsigned)L), dim3(section::THREADS), section::lds_bytes(n), st, (const long long*)ptr, n,
+                       (const int*)n_used, score, g, d2, filtered, scale);
+    GBP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(section::k_section_draw, dim3((unsigned)L, (unsigned)((n_draws + 63) / 64)), dim3(64), 0, st, (const long long*)ptr,
+                       (long long)total_n, n, (const int*)n_used, g, d2, (const long long*)row_key, (unsigned long long)seed, n_draws,
+                       (const double*)filtered, (int*)draw_state);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" gbp_status gbp_section_draw(int L, const int64_t* ptr, int64_t total_n, int n, const int32_t* n_used, const double* score,
+                                       const double* g, const double* d2, const int64_t* row_key, uint64_t seed, int n_draws,
+                                       double* filtered, double* scale, int32_t* draw_state, void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: L must be >= 0%s");
+    if (n < 1 || n > section::MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: n must lie in 1 .. 1024%s");
+    if (n_draws < 1 || n_draws > section::MAX_DRAWS) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: n_draws must lie in 1 .. 65536%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < L) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: total_n does not fit L sequences of at least one sounding%s");
+    if (total_n > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: total_n * n * n out of range%s");
+    if (total_n > 0x7fffffffffffffffLL / 4 / n_draws) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: n_draws * total_n out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: ptr is NULL%s");
+    if (!n_used || !score || !g || !d2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: NULL pointer (n_used, score, g, d2)%s");
+    if (!filtered || !scale) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: NULL pointer (filtered, the scale workspace)%s");
+    if (!draw_state) return fail(GBP_ERR_INVALID_ARG, "gbp_section_draw: draw_state is NULL%s");
+    hipStream_t st = (hipStream_t)stream;
+    switch ((n + section::THREADS - 1) / section::THREADS) {
+        case 1: return section_draw_launch<1>(L, ptr, total_n, n, n_used, score, g, d2, row_key, seed, n_draws, filtered, scale, draw_state, st);
+        case 2: return section_draw_launch<2>(L, ptr, total_n, n, n_used, score, g, d2, row_key, seed, n_draws, filtered, scale, draw_state, st);
+        case 3: return section_draw_launch<3>(L, ptr, total_n, n, n_used, score, g, d2, row_key, seed, n_draws, filtered, scale, draw_state, st);
+        default: return section_draw_launch<section::MAX_OWNED>(L, ptr, total_n, n, n_used, score, g, d2, row_key, seed, n_draws, filtered, scale,
+                                                                draw_state, st);
+    }
+}

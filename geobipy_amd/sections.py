@@ -20,6 +20,11 @@ the depth window (the distance of ``families.distance``, between the models of t
 ``sections``        all of the above for an ensemble, and the chosen models: a section made of models the sampler visited, as continuous
                     along the line as the posteriors allow, with the weight every sounding's models get from their neighbours.
 ``from_survey``     the same for a ``survey.SurveyResult`` (or its saved file) that carries the ensemble; sequences are the flight lines.
+``draw``            joint draws of whole sections from the chain's posterior by forward filtering and backward sampling (DESIGN.md 3.26;
+                    gbp_section_draw: csrc/gbp_section.h k_section_filter / k_section_draw; ``draw_reference`` states the rule and
+                    ``philox_uniform`` its random numbers).  ``sections(..., draws=R, seed=N)`` adds them to its result, ``draw_models``
+                    gathers their models (and rasters them), and ``exceedance_area`` is one product that needs them: the area of a
+                    section above a conductivity threshold, a quantity of the line with a posterior only over joint realisations.
 
 The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L + 1]; m_r = n_used[r] in 1 .. n.
   Viterbi: V_0[j] = score[r0, j] for j < m_0.  Per step r -> r + 1 and per j < m_{r+1}: best = -inf, arg = 0; for i = 0 .. m_r - 1
@@ -31,8 +36,8 @@ The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L 
 Nothing outside the prefixes i < m_r, j < m_{r+1} of d2 is read, nor the entry of a sequence's last sounding.
 
 ``python -m geobipy_amd.sections <survey.npz> --depth Z1 [--from Z0] [--measure log] [--tau T] [--length L] [--max-models n]
-[--chains C] [--no-marginals]`` writes ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``, ``track`` and ``sections``
-refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
+[--chains C] [--no-marginals] [--draws R [--seed N]]`` writes ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``,
+``track``, ``draw`` and ``sections`` refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
 after the run, like ``horizons.from_products``.  Left out on purpose: coupling across lines, carrying a sequence across launches,
 weighted re-binning of the hit maps by ``weight``, and learning ``tau`` (``log_partition`` is returned for whoever wants to scan it).
 """
@@ -40,20 +45,23 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensembles import Ensemble, check_chains
+from .ensembles import Ensemble, check_chains, realisations
 from .families import MAX_K, MAX_MODELS, _check_block, _check_int, _stream, check_window, distance_reference, used_rows
 
 MAX_STATES = 1024
+MAX_DRAWS = 65536
 OUTPUT_SUFFIX = ".sections.npz"
 
 
-def check_ptr(ptr, total):
-    """``ptr`` as int64 numpy [L + 1]: starts at 0, ends at ``total``, every sequence holds at least one sounding."""
+def check_ptr(ptr, total, empty=False):
+    """``ptr`` as int64 numpy [L + 1]: starts at 0, ends at ``total``, every sequence holds at least one sounding (``empty``: or none)."""
     p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr)
     if p.ndim != 1 or p.size < 1 or p.dtype.kind not in "iu":
         raise ValueError("sections: ptr must be a vector of L + 1 integers")
     p = p.astype(np.int64)
-    if p[0] != 0 or p[-1] != total or np.any(np.diff(p) < 1):
+    if empty and (p[0] != 0 or p[-1] != total or np.any(np.diff(p) < 0)):
+        raise ValueError("sections: ptr must start at 0, end at the number of soundings (%d) and not decrease" % total)
+    if p[0] != 0 or p[-1] != total or (not empty and np.any(np.diff(p) < 1)):
         raise ValueError("sections: ptr must start at 0, end at the number of soundings (%d) and give every sequence at least one" % total)
     return p
 
@@ -153,12 +161,12 @@ def steps(x, y, tau=0.1, length=100.0, min_distance=1.0, ptr=None):
     return length / (2.0 * tau * tau * np.maximum(dx, min_distance))
 
 
-def _check_chain(ptr, score, g, d2, n_used, what):
-    """The host checks ``track`` and ``track_reference`` share; returns ptr (numpy), n_used (numpy int64)."""
+def _check_chain(ptr, score, g, d2, n_used, what, empty=False):
+    """The host checks ``track``, ``draw`` and their references share; returns ptr (numpy), n_used (numpy int64)."""
     if d2.ndim != 3 or d2.shape[1] != d2.shape[2] or not 1 <= d2.shape[1] <= MAX_STATES:
         raise ValueError("%s: d2 [T, n, n] with 1 <= n <= %d" % (what, MAX_STATES))
     total, n = d2.shape[0], d2.shape[1]
-    ptr = check_ptr(ptr, total)
+    ptr = check_ptr(ptr, total, empty)
     nu = _host(n_used).reshape(-1)
     if nu.size != total or nu.dtype.kind not in "iu":
         raise ValueError("%s: n_used must hold one integer per sounding" % what)
@@ -247,6 +255,120 @@ def _first_max(v):
         if v[j] > v[cur]:
             cur = j
     return cur
+
+
+# ---- joint draws: the rule ----------------------------------------------------------------------------------------------------------
+
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("sections: seed must be an integer in 0 .. 2^64 - 1")
+    return int(seed)
+
+
+def _check_row_key(row_key, total, what):
+    """``row_key`` as int64 numpy [T]; None: the row index."""
+    if row_key is None:
+        return np.arange(total, dtype=np.int64)
+    key = _host(row_key)
+    if key.shape != (total,) or key.dtype.kind not in "iu":
+        raise ValueError("%s: row_key must hold one integer per sounding" % what)
+    return key.astype(np.int64)
+
+
+def philox_uniform(seed, draw, row_key):
+    """The uniform of a draw, float64 in [0, 1), vectorised over ``draw`` and ``row_key`` (broadcast against each other): u53(x, y) of
+    the Philox4x32-10 block with key ``seed`` (uint64: low word, high word) and counter (draw, row_key & 0xFFFFFFFF, row_key >> 32, 0)
+    -- the generator and the 53-bit uniform of the sampler (csrc/gbp_philox.h), counter layout of the section draws."""
+    seed = _check_seed(seed)
+    c0, key = np.broadcast_arrays(np.asarray(draw, dtype=np.int64).astype(np.uint64) & _M32, np.asarray(row_key, dtype=np.int64).astype(np.uint64))
+    c1, c2, c3 = key & _M32, key >> _S32, np.zeros(key.shape, dtype=np.uint64)
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2          # 32 x 32 bits: no overflow in 64
+        c0, c1, c2, c3 = ((p1 >> _S32) ^ c1 ^ k0) & _M32, p1 & _M32, ((p0 >> _S32) ^ c3 ^ k1) & _M32, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return ((c0 >> np.uint64(5)).astype(np.float64) * 67108864.0 + (c1 >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
+
+
+def draw_reference(ptr, score, g, d2, n_used, n_draws, seed=0, row_key=None, dtype=np.float64):
+    """The rule of ``draw`` in numpy, evaluated in ``dtype``: joint draws of whole sections from the chain of the module's docstring
+    by forward filtering and backward sampling.  The inputs of ``track_reference`` (a sequence of ``ptr`` may be empty here), ``n_draws``
+    = R in 1 .. 65536, ``seed`` (uint64) and ``row_key`` int64 [T] (None: the row index).
+
+    Filter, per sequence: the forward pass of ``track_reference``, word for word -- w_s = exp(score), alpha_0 = w_0 / sum w_0, u[j] =
+    sum_i alpha_s[i] exp(-(g_s d2[s, i, j])) with i ascending and u = u + a * e, alpha_{s+1} = (w_{s+1} u) / sum.
+    Draws: realisation rho walks s = N - 1 .. 0.  Over i < m_s the weights are W[i] = alpha_s[i] at the last sounding and alpha_s[i] *
+    exp(-(g_s * d2[s, i, j])) elsewhere, j the state just drawn under s + 1; c = cumsum(W), sequential with i ascending; thr = u *
+    c[m_s - 1]; pick = min(#{i : c[i] <= thr}, m_s - 1).  A state of weight 0 is never the first to pass thr, so it is never drawn; with
+    a NaN total no comparison holds and the pick is 0.  u = ``philox_uniform(seed, rho, row_key[s])``: a draw depends on the seed, the
+    realisation and the sounding's key -- not on R, on the grouping of sequences into calls, or on a launch shape.
+
+    Returns ``draw_state`` int32 [R, T], ``filtered`` [T, n] (alpha, 0.0 for the states >= m_s) and ``margin`` [R, T] = min_i |c[i] -
+    thr| / c[m_s - 1]: how close the draw came to another outcome (a device whose exp differs in the last bit may decide a draw with a
+    margin of a few ulp the other way)."""
+    ft = np.dtype(dtype).type
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.draw_reference", empty=True)
+    R = _check_int(n_draws, 1, MAX_DRAWS, "sections.draw_reference: n_draws")
+    total, n = d2.shape[0], d2.shape[1]
+    key = _check_row_key(row_key, total, "sections.draw_reference")
+    seed = _check_seed(seed)
+    score = (np.zeros((total, n)) if score is None else score).astype(ft)
+    g = np.asarray(g, dtype=np.float64).reshape(-1).astype(ft)
+    rho = np.arange(R, dtype=np.int64)
+    draw_state, filtered, margin = np.zeros((R, total), dtype=np.int32), np.zeros((total, n), dtype=ft), np.zeros((R, total), dtype=ft)
+    for l in range(ptr.size - 1):
+        r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+        if N == 0:
+            continue
+        m = [int(v) for v in nu[r0:r0 + N]]
+        E = [np.exp(-(g[r0 + s] * d2[r0 + s, :m[s], :m[s + 1]].astype(ft))) for s in range(N - 1)]      # prefixes only
+        w = [np.exp(score[r0 + s, :m[s]]) for s in range(N)]
+        alpha = [None] * N
+        alpha[0] = w[0] / w[0].sum()
+        for s in range(N - 1):
+            u = np.zeros(m[s + 1], dtype=ft)
+            for i in range(m[s]):                                            # i ascending
+                u = u + alpha[s][i] * E[s][i]
+            u = w[s + 1] * u
+            alpha[s + 1] = u / u.sum()
+        j = None
+        for s in range(N - 1, -1, -1):
+            filtered[r0 + s, :m[s]] = alpha[s]
+            W = np.broadcast_to(alpha[s][None, :], (R, m[s])) if s == N - 1 else alpha[s][None, :] * E[s][:, j].T
+            c = np.cumsum(W, axis=1, dtype=ft)                               # sequential, i ascending
+            thr = philox_uniform(seed, rho, key[r0 + s]).astype(ft) * c[:, -1]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                j = np.minimum((c <= thr[:, None]).sum(axis=1), m[s] - 1)
+                margin[:, r0 + s] = np.abs(c - thr[:, None]).min(axis=1) / c[:, -1]
+            draw_state[:, r0 + s] = j
+    return dict(draw_state=draw_state, filtered=filtered, margin=margin)
+
+
+def exceedance_area_reference(k, edges, sigma, x, y, ptr, threshold, z0, z1, above=True):
+    """The rule of ``exceedance_area`` in numpy loops: [R, L] in m^2."""
+    k, edges, sigma = np.asarray(k), np.asarray(edges, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+    R, S = k.shape
+    p = _default_ptr(ptr, S)
+    width = section_widths(x, y, p)
+    out = np.zeros((R, p.size - 1))
+    for l in range(p.size - 1):
+        for r in range(R):
+            area = 0.0
+            for s in range(int(p[l]), int(p[l + 1])):
+                thick = 0.0
+                for q in range(int(k[r, s])):
+                    top, bottom = (0.0 if q == 0 else edges[r, s, q - 1]), (edges[r, s, q] if q < k[r, s] - 1 else np.inf)
+                    if (sigma[r, s, q] >= threshold) if above else (sigma[r, s, q] < threshold):
+                        thick = thick + max(0.0, min(bottom, z1) - max(top, z0))
+                area = area + width[s] * thick
+            out[r, l] = area
+    return out
 
 
 # ---- the entries --------------------------------------------------------------------------------------------------------------------
@@ -354,8 +476,52 @@ def track(d2, g, ptr, n_used, score=None, marginals=True):
     return out
 
 
+def draw(d2, g, ptr, n_used, n_draws, seed=0, score=None, row_key=None):
+    """Joint draws of whole sections from the chain of ``track`` by forward filtering and backward sampling (gbp_section_draw;
+    ``draw_reference`` states the rule): ``d2``, ``g``, ``ptr``, ``n_used``, ``score`` as ``track`` takes them (a sequence of ``ptr``
+    may be empty), ``n_draws`` = R in 1 .. 65536, ``seed`` a uint64, ``row_key`` int64 [T] (host or device; None: the row index) -- the
+    uniform of realisation rho under a sounding is ``philox_uniform(seed, rho, row_key)``, so soundings keep their draws however they
+    are grouped into calls.  Returns on the device ``draw_state`` int32 [R, T] and ``filtered`` [T, n]."""
+    entry = "gbp_section_draw"
+    _are_tensors((d2,) + (() if score is None else (score,)), "draw", entry)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.draw", empty=True)
+    R = _check_int(n_draws, 1, MAX_DRAWS, "sections.draw: n_draws")
+    seed = _check_seed(seed)
+    if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
+        raise TypeError("sections.draw: d2 and score are float64")
+    total, n = d2.shape[0], d2.shape[1]
+    key = None if row_key is None else _check_row_key(row_key, total, "sections.draw")
+    _on_device((d2,) + (() if score is None else (score,)), "draw", entry)
+    dev = d2.device
+    L = ptr.size - 1
+    f64 = dict(dtype=torch.float64, device=dev)
+    d2 = d2.contiguous()
+    score = torch.zeros((total, n), **f64) if score is None else score.contiguous()
+    t_ptr = torch.as_tensor(ptr, dtype=torch.int64).to(dev)
+    t_g = torch.as_tensor(_host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_nu = torch.as_tensor(nu.astype(np.int32)).to(dev)
+    t_key = None if key is None else torch.as_tensor(key).to(dev)
+    scale = torch.empty(total, **f64)
+    out = dict(draw_state=torch.empty((R, total), dtype=torch.int32, device=dev), filtered=torch.empty((total, n), **f64))
+    if L > 0 and total > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gbp_section_draw(L, t_ptr.data_ptr(), total, n, t_nu.data_ptr(), score.data_ptr(), t_g.data_ptr(), d2.data_ptr(),
+                                                    None if t_key is None else t_key.data_ptr(), seed, R, out["filtered"].data_ptr(),
+                                                    scale.data_ptr(), out["draw_state"].data_ptr(), _stream(dev)))
+    return out
+
+
+def _run_sums(terms, piece_ptr):
+    """[R, P]: the sums of ``terms`` [R, T] over the runs of ``piece_ptr`` [P + 1], one reduction per run -- the shape of a run alone
+    decides the order of its sum, not what else shares the launch."""
+    out = torch.zeros((terms.shape[0], len(piece_ptr) - 1), dtype=terms.dtype, device=terms.device)
+    for q in range(len(piece_ptr) - 1):
+        out[:, q] = terms[:, int(piece_ptr[q]):int(piece_ptr[q + 1])].sum(dim=1)
+    return out
+
+
 def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=128, tau=0.1, length=100.0, min_distance=1.0, score=None,
-             marginals=True, budget_bytes=4 << 30):
+             marginals=True, budget_bytes=4 << 30, draws=0, seed=0):
     """One kept model per sounding, chosen jointly along every sequence of ``ptr`` [L + 1] (None: one sequence) for the ensemble
     ``ens`` of soundings at ``x``, ``y`` [S] (host; m) over the depth window [z0, z1]: ``families.used_rows`` (``chains``,
     ``max_models`` <= 1024), ``cross_distance`` (squared), ``steps`` (``tau``, ``length``, ``min_distance``), ``track`` and a gather.
@@ -368,7 +534,13 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     (bit copies of the chosen slots; NaN: none), ``step_distance`` f64 [S] (D in decades between the chosen models of s and s + 1; NaN at
     the end of a run), ``log_score`` f64 [L] (the sum over the sequence's runs; 0 for a sequence without models); with ``marginals``
     ``weight`` f64 [S, n] (the smoothed marginal of every used model; NaN: no models), ``chosen_weight`` [S], ``n_effective`` [S] =
-    1 / sum w^2 (between 1 and n_used: how strongly the neighbours re-weight the sounding's samples) and ``log_partition`` [L]."""
+    1 / sum w^2 (between 1 and n_used: how strongly the neighbours re-weight the sounding's samples) and ``log_partition`` [L].
+
+    ``draws`` = R > 0 adds R joint realisations of every sequence from the chain's posterior (``draw`` with ``seed``; the key of a
+    sounding is its index in the survey, so ``budget_bytes`` cannot change a draw): ``draw_state`` int32 [R, S] (the position in
+    ``rows``; -1: no models), ``draw_slot`` int32 [R, S] (the ensemble slot; -1) and ``draw_log_score`` f64 [R, L] = sum score - sum g
+    d2 along the drawn path, summed over a cut sequence's runs: on the scale of ``log_score``, so that ``draw_log_score -
+    log_partition`` is the path's log probability.  ``draw_models`` gathers the models."""
     z0, z1, _ = check_window(z0, z1, measure)
     k, edges, sigma = ens.k, ens.edges, ens.sigma
     _are_tensors((k, edges, sigma), "sections", "gbp_ensemble_cross_distance")
@@ -377,6 +549,7 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     C = check_chains(chains, k.shape[1])
     max_models = _check_int(max_models, 1, MAX_STATES, "max_models")
     budget_bytes = _check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
+    R, seed = _check_int(draws, 0, MAX_DRAWS, "draws"), _check_seed(seed)
     S, K = k.shape[0], edges.shape[2]
     x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
     if x.size != S or y.size != S:
@@ -404,6 +577,8 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     log_score = torch.zeros(L, **f64)
     weight = torch.full((S, n), nan, **f64) if marginals else None
     log_partition = torch.zeros(L, **f64) if marginals else None
+    draw_state = torch.full((R, S), -1, **i32) if R else None
+    draw_log_score = torch.zeros((R, L), **f64) if R else None
     P, p0 = piece_ptr.size - 1, 0
     while p0 < P:
         p1 = p0 + 1
@@ -429,6 +604,19 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
         if marginals:
             weight[idx] = res["marginal"]
             log_partition.index_add_(0, own, res["log_partition"])
+        if R:
+            sc = None if score is None else score[idx]
+            ds = draw(d2, g[idx_h], local, n_used[idx], R, seed=seed, score=sc, row_key=idx_h)["draw_state"]
+            draw_state[:, idx] = ds
+            dl = ds.long()
+            cost = torch.as_tensor(g[idx_h]).to(dev)[None, :] * d2[t[None, :], dl, dl[:, nxt]]
+            terms = -torch.where(torch.as_tensor(partner >= 0).to(dev)[None, :], cost, torch.zeros((), **f64))
+            if sc is not None:
+                terms = torch.gather(sc[None, :, :].expand(R, T, n), 2, dl[:, :, None])[:, :, 0] + terms
+            runs = _run_sums(terms, local)
+            for q in range(p1 - p0):                                         # run after run: a cut sequence sums its runs in their order
+                draw_log_score[:, int(owner[p0 + q])] += runs[:, q]
+            del ds, dl, cost, terms
         del d2, res
         p0 = p1
     has = state >= 0
@@ -445,7 +633,93 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
         out["chosen_weight"] = torch.where(has, torch.gather(w, 1, state.long().clamp(min=0)[:, None])[:, 0], nanv) if S else torch.zeros(0, **f64)
         out["n_effective"] = torch.where(has, 1.0 / (w * w).sum(dim=1), nanv)
         out["log_partition"] = log_partition
+    if R:
+        dhas = draw_state >= 0
+        dslot = torch.gather(rows.long()[None, :, :].expand(R, S, n), 2, draw_state.long().clamp(min=0)[:, :, None])[:, :, 0].clamp(min=0)
+        out.update(draw_state=draw_state, draw_slot=torch.where(dhas, dslot, torch.full_like(dslot, -1)).to(torch.int32), draw_log_score=draw_log_score)
     return out
+
+
+def draw_models(ens, draw_slot, depth_edges=None, log10=True):
+    """The models of joint realisations: ``draw_slot`` int32 [R, S] (``sections(..., draws=R)``; -1: none) into the ensemble ``ens``.
+    Returns on the device ``k`` int32 [R, S] (0: none), ``edges`` / ``sigma`` f64 [R, S, K] (bit copies of the drawn slots; NaN: none),
+    and with ``depth_edges`` [n_depth + 1] ``raster`` f64 [R, S, n_depth]: ``ensembles.realisations`` (its ``log10``) of the gathered
+    models -- the section of every realisation on a depth axis."""
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    _are_tensors((k, edges, sigma, draw_slot), "draw_models", "gbp_ensemble_raster")
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
+        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
+    if draw_slot.ndim != 2 or draw_slot.shape[1] != k.shape[0] or draw_slot.shape[0] < 1 or draw_slot.dtype != torch.int32:
+        raise ValueError("draw_models: draw_slot is int32 [R, S] with R >= 1")
+    _on_device((k, edges, sigma, draw_slot), "draw_models", "gbp_ensemble_raster")
+    if bool(((draw_slot < -1) | (draw_slot >= k.shape[1])).any()):
+        raise ValueError("draw_models: every slot must lie in -1 .. n_slots - 1")
+    S, dev = k.shape[0], k.device
+    has = draw_slot >= 0
+    slot = draw_slot.long().clamp(min=0)
+    at = torch.arange(S, device=dev)[None, :]
+    nanv = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    out = dict(k=torch.where(has, k[at, slot], torch.zeros((), dtype=k.dtype, device=dev)),
+               edges=torch.where(has[:, :, None], edges[at, slot], nanv), sigma=torch.where(has[:, :, None], sigma[at, slot], nanv))
+    if depth_edges is not None:
+        parts = []
+        for r0 in range(0, draw_slot.shape[0], 4096):                         # the raster takes up to 4096 models per sounding
+            sl = slice(r0, r0 + 4096)
+            sub = Ensemble(out["k"][sl].t().contiguous(), out["edges"][sl].permute(1, 0, 2).contiguous(), out["sigma"][sl].permute(1, 0, 2).contiguous(),
+                           None, None, ens.thin, None)
+            parts.append(realisations(sub, depth_edges, log10=log10).permute(1, 0, 2))
+        out["raster"] = torch.cat(parts).contiguous()
+    return out
+
+
+def section_widths(x, y, ptr=None):
+    """float64 [S] (numpy): the along-line width a sounding stands for -- half the distance to each neighbour in its sequence of
+    ``ptr`` (None: one sequence); a sequence's end has one neighbour and takes the whole distance to it (half of it on either side);
+    a sequence of one sounding has no width."""
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != y.size:
+        raise ValueError("sections: x and y must have one entry per sounding")
+    S = x.size
+    p = _default_ptr(ptr, S)
+    gap = np.zeros(S + 1)                                                      # gap[s]: the distance from s - 1 to s within a sequence
+    if S > 1:
+        gap[1:-1] = np.hypot(np.diff(x), np.diff(y))
+    gap[p] = 0.0
+    before, after = gap[:-1], gap[1:]
+    first, last = np.zeros(S, dtype=bool), np.zeros(S, dtype=bool)
+    if S:
+        first[p[:-1]], last[p[1:] - 1] = True, True
+    return np.where(first, after, np.where(last, before, 0.5 * before + 0.5 * after))
+
+
+def exceedance_area(k, edges, sigma, x, y, ptr, threshold, z0, z1, above=True):
+    """f64 [R, L] on the models' device, m^2: per realisation and sequence of ``ptr`` [L + 1] (None: one sequence) the area of the
+    section within the depth window [z0, z1] whose conductivity is >= ``threshold`` (S/m; ``above=False``: < threshold) -- the sum over
+    the soundings of ``section_widths`` times the thickness of the qualifying layers clipped to the window.  ``k`` [R, S], ``edges`` /
+    ``sigma`` [R, S, K]: what ``draw_models`` returns (a sounding without a model adds nothing); ``x``, ``y`` [S] (host; m).  A quantity
+    of the line: it has a posterior only over joint realisations.  Plain torch; ``exceedance_area_reference`` states the rule."""
+    if not (torch.is_tensor(k) and torch.is_tensor(edges) and torch.is_tensor(sigma)):
+        raise ValueError("exceedance_area: k, edges and sigma are torch tensors (draw_models)")
+    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
+        raise ValueError("exceedance_area: k [R, S], edges and sigma [R, S, K]")
+    threshold = _check_number(threshold, "threshold", positive=False)
+    z0, z1 = _check_number(z0, "z0", positive=False), _check_number(z1, "z1", positive=False)
+    if not 0.0 <= z0 < z1:
+        raise ValueError("exceedance_area: the window needs 0 <= z0 < z1")
+    R, S, K = edges.shape
+    if np.size(x) != S or np.size(y) != S:
+        raise ValueError("exceedance_area: x and y must hold one entry per sounding (%d)" % S)
+    p = _default_ptr(ptr, S)
+    width = torch.as_tensor(section_widths(x, y, p)).to(edges.device)
+    layer = torch.arange(K, device=edges.device)[None, None, :]
+    kk = k.long()[:, :, None]
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=edges.device)
+    zero = torch.zeros((), dtype=torch.float64, device=edges.device)
+    top = torch.cat([torch.zeros((R, S, 1), dtype=torch.float64, device=edges.device), edges[:, :, :-1]], dim=2)
+    bottom = torch.where(layer < kk - 1, edges, inf)
+    counts = (layer < kk) & ((sigma >= threshold) if above else (sigma < threshold))
+    thick = torch.where(counts, (bottom.clamp(max=z1) - top.clamp(min=z0)).clamp(min=0.0), zero).sum(dim=2)
+    return _run_sums(width[None, :] * thick, p)
 
 
 def line_ptr(line):
@@ -514,6 +788,8 @@ def _parser():
     p.add_argument("--max-models", type=int, default=128, metavar="n", help="the most models per sounding, 1 .. 1024 (default 128)")
     p.add_argument("--chains", type=int, default=1, metavar="C", help="replicate chains on the slot axis (default 1)")
     p.add_argument("--no-marginals", action="store_true", help="only the path: skip the forward-backward pass")
+    p.add_argument("--draws", type=int, default=0, metavar="R", help="joint realisations of every line to draw, 0 .. 65536 (default 0: none)")
+    p.add_argument("--seed", type=int, default=0, metavar="N", help="the seed of the draws, a uint64 (default 0)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -528,10 +804,15 @@ def parse_args(argv=None):
         _check_number(a.length, "--length")
         _check_int(a.chains, 1, 8, "--chains")
         _check_int(a.max_models, 1, MAX_STATES, "--max-models")
+        _check_int(a.draws, 0, MAX_DRAWS, "--draws")
+        _check_seed(a.seed)
     except ValueError as e:
         p.error(str(e))
-    return a.survey, dict(z1=a.depth, z0=a.z0, measure=a.measure, tau=a.tau, length=a.length, max_models=a.max_models, chains=a.chains,
-                          marginals=not a.no_marginals, device=a.device)
+    kw = dict(z1=a.depth, z0=a.z0, measure=a.measure, tau=a.tau, length=a.length, max_models=a.max_models, chains=a.chains,
+              marginals=not a.no_marginals, device=a.device)
+    if a.draws:
+        kw.update(draws=a.draws, seed=a.seed)
+    return a.survey, kw
 
 
 def main(argv=None):

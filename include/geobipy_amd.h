@@ -1011,6 +1011,27 @@ gbp_status gbp_section_track(int L, const int64_t *ptr, int64_t total_n, int n, 
                              const double *g, const double *d2, uint16_t *back, int32_t *state, double *log_score, double *marginal,
                              double *log_partition, double *scale, void *stream);
 
+/* Joint draws of whole sections from the chain of gbp_section_track by forward filtering and backward sampling (csrc/gbp_section.h
+ * k_section_filter, k_section_draw; the rule is stated in numpy as sections.draw_reference).  L, ptr, total_n, n,
+ * n_used, score, g, d2 as above, with one difference: a sequence may be empty (ptr repeated; nothing is written for it).
+ *   Filter: the forward pass of the marginals above, by the same device function: filtered f64 [total_n, n] = alpha_r, 0.0 for the
+ *   states >= m_r; scale [total_n] = s_r, a workspace the caller provides.
+ *   Draws: realisation rho = 0 .. n_draws - 1 walks r = last .. first of every sequence.  W[i] = alpha_r[i] at the last row, alpha_r[i]
+ *   * exp(-(g[r] * d2[r, i, j])) elsewhere, j the state just drawn under r + 1; c[i] = c[i - 1] + W[i] for i = 0 .. m_r - 1 ascending;
+ *   thr = u * c[m_r - 1]; the state is min(#{i : c[i] <= thr}, m_r - 1): a state of weight 0 is never drawn, and with a NaN total no
+ *   comparison holds and the state is 0.  u = u53(x, y) of Philox4x32-10 with key seed and counter (rho, key & 0xFFFFFFFF, key >> 32,
+ *   0), key = row_key[r] (int64 [total_n]; NULL: r): a draw depends on the seed, the realisation and the row's key, not on n_draws nor
+ *   on how sequences are grouped into launches.  draw_state int32 [n_draws, total_n], every state < m_r.  The device's exp is not
+ *   numpy's to the last bit: a draw whose threshold lies within rounding of a c[i] may fall either way, and the walk differs from there.
+ * One 256-thread workgroup per sequence for the filter (LDS as above), one wave per (sequence, 64 realisations) for the draws: no LDS,
+ * no atomics, no barrier.  A call repeats its own bits.
+ * GBP_ERR_INVALID_ARG, before any launch: L < 0, n < 1 or n > 1024, n_draws < 1 or > 65536, total_n < L, sizes out of range
+ * (total_n * n * n doubles, n_draws * total_n int32), a NULL ptr / n_used / score / g / d2 / filtered / scale / draw_state.  L == 0
+ * launches nothing. */
+gbp_status gbp_section_draw(int L, const int64_t *ptr, int64_t total_n, int n, const int32_t *n_used, const double *score,
+                            const double *g, const double *d2, const int64_t *row_key, uint64_t seed, int n_draws, double *filtered,
+                            double *scale, int32_t *draw_state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

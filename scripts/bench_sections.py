@@ -12,7 +12,12 @@ The cross distance needs no speed: its time is listed beside gbp_ensemble_distan
 entries are timed on preallocated buffers with device events, medians after warm-up rounds, taking turns with the yardstick in one
 process.  Writes one JSON file.
 
-    python scripts/bench_sections.py [--sequences 64] [--soundings 1024] [--models 128] [--rounds 5] [--out profiles/sections/bench.json]
+``--draws R`` also times gbp_section_draw on the same d2: the filter launch and the draw launch of R joint realisations
+per sequence together, between device events, beside the chain's times of the same run.  It has no yardstick either: the time is
+recorded, with the share of draws that fall on the Viterbi path and the spread of the smoothed marginals they reproduce.
+
+    python scripts/bench_sections.py [--sequences 64] [--soundings 1024] [--models 128] [--rounds 5] [--draws 0] [--seed 0]
+                                     [--out profiles/sections/bench.json]
 """
 import argparse
 import json
@@ -53,6 +58,8 @@ def main(argv=None):
     p.add_argument("--models", type=int, default=128)
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--draws", type=int, default=0, help="joint realisations per sequence to draw and time (0: none)")
+    p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "sections", "bench.json"))
     a = p.parse_args(argv)
     assert torch.cuda.is_available(), "bench_sections needs a GPU"
@@ -131,6 +138,31 @@ def main(argv=None):
                            largest_row_sum_error=float((weights - 1.0).abs().max()), mean_n_effective=float((1.0 / (marginal * marginal).sum(dim=1)).mean()))
     print("chain: viterbi %.3f ms; torch loop %.3f ms (x%.2f); paths equal: %s; with marginals %.3f ms"
           % (med["viterbi"], med["torch"], result["chain"]["ratio_torch_over_kernel"], same, med["both"]))
+    if a.draws > 0:
+        R = a.draws
+        filtered, scale_ws = torch.empty((S, n), dtype=torch.float64, device=dev), torch.empty((S,), dtype=torch.float64, device=dev)
+        draw_state = torch.empty((R, S), dtype=torch.int32, device=dev)
+
+        def draw():
+            _lib.check(lib.gbp_section_draw(L, ptr.data_ptr(), S, n, n_used.data_ptr(), score.data_ptr(), g.data_ptr(), d2.data_ptr(), None, a.seed, R,
+                                            filtered.data_ptr(), scale_ws.data_ptr(), draw_state.data_ptr(), stream))
+
+        for _ in range(a.warmup):
+            draw()
+        torch.cuda.synchronize(dev)
+        t_draw = [events_ms(draw, dev)[0] for _ in range(a.rounds)]
+        med_draw = float(np.median(t_draw))
+        track(True)                                                         # the smoothed marginals of the same chain, for the draws' frequencies
+        torch.cuda.synchronize(dev)
+        freq = torch.zeros((S, n), dtype=torch.float64, device=dev)
+        freq.scatter_add_(1, draw_state.long().t().contiguous(), torch.ones((S, R), dtype=torch.float64, device=dev))
+        z = ((freq - R * marginal) / torch.sqrt((R * marginal * (1.0 - marginal)).clamp(min=1e-300)))[R * marginal >= 5.0]
+        result["draws"] = dict(n_draws=R, seed=a.seed, filter_and_draw_ms=t_draw, viterbi_and_marginals_ms_median=med["both"], viterbi_ms_median=med["viterbi"],
+                               sounding_draws_per_s=float(R) * S / (med_draw * 1e-3), states_in_range=bool(((draw_state >= 0) & (draw_state < n)).all()),
+                               share_of_sounding_draws_on_the_viterbi_path=float((draw_state == state[None, :]).double().mean()),
+                               cells_compared=int(z.numel()), rms_z_against_the_marginals=float(torch.sqrt((z * z).mean())) if z.numel() else None)
+        print("draws: filter + %d draws per sequence %.3f ms (%.3g sounding-draws/s); rms z against the marginals %.3f over %d cells"
+              % (R, med_draw, result["draws"]["sounding_draws_per_s"], result["draws"]["rms_z_against_the_marginals"] or 0.0, z.numel()))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
