@@ -6,6 +6,8 @@ here raises.  Build it with ``python __graft_entry__.py`` (or ``geobipy_amd.buil
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgeobipy_amd.so")
 
@@ -214,3 +216,33 @@ def check(status):
     if status != 0:
         msg = load().gbp_last_error().decode(errors="replace")
         raise NativeLibraryError(f"geobipy_amd native call failed (status {status}): {msg}")
+
+
+def stream(dev):
+    """The raw handle of torch's current stream on ``dev``."""
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def pointers(name, dev, args):
+    """``args`` as the entry ``name`` takes them: a tensor becomes its ``data_ptr()`` -- it must live on ``dev``, the device whose
+    stream the launch runs on, and be contiguous, or the kernel would read other memory than the caller meant --; None, numbers,
+    ctypes arrays, ``byref`` objects and handles pass as they are.  No device is touched."""
+    out = []
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if a.device != dev:
+                raise NativeLibraryError("%s: argument %d is a tensor on %s, the launch runs on %s" % (name, i, a.device, dev))
+            if not a.is_contiguous():
+                raise NativeLibraryError("%s: argument %d is not contiguous (shape %r, strides %r)" % (name, i, tuple(a.shape), a.stride()))
+            a = a.data_ptr()
+        out.append(a)
+    return out
+
+
+def call(name, dev, *args):
+    """Launch the entry ``name`` on torch's current stream of ``dev``: ``args`` through ``pointers``, the stream appended as the last
+    argument, the status through ``check``.  The one way the product modules reach a ``gbp_*`` entry."""
+    args = pointers(name, dev, args)
+    entry = getattr(load(), name)
+    with torch.cuda.device(dev):
+        check(entry(*args, stream(dev)))

@@ -12,6 +12,8 @@ on CPU tensors too.
 import numpy as np
 import torch
 
+from ._args import load_npz as load, save_npz as save  # noqa: F401  (this module's ``save`` and ``load``)
+
 STATISTICS = ("mean", "median", "mode", "credible_range")
 
 
@@ -109,15 +111,3 @@ def products(chains_or_arrays, percentiles=(5, 50, 95), credible=90.0):
         out["data_predicted_" + k] = obs + scale * out["data_residual_" + k]
     out.update(misfit_statistics(torch.as_tensor(mh).to(dev), mhw, percentiles))
     return out
-
-
-def save(products, path):
-    """Write ``products`` to ``path`` with np.savez_compressed (as ``unit_posteriors.save``); returns the path."""
-    np.savez_compressed(path, **{k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in products.items()})
-    return path
-
-
-def load(path):
-    """{name: numpy array} of a file written by ``save``."""
-    with np.load(path) as f:
-        return {k: f[k] for k in f.files}

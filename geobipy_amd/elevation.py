@@ -21,18 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import host
 
 LEVELS, INTERVALS = 0, 1            # GBP_ELEVATION_LEVELS / GBP_ELEVATION_INTERVALS
 MAX_DEPTH_CELLS = 8191
 
 
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def check_depth_edges(depth_edges):
     """The depth edges as a float64 array: at least two, finite, strictly increasing, at most 8191 cells."""
-    e = np.asarray(_host(depth_edges), dtype=np.float64).reshape(-1)
+    e = np.asarray(host(depth_edges), dtype=np.float64).reshape(-1)
     if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0.0):
         raise ValueError("depth_edges: at least two finite, strictly increasing edges are needed")
     if e.size - 1 > MAX_DEPTH_CELLS:
@@ -46,11 +43,11 @@ def check_axis(levels=None, edges=None):
     if (levels is None) == (edges is None):
         raise ValueError("exactly one of levels and edges must be given")
     if levels is not None:
-        a = np.asarray(_host(levels), dtype=np.float64).reshape(-1)
+        a = np.asarray(host(levels), dtype=np.float64).reshape(-1)
         if a.size < 1 or not np.all(np.isfinite(a)):
             raise ValueError("levels: at least one elevation, all finite")
         return LEVELS, a, a.size
-    a = np.asarray(_host(edges), dtype=np.float64).reshape(-1)
+    a = np.asarray(host(edges), dtype=np.float64).reshape(-1)
     if a.size < 2 or not np.all(np.isfinite(a)) or not np.all(np.diff(a) > 0.0):
         raise ValueError("edges: at least two finite, strictly increasing elevation edges are needed")
     return INTERVALS, a, a.size - 1
@@ -64,7 +61,7 @@ def regular_axis(surface, depth_edges, dz, top=None, bottom=None):
     if not (dz > 0.0 and np.isfinite(dz)):
         raise ValueError("dz must be positive and finite")
     if top is None or bottom is None:
-        s = np.asarray(_host(surface), dtype=np.float64).reshape(-1)
+        s = np.asarray(host(surface), dtype=np.float64).reshape(-1)
         s = s[np.isfinite(s)]
         if s.size == 0:
             raise ValueError("no finite surface elevation to span an axis over")
@@ -113,13 +110,11 @@ def resample(values, surface, depth_edges, levels=None, edges=None, columns=None
     if torch.is_tensor(surface) and surface.device == dev and surface.dtype == torch.float64:
         s = surface.reshape(-1).contiguous()
     else:
-        s = torch.as_tensor(np.ascontiguousarray(_host(surface), dtype=np.float64).reshape(-1)).to(dev)
+        s = torch.as_tensor(np.ascontiguousarray(host(surface), dtype=np.float64).reshape(-1)).to(dev)
     if s.numel() != N:
         raise ValueError("surface holds %d elevations for %d soundings" % (s.numel(), N))
     v = values.to(torch.float64).contiguous()
     out = torch.empty((N * K, c1 - c0), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        te, ta = torch.as_tensor(e).to(dev), torch.as_tensor(axis).to(dev)
-        _lib.check(_lib.load().gbp_elevation_resample(mode, N * K, K, n, v.data_ptr(), s.data_ptr(), te.data_ptr(), E, ta.data_ptr(), c0, c1,
-                                                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    te, ta = torch.as_tensor(e).to(dev), torch.as_tensor(axis).to(dev)
+    _lib.call("gbp_elevation_resample", dev, mode, N * K, K, n, v, s, te, E, ta, c0, c1, out)
     return out.reshape(N, K, c1 - c0) if values.dim() == 3 else out

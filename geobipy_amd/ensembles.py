@@ -37,15 +37,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import are_tensors, check_block, check_ensemble, on_device
 
 Ensemble = namedtuple("Ensemble", ("k", "edges", "sigma", "misfit", "count", "thin", "log_mean_prior"))
 Ensemble.__doc__ = """k int32 [B, n_keep] (0: empty slot), edges / sigma f64 [B, n_keep, K] (a slot's k - 1 interface depths then +inf,
 its k conductivities then NaN), misfit f64 [B, n_keep] (chi^2), count [B] (filled slots: they are the first ``count`` ones of a
 single chain), thin (every thin-th accumulated sample was kept), log_mean_prior f64 [B] (ln of the chain's prior mean conductivity)."""
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def from_chains(dc):
@@ -60,18 +57,13 @@ def from_chains(dc):
 
 
 def _check(ens, what):
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    for a in (k, edges, sigma):
+    for a in (ens.k, ens.edges, ens.sigma):
         if not torch.is_tensor(a) or a.device.type != "cuda":
             raise _lib.NativeLibraryError("ensembles.%s runs on the device (gbp_ensemble_%s); there is no host fallback" % (what[0], what[1]))
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
-        raise ValueError("ensemble: k [B, n_keep], edges and sigma [B, n_keep, K]")
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64:
-        raise TypeError("ensemble: k is int32, edges and sigma are float64")
-    B, ne, K = edges.shape
+    k, edges, sigma, B, ne, K = check_ensemble(ens, slots="n_keep")
     if not 1 <= ne <= 4096 or not 1 <= K <= 64:
         raise ValueError("ensemble: n_keep must be in [1, 4096] and K in [1, 64]")
-    return k.contiguous(), edges.contiguous(), sigma.contiguous(), B, ne, K
+    return k, edges, sigma, B, ne, K
 
 
 def centres(depth_edges):
@@ -106,9 +98,7 @@ def realisations(ens, depth_edges, slots=None, log10=True):
     out = torch.empty((B, s_np.size, z_np.size), dtype=torch.float64, device=dev)
     if B > 0:
         z, s = torch.as_tensor(z_np).to(dev), torch.as_tensor(s_np).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_ensemble_raster(B, ne, K, k.data_ptr(), edges.data_ptr(), sigma.data_ptr(), int(s_np.size), s.data_ptr(),
-                                                       int(z_np.size), z.data_ptr(), out.data_ptr(), _stream(dev)))
+        _lib.call("gbp_ensemble_raster", dev, B, ne, K, k, edges, sigma, int(s_np.size), s, int(z_np.size), z, out)
     return torch.log10(out) if log10 else out
 
 
@@ -191,12 +181,9 @@ def rebin(ens, n_value_bins, value_half_width, depth, units=None, unit_kinds=("a
     hm = i32(B, nv, nd) if hitmap else None
     uz = torch.as_tensor(z, dtype=torch.float64).to(dev).contiguous() if M else None
     uh, fh, fn = (i32(B, Q, nv, M) if M else None), (i32(B, T, nd) if T else None), (i32(B, T) if T else None)
-    ptr = lambda a: None if a is None else a.data_ptr()      # noqa: E731
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_ensemble_rebin(B, ne, K, k.data_ptr(), edges.data_ptr(), sigma.data_ptr(), lmp.data_ptr(), nv, hw, nd, width,
-                                                      ptr(hm), M, bits, ptr(uz), ptr(uh), T, (ctypes.c_double * 4)(*(list(th) + [1.0] * (4 - T))),
-                                                      (ctypes.c_int32 * 4)(*([int(d) for d in di] + [1] * (4 - T))), ptr(fh), ptr(fn), _stream(dev)))
+        _lib.call("gbp_ensemble_rebin", dev, B, ne, K, k, edges, sigma, lmp, nv, hw, nd, width, hm, M, bits, uz, uh, T,
+                  (ctypes.c_double * 4)(*(list(th) + [1.0] * (4 - T))), (ctypes.c_int32 * 4)(*([int(d) for d in di] + [1] * (4 - T))), fh, fn)
     for name, a in (("hitmap", hm), ("unit_z", uz), ("unit_hist", uh), ("first_hist", fh), ("first_none", fn)):
         if a is not None:
             out[name] = a
@@ -321,19 +308,6 @@ def segments(count_per_chain, slots_per_chain):
     return start, (2 * n_used).astype(np.int32), N, n_used
 
 
-def _on_device(tensors, what, entry):
-    """The last check of an entry: shapes, dtypes and values are refused first, whatever device the tensors are on."""
-    for a in tensors:
-        if a.device.type != "cuda":
-            raise _lib.NativeLibraryError("ensembles.%s runs on the device (%s); there is no host fallback" % (what, entry))
-
-
-def _are_tensors(tensors, what, entry):
-    for a in tensors:
-        if not torch.is_tensor(a):
-            raise _lib.NativeLibraryError("ensembles.%s takes torch tensors on the device (%s); there is no host fallback" % (what, entry))
-
-
 def _check_segments(seg_start, seg_m, seg_n, B, n_rows, what):
     """dtype, shapes and values of a caller's segment lists (the kernel reads seg_start[b, :seg_m[b]] and the rows they name: these
     checks are what keeps it inside its arrays); any device."""
@@ -357,7 +331,7 @@ def _check_series(x, seg_start, seg_m, seg_n, what, entry, check_v=lambda V: Non
     """The checks ``series_diagnostics`` and ``series_correlation`` share, in their order: tensors, x, ``check_v(V)`` (the entry's own
     check that needs V), the segment lists, and the device last.  Returns x and the lists, contiguous, and what ``check_v`` gave.
     ``ranked``: the columns are ranked too (``series_ranks``): at most 16 384 rows, and segments that do not overlap."""
-    _are_tensors((x, seg_start, seg_m, seg_n), what, entry)
+    are_tensors((x, seg_start, seg_m, seg_n), "ensembles", what, entry)
     if x.dtype != torch.float64:
         raise TypeError("%s: x is float64" % what)
     if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[1] > 32768:
@@ -368,13 +342,8 @@ def _check_series(x, seg_start, seg_m, seg_n, what, entry, check_v=lambda V: Non
     seg_start, seg_m, seg_n = _check_segments(seg_start, seg_m, seg_n, x.shape[0], x.shape[1], what)
     if ranked and seg_m.numel() and bool((seg_m.to(torch.int64) * seg_n.to(torch.int64) > x.shape[1]).any()):
         raise ValueError("%s: the segments overlap (seg_m * seg_n > n_rows)" % what)
-    _on_device((x, seg_start, seg_m, seg_n), what, entry)
+    on_device((x, seg_start, seg_m, seg_n), "ensembles", what, entry)
     return x.contiguous(), seg_start, seg_m, seg_n, own
-
-
-def _check_block(block, what):
-    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
-        raise ValueError("%s: block must be a positive integer" % what)
 
 
 def _unpack(stats, pairs, rho, seg_n, max_lag):
@@ -400,10 +369,7 @@ def series_diagnostics(x, seg_start, seg_m, seg_n, max_lag=255, return_rho=False
     pairs = torch.empty((B, V), dtype=torch.int32, device=dev)
     rho = torch.empty((B, max_lag + 1, V), dtype=torch.float64, device=dev) if return_rho else None
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_series_diagnostics(B, n_rows, V, x.data_ptr(), int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(),
-                                                          seg_n.data_ptr(), max_lag, stats.data_ptr(), pairs.data_ptr(),
-                                                          None if rho is None else rho.data_ptr(), _stream(dev)))
+        _lib.call("gbp_series_diagnostics", dev, B, n_rows, V, x, int(seg_start.shape[1]), seg_start, seg_m, seg_n, max_lag, stats, pairs, rho)
     return _unpack(stats, pairs, rho, seg_n, max_lag)
 
 
@@ -420,19 +386,14 @@ def _check_chained(ens, chains, what, entry, misfit):
     """What ``diagnostics`` and ``correlation`` ask of an ensemble whose slot axis holds ``chains`` chains (``misfit``: it takes part),
     refused in this order: tensors, shapes, dtypes, sizes, and the device last.  Returns k, edges, sigma (contiguous), B, n_slots, K,
     C, the lists of ``segments`` for the chains' filled slots on the device (seg_start, seg_m, seg_n) and n_chains_used."""
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    tensors = (k, edges, sigma, ens.misfit) if misfit else (k, edges, sigma)
-    _are_tensors(tensors, what, entry)
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape) or (misfit and ens.misfit.shape != k.shape):
-        raise ValueError("ensemble: %s [B, n_slots], edges and sigma [B, n_slots, K]" % ("k and misfit" if misfit else "k"))
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or (misfit and not ens.misfit.dtype.is_floating_point):
-        raise TypeError("ensemble: k is int32, edges and sigma are float64" + (", misfit is floating point" if misfit else ""))
-    B, ns, K = edges.shape
+    tensors = (ens.k, ens.edges, ens.sigma, ens.misfit) if misfit else (ens.k, ens.edges, ens.sigma)
+    are_tensors(tensors, "ensembles", what, entry)
+    k, edges, sigma, B, ns, K = check_ensemble(ens, misfit=misfit)
     C = check_chains(chains, ns)
     if not 1 <= ns <= 4096 * C or not 1 <= K <= 64:
         raise ValueError("ensemble: at most 4096 slots per chain and K in [1, 64]")
-    _on_device(tensors, what, entry)
-    k, edges, sigma, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), k.device
+    on_device(tensors, "ensembles", what, entry)
+    dev = k.device
     count = (k.reshape(B, C, ns // C) > 0).sum(dim=2).cpu().numpy()
     start, seg_m, seg_n, used = (torch.as_tensor(a).to(dev) for a in segments(count, ns // C))
     return k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used
@@ -451,7 +412,7 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
     if torch.is_tensor(ens.k) and ens.k.ndim == 2:
         check_chains(chains, ens.k.shape[1])
     z_np = centres(depth_edges)
-    _check_block(block, "diagnostics")
+    check_block(block, "diagnostics")
     k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "diagnostics", "gbp_ensemble_diagnostics", misfit=True)
     nd, dev = int(z_np.size), k.device
     stats = torch.empty((B, 6, nd), dtype=torch.float64, device=dev)
@@ -460,14 +421,10 @@ def diagnostics(ens, depth_edges, chains=1, max_lag=None, block=None, return_rho
     if B > 0:
         z = torch.as_tensor(z_np).to(dev)
         step = B if block is None else int(block)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            for b0 in range(0, B, step):
-                s = slice(b0, min(B, b0 + step))
-                _lib.check(lib.gbp_ensemble_diagnostics(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
-                                                        z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), max_lag,
-                                                        stats[s].data_ptr(), pairs[s].data_ptr(), None if rho is None else rho[s].data_ptr(),
-                                                        _stream(dev)))
+        for b0 in range(0, B, step):
+            s = slice(b0, min(B, b0 + step))
+            _lib.call("gbp_ensemble_diagnostics", dev, s.stop - s.start, ns, K, k[s], edges[s], sigma[s], nd, z, 2 * C, start[s], seg_m[s], seg_n[s],
+                      max_lag, stats[s], pairs[s], None if rho is None else rho[s])
     out = _unpack(stats, pairs, rho, seg_n, max_lag)
     scalars = torch.stack((k.to(torch.float64), torch.log10(ens.misfit.to(torch.float64))), dim=2)
     two = series_diagnostics(scalars, start, seg_m, seg_n, max_lag=max_lag)
@@ -653,12 +610,10 @@ def _launch_ranks(entry, head, B, n_rows, V, dev, seg_start, seg_m, seg_n, fold,
         out["order"] = torch.empty((B, p.size, 2, V), dtype=torch.float64, device=dev)
     if values:
         out["x_out"] = torch.empty((B, n_rows, V), dtype=torch.float64, device=dev)
-    ptr = lambda name: out[name].data_ptr() if name in out and out[name].numel() else None      # noqa: E731
+    given = lambda name: out[name] if name in out and out[name].numel() else None      # noqa: E731
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(getattr(_lib.load(), entry)(*head, int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(), seg_n.data_ptr(),
-                                                   int(bool(fold)), int(p.size), (ctypes.c_double * max(int(p.size), 1))(*p), ptr("less"),
-                                                   ptr("leq"), ptr("order"), ptr("x_out"), _stream(dev)))
+        _lib.call(entry, dev, *head, int(seg_start.shape[1]), seg_start, seg_m, seg_n, int(bool(fold)), int(p.size),
+                  (ctypes.c_double * max(int(p.size), 1))(*p), given("less"), given("leq"), given("order"), given("x_out"))
     return out
 
 
@@ -670,7 +625,7 @@ def series_ranks(x, seg_start, seg_m, seg_n, fold=False, probabilities=None, cou
     p = check_probabilities(probabilities)
     x, seg_start, seg_m, seg_n, _ = _check_series(x, seg_start, seg_m, seg_n, "series_ranks", "gbp_series_ranks", ranked=True)
     B, n_rows, V = x.shape
-    return _launch_ranks("gbp_series_ranks", (B, n_rows, V, x.data_ptr()), B, n_rows, V, x.device, seg_start, seg_m, seg_n, fold, p, counts,
+    return _launch_ranks("gbp_series_ranks", (B, n_rows, V, x), B, n_rows, V, x.device, seg_start, seg_m, seg_n, fold, p, counts,
                          p.size > 0, values)
 
 
@@ -702,7 +657,7 @@ def series_rank_diagnostics(x, seg_start, seg_m, seg_n, max_lag=255, percentiles
     qs = check_percentiles(percentiles)
     x, seg_start, seg_m, seg_n, _ = _check_series(x, seg_start, seg_m, seg_n, "series_rank_diagnostics", "gbp_series_ranks", ranked=True)
     B, n_rows, V = x.shape
-    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, n_rows, V, x.data_ptr()), B, n_rows, V, x.device, seg_start, seg_m, seg_n,      # noqa: E731
+    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, n_rows, V, x), B, n_rows, V, x.device, seg_start, seg_m, seg_n,      # noqa: E731
                                            fold, p, True, p.size > 0, False)
     return _rank_products(ranker, seg_start, seg_m, seg_n, max_lag, qs)
 
@@ -715,7 +670,7 @@ def _check_slots(ens, what):
 def _ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s):
     """``ranker(fold, p, counts=True, values=False)`` of soundings ``s`` (a slice) through gbp_ensemble_ranks."""
     n = s.stop - s.start
-    head = (n, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd, z.data_ptr())
+    head = (n, ns, K, k[s], edges[s], sigma[s], nd, z)
     return lambda fold, p, counts=True, values=False: _launch_ranks("gbp_ensemble_ranks", head, n, ns, nd, k.device, start[s], seg_m[s], seg_n[s],
                                                                     fold, p, counts, p.size > 0, values)
 
@@ -756,7 +711,7 @@ def rank_diagnostics(ens, depth_edges, chains=1, max_lag=None, percentiles=(5, 5
     if torch.is_tensor(ens.k) and ens.k.ndim == 2:
         check_chains(chains, ens.k.shape[1])
     z_np = centres(depth_edges)
-    _check_block(block, "rank_diagnostics")
+    check_block(block, "rank_diagnostics")
     k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "rank_diagnostics", "gbp_ensemble_ranks", misfit=True)
     nd, dev = int(z_np.size), k.device
     z = torch.as_tensor(z_np).to(dev)
@@ -769,7 +724,7 @@ def rank_diagnostics(ens, depth_edges, chains=1, max_lag=None, percentiles=(5, 5
         parts.append(_rank_products(_ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, slice(0, 0)), start, seg_m, seg_n, max_lag, qs))
     out = {name: torch.cat([q[name] for q in parts]) for name in parts[0]}
     scalars = torch.stack((k.to(torch.float64), torch.log10(ens.misfit.to(torch.float64))), dim=2).contiguous()
-    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, ns, 2, scalars.data_ptr()), B, ns, 2, dev, start, seg_m, seg_n, fold, p, True,      # noqa: E731
+    ranker = lambda fold, p: _launch_ranks("gbp_series_ranks", (B, ns, 2, scalars), B, ns, 2, dev, start, seg_m, seg_n, fold, p, True,      # noqa: E731
                                            p.size > 0, False)
     two = _rank_products(ranker, start, seg_m, seg_n, max_lag, qs)
     for name in list(two):
@@ -790,7 +745,7 @@ def quantiles(ens, depth_edges, percentiles, chains=1, block=None):
     if torch.is_tensor(ens.k) and ens.k.ndim == 2:
         check_chains(chains, ens.k.shape[1])
     z_np = centres(depth_edges)
-    _check_block(block, "quantiles")
+    check_block(block, "quantiles")
     k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "quantiles", "gbp_ensemble_ranks", misfit=False)
     nd, dev = int(z_np.size), k.device
     z = torch.as_tensor(z_np).to(dev)
@@ -958,16 +913,14 @@ def series_correlation(x, seg_start, seg_m, seg_n, band=None, normalise=True, ra
     stats = torch.empty((B, 2, V), dtype=torch.float64, device=dev)
     out = torch.empty((B, V, W + 1), dtype=torch.float64, device=dev)
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_series_correlation(B, n_rows, V, x.data_ptr(), int(seg_start.shape[1]), seg_start.data_ptr(), seg_m.data_ptr(),
-                                                          seg_n.data_ptr(), W, int(bool(normalise)), stats.data_ptr(), out.data_ptr(), _stream(dev)))
+        _lib.call("gbp_series_correlation", dev, B, n_rows, V, x, int(seg_start.shape[1]), seg_start, seg_m, seg_n, W, int(bool(normalise)), stats, out)
     return dict(mean=stats[:, 0], sd=stats[:, 1], band=out)
 
 
 def correlation_runs(band, threshold):
     """``correlation_runs_reference`` on a device band f64 [B, V, W + 1] (gbp_band_runs): {up, down int32 [B, V], closed_up,
     closed_down bool [B, V]}.  ``threshold``: any number that is not NaN."""
-    _are_tensors((band,), "correlation_runs", "gbp_band_runs")
+    are_tensors((band,), "ensembles", "correlation_runs", "gbp_band_runs")
     if band.dtype != torch.float64:
         raise TypeError("correlation_runs: band is float64")
     if band.ndim != 3 or not 1 <= band.shape[2] <= band.shape[1]:
@@ -975,14 +928,13 @@ def correlation_runs(band, threshold):
     threshold = float(threshold)
     if threshold != threshold:
         raise ValueError("correlation_runs: threshold is NaN")
-    _on_device((band,), "correlation_runs", "gbp_band_runs")
+    on_device((band,), "ensembles", "correlation_runs", "gbp_band_runs")
     band, dev = band.contiguous(), band.device
     B, V, W1 = band.shape
     up, down = (torch.empty((B, V), dtype=torch.int32, device=dev) for _ in range(2))
     closed = torch.empty((B, 2, V), dtype=torch.uint8, device=dev)
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_band_runs(B, V, W1 - 1, band.data_ptr(), threshold, up.data_ptr(), down.data_ptr(), closed.data_ptr(), _stream(dev)))
+        _lib.call("gbp_band_runs", dev, B, V, W1 - 1, band, threshold, up, down, closed)
     return dict(up=up, down=down, closed_up=closed[:, 0].bool(), closed_down=closed[:, 1].bool())
 
 
@@ -1011,7 +963,7 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     nd = int(z_np.size)
     W = check_band(band, nd)
     threshold = check_threshold(threshold)
-    _check_block(block, "correlation")
+    check_block(block, "correlation")
     k, edges, sigma, B, ns, K, C, start, seg_m, seg_n, used = _check_chained(ens, chains, "correlation", "gbp_ensemble_correlation", misfit=False)
     dev = k.device
     step = max(1, BAND_BLOCK_BYTES // (nd * (W + 1) * 8)) if block is None else int(block)
@@ -1024,27 +976,22 @@ def correlation(ens, depth_edges, chains=1, band=64, threshold=0.5, normalise=Tr
     live = torch.empty((B, nd), dtype=torch.bool, device=dev)
     if B > 0:
         z = torch.as_tensor(z_np).to(dev)
-        lib = _lib.load()
         work = None if keep_band else torch.empty((min(step, B), nd, W + 1), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            for b0 in range(0, B, step):
-                s = slice(b0, min(B, b0 + step))
-                part = full[s] if keep_band else work[:s.stop - s.start]
-                if rank:
-                    r = _ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s)(False, np.zeros(0))
-                    mid = midranks(r["less"], r["leq"])
-                    del r
-                    _lib.check(lib.gbp_series_correlation(s.stop - s.start, ns, nd, mid.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(),
-                                                          seg_n[s].data_ptr(), W, int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(),
-                                                          _stream(dev)))
-                    del mid
-                else:
-                    _lib.check(lib.gbp_ensemble_correlation(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), nd,
-                                                            z.data_ptr(), 2 * C, start[s].data_ptr(), seg_m[s].data_ptr(), seg_n[s].data_ptr(), W,
-                                                            int(bool(normalise)), stats[s].data_ptr(), part.data_ptr(), _stream(dev)))
-                _lib.check(lib.gbp_band_runs(s.stop - s.start, nd, W, part.data_ptr(), threshold, up[s].data_ptr(), down[s].data_ptr(),
-                                             closed[s].data_ptr(), _stream(dev)))
-                live[s] = ~torch.isnan(part[:, :, 0])
+        for b0 in range(0, B, step):
+            s = slice(b0, min(B, b0 + step))
+            part = full[s] if keep_band else work[:s.stop - s.start]
+            if rank:
+                r = _ensemble_ranker(k, edges, sigma, ns, K, C, z, nd, start, seg_m, seg_n, s)(False, np.zeros(0))
+                mid = midranks(r["less"], r["leq"])
+                del r
+                _lib.call("gbp_series_correlation", dev, s.stop - s.start, ns, nd, mid, 2 * C, start[s], seg_m[s], seg_n[s], W, int(bool(normalise)),
+                          stats[s], part)
+                del mid
+            else:
+                _lib.call("gbp_ensemble_correlation", dev, s.stop - s.start, ns, K, k[s], edges[s], sigma[s], nd, z, 2 * C, start[s], seg_m[s], seg_n[s],
+                          W, int(bool(normalise)), stats[s], part)
+            _lib.call("gbp_band_runs", dev, s.stop - s.start, nd, W, part, threshold, up[s], down[s], closed[s])
+            live[s] = ~torch.isnan(part[:, :, 0])
     out = dict(mean=stats[:, 0], sd=stats[:, 1], up=up, down=down, closed_up=closed[:, 0].bool(), closed_down=closed[:, 1].bool())
     if keep_band:
         out["band"] = full

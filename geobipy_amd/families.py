@@ -22,15 +22,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import are_tensors, check_block, check_ensemble, check_int, on_device
 from .ensembles import MIN_CHAIN_COUNT, check_chains, segments  # noqa: F401  (MIN_CHAIN_COUNT: the rule ``used_rows`` shares)
 
 MEASURES = ("linear", "log")
 MAX_MODELS, MAX_FAMILIES, MAX_K = 4096, 8, 64
 DISTANCE_BLOCK_BYTES = 2 << 30
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def check_window(z0, z1, measure):
@@ -46,12 +43,6 @@ def check_window(z0, z1, measure):
     if measure == "log" and z0 == 0.0:
         raise ValueError("the log measure needs z0 > 0")
     return z0, z1, MEASURES.index(measure)
-
-
-def _check_int(value, lo, hi, what):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
-        raise ValueError("%s must be an integer in %d .. %d" % (what, lo, hi))
-    return int(value)
 
 
 # ---- the rules ------------------------------------------------------------------------------------------------------------------------
@@ -124,7 +115,7 @@ def families_reference(D, n_used, q_max, max_iter):
     if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
         raise ValueError("families_reference: D [n, n]")
     n = D.shape[0]
-    Q, max_iter = _check_int(q_max, 1, MAX_FAMILIES, "q_max"), _check_int(max_iter, 0, 2 ** 31 - 1, "max_iter")
+    Q, max_iter = check_int(q_max, 1, MAX_FAMILIES, "q_max"), check_int(max_iter, 0, 2 ** 31 - 1, "max_iter")
     out = dict(medoid=np.full((Q, Q), -1, dtype=np.int32), label=np.full((Q, n), -1, dtype=np.int32), nearest=np.full((Q, n), np.nan),
                second=np.full((Q, n), np.nan), iterations=np.zeros(Q, dtype=np.int32), converged=np.zeros(Q, dtype=np.uint8), n_found=np.int32(0))
     m = min(max(int(n_used), 0), n)
@@ -183,7 +174,7 @@ def used_rows(ens, chains=1, max_models=1024):
     if kn.ndim != 2 or kn.shape[1] < 1 or kn.dtype.kind not in "iu":
         raise ValueError("used_rows: k is an integer array [B, n_slots]")
     C = check_chains(chains, kn.shape[1])
-    max_models = _check_int(max_models, 1, MAX_MODELS, "max_models")
+    max_models = check_int(max_models, 1, MAX_MODELS, "max_models")
     B, per = kn.shape[0], kn.shape[1] // C
     count = (kn.reshape(B, C, per) > 0).sum(axis=2)
     start, seg_m, seg_n, _ = segments(count, per)
@@ -205,57 +196,30 @@ def used_rows(ens, chains=1, max_models=1024):
 
 # ---- the entries ---------------------------------------------------------------------------------------------------------------------
 
-def _are_tensors(tensors, what, entry):
-    for a in tensors:
-        if not torch.is_tensor(a):
-            raise _lib.NativeLibraryError("families.%s takes torch tensors on the device (%s); there is no host fallback" % (what, entry))
-
-
-def _on_device(tensors, what, entry):
-    """The last check of an entry: shapes, dtypes and values are refused first, whatever device the tensors are on."""
-    for a in tensors:
-        if a.device.type != "cuda":
-            raise _lib.NativeLibraryError("families.%s runs on the device (%s); there is no host fallback" % (what, entry))
-
-
-def _check_block(block, what):
-    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) < 1):
-        raise ValueError("%s: block must be a positive integer" % what)
-
-
 def distance(ens, rows, z0, z1, measure="linear", squared=False, block=None, log10=True):
     """D f64 [B, n, n] on the device: the distance (``distance_reference`` states the rule; ``squared``: D^2) between the models
     ``rows`` int32 [B, n] (slot indices; a row outside the slots or an empty slot is absent: NaN) of every sounding of the ensemble over
     the window [z0, z1] with ``measure`` "linear" or "log".  ``log10=False``: the stored values as they are.  ``block``: soundings per
     launch (None: as many as keep a launch's output under 2 GiB).  One kernel (gbp_ensemble_distance)."""
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma, rows), "distance", "gbp_ensemble_distance")
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
-        raise ValueError("ensemble: k [B, n_slots], edges and sigma [B, n_slots, K]")
-    if rows.ndim != 2 or rows.shape[0] != k.shape[0] or not 1 <= rows.shape[1] <= MAX_MODELS:
-        raise ValueError("distance: rows [B, n] with 1 <= n <= %d" % MAX_MODELS)
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or rows.dtype != torch.int32:
-        raise TypeError("ensemble: k is int32, edges and sigma are float64; rows is int32")
-    B, ns, K = edges.shape
+    entry = "gbp_ensemble_distance"
+    are_tensors((ens.k, ens.edges, ens.sigma, rows), "families", "distance", entry)
+    k, edges, sigma, B, ns, K = check_ensemble(ens, rows=rows, what="distance", max_rows=MAX_MODELS)
     if ns < 1 or not 1 <= K <= MAX_K:
         raise ValueError("ensemble: at least one slot and K in [1, %d]" % MAX_K)
     z0, z1, log = check_window(z0, z1, measure)
-    _check_block(block, "distance")
-    _on_device((k, edges, sigma, rows), "distance", "gbp_ensemble_distance")
-    k, edges, sigma, rows, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), rows.contiguous(), k.device
+    check_block(block, "distance")
+    on_device((k, edges, sigma, rows), "families", "distance", entry)
+    rows, dev = rows.contiguous(), k.device
     n = rows.shape[1]
     out = torch.empty((B, n, n), dtype=torch.float64, device=dev)
     if B > 0:
         tiles = (n + 15) // 16
         most = (2 ** 32 - 1) // (256 * (tiles * (tiles + 1) // 2))         # soundings one launch can take: 256 threads per tile pair
         step = min(max(1, DISTANCE_BLOCK_BYTES // (n * n * 8)), most) if block is None else int(block)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            for b0 in range(0, B, step):
-                s = slice(b0, min(B, b0 + step))
-                _lib.check(lib.gbp_ensemble_distance(s.stop - s.start, ns, K, k[s].data_ptr(), edges[s].data_ptr(), sigma[s].data_ptr(), n,
-                                                     rows[s].data_ptr(), z0, z1, log, int(bool(log10)), int(bool(squared)), out[s].data_ptr(),
-                                                     _stream(dev)))
+        for b0 in range(0, B, step):
+            s = slice(b0, min(B, b0 + step))
+            _lib.call(entry, dev, s.stop - s.start, ns, K, k[s], edges[s], sigma[s], n, rows[s], z0, z1, log, int(bool(log10)), int(bool(squared)),
+                      out[s])
     return out
 
 
@@ -285,13 +249,13 @@ def cluster(dist, n_used, max_families=4, max_iter=100):
     first ``n_used`` int32 [B] models of every sounding (``families_reference`` states the rule).  Returns {medoid int32 [B, Q, Q], label
     int32 [B, Q, n], nearest, second f64 [B, Q, n], iterations int32 [B, Q], converged bool [B, Q], n_found int32 [B]} from one kernel
     (gbp_distance_families), and cost, silhouette f64 [B, Q], share f64 [B, Q, Q] (``summaries``)."""
-    _are_tensors((dist, n_used), "cluster", "gbp_distance_families")
+    are_tensors((dist, n_used), "families", "cluster", "gbp_distance_families")
     if dist.ndim != 3 or dist.shape[1] != dist.shape[2] or not 1 <= dist.shape[1] <= MAX_MODELS or n_used.shape != (dist.shape[0],):
         raise ValueError("cluster: dist [B, n, n] with 1 <= n <= %d and n_used [B]" % MAX_MODELS)
     if dist.dtype != torch.float64 or n_used.dtype != torch.int32:
         raise TypeError("cluster: dist is float64 and n_used is int32")
-    Q, max_iter = _check_int(max_families, 1, MAX_FAMILIES, "max_families"), _check_int(max_iter, 0, 2 ** 31 - 1, "max_iter")
-    _on_device((dist, n_used), "cluster", "gbp_distance_families")
+    Q, max_iter = check_int(max_families, 1, MAX_FAMILIES, "max_families"), check_int(max_iter, 0, 2 ** 31 - 1, "max_iter")
+    on_device((dist, n_used), "families", "cluster", "gbp_distance_families")
     dist, n_used, dev = dist.contiguous(), n_used.contiguous(), dist.device
     B, n = dist.shape[0], dist.shape[1]
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)       # noqa: E731  (the kernel writes every entry)
@@ -299,10 +263,8 @@ def cluster(dist, n_used, max_families=4, max_iter=100):
     out = dict(medoid=i32(B, Q, Q), label=i32(B, Q, n), nearest=f64(B, Q, n), second=f64(B, Q, n), iterations=i32(B, Q), n_found=i32(B))
     conv = torch.empty((B, Q), dtype=torch.uint8, device=dev)
     if B > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_distance_families(B, n, dist.data_ptr(), n_used.data_ptr(), Q, max_iter, out["medoid"].data_ptr(),
-                                                         out["label"].data_ptr(), out["nearest"].data_ptr(), out["second"].data_ptr(),
-                                                         out["iterations"].data_ptr(), conv.data_ptr(), out["n_found"].data_ptr(), _stream(dev)))
+        _lib.call("gbp_distance_families", dev, B, n, dist, n_used, Q, max_iter, out["medoid"], out["label"], out["nearest"], out["second"],
+                  out["iterations"], conv, out["n_found"])
     out["converged"] = conv.bool()
     out["cost"], out["silhouette"], out["share"] = summaries(out)
     return out
@@ -348,10 +310,10 @@ def families(ens, z1, z0=0.0, measure="linear", chains=1, max_families=4, max_mo
 
     ``keep_distance``: also ``distance`` f64 [B, n_max, n_max].  The medoid models are gathered with torch indexing."""
     z0, z1, _ = check_window(z0, z1, measure)
-    Q = _check_int(max_families, 1, MAX_FAMILIES, "max_families")
-    _check_block(block, "families")
+    Q = check_int(max_families, 1, MAX_FAMILIES, "max_families")
+    check_block(block, "families")
     k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma), "families", "gbp_ensemble_distance")
+    are_tensors((k, edges, sigma), "families", "families", "gbp_ensemble_distance")
     if k.ndim != 2:
         raise ValueError("ensemble: k [B, n_slots], edges and sigma [B, n_slots, K]")
     C = check_chains(chains, k.shape[1])
@@ -421,9 +383,9 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     try:
         check_window(a.z0, a.depth, a.measure)
-        _check_int(a.chains, 1, 8, "--chains")
-        _check_int(a.max_families, 1, MAX_FAMILIES, "--max-families")
-        _check_int(a.max_models, 1, MAX_MODELS, "--max-models")
+        check_int(a.chains, 1, 8, "--chains")
+        check_int(a.max_families, 1, MAX_FAMILIES, "--max-families")
+        check_int(a.max_models, 1, MAX_MODELS, "--max-models")
     except ValueError as e:
         p.error(str(e))
     return a.ensemble, dict(z1=a.depth, z0=a.z0, measure=a.measure, chains=a.chains, max_families=a.max_families, max_models=a.max_models), a.device

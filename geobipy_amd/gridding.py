@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import host
 
 
 def centred_grid_nodes(bounds, spacing):
@@ -65,10 +66,6 @@ def pixel_coordinates(x, y, x_edges, y_edges):
     return x, y, dx, dy
 
 
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def axis_offsets(log_mean_prior, half_width, n_value):
     """u [N] float64: the soundings' axis offsets in value cells, ``log10_shift(log_mean_prior) / w`` with w = 2 half_width / n_value,
     computed once by numpy on the host so that the device only subtracts and rounds."""
@@ -94,7 +91,7 @@ def _pool_arguments(plan, maps, pixels, log_mean_prior, half_width, max_total, o
     if pixels is None:
         pix = np.arange(P, dtype=np.int64)
     else:
-        pix = _host(pixels)
+        pix = host(pixels)
         if pix.dtype.kind not in "iu" or pix.ndim != 1:
             raise TypeError("gbp_sibson_pool: pixels are a list [P] of integers (flat pixel numbers), got %s %r" % (pix.dtype, pix.shape))
         pix = pix.astype(np.int64)
@@ -105,7 +102,7 @@ def _pool_arguments(plan, maps, pixels, log_mean_prior, half_width, max_total, o
         raise ValueError("gbp_sibson_pool: log_mean_prior and half_width come together")
     u = lmp = None
     if log_mean_prior is not None:
-        lmp = np.array(_host(log_mean_prior), dtype=np.float64)
+        lmp = np.array(host(log_mean_prior), dtype=np.float64)
         if lmp.shape != (N,) or not np.all(np.isfinite(lmp)):
             raise ValueError("gbp_sibson_pool: log_mean_prior must hold %d finite values" % N)
         if not (np.isfinite(float(half_width)) and float(half_width) > 0.0):
@@ -136,13 +133,13 @@ class SibsonPlan:
             raise _lib.NativeLibraryError("SibsonPlan runs on the device (gbp_sibson_plan_create); there is no host fallback")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        px, py, dx, dy = pixel_coordinates(_host(x), _host(y), _host(x_edges), _host(y_edges))
+        px, py, dx, dy = pixel_coordinates(host(x), host(y), host(x_edges), host(y_edges))
         if not np.all(np.isfinite(px)) or not np.all(np.isfinite(py)):
             raise ValueError("the soundings' coordinates must be finite")
         md = float("inf") if not max_distance else float(max_distance)
         if not md > 0.0:
             raise ValueError("max_distance must be positive (None for no mask)")
-        self.x_edges, self.y_edges = np.asarray(_host(x_edges), dtype=np.float64), np.asarray(_host(y_edges), dtype=np.float64)
+        self.x_edges, self.y_edges = np.asarray(host(x_edges), dtype=np.float64), np.asarray(host(y_edges), dtype=np.float64)
         self.nx, self.ny, self.n_soundings = self.x_edges.size - 1, self.y_edges.size - 1, px.size
         self.max_distance_px2 = md / (dx * dy)
         self.device = dev
@@ -151,14 +148,12 @@ class SibsonPlan:
         with torch.cuda.device(dev):
             tpx, tpy = torch.as_tensor(px).to(dev), torch.as_tensor(py).to(dev)
             _lib.check(lib.gbp_sibson_plan_create_ex(px.size, tpx.data_ptr(), tpy.data_ptr(), self.nx, self.ny, self.max_distance_px2,
-                                                     int(list_budget_bytes), torch.cuda.current_stream(dev).cuda_stream,
-                                                     ctypes.byref(self._handle)))
-            self.index = torch.empty((self.ny, self.nx), dtype=torch.int32, device=dev)
-            self.distance = torch.empty_like(self.index)
-            self.count = torch.empty_like(self.index)
-            info = (ctypes.c_int64 * 4)()
-            _lib.check(lib.gbp_sibson_plan_query(self._handle, self.index.data_ptr(), self.distance.data_ptr(), self.count.data_ptr(), info,
-                                                 torch.cuda.current_stream(dev).cuda_stream))
+                                                     int(list_budget_bytes), _lib.stream(dev), ctypes.byref(self._handle)))
+        self.index = torch.empty((self.ny, self.nx), dtype=torch.int32, device=dev)
+        self.distance = torch.empty_like(self.index)
+        self.count = torch.empty_like(self.index)
+        info = (ctypes.c_int64 * 4)()
+        _lib.call("gbp_sibson_plan_query", dev, self._handle, self.index, self.distance, self.count, info)
         self.list_length, self.longest_list, self.n_bands, self.bytes_held = (int(v) for v in info)
 
     def apply(self, values):
@@ -177,9 +172,7 @@ class SibsonPlan:
         if C < 1:
             raise ValueError("values hold no column")
         out = torch.empty((C, self.ny, self.nx), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gbp_sibson_apply(self._handle, C, v.data_ptr(), out.data_ptr(),
-                                                    torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.call("gbp_sibson_apply", self.device, self._handle, C, v, out)
         return out[0] if values.dim() == 1 else out
 
     def pool(self, maps, pixels=None, log_mean_prior=None, half_width=None, max_total=None, out=None):
@@ -213,9 +206,7 @@ class SibsonPlan:
                 clipped = torch.empty((P, nz), dtype=torch.int64, device=dev)
             else:
                 pooled, clipped = out["pooled"][:P], out["clipped"][:P]
-            _lib.check(_lib.load().gbp_sibson_pool(self._handle, P, pix_d.data_ptr(), nv, nz, maps.data_ptr(),
-                                                   None if u_d is None else u_d.data_ptr(), int(max_total), pooled.data_ptr(),
-                                                   clipped.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call("gbp_sibson_pool", dev, self._handle, P, pix_d, nv, nz, maps, u_d, int(max_total), pooled, clipped)
             where = pix_d.long()
             near = self.index.reshape(-1)[where].long()
             d = self.distance.reshape(-1)[where].to(torch.float64)

@@ -13,16 +13,12 @@ from . import _lib
 from .line_products import entropy_bits, log10_shift, quantiles, value_centres
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _entry(hm, name):
-    """The C entry ``name`` for int32 maps, ``name``_i64 for int64 ones; other count types are refused."""
+    """The name of the C entry: ``name`` for int32 maps, ``name``_i64 for int64 ones; other count types are refused."""
     if hm.dtype == torch.int32:
-        return getattr(_lib.load(), name)
+        return name
     if hm.dtype == torch.int64:
-        return getattr(_lib.load(), name + "_i64")
+        return name + "_i64"
     raise TypeError("hit maps are int32 (or int64 interval marginals), not %s" % hm.dtype)
 
 
@@ -37,9 +33,7 @@ def statistics(hitmap, log_mean_prior, half_width):
     assert hm.dtype == torch.int32
     lmp = log_mean_prior.to(torch.float64).contiguous()
     out = torch.empty((4, B, nz), dtype=torch.float64, device=hm.device)
-    with torch.cuda.device(hm.device):
-        _lib.check(_lib.load().gbp_hitmap_statistics(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), out[0].data_ptr(), out[1].data_ptr(),
-                                                     out[2].data_ptr(), out[3].data_ptr(), _stream(hm.device)))
+    _lib.call("gbp_hitmap_statistics", hm.device, B, nv, nz, hm, lmp, float(half_width), out[0], out[1], out[2], out[3])
     return out[0], [out[1], out[2], out[3]]
 
 
@@ -52,17 +46,15 @@ def runs(hitmap):
     assert hm.dtype == torch.int32
     B, M = hm.shape
     dev = hm.device
-    lib = _lib.load()
     ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
     if B == 0:
         return ptr, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.gbp_hitmap_runs(B, M, hm.data_ptr(), ptr[1:].data_ptr(), None, None, None, _stream(dev)))
-        torch.cumsum(ptr[1:], 0, out=ptr[1:])
-        n = int(ptr[-1])
-        start = torch.empty(n, dtype=torch.int32, device=dev)
-        value = torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.check(lib.gbp_hitmap_runs(B, M, hm.data_ptr(), None, ptr.data_ptr(), start.data_ptr(), value.data_ptr(), _stream(dev)))
+    _lib.call("gbp_hitmap_runs", dev, B, M, hm, ptr[1:], None, None, None)
+    torch.cumsum(ptr[1:], 0, out=ptr[1:])
+    n = int(ptr[-1])
+    start = torch.empty(n, dtype=torch.int32, device=dev)
+    value = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.call("gbp_hitmap_runs", dev, B, M, hm, None, ptr, start, value)
     return ptr, start, value
 
 
@@ -83,9 +75,7 @@ def moments(hitmap, log_mean_prior, half_width, q):
     total = torch.empty((B, nz), dtype=torch.int64, device=dev)
     mode_idx = torch.empty((B, nz), dtype=torch.int32, device=dev)
     q_idx = torch.empty((len(q), B, nz), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(entry(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), len(q), qa, mean.data_ptr(), mode_idx.data_ptr(),
-                         q_idx.data_ptr(), total.data_ptr(), s1.data_ptr(), _stream(dev)))
+    _lib.call(entry, dev, B, nv, nz, hm, lmp, float(half_width), len(q), qa, mean, mode_idx, q_idx, total, s1)
     return dict(mean=mean, mode_idx=mode_idx, q_idx=q_idx, total=total, s1=s1)
 
 
@@ -141,9 +131,7 @@ def class_probability(hitmap, log_mean_prior, half_width, means, scales):
     prob = torch.empty((B, K, nz), dtype=torch.float64, device=dev)
     best = torch.empty((B, nz), dtype=torch.int32, device=dev)
     best_p = torch.empty((B, nz), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(entry(B, nv, nz, hm.data_ptr(), lmp.data_ptr(), float(half_width), K, ma, sa, prob.data_ptr(), best.data_ptr(),
-                         best_p.data_ptr(), _stream(dev)))
+    _lib.call(entry, dev, B, nv, nz, hm, lmp, float(half_width), K, ma, sa, prob, best, best_p)
     return dict(probability=prob, highest_marginal=best, probability_of_highest_marginal=best_p)
 
 
@@ -177,9 +165,7 @@ def interval_marginals(hitmap, lo, hi):
         raise ValueError("lo and hi differ in shape: %r, %r" % (tuple(lo_d.shape), tuple(hi_d.shape)))
     M = lo_d.shape[1]
     out = torch.empty((B, nv, M), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gbp_hitmap_intervals(B, nv, nz, M, hm.data_ptr(), lo_d.data_ptr(), hi_d.data_ptr(), out.data_ptr(),
-                                                    _stream(dev)))
+    _lib.call("gbp_hitmap_intervals", dev, B, nv, nz, M, hm, lo_d, hi_d, out)
     return out
 
 
@@ -215,9 +201,8 @@ def mixture(maps, half_width, max_components=3, n_iter=50, reg=None):
     S = K * (K + 1) // 2
     out = dict(weight=f64(B, S, nz), mean=f64(B, S, nz), sd=f64(B, S, nz), loglik=f64(B, K, nz), ll_change=f64(B, K, nz),
                misfit=f64(B, K, 2, nz))
-    with torch.cuda.device(dev):
-        _lib.check(entry(B, nv, nz, maps.data_ptr(), float(half_width), K, n, reg, out["weight"].data_ptr(), out["mean"].data_ptr(),
-                         out["sd"].data_ptr(), out["loglik"].data_ptr(), out["ll_change"].data_ptr(), out["misfit"].data_ptr(), _stream(dev)))
+    _lib.call(entry, dev, B, nv, nz, maps, float(half_width), K, n, reg, out["weight"], out["mean"], out["sd"], out["loglik"], out["ll_change"],
+              out["misfit"])
     return out
 
 
@@ -269,8 +254,6 @@ def pool(maps, C, use=None, half_width=1.0, max_total=None):
     out = dict(pooled=torch.empty((S, nv, nz), dtype=torch.int32, device=dev), n_used=torch.empty((S, nz), dtype=torch.int32, device=dev),
                chain_mean=torch.empty((S, C, nz), dtype=torch.float64, device=dev), rhat=torch.empty((S, nz), dtype=torch.float64, device=dev),
                jsd=torch.empty((S, nz), dtype=torch.float64, device=dev))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gbp_hitmap_pool(S, C, nv, nz, maps.data_ptr(), use.data_ptr(), float(half_width), out["pooled"].data_ptr(),
-                                               out["n_used"].data_ptr(), out["chain_mean"].data_ptr(), out["rhat"].data_ptr(),
-                                               out["jsd"].data_ptr(), _stream(dev)))
+    _lib.call("gbp_hitmap_pool", dev, S, C, nv, nz, maps, use, float(half_width), out["pooled"], out["n_used"], out["chain_mean"], out["rhat"],
+              out["jsd"])
     return out

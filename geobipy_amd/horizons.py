@@ -30,7 +30,8 @@ import argparse
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import first_max, load_npz as load, save_npz as save  # noqa: F401  (this module's ``save`` and ``load``)
 
 MAX_STATES = 2048
 OUTPUT_SUFFIX = ".horizons.npz"
@@ -42,13 +43,7 @@ def percentile_name(p):
 
 def check_ptr(ptr, total):
     """``ptr`` as int64 numpy [L + 1]: starts at 0, ends at ``total``, every sequence holds at least one sounding."""
-    p = np.asarray(ptr)
-    if p.ndim != 1 or p.size < 1 or p.dtype.kind not in "iu":
-        raise ValueError("horizons: ptr must be a vector of L + 1 integers")
-    p = p.astype(np.int64)
-    if p[0] != 0 or p[-1] != total or np.any(np.diff(p) < 1):
-        raise ValueError("horizons: ptr must start at 0, end at the number of soundings (%d) and give every sequence at least one" % total)
-    return p
+    return _args.check_ptr(ptr, total, "horizons")
 
 
 def steps(x, y, surface, slope=0.05, min_distance=1.0, ptr=None):
@@ -108,12 +103,6 @@ def evidence_scores(evidence, absent=None, floor=1e-6):
     return score, absent_score
 
 
-def _first_max(v):
-    """(index, value) of the first maximum of a vector, strict > to replace."""
-    i = int(np.argmax(v))
-    return i, v[i]
-
-
 def track_reference(ptr, score, absent_score, g, d, dz, switch, marginals=True, dtype=np.float64):
     """The rule of the module's docstring in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the
     yardstick of the reference's own rounding).  ``ptr`` [L + 1], ``score`` [sum N, S], ``absent_score`` [sum N] or None, ``g``, ``d``
@@ -169,7 +158,8 @@ def track_reference(ptr, score, absent_score, g, d, dz, switch, marginals=True, 
                 via = V[S] - switch
                 repl = via > m
                 arg, m = np.where(repl, S, arg), np.where(repl, via, m)
-                a_arg, a_m = _first_max(V[:S] - switch)
+                a_arg = first_max(V[:S] - switch)
+                a_m = V[a_arg] - switch
                 if V[S] > a_m:
                     a_arg, a_m = S, V[S]
                 nxt[S] = absent_score[r0 + n + 1] + a_m
@@ -177,7 +167,8 @@ def track_reference(ptr, score, absent_score, g, d, dz, switch, marginals=True, 
             nxt[:S] = score[r0 + n + 1] + m
             back[n + 1, :S] = arg
             V = nxt
-        cur, log_score[l] = _first_max(V)
+        cur = first_max(V)
+        log_score[l] = V[cur]
         for n in range(N - 1, -1, -1):
             cell[r0 + n] = cur
             cur = back[n, cur]
@@ -267,7 +258,6 @@ def _launch(score, absent_score, ptr, g, d, dz, switch, marginals):
     total, S = score.shape
     L = ptr.size - 1
     SA = S + (absent_score is not None)
-    lib = _lib.load()
     f64 = dict(dtype=torch.float64, device=dev)
     score = score.contiguous()
     absent_score = None if absent_score is None else absent_score.contiguous()
@@ -277,11 +267,8 @@ def _launch(score, absent_score, ptr, g, d, dz, switch, marginals):
     out = dict(cell=torch.empty(total, dtype=torch.int32, device=dev), log_score=torch.empty(L, **f64))
     if marginals:
         out.update(marginal=torch.empty((total, SA), **f64), log_partition=torch.empty(L, **f64), scale=torch.empty(total, **f64))
-    p = lambda t: None if t is None else t.data_ptr()                         # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(lib.gbp_horizon_track(L, p(t_ptr), total, int(np.diff(ptr).max()) if L else 0, S, float(dz), p(score), p(absent_score),
-                                         p(t_g), p(t_d), float(switch), p(back), p(out["cell"]), p(out["log_score"]), p(out.get("marginal")),
-                                         p(out.get("log_partition")), p(out.get("scale")), torch.cuda.current_stream().cuda_stream))
+    _lib.call("gbp_horizon_track", dev, L, t_ptr, total, int(np.diff(ptr).max()) if L else 0, S, float(dz), score, absent_score, t_g, t_d,
+              float(switch), back, out["cell"], out["log_score"], out.get("marginal"), out.get("log_partition"), out.get("scale"))
     return out
 
 
@@ -490,18 +477,6 @@ def as_intervals(top, bottom):
     if t.shape != b.shape or t.ndim != 1:
         raise ValueError("horizons.as_intervals: top and bottom must both be [N]")
     return {"kind": "horizons", "top": t, "bottom": b}
-
-
-def save(result, path):
-    """Write a result ({name: tensor or array}) to ``path`` (``<line>.horizons.npz``) with np.savez_compressed; returns the path."""
-    np.savez_compressed(path, **{k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in result.items()})
-    return path
-
-
-def load(path):
-    """{name: numpy array} of a file written by ``save``."""
-    with np.load(path) as f:
-        return {k: f[k] for k in f.files}
 
 
 def output_path(container):

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, gridding, hitmap
+from ._args import host
 from .line_products import check_classes, entropy_bits, quantiles
 
 VARIABLES = ("mean", "median", "mode", "credible_low", "credible_high", "credible_range", "entropy", "class_probability",
@@ -63,7 +64,7 @@ def at(plan, x, y):
     x_edges[j] <= x < x_edges[j + 1], y_edges[i] <= y < y_edges[i + 1], and its posterior is that of the cell's lower-left NODE, the
     point at which the plan finds every pixel's nearest sounding.  For boreholes and planned wells: ``plan.pool(maps, pixels=at(plan,
     x, y), ...)``.  A coordinate outside the raster (the last edges included) raises ValueError."""
-    px, py, _, _ = gridding.pixel_coordinates(np.atleast_1d(gridding._host(x)), np.atleast_1d(gridding._host(y)), plan.x_edges, plan.y_edges)
+    px, py, _, _ = gridding.pixel_coordinates(np.atleast_1d(host(x)), np.atleast_1d(host(y)), plan.x_edges, plan.y_edges)
     if not (np.all(np.isfinite(px)) and np.all(np.isfinite(py))):
         raise ValueError("the coordinates must be finite")
     j, i = np.floor(px).astype(np.int64), np.floor(py).astype(np.int64)
@@ -71,7 +72,7 @@ def at(plan, x, y):
     if bad.any():
         k = int(np.flatnonzero(bad)[0])
         raise ValueError("(%g, %g) is outside the raster [%g, %g) x [%g, %g)" % (
-            np.atleast_1d(gridding._host(x)).reshape(-1)[k], np.atleast_1d(gridding._host(y)).reshape(-1)[k], plan.x_edges[0],
+            np.atleast_1d(host(x)).reshape(-1)[k], np.atleast_1d(host(y)).reshape(-1)[k], plan.x_edges[0],
             plan.x_edges[-1], plan.y_edges[0], plan.y_edges[-1]))
     return i * plan.nx + j
 

@@ -44,9 +44,11 @@ weighted re-binning of the hit maps by ``weight``, and learning ``tau`` (``log_p
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import are_tensors, check_block, check_ensemble, check_int, first_max, host, on_device
+from ._args import load_npz as load, save_npz as save  # noqa: F401  (this module's ``save`` and ``load``)
 from .ensembles import Ensemble, check_chains, realisations
-from .families import MAX_K, MAX_MODELS, _check_block, _check_int, _stream, check_window, distance_reference, used_rows
+from .families import MAX_K, MAX_MODELS, check_window, distance_reference, used_rows
 
 MAX_STATES = 1024
 MAX_DRAWS = 65536
@@ -55,15 +57,7 @@ OUTPUT_SUFFIX = ".sections.npz"
 
 def check_ptr(ptr, total, empty=False):
     """``ptr`` as int64 numpy [L + 1]: starts at 0, ends at ``total``, every sequence holds at least one sounding (``empty``: or none)."""
-    p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr)
-    if p.ndim != 1 or p.size < 1 or p.dtype.kind not in "iu":
-        raise ValueError("sections: ptr must be a vector of L + 1 integers")
-    p = p.astype(np.int64)
-    if empty and (p[0] != 0 or p[-1] != total or np.any(np.diff(p) < 0)):
-        raise ValueError("sections: ptr must start at 0, end at the number of soundings (%d) and not decrease" % total)
-    if p[0] != 0 or p[-1] != total or (not empty and np.any(np.diff(p) < 1)):
-        raise ValueError("sections: ptr must start at 0, end at the number of soundings (%d) and give every sequence at least one" % total)
-    return p
+    return _args.check_ptr(ptr, total, "sections", empty)
 
 
 def _default_ptr(ptr, total):
@@ -71,10 +65,6 @@ def _default_ptr(ptr, total):
     if ptr is None:
         return np.array([0, total] if total else [0], dtype=np.int64)
     return check_ptr(ptr, total)
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
 def _check_number(v, what, positive=True):
@@ -88,7 +78,7 @@ def _check_number(v, what, positive=True):
 def partners(ptr, n_used):
     """int32 [S] (numpy): the sounding that sounding s is paired with -- s + 1 within a sequence of ``ptr`` [L + 1] (None: one sequence),
     -1 at a sequence's end.  Sequences are cut at soundings with ``n_used`` == 0: such a sounding, and the one before it, get -1."""
-    nu = _host(n_used).reshape(-1)
+    nu = host(n_used).reshape(-1)
     S = nu.size
     p = _default_ptr(ptr, S)
     out = np.arange(1, S + 1, dtype=np.int32)
@@ -102,7 +92,7 @@ def partners(ptr, n_used):
 def pieces(ptr, n_used):
     """The chains of a launch: (keep int64 [T], piece_ptr int64 [P + 1], owner int64 [P]) -- the soundings with models in their order,
     the runs of them that ``partners`` connects as sequences over ``keep``, and the sequence of ``ptr`` every run belongs to."""
-    nu = _host(n_used).reshape(-1)
+    nu = host(n_used).reshape(-1)
     p = _default_ptr(ptr, nu.size)
     partner = partners(p, nu)
     keep = np.flatnonzero(nu > 0).astype(np.int64)
@@ -167,7 +157,7 @@ def _check_chain(ptr, score, g, d2, n_used, what, empty=False):
         raise ValueError("%s: d2 [T, n, n] with 1 <= n <= %d" % (what, MAX_STATES))
     total, n = d2.shape[0], d2.shape[1]
     ptr = check_ptr(ptr, total, empty)
-    nu = _host(n_used).reshape(-1)
+    nu = host(n_used).reshape(-1)
     if nu.size != total or nu.dtype.kind not in "iu":
         raise ValueError("%s: n_used must hold one integer per sounding" % what)
     if np.any(nu < 1) or np.any(nu > n):
@@ -213,7 +203,7 @@ def track_reference(ptr, score, g, d2, n_used, marginals=True, dtype=np.float64)
                     best, arg = np.where(repl, cand, best), np.where(repl, i, arg)
             V = score[r0 + s + 1, :m[s + 1]] + best
             back.append(arg)
-        cur = _first_max(V)
+        cur = first_max(V)
         log_score[l] = V[cur]
         for s in range(N - 1, -1, -1):
             state[r0 + s] = cur
@@ -248,15 +238,6 @@ def track_reference(ptr, score, g, d2, n_used, marginals=True, dtype=np.float64)
     return out
 
 
-def _first_max(v):
-    """The first maximum of a vector with strict > to replace, starting from v[0] (what the device's one lane does)."""
-    cur = 0
-    for j in range(1, v.size):
-        if v[j] > v[cur]:
-            cur = j
-    return cur
-
-
 # ---- joint draws: the rule ----------------------------------------------------------------------------------------------------------
 
 _M32 = np.uint64(0xFFFFFFFF)
@@ -273,7 +254,7 @@ def _check_row_key(row_key, total, what):
     """``row_key`` as int64 numpy [T]; None: the row index."""
     if row_key is None:
         return np.arange(total, dtype=np.int64)
-    key = _host(row_key)
+    key = host(row_key)
     if key.shape != (total,) or key.dtype.kind not in "iu":
         raise ValueError("%s: row_key must hold one integer per sounding" % what)
     return key.astype(np.int64)
@@ -314,7 +295,7 @@ def draw_reference(ptr, score, g, d2, n_used, n_draws, seed=0, row_key=None, dty
     d2 = np.asarray(d2, dtype=np.float64)
     score = None if score is None else np.asarray(score, dtype=np.float64)
     ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.draw_reference", empty=True)
-    R = _check_int(n_draws, 1, MAX_DRAWS, "sections.draw_reference: n_draws")
+    R = check_int(n_draws, 1, MAX_DRAWS, "sections.draw_reference: n_draws")
     total, n = d2.shape[0], d2.shape[1]
     key = _check_row_key(row_key, total, "sections.draw_reference")
     seed = _check_seed(seed)
@@ -373,19 +354,6 @@ def exceedance_area_reference(k, edges, sigma, x, y, ptr, threshold, z0, z1, abo
 
 # ---- the entries --------------------------------------------------------------------------------------------------------------------
 
-def _are_tensors(tensors, what, entry):
-    for a in tensors:
-        if not torch.is_tensor(a):
-            raise _lib.NativeLibraryError("sections.%s takes torch tensors on the device (%s); there is no host fallback" % (what, entry))
-
-
-def _on_device(tensors, what, entry):
-    """The last check of an entry: shapes, dtypes and values are refused first, whatever device the tensors are on."""
-    for a in tensors:
-        if a.device.type != "cuda":
-            raise _lib.NativeLibraryError("sections.%s runs on the device (%s); there is no host fallback" % (what, entry))
-
-
 def cross_distance(ens, rows, partner, z0, z1, measure="linear", squared=True, log10=True, block=None):
     """D^2 (``squared``; else D) f64 [S, n, n] on the device: entry [s, i, j] is the distance of ``families.distance`` between model
     ``rows[s, i]`` of sounding s and model ``rows[partner[s], j]`` of sounding ``partner[s]`` (``rows`` int32 [S, n] on the device;
@@ -394,51 +362,41 @@ def cross_distance(ens, rows, partner, z0, z1, measure="linear", squared=True, l
     (None: one launch unless it would exceed 2^32 - 1 threads); a block brings the partners outside it along, the bits are the same.
     One kernel (gbp_ensemble_cross_distance)."""
     entry = "gbp_ensemble_cross_distance"
-    k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma, rows), "cross_distance", entry)
-    if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
-        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
-    if rows.ndim != 2 or rows.shape[0] != k.shape[0] or not 1 <= rows.shape[1] <= MAX_MODELS:
-        raise ValueError("cross_distance: rows [S, n] with 1 <= n <= %d" % MAX_MODELS)
-    if k.dtype != torch.int32 or edges.dtype != torch.float64 or sigma.dtype != torch.float64 or rows.dtype != torch.int32:
-        raise TypeError("ensemble: k is int32, edges and sigma are float64; rows is int32")
-    S, ns, K = edges.shape
+    are_tensors((ens.k, ens.edges, ens.sigma, rows), "sections", "cross_distance", entry)
+    k, edges, sigma, S, ns, K = check_ensemble(ens, batch="S", rows=rows, what="cross_distance", max_rows=MAX_MODELS)
     if ns < 1 or not 1 <= K <= MAX_K:
         raise ValueError("ensemble: at least one slot and K in [1, %d]" % MAX_K)
-    pn = _host(partner)
+    pn = host(partner)
     if pn.shape != (S,) or pn.dtype.kind not in "iu":
         raise ValueError("cross_distance: partner must hold one integer per sounding")
     z0, z1, log = check_window(z0, z1, measure)
-    _check_block(block, "cross_distance")
-    _on_device((k, edges, sigma, rows), "cross_distance", entry)
-    k, edges, sigma, rows, dev = k.contiguous(), edges.contiguous(), sigma.contiguous(), rows.contiguous(), k.device
+    check_block(block, "cross_distance")
+    on_device((k, edges, sigma, rows), "sections", "cross_distance", entry)
+    rows, dev = rows.contiguous(), k.device
     n = rows.shape[1]
     out = torch.empty((S, n, n), dtype=torch.float64, device=dev)
     if S == 0:
         return out
     tiles = (n + 15) // 16
     step = (2 ** 32 - 1) // (256 * tiles * tiles) if block is None else int(block)      # soundings one launch takes: 256 threads per tile
-    lib = _lib.load()
 
     def launch(k_, e_, s_, rows_, partner_, out_):
         p_ = torch.as_tensor(np.ascontiguousarray(partner_, dtype=np.int32)).to(dev)
-        _lib.check(lib.gbp_ensemble_cross_distance(k_.shape[0], ns, K, k_.data_ptr(), e_.data_ptr(), s_.data_ptr(), n, rows_.data_ptr(), p_.data_ptr(),
-                                                   z0, z1, log, int(bool(log10)), int(bool(squared)), out_.data_ptr(), _stream(dev)))
+        _lib.call(entry, dev, k_.shape[0], ns, K, k_, e_, s_, n, rows_, p_, z0, z1, log, int(bool(log10)), int(bool(squared)), out_)
 
-    with torch.cuda.device(dev):
-        if S <= step:
-            launch(k, edges, sigma, rows, pn, out)
-            return out
-        for b0 in range(0, S, step):
-            b1 = min(S, b0 + step)
-            p = pn[b0:b1].astype(np.int64)
-            valid = (p >= 0) & (p < S)
-            extra = np.unique(p[valid & ((p < b0) | (p >= b1))])                  # the partners outside the block come along, unpaired
-            local = np.where(valid, np.where((p >= b0) & (p < b1), p - b0, (b1 - b0) + np.searchsorted(extra, p)), -1)
-            idx = torch.as_tensor(np.concatenate([np.arange(b0, b1), extra])).to(dev)
-            part = torch.empty((idx.numel(), n, n), dtype=torch.float64, device=dev)
-            launch(k[idx], edges[idx], sigma[idx], rows[idx], np.concatenate([local, np.full(extra.size, -1)]), part)
-            out[b0:b1] = part[:b1 - b0]
+    if S <= step:
+        launch(k, edges, sigma, rows, pn, out)
+        return out
+    for b0 in range(0, S, step):
+        b1 = min(S, b0 + step)
+        p = pn[b0:b1].astype(np.int64)
+        valid = (p >= 0) & (p < S)
+        extra = np.unique(p[valid & ((p < b0) | (p >= b1))])                  # the partners outside the block come along, unpaired
+        local = np.where(valid, np.where((p >= b0) & (p < b1), p - b0, (b1 - b0) + np.searchsorted(extra, p)), -1)
+        idx = torch.as_tensor(np.concatenate([np.arange(b0, b1), extra])).to(dev)
+        part = torch.empty((idx.numel(), n, n), dtype=torch.float64, device=dev)
+        launch(k[idx], edges[idx], sigma[idx], rows[idx], np.concatenate([local, np.full(extra.size, -1)]), part)
+        out[b0:b1] = part[:b1 - b0]
     return out
 
 
@@ -449,11 +407,11 @@ def track(d2, g, ptr, n_used, score=None, marginals=True):
     models are equally weighted samples.  Returns on the device ``state`` int32 [T], ``log_score`` [L], and with ``marginals``
     ``marginal`` [T, n], ``log_partition`` [L] and ``scale`` [T]."""
     entry = "gbp_section_track"
-    _are_tensors((d2,) + (() if score is None else (score,)), "track", entry)
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "track", entry)
     ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.track")
     if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
         raise TypeError("sections.track: d2 and score are float64")
-    _on_device((d2,) + (() if score is None else (score,)), "track", entry)
+    on_device((d2,) + (() if score is None else (score,)), "sections", "track", entry)
     dev = d2.device
     total, n = d2.shape[0], d2.shape[1]
     L = ptr.size - 1
@@ -461,18 +419,15 @@ def track(d2, g, ptr, n_used, score=None, marginals=True):
     d2 = d2.contiguous()
     score = torch.zeros((total, n), **f64) if score is None else score.contiguous()
     t_ptr = torch.as_tensor(ptr, dtype=torch.int64).to(dev)
-    t_g = torch.as_tensor(_host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
     t_nu = torch.as_tensor(nu.astype(np.int32)).to(dev)
     back = torch.empty((total, n), dtype=torch.int16, device=dev)
     out = dict(state=torch.empty(total, dtype=torch.int32, device=dev), log_score=torch.empty(L, **f64))
     if marginals:
         out.update(marginal=torch.empty((total, n), **f64), log_partition=torch.empty(L, **f64), scale=torch.empty(total, **f64))
-    p = lambda t: None if t is None else t.data_ptr()                         # noqa: E731
     if L > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_section_track(L, p(t_ptr), total, n, p(t_nu), p(score), p(t_g), p(d2), p(back), p(out["state"]),
-                                                     p(out["log_score"]), p(out.get("marginal")), p(out.get("log_partition")),
-                                                     p(out.get("scale")), _stream(dev)))
+        _lib.call(entry, dev, L, t_ptr, total, n, t_nu, score, t_g, d2, back, out["state"], out["log_score"], out.get("marginal"),
+                  out.get("log_partition"), out.get("scale"))
     return out
 
 
@@ -483,31 +438,28 @@ def draw(d2, g, ptr, n_used, n_draws, seed=0, score=None, row_key=None):
     uniform of realisation rho under a sounding is ``philox_uniform(seed, rho, row_key)``, so soundings keep their draws however they
     are grouped into calls.  Returns on the device ``draw_state`` int32 [R, T] and ``filtered`` [T, n]."""
     entry = "gbp_section_draw"
-    _are_tensors((d2,) + (() if score is None else (score,)), "draw", entry)
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "draw", entry)
     ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.draw", empty=True)
-    R = _check_int(n_draws, 1, MAX_DRAWS, "sections.draw: n_draws")
+    R = check_int(n_draws, 1, MAX_DRAWS, "sections.draw: n_draws")
     seed = _check_seed(seed)
     if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
         raise TypeError("sections.draw: d2 and score are float64")
     total, n = d2.shape[0], d2.shape[1]
     key = None if row_key is None else _check_row_key(row_key, total, "sections.draw")
-    _on_device((d2,) + (() if score is None else (score,)), "draw", entry)
+    on_device((d2,) + (() if score is None else (score,)), "sections", "draw", entry)
     dev = d2.device
     L = ptr.size - 1
     f64 = dict(dtype=torch.float64, device=dev)
     d2 = d2.contiguous()
     score = torch.zeros((total, n), **f64) if score is None else score.contiguous()
     t_ptr = torch.as_tensor(ptr, dtype=torch.int64).to(dev)
-    t_g = torch.as_tensor(_host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
     t_nu = torch.as_tensor(nu.astype(np.int32)).to(dev)
     t_key = None if key is None else torch.as_tensor(key).to(dev)
     scale = torch.empty(total, **f64)
     out = dict(draw_state=torch.empty((R, total), dtype=torch.int32, device=dev), filtered=torch.empty((total, n), **f64))
     if L > 0 and total > 0:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().gbp_section_draw(L, t_ptr.data_ptr(), total, n, t_nu.data_ptr(), score.data_ptr(), t_g.data_ptr(), d2.data_ptr(),
-                                                    None if t_key is None else t_key.data_ptr(), seed, R, out["filtered"].data_ptr(),
-                                                    scale.data_ptr(), out["draw_state"].data_ptr(), _stream(dev)))
+        _lib.call(entry, dev, L, t_ptr, total, n, t_nu, score, t_g, d2, t_key, seed, R, out["filtered"], scale, out["draw_state"])
     return out
 
 
@@ -543,13 +495,13 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     log_partition`` is the path's log probability.  ``draw_models`` gathers the models."""
     z0, z1, _ = check_window(z0, z1, measure)
     k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma), "sections", "gbp_ensemble_cross_distance")
+    are_tensors((k, edges, sigma), "sections", "sections", "gbp_ensemble_cross_distance")
     if k.ndim != 2 or edges.ndim != 3:
         raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
     C = check_chains(chains, k.shape[1])
-    max_models = _check_int(max_models, 1, MAX_STATES, "max_models")
-    budget_bytes = _check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
-    R, seed = _check_int(draws, 0, MAX_DRAWS, "draws"), _check_seed(seed)
+    max_models = check_int(max_models, 1, MAX_STATES, "max_models")
+    budget_bytes = check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
+    R, seed = check_int(draws, 0, MAX_DRAWS, "draws"), _check_seed(seed)
     S, K = k.shape[0], edges.shape[2]
     x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
     if x.size != S or y.size != S:
@@ -559,7 +511,7 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     rows, n_used, _ = used_rows(ens, chains=C, max_models=max_models)
     n = rows.shape[1]
     if score is not None:
-        _are_tensors((score,), "sections", "gbp_section_track")
+        are_tensors((score,), "sections", "sections", "gbp_section_track")
         if tuple(score.shape) != (S, n) or score.dtype != torch.float64:
             raise ValueError("sections: score must be float64 [S, n] with n = %d, the width of used_rows" % n)
     dev, L = k.device, p.size - 1
@@ -569,7 +521,7 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     if longest * slab > budget_bytes:
         raise ValueError("sections: a sequence of %d soundings with %d models each needs %d bytes of distances, more than budget_bytes = %d; lower "
                          "max_models or raise budget_bytes (no state is carried between pieces of a sequence)" % (longest, n, longest * slab, budget_bytes))
-    _on_device((k, edges, sigma) + (() if score is None else (score,)), "sections", "gbp_ensemble_cross_distance")
+    on_device((k, edges, sigma) + (() if score is None else (score,)), "sections", "sections", "gbp_ensemble_cross_distance")
     f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
     nan = float("nan")
     state = torch.full((S,), -1, **i32)
@@ -646,12 +598,12 @@ def draw_models(ens, draw_slot, depth_edges=None, log10=True):
     and with ``depth_edges`` [n_depth + 1] ``raster`` f64 [R, S, n_depth]: ``ensembles.realisations`` (its ``log10``) of the gathered
     models -- the section of every realisation on a depth axis."""
     k, edges, sigma = ens.k, ens.edges, ens.sigma
-    _are_tensors((k, edges, sigma, draw_slot), "draw_models", "gbp_ensemble_raster")
+    are_tensors((k, edges, sigma, draw_slot), "sections", "draw_models", "gbp_ensemble_raster")
     if k.ndim != 2 or edges.ndim != 3 or edges.shape != sigma.shape or tuple(edges.shape[:2]) != tuple(k.shape):
         raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
     if draw_slot.ndim != 2 or draw_slot.shape[1] != k.shape[0] or draw_slot.shape[0] < 1 or draw_slot.dtype != torch.int32:
         raise ValueError("draw_models: draw_slot is int32 [R, S] with R >= 1")
-    _on_device((k, edges, sigma, draw_slot), "draw_models", "gbp_ensemble_raster")
+    on_device((k, edges, sigma, draw_slot), "sections", "draw_models", "gbp_ensemble_raster")
     if bool(((draw_slot < -1) | (draw_slot >= k.shape[1])).any()):
         raise ValueError("draw_models: every slot must lie in -1 .. n_slots - 1")
     S, dev = k.shape[0], k.device
@@ -753,18 +705,6 @@ def from_survey(result_or_path, z1, device=None, **kw):
     return out
 
 
-def save(result, path):
-    """Write a result ({name: tensor or array}) to ``path`` (``<name>.sections.npz``) with np.savez_compressed; returns the path."""
-    np.savez_compressed(path, **{k: _host(v) for k, v in result.items()})
-    return path
-
-
-def load(path):
-    """{name: numpy array} of a file written by ``save``."""
-    with np.load(path) as f:
-        return {k: f[k] for k in f.files}
-
-
 def output_path(path):
     """<name>.sections.npz beside the survey result <name>.npz."""
     path = str(path)
@@ -802,9 +742,9 @@ def parse_args(argv=None):
         check_window(a.z0, a.depth, a.measure)
         _check_number(a.tau, "--tau")
         _check_number(a.length, "--length")
-        _check_int(a.chains, 1, 8, "--chains")
-        _check_int(a.max_models, 1, MAX_STATES, "--max-models")
-        _check_int(a.draws, 0, MAX_DRAWS, "--draws")
+        check_int(a.chains, 1, 8, "--chains")
+        check_int(a.max_models, 1, MAX_STATES, "--max-models")
+        check_int(a.draws, 0, MAX_DRAWS, "--draws")
         _check_seed(a.seed)
     except ValueError as e:
         p.error(str(e))

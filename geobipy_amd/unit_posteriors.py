@@ -15,6 +15,8 @@ conductivity is; being averages of layer conductivities they leave it no more of
 import numpy as np
 import torch
 
+from ._args import save_npz as save  # noqa: F401  (this module's ``save``)
+
 KINDS = ("arithmetic", "harmonic")
 STATISTICS = ("mean", "median", "mode", "credible_range")
 
@@ -124,9 +126,3 @@ def products(chains_or_arrays, percentiles=(5, 50, 95), credible=90.0, classes=N
     if fh is not None:
         out.update(first_depth(fh, fnone, dbw, percentiles))
     return out
-
-
-def save(products, path):
-    """Write ``products`` to ``path`` with np.savez_compressed (as ``line_products.save``); returns the path."""
-    np.savez_compressed(path, **{k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in products.items()})
-    return path

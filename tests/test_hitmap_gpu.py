@@ -88,3 +88,52 @@ def test_hitmap_runs_and_statistics_equal_the_torch_formulations():
     d = hdf._Dataset("/x", shape=hm.shape, dtype="i4", fillvalue=0)
     d.write_run_rows(np.arange(B), ptr.cpu().numpy(), start.cpu().numpy(), value.cpu().numpy())
     assert np.array_equal(d.arr, hm)
+
+
+@pytest.mark.gpu
+def test_launches_follow_torchs_current_stream():
+    """``_lib.call`` launches on torch's current stream of the tensors' device: under ``torch.cuda.stream(side)`` a value-axis
+    reduction (hitmap.statistics) and a chain with a back-pointer (sections.track) give the default stream's bits."""
+    import torch
+    from geobipy_amd import hitmap, sections
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(11)
+    hm = torch.as_tensor(rng.integers(0, 9, (2, 4, 3)).astype(np.int32), device=dev)
+    lmp = torch.as_tensor(rng.normal(-4.0, 0.5, 2), device=dev)
+    d2 = torch.as_tensor(rng.uniform(0.0, 2.0, (3, 2, 2)), device=dev)
+    g, ptr, n_used = np.array([0.7, 1.3, 1.0]), [0, 3], np.array([2, 2, 2])
+    mean0, pct0 = hitmap.statistics(hm, lmp, 2.3)
+    track0 = sections.track(d2, g, ptr, n_used)
+    torch.cuda.synchronize(dev)
+    side = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(side):
+        mean1, pct1 = hitmap.statistics(hm, lmp, 2.3)
+        track1 = sections.track(d2, g, ptr, n_used)
+    side.synchronize()
+    bits = lambda t: t.view(torch.int64) if t.dtype == torch.float64 else t      # noqa: E731
+    assert torch.equal(bits(mean0), bits(mean1))
+    for a, b in zip(pct0, pct1):
+        assert torch.equal(bits(a), bits(b))
+    assert set(track0) == set(track1) == {"state", "log_score", "marginal", "log_partition", "scale"}
+    for name in track0:
+        assert torch.equal(bits(track0[name]), bits(track1[name])), name
+
+
+@pytest.mark.gpu
+def test_blocks_of_soundings_pass_the_marshalling_check_with_the_same_bits():
+    """families.distance in blocks of two soundings out of three -- the slices k[s], edges[s], sigma[s], rows[s] and out[s], the last
+    block shorter -- through ``_lib.call``: the bits of one launch."""
+    import torch
+    from geobipy_amd import ensembles, families
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(12)
+    B, ns, K, n = 3, 4, 3, 2
+    k = rng.integers(1, K + 1, (B, ns)).astype(np.int32)
+    edges = np.sort(rng.uniform(1.0, 90.0, (B, ns, K)), axis=2)
+    sigma = 10.0 ** rng.uniform(-3.0, 0.0, (B, ns, K))
+    ens = ensembles.Ensemble(*(torch.as_tensor(a).to(dev) for a in (k, edges, sigma)), None, None, 1, None)
+    rows = torch.as_tensor(np.array([[0, 3], [2, 1], [1, 1]], dtype=np.int32)).to(dev)
+    one = families.distance(ens, rows, 0.0, 100.0, block=None)
+    two = families.distance(ens, rows, 0.0, 100.0, block=2)
+    assert one.shape == (B, n, n) and bool(torch.isfinite(one).all()) and float(one[0, 0, 1]) > 0.0
+    assert torch.equal(one.view(torch.int64), two.view(torch.int64))
