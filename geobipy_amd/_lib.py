@@ -151,6 +151,10 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "gbp_ensemble_ranks": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_double_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gbp_series_weighted": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double_p, c_int, c_double_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gbp_ensemble_weighted": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_double_p, c_int, c_double_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gbp_series_correlation": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
     "gbp_ensemble_correlation": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -39,11 +39,10 @@ struct RankArgs : SeriesArgs {           // reach: n_p
 
 constexpr size_t rank_lds_bytes(int T, int P) { return ((size_t)T * P + T) * sizeof(double) + (size_t)T * sizeof(int); }
 
-// The value of variable v in row `row` of sounding b, one per lane.
+// The value of variable v in source row `src` (series_row) of the series, one per lane: what k_series_weighted shares.
 template <int SOURCE>
-__device__ __forceinline__ double rank_fetch(const RankArgs& a, size_t b, int row, int v, double zc)
+__device__ __forceinline__ double series_value(const SeriesArgs& a, size_t src, int v, double zc)
 {
-    const size_t src = series_row(a, b, row);
     if (SOURCE == SERIES_PLAIN) return a.x[src * (size_t)a.V + v];
     const int k = min(max(a.ens_k[src], 0), a.K);
     if (k == 0) return __longlong_as_double(0x7ff8000000000000ll);
@@ -51,6 +50,13 @@ __device__ __forceinline__ double rank_fetch(const RankArgs& a, size_t b, int ro
     int layer = 0;
     for (int l = 0; l < k - 1; ++l) layer += e[l] <= zc ? 1 : 0;
     return log10(a.ens_sigma[src * a.K + layer]);
+}
+
+// The value of variable v in row `row` of sounding b, one per lane.
+template <int SOURCE>
+__device__ __forceinline__ double rank_fetch(const RankArgs& a, size_t b, int row, int v, double zc)
+{
+    return series_value<SOURCE>(a, series_row(a, b, row), v, zc);
 }
 
 // col[i * T + c], i < P, ascending per column c

@@ -1948,6 +1948,73 @@ extern "C" gbp_status gbp_ensemble_ranks(int B, int n_slots, int K, const int32_
     return series_ranks_launch("gbp_ensemble_ranks", ensemble::SERIES_RASTER, B, a, fold, p, stream);
 }
 
+#include "gbp_ensemble_weighted.h"
+
+// Weighted products within columns (csrc/gbp_ensemble_weighted.h k_series_weighted; the rule: include/geobipy_amd.h): one workgroup per
+// (sounding, tile of T columns), T from the power of two >= n.
+static gbp_status series_weighted_launch(const char* entry, int source, int B, ensemble::WeightedArgs a, const double* p, const double* thr, void* stream)
+{
+    using namespace ensemble;
+    if (B < 0 || a.n_rows < 1 || a.V < 1) return fail(GBP_ERR_INVALID_ARG, "%s: negative or zero size", entry);
+    if (a.n < 1 || a.n > WGT_MAX_ROWS) return fail(GBP_ERR_INVALID_ARG, "%s: n outside 1 .. 4096", entry);
+    if (source == SERIES_RASTER && (a.K < 1 || a.K > 64)) return fail(GBP_ERR_INVALID_ARG, "%s: K outside 1 .. 64", entry);
+    if (a.n_p < 0 || a.n_p > WGT_MAX_P) return fail(GBP_ERR_INVALID_ARG, "%s: n_p outside 0 .. 16", entry);
+    if (a.n_t < 0 || a.n_t > WGT_MAX_T) return fail(GBP_ERR_INVALID_ARG, "%s: n_t outside 0 .. 8", entry);
+    if ((a.n_p > 0 && !p) || (a.n_t > 0 && !thr)) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    for (int i = 0; i < a.n_p; ++i) {
+        if (!(std::isfinite(p[i]) && p[i] >= 0.0 && p[i] <= 1.0)) return fail(GBP_ERR_INVALID_ARG, "%s: a probability outside [0, 1]", entry);
+        a.p[i] = p[i];
+    }
+    for (int j = 0; j < a.n_t; ++j) {
+        if (!std::isfinite(thr[j])) return fail(GBP_ERR_INVALID_ARG, "%s: a threshold that is not finite", entry);
+        a.thr[j] = thr[j];
+    }
+    int P = 1;
+    while (P < a.n) P <<= 1;
+    const int T = std::min(64, WGT_TILE / P);
+    const int64_t blocks = (int64_t)B * ((a.V + T - 1) / T);
+    if (blocks * WGT_THREADS > 0xffffffffLL)                        // (a dispatch counts its work-items in 32 bits)
+        return fail(GBP_ERR_INVALID_ARG, "%s: B * column tiles out of range (more than 2^32 - 1 threads)", entry);
+    if (B == 0) return GBP_OK;                                      // (an empty block: empty device arrays have no address)
+    const bool inputs = source == SERIES_RASTER ? a.ens_k && a.ens_edges && a.ens_sigma && a.z : a.x != nullptr;
+    if (!inputs || !a.rows || !a.n_used || !a.q || !a.total) return fail(GBP_ERR_INVALID_ARG, "%s: NULL pointer", entry);
+    a.T = T;
+    a.P = P;
+    const size_t lds = weighted_lds_bytes(T, P);
+    auto launch = [&](auto kern) -> gbp_status {
+        static std::atomic<bool> allowed[64];      // per instantiation and device: asked for once, for the largest tile
+        int dev = 0;
+        GBP_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !allowed[dev].load(std::memory_order_acquire)) {
+            GBP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)weighted_lds_bytes(64, WGT_TILE / 64)));
+            if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_release);
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WGT_THREADS), lds, (hipStream_t)stream, a);
+        GBP_HIP(hipGetLastError());
+        return GBP_OK;
+    };
+    return source == SERIES_RASTER ? launch(k_series_weighted<SERIES_RASTER>) : launch(k_series_weighted<SERIES_PLAIN>);
+}
+
+extern "C" gbp_status gbp_series_weighted(int B, int n_rows, int V, const double* x, int n, const int32_t* rows, const int32_t* n_used, const int64_t* q,
+                                          int n_p, const double* p, int n_t, const double* thr, int64_t* total, double* quantile, int64_t* above,
+                                          double* stats, void* stream)
+{
+    const ensemble::WeightedArgs a = {{n_rows, V, x, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}, n, rows, n_used,
+                                      (const long long*)q, n_p, n_t, (long long*)total, quantile, (long long*)above, stats, 0, 0, {}, {}};
+    return series_weighted_launch("gbp_series_weighted", ensemble::SERIES_PLAIN, B, a, p, thr, stream);
+}
+
+extern "C" gbp_status gbp_ensemble_weighted(int B, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                            int n_depth, const double* z, int n, const int32_t* rows, const int32_t* n_used, const int64_t* q,
+                                            int n_p, const double* p, int n_t, const double* thr, int64_t* total, double* quantile,
+                                            int64_t* above, double* stats, void* stream)
+{
+    const ensemble::WeightedArgs a = {{n_slots, n_depth, nullptr, K, ens_k, ens_edges, ens_sigma, z, 0, 0, nullptr, nullptr, nullptr}, n, rows, n_used,
+                                      (const long long*)q, n_p, n_t, (long long*)total, quantile, (long long*)above, stats, 0, 0, {}, {}};
+    return series_weighted_launch("gbp_ensemble_weighted", ensemble::SERIES_RASTER, B, a, p, thr, stream);
+}
+
 #include "gbp_ensemble_corr.h"
 
 // Correlation between variables (csrc/gbp_ensemble_corr.h; the rule: include/geobipy_amd.h): the moments, the MFMA kernel, then the two

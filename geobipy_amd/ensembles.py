@@ -27,8 +27,15 @@ every ``thin``-th sampled model of every chain, in chain order, up to ``n_keep``
                    3.24); ``quantiles``: the exact sample quantiles of the kept models; ``correlation(rank=True)``: Spearman's.
                    ``python -m geobipy_amd.ensembles <ensemble.npz> --depth-axis N WIDTH --rank [--percentiles P ...]``.
 
+``weighted``       every product above treats the kept models as equally weighted samples; this one takes weights -- the smoothed
+                   marginals of ``sections.sections``, a borehole's likelihood, importance weights under another prior, dwell counts --
+                   and gives, per depth cell, the weighted mean, sd, percentiles (type-1 inverse of the weighted ECDF) and exceedance
+                   probabilities (gbp_ensemble_weighted / gbp_series_weighted).  The weights are INTEGER
+                   multiplicities (``quantise_weights``: q = rint(w / max w * 2^40)), so the device is held to ``weighted_reference``
+                   with ``==``.
+
 There is no host fallback: all refuse tensors that are not on the device (``realisations_reference`` states the raster's rule in numpy,
-``diagnostics_reference`` that of the diagnostics, ``correlation_reference`` and ``correlation_runs_reference`` those of the correlation, ``rank_counts_reference`` that of the ranks).
+``diagnostics_reference`` that of the diagnostics, ``correlation_reference`` and ``correlation_runs_reference`` those of the correlation, ``rank_counts_reference`` that of the ranks, ``weighted_reference`` that of the weighted products).
 """
 import ctypes
 from collections import namedtuple
@@ -756,6 +763,224 @@ def quantiles(ens, depth_edges, percentiles, chains=1, block=None):
     nu = _used_count(seg_m, seg_n, order[:, 0, 0])
     out = {"quantile_" + percentile_name(q): sample_quantile(order, nu, i, p[i]) for i, q in enumerate(qs)}
     out["n_chains_used"], out["segment_length"], out["n_segments"] = used, seg_n, seg_m
+    return out
+
+
+# ---- weighted products ---------------------------------------------------------------------------------------------
+
+WEIGHT_MAX_ROWS, WEIGHT_MAX_THRESHOLDS, WEIGHT_ONE = 4096, 8, 2 ** 40
+
+
+def check_thresholds(thresholds):
+    """``thresholds`` (None: none) as a float64 numpy list of at most 8 finite numbers."""
+    if thresholds is None:
+        return np.zeros(0, dtype=np.float64)
+    t = np.asarray(thresholds, dtype=np.float64)
+    if t.ndim != 1 or t.size > WEIGHT_MAX_THRESHOLDS:
+        raise ValueError("thresholds: a list of at most %d numbers" % WEIGHT_MAX_THRESHOLDS)
+    if not np.all(np.isfinite(t)):
+        raise ValueError("thresholds: every one finite")
+    return t
+
+
+def quantise_weights(w, n_used):
+    """The one step from floating-point weights to the integer multiplicities the weighted products take: ``w`` [B, n] (floating point;
+    torch on any device, or numpy), ``n_used`` [B] integers in 0 .. n.  Per sounding, over the used rows u < n_used,
+    q = rint(w / max_u w * 2^40): one IEEE division, one exact scaling, one rounding to the nearest integer (ties to even), so that
+    torch on a device and numpy give the same integers.  Returns int64 [B, n] of the kind of ``w``: the largest weight maps to 2^40,
+    the rows >= n_used to 0 whatever they hold.  A NaN, infinite or negative weight among the used rows is refused.  A sounding with
+    n_used == 0 or all weights 0 gives q = 0.  A weight below 2^-41 of the largest becomes 0: twelve orders of magnitude below
+    anything a Monte-Carlo sample of at most 4096 models can resolve."""
+    tensor = torch.is_tensor(w)
+    if not tensor:
+        w = np.asarray(w)
+    if w.ndim != 2 or not (w.dtype.is_floating_point if tensor else w.dtype.kind == "f"):
+        raise ValueError("quantise_weights: w is floating point [B, n]")
+    B, n = w.shape
+    nu = n_used.detach().cpu().numpy() if torch.is_tensor(n_used) else np.asarray(n_used)
+    if nu.shape != (B,) or nu.dtype.kind not in "iu" or (B and (nu.min() < 0 or nu.max() > n)):
+        raise ValueError("quantise_weights: n_used holds one integer in 0 .. n per sounding")
+    used = np.arange(n)[None, :] < nu[:, None]
+    if tensor:
+        used = torch.as_tensor(used).to(w.device)
+        w = w.to(torch.float64)
+        if bool((used & ~((w >= 0.0) & torch.isfinite(w))).any()):
+            raise ValueError("quantise_weights: a NaN, infinite or negative weight among the used rows")
+        if n == 0:
+            return torch.zeros((B, 0), dtype=torch.int64, device=w.device)
+        wu = torch.where(used, w, torch.zeros((), dtype=torch.float64, device=w.device))
+        top = wu.max(dim=1, keepdim=True).values
+        q = torch.round(wu / top * float(WEIGHT_ONE))
+        return torch.where(used & (top > 0.0), q, torch.zeros_like(q)).to(torch.int64)
+    w = w.astype(np.float64)
+    if np.any(used & ~((w >= 0.0) & np.isfinite(w))):
+        raise ValueError("quantise_weights: a NaN, infinite or negative weight among the used rows")
+    if n == 0:
+        return np.zeros((B, 0), dtype=np.int64)
+    wu = np.where(used, w, 0.0)
+    top = wu.max(axis=1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.rint(wu / top * float(WEIGHT_ONE))
+    return np.where(used & (top > 0.0), q, 0.0).astype(np.int64)
+
+
+def weighted_reference(x, rows, n_used, q, probabilities=None, thresholds=None, dtype=np.float64):
+    """The rule of the weighted products in numpy: ``x`` [B, n_rows, V] (for an ensemble: log10 conductivity of the slots at the cell
+    centres), ``rows`` integers [B, n], ``n_used`` [B], ``q`` int64 [B, n].  Model u < m = n_used[b] (clamped to 0 .. n) is row
+    rows[b, u] with the INTEGER multiplicity q[b, u] (clamped to 0 .. 2^40; ``quantise_weights`` makes them from floating-point
+    weights); a row with q == 0 takes no part whatever it holds or names, a participating row index is clamped into the rows.
+    W = sum q; C(t) = sum of q over the participating values <= t (compared as doubles).  Returns
+
+    ``total`` int64 [B] = W;
+    ``quantile`` f64 [B, n_p, V]: the smallest participating value t with float64(C(t)) >= max(p * float64(W), 1.0) -- the inverse of
+        the weighted ECDF, Hyndman & Fan's type 1; p = 0 gives the smallest value of positive weight.  With equal weights this is
+        s[max(ceil(p n), 1) - 1] of the sorted column: NOT the interpolated ``quantiles`` (numpy's "linear", type 7);
+    ``above`` int64 [B, n_t, V] = sum of q over the participating values >= the threshold (divided by W: the exceedance probability);
+    ``mean`` = sum q x / W and ``sd`` = sqrt(sum q (x - mean)^2 / W) [B, V], two passes evaluated in ``dtype`` (np.longdouble: the
+        yardstick of the rounding of the device's fp64 sums, whose order of addition is not part of the rule).
+
+    W == 0: quantile, mean, sd NaN and above 0.  A column with a non-finite participating value: quantile, mean, sd NaN, above -1.
+    Every decision is a comparison of integers (exact in fp64 up to 2^52 >= W): no order of addition or of ties can change a bit."""
+    ft = np.dtype(dtype).type
+    x, rows, q = np.asarray(x, dtype=np.float64), np.asarray(rows), np.asarray(q)
+    nu = np.asarray(n_used).reshape(-1)
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise ValueError("weighted_reference: x [B, n_rows, V]")
+    B, n_rows, V = x.shape
+    if rows.ndim != 2 or rows.shape[0] != B or not 1 <= rows.shape[1] <= WEIGHT_MAX_ROWS or rows.dtype.kind not in "iu":
+        raise ValueError("weighted_reference: rows holds integers [B, n] with 1 <= n <= %d" % WEIGHT_MAX_ROWS)
+    if q.shape != rows.shape or q.dtype.kind not in "iu" or nu.shape != (B,) or nu.dtype.kind not in "iu":
+        raise ValueError("weighted_reference: q holds integers [B, n], n_used [B]")
+    p, thr = check_probabilities(probabilities), check_thresholds(thresholds)
+    n = rows.shape[1]
+    total = np.zeros(B, dtype=np.int64)
+    quantile, above = np.full((B, p.size, V), np.nan), np.zeros((B, thr.size, V), dtype=np.int64)
+    mean, sd = np.full((B, V), np.nan, dtype=ft), np.full((B, V), np.nan, dtype=ft)
+    for b in range(B):
+        m = int(min(max(nu[b], 0), n))
+        qq = np.clip(q[b, :m].astype(np.int64), 0, WEIGHT_ONE)
+        W = int(qq.sum())
+        total[b] = W
+        if W == 0:
+            continue
+        part = qq > 0
+        r, wq = np.clip(rows[b, :m][part].astype(np.int64), 0, n_rows - 1), qq[part]
+        for v in range(V):
+            c = x[b, r, v]
+            if not np.all(np.isfinite(c)):
+                above[b, :, v] = -1
+                continue
+            order = np.argsort(c, kind="stable")
+            s = c[order]
+            C = np.cumsum(wq[order])[np.searchsorted(s, s, side="right") - 1]      # C(s_i): ties share the weight of their run
+            for i in range(p.size):
+                quantile[b, i, v] = s[int(np.argmax(C.astype(np.float64) >= max(p[i] * np.float64(W), 1.0)))]
+            for j in range(thr.size):
+                above[b, j, v] = wq[c >= thr[j]].sum()
+            cf, wf = c.astype(ft), wq.astype(ft)
+            mean[b, v] = (wf * cf).sum() / ft(W)
+            d = cf - mean[b, v]
+            sd[b, v] = np.sqrt((wf * (d * d)).sum() / ft(W))
+    return dict(total=total, quantile=quantile, above=above, mean=mean, sd=sd)
+
+
+def _check_percentiles_or_none(percentiles):
+    return () if percentiles is None or (np.ndim(percentiles) == 1 and np.size(percentiles) == 0) else check_percentiles(percentiles)
+
+
+def _check_listed(rows, n_used, q, B, what, floating=False):
+    """``rows`` int32 [B, n], ``n_used`` int32 [B], ``q`` int64 [B, n] (``floating``: or float64 weights) (torch, any device),
+    1 <= n <= 4096."""
+    if rows.ndim != 2 or rows.shape[0] != B or not 1 <= rows.shape[1] <= WEIGHT_MAX_ROWS:
+        raise ValueError("%s: rows [B, n] with 1 <= n <= %d" % (what, WEIGHT_MAX_ROWS))
+    if tuple(q.shape) != tuple(rows.shape) or tuple(n_used.shape) != (B,):
+        raise ValueError("%s: q [B, n] as rows, n_used [B]" % what)
+    if rows.dtype != torch.int32 or n_used.dtype != torch.int32 or not (q.dtype == torch.int64 or (floating and q.dtype == torch.float64)):
+        raise TypeError("%s: rows and n_used are int32, q is int64" % what + (" (weights: float64 or int64)" if floating else ""))
+
+
+def _launch_weighted(entry, head, B, V, dev, rows, n_used, q, p, thr):
+    """One call of gbp_series_weighted / gbp_ensemble_weighted (``head``: the entry's arguments up to n) on fresh outputs."""
+    out = dict(total=torch.empty(B, dtype=torch.int64, device=dev), quantile=torch.empty((B, p.size, V), dtype=torch.float64, device=dev),
+               above=torch.empty((B, thr.size, V), dtype=torch.int64, device=dev))
+    stats = torch.empty((B, 2, V), dtype=torch.float64, device=dev)
+    given = lambda a: a if a.numel() else None      # noqa: E731
+    if B > 0:
+        _lib.call(entry, dev, *head, int(rows.shape[1]), rows, n_used, q, int(p.size), (ctypes.c_double * max(int(p.size), 1))(*p),
+                  int(thr.size), (ctypes.c_double * max(int(thr.size), 1))(*thr), out["total"], given(out["quantile"]), given(out["above"]), stats)
+    out["mean"], out["sd"] = stats[:, 0], stats[:, 1]
+    return out
+
+
+def series_weighted(x, rows, n_used, q, percentiles=(5, 50, 95), thresholds=()):
+    """The weighted products (``weighted_reference`` states the rule) within the columns of the series ``x`` f64 [B, n_rows, V] on the
+    device: ``rows`` int32 [B, n] (n <= 4096), ``n_used`` int32 [B], ``q`` int64 [B, n] integer multiplicities in 0 .. 2^40
+    (``quantise_weights``).  Returns {total int64 [B], quantile f64 [B, n_p, V] at ``percentiles`` / 100 -- the type-1 inverse of the
+    weighted ECDF, not the interpolated ``quantiles`` --, above int64 [B, n_t, V], mean, sd f64 [B, V]}.  One kernel
+    (gbp_series_weighted)."""
+    entry = "gbp_series_weighted"
+    qs, thr = _check_percentiles_or_none(percentiles), check_thresholds(thresholds)
+    are_tensors((x, rows, n_used, q), "ensembles", "series_weighted", entry)
+    if x.dtype != torch.float64:
+        raise TypeError("series_weighted: x is float64")
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise ValueError("series_weighted: x is float64 [B, n_rows, V] with n_rows >= 1 and V >= 1")
+    _check_listed(rows, n_used, q, x.shape[0], "series_weighted")
+    on_device((x, rows, n_used, q), "ensembles", "series_weighted", entry)
+    B, n_rows, V = x.shape
+    p = np.asarray([v / 100.0 for v in qs], dtype=np.float64)
+    return _launch_weighted(entry, (B, n_rows, V, x.contiguous()), B, V, x.device, rows.contiguous(), n_used.contiguous(), q.contiguous(), p, thr)
+
+
+def weighted(ens, depth_edges, rows, weight, n_used=None, percentiles=(5, 50, 95), thresholds=(), block=None):
+    """The posterior of every sounding under weights on its kept models: per sounding and cell of ``depth_edges`` [n_depth + 1] the
+    weighted mean, sd, percentiles and exceedance probabilities of log10 conductivity at the cell centre (``weighted_reference``
+    states the rule), the series never read from memory (gbp_ensemble_weighted).  ``rows`` int32 [B, n] (n <= 4096): model u of
+    sounding b is slot rows[b, u]; ``n_used`` int32 [B] (None: all n); ``weight`` [B, n]: float64 -- the smoothed marginals of
+    ``sections.sections``, a borehole's likelihood, importance weights: quantised by ``quantise_weights`` -- or int64, taken as the
+    multiplicities themselves (dwell counts).  ``thresholds``: at most 8, in log10 S/m.
+
+    Returns on the device ``mean``, ``sd``, ``percentile_<p>`` (``percentile_name``) f64 [B, n_depth]; ``exceedance`` f64 [B, n_t,
+    n_depth], the weight of the models >= the threshold over the total (NaN where the total is 0 or the column holds a non-finite
+    value); ``weight_total`` int64 [B], the sum W of the multiplicities; ``n_effective`` f64 [B] = W^2 / sum q^2 (NaN: W == 0).
+    The percentiles are the type-1 inverse of the weighted ECDF -- a value one of the models holds --, NOT the interpolated
+    ``quantiles``.  ``block``: soundings per launch (None: as many as keep a launch under 2^32 - 1 threads)."""
+    entry = "gbp_ensemble_weighted"
+    qs, thr = check_percentiles(percentiles), check_thresholds(thresholds)
+    z_np = centres(depth_edges)
+    check_block(block, "weighted")
+    tensors = (ens.k, ens.edges, ens.sigma, rows, weight) + (() if n_used is None else (n_used,))
+    are_tensors(tensors, "ensembles", "weighted", entry)
+    k, edges, sigma, B, ns, K = check_ensemble(ens)
+    if ns < 1 or not 1 <= K <= 64:
+        raise ValueError("ensemble: at least one slot and K in [1, 64]")
+    if weight.dtype not in (torch.float64, torch.int64):
+        raise TypeError("weighted: weight is float64 (quantised) or int64 (the multiplicities)")
+    if n_used is None:
+        n_used = torch.full((B,), rows.shape[1] if rows.ndim == 2 else 0, dtype=torch.int32, device=rows.device)
+    _check_listed(rows, n_used, weight, B, "weighted", floating=True)
+    q = weight if weight.dtype == torch.int64 else quantise_weights(weight, n_used.clamp(min=0, max=rows.shape[1]))
+    on_device(tensors, "ensembles", "weighted", entry)
+    nd, dev, n = int(z_np.size), k.device, rows.shape[1]
+    rows, n_used, q = rows.contiguous(), n_used.contiguous(), q.contiguous()
+    z = torch.as_tensor(z_np).to(dev)
+    p = np.asarray([v / 100.0 for v in qs], dtype=np.float64)
+    P = 1 << max(n - 1, 0).bit_length()
+    tiles = -(-nd // min(64, 8192 // P))
+    step = max(1, (2 ** 32 - 1) // (1024 * tiles)) if block is None else int(block)
+    parts = [_launch_weighted(entry, (s.stop - s.start, ns, K, k[s], edges[s], sigma[s], nd, z), s.stop - s.start, nd, dev, rows[s], n_used[s], q[s], p, thr)
+             for s in (slice(b0, min(B, b0 + step)) for b0 in range(0, max(B, 1), step))]
+    r = {name: torch.cat([part[name] for part in parts]) for name in parts[0]}
+    out = dict(mean=r["mean"], sd=r["sd"])
+    for i, v in enumerate(qs):
+        out["percentile_" + percentile_name(v)] = r["quantile"][:, i]
+    W = r["total"].to(torch.float64)
+    nanv = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    out["exceedance"] = torch.where(r["above"] >= 0, r["above"].to(torch.float64) / W[:, None, None], nanv)
+    out["weight_total"] = r["total"]
+    live = torch.arange(n, device=dev)[None, :] < n_used[:, None]
+    qf = torch.where(live, q.clamp(min=0, max=WEIGHT_ONE), torch.zeros_like(q)).to(torch.float64)
+    out["n_effective"] = W * W / (qf * qf).sum(dim=1)
     return out
 
 

@@ -25,6 +25,10 @@ the depth window (the distance of ``families.distance``, between the models of t
                     ``philox_uniform`` its random numbers).  ``sections(..., draws=R, seed=N)`` adds them to its result, ``draw_models``
                     gathers their models (and rasters them), and ``exceedance_area`` is one product that needs them: the area of a
                     section above a conductivity threshold, a quantity of the line with a posterior only over joint realisations.
+``lateral_products``  the laterally informed posterior of every sounding on a depth axis (gbp_ensemble_weighted through
+                    ``ensembles.weighted``): the weighted mean, sd, percentiles and exceedance probabilities of log10 conductivity
+                    per depth cell, the kept models weighted by the smoothed marginals ``weight``.  ``sections(..., products=dict(
+                    depth_edges=...))`` adds them to its result: a section of medians with a credible band.
 
 The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L + 1]; m_r = n_used[r] in 1 .. n.
   Viterbi: V_0[j] = score[r0, j] for j < m_0.  Per step r -> r + 1 and per j < m_{r+1}: best = -inf, arg = 0; for i = 0 .. m_r - 1
@@ -36,10 +40,12 @@ The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L 
 Nothing outside the prefixes i < m_r, j < m_{r+1} of d2 is read, nor the entry of a sequence's last sounding.
 
 ``python -m geobipy_amd.sections <survey.npz> --depth Z1 [--from Z0] [--measure log] [--tau T] [--length L] [--max-models n]
-[--chains C] [--no-marginals] [--draws R [--seed N]]`` writes ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``,
-``track``, ``draw`` and ``sections`` refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
-after the run, like ``horizons.from_products``.  Left out on purpose: coupling across lines, carrying a sequence across launches,
-weighted re-binning of the hit maps by ``weight``, and learning ``tau`` (``log_partition`` is returned for whoever wants to scan it).
+[--chains C] [--no-marginals] [--draws R [--seed N]] [--depth-axis N WIDTH [--percentiles P ...] [--exceed T ...]]`` writes
+``<name>.sections.npz``.  There is no host fallback: ``cross_distance``, ``track``, ``draw``, ``sections`` and ``lateral_products``
+refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
+after the run, like ``horizons.from_products``.  Left out on purpose: coupling across lines, carrying a sequence across launches, and
+learning ``tau`` (``log_partition`` is returned for whoever wants to scan it).  (The weighted re-binning by ``weight`` that this list
+used to name is ``lateral_products``.)
 """
 import numpy as np
 import torch
@@ -473,7 +479,7 @@ def _run_sums(terms, piece_ptr):
 
 
 def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=128, tau=0.1, length=100.0, min_distance=1.0, score=None,
-             marginals=True, budget_bytes=4 << 30, draws=0, seed=0):
+             marginals=True, budget_bytes=4 << 30, draws=0, seed=0, products=None):
     """One kept model per sounding, chosen jointly along every sequence of ``ptr`` [L + 1] (None: one sequence) for the ensemble
     ``ens`` of soundings at ``x``, ``y`` [S] (host; m) over the depth window [z0, z1]: ``families.used_rows`` (``chains``,
     ``max_models`` <= 1024), ``cross_distance`` (squared), ``steps`` (``tau``, ``length``, ``min_distance``), ``track`` and a gather.
@@ -492,8 +498,16 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     sounding is its index in the survey, so ``budget_bytes`` cannot change a draw): ``draw_state`` int32 [R, S] (the position in
     ``rows``; -1: no models), ``draw_slot`` int32 [R, S] (the ensemble slot; -1) and ``draw_log_score`` f64 [R, L] = sum score - sum g
     d2 along the drawn path, summed over a cut sequence's runs: on the scale of ``log_score``, so that ``draw_log_score -
-    log_partition`` is the path's log probability.  ``draw_models`` gathers the models."""
+    log_partition`` is the path's log probability.  ``draw_models`` gathers the models.
+
+    ``products`` = dict(depth_edges=, percentiles=, thresholds=) adds what ``lateral_products`` returns for this result: the weighted
+    mean, sd, percentiles and exceedance probabilities of every sounding's models under ``weight`` on a depth axis (it needs
+    ``marginals``).  Without it the result is what it was, bit for bit."""
     z0, z1, _ = check_window(z0, z1, measure)
+    if products is not None:
+        products = check_products(products)
+        if not marginals:
+            raise ValueError("sections: products are weighted by the smoothed marginals; they need marginals=True")
     k, edges, sigma = ens.k, ens.edges, ens.sigma
     are_tensors((k, edges, sigma), "sections", "sections", "gbp_ensemble_cross_distance")
     if k.ndim != 2 or edges.ndim != 3:
@@ -589,7 +603,40 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
         dhas = draw_state >= 0
         dslot = torch.gather(rows.long()[None, :, :].expand(R, S, n), 2, draw_state.long().clamp(min=0)[:, :, None])[:, :, 0].clamp(min=0)
         out.update(draw_state=draw_state, draw_slot=torch.where(dhas, dslot, torch.full_like(dslot, -1)).to(torch.int32), draw_log_score=draw_log_score)
+    if products is not None:
+        out.update(lateral_products(ens, out, **products))
     return out
+
+
+PRODUCT_KEYS = ("depth_edges", "percentiles", "thresholds")
+
+
+def check_products(products):
+    """``products`` of ``sections`` as the keywords of ``lateral_products``: a dictionary with ``depth_edges`` [n_depth + 1] and, optionally,
+    ``percentiles`` (default 5, 50, 95) and ``thresholds`` (log10 S/m; default none).  Refuses before any device work."""
+    from .ensembles import centres, check_percentiles, check_thresholds
+    if not isinstance(products, dict) or "depth_edges" not in products or not set(products) <= set(PRODUCT_KEYS):
+        raise ValueError("sections: products is a dictionary with depth_edges and optionally percentiles and thresholds")
+    centres(products["depth_edges"])
+    return dict(depth_edges=np.asarray(products["depth_edges"], dtype=np.float64), percentiles=check_percentiles(products.get("percentiles", (5, 50, 95))),
+                thresholds=tuple(float(t) for t in check_thresholds(products.get("thresholds", ()))))
+
+
+def lateral_products(ens, s, depth_edges, percentiles=(5, 50, 95), thresholds=()):
+    """The laterally informed posterior of every sounding on a depth axis: the kept models of ``ens`` re-weighted by the smoothed
+    marginals of a result ``s`` of ``sections`` (its ``rows``, ``n_used`` and ``weight``: ``marginals=True``), through
+    ``ensembles.weighted`` (gbp_ensemble_weighted).  Returns on the device ``lateral_mean``, ``lateral_sd``,
+    ``lateral_percentile_<p>`` f64 [S, n_depth] of log10 conductivity at the centres of ``depth_edges`` [n_depth + 1] and
+    ``lateral_exceedance`` f64 [S, n_t, n_depth], the probability of log10 conductivity >= each of ``thresholds``; a sounding without
+    models gives rows of NaN.  The percentiles are weighted type-1 quantiles (a value one of the models holds): where a sounding's
+    posterior has two families, the median takes the value of the family its neighbours support -- a section with a credible band,
+    where the Viterbi path has no spread and ``draws`` would have to be rastered and counted."""
+    from .ensembles import weighted
+    missing = [name for name in ("rows", "n_used", "weight") if name not in s]
+    if missing:
+        raise ValueError("sections.lateral_products: the result holds no %s (sections(..., marginals=True) gives the weights)" % ", ".join(missing))
+    w = weighted(ens, depth_edges, s["rows"], s["weight"], n_used=s["n_used"], percentiles=percentiles, thresholds=thresholds)
+    return {"lateral_" + name: v for name, v in w.items() if name not in ("weight_total", "n_effective")}
 
 
 def draw_models(ens, draw_slot, depth_edges=None, log10=True):
@@ -730,6 +777,11 @@ def _parser():
     p.add_argument("--no-marginals", action="store_true", help="only the path: skip the forward-backward pass")
     p.add_argument("--draws", type=int, default=0, metavar="R", help="joint realisations of every line to draw, 0 .. 65536 (default 0: none)")
     p.add_argument("--seed", type=int, default=0, metavar="N", help="the seed of the draws, a uint64 (default 0)")
+    p.add_argument("--depth-axis", nargs=2, metavar=("N", "WIDTH"), default=None,
+                   help="add the laterally weighted posterior on N uniform cells of WIDTH starting at 0: lateral_mean, lateral_sd, "
+                        "lateral_percentile_<p>, lateral_exceedance")
+    p.add_argument("--percentiles", type=float, nargs="+", default=None, metavar="P", help="with --depth-axis: ascending percentiles in [0, 100] (default 5 50 95)")
+    p.add_argument("--exceed", type=float, nargs="+", default=None, metavar="T", help="with --depth-axis: at most 8 thresholds in log10 S/m (default none)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -752,6 +804,24 @@ def parse_args(argv=None):
               marginals=not a.no_marginals, device=a.device)
     if a.draws:
         kw.update(draws=a.draws, seed=a.seed)
+    if a.depth_axis is None:
+        if a.percentiles is not None or a.exceed is not None:
+            p.error("--percentiles and --exceed need --depth-axis")
+    else:
+        try:
+            n, w = int(a.depth_axis[0]), float(a.depth_axis[1])
+        except ValueError:
+            p.error("--depth-axis N WIDTH: an integer and a number")
+        if n < 1 or not (np.isfinite(w) and w > 0.0):
+            p.error("--depth-axis: N >= 1 and a finite, positive WIDTH")
+        if a.no_marginals:
+            p.error("--depth-axis needs the marginals (drop --no-marginals)")
+        try:
+            kw["products"] = check_products(dict(depth_edges=np.arange(n + 1, dtype=np.float64) * w,
+                                                 percentiles=(5, 50, 95) if a.percentiles is None else a.percentiles,
+                                                 thresholds=() if a.exceed is None else a.exceed))
+        except ValueError as e:
+            p.error("--" + str(e))
     return a.survey, kw
 
 

@@ -779,6 +779,39 @@ gbp_status gbp_ensemble_ranks(int B, int n_slots, int K, const int32_t *ens_k, c
                               int n_depth, const double *z, int M_max, const int32_t *seg_start, const int32_t *seg_m,
                               const int32_t *seg_n, int fold, int n_p, const double *p, int32_t *less, int32_t *leq, double *order,
                               double *x_out, void *stream);
+/* Weighted products within the columns of such series (csrc/gbp_ensemble_weighted.h; the host statement of the rule is
+ * geobipy_amd/ensembles.py weighted_reference): the mean, sd, quantiles and exceedance weights of a sounding's models under weights --
+ * the smoothed marginals of a section, a borehole's re-weighting, importance weights, dwell counts.
+ * WEIGHTS ARE INTEGERS.  Model u < m = n_used[b] (clamped to 0 .. n) of sounding b is row rows[b, u] (rows int32 [B, n]; gbp_series_weighted: a
+ * row of x f64 [B, n_rows, V]; gbp_ensemble_weighted: a slot) with multiplicity q[b, u] (int64 [B, n], 0 <= q <= 2^40; a value outside is
+ * the caller's error and is clamped), so that sum q <= 2^52 and every decision below is a comparison of integers, or of integers exact
+ * in fp64: no order of addition and no tie order can change a bit.  (ensembles.quantise_weights is the one documented step from
+ * floating-point weights: q = rint(w / max w * 2^40).)
+ *   x_u      gbp_series_weighted: x[b, rows[b, u], v]; gbp_ensemble_weighted: log10 of the stored conductivity of layer
+ *            #{l < k - 1 : edges[l] <= z[v]} of the slot -- the expression of gbp_ensemble_ranks / gbp_ensemble_diagnostics.
+ *   A row with q_u == 0 takes no part, whatever it holds or names: it is never loaded.  A participating row index outside the rows is
+ *   the caller's error and is clamped before any load; a participating empty slot (k == 0) has the value NaN.
+ *   total[b] = W = sum_u q_u (int64 [B]).  C(t) = sum_{u : x_u <= t} q_u, values compared as doubles (-0.0 equals +0.0).
+ *   quantile[b, i, v] = the smallest participating value t with (double)C(t) >= max(p[i] * (double)W, 1.0) (one fp64 product): the inverse
+ *            of the weighted ECDF, type 1; p = 0 gives the smallest value of positive weight.  With equal weights it is s[max(ceil(p n),
+ *            1) - 1] of the sorted column -- NOT the interpolated pair of gbp_ensemble_ranks' order.
+ *   above[b, j, v] = sum_{u : x_u >= thr[j]} q_u (int64): divided by W it is the exceedance probability.
+ *   stats[b, 0, v] = mean = sum q x / W; stats[b, 1, v] = sd = sqrt(sum q (x - mean)^2 / W): two passes in fp64 (tied values enter with
+ *            their summed weight; the order of addition is fixed, so a call repeats its bits, but it is not part of the rule).
+ *   W == 0: quantile, mean and sd NaN, above 0.  A column with a non-finite participating value: quantile, mean, sd NaN, above -1.
+ * quantile f64 [B, n_p, V], above int64 [B, n_t, V], stats f64 [B, 2, V]: each may be NULL and is then skipped.  p: HOST array of n_p
+ * probabilities, thr: HOST array of n_t thresholds (gbp_ensemble_weighted: log10 S/m).
+ * 1 <= n <= 4096 (keys and bins of a padded column live in LDS), n_rows / n_slots >= 1, V / n_depth >= 1, 1 <= K <= 64, 0 <= n_p <= 16 with
+ * every p finite in [0, 1], 0 <= n_t <= 8 with every thr finite, at most 2^32 - 1 threads; GBP_ERR_INVALID_ARG for these and NULL pointers,
+ * every check before any launch, the entry named in gbp_last_error; B == 0 launches nothing.  No global atomics, every output has one
+ * writer, the additions in LDS are of integers: a call repeats its own bits. */
+gbp_status gbp_series_weighted(int B, int n_rows, int V, const double *x, int n, const int32_t *rows, const int32_t *n_used, const int64_t *q,
+                               int n_p, const double *p, int n_t, const double *thr, int64_t *total, double *quantile, int64_t *above,
+                               double *stats, void *stream);
+gbp_status gbp_ensemble_weighted(int B, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma,
+                                 int n_depth, const double *z, int n, const int32_t *rows, const int32_t *n_used, const int64_t *q,
+                                 int n_p, const double *p, int n_t, const double *thr, int64_t *total, double *quantile, int64_t *above,
+                                 double *stats, void *stream);
 /* Correlation between the variables of such series (csrc/gbp_ensemble_corr.h): what moves together.  Per sounding b
  * the used rows are those of its M = seg_m[b] segments of N = seg_n[b] rows (the lists of the diagnostics), n = M N of them:
  * mu_v = (1/n) sum_t x_tv; d_tv = x_tv - mu_v; C(u, v) = (1/(n - 1)) sum_t d_tu d_tv (the pooled sample covariance); sd_v = sqrt(C(v, v));
