@@ -22,8 +22,15 @@
  * reciprocal-then-multiply for Yn, Smith complex division as numpy/numba do),
  * so differences to the interpreted reference stay at the 1e-12 ppm level.
  * Compile with -ffp-contract=off (see oracle/Makefile).
+ *
+ * One real type.  The default build is fp64 (libgbp_oracle.so), the checker described above.  With
+ * -DORACLE_LONG_DOUBLE every real is a long double, the libm calls are their l forms and pi, mu0 are long-double
+ * literals (libgbp_oracle_ld.so): the same formula evaluated with a 64-bit mantissa on x86, which is what the
+ * fp64 oracle and the kernels are both measured against (tests/test_forward_long_double.py).  Inputs of that build
+ * are fp64 values widened exactly by the caller; lamda^2 is formed by the caller in long double.
  */
 #include <complex.h>
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -33,43 +40,62 @@
 #include <omp.h>
 #endif
 
+#ifdef ORACLE_LONG_DOUBLE
+typedef long double real_t;
+typedef long double complex rcomplex_t;
+#define RL(x) x##L          /* a literal that is not exact in fp64 */
+#define RM(f) f##l          /* the libm function of the real type */
+#define RCMPLX(re, im) CMPLXL(re, im)
+#define ORACLE_MANT_DIG LDBL_MANT_DIG
+#else
+typedef double real_t;
+typedef double complex rcomplex_t;
+#define RL(x) x
+#define RM(f) f
+#define RCMPLX(re, im) CMPLX(re, im)
+#define ORACLE_MANT_DIG DBL_MANT_DIG
+#endif
+
+/* mantissa width of real_t in bits (53, or 64 for the x87 long double); the Python side asserts what it needs */
+int oracle_real_mant_dig(void) { return ORACLE_MANT_DIG; }
+
 #define NC0 120 /* FD:18 */
 #define NC1 140 /* FD:19 */
 
-typedef struct { double re, im; } cx;
+typedef struct { real_t re, im; } cx;
 
-static const double PI = 3.14159265358979323846;
+static const real_t PI = RL(3.14159265358979323846);
 
 /* FD:13-17 */
-static double mu0(void) { return 4.e-7 * PI; }
-static double eps0(void) { const double c = 299792458.0; return 1.0 / (mu0() * pow(c, 2.0)); }
+static real_t mu0(void) { return RL(4.e-7) * PI; }
+static real_t eps0(void) { const real_t c = 299792458.0; return 1.0 / (mu0() * RM(pow)(c, 2.0)); }
 
-static inline cx cx_(double re, double im) { cx z = {re, im}; return z; }
+static inline cx cx_(real_t re, real_t im) { cx z = {re, im}; return z; }
 static inline cx cadd(cx a, cx b) { return cx_(a.re + b.re, a.im + b.im); }
 static inline cx csub(cx a, cx b) { return cx_(a.re - b.re, a.im - b.im); }
 static inline cx cmul(cx a, cx b) { return cx_(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re); }
-static inline cx cscale(cx a, double s) { return cx_(a.re * s, a.im * s); }
+static inline cx cscale(cx a, real_t s) { return cx_(a.re * s, a.im * s); }
 /* Smith's algorithm: what numpy's complex128 true_divide loop and numba's
  * complex division both use. */
 static inline cx cdiv(cx a, cx b)
 {
-    double abr = fabs(b.re), abi = fabs(b.im);
+    real_t abr = RM(fabs)(b.re), abi = RM(fabs)(b.im);
     if (abr >= abi) {
         if (abr == 0.0 && abi == 0.0) return cx_(a.re / abr, a.im / abr);
-        double rat = b.im / b.re;
-        double scl = 1.0 / (b.re + b.im * rat);
+        real_t rat = b.im / b.re;
+        real_t scl = 1.0 / (b.re + b.im * rat);
         return cx_((a.re + a.im * rat) * scl, (a.im - a.re * rat) * scl);
     } else {
-        double rat = b.re / b.im;
-        double scl = 1.0 / (b.im + b.re * rat);
+        real_t rat = b.re / b.im;
+        real_t scl = 1.0 / (b.im + b.re * rat);
         return cx_((a.re * rat + a.im) * scl, (a.im * rat - a.re) * scl);
     }
 }
-static inline cx csqrt_(cx a) { double complex r = csqrt(CMPLX(a.re, a.im)); return cx_(creal(r), cimag(r)); }
-static inline cx cexp_(cx a) { double complex r = cexp(CMPLX(a.re, a.im)); return cx_(creal(r), cimag(r)); }
+static inline cx csqrt_(cx a) { rcomplex_t r = RM(csqrt)(RCMPLX(a.re, a.im)); return cx_(RM(creal)(r), RM(cimag)(r)); }
+static inline cx cexp_(cx a) { rcomplex_t r = RM(cexp)(RCMPLX(a.re, a.im)); return cx_(RM(creal)(r), RM(cimag)(r)); }
 static inline cx cneg(cx a) { return cx_(-a.re, -a.im); }
-static inline cx radd(double r, cx a) { return cx_(r + a.re, a.im); }   /* real + complex */
-static inline cx rsub(double r, cx a) { return cx_(r - a.re, -a.im); }  /* real - complex */
+static inline cx radd(real_t r, cx a) { return cx_(r + a.re, a.im); }   /* real + complex */
+static inline cx rsub(real_t r, cx a) { return cx_(r - a.re, -a.im); }  /* real - complex */
 
 /* FD:441-448 cTanh: overflow-safe complex tanh */
 static cx cTanh(cx z)
@@ -103,17 +129,17 @@ static int coef_alloc(coef_t *w, int nL1, int nF, int nC)
 static void coef_free(coef_t *w) { free(w->un); free(w->Y); free(w->Yn); }
 
 /* FD:157-191 initCoefficients.  par/kappa/perm have the air layer prepended. */
-static void initCoefficients(coef_t *w, int nLayers, const double *frequencies,
-                             const double *lamda2 /* [F, C] */, const double *par,
-                             const double *kappa, const double *perm)
+static void initCoefficients(coef_t *w, int nLayers, const real_t *frequencies,
+                             const real_t *lamda2 /* [F, C] */, const real_t *par,
+                             const real_t *kappa, const real_t *perm)
 {
     const int nL1 = nLayers + 1, nF = w->nF, nC = w->nC;
     for (int k = 0; k < nL1; ++k) {
-        double p = par[k];
-        double mu = mu0() * (1.0 + kappa[k]);
-        double eps = eps0() * (1.0 + perm[k]);
+        real_t p = par[k];
+        real_t mu = mu0() * (1.0 + kappa[k]);
+        real_t eps = eps0() * (1.0 + perm[k]);
         for (int i = 0; i < nF; ++i) {
-            double omega = 2.0 * PI * frequencies[i];  /* FD:166-168 */
+            real_t omega = 2.0 * PI * frequencies[i];  /* FD:166-168 */
             cx yn = cx_(p, omega * eps);                /* FD:176 */
             cx zn = cx_(0.0, omega * mu);               /* FD:177 */
             cx ynzn = cmul(yn, zn);                     /* FD:178 */
@@ -132,11 +158,11 @@ static void initCoefficients(coef_t *w, int nLayers, const double *frequencies,
 }
 
 /* FD:194-219 M1_0: admittance recursion, returns rTE[F,C], u0[F,C] */
-static void M1_0(coef_t *w, int nLayers, const double *thk, cx *rTE, cx *u0)
+static void M1_0(coef_t *w, int nLayers, const real_t *thk, cx *rTE, cx *u0)
 {
     const int nF = w->nF, nC = w->nC;
     for (int k = nLayers - 1; k > 0; --k) {
-        double t = thk[k];
+        real_t t = thk[k];
         for (int i = 0; i < nF; ++i)
             for (int jc = 0; jc < nC; ++jc) {
                 cx Yn_ = w->Yn[IDX(w, k, i, jc)];
@@ -170,8 +196,8 @@ static int g_exact_jacobian = 0;
 void oracle_set_exact_jacobian(int exact) { g_exact_jacobian = exact != 0; }
 
 /* FD:222-303 M1_1: recursion + per-layer sensitivities sens[L,F,C] */
-static void M1_1(coef_t *w, int nLayers, const double *frequencies, const double *thk,
-                 const double *par, const double *kappa, cx *u0, cx *sens)
+static void M1_1(coef_t *w, int nLayers, const real_t *frequencies, const real_t *thk,
+                 const real_t *par, const real_t *kappa, cx *u0, cx *sens)
 {
     const int nF = w->nF, nC = w->nC;
     const size_t FC = (size_t)nF * nC;
@@ -179,10 +205,10 @@ static void M1_1(coef_t *w, int nLayers, const double *frequencies, const double
 
     for (int k = nLayers - 1; k > 0; --k) {
         int k1 = k + 1, k2 = k - 1;
-        double p = par[k], t = thk[k];
-        double mu = mu0() * (1.0 + kappa[k]);
+        real_t p = par[k], t = thk[k];
+        real_t mu = mu0() * (1.0 + kappa[k]);
         for (int i = 0; i < nF; ++i) {
-            double omega = 2.0 * PI * frequencies[i];
+            real_t omega = 2.0 * PI * frequencies[i];
             cx oTmp = cx_(0.0, omega * mu * t); /* FD:245 */
             for (int jc = 0; jc < nC; ++jc) {
                 cx Yn_ = w->Yn[IDX(w, k, i, jc)];
@@ -213,7 +239,7 @@ static void M1_1(coef_t *w, int nLayers, const double *frequencies, const double
         }
     }
     {
-        double p = par[nLayers];
+        real_t p = par[nLayers];
         for (int i = 0; i < nF; ++i)
             for (int jc = 0; jc < nC; ++jc) /* FD:277-279 */
                 sens[(size_t)(nLayers - 1) * FC + (size_t)i * nC + jc] =
@@ -240,14 +266,14 @@ static void M1_1(coef_t *w, int nLayers, const double *frequencies, const double
 }
 
 /* FD:130-154 calcFdemSensitivity1D */
-static void calcFdemSensitivity1D(coef_t *w, int nLayers, const double *frequencies,
-                                  const double *lamda2, const double *par, const double *kappa,
-                                  const double *perm, const double *thk, cx *u0, cx *sens)
+static void calcFdemSensitivity1D(coef_t *w, int nLayers, const real_t *frequencies,
+                                  const real_t *lamda2, const real_t *par, const real_t *kappa,
+                                  const real_t *perm, const real_t *thk, cx *u0, cx *sens)
 {
     const int nF = w->nF, nC = w->nC;
     initCoefficients(w, nLayers, frequencies, lamda2, par, kappa, perm);
     if (nLayers == 1) {
-        double p = par[1];
+        real_t p = par[1];
         for (int i = 0; i < nF; ++i)
             for (int jc = 0; jc < nC; ++jc) {
                 size_t q = (size_t)i * nC + jc;
@@ -265,18 +291,18 @@ static void calcFdemSensitivity1D(coef_t *w, int nLayers, const double *frequenc
 }
 
 /* FD:410-438 Hzz */
-static void Hzz(double tHeight, double rHeight, double moments, double separation,
-                const cx *rTE, const cx *u0, const double *w0, const double *lamda0, cx *H, cx *H0)
+static void Hzz(real_t tHeight, real_t rHeight, real_t moments, real_t separation,
+                const cx *rTE, const cx *u0, const real_t *w0, const real_t *lamda0, cx *H, cx *H0)
 {
-    double hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
-    double a2 = moments / (4.0 * PI * separation);
+    real_t hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
+    real_t a2 = moments / (4.0 * PI * separation);
     cx h = cx_(0, 0), h0 = cx_(0, 0);
     for (int jc = 0; jc < NC0; ++jc) {
-        double w0_ = a2 * w0[jc];
+        real_t w0_ = a2 * w0[jc];
         cx u0_ = u0[jc];
-        double J0_ = lamda0[jc];
+        real_t J0_ = lamda0[jc];
         cx a0 = cexp_(cscale(cneg(u0_), hSum));
-        cx a1 = cdiv(cx_(pow(J0_, 3.0), 0.0), u0_);
+        cx a1 = cdiv(cx_(RM(pow)(J0_, 3.0), 0.0), u0_);
         cx k = cmul(cadd(a0, cmul(rTE[jc], cexp_(cscale(u0_, hDiff)))), a1);
         h = cadd(h, cscale(k, w0_));
         k = cmul(a0, a1);
@@ -286,63 +312,63 @@ static void Hzz(double tHeight, double rHeight, double moments, double separatio
 }
 
 /* FD:306-355 Hxx */
-static void Hxx(double tHeight, double rHeight, double moments, double rx, double separation,
-                const cx *rTEj0, const double *w0, const double *lamda0, const double *lamda02,
-                const cx *rTEj1, const double *w1, const double *lamda1, cx *H, cx *H0)
+static void Hxx(real_t tHeight, real_t rHeight, real_t moments, real_t rx, real_t separation,
+                const cx *rTEj0, const real_t *w0, const real_t *lamda0, const real_t *lamda02,
+                const cx *rTEj1, const real_t *w1, const real_t *lamda1, cx *H, cx *H0)
 {
-    double hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
-    double r = 1.0 / separation;
-    double c0 = -(moments / (4.0 * PI)) * r;
-    double d0 = c0 * pow(rx * r, 2.0);
-    double d1 = c0 * (r - ((2.0 * pow(rx, 2.0)) * pow(r, 3.0)));
+    real_t hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
+    real_t r = 1.0 / separation;
+    real_t c0 = -(moments / (4.0 * PI)) * r;
+    real_t d0 = c0 * RM(pow)(rx * r, 2.0);
+    real_t d1 = c0 * (r - ((2.0 * RM(pow)(rx, 2.0)) * RM(pow)(r, 3.0)));
     cx h = cx_(0, 0), h0 = cx_(0, 0);
     for (int jc = 0; jc < NC1; ++jc) {
         if (jc < NC0) {
-            double w0_ = d0 * w0[jc];
-            double J0_ = lamda0[jc];
-            double a1 = lamda02[jc];
-            double a0 = exp(-J0_ * hSum);
-            cx k = cscale(rsub(a0, cscale(rTEj0[jc], exp(J0_ * hDiff))), a1);
+            real_t w0_ = d0 * w0[jc];
+            real_t J0_ = lamda0[jc];
+            real_t a1 = lamda02[jc];
+            real_t a0 = RM(exp)(-J0_ * hSum);
+            cx k = cscale(rsub(a0, cscale(rTEj0[jc], RM(exp)(J0_ * hDiff))), a1);
             h = cadd(h, cscale(k, w0_));
-            double k1 = a0 * a1;
+            real_t k1 = a0 * a1;
             h0 = cx_(h0.re + k1 * w0_, h0.im);
         }
-        double w1_ = d1 * w1[jc];
-        double J1_ = lamda1[jc];
-        double b0 = exp(-J1_ * hSum);
-        cx k2 = cscale(rsub(b0, cscale(rTEj1[jc], exp(J1_ * hDiff))), J1_);
+        real_t w1_ = d1 * w1[jc];
+        real_t J1_ = lamda1[jc];
+        real_t b0 = RM(exp)(-J1_ * hSum);
+        cx k2 = cscale(rsub(b0, cscale(rTEj1[jc], RM(exp)(J1_ * hDiff))), J1_);
         h = cadd(h, cscale(k2, w1_));
-        double k3 = b0 * J1_;
+        real_t k3 = b0 * J1_;
         h0 = cx_(h0.re + k3 * w1_, h0.im);
     }
     *H = h; *H0 = h0;
 }
 
 /* FD:358-381 Hxz (tid 3) and FD:384-408 Hzx (tid 7; exponent uses u1) */
-static void Hxz(double tHeight, double rHeight, double moments, double rx, double separation,
-                const cx *rTE1, const double *w1, const double *lamda1, const double *lamda12, cx *H, cx *H0)
+static void Hxz(real_t tHeight, real_t rHeight, real_t moments, real_t rx, real_t separation,
+                const cx *rTE1, const real_t *w1, const real_t *lamda1, const real_t *lamda12, cx *H, cx *H0)
 {
-    double hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
-    double d1 = (rx * moments) / (4.0 * PI * separation);
+    real_t hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
+    real_t d1 = (rx * moments) / (4.0 * PI * separation);
     cx h = cx_(0, 0), h0 = cx_(0, 0);
     for (int jc = 0; jc < NC1; ++jc) {
-        double w1_ = d1 * w1[jc], J1_ = lamda1[jc], a1 = lamda12[jc];
-        double b0 = exp(-J1_ * hSum);
-        cx k = cscale(rsub(b0, cscale(rTE1[jc], exp(J1_ * hDiff))), a1);
+        real_t w1_ = d1 * w1[jc], J1_ = lamda1[jc], a1 = lamda12[jc];
+        real_t b0 = RM(exp)(-J1_ * hSum);
+        cx k = cscale(rsub(b0, cscale(rTE1[jc], RM(exp)(J1_ * hDiff))), a1);
         h = cadd(h, cscale(k, w1_));
-        double kk = b0 * a1;
+        real_t kk = b0 * a1;
         h0 = cx_(h0.re + kk * w1_, h0.im);
     }
     *H = h; *H0 = h0;
 }
-static void Hzx(double tHeight, double rHeight, double moments, double rx, double separation,
-                const cx *rTE1, const cx *u1, const double *w1, const double *lamda12, cx *H, cx *H0)
+static void Hzx(real_t tHeight, real_t rHeight, real_t moments, real_t rx, real_t separation,
+                const cx *rTE1, const cx *u1, const real_t *w1, const real_t *lamda12, cx *H, cx *H0)
 {
-    double hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
-    double d1 = (rx * moments) / (4.0 * PI * separation);
+    real_t hSum = rHeight + tHeight, hDiff = rHeight - tHeight;
+    real_t d1 = (rx * moments) / (4.0 * PI * separation);
     cx h = cx_(0, 0), h0 = cx_(0, 0);
     for (int jc = 0; jc < NC1; ++jc) {
-        double w1_ = d1 * w1[jc], a1 = lamda12[jc];
+        real_t w1_ = d1 * w1[jc], a1 = lamda12[jc];
         cx u1_ = u1[jc];
         cx b0 = cexp_(cscale(cneg(u1_), hSum));
         cx k = cscale(csub(b0, cmul(rTE1[jc], cexp_(cscale(u1_, hDiff)))), a1);
@@ -362,9 +388,9 @@ static int uses_j0(const int32_t *tid, int nF)
     return 0;
 }
 
-static int hankel(int id, int i, const double *tHeight, const double *rHeight, const double *moments,
-                  const double *rx, const double *separation, const double *w0, const double *lamda0,
-                  const double *lamda02, const double *w1, const double *lamda1, const double *lamda12,
+static int hankel(int id, int i, const real_t *tHeight, const real_t *rHeight, const real_t *moments,
+                  const real_t *rx, const real_t *separation, const real_t *w0, const real_t *lamda0,
+                  const real_t *lamda02, const real_t *w1, const real_t *lamda1, const real_t *lamda12,
                   const cx *r0, const cx *u0j0, const cx *r1, const cx *u0j1, cx *H, cx *H0)
 {
     switch (id) { /* FD:57-66 */
@@ -381,21 +407,21 @@ static int hankel(int id, int i, const double *tHeight, const double *rHeight, c
     }
 }
 
-static void prepend_air(int nLayers, const double *src, double *dst)
-{ dst[0] = 0.0; memcpy(dst + 1, src, (size_t)nLayers * sizeof(double)); }
+static void prepend_air(int nLayers, const real_t *src, real_t *dst)
+{ dst[0] = 0.0; memcpy(dst + 1, src, (size_t)nLayers * sizeof(real_t)); }
 
 /* FD:24-68 nbFdem1dfwd.  out = complex128[F] as interleaved (re, im). returns 0 / -1 (bad tid) */
-int oracle_fdem1dfwd(int nF, int nLayers, const int32_t *tid, const double *frequencies,
-                     const double *tHeight, const double *rHeight, const double *moments,
-                     const double *rx, const double *separation, const double *w0,
-                     const double *lamda0, const double *lamda02, const double *w1,
-                     const double *lamda1, const double *lamda12, const double *scale,
-                     const double *conductivity, const double *susceptibility,
-                     const double *permeability, const double *thickness, double *out)
+int oracle_fdem1dfwd(int nF, int nLayers, const int32_t *tid, const real_t *frequencies,
+                     const real_t *tHeight, const real_t *rHeight, const real_t *moments,
+                     const real_t *rx, const real_t *separation, const real_t *w0,
+                     const real_t *lamda0, const real_t *lamda02, const real_t *w1,
+                     const real_t *lamda1, const real_t *lamda12, const real_t *scale,
+                     const real_t *conductivity, const real_t *susceptibility,
+                     const real_t *permeability, const real_t *thickness, real_t *out)
 {
     const int nL1 = nLayers + 1;
-    double *par = (double *)malloc(4 * (size_t)nL1 * sizeof(double));
-    double *kappa = par + nL1, *perm = kappa + nL1, *thk = perm + nL1;
+    real_t *par = (real_t *)malloc(4 * (size_t)nL1 * sizeof(real_t));
+    real_t *kappa = par + nL1, *perm = kappa + nL1, *thk = perm + nL1;
     prepend_air(nLayers, conductivity, par);
     prepend_air(nLayers, susceptibility, kappa);
     prepend_air(nLayers, permeability, perm);
@@ -420,7 +446,7 @@ int oracle_fdem1dfwd(int nF, int nLayers, const int32_t *tid, const double *freq
         if (hankel(tid[i], i, tHeight, rHeight, moments, rx, separation, w0, lamda0, lamda02, w1,
                    lamda1, lamda12, r0, u0, r1, u1, &H, &H0)) { rc = -1; out[2 * i] = out[2 * i + 1] = NAN; continue; }
         cx q = cdiv(csub(H, H0), H0);         /* FD:68  1e6 * scale * ((H - H0) / H0) */
-        double s = 1.e6 * scale[i];
+        real_t s = 1.e6 * scale[i];
         out[2 * i] = s * q.re; out[2 * i + 1] = s * q.im;
     }
     if (useJ0) { coef_free(&c0); free(r0); }
@@ -429,17 +455,17 @@ int oracle_fdem1dfwd(int nF, int nLayers, const int32_t *tid, const double *freq
 }
 
 /* FD:71-121 nbFdem1dsen.  J = complex128[F, L] interleaved. */
-int oracle_fdem1dsen(int nF, int nLayers, const int32_t *tid, const double *frequencies,
-                     const double *tHeight, const double *rHeight, const double *moments,
-                     const double *rx, const double *separation, const double *w0,
-                     const double *lamda0, const double *lamda02, const double *w1,
-                     const double *lamda1, const double *lamda12, const double *scale,
-                     const double *conductivity, const double *susceptibility,
-                     const double *permeability, const double *thickness, double *J)
+int oracle_fdem1dsen(int nF, int nLayers, const int32_t *tid, const real_t *frequencies,
+                     const real_t *tHeight, const real_t *rHeight, const real_t *moments,
+                     const real_t *rx, const real_t *separation, const real_t *w0,
+                     const real_t *lamda0, const real_t *lamda02, const real_t *w1,
+                     const real_t *lamda1, const real_t *lamda12, const real_t *scale,
+                     const real_t *conductivity, const real_t *susceptibility,
+                     const real_t *permeability, const real_t *thickness, real_t *J)
 {
     const int nL1 = nLayers + 1;
-    double *par = (double *)malloc(4 * (size_t)nL1 * sizeof(double));
-    double *kappa = par + nL1, *perm = kappa + nL1, *thk = perm + nL1;
+    real_t *par = (real_t *)malloc(4 * (size_t)nL1 * sizeof(real_t));
+    real_t *kappa = par + nL1, *perm = kappa + nL1, *thk = perm + nL1;
     prepend_air(nLayers, conductivity, par);
     prepend_air(nLayers, susceptibility, kappa);
     prepend_air(nLayers, permeability, perm);
@@ -462,7 +488,7 @@ int oracle_fdem1dsen(int nF, int nLayers, const int32_t *tid, const double *freq
             cx dH, dH0;
             const cx *sk0 = s0 ? s0 + (size_t)k * nF * NC0 : NULL;
             const cx *sk1 = s1 + (size_t)k * nF * NC1;
-            double *o = J + 2 * ((size_t)i * nLayers + k);
+            real_t *o = J + 2 * ((size_t)i * nLayers + k);
             if (hankel(tid[i], i, tHeight, rHeight, moments, rx, separation, w0, lamda0, lamda02, w1,
                        lamda1, lamda12, sk0, u0, sk1, u1, &dH, &dH0)) { rc = -1; o[0] = o[1] = NAN; continue; }
             /* FD:117-119  1e6 * scale[i] * (dH - dH0) / dH0 : ((s * d) / dH0) */
@@ -481,24 +507,24 @@ int oracle_fdem1dsen(int nF, int nLayers, const int32_t *tid, const double *freq
  * diagonal matrix: -(Na/2) ln(2 pi) - 0.5 * sum ln var_i - 0.5 * sum r_i^2 / var_i.
  * pred/obs: [N]; returns chi2, logL, n_active.
  */
-void oracle_gauss_loglike(int N, const double *pred, const double *obs, double rel, double add,
-                          double *std_out, double *chi2, double *logL, int *n_active)
+void oracle_gauss_loglike(int N, const real_t *pred, const real_t *obs, real_t rel, real_t add,
+                          real_t *std_out, real_t *chi2, real_t *logL, int *n_active)
 {
-    double s2 = 0.0, logdet = 0.0;
+    real_t s2 = 0.0, logdet = 0.0;
     int na = 0;
     for (int i = 0; i < N; ++i) {
-        double variance = pow(rel * obs[i], 2.0) + pow(add, 2.0); /* DP:274 */
-        double sd = sqrt(variance);
+        real_t variance = RM(pow)(rel * obs[i], 2.0) + RM(pow)(add, 2.0); /* DP:274 */
+        real_t sd = RM(sqrt)(variance);
         if (std_out) std_out[i] = sd;
         int active = (obs[i] > 0.0) && !isnan(obs[i]);           /* EmDataPoint.py:54-56 */
         if (!active) continue;
-        double r = (pred[i] - obs[i]) * (1.0 / sd);               /* DP:523-524 */
+        real_t r = (pred[i] - obs[i]) * (1.0 / sd);               /* DP:523-524 */
         s2 += r * r;
-        logdet += log(variance);
+        logdet += RM(log)(variance);
         ++na;
     }
     *chi2 = s2;
-    *logL = -(0.5 * na) * log(2.0 * PI) - 0.5 * logdet - 0.5 * s2;
+    *logL = -(0.5 * na) * RM(log)(2.0 * PI) - 0.5 * logdet - 0.5 * s2;
     if (n_active) *n_active = na;
 }
 
@@ -511,13 +537,24 @@ void oracle_gauss_loglike(int N, const double *pred, const double *obs, double r
  * pred[B, 2F] = [Re(out_0..F-1), Im(out_0..F-1)] (FdemDataPoint.py:544-545).
  * OpenMP over soundings when compiled with -fopenmp.
  * ------------------------------------------------------------------------- */
+/* tH, rH of one sounding.  They are formed in fp64 in both builds (fdem1d.py:31-32 runs in fp64, and these rounded values are
+ * the inputs the forward solve is a function of); the long-double build widens them exactly. */
+static void sensor_heights(int nF, real_t height, const real_t *tx_z, const real_t *rx_z, real_t *tH, real_t *rH)
+{
+    for (int i = 0; i < nF; ++i) {
+        double t = (double)height + (double)tx_z[i];
+        double r = -t + (double)rx_z[i];
+        tH[i] = t; rH[i] = r;
+    }
+}
+
 int oracle_fdem_forward_loglike_batch(
-    int B, int nF, int Lmax, const int32_t *tid, const double *frequencies, const double *tx_z,
-    const double *rx_z, const double *tx_moment, const double *scale, const double *rx_off,
-    const double *separation, const double *w0, const double *lamda0, const double *lamda02,
-    const double *w1, const double *lamda1, const double *lamda12, const int32_t *nlayers,
-    const double *sigma, const double *thk, const double *height, const double *obs,
-    const double *rel, const double *add, double *pred, double *chi2, double *logL, int nthreads)
+    int B, int nF, int Lmax, const int32_t *tid, const real_t *frequencies, const real_t *tx_z,
+    const real_t *rx_z, const real_t *tx_moment, const real_t *scale, const real_t *rx_off,
+    const real_t *separation, const real_t *w0, const real_t *lamda0, const real_t *lamda02,
+    const real_t *w1, const real_t *lamda1, const real_t *lamda12, const int32_t *nlayers,
+    const real_t *sigma, const real_t *thk, const real_t *height, const real_t *obs,
+    const real_t *rel, const real_t *add, real_t *pred, real_t *chi2, real_t *logL, int nthreads)
 {
     int rc = 0;
 #ifdef _OPENMP
@@ -525,20 +562,55 @@ int oracle_fdem_forward_loglike_batch(
 #pragma omp parallel for schedule(dynamic, 16) reduction(| : rc)
 #endif
     for (int b = 0; b < B; ++b) {
-        double tH[64], rH[64], outc[128], zero[64];
+        real_t tH[64], rH[64], outc[128], zero[64];
         int L = nlayers[b];
-        double *z0 = L <= 64 ? zero : (double *)calloc((size_t)L, sizeof(double));
+        real_t *z0 = L <= 64 ? zero : (real_t *)calloc((size_t)L, sizeof(real_t));
         if (L <= 64) memset(zero, 0, sizeof(zero));
-        for (int i = 0; i < nF; ++i) { tH[i] = height[b] + tx_z[i]; rH[i] = -tH[i] + rx_z[i]; }
+        sensor_heights(nF, height[b], tx_z, rx_z, tH, rH);
         int r = oracle_fdem1dfwd(nF, L, tid, frequencies, tH, rH, tx_moment, rx_off, separation, w0, lamda0,
                                  lamda02, w1, lamda1, lamda12, scale, sigma + (size_t)b * Lmax, z0, z0,
                                  thk + (size_t)b * Lmax, outc);
         rc |= (r != 0);
-        double *p = pred + (size_t)b * 2 * nF;
+        real_t *p = pred + (size_t)b * 2 * nF;
         for (int i = 0; i < nF; ++i) { p[i] = outc[2 * i]; p[nF + i] = outc[2 * i + 1]; }
         if (obs)
             oracle_gauss_loglike(2 * nF, p, obs + (size_t)b * 2 * nF, rel[b], add[b], NULL, chi2 + b, logL + b, NULL);
         if (L > 64) free(z0);
+    }
+    return rc ? -1 : 0;
+}
+
+/* Batched Jacobian, same inputs as the driver above: J[B, 2F, Lmax] = d pred / d ln sigma, rows [Re(0..F-1), Im(0..F-1)],
+ * zero beyond a sounding's own layers.  Reference formula or true derivative as oracle_set_exact_jacobian says. */
+int oracle_fdem_sens_batch(
+    int B, int nF, int Lmax, const int32_t *tid, const real_t *frequencies, const real_t *tx_z,
+    const real_t *rx_z, const real_t *tx_moment, const real_t *scale, const real_t *rx_off,
+    const real_t *separation, const real_t *w0, const real_t *lamda0, const real_t *lamda02,
+    const real_t *w1, const real_t *lamda1, const real_t *lamda12, const int32_t *nlayers,
+    const real_t *sigma, const real_t *thk, const real_t *height, real_t *J, int nthreads)
+{
+    int rc = 0;
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 4) reduction(| : rc)
+#endif
+    for (int b = 0; b < B; ++b) {
+        real_t tH[64], rH[64];
+        int L = nlayers[b];
+        real_t *z0 = (real_t *)calloc((size_t)L, sizeof(real_t));
+        real_t *Jc = (real_t *)malloc(2 * (size_t)nF * L * sizeof(real_t));
+        sensor_heights(nF, height[b], tx_z, rx_z, tH, rH);
+        int r = oracle_fdem1dsen(nF, L, tid, frequencies, tH, rH, tx_moment, rx_off, separation, w0, lamda0,
+                                 lamda02, w1, lamda1, lamda12, scale, sigma + (size_t)b * Lmax, z0, z0,
+                                 thk + (size_t)b * Lmax, Jc);
+        rc |= (r != 0);
+        real_t *o = J + (size_t)b * 2 * nF * Lmax;
+        for (int i = 0; i < nF; ++i)
+            for (int k = 0; k < Lmax; ++k) {
+                o[(size_t)i * Lmax + k] = k < L ? Jc[2 * ((size_t)i * L + k)] : 0.0;
+                o[(size_t)(nF + i) * Lmax + k] = k < L ? Jc[2 * ((size_t)i * L + k) + 1] : 0.0;
+            }
+        free(Jc); free(z0);
     }
     return rc ? -1 : 0;
 }

@@ -177,6 +177,184 @@ def gauss_loglike(pred, obs, rel, add):
     return sd, chi2.value, logl.value, na.value
 
 
+def _sysargs_batch(s, conv):
+    return [_i(s.tid), conv(s.frequencies), conv(s.tx_xyz[:, 2]), conv(s.rx_xyz[:, 2]), conv(s.tx_moment), conv(s.scale),
+            conv(s.rx_off), conv(s.separation)]
+
+
+def sensitivity_batch(system, nlayers, sigma, thk, height, nthreads=1):
+    """Batched fp64 Jacobian J[B, 2F, Lmax] (rows [Re, Im], zero beyond a sounding's layers); mode as ``set_exact_jacobian``."""
+    s = system
+    nl, pnl = _i(nlayers)
+    sig, psig = _d(sigma)
+    B, Lmax = sig.shape
+    th, pth = _d(thk)
+    h, ph = _d(height)
+    assert s.nF <= 64 and nl.size == B and th.shape == sig.shape and h.size == B
+    J = np.empty((B, 2 * s.nF, Lmax))
+    keep = _sysargs_batch(s, _d) + [_d(s.w0), _d(s.lamda0), _d(s.lamda02), _d(s.w1), _d(s.lamda1), _d(s.lamda12)]
+    rc = lib().oracle_fdem_sens_batch(ctypes.c_int(B), ctypes.c_int(s.nF), ctypes.c_int(Lmax), *[k[1] for k in keep],
+                                      pnl, psig, pth, ph, J.ctypes.data_as(_dp), ctypes.c_int(nthreads))
+    if rc != 0:
+        raise ValueError("unsupported tensor id in system")
+    return J
+
+
+# ---- the long-double build (libgbp_oracle_ld.so): the same C file with every real a long double -------------------------
+# Inputs are the fp64 values the fp64 oracle and the kernels see (frequencies, geometry, lamda, weights, sigma, thickness,
+# height; tHeight / rHeight are formed in fp64 as fdem1d.py does) widened exactly; lamda^2 is formed here in long double.
+# Outputs are np.longdouble.  Every converted array stays referenced by a local until the ctypes call has returned.
+_LIB_LD = None
+MAX_THREADS_LD = 16
+
+
+def lib_ld():
+    global _LIB_LD
+    if _LIB_LD is None:
+        so = os.path.join(_HERE, "libgbp_oracle_ld.so")
+        if not os.path.exists(so):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "-B", "libgbp_oracle_ld.so"])
+        L = ctypes.CDLL(so)
+        L.oracle_real_mant_dig.restype = ctypes.c_int
+        for f in ("oracle_fdem1dfwd", "oracle_fdem1dsen", "oracle_fdem_forward_loglike_batch", "oracle_fdem_sens_batch"):
+            getattr(L, f).restype = ctypes.c_int
+        L.oracle_gauss_loglike.restype = None
+        L.oracle_set_exact_jacobian.restype = None
+        # the C long double must be numpy's longdouble, and wider than fp64 by the 11 bits the bars reason with
+        assert L.oracle_real_mant_dig() >= 64, "long double has a %d-bit mantissa, 64 needed" % L.oracle_real_mant_dig()
+        assert np.finfo(np.longdouble).nmant + 1 == L.oracle_real_mant_dig() and \
+            np.dtype(np.longdouble).itemsize == ctypes.sizeof(ctypes.c_longdouble)
+        _LIB_LD = L
+    return _LIB_LD
+
+
+def mantissa_bits_ld():
+    """LDBL_MANT_DIG of the long-double library (64 on x86)."""
+    return lib_ld().oracle_real_mant_dig()
+
+
+def _q(a):
+    a = np.ascontiguousarray(a, dtype=np.longdouble)
+    return a, ctypes.c_void_p(a.ctypes.data)
+
+
+def _threads_ld(nthreads):
+    n = int(nthreads)
+    if n <= 0:
+        n = os.cpu_count() or 1
+    return max(1, min(n, MAX_THREADS_LD))
+
+
+def _tables_ld(s):
+    l0, l1 = np.asarray(s.lamda0, dtype=np.longdouble), np.asarray(s.lamda1, dtype=np.longdouble)
+    return [_q(s.w0), _q(l0), _q(l0 * l0), _q(s.w1), _q(l1), _q(l1 * l1)]
+
+
+def _one_ld(fn, system, conductivity, thickness, height, nout):
+    s = system
+    sig, psig = _q(conductivity)
+    L = sig.size
+    thk, pthk = _q(thickness)
+    assert thk.size == L
+    zeros, pz = _q(np.zeros(L))
+    tH, rH = _sysargs(s, float(height))          # fp64, as the fp64 oracle forms them
+    out = np.empty(2 * nout(L), dtype=np.longdouble)
+    keep = [_i(s.tid), _q(s.frequencies), _q(tH), _q(rH), _q(s.tx_moment), _q(s.rx_off), _q(s.separation)] + \
+        _tables_ld(s) + [_q(s.scale)]
+    rc = fn(ctypes.c_int(s.nF), ctypes.c_int(L), *[k[1] for k in keep], psig, pz, pz, pthk, ctypes.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise ValueError("unsupported tensor id in system")
+    del keep, sig, thk, zeros
+    return out[0::2] + 1j * out[1::2]
+
+
+def forward_ld(system, conductivity, thickness, height):
+    """``forward`` in long double -> clongdouble[F]."""
+    return _one_ld(lib_ld().oracle_fdem1dfwd, system, conductivity, thickness, height, lambda L: system.nF)
+
+
+def sensitivity_ld(system, conductivity, thickness, height, exact=False):
+    """``sensitivity`` in long double -> clongdouble[F, L]; ``exact``: the true derivative of the forward recursion."""
+    L = np.size(conductivity)
+    lib_ld().oracle_set_exact_jacobian(ctypes.c_int(1 if exact else 0))
+    try:
+        return _one_ld(lib_ld().oracle_fdem1dsen, system, conductivity, thickness, height,
+                       lambda L: system.nF * L).reshape(system.nF, L)
+    finally:
+        lib_ld().oracle_set_exact_jacobian(ctypes.c_int(0))
+
+
+def gauss_loglike_ld(pred, obs, rel, add):
+    """``gauss_loglike`` in long double: (std[N], chi2, logL, n_active), the first three np.longdouble."""
+    p, pp = _q(pred)
+    o, po = _q(obs)
+    N = p.size
+    sd = np.empty(N, dtype=np.longdouble)
+    res = np.empty(2, dtype=np.longdouble)
+    na = ctypes.c_int()
+    ra = ctypes.c_longdouble(np.float64(rel))
+    lib_ld().oracle_gauss_loglike(ctypes.c_int(N), pp, po, ra, ctypes.c_longdouble(np.float64(add)),
+                                  ctypes.c_void_p(sd.ctypes.data), ctypes.c_void_p(res.ctypes.data),
+                                  ctypes.c_void_p(res.ctypes.data + res.itemsize), ctypes.byref(na))
+    del p, o
+    return sd, res[0], res[1], na.value
+
+
+def forward_loglike_batch_ld(system, nlayers, sigma, thk, height, obs=None, rel=None, add=None, nthreads=0):
+    """``forward_loglike_batch`` in long double (OpenMP over soundings, at most 16 threads): pred[B, 2F], chi2[B], logL[B]
+    as np.longdouble.  ``obs`` may be fp64 or long double (predictions of this build, say)."""
+    s = system
+    nl, pnl = _i(nlayers)
+    B = nl.size
+    sig, psig = _q(sigma)
+    Lmax = sig.shape[1]
+    th, pth = _q(thk)
+    h, ph = _q(height)
+    assert s.nF <= 64 and th.shape == sig.shape and h.size == B
+    pred = np.empty((B, 2 * s.nF), dtype=np.longdouble)
+    chi2 = np.full(B, np.nan, dtype=np.longdouble)
+    logl = np.full(B, np.nan, dtype=np.longdouble)
+    if obs is not None:
+        o, po = _q(obs)
+        r, pr = _q(np.broadcast_to(rel, (B,)))
+        a, pa = _q(np.broadcast_to(add, (B,)))
+    else:
+        o = r = a = po = pr = pa = None
+    keep = _sysargs_batch(s, _q) + _tables_ld(s)
+    rc = lib_ld().oracle_fdem_forward_loglike_batch(
+        ctypes.c_int(B), ctypes.c_int(s.nF), ctypes.c_int(Lmax), *[k[1] for k in keep], pnl, psig, pth, ph,
+        po, pr, pa, ctypes.c_void_p(pred.ctypes.data), ctypes.c_void_p(chi2.ctypes.data),
+        ctypes.c_void_p(logl.ctypes.data), ctypes.c_int(_threads_ld(nthreads)))
+    if rc != 0:
+        raise ValueError("unsupported tensor id in system")
+    del keep, sig, th, h, o, r, a
+    return pred, chi2, logl
+
+
+def sensitivity_batch_ld(system, nlayers, sigma, thk, height, exact=False, nthreads=0):
+    """``sensitivity_batch`` in long double -> np.longdouble J[B, 2F, Lmax]."""
+    s = system
+    nl, pnl = _i(nlayers)
+    sig, psig = _q(sigma)
+    B, Lmax = sig.shape
+    th, pth = _q(thk)
+    h, ph = _q(height)
+    assert s.nF <= 64 and nl.size == B and th.shape == sig.shape and h.size == B
+    J = np.empty((B, 2 * s.nF, Lmax), dtype=np.longdouble)
+    keep = _sysargs_batch(s, _q) + _tables_ld(s)
+    lib_ld().oracle_set_exact_jacobian(ctypes.c_int(1 if exact else 0))
+    try:
+        rc = lib_ld().oracle_fdem_sens_batch(ctypes.c_int(B), ctypes.c_int(s.nF), ctypes.c_int(Lmax),
+                                             *[k[1] for k in keep], pnl, psig, pth, ph, ctypes.c_void_p(J.ctypes.data),
+                                             ctypes.c_int(_threads_ld(nthreads)))
+    finally:
+        lib_ld().oracle_set_exact_jacobian(ctypes.c_int(0))
+    if rc != 0:
+        raise ValueError("unsupported tensor id in system")
+    del keep, sig, th, h
+    return J
+
+
 def forward_loglike_batch(system, nlayers, sigma, thk, height, obs=None, rel=None, add=None, nthreads=1):
     """Batched oracle (and the "port" CPU baseline of bench.py): returns pred[B,2F], chi2[B], logL[B]."""
     s = system

@@ -35,7 +35,10 @@ def test_device_math_accuracy_on_hardware():
     a = rng.uniform(-1e-5, 1.0, n) * np.exp(rng.uniform(-30, 3, n))
     b = np.exp(rng.uniform(np.log(1e-12), np.log(2.0), n))
     re, im = run(2, a, b, two=True)
-    z = np.sqrt(a.astype(np.longdouble) + 1j * b.astype(np.longdouble)) if False else np.sqrt(a + 1j * b)
+    assert np.finfo(np.longdouble).nmant >= 63
+    z = np.sqrt(a.astype(np.longdouble) + 1j * b.astype(np.longdouble))
+    assert z.dtype == np.clongdouble and np.max(np.abs((re + 1j * im) - z) / np.abs(z)) < 1.5e-15
+    z = np.sqrt(a + 1j * b)
     assert np.max(np.abs((re + 1j * im) - z) / np.abs(z)) < 1.5e-15
     x = np.exp(rng.uniform(-200, 200, n))
     assert np.max(np.abs(run(3, x) * x - 1.0)) < 5e-16

@@ -148,6 +148,9 @@ def test_device_math_accuracy(emul):
     emul.emul_csqrt(len(a), D(a)[1], D(b)[1], re.ctypes.data_as(dp), im.ctypes.data_as(dp))
     z = np.sqrt(a + 1j * b)
     assert np.max(np.abs((re + 1j * im) - z) / np.abs(z)) < 1e-15
+    assert np.finfo(np.longdouble).nmant >= 63
+    zl = np.sqrt(a.astype(np.longdouble) + 1j * b.astype(np.longdouble))      # the square root itself, not libm's fp64 rounding of it
+    assert zl.dtype == np.clongdouble and np.max(np.abs((re + 1j * im) - zl) / np.abs(zl)) < 1e-15
     x = np.exp(rng.uniform(-200, 200, 100000))
     y = np.empty_like(x)
     emul.emul_rcp(len(x), D(x)[1], y.ctypes.data_as(dp))
@@ -177,8 +180,7 @@ def test_kernel_scheme_on_host_vs_reference_fixtures(emul, golden_npz, name):
 @pytest.mark.parametrize("name", ["resolve", "syn10", "mixed"])
 def test_jacobian_scheme_on_host_vs_reference_fixtures(emul, golden_npz, name):
     """sens_point (suffix-propagated chain rule) reproduces the reference's nbFdem1dsen fixtures (exact = 0),
-    and in exact mode it is the true derivative of the forward solve (central differences of the oracle)."""
-    from oracle import fdem_oracle as fo
+    and in exact mode it is the true derivative of the forward solve (central differences of the long-double oracle)."""
     s = oracle_system(name)
     keep = [I(s.tid), D(s.frequencies), D(s.tx_xyz[:, 2]), D(s.rx_xyz[:, 2]), D(s.tx_moment), D(s.scale),
             D(s.rx_off), D(s.separation), D(s.w0), D(s.lamda0), D(s.w1), D(s.lamda1)]
@@ -200,16 +202,18 @@ def test_jacobian_scheme_on_host_vs_reference_fixtures(emul, golden_npz, name):
     J = np.empty((2, 2 * s.nF, 5))
     emul.emul_fdem_sens(s.nF, *[q[1] for q in keep], 2, 5, I(np.full(2, 5))[1], D(sig)[1], D(thk)[1], D(h)[1], 1,
                         J.ctypes.data_as(dp))
-    eps = 1e-4      # the oracle forward carries ~5e-9 ppm rounding noise -> 5e-5 in the difference quotient
-    for b in range(2):
-        for m in range(5):
-            sp, sm = sig[b].copy(), sig[b].copy()
-            sp[m] *= np.exp(eps)
-            sm[m] *= np.exp(-eps)
-            fd = (fo.predicted_data(s, sp, thk[b], h[b]) - fo.predicted_data(s, sm, thk[b], h[b])) / (2 * eps)
-            # 'mixed' has ~6e-8 ppm of rounding noise in the oracle forward (non-zero hSum, real-exponent kernels)
-            atol = 2e-3 if name == "mixed" else 2e-4
-            assert np.all(np.abs(J[b, :, m] - fd) <= atol + 1e-6 * np.abs(fd)), (name, b, m)
+    # The difference quotient is taken of the long-double forward (Richardson-extrapolated, tests/test_forward_long_double.py), whose
+    # rounding is 2^-11 of the fp64 oracle's: what the quotient itself may be off by comes with it and is below 2e-6 ppm here, where
+    # the quotient of the fp64 oracle needed 2e-4 (2e-3 on `mixed`).  On top, the scheme's own distance from the long-double exact
+    # Jacobian: the largest J_exact scheme_bar of the system in tests/golden/fdem_ld_bars.json (a share of the parity bar, < 0.02).
+    import test_forward_long_double as ld
+    fd, allow = ld.richardson_fd(s, np.full(2, 5), sig, thk, h)
+    share = max(v["scheme_bar"] for k, v in ld.load_bars().items() if k.startswith(name + "/") and k.endswith("/J_exact"))
+    assert share < 0.02 and allow.max() < 2e-6, (share, float(allow.max()))
+    tol = allow + share * (PRED_ATOL + PRED_RTOL * np.abs(fd))
+    assert np.all(tol < 0.01 * (2e-4 + 1e-6 * np.abs(fd)))          # a hundred times tighter than the bar this replaces
+    err = np.abs(J - fd)
+    assert np.all(err <= tol), (name, float((err / tol).max()))
 
 
 @pytest.mark.parametrize("name", ["resolve", "syn10", "mixed"])
