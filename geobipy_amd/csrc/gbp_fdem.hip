@@ -2577,3 +2577,65 @@ extern "C" gbp_status gbp_section_draw(int L, const int64_t* ptr, int64_t total_
                                                                 draw_state, st);
     }
 }
+
+#include "gbp_section_graph.h"
+
+// Sections across lines (gbp_section_graph.h): K and the first messages, one launch per sweep with one workgroup per undirected edge,
+// the residuals of all sweeps in one launch, the beliefs.  Every refusal comes before any launch; no device array is read on the host.
+extern "C" gbp_status gbp_section_propagate(int S, int E, int n, const int32_t* eu, const int32_t* ev, const int32_t* n_used,
+                                            const double* score, const double* g, const double* d2, const int32_t* in_ptr,
+                                            const int32_t* in_edge, int sweeps, double damping, double* K, double* w, double* mu,
+                                            double* resid, double* belief, int32_t* state, double* residual, void* stream)
+{
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: S must be >= 0%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: E must lie in 0 .. 2^30 - 1%s");
+    if (n < 1 || n > section::GRAPH_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: n must lie in 1 .. 256%s");
+    if (sweeps < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: sweeps must be >= 1%s");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: damping must lie in [0, 1)%s");
+    if (E > 0 && S < 2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: an edge needs two soundings%s");
+    if ((long long)S + 2LL * E > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: S + 2 E out of range%s");
+    if (E > 0 && (long long)E > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: E * n * n out of range%s");
+    if (E > 0 && (long long)sweeps > 0x7fffffffffffffffLL / 16 / E) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: sweeps * 2 E out of range%s");
+    if (!residual) return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: residual is NULL%s");
+    if (S > 0 && (!n_used || !score || !in_ptr || !w || !belief || !state))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: NULL pointer (n_used, score, in_ptr, w, belief, state)%s");
+    if (E > 0 && (!eu || !ev || !g || !d2 || !in_edge || !K || !mu || !resid))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_propagate: NULL pointer (eu, ev, g, d2, in_edge, K, mu, resid)%s");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(section::THREADS);
+    const size_t half = (size_t)2 * E * n;                                  // one message buffer
+    if (E > 0) {
+        hipLaunchKernelGGL(section::k_graph_kernel, dim3((unsigned)E), block, 0, st, S, n, (const int*)eu, (const int*)ev, (const int*)n_used, g, d2, K);
+        GBP_HIP(hipGetLastError());
+    }
+    if (S > 0) {
+        hipLaunchKernelGGL(section::k_graph_init, dim3((unsigned)(S + 2 * E)), block, 0, st, S, E, n, (const int*)eu, (const int*)ev,
+                           (const int*)n_used, score, w, mu, mu ? mu + half : mu);
+        GBP_HIP(hipGetLastError());
+    }
+    for (int t = 0; E > 0 && t < sweeps; ++t) {
+        const double* from = mu + (size_t)(t & 1) * half;
+        double* to = mu + (size_t)((t + 1) & 1) * half;
+        double* r = resid + (size_t)t * 2 * E;
+#define GBP_GRAPH_SWEEP(DAMP, MAXN)                                                                                                      \
+    hipLaunchKernelGGL((section::k_graph_sweep<DAMP, MAXN>), dim3((unsigned)E), block, 0, st, S, E, n, (const int*)eu, (const int*)ev,     \
+                       (const int*)n_used, (const double*)w, (const double*)K, (const int*)in_ptr, (const int*)in_edge, from, to, damping, r)
+        if (n <= 64) {
+            if (damping != 0.0) GBP_GRAPH_SWEEP(true, 64);
+            else GBP_GRAPH_SWEEP(false, 64);
+        } else {
+            if (damping != 0.0) GBP_GRAPH_SWEEP(true, section::GRAPH_MAX_STATES);
+            else GBP_GRAPH_SWEEP(false, section::GRAPH_MAX_STATES);
+        }
+#undef GBP_GRAPH_SWEEP
+        GBP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(section::k_graph_residual, dim3((unsigned)sweeps), block, 0, st, 2LL * E, (const double*)resid, residual);
+    GBP_HIP(hipGetLastError());
+    if (S > 0) {
+        hipLaunchKernelGGL(section::k_graph_belief, dim3((unsigned)S), block, 0, st, E, n, (const int*)n_used, (const double*)w, (const int*)in_ptr,
+                           (const int*)in_edge, (const double*)(mu ? mu + (size_t)(sweeps & 1) * half : mu), belief, (int*)state);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}

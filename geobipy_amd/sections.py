@@ -43,9 +43,17 @@ Nothing outside the prefixes i < m_r, j < m_{r+1} of d2 is read, nor the entry o
 [--chains C] [--no-marginals] [--draws R [--seed N]] [--depth-axis N WIDTH [--percentiles P ...] [--exceed T ...]]`` writes
 ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``, ``track``, ``draw``, ``sections`` and ``lateral_products``
 refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
-after the run, like ``horizons.from_products``.  Left out on purpose: coupling across lines, carrying a sequence across launches, and
-learning ``tau`` (``log_partition`` is returned for whoever wants to scan it).  (The weighted re-binning by ``weight`` that this list
-used to name is ``lateral_products``.)
+after the run, like ``horizons.from_products``.  Left out on purpose: carrying a sequence across launches, and learning ``tau``
+(``log_partition`` is returned for whoever wants to scan it).  (The weighted re-binning by ``weight`` that this list used to name is
+``lateral_products``; coupling across lines is ``spatial``.)
+
+Across lines (gbp_section_propagate: csrc/gbp_section_graph.h).  ``neighbours`` joins every sounding to the next of
+its line and to the nearest sounding of every other line within ``max_distance``; ``edge_distance`` gives D^2 per edge through
+``cross_distance``; ``propagate`` runs synchronous sum-product message passing on that graph (``propagate_reference`` states the rule)
+and returns *beliefs*: the marginals on a forest, a documented approximation on a graph with loops; ``spatial`` is all of it for an
+ensemble, with the keys of ``sections`` that still have a meaning, and ``spatial_from_survey`` / ``from_survey(..., spatial=dict(
+max_distance=...))`` / ``--spatial MAX_DISTANCE [--sweeps N] [--damping L]`` (``<name>.spatial.npz``) for a survey.  Left out on
+purpose: max-product and joint draws on the graph, tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
 """
 import numpy as np
 import torch
@@ -586,13 +594,9 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
         del d2, res
         p0 = p1
     has = state >= 0
-    at = torch.arange(S, device=dev)
-    slot = torch.gather(rows.long(), 1, state.long().clamp(min=0)[:, None])[:, 0].clamp(min=0) if S else torch.zeros(0, dtype=torch.int64, device=dev)
     nanv = torch.full((), nan, **f64)
-    out = dict(state=state, slot=torch.where(has, slot, torch.full_like(slot, -1)).to(torch.int32), rows=rows, n_used=n_used,
-               section_k=torch.where(has, k[at, slot], torch.zeros_like(k[at, slot])),
-               section_edges=torch.where(has[:, None], edges[at, slot], nanv), section_sigma=torch.where(has[:, None], sigma[at, slot], nanv),
-               step_distance=step_distance, log_score=log_score)
+    out = _chosen_models(k, edges, sigma, rows, n_used, state)
+    out.update(step_distance=step_distance, log_score=log_score)
     if marginals:
         w = torch.where(has[:, None], weight, torch.zeros((), **f64))
         out["weight"] = weight
@@ -606,6 +610,19 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     if products is not None:
         out.update(lateral_products(ens, out, **products))
     return out
+
+
+def _chosen_models(k, edges, sigma, rows, n_used, state):
+    """What ``sections`` and ``spatial`` return of the chosen models: ``state``, ``slot`` (-1: none), ``rows``, ``n_used``, ``section_k``
+    (0: none) and ``section_edges`` / ``section_sigma`` (bit copies of the chosen slots; NaN: none)."""
+    S, dev = k.shape[0], k.device
+    has = state >= 0
+    at = torch.arange(S, device=dev)
+    slot = torch.gather(rows.long(), 1, state.long().clamp(min=0)[:, None])[:, 0].clamp(min=0) if S else torch.zeros(0, dtype=torch.int64, device=dev)
+    nanv = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    return dict(state=state, slot=torch.where(has, slot, torch.full_like(slot, -1)).to(torch.int32), rows=rows, n_used=n_used,
+                section_k=torch.where(has, k[at, slot], torch.zeros_like(k[at, slot])),
+                section_edges=torch.where(has[:, None], edges[at, slot], nanv), section_sigma=torch.where(has[:, None], sigma[at, slot], nanv))
 
 
 PRODUCT_KEYS = ("depth_edges", "percentiles", "thresholds")
@@ -721,6 +738,323 @@ def exceedance_area(k, edges, sigma, x, y, ptr, threshold, z0, z1, above=True):
     return _run_sums(width[None, :] * thick, p)
 
 
+# ---- across lines: belief propagation on the survey graph -----------------------------------------------------------
+
+MAX_GRAPH_STATES = 256
+MAX_SWEEPS = 65536
+SPATIAL_SUFFIX = ".spatial.npz"
+
+
+def _check_damping(damping, what):
+    if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) or not 0.0 <= damping < 1.0:
+        raise ValueError("%s: damping must be a number in [0, 1)" % what)
+    return float(damping)
+
+
+def _check_graph(eu, ev, g, d2, n_used, score, sweeps, damping, what):
+    """The host checks ``propagate`` and its reference share; returns eu, ev (numpy int64 [E]), n_used (numpy int64 [S]), sweeps and
+    damping."""
+    if d2.ndim != 3 or d2.shape[1] != d2.shape[2] or not 1 <= d2.shape[1] <= MAX_GRAPH_STATES:
+        raise ValueError("%s: d2 [E, n, n] with 1 <= n <= %d" % (what, MAX_GRAPH_STATES))
+    E, n = d2.shape[0], d2.shape[1]
+    nu = host(n_used).reshape(-1)
+    S = nu.size
+    if nu.dtype.kind not in "iu":
+        raise ValueError("%s: n_used must hold one integer per sounding" % what)
+    if np.any(nu < 1) or np.any(nu > n):
+        raise ValueError("%s: n_used must lie in 1 .. n (soundings without models are left out of the graph)" % what)
+    eu, ev = host(eu).reshape(-1), host(ev).reshape(-1)
+    if eu.size != E or ev.size != E or eu.dtype.kind not in "iu" or ev.dtype.kind not in "iu":
+        raise ValueError("%s: eu and ev must hold one integer per edge (%d)" % (what, E))
+    eu, ev = eu.astype(np.int64), ev.astype(np.int64)
+    if np.any(eu < 0) or np.any(ev >= S) or np.any(eu >= ev):
+        raise ValueError("%s: every edge needs 0 <= eu < ev < the number of soundings (%d)" % (what, S))
+    if np.any(np.diff(eu * S + ev) <= 0):
+        raise ValueError("%s: the edges must be sorted by (eu, ev) and hold no duplicates" % what)
+    if host(g).size != E:
+        raise ValueError("%s: g must hold one entry per edge" % what)
+    if score is not None and tuple(score.shape) != (S, n):
+        raise ValueError("%s: score must be [S, n]" % what)
+    return eu, ev, nu.astype(np.int64), check_int(sweeps, 1, MAX_SWEEPS, "%s: sweeps" % what), _check_damping(damping, what)
+
+
+def incoming(eu, ev, n_soundings):
+    """The CSR of every sounding's incoming directed edges (numpy int32): ``in_ptr`` [S + 1] and ``in_edge`` [2 E], sorted by the
+    sounding a message comes from.  Directed edge 2 e is eu[e] -> ev[e], 2 e + 1 is ev[e] -> eu[e]."""
+    eu, ev = np.asarray(eu, dtype=np.int64).reshape(-1), np.asarray(ev, dtype=np.int64).reshape(-1)
+    src, dst = np.empty(2 * eu.size, dtype=np.int64), np.empty(2 * eu.size, dtype=np.int64)
+    src[0::2], dst[0::2], src[1::2], dst[1::2] = eu, ev, ev, eu
+    in_edge = np.lexsort((src, dst)).astype(np.int32)
+    in_ptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=int(n_soundings)))]).astype(np.int32)
+    return in_ptr, in_edge
+
+
+def _nan_max(r, d):
+    """max that keeps a NaN once it has one."""
+    return d if (d > r or d != d) else r
+
+
+def propagate_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.0, dtype=np.float64):
+    """The rule of ``propagate`` in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the yardstick of the
+    rule's own rounding): synchronous sum-product message passing on the graph of S = len(n_used) soundings with the undirected edges
+    ``eu[e]`` < ``ev[e]`` (sorted by (eu, ev), no duplicates), ``g`` [E] and ``d2`` [E, n, n], entry [e, i, j] between state i of
+    eu[e] and state j of ev[e]; only the prefixes i < m_u, j < m_v are read (m_s = n_used[s] in 1 .. n).
+
+    w_s = exp(score[s]) (None: ones); K_e = exp(-(g[e] * d2[e])), one multiply and one exp per entry.  Directed edge 2 e is u -> v
+    and uses K_e, 2 e + 1 is v -> u and uses its transpose; the message mu[d] has m_dst entries and starts at 1 / m_dst.  One sweep
+    computes every message from the last sweep's.  For a -> b: h[i] = w_a[i] times mu[c -> a][i] over the neighbours c != b of a,
+    ascending c; u[j] = sum_i h[i] K[i, j], i ascending, u = u + h[i] * K[i]; tot = sum_j u[j], j ascending; mu' = u / tot; with
+    ``damping`` = lam != 0 mu' = (1 - lam) mu' + lam mu_old (lam = 0 skips the blend).  ``residual[t]`` is the largest |mu' - mu_old|
+    over the messages of sweep t (NaN if one of them is; 0.0 without edges).  After the last sweep belief_s = w_s times all incoming
+    messages (ascending neighbour), divided by its sum (i ascending), 0.0 for the states >= m_s; ``state[s]`` is its first maximum.
+    A sounding without edges gets its normalised w.  A zero tot gives NaN, as a zero scale does in ``track_reference``.
+
+    Exact on a tree once the sweeps reach its diameter (the residual is 0.0 from then on: every message has its final bits); on a
+    graph with loops a documented approximation: the output is a *belief*, not a marginal.
+
+    Returns ``belief`` [S, n] (``dtype``), ``state`` int32 [S] and ``residual`` [sweeps]."""
+    ft = np.dtype(dtype).type
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    eu, ev, nu, sweeps, damping = _check_graph(eu, ev, g, d2, n_used, score, sweeps, damping, "sections.propagate_reference")
+    E, n, S = d2.shape[0], d2.shape[1], nu.size
+    g = np.asarray(g, dtype=np.float64).reshape(-1).astype(ft)
+    w = [np.exp((np.zeros(nu[s]) if score is None else score[s, :nu[s]]).astype(ft)) for s in range(S)]
+    K = [np.exp(-(g[e] * d2[e, :nu[eu[e]], :nu[ev[e]]].astype(ft))) for e in range(E)]
+    in_ptr, in_edge = incoming(eu, ev, S)
+    src = np.empty(2 * E, dtype=np.int64)
+    src[0::2], src[1::2] = eu, ev
+    dst = np.empty(2 * E, dtype=np.int64)
+    dst[0::2], dst[1::2] = ev, eu
+    inc = [in_edge[in_ptr[s]:in_ptr[s + 1]] for s in range(S)]
+    msg = [np.full(nu[dst[d]], ft(1) / ft(nu[dst[d]]), dtype=ft) for d in range(2 * E)]
+    lam = ft(damping)
+    residual = np.zeros(sweeps, dtype=ft)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for t in range(sweeps):
+            new, r = [], ft(0)
+            for d in range(2 * E):
+                a, b = int(src[d]), int(dst[d])
+                h = w[a].copy()
+                for q in inc[a]:                                             # ascending neighbour
+                    if src[q] != b:
+                        h = h * msg[q]
+                Kd = K[d // 2] if d % 2 == 0 else K[d // 2].T
+                u = np.zeros(nu[b], dtype=ft)
+                for i in range(nu[a]):                                       # i ascending
+                    u = u + h[i] * Kd[i]
+                tot = ft(0)
+                for j in range(nu[b]):                                       # j ascending
+                    tot = tot + u[j]
+                m = u / tot
+                if damping != 0.0:
+                    m = (ft(1) - lam) * m + lam * msg[d]
+                r = _nan_max(r, np.abs(m - msg[d]).max())
+                new.append(m)
+            msg = new
+            residual[t] = r
+        belief, state = np.zeros((S, n), dtype=ft), np.zeros(S, dtype=np.int32)
+        for s in range(S):
+            h = w[s].copy()
+            for q in inc[s]:
+                h = h * msg[q]
+            tot = ft(0)
+            for i in range(nu[s]):
+                tot = tot + h[i]
+            belief[s, :nu[s]] = h / tot
+            state[s] = first_max(belief[s, :nu[s]])
+    return dict(belief=belief, state=state, residual=residual)
+
+
+def neighbours(x, y, ptr=None, n_used=None, *, max_distance, tau=0.1, length=100.0, min_distance=1.0):
+    """The survey graph (host, numpy): ``eu``, ``ev`` int32 [E] with eu < ev, sorted by (eu, ev) without duplicates, ``g`` float64
+    [E] and ``dist`` float64 [E] (m) for soundings at ``x``, ``y`` [S] in the sequences of ``ptr`` [L + 1] (None: one sequence).
+    Along a line the edges are exactly the pairs ``partners(ptr, n_used)`` connects.  Across lines every sounding with models
+    (``n_used`` > 0; None: all) is joined to the nearest sounding with models of every *other* sequence -- a tie goes to the lowest
+    index -- if that distance is <= ``max_distance``; the union is undirected.  g = length / (2 tau^2 max(dist, min_distance)): the
+    convention of ``steps``, applied to the edge's horizontal distance.  ``max_distance`` is required: about 1.5 line spacings is the
+    natural value, and it is not guessed.  Lines are taken pair by pair, a pair whose bounding boxes lie further apart than
+    ``max_distance`` is skipped, and the distances of one pair are held at a time: memory is O(longest line^2)."""
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != y.size:
+        raise ValueError("sections.neighbours: x and y must have one entry per sounding")
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError("sections.neighbours: x and y must be finite")
+    S = x.size
+    max_distance = _check_number(max_distance, "max_distance")
+    tau, length, min_distance = _check_number(tau, "tau"), _check_number(length, "length"), _check_number(min_distance, "min_distance")
+    p = _default_ptr(ptr, S)
+    nu = np.ones(S, dtype=np.int64) if n_used is None else host(n_used).reshape(-1)
+    if nu.size != S or nu.dtype.kind not in "iu":
+        raise ValueError("sections.neighbours: n_used must hold one integer per sounding")
+    partner = partners(p, nu).astype(np.int64)
+    has = np.flatnonzero(partner >= 0)
+    keys = [has * S + partner[has]]
+    members = [a + np.flatnonzero(nu[a:b] > 0) for a, b in zip(p[:-1], p[1:])]
+    boxes = [(x[m].min(), x[m].max(), y[m].min(), y[m].max()) if m.size else None for m in members]
+    for la in range(len(members)):
+        for lb in range(la + 1, len(members)):
+            A, B = members[la], members[lb]
+            if not A.size or not B.size:
+                continue
+            ba, bb = boxes[la], boxes[lb]
+            gap_x, gap_y = max(ba[0] - bb[1], bb[0] - ba[1], 0.0), max(ba[2] - bb[3], bb[2] - ba[3], 0.0)
+            if np.hypot(gap_x, gap_y) > max_distance:
+                continue
+            D = np.hypot(x[A][:, None] - x[B][None, :], y[A][:, None] - y[B][None, :])
+            ja, ib = np.argmin(D, axis=1), np.argmin(D, axis=0)              # the first minimum: the lowest index
+            near = D[np.arange(A.size), ja] <= max_distance
+            keys.append(np.minimum(A[near], B[ja[near]]) * S + np.maximum(A[near], B[ja[near]]))
+            near = D[ib, np.arange(B.size)] <= max_distance
+            keys.append(np.minimum(A[ib[near]], B[near]) * S + np.maximum(A[ib[near]], B[near]))
+    key = np.unique(np.concatenate(keys)) if S else np.zeros(0, dtype=np.int64)
+    eu, ev = (key // S, key % S) if S else (key, key)
+    dist = np.hypot(x[ev] - x[eu], y[ev] - y[eu])
+    return eu.astype(np.int32), ev.astype(np.int32), length / (2.0 * tau * tau * np.maximum(dist, min_distance)), dist
+
+
+def edge_distance(ens, rows, eu, ev, z0, z1, measure="linear"):
+    """D^2 f64 [E, n, n] on the device for the edges ``eu`` < ``ev`` (host; sorted by (eu, ev)): entry [e, i, j] is the squared
+    distance of ``cross_distance`` between model ``rows[eu[e], i]`` and model ``rows[ev[e], j]``.  No kernel of its own: pass p calls
+    ``cross_distance`` with every sounding paired with its p-th higher-indexed neighbour and copies the slabs out, so every entry has
+    that kernel's bits; the passes are as many as the largest number of higher-indexed neighbours of a sounding."""
+    are_tensors((ens.k, ens.edges, ens.sigma, rows), "sections", "edge_distance", "gbp_ensemble_cross_distance")
+    S = ens.k.shape[0]
+    eu, ev = host(eu).reshape(-1), host(ev).reshape(-1)
+    if eu.size != ev.size or eu.dtype.kind not in "iu" or ev.dtype.kind not in "iu":
+        raise ValueError("sections.edge_distance: eu and ev must hold one integer per edge")
+    eu, ev = eu.astype(np.int64), ev.astype(np.int64)
+    if np.any(eu < 0) or np.any(ev >= S) or np.any(eu >= ev) or np.any(np.diff(eu * S + ev) <= 0):
+        raise ValueError("sections.edge_distance: the edges need 0 <= eu < ev < S, sorted by (eu, ev) without duplicates")
+    E = eu.size
+    if rows.ndim != 2:
+        raise ValueError("sections.edge_distance: rows [S, n]")
+    n = rows.shape[1]
+    first = np.searchsorted(eu, eu, side="left")                              # the first edge of every edge's lower sounding
+    rank = np.arange(E) - first
+    out = None
+    for p in range(int(rank.max(initial=-1)) + 1):
+        at = np.flatnonzero(rank == p)
+        partner = np.full(S, -1, dtype=np.int32)
+        partner[eu[at]] = ev[at]
+        d = cross_distance(ens, rows, partner, z0, z1, measure=measure, squared=True)
+        if out is None:
+            out = torch.empty((E, n, n), dtype=torch.float64, device=d.device)
+        out[torch.as_tensor(at).to(d.device)] = d[torch.as_tensor(eu[at]).to(d.device)]
+        del d
+    if out is None:
+        check_window(z0, z1, measure)
+        on_device((ens.k, rows), "sections", "edge_distance", "gbp_ensemble_cross_distance")
+        out = torch.empty((0, n, n), dtype=torch.float64, device=rows.device)
+    return out
+
+
+def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0):
+    """Beliefs of the graph of ``propagate_reference`` on the device (gbp_section_propagate: csrc/gbp_section_graph.h): ``d2`` f64
+    [E, n, n] on the device (``edge_distance``), n <= 256; ``g`` [E], ``eu`` < ``ev`` [E] (host or device; sorted by (eu, ev), no
+    duplicates), ``n_used`` [S] in 1 .. n with S = ``n_soundings``, ``score`` f64 [S, n] on the device or None: zeros; ``sweeps`` >= 1
+    synchronous sweeps with ``damping`` in [0, 1).  Returns on the device ``belief`` f64 [S, n], ``state`` int32 [S] (the first maximum
+    of the belief) and ``residual`` f64 [sweeps] (the largest change of a message per sweep: 0.0 once a tree has converged).  d2 is
+    left as it is; K = exp(-(g d2)) takes a second buffer of its size.  The CSR of incoming edges is made once on the host."""
+    entry = "gbp_section_propagate"
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "propagate", entry)
+    S = check_int(n_soundings, 0, 2 ** 31 - 1, "sections.propagate: n_soundings")
+    if np.size(host(n_used)) != S:
+        raise ValueError("sections.propagate: n_used must hold one integer per sounding (%d)" % S)
+    eu, ev, nu, sweeps, damping = _check_graph(eu, ev, g, d2, n_used, score, sweeps, damping, "sections.propagate")
+    if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
+        raise TypeError("sections.propagate: d2 and score are float64")
+    on_device((d2,) + (() if score is None else (score,)), "sections", "propagate", entry)
+    dev = d2.device
+    E, n = d2.shape[0], d2.shape[1]
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    out = dict(belief=torch.empty((S, n), **f64), state=torch.empty(S, **i32), residual=torch.zeros(sweeps, **f64))
+    if S == 0:
+        return out
+    in_ptr, in_edge = incoming(eu, ev, S)
+    d2 = d2.contiguous()
+    score = torch.zeros((S, n), **f64) if score is None else score.contiguous()
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_eu, t_ev, t_nu = (torch.as_tensor(a.astype(np.int32)).to(dev) for a in (eu, ev, nu))
+    t_ptr, t_edge = torch.as_tensor(in_ptr).to(dev), torch.as_tensor(in_edge).to(dev)
+    K, w = torch.empty_like(d2), torch.empty((S, n), **f64)
+    mu, resid = torch.empty((2, 2 * E, n), **f64), torch.empty((sweeps, 2 * E), **f64)
+    _lib.call(entry, dev, S, E, n, t_eu, t_ev, t_nu, score, t_g, d2, t_ptr, t_edge, sweeps, damping, K, w, mu, resid, out["belief"], out["state"],
+              out["residual"])
+    return out
+
+
+def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=64, *, max_distance, tau=0.1, length=100.0, min_distance=1.0,
+            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None):
+    """One kept model per sounding, and a weight for every kept model, from the whole survey at once: the chain of
+    ``sections`` along every sequence of ``ptr`` plus edges to the nearest sounding of every other sequence within ``max_distance``
+    (required; about 1.5 line spacings), solved by ``sweeps`` synchronous sweeps of sum-product message passing with ``damping``.
+    The pipeline is ``families.used_rows`` (``chains``, ``max_models`` <= 256), ``neighbours`` (``tau``, ``length``, ``min_distance``),
+    ``edge_distance``, ``propagate`` and a gather.  Exact along a line and on any survey whose graph is a forest; with loops the
+    weights are beliefs, an approximation whose size DESIGN.md 3.28 records, and ``residual`` says whether the sweeps settled.
+
+    Returns, on the device: ``weight`` f64 [S, n] (the belief; NaN: no models), ``n_effective`` f64 [S] = 1 / sum w^2, ``state`` int32
+    [S] (the first maximum of the belief, a position in ``rows``; -1: no models), ``slot`` int32 [S], ``rows`` int32 [S, n],
+    ``n_used`` int32 [S], ``section_k`` / ``section_edges`` / ``section_sigma`` (bit copies of the chosen slots, as in ``sections``),
+    ``edge_u`` / ``edge_v`` int32 [E], ``edge_length`` f64 [E] (m), ``edge_distance`` f64 [E] (D in decades between the chosen models
+    of the edge's soundings) and ``residual`` f64 [sweeps].  ``products`` = dict(depth_edges=, percentiles=, thresholds=) adds what
+    ``lateral_products`` gives under this ``weight``.  The graph is one problem and is not cut into blocks: E n^2 8 bytes of distances
+    (and as much again for exp(-g D^2)) above ``budget_bytes`` are refused."""
+    z0, z1, _ = check_window(z0, z1, measure)
+    if products is not None:
+        products = check_products(products)
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    are_tensors((k, edges, sigma), "sections", "spatial", "gbp_ensemble_cross_distance")
+    if k.ndim != 2 or edges.ndim != 3:
+        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
+    C = check_chains(chains, k.shape[1])
+    max_models = check_int(max_models, 1, MAX_GRAPH_STATES, "max_models")
+    budget_bytes = check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
+    sweeps, damping = check_int(sweeps, 1, MAX_SWEEPS, "sweeps"), _check_damping(damping, "sections.spatial")
+    S = k.shape[0]
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != S or y.size != S:
+        raise ValueError("sections: x and y must hold one entry per sounding (%d)" % S)
+    p = _default_ptr(ptr, S)
+    max_distance = _check_number(max_distance, "max_distance")
+    steps(x, y, tau, length, min_distance, p)                                  # (its refusals of x, y, tau, length and min_distance)
+    rows, n_used, _ = used_rows(ens, chains=C, max_models=max_models)
+    n = rows.shape[1]
+    if score is not None:
+        are_tensors((score,), "sections", "spatial", "gbp_section_propagate")
+        if tuple(score.shape) != (S, n) or score.dtype != torch.float64:
+            raise ValueError("sections: score must be float64 [S, n] with n = %d, the width of used_rows" % n)
+    nu = host(n_used).reshape(-1).astype(np.int64)
+    eu, ev, g, dist = neighbours(x, y, p, nu, max_distance=max_distance, tau=tau, length=length, min_distance=min_distance)
+    E = eu.size
+    if E * n * n * 8 > budget_bytes:
+        raise ValueError("sections.spatial: %d edges with %d models a sounding need %d bytes of distances, more than budget_bytes = %d; lower "
+                         "max_models or max_distance, or raise budget_bytes (the graph is one problem: it is not cut into blocks)"
+                         % (E, n, E * n * n * 8, budget_bytes))
+    on_device((k, edges, sigma) + (() if score is None else (score,)), "sections", "spatial", "gbp_ensemble_cross_distance")
+    dev = k.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    d2 = edge_distance(ens, rows, eu, ev, z0, z1, measure=measure)
+    keep = np.flatnonzero(nu > 0)
+    local = np.cumsum(nu > 0) - 1                                              # the soundings with models, renumbered: the order stays
+    idx = torch.as_tensor(keep).to(dev)
+    res = propagate(d2, g, local[eu], local[ev], nu[keep], keep.size, score=None if score is None else score[idx], sweeps=sweeps, damping=damping)
+    nan = float("nan")
+    weight, state = torch.full((S, n), nan, **f64), torch.full((S,), -1, dtype=torch.int32, device=dev)
+    weight[idx], state[idx] = res["belief"], res["state"]
+    has = state >= 0
+    w = torch.where(has[:, None], weight, torch.zeros((), **f64))
+    out = dict(weight=weight, n_effective=torch.where(has, 1.0 / (w * w).sum(dim=1), torch.full((), nan, **f64)))
+    out.update(_chosen_models(k, edges, sigma, rows, n_used, state))
+    t_u, t_v = torch.as_tensor(eu.astype(np.int64)).to(dev), torch.as_tensor(ev.astype(np.int64)).to(dev)
+    st = state.long()
+    out.update(edge_u=t_u.to(torch.int32), edge_v=t_v.to(torch.int32), edge_length=torch.as_tensor(dist).to(dev),
+               edge_distance=torch.sqrt(d2[torch.arange(E, device=dev), st[t_u], st[t_v]]), residual=res["residual"])
+    if products is not None:
+        out.update(lateral_products(ens, out, **products))
+    return out
+
+
 def line_ptr(line):
     """ptr int64 [L + 1] of the runs of consecutive rows with equal ``line`` number."""
     line = np.asarray(line).reshape(-1)
@@ -728,34 +1062,70 @@ def line_ptr(line):
     return np.concatenate([[0], cut, [line.size]]).astype(np.int64) if line.size else np.zeros(1, dtype=np.int64)
 
 
-def from_survey(result_or_path, z1, device=None, **kw):
-    """``sections`` for a ``survey.SurveyResult`` -- or the file its ``save`` wrote -- that carries the kept models (``survey.infer(...,
-    ensemble=...)``: ensemble_k / _edges / _sigma).  The sequences are the runs of consecutive rows with equal line number; ``kw``: the
-    keywords of ``sections`` but ``ptr``.  Returns its dictionary on ``device`` (default cuda:0) plus ``line``, ``fiducial``, ``x``, ``y``
-    (numpy, as stored)."""
+def _survey_ensemble(result_or_path, device, what):
+    """The survey result (or the file its ``save`` wrote) and the ensemble it carries, on ``device`` (default cuda:0)."""
     from .survey import SurveyResult
     res = SurveyResult.load(result_or_path) if isinstance(result_or_path, (str, bytes)) or hasattr(result_or_path, "__fspath__") else result_or_path
     missing = [name for name in ("ensemble_k", "ensemble_edges", "ensemble_sigma", "line", "x", "y") if name not in res]
     if missing:
-        raise ValueError("sections.from_survey: the survey result holds no %s (survey.infer(..., ensemble=n_keep) keeps the models)" % ", ".join(missing))
-    if "ptr" in kw:
-        raise ValueError("sections.from_survey: the sequences are the survey's lines; ptr is not taken")
+        raise ValueError("sections.%s: the survey result holds no %s (survey.infer(..., ensemble=n_keep) keeps the models)" % (what, ", ".join(missing)))
     dev = torch.device(device) if device is not None else torch.device("cuda", 0)
     k = torch.as_tensor(np.ascontiguousarray(res["ensemble_k"], dtype=np.int32))
     e, s = (torch.as_tensor(np.ascontiguousarray(res[name], dtype=np.float64)) for name in ("ensemble_edges", "ensemble_sigma"))
     if dev.type == "cuda":
         k, e, s = k.to(dev), e.to(dev), s.to(dev)
-    ens = Ensemble(k, e, s, None, None, 1, None)
+    return res, Ensemble(k, e, s, None, None, 1, None)
+
+
+def _survey_columns(res, S):
+    return dict(line=np.asarray(res["line"]), fiducial=np.asarray(res["fiducial"]) if "fiducial" in res else np.arange(S),
+                x=np.asarray(res["x"]), y=np.asarray(res["y"]))
+
+
+SPATIAL_SHARED = ("z0", "measure", "chains", "tau", "length", "min_distance")
+
+
+def _spatial_of_lines(ens, res, z1, **kw):
+    return spatial(ens, res["x"], res["y"], z1, ptr=line_ptr(res["line"]), **kw)
+
+
+def from_survey(result_or_path, z1, device=None, spatial=None, **kw):
+    """``sections`` for a ``survey.SurveyResult`` -- or the file its ``save`` wrote -- that carries the kept models (``survey.infer(...,
+    ensemble=...)``: ensemble_k / _edges / _sigma).  The sequences are the runs of consecutive rows with equal line number; ``kw``: the
+    keywords of ``sections`` but ``ptr``.  Returns its dictionary on ``device`` (default cuda:0) plus ``line``, ``fiducial``, ``x``, ``y``
+    (numpy, as stored).  ``spatial`` = dict(max_distance=..., ...) adds the result of ``spatial_from_survey`` -- the survey solved as
+    one graph -- as ``spatial_<name>``: the dictionary holds keywords of ``spatial`` (``max_distance`` is required), and ``z0``,
+    ``measure``, ``chains``, ``tau``, ``length`` and ``min_distance`` are taken from ``kw`` unless it names them."""
+    if spatial is not None and (not isinstance(spatial, dict) or "max_distance" not in spatial or "ptr" in spatial):
+        raise ValueError("sections.from_survey: spatial is a dictionary of keywords of sections.spatial with max_distance, without ptr")
+    if "ptr" in kw:
+        raise ValueError("sections.from_survey: the sequences are the survey's lines; ptr is not taken")
+    res, ens = _survey_ensemble(result_or_path, device, "from_survey")
     out = sections(ens, res["x"], res["y"], z1, ptr=line_ptr(res["line"]), **kw)
-    out.update(line=np.asarray(res["line"]), fiducial=np.asarray(res["fiducial"]) if "fiducial" in res else np.arange(k.shape[0]),
-               x=np.asarray(res["x"]), y=np.asarray(res["y"]))
+    if spatial is not None:
+        across = _spatial_of_lines(ens, res, z1, **dict({name: kw[name] for name in SPATIAL_SHARED if name in kw}, **spatial))
+        out.update({"spatial_" + name: v for name, v in across.items()})
+    out.update(_survey_columns(res, ens.k.shape[0]))
     return out
 
 
-def output_path(path):
-    """<name>.sections.npz beside the survey result <name>.npz."""
+def spatial_from_survey(result_or_path, z1, device=None, **kw):
+    """``spatial`` for a ``survey.SurveyResult`` or its saved file: the sequences are the survey's lines; ``kw``: the keywords of
+    ``spatial`` but ``ptr`` (``max_distance`` is required).  Returns its dictionary plus ``line``, ``fiducial``, ``x``, ``y``."""
+    if "ptr" in kw:
+        raise ValueError("sections.spatial_from_survey: the sequences are the survey's lines; ptr is not taken")
+    if "max_distance" not in kw:
+        raise ValueError("sections.spatial_from_survey: max_distance is required (about 1.5 line spacings)")
+    res, ens = _survey_ensemble(result_or_path, device, "spatial_from_survey")
+    out = _spatial_of_lines(ens, res, z1, **kw)
+    out.update(_survey_columns(res, ens.k.shape[0]))
+    return out
+
+
+def output_path(path, suffix=OUTPUT_SUFFIX):
+    """<name>.sections.npz (``suffix``) beside the survey result <name>.npz."""
     path = str(path)
-    return (path[:-4] if path.endswith(".npz") else path) + OUTPUT_SUFFIX
+    return (path[:-4] if path.endswith(".npz") else path) + suffix
 
 
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
@@ -782,6 +1152,11 @@ def _parser():
                         "lateral_percentile_<p>, lateral_exceedance")
     p.add_argument("--percentiles", type=float, nargs="+", default=None, metavar="P", help="with --depth-axis: ascending percentiles in [0, 100] (default 5 50 95)")
     p.add_argument("--exceed", type=float, nargs="+", default=None, metavar="T", help="with --depth-axis: at most 8 thresholds in log10 S/m (default none)")
+    p.add_argument("--spatial", type=float, default=None, metavar="MAX_DISTANCE",
+                   help="solve the survey as one graph: join every sounding to the nearest one of every other line within MAX_DISTANCE metres "
+                        "(about 1.5 line spacings) and write <name>.spatial.npz instead (--max-models <= 256)")
+    p.add_argument("--sweeps", type=int, default=None, metavar="N", help="with --spatial: sweeps of message passing (default 32)")
+    p.add_argument("--damping", type=float, default=None, metavar="L", help="with --spatial: the damping of the messages in [0, 1) (default 0)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -822,12 +1197,32 @@ def parse_args(argv=None):
                                                  thresholds=() if a.exceed is None else a.exceed))
         except ValueError as e:
             p.error("--" + str(e))
+    if a.spatial is None:
+        if a.sweeps is not None or a.damping is not None:
+            p.error("--sweeps and --damping need --spatial")
+    else:
+        if a.no_marginals or a.draws:
+            p.error("--spatial gives beliefs alone: it takes neither --no-marginals nor --draws")
+        try:
+            _check_number(a.spatial, "--spatial")
+            check_int(a.max_models, 1, MAX_GRAPH_STATES, "--max-models (with --spatial)")
+            if a.sweeps is not None:
+                check_int(a.sweeps, 1, MAX_SWEEPS, "--sweeps")
+            if a.damping is not None:
+                _check_damping(a.damping, "--damping")
+        except ValueError as e:
+            p.error(str(e))
+        del kw["marginals"]
+        kw.update(max_distance=a.spatial, **({} if a.sweeps is None else dict(sweeps=a.sweeps)), **({} if a.damping is None else dict(damping=a.damping)))
     return a.survey, kw
 
 
 def main(argv=None):
     path, kw = parse_args(argv)
-    out = save(from_survey(path, **kw), output_path(path))
+    if "max_distance" in kw:
+        out = save(spatial_from_survey(path, **kw), output_path(path, SPATIAL_SUFFIX))
+    else:
+        out = save(from_survey(path, **kw), output_path(path))
     print("wrote", out)
     return out
 

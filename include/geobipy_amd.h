@@ -1065,6 +1065,33 @@ gbp_status gbp_section_draw(int L, const int64_t *ptr, int64_t total_n, int n, c
                             const double *g, const double *d2, const int64_t *row_key, uint64_t seed, int n_draws, double *filtered,
                             double *scale, int32_t *draw_state, void *stream);
 
+/* Sections across lines: synchronous sum-product message passing (loopy belief propagation) on a graph of soundings
+ * (csrc/gbp_section_graph.h k_graph_kernel, k_graph_init, k_graph_sweep, k_graph_residual, k_graph_belief; the rule is
+ * stated in numpy as sections.propagate_reference).  The conventions of gbp_section_track: DEVICE arrays throughout, none read on
+ * the host.  S soundings with m_s = n_used[s] (1 .. n) of n <= 256 states and weights w_s = exp(score[s]), score f64 [S, n]; E
+ * undirected edges eu[e] < ev[e] int32 [E], sorted by (eu, ev) without duplicates, with g f64 [E] and d2 f64 [E, n, n], [e, i, j]
+ * between state i of eu[e] and state j of ev[e]; nothing outside the prefixes i < m_u, j < m_v is read.  Directed edge 2 e is
+ * eu -> ev, 2 e + 1 is ev -> eu; in_ptr int32 [S + 1] and in_edge int32 [2 E] are the CSR of every sounding's incoming directed
+ * edges, sorted by the sounding they come from.
+ *   K_e = exp(-(g[e] * d2[e])).  Messages start at 1 / m_dst.  A sweep computes every message from the last sweep's: for a -> b,
+ *   h[i] = w_a[i] times the messages into a from all neighbours but b, ascending neighbour; u[j] = sum_i h[i] K[i, j], i ascending,
+ *   one multiply and one add per term; tot = sum_j u[j], j ascending; mu' = u / tot; with damping != 0 mu' = (1 - damping) mu' +
+ *   damping mu_old.  residual f64 [sweeps]: the largest |mu' - mu_old| of the sweep (NaN if a message is NaN; 0.0 without edges).
+ *   belief f64 [S, n] = w_s times all incoming messages, divided by its sum (i ascending); 0.0 for the states >= m_s.  state int32
+ *   [S]: the first maximum of the belief.  A zero tot gives NaN, and the NaN travels as the arithmetic takes it.
+ *   The device's exp is not numpy's to the last bit; every other operation is the rule's: a few ulp.  A call repeats its own bits.
+ * Workspaces the caller provides: K f64 [E, n, n] (K == d2 works in place), w f64 [S, n], mu f64 [2, 2 E, n], resid f64 [sweeps,
+ * 2 E].  One 256-thread workgroup per undirected edge and sweep (35 KiB of static LDS for n <= 64, 41 KiB above), one per sounding for
+ * the beliefs.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, E < 0 or > 2^30 - 1, n < 1 or n > 256, sweeps < 1, damping outside [0, 1), E > 0
+ * with S < 2, sizes out of range, a NULL residual, with S > 0 a NULL n_used / score / in_ptr / w / belief / state, with E > 0 a NULL
+ * eu / ev / g / d2 / in_edge / K / mu / resid.  An endpoint outside 0 .. S - 1 or an entry of in_edge outside 0 .. 2 E - 1 is
+ * skipped on the device, never followed. */
+gbp_status gbp_section_propagate(int S, int E, int n, const int32_t *eu, const int32_t *ev, const int32_t *n_used, const double *score,
+                                 const double *g, const double *d2, const int32_t *in_ptr, const int32_t *in_edge, int sweeps,
+                                 double damping, double *K, double *w, double *mu, double *resid, double *belief, int32_t *state,
+                                 double *residual, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
