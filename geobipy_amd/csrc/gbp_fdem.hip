@@ -2639,3 +2639,71 @@ extern "C" gbp_status gbp_section_propagate(int S, int E, int n, const int32_t* 
     }
     return GBP_OK;
 }
+
+#include "gbp_section_graph_draw.h"
+
+// Joint draws across lines (gbp_section_graph_draw.h): K unless the caller has it, the weights, then per sweep a filter launch and a draw
+// launch -- over every sequence at the start sweep, per colour class afterwards.  A launch holds a block for every (sequence, realisation)
+// and the blocks past the colour's own sequences leave at once: colour_ptr stays on the device.  Every refusal comes before any launch;
+// no device array is read on the host.
+extern "C" gbp_status gbp_section_graph_draw(int S, int E, int n, int L, const int64_t* ptr, const int32_t* eu, const int32_t* ev,
+                                             const int32_t* n_used, const double* score, const double* g, const double* d2,
+                                             int kernel_ready, double* K, const int32_t* step_edge, const int32_t* cross_ptr,
+                                             const int32_t* cross_edge, int n_colours, const int32_t* colour_ptr,
+                                             const int32_t* colour_line, const int64_t* row_key, uint64_t seed, int n_draws,
+                                             int first_draw, int first_sweep, int last_sweep, double* w, double* filtered, double* scale,
+                                             int32_t* draw_state, void* stream)
+{
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: S must be >= 0%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: E must lie in 0 .. 2^30 - 1%s");
+    if (n < 1 || n > section::GRAPH_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: n must lie in 1 .. 256%s");
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: L must be >= 0%s");
+    if (n_draws < 1 || n_draws > section::MAX_DRAWS) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: n_draws must lie in 1 .. 65536%s");
+    if (first_draw < 0 || first_draw > section::MAX_DRAWS - n_draws)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: first_draw + n_draws must lie in 1 .. 65536%s");
+    if (first_sweep < 0 || last_sweep < first_sweep || last_sweep > 65535)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: the sweeps need 0 <= first_sweep <= last_sweep <= 65535%s");
+    if (E > 0 && S < 2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: an edge needs two soundings%s");
+    if (S > 0 && L < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: soundings need a sequence (L >= 1)%s");
+    if (L > 0 && (n_colours < 1 || n_colours > L)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: n_colours must lie in 1 .. L%s");
+    // (E n n and n_draws S n doubles fit 63 bits under the limits above; the grid of the filter is what can overflow)
+    if ((long long)L * n_draws > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: L * n_draws out of range%s");
+    if (S > 0 && (!ptr || !n_used || !score || !step_edge || !cross_ptr || !colour_ptr || !colour_line))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: NULL pointer (ptr, n_used, score, step_edge, cross_ptr, colour_ptr, colour_line)%s");
+    if (S > 0 && (!w || !filtered || !scale || !draw_state))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: NULL pointer (w, filtered, scale, draw_state)%s");
+    if (E > 0 && (!eu || !ev || !K || !cross_edge)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: NULL pointer (eu, ev, K, cross_edge)%s");
+    if (E > 0 && !kernel_ready && (!g || !d2)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_draw: NULL pointer (g, d2) without kernel_ready%s");
+    if (S == 0) return GBP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(section::THREADS);
+    if (E > 0 && !kernel_ready) {
+        hipLaunchKernelGGL(section::k_graph_kernel, dim3((unsigned)E), block, 0, st, S, n, (const int*)eu, (const int*)ev, (const int*)n_used, g, d2, K);
+        GBP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(section::k_graph_weights, dim3((unsigned)S), block, 0, st, n, (const int*)n_used, score, w);
+    GBP_HIP(hipGetLastError());
+    const size_t lds = section::lds_bytes(n);
+    const dim3 grid_filter((unsigned)((long long)L * n_draws)), grid_draw((unsigned)((long long)L * ((n_draws + 63) / 64)));
+#define GBP_GRAPH_DRAW(COND, LINES, COLOUR, SWEEP)                                                                                        \
+    hipLaunchKernelGGL((section::k_graph_line_filter<COND>), grid_filter, block, lds, st, S, E, n, L, (const long long*)ptr, (const int*)eu,  \
+                       (const int*)ev, (const int*)n_used, (const double*)w, (const double*)K, (const int*)step_edge, (const int*)cross_ptr,  \
+                       (const int*)cross_edge, (const int*)colour_ptr, (const int*)(LINES), COLOUR, (const int*)draw_state, filtered, scale); \
+    GBP_HIP(hipGetLastError());                                                                                                           \
+    hipLaunchKernelGGL(section::k_graph_line_draw, grid_draw, dim3(64), 0, st, S, E, n, L, (const long long*)ptr, (const int*)n_used,         \
+                       (const double*)K, (const int*)step_edge, (const int*)colour_ptr, (const int*)(LINES), COLOUR,                          \
+                       (const long long*)row_key, (unsigned long long)seed, n_draws, first_draw, (unsigned)(SWEEP),                           \
+                       (const double*)filtered, (int*)draw_state);                                                                        \
+    GBP_HIP(hipGetLastError())
+    for (int t = first_sweep; t <= last_sweep; ++t) {
+        if (t == 0) {                                                       // the start: every sequence alone
+            GBP_GRAPH_DRAW(false, nullptr, 0, 0);
+            continue;
+        }
+        for (int c = 0; c < n_colours; ++c) {
+            GBP_GRAPH_DRAW(true, colour_line, c, t);
+        }
+    }
+#undef GBP_GRAPH_DRAW
+    return GBP_OK;
+}

@@ -53,7 +53,17 @@ its line and to the nearest sounding of every other line within ``max_distance``
 and returns *beliefs*: the marginals on a forest, a documented approximation on a graph with loops; ``spatial`` is all of it for an
 ensemble, with the keys of ``sections`` that still have a meaning, and ``spatial_from_survey`` / ``from_survey(..., spatial=dict(
 max_distance=...))`` / ``--spatial MAX_DISTANCE [--sweeps N] [--damping L]`` (``<name>.spatial.npz``) for a survey.  Left out on
-purpose: max-product and joint draws on the graph, tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
+purpose: max-product on the graph, tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
+
+Joint draws across lines (gbp_section_graph_draw: csrc/gbp_section_graph_draw.h).  ``graph_draw`` draws R joint
+realisations of the whole graph by Gibbs sampling blocked by flight line (``graph_draw_reference`` states the rule, ``line_colours``
+which lines one launch may draw together): from the line-alone start of ``draw``, every sweep redraws every line exactly from its
+conditional given its neighbours' current states.  The stationary law is the exact joint, loops included; the realisations are
+draws of it as far as ``sweeps`` sweeps have mixed, and 8 is a convention.  ``propagate(..., keep_kernel=True)`` hands its K on,
+``spatial(..., draws=R, seed=N, draw_sweeps=T)`` adds ``draw_state``, ``draw_slot``, ``draw_log_score``, ``draw_share`` and
+``draw_change_share``, and ``--spatial D --spatial-draws R [--seed N] [--draw-sweeps T]`` writes them.  Left out on purpose: the
+filter on the matrix cores, cluster moves and tempering, draws conditioned on boreholes, learning ``tau`` (the pair potential
+exp(-g D^2) is not a normalised transition, so the evidence grows monotonically as g -> 0).
 """
 import numpy as np
 import torch
@@ -274,13 +284,15 @@ def _check_row_key(row_key, total, what):
     return key.astype(np.int64)
 
 
-def philox_uniform(seed, draw, row_key):
+def philox_uniform(seed, draw, row_key, sweep=0):
     """The uniform of a draw, float64 in [0, 1), vectorised over ``draw`` and ``row_key`` (broadcast against each other): u53(x, y) of
-    the Philox4x32-10 block with key ``seed`` (uint64: low word, high word) and counter (draw, row_key & 0xFFFFFFFF, row_key >> 32, 0)
-    -- the generator and the 53-bit uniform of the sampler (csrc/gbp_philox.h), counter layout of the section draws."""
+    the Philox4x32-10 block with key ``seed`` (uint64: low word, high word) and counter (draw, row_key & 0xFFFFFFFF, row_key >> 32,
+    sweep) -- the generator and the 53-bit uniform of the sampler (csrc/gbp_philox.h), counter layout of the section draws (DESIGN.md
+    3.26); ``sweep`` is 0 but for the sweeps of the draws across lines."""
     seed = _check_seed(seed)
+    sweep = check_int(sweep, 0, 2 ** 32 - 1, "sections: sweep")
     c0, key = np.broadcast_arrays(np.asarray(draw, dtype=np.int64).astype(np.uint64) & _M32, np.asarray(row_key, dtype=np.int64).astype(np.uint64))
-    c1, c2, c3 = key & _M32, key >> _S32, np.zeros(key.shape, dtype=np.uint64)
+    c1, c2, c3 = key & _M32, key >> _S32, np.full(key.shape, sweep, dtype=np.uint64)
     k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
     for _ in range(10):
         p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2          # 32 x 32 bits: no overflow in 64
@@ -949,13 +961,15 @@ def edge_distance(ens, rows, eu, ev, z0, z1, measure="linear"):
     return out
 
 
-def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0):
+def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0, keep_kernel=False):
     """Beliefs of the graph of ``propagate_reference`` on the device (gbp_section_propagate: csrc/gbp_section_graph.h): ``d2`` f64
     [E, n, n] on the device (``edge_distance``), n <= 256; ``g`` [E], ``eu`` < ``ev`` [E] (host or device; sorted by (eu, ev), no
     duplicates), ``n_used`` [S] in 1 .. n with S = ``n_soundings``, ``score`` f64 [S, n] on the device or None: zeros; ``sweeps`` >= 1
     synchronous sweeps with ``damping`` in [0, 1).  Returns on the device ``belief`` f64 [S, n], ``state`` int32 [S] (the first maximum
     of the belief) and ``residual`` f64 [sweeps] (the largest change of a message per sweep: 0.0 once a tree has converged).  d2 is
-    left as it is; K = exp(-(g d2)) takes a second buffer of its size.  The CSR of incoming edges is made once on the host."""
+    left as it is; K = exp(-(g d2)) takes a second buffer of its size.  The CSR of incoming edges is made once on the host.
+    ``keep_kernel`` adds that K buffer as ``kernel`` f64 [E, n, n] (valid on the prefixes i < m_u, j < m_v): what ``graph_draw`` takes
+    as ``kernel=``."""
     entry = "gbp_section_propagate"
     are_tensors((d2,) + (() if score is None else (score,)), "sections", "propagate", entry)
     S = check_int(n_soundings, 0, 2 ** 31 - 1, "sections.propagate: n_soundings")
@@ -970,6 +984,8 @@ def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping
     f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
     out = dict(belief=torch.empty((S, n), **f64), state=torch.empty(S, **i32), residual=torch.zeros(sweeps, **f64))
     if S == 0:
+        if keep_kernel:
+            out["kernel"] = torch.empty_like(d2)
         return out
     in_ptr, in_edge = incoming(eu, ev, S)
     d2 = d2.contiguous()
@@ -981,11 +997,288 @@ def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping
     mu, resid = torch.empty((2, 2 * E, n), **f64), torch.empty((sweeps, 2 * E), **f64)
     _lib.call(entry, dev, S, E, n, t_eu, t_ev, t_nu, score, t_g, d2, t_ptr, t_edge, sweeps, damping, K, w, mu, resid, out["belief"], out["state"],
               out["residual"])
+    if keep_kernel:
+        out["kernel"] = K
+    return out
+
+
+# ---- across lines: joint draws by Gibbs sampling blocked by flight line ----------------------------------------------
+
+MAX_DRAW_SWEEPS = 65535
+
+
+def _line_of(ptr, S):
+    """int64 [S]: the sequence of ``ptr`` every sounding lies in (empty sequences own none)."""
+    return np.searchsorted(ptr, np.arange(S), side="right") - 1
+
+
+def check_lines(eu, ev, ptr, S, what):
+    """The sequences of a graph: ``ptr`` as int64 [L + 1] (sequences may be empty), ``step_edge`` int32 [S] (the edge of the step
+    s -> s + 1; -1 at a sequence's last sounding) and ``cross`` bool [E].  An edge inside a sequence must be a step and every
+    consecutive pair of a sequence must be an edge."""
+    ptr = check_ptr(ptr, S, empty=True)
+    line = _line_of(ptr, S)
+    same = line[eu] == line[ev]
+    step = same & (ev == eu + 1)
+    if np.any(same & ~step):
+        e = int(np.flatnonzero(same & ~step)[0])
+        raise ValueError("%s: an edge inside a sequence must join consecutive soundings; edge (%d, %d) is not a step" % (what, eu[e], ev[e]))
+    step_edge = np.full(S, -1, dtype=np.int32)
+    step_edge[eu[step]] = np.flatnonzero(step)
+    last = np.zeros(S, dtype=bool)
+    last[ptr[1:][np.diff(ptr) > 0] - 1] = True
+    if np.any((step_edge < 0) & ~last):
+        s = int(np.flatnonzero((step_edge < 0) & ~last)[0])
+        raise ValueError("%s: consecutive soundings of a sequence must be joined by an edge; the step %d -> %d is missing (cut ptr there)" % (what, s, s + 1))
+    return ptr, step_edge, ~same
+
+
+def line_colours(eu, ev, ptr):
+    """The colour classes of the sequences of ``ptr`` [L + 1] under the edges ``eu``, ``ev`` (host): two sequences are adjacent if an
+    edge joins a sounding of one to a sounding of the other; the colouring is greedy in ascending sequence index, every sequence
+    taking the smallest colour no adjacent, already coloured sequence holds.  Returns ``colour`` int32 [L] and ``n_colours``.
+    Sequences of one colour share no edge, so given the other colours they are independent: one launch draws them all."""
+    p = host(ptr).reshape(-1)
+    if p.size < 1 or p.dtype.kind not in "iu":
+        raise ValueError("sections: ptr must be a vector of L + 1 integers")
+    ptr = check_ptr(p, int(p[-1]), empty=True)
+    S, L = int(ptr[-1]), ptr.size - 1
+    eu, ev = host(eu).reshape(-1), host(ev).reshape(-1)
+    if eu.size != ev.size or (eu.size and (eu.dtype.kind not in "iu" or ev.dtype.kind not in "iu")):
+        raise ValueError("sections.line_colours: eu and ev must hold one integer per edge")
+    eu, ev = eu.astype(np.int64), ev.astype(np.int64)
+    if np.any(eu < 0) or np.any(ev < 0) or np.any(eu >= S) or np.any(ev >= S):
+        raise ValueError("sections.line_colours: every endpoint must lie in 0 .. %d" % (S - 1))
+    line = _line_of(ptr, S)
+    a, b = line[eu], line[ev]
+    adjacent = [set() for _ in range(L)]
+    for p_, q_ in zip(a[a != b].tolist(), b[a != b].tolist()):
+        adjacent[p_].add(q_)
+        adjacent[q_].add(p_)
+    colour = np.zeros(L, dtype=np.int32)
+    for l in range(L):
+        taken = {int(colour[q]) for q in adjacent[l] if q < l}
+        c = 0
+        while c in taken:
+            c += 1
+        colour[l] = c
+    return colour, int(colour.max(initial=-1)) + 1
+
+
+def cross_incoming(eu, ev, cross, n_soundings):
+    """The CSR of every sounding's incoming CROSS directed edges (numpy int32): ``cross_ptr`` [S + 1] and ``cross_edge``, ids 2 e
+    (eu[e] -> ev[e]) and 2 e + 1 (ev[e] -> eu[e]) of the edges with ``cross`` [E] set, sorted by the sounding they come from."""
+    at = np.flatnonzero(cross).astype(np.int64)
+    src, dst = np.concatenate([eu[at], ev[at]]).astype(np.int64), np.concatenate([ev[at], eu[at]]).astype(np.int64)
+    ids = np.concatenate([2 * at, 2 * at + 1])
+    order = np.lexsort((src, dst))
+    cross_ptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=int(n_soundings)))]).astype(np.int32)
+    return cross_ptr, ids[order].astype(np.int32)
+
+
+def _check_graph_draw(eu, ev, g, d2, n_used, score, ptr, n_draws, seed, sweeps, row_key, state, first_sweep, what):
+    """The host checks ``graph_draw`` and its reference share, in the project's order (shapes, dtypes, values).  Returns eu, ev, n_used
+    (numpy int64), ptr, step_edge, cross, R, seed, sweeps, first_sweep, the keys (int64 [S]) and the states to continue from (int32
+    [R, S] or None)."""
+    eu, ev, nu, _, _ = _check_graph(eu, ev, g, d2, n_used, score, 1, 0.0, what)
+    S = nu.size
+    ptr, step_edge, cross = check_lines(eu, ev, ptr, S, what)
+    R = check_int(n_draws, 1, MAX_DRAWS, "%s: n_draws" % what)
+    seed = _check_seed(seed)
+    sweeps = check_int(sweeps, 0, MAX_DRAW_SWEEPS, "%s: sweeps" % what)
+    first_sweep = check_int(first_sweep, 0, sweeps, "%s: first_sweep (at most sweeps)" % what)
+    key = _check_row_key(row_key, S, what)
+    if (state is None) != (first_sweep == 0):
+        raise ValueError("%s: state holds the states to continue from: it goes with first_sweep > 0, and only with it" % what)
+    if state is not None:
+        state = host(state)
+        if state.shape != (R, S) or state.dtype.kind not in "iu":
+            raise ValueError("%s: state must hold one integer per realisation and sounding [%d, %d]" % (what, R, S))
+        if np.any(state < 0) or np.any(state >= nu[None, :]):
+            raise ValueError("%s: every state must lie in 0 .. n_used - 1" % what)
+        state = state.astype(np.int32)
+    return eu, ev, nu, ptr, step_edge, cross, R, seed, sweeps, first_sweep, key, state
+
+
+def graph_draw_reference(eu, ev, g, d2, n_used, ptr, n_draws, seed=0, sweeps=8, score=None, row_key=None, state=None, first_sweep=0,
+                         dtype=np.float64):
+    """The rule of ``graph_draw`` in numpy, evaluated in ``dtype``: R joint realisations of the whole graph of ``propagate_reference``
+    by Gibbs sampling blocked by flight line.  The graph as there (``eu`` < ``ev`` sorted, ``g`` [E], ``d2`` [E, n, n],
+    ``n_used`` [S] in 1 .. n, ``score`` [S, n] or None); ``ptr`` [L + 1]: the sequences in the same numbering, contiguous, possibly
+    empty; ``n_draws`` = R in 1 .. 65536; ``seed`` (uint64); ``sweeps`` = T >= 0; ``row_key`` int64 [S] (None: the index).
+
+    Edges.  An edge with ev = eu + 1 inside one sequence is a *step*; every other edge must join two different sequences: a *cross*
+    edge.  An edge inside a sequence that is not a step is refused, and so is a sequence in which a consecutive pair is not an edge
+    (cut ``ptr`` there; ``neighbours`` produces neither).  A sequence of one sounding is legal: with L = S singletons the scheme is
+    chromatic single-site Gibbs.  Colours: ``line_colours``.  K_e = exp(-(g[e] * d2[e])) on the prefixes, w_s = exp(score_s).
+
+    Sweep 0, the start: every sequence alone -- ``draw_reference`` word for word, cross edges ignored, the uniform
+    ``philox_uniform(seed, rho, row_key[s], sweep=0)``.
+    Sweep t = 1 .. T: colours ascending; for every sequence of the colour and every realisation rho the same filter and walk with w'
+    in place of w: w'_s[i] = w_s[i] times, for every cross edge of s in ascending order of the neighbour q, K_e[i, x_q] if s = eu[e]
+    or K_e[x_q, i] if s = ev[e], x_q the neighbour's current state in realisation rho, the multiplies left to right.  The step matrix
+    is K of the step edge; the uniform is ``philox_uniform(seed, rho, row_key[s], sweep=t)``.  States are replaced in place; the
+    sequences of a colour read only states of other colours.
+    ``first_sweep`` > 0 continues from ``state`` int32 [R, S] and runs the sweeps first_sweep .. T.
+
+    Every line update leaves the joint law invariant, so the chain's stationary law is the *exact* joint, loops included -- where the
+    beliefs of ``propagate`` are an approximation.  The R realisations are independent chains of T sweeps from the line-alone start:
+    draws of the joint only as far as T sweeps have mixed.  T = 8 is a convention, not a measured mixing time.
+
+    Returns ``draw_state`` int32 [R, S] after sweep T, ``filtered`` [R, S, n] (the alpha of the last sweep in which each sounding was
+    drawn; 0.0 for the states >= m_s) and ``margin`` [R, S]: the smallest, over the sweeps run, of ``draw_reference``'s margin."""
+    ft = np.dtype(dtype).type
+    what = "sections.graph_draw_reference"
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    eu, ev, nu, ptr, step_edge, cross, R, seed, T, first, key, state = _check_graph_draw(eu, ev, g, d2, n_used, score, ptr, n_draws, seed, sweeps,
+                                                                                         row_key, state, first_sweep, what)
+    E, n, S = d2.shape[0], d2.shape[1], nu.size
+    g64 = np.asarray(host(g), dtype=np.float64).reshape(-1)
+    score64 = np.zeros((S, n)) if score is None else score
+    rho = np.arange(R, dtype=np.int64)
+    X = np.zeros((R, S), dtype=np.int32) if state is None else state.copy()
+    filtered, margin = np.zeros((R, S, n), dtype=ft), np.full((R, S), np.inf, dtype=ft)
+    if first == 0:                                                            # the start: the chains of the steps alone
+        has = step_edge >= 0
+        gc, dc = np.ones(S), np.zeros((S, n, n))
+        gc[has], dc[has] = g64[step_edge[has]], d2[step_edge[has]]
+        start = draw_reference(ptr, score64, gc, dc, nu, R, seed=seed, row_key=key, dtype=dtype)
+        X[:], filtered[:], margin[:] = start["draw_state"], start["filtered"][None, :, :], start["margin"]
+    if T < max(first, 1):
+        return dict(draw_state=X, filtered=filtered, margin=margin)
+    gq = g64.astype(ft)
+    w = [np.exp(score64[s, :nu[s]].astype(ft)) for s in range(S)]
+    K = [np.exp(-(gq[e] * d2[e, :nu[eu[e]], :nu[ev[e]]].astype(ft))) for e in range(E)]
+    cross_ptr, cross_edge = cross_incoming(eu, ev, cross, S)
+    colour, n_colours = line_colours(eu, ev, ptr)
+
+    def conditioned(s):
+        """w' [R, m_s] under the current states."""
+        v = np.repeat(w[s][None, :], R, axis=0)
+        for d in cross_edge[cross_ptr[s]:cross_ptr[s + 1]]:                   # ascending neighbour
+            e = int(d) >> 1
+            v = v * (K[e][:, X[:, ev[e]]].T if d & 1 else K[e][X[:, eu[e]], :])
+        return np.ascontiguousarray(v)
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for t in range(max(first, 1), T + 1):
+            for c in range(n_colours):
+                for l in np.flatnonzero(colour == c):
+                    r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+                    if N == 0:
+                        continue
+                    m = [int(v) for v in nu[r0:r0 + N]]
+                    alpha = [None] * N
+                    v = conditioned(r0)
+                    alpha[0] = v / v.sum(axis=1)[:, None]
+                    for s in range(N - 1):
+                        Ks = K[step_edge[r0 + s]]
+                        u = np.zeros((R, m[s + 1]), dtype=ft)
+                        for i in range(m[s]):                                # i ascending
+                            u = u + alpha[s][:, i, None] * Ks[i][None, :]
+                        u = np.ascontiguousarray(conditioned(r0 + s + 1) * u)
+                        alpha[s + 1] = u / u.sum(axis=1)[:, None]
+                    j, new = None, np.zeros((R, N), dtype=np.int32)
+                    for s in range(N - 1, -1, -1):
+                        filtered[:, r0 + s, :m[s]] = alpha[s]
+                        W = alpha[s] if s == N - 1 else alpha[s] * K[step_edge[r0 + s]][:, j].T
+                        cs = np.cumsum(np.ascontiguousarray(W), axis=1, dtype=ft)      # sequential, i ascending
+                        thr = philox_uniform(seed, rho, key[r0 + s], sweep=t).astype(ft) * cs[:, -1]
+                        j = np.minimum((cs <= thr[:, None]).sum(axis=1), m[s] - 1)
+                        margin[:, r0 + s] = np.minimum(margin[:, r0 + s], np.abs(cs - thr[:, None]).min(axis=1) / cs[:, -1])
+                        new[:, s] = j
+                    X[:, r0:r0 + N] = new
+    return dict(draw_state=X, filtered=filtered, margin=margin)
+
+
+def graph_log_score(draw_state, score, g, d2, eu, ev):
+    """f64 [R]: the log score sum_s score[s, x_s] - sum_e g[e] d2[e, x_u, x_v] of every realisation ``draw_state`` [R, S], by gathers in
+    torch on the device of ``d2`` (``score`` None: zeros; ``g``, ``eu``, ``ev`` tensors there)."""
+    x = draw_state.long()
+    R, S = x.shape
+    out = torch.zeros(R, dtype=torch.float64, device=x.device)
+    if score is not None and S:
+        out = score[torch.arange(S, device=x.device)[None, :], x].sum(dim=1)
+    if d2.shape[0]:
+        out = out - (g[None, :] * d2[torch.arange(d2.shape[0], device=x.device)[None, :], x[:, eu.long()], x[:, ev.long()]]).sum(dim=1)
+    return out
+
+
+def graph_draw(d2, g, eu, ev, n_used, ptr, n_draws, seed=0, sweeps=8, score=None, row_key=None, kernel=None, state=None, first_sweep=0,
+               block=None, budget_bytes=4 << 30, trace=False, filtered=True):
+    """R joint realisations of the whole survey graph on the device by Gibbs sampling blocked by flight line (gbp_section_graph_draw:
+    csrc/gbp_section_graph_draw.h; ``graph_draw_reference`` states the rule and what its draws are).  ``d2`` f64 [E, n, n] on the
+    device, n <= 256; ``g``, ``eu``, ``ev``, ``n_used`` as ``propagate`` takes them; ``ptr`` [L + 1] (host): the sequences; ``n_draws``
+    = R in 1 .. 65536, ``seed`` a uint64, ``sweeps`` = T in 0 .. 65535 (8 is a convention, not a measured mixing time), ``score`` f64
+    [S, n] on the device or None, ``row_key`` int64 [S] (None: the index).  ``kernel``: the K = exp(-(g d2)) that
+    ``propagate(..., keep_kernel=True)`` left for the same graph; the entry then reads neither g nor d2.  ``first_sweep`` > 0 continues
+    from ``state`` int32 [R, S] (host or device).  Realisations are independent chains whose random numbers depend on (seed,
+    realisation, key, sweep): they are processed in blocks of ``block`` (None: as many as keep the block's alpha, R_b S n 8 bytes,
+    under ``budget_bytes``), and the blocking changes no draw.
+
+    Returns on the device ``draw_state`` int32 [R, S] and, with ``filtered``, ``filtered`` f64 [R, S, n] (then the blocks are slices
+    of it).  ``trace`` runs sweep by sweep and adds ``log_score_trace`` f64 [T - first_sweep + 1, R] (the log score
+    ``graph_log_score`` after every sweep that was run: T + 1 rows from the start, the start included) and ``change_share`` f64
+    [T - max(first_sweep, 1) + 1]: the share of (realisation, sounding) pairs whose state a conditioned sweep changed -- how a user
+    looks at mixing.  There is no host fallback."""
+    entry, what = "gbp_section_graph_draw", "sections.graph_draw"
+    given = (d2,) + tuple(a for a in (score, kernel) if a is not None)
+    are_tensors(given, "sections", "graph_draw", entry)
+    eu, ev, nu, ptr, step_edge, cross, R, seed, T, first, key, state = _check_graph_draw(eu, ev, g, d2, n_used, score, ptr, n_draws, seed, sweeps,
+                                                                                         None if row_key is None else row_key, state, first_sweep, what)
+    if kernel is not None and tuple(kernel.shape) != tuple(d2.shape):
+        raise ValueError("%s: kernel must have the shape of d2" % what)
+    if any(a.dtype != torch.float64 for a in given):
+        raise TypeError("%s: d2, score and kernel are float64" % what)
+    check_block(block, what)
+    budget_bytes = check_int(budget_bytes, 1, 2 ** 62, "%s: budget_bytes" % what)
+    on_device(given, "sections", "graph_draw", entry)
+    dev = d2.device
+    E, n, S, L = d2.shape[0], d2.shape[1], nu.size, ptr.size - 1
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    per = int(block) if block is not None else max(1, min(R, budget_bytes // max(1, S * n * 8)))
+    per = min(per, R)
+    out = dict(draw_state=torch.zeros((R, S), **i32) if state is None else torch.as_tensor(state).to(dev).contiguous())
+    alpha = torch.zeros((R if filtered else per, S, n), **f64)
+    if filtered:
+        out["filtered"] = alpha
+    run_first = max(first, 1)
+    if trace:
+        out.update(log_score_trace=torch.zeros((T - first + 1, R), **f64), change_share=torch.zeros(max(T - run_first + 1, 0), **f64))
+    if S == 0:
+        return out
+    colour, n_colours = line_colours(eu, ev, ptr)
+    order = np.argsort(colour, kind="stable")
+    colour_ptr = np.concatenate([[0], np.cumsum(np.bincount(colour, minlength=n_colours))])
+    cross_ptr, cross_edge = cross_incoming(eu, ev, cross, S)
+    to = lambda a, t=np.int32: torch.as_tensor(np.ascontiguousarray(a, dtype=t)).to(dev)      # noqa: E731
+    t_eu, t_ev, t_nu, t_step, t_cptr, t_colptr, t_colline = (to(a) for a in (eu, ev, nu, step_edge, cross_ptr, colour_ptr, order))
+    t_cedge = to(np.concatenate([cross_edge, [-1]]))                           # (never empty: the entry refuses a NULL pointer)
+    t_ptr, t_key = to(ptr, np.int64), None if row_key is None else to(key, np.int64)
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    d2 = d2.contiguous()
+    t_score = torch.zeros((S, n), **f64) if score is None else score.contiguous()
+    K = torch.empty_like(d2) if kernel is None else kernel.contiguous()
+    ready = kernel is not None
+    w, scale = torch.empty((S, n), **f64), torch.empty((per, S), **f64)
+    X = out["draw_state"]
+    for a, b in ([(t, t) for t in range(first, T + 1)] if trace else [(first, T)]):
+        before = X.clone() if trace and a >= 1 else None
+        for r0 in range(0, R, per):
+            r1 = min(R, r0 + per)
+            _lib.call(entry, dev, S, E, n, L, t_ptr, t_eu, t_ev, t_nu, t_score, t_g, d2, int(ready), K, t_step, t_cptr, t_cedge, n_colours, t_colptr,
+                      t_colline, t_key, seed, r1 - r0, r0, a, b, w, alpha[r0:r1] if filtered else alpha[:r1 - r0], scale, X[r0:r1])
+        ready = True
+        if trace:
+            out["log_score_trace"][a - first] = graph_log_score(X, None if score is None else t_score, t_g, d2, t_eu, t_ev)
+            if before is not None:
+                out["change_share"][a - run_first] = (X != before).double().mean()
     return out
 
 
 def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=64, *, max_distance, tau=0.1, length=100.0, min_distance=1.0,
-            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None):
+            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None, draws=None, seed=0, draw_sweeps=8):
     """One kept model per sounding, and a weight for every kept model, from the whole survey at once: the chain of
     ``sections`` along every sequence of ``ptr`` plus edges to the nearest sounding of every other sequence within ``max_distance``
     (required; about 1.5 line spacings), solved by ``sweeps`` synchronous sweeps of sum-product message passing with ``damping``.
@@ -999,10 +1292,20 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
     ``edge_u`` / ``edge_v`` int32 [E], ``edge_length`` f64 [E] (m), ``edge_distance`` f64 [E] (D in decades between the chosen models
     of the edge's soundings) and ``residual`` f64 [sweeps].  ``products`` = dict(depth_edges=, percentiles=, thresholds=) adds what
     ``lateral_products`` gives under this ``weight``.  The graph is one problem and is not cut into blocks: E n^2 8 bytes of distances
-    (and as much again for exp(-g D^2)) above ``budget_bytes`` are refused."""
+    (and as much again for exp(-g D^2)) above ``budget_bytes`` are refused.
+
+    ``draws`` = R adds R joint realisations of the whole survey (``graph_draw`` with ``seed`` and ``draw_sweeps`` sweeps, on the K of
+    ``propagate``; the key of a sounding is its index in the survey before soundings without models are dropped):
+    ``draw_state`` / ``draw_slot`` int32 [R, S] (-1: no models; ``draw_models`` gathers the models), ``draw_log_score`` f64 [R]
+    (sum score - sum g d2 over the graph), ``draw_share`` f64 [S, n] (the frequency of every state among the draws, NaN without
+    models: to be read against ``weight``, which is an approximation on loops where the draws' law is exact once mixed) and
+    ``draw_change_share`` f64 [draw_sweeps] (the share of states every sweep changed).  With ``draws`` None every other output keeps
+    its bits."""
     z0, z1, _ = check_window(z0, z1, measure)
     if products is not None:
         products = check_products(products)
+    R = None if draws is None else check_int(draws, 1, MAX_DRAWS, "sections.spatial: draws")
+    seed, draw_sweeps = _check_seed(seed), check_int(draw_sweeps, 0, MAX_DRAW_SWEEPS, "sections.spatial: draw_sweeps")
     k, edges, sigma = ens.k, ens.edges, ens.sigma
     are_tensors((k, edges, sigma), "sections", "spatial", "gbp_ensemble_cross_distance")
     if k.ndim != 2 or edges.ndim != 3:
@@ -1038,7 +1341,8 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
     keep = np.flatnonzero(nu > 0)
     local = np.cumsum(nu > 0) - 1                                              # the soundings with models, renumbered: the order stays
     idx = torch.as_tensor(keep).to(dev)
-    res = propagate(d2, g, local[eu], local[ev], nu[keep], keep.size, score=None if score is None else score[idx], sweeps=sweeps, damping=damping)
+    res = propagate(d2, g, local[eu], local[ev], nu[keep], keep.size, score=None if score is None else score[idx], sweeps=sweeps, damping=damping,
+                    keep_kernel=R is not None)
     nan = float("nan")
     weight, state = torch.full((S, n), nan, **f64), torch.full((S,), -1, dtype=torch.int32, device=dev)
     weight[idx], state[idx] = res["belief"], res["state"]
@@ -1050,6 +1354,18 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
     st = state.long()
     out.update(edge_u=t_u.to(torch.int32), edge_v=t_v.to(torch.int32), edge_length=torch.as_tensor(dist).to(dev),
                edge_distance=torch.sqrt(d2[torch.arange(E, device=dev), st[t_u], st[t_v]]), residual=res["residual"])
+    if R is not None:
+        _, piece_ptr, _ = pieces(p, nu)                                        # the runs of soundings with models: the sequences of the graph
+        drawn = graph_draw(d2, g, local[eu], local[ev], nu[keep], piece_ptr, R, seed=seed, sweeps=draw_sweeps, score=None if score is None else score[idx],
+                           row_key=keep, kernel=res["kernel"], budget_bytes=budget_bytes, trace=True, filtered=False)
+        draw_state = torch.full((R, S), -1, dtype=torch.int32, device=dev)
+        draw_state[:, idx] = drawn["draw_state"]
+        dl = draw_state.long().clamp(min=0)
+        dslot = torch.gather(rows.long()[None, :, :].expand(R, S, n), 2, dl[:, :, None])[:, :, 0].clamp(min=0)
+        share = torch.zeros((S, n), **f64).scatter_add_(1, dl.t().contiguous(), torch.ones((S, R), **f64)) / R
+        out.update(draw_state=draw_state, draw_slot=torch.where(draw_state >= 0, dslot, torch.full_like(dslot, -1)).to(torch.int32),
+                   draw_log_score=drawn["log_score_trace"][-1].clone(), draw_share=torch.where(has[:, None], share, torch.full((), nan, **f64)),
+                   draw_change_share=drawn["change_share"])
     if products is not None:
         out.update(lateral_products(ens, out, **products))
     return out
@@ -1157,6 +1473,10 @@ def _parser():
                         "(about 1.5 line spacings) and write <name>.spatial.npz instead (--max-models <= 256)")
     p.add_argument("--sweeps", type=int, default=None, metavar="N", help="with --spatial: sweeps of message passing (default 32)")
     p.add_argument("--damping", type=float, default=None, metavar="L", help="with --spatial: the damping of the messages in [0, 1) (default 0)")
+    p.add_argument("--spatial-draws", type=int, default=None, metavar="R",
+                   help="with --spatial: joint realisations of the whole survey to draw, 1 .. 65536 (uses --seed); adds draw_state, draw_slot, "
+                        "draw_log_score, draw_share and draw_change_share")
+    p.add_argument("--draw-sweeps", type=int, default=None, metavar="T", help="with --spatial-draws: Gibbs sweeps over the lines (default 8)")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -1198,12 +1518,20 @@ def parse_args(argv=None):
         except ValueError as e:
             p.error("--" + str(e))
     if a.spatial is None:
-        if a.sweeps is not None or a.damping is not None:
-            p.error("--sweeps and --damping need --spatial")
+        if a.sweeps is not None or a.damping is not None or a.spatial_draws is not None:
+            p.error("--sweeps, --damping and --spatial-draws need --spatial")
+        if a.draw_sweeps is not None:
+            p.error("--draw-sweeps needs --spatial-draws")
     else:
         if a.no_marginals or a.draws:
-            p.error("--spatial gives beliefs alone: it takes neither --no-marginals nor --draws")
+            p.error("--spatial takes neither --no-marginals nor --draws (the draws of single lines); joint draws of the survey are --spatial-draws")
+        if a.draw_sweeps is not None and a.spatial_draws is None:
+            p.error("--draw-sweeps needs --spatial-draws")
         try:
+            if a.spatial_draws is not None:
+                check_int(a.spatial_draws, 1, MAX_DRAWS, "--spatial-draws")
+            if a.draw_sweeps is not None:
+                check_int(a.draw_sweeps, 0, MAX_DRAW_SWEEPS, "--draw-sweeps")
             _check_number(a.spatial, "--spatial")
             check_int(a.max_models, 1, MAX_GRAPH_STATES, "--max-models (with --spatial)")
             if a.sweeps is not None:
@@ -1214,6 +1542,8 @@ def parse_args(argv=None):
             p.error(str(e))
         del kw["marginals"]
         kw.update(max_distance=a.spatial, **({} if a.sweeps is None else dict(sweeps=a.sweeps)), **({} if a.damping is None else dict(damping=a.damping)))
+        if a.spatial_draws is not None:
+            kw.update(draws=a.spatial_draws, seed=a.seed, **({} if a.draw_sweeps is None else dict(draw_sweeps=a.draw_sweeps)))
     return a.survey, kw
 
 

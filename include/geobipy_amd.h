@@ -1092,6 +1092,43 @@ gbp_status gbp_section_propagate(int S, int E, int n, const int32_t *eu, const i
                                  double damping, double *K, double *w, double *mu, double *resid, double *belief, int32_t *state,
                                  double *residual, void *stream);
 
+/* Joint draws of the whole graph of gbp_section_propagate by Gibbs sampling blocked by flight line (csrc/gbp_section_graph_draw.h
+ * k_graph_weights, k_graph_line_filter, k_graph_line_draw; the rule is stated in numpy as
+ * sections.graph_draw_reference).  DEVICE arrays throughout, none read on the host.  S, E, n, eu, ev, n_used, score, g, d2 as above.
+ * ptr int64 [L + 1]: the sequences (flight lines) in the same numbering, contiguous, possibly empty.  An edge with ev = eu + 1 inside
+ * one sequence is a step and every consecutive pair of a sequence is one; every other edge joins two sequences: a cross edge.
+ *   step_edge int32 [S]: the edge of the step s -> s + 1, -1 at a sequence's last sounding.
+ *   cross_ptr int32 [S + 1], cross_edge int32 [cross_ptr[S]]: the CSR of every sounding's incoming CROSS directed edges, ids 2 e
+ *   (eu -> ev) and 2 e + 1 (ev -> eu), sorted by the sounding they come from.
+ *   colour_ptr int32 [n_colours + 1], colour_line int32 [L]: the sequences grouped by colour; sequences of one colour share no
+ *   cross edge (sections.line_colours).
+ *   K f64 [E, n, n] = exp(-(g[e] * d2[e])) on the prefixes: with kernel_ready != 0 it already holds what gbp_section_propagate leaves
+ *   in its K for the same arguments, and g and d2 are not read (they may be NULL); otherwise the entry fills it first.
+ * Sweeps first_sweep .. last_sweep inclusive are run for the realisations rho = first_draw .. first_draw + n_draws - 1, which are
+ * independent chains.  Sweep 0, the start, draws every sequence alone, as gbp_section_draw does (cross edges ignored); first_sweep > 0
+ * continues from the states in draw_state.  Sweep t >= 1 takes the colours in ascending order and draws every sequence of a colour
+ * from its conditional given the other colours' current states by forward filtering and backward sampling, with the weights
+ * w'_s[i] = w_s[i] times K_e[i, x_q] (s = eu[e]) or K_e[x_q, i] (s = ev[e]) over the cross edges of s, ascending neighbour q, x_q the
+ * neighbour's state; the filter and the walk are those of gbp_section_draw with K read in place of exp(-(g d2)).
+ * u = u53(x, y) of Philox4x32-10 with key seed and counter (rho, key & 0xFFFFFFFF, key >> 32, sweep), key = row_key[s] (int64 [S];
+ * NULL: s): a draw depends on the seed, the realisation, the sounding's key and the sweep -- not on n_draws, nor on how realisations
+ * are cut into calls by first_draw.
+ * Outputs: draw_state int32 [n_draws, S] (read when first_sweep > 0; every state < m_s); filtered f64 [n_draws, S, n], the alpha of
+ * the last sweep run, 0.0 for the states >= m_s; workspaces w f64 [S, n] and scale f64 [n_draws, S].
+ * One 256-thread workgroup per (sequence, realisation) for the filter (LDS: (2 n + 4) doubles), one wave per (sequence, 64
+ * realisations) for the walk; no atomics: a call repeats its own bits.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, E < 0 or > 2^30 - 1, n < 1 or n > 256, L < 0, n_draws < 1 or > 65536, first_draw < 0
+ * or first_draw + n_draws > 65536, first_sweep < 0, last_sweep < first_sweep or > 65535, E > 0 with S < 2, S > 0 with L < 1,
+ * n_colours outside 1 .. L, sizes out of range, with S > 0 a NULL ptr / n_used / score / step_edge / cross_ptr / colour_ptr /
+ * colour_line or a NULL w / filtered / scale / draw_state, with E > 0 a NULL eu / ev / K / cross_edge, and without kernel_ready a NULL
+ * g / d2.  S == 0 launches nothing.  An index that does not fit is skipped on the device, never followed. */
+gbp_status gbp_section_graph_draw(int S, int E, int n, int L, const int64_t *ptr, const int32_t *eu, const int32_t *ev,
+                                  const int32_t *n_used, const double *score, const double *g, const double *d2, int kernel_ready,
+                                  double *K, const int32_t *step_edge, const int32_t *cross_ptr, const int32_t *cross_edge,
+                                  int n_colours, const int32_t *colour_ptr, const int32_t *colour_line, const int64_t *row_key,
+                                  uint64_t seed, int n_draws, int first_draw, int first_sweep, int last_sweep, double *w,
+                                  double *filtered, double *scale, int32_t *draw_state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
