@@ -1,7 +1,8 @@
 """Device-resident rjMCMC (geobipy_amd/rjmcmc_gpu.py, csrc/gbp_rjmcmc.h).
 
 CPU tier: the counter-based generator against its published known answers, the batched prior against rjmcmc.py.
-GPU tier: every stage kernel against the host emulation (tests/rj_emul.py = rjmcmc.py + the same random streams);
+GPU tier: every stage kernel against the host emulation (tests/rj_emul.py = rjmcmc.py + the same random streams; the Newton and accept
+stages against the rule in long double, at their launch-shape borders: tests/rj_longdouble.py, test_rjmcmc_algebra.py, test_rjmcmc_algebra_gpu.py);
 state coherence after many steps; the posterior accumulators against a host replay; the ensembles against the
 host sampler that reproduces the reference's chains."""
 import ctypes
