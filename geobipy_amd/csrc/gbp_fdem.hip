@@ -2707,3 +2707,59 @@ extern "C" gbp_status gbp_section_graph_draw(int S, int E, int n, int L, const i
 #undef GBP_GRAPH_DRAW
     return GBP_OK;
 }
+
+#include "gbp_bodies.h"
+
+// Connected bodies (gbp_bodies.h): one launch, one workgroup per (realisation, group).  group_ptr, eu and ev are device arrays that the
+// kernel reads; the entry copies them to the host first, behind the stream's earlier work, because an edge that does not fit would be
+// followed outside the outputs: every refusal comes before the launch.
+extern "C" gbp_status gbp_bodies_label(int R, int S, int C, int E, int G, const int64_t* group_ptr, const int32_t* eu, const int32_t* ev,
+                                       const double* raster, double lo, double hi, const double* a, const double* t, double unit,
+                                       int32_t* label, int32_t* cells, int64_t* measure_q, int32_t* sweeps, void* stream)
+{
+    if (R < 1 || R > bodies::MAX_REALISATIONS) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: R must lie in 1 .. 65536%s");
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: S must be >= 0%s");
+    if (C < 1 || C > bodies::MAX_COLUMNS) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: C must lie in 1 .. 4096%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: E must lie in 0 .. 2^30 - 1%s");
+    if (G < 0 || G > S) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: G must lie in 0 .. S%s");
+    if ((long long)R * S * C > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: R * S * C must be below 2^31%s");
+    if (E > 0 && S < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: an edge needs a sounding%s");
+    if (S > 0 && G < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: soundings need a group (G >= 1)%s");
+    if ((a == nullptr) != (t == nullptr)) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: a and t are given together or not at all%s");
+    if (a && !(unit > 0.0 && unit <= 1.7976931348623157e308)) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: unit must be finite and > 0%s");
+    if (S > 0 && (!group_ptr || !raster || !label || !cells || !sweeps))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: NULL pointer (group_ptr, raster, label, cells, sweeps)%s");
+    if (S > 0 && a && !measure_q) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: NULL pointer (measure_q with a and t)%s");
+    if (E > 0 && (!eu || !ev)) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: NULL pointer (eu, ev)%s");
+    if (S == 0) return GBP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int64_t> gp((size_t)G + 1);
+    std::vector<int32_t> hu((size_t)E), hv((size_t)E);
+    GBP_HIP(hipMemcpyAsync(gp.data(), group_ptr, gp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (E > 0) {
+        GBP_HIP(hipMemcpyAsync(hu.data(), eu, hu.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        GBP_HIP(hipMemcpyAsync(hv.data(), ev, hv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    GBP_HIP(hipStreamSynchronize(st));
+    if (gp[0] != 0 || gp[(size_t)G] != S) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: group_ptr must start at 0 and end at S%s");
+    for (int g = 0; g < G; ++g)
+        if (gp[(size_t)g + 1] < gp[(size_t)g]) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: group_ptr must not decrease%s");
+    int g = 0;                                                              // the group of the edge before: the edges come group by group
+    for (int e = 0; e < E; ++e) {
+        const long long u = hu[(size_t)e], v = hv[(size_t)e];
+        if (u < 0 || u >= S || v < 0 || v >= S) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: an edge's sounding lies outside 0 .. S - 1%s");
+        if (u < gp[(size_t)g]) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: the edges must be sorted by the group of eu%s");
+        while (u >= gp[(size_t)g + 1]) ++g;                                 // (u < S = gp[G]: it ends)
+        if (v < gp[(size_t)g] || v >= gp[(size_t)g + 1]) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: an edge joins two groups%s");
+    }
+    if ((long long)R * G > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_bodies_label: R * G out of range%s");
+    const dim3 grid((unsigned)((long long)R * G)), block(bodies::THREADS);
+    if (a)
+        hipLaunchKernelGGL(bodies::k_bodies_label<true>, grid, block, 0, st, S, C, E, G, (const long long*)group_ptr, (const int*)eu, (const int*)ev,
+                           raster, lo, hi, a, t, unit, (int*)label, (int*)cells, (long long*)measure_q, (int*)sweeps);
+    else
+        hipLaunchKernelGGL(bodies::k_bodies_label<false>, grid, block, 0, st, S, C, E, G, (const long long*)group_ptr, (const int*)eu, (const int*)ev,
+                           raster, lo, hi, a, t, unit, (int*)label, (int*)cells, (long long*)nullptr, (int*)sweeps);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}

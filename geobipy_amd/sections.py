@@ -64,6 +64,12 @@ draws of it as far as ``sweeps`` sweeps have mixed, and 8 is a convention.  ``pr
 ``draw_change_share``, and ``--spatial D --spatial-draws R [--seed N] [--draw-sweeps T]`` writes them.  Left out on purpose: the
 filter on the matrix cores, cluster moves and tempering, draws conditioned on boreholes, learning ``tau`` (the pair potential
 exp(-g D^2) is not a normalised transition, so the evidence grows monotonically as g -> 0).
+
+Connected bodies of the realisations (gbp_bodies_label: csrc/gbp_bodies.h, through ``geobipy_amd.bodies``).
+``draw_bodies`` rasters the drawn models, on terrain resamples them onto one elevation axis, labels the connected bodies of the cells
+with lo <= value <= hi and summarises them; ``sections(..., draws=R, bodies=dict(depth_edges=, lo=, hi=))`` and ``spatial(..., draws=R,
+bodies=dict(...))`` add ``body_count``, ``body_largest_measure``, ``body_member_measure`` and ``body_largest_share``, and ``--bodies LO
+HI --depth-axis N WIDTH`` with ``--draws R`` or ``--spatial D --spatial-draws R`` writes them.
 """
 import numpy as np
 import torch
@@ -499,7 +505,7 @@ def _run_sums(terms, piece_ptr):
 
 
 def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=128, tau=0.1, length=100.0, min_distance=1.0, score=None,
-             marginals=True, budget_bytes=4 << 30, draws=0, seed=0, products=None):
+             marginals=True, budget_bytes=4 << 30, draws=0, seed=0, products=None, bodies=None):
     """One kept model per sounding, chosen jointly along every sequence of ``ptr`` [L + 1] (None: one sequence) for the ensemble
     ``ens`` of soundings at ``x``, ``y`` [S] (host; m) over the depth window [z0, z1]: ``families.used_rows`` (``chains``,
     ``max_models`` <= 1024), ``cross_distance`` (squared), ``steps`` (``tau``, ``length``, ``min_distance``), ``track`` and a gather.
@@ -522,12 +528,19 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
 
     ``products`` = dict(depth_edges=, percentiles=, thresholds=) adds what ``lateral_products`` returns for this result: the weighted
     mean, sd, percentiles and exceedance probabilities of every sounding's models under ``weight`` on a depth axis (it needs
-    ``marginals``).  Without it the result is what it was, bit for bit."""
+    ``marginals``).  Without it the result is what it was, bit for bit.
+
+    ``bodies`` = dict(depth_edges=, lo=, hi=, ...) (the keywords of ``draw_bodies`` but the geometry; it needs ``draws``) adds the
+    connected bodies of the realisations along every sequence: ``body_count`` int64 [R, L], ``body_largest_measure`` /
+    ``body_member_measure`` f64 [R, L] (m^2 under the default widths) and ``body_largest_share`` f64 [S, C], the share of realisations
+    in which the cell belongs to the largest body of its sequence.  With None every other output keeps its bits."""
     z0, z1, _ = check_window(z0, z1, measure)
     if products is not None:
         products = check_products(products)
         if not marginals:
             raise ValueError("sections: products are weighted by the smoothed marginals; they need marginals=True")
+    if bodies is not None:
+        bodies = check_bodies(bodies, "sections")
     k, edges, sigma = ens.k, ens.edges, ens.sigma
     are_tensors((k, edges, sigma), "sections", "sections", "gbp_ensemble_cross_distance")
     if k.ndim != 2 or edges.ndim != 3:
@@ -536,6 +549,8 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
     max_models = check_int(max_models, 1, MAX_STATES, "max_models")
     budget_bytes = check_int(budget_bytes, 1, 2 ** 62, "budget_bytes")
     R, seed = check_int(draws, 0, MAX_DRAWS, "draws"), _check_seed(seed)
+    if bodies is not None and not R:
+        raise ValueError("sections: bodies are those of joint realisations; they need draws >= 1")
     S, K = k.shape[0], edges.shape[2]
     x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
     if x.size != S or y.size != S:
@@ -621,6 +636,8 @@ def sections(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mo
         out.update(draw_state=draw_state, draw_slot=torch.where(dhas, dslot, torch.full_like(dslot, -1)).to(torch.int32), draw_log_score=draw_log_score)
     if products is not None:
         out.update(lateral_products(ens, out, **products))
+    if bodies is not None:
+        out.update(_body_products(ens, out["draw_slot"], x, y, p, dict(bodies, group_ptr=p)))
     return out
 
 
@@ -748,6 +765,79 @@ def exceedance_area(k, edges, sigma, x, y, ptr, threshold, z0, z1, above=True):
     counts = (layer < kk) & ((sigma >= threshold) if above else (sigma < threshold))
     thick = torch.where(counts, (bottom.clamp(max=z1) - top.clamp(min=z0)).clamp(min=0.0), zero).sum(dim=2)
     return _run_sums(width[None, :] * thick, p)
+
+
+# ---- connected bodies of the realisations ----------------------------------------------------------------------------
+
+BODY_KEYS = ("depth_edges", "lo", "hi", "log10", "surface", "elevation_edges", "a", "min_cells")
+
+
+def check_bodies(bodies, what):
+    """``bodies`` of ``sections`` / ``spatial`` as keywords of ``draw_bodies``: a dictionary with ``depth_edges`` and optionally ``lo``,
+    ``hi``, ``log10``, ``surface``, ``elevation_edges``, ``a`` and ``min_cells``.  Refuses before any device work."""
+    from .ensembles import centres
+    if not isinstance(bodies, dict) or "depth_edges" not in bodies or not set(bodies) <= set(BODY_KEYS):
+        raise ValueError("%s: bodies is a dictionary with depth_edges and optionally %s" % (what, ", ".join(BODY_KEYS[1:])))
+    centres(bodies["depth_edges"])
+    if "lo" in bodies or "hi" in bodies:
+        from .bodies import _check_bounds
+        _check_bounds(bodies.get("lo", -np.inf), bodies.get("hi", np.inf), what + ": bodies")
+    return dict(bodies, depth_edges=np.asarray(bodies["depth_edges"], dtype=np.float64))
+
+
+def line_edges(ptr):
+    """(eu, ev) int64: the consecutive pairs inside every sequence of ``ptr`` [L + 1] -- the graph of a survey whose lines stand alone."""
+    p = np.asarray(ptr, dtype=np.int64)
+    S = int(p[-1]) if p.size else 0
+    last = np.zeros(S, dtype=bool)
+    last[p[1:][p[1:] > p[:-1]] - 1] = True
+    eu = np.flatnonzero(~last).astype(np.int64)
+    return eu, eu + 1
+
+
+def draw_bodies(ens, draw_slot, depth_edges, x, y, ptr, lo=-np.inf, hi=np.inf, log10=True, eu=None, ev=None, surface=None, elevation_edges=None,
+                a=None, group_ptr=None, **summary_kw):
+    """The connected bodies of joint realisations: ``draw_models(ens, draw_slot, depth_edges, log10)`` rasters the
+    drawn models [R, S, n_depth]; with ``surface`` [S] (the soundings' elevation) ``elevation.resample`` takes the raster onto ONE
+    elevation axis ``elevation_edges`` (default ``elevation.regular_axis`` at the thinnest depth cell's width; NaN, never a member,
+    outside a sounding's mesh), so that lateral adjacency is horizontal; ``bodies.label`` labels the bodies of the cells with lo <=
+    value <= hi (log10 S/m with ``log10``) over the edges ``eu`` / ``ev`` (default: the consecutive pairs inside ``ptr``: every line
+    alone; ``edge_u`` / ``edge_v`` of ``spatial`` join the lines) with ``a`` [S] (default ``section_widths``: the measure is an area
+    in m^2; ``bodies.sounding_areas`` makes it a volume) and the cells' thickness; ``bodies.summary`` (``summary_kw``) sums them up.
+    Returns what ``label`` and ``summary`` return, plus ``a`` and ``t`` (numpy)."""
+    from . import bodies as body_labels, elevation
+    e = elevation.check_depth_edges(depth_edges)
+    S = ens.k.shape[0]
+    p = _default_ptr(ptr, S)
+    if (eu is None) != (ev is None):
+        raise ValueError("sections.draw_bodies: eu and ev are given together or not at all")
+    if eu is None:
+        eu, ev = line_edges(p)
+    a = section_widths(x, y, p) if a is None else np.asarray(host(a), dtype=np.float64).reshape(-1)
+    if surface is not None:
+        axis = elevation.regular_axis(surface, e, float(np.diff(e).min())) if elevation_edges is None else elevation.check_axis(edges=elevation_edges)[1]
+    raster = draw_models(ens, draw_slot, depth_edges=e, log10=log10)["raster"]
+    if surface is None:
+        t = np.diff(e)
+    else:
+        raster = elevation.resample(raster.permute(1, 0, 2).contiguous(), surface, e, edges=axis).permute(1, 0, 2).contiguous()
+        t = np.diff(axis)
+    lab = body_labels.label(raster, lo, hi, eu, ev, group_ptr=group_ptr, a=a, t=t)
+    lab.update(body_labels.summary(lab, **summary_kw))
+    lab.update(a=a, t=t)
+    return lab
+
+
+def _body_products(ens, draw_slot, x, y, ptr, kw):
+    """``body_count``, ``body_largest_measure``, ``body_member_measure`` [R, G] and ``body_largest_share`` [S, C] of ``draw_bodies``."""
+    from .bodies import _cell_groups
+    b = draw_bodies(ens, draw_slot, x=x, y=y, ptr=ptr, **kw)
+    R, S, C = b["label"].shape
+    gid, _ = _cell_groups(b)
+    flat = b["label"].reshape(R, S * C).long()
+    own = torch.gather(b["largest_root"], 1, gid[None, :].expand(R, S * C)) if S * C else flat
+    share = ((flat >= 0) & (flat == own)).to(torch.float64).mean(dim=0).reshape(S, C)
+    return dict(body_count=b["n_bodies"], body_largest_measure=b["largest_measure"], body_member_measure=b["member_measure"], body_largest_share=share)
 
 
 # ---- across lines: belief propagation on the survey graph (DESIGN.md 3.28) -----------------------------------------------------------
@@ -1278,7 +1368,7 @@ def graph_draw(d2, g, eu, ev, n_used, ptr, n_draws, seed=0, sweeps=8, score=None
 
 
 def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=64, *, max_distance, tau=0.1, length=100.0, min_distance=1.0,
-            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None, draws=None, seed=0, draw_sweeps=8):
+            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None, draws=None, seed=0, draw_sweeps=8, bodies=None):
     """One kept model per sounding, and a weight for every kept model, from the whole survey at once: the chain of
     ``sections`` along every sequence of ``ptr`` plus edges to the nearest sounding of every other sequence within ``max_distance``
     (required; about 1.5 line spacings), solved by ``sweeps`` synchronous sweeps of sum-product message passing with ``damping``.
@@ -1300,10 +1390,19 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
     (sum score - sum g d2 over the graph), ``draw_share`` f64 [S, n] (the frequency of every state among the draws, NaN without
     models: to be read against ``weight``, which is an approximation on loops where the draws' law is exact once mixed) and
     ``draw_change_share`` f64 [draw_sweeps] (the share of states every sweep changed).  With ``draws`` None every other output keeps
-    its bits."""
+    its bits.
+
+    ``bodies`` = dict(depth_edges=, lo=, hi=, ...) (it needs ``draws``) adds the connected bodies of the realisations on this graph,
+    ``edge_u`` / ``edge_v`` (``draw_bodies``): ``body_count`` int64, ``body_largest_measure`` / ``body_member_measure``
+    f64 [R, G] per connected piece of the graph (``a`` defaults to ``section_widths``: m^2; give ``bodies.sounding_areas`` for m^3) and
+    ``body_largest_share`` f64 [S, C].  With None every other output keeps its bits."""
     z0, z1, _ = check_window(z0, z1, measure)
     if products is not None:
         products = check_products(products)
+    if bodies is not None:
+        bodies = check_bodies(bodies, "sections.spatial")
+        if draws is None:
+            raise ValueError("sections.spatial: bodies are those of joint realisations; they need draws")
     R = None if draws is None else check_int(draws, 1, MAX_DRAWS, "sections.spatial: draws")
     seed, draw_sweeps = _check_seed(seed), check_int(draw_sweeps, 0, MAX_DRAW_SWEEPS, "sections.spatial: draw_sweeps")
     k, edges, sigma = ens.k, ens.edges, ens.sigma
@@ -1368,6 +1467,8 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
                    draw_change_share=drawn["change_share"])
     if products is not None:
         out.update(lateral_products(ens, out, **products))
+    if bodies is not None:
+        out.update(_body_products(ens, out["draw_slot"], x, y, p, dict(bodies, eu=eu, ev=ev)))
     return out
 
 
@@ -1477,6 +1578,9 @@ def _parser():
                    help="with --spatial: joint realisations of the whole survey to draw, 1 .. 65536 (uses --seed); adds draw_state, draw_slot, "
                         "draw_log_score, draw_share and draw_change_share")
     p.add_argument("--draw-sweeps", type=int, default=None, metavar="T", help="with --spatial-draws: Gibbs sweeps over the lines (default 8)")
+    p.add_argument("--bodies", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="with --depth-axis and --draws (or --spatial-draws): the connected bodies of the realisations' cells with LO <= log10 S/m "
+                        "<= HI (a bound far outside, such as -99 or 99: none); adds body_count, body_largest_measure, body_member_measure and body_largest_share")
     p.add_argument("--device", default="cuda:0")
     return p
 
@@ -1499,9 +1603,13 @@ def parse_args(argv=None):
               marginals=not a.no_marginals, device=a.device)
     if a.draws:
         kw.update(draws=a.draws, seed=a.seed)
+    if a.bodies is not None and not (a.draws if a.spatial is None else a.spatial_draws):
+        p.error("--bodies labels joint realisations: it needs --draws R (or --spatial D --spatial-draws R)")
     if a.depth_axis is None:
         if a.percentiles is not None or a.exceed is not None:
             p.error("--percentiles and --exceed need --depth-axis")
+        if a.bodies is not None:
+            p.error("--bodies needs --depth-axis (the cells the bodies are made of)")
     else:
         try:
             n, w = int(a.depth_axis[0]), float(a.depth_axis[1])
@@ -1517,6 +1625,11 @@ def parse_args(argv=None):
                                                  thresholds=() if a.exceed is None else a.exceed))
         except ValueError as e:
             p.error("--" + str(e))
+        if a.bodies is not None:
+            try:
+                kw["bodies"] = check_bodies(dict(depth_edges=np.arange(n + 1, dtype=np.float64) * w, lo=a.bodies[0], hi=a.bodies[1]), "--bodies")
+            except ValueError as e:
+                p.error(str(e))
     if a.spatial is None:
         if a.sweeps is not None or a.damping is not None or a.spatial_draws is not None:
             p.error("--sweeps, --damping and --spatial-draws need --spatial")

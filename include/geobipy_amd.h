@@ -1129,6 +1129,30 @@ gbp_status gbp_section_graph_draw(int S, int E, int n, int L, const int64_t *ptr
                                   uint64_t seed, int n_draws, int first_draw, int first_sweep, int last_sweep, double *w,
                                   double *filtered, double *scale, int32_t *draw_state, void *stream);
 
+/* Connected bodies of R realisations of a raster (csrc/gbp_bodies.h k_bodies_label; the rule is stated in numpy as
+ * bodies.label_reference).  raster f64 [R, S, C]: S soundings, C cells each (depth or ONE elevation axis).  A cell is a member iff
+ * lo <= v <= hi in fp64 (a NaN never is; +-inf bounds give one-sided thresholds).  Cells (s, c) and (s, c + 1) are adjacent, and
+ * (eu[e], c) and (ev[e], c) for every edge e of eu / ev int32 [E]: undirected, in either direction, repeats allowed.  A body is a
+ * connected set of members.  group_ptr int64 [G + 1] cuts the soundings into contiguous ranges (possibly empty) that no edge leaves;
+ * the edges come group by group: the group of eu[e] does not decrease along e.  DEVICE arrays throughout; group_ptr, eu and ev are
+ * also copied to the host and checked before the launch, which waits for the stream's earlier work (the one departure from
+ * gbp_section_graph_draw: an edge that does not fit would be followed outside the outputs).
+ * Outputs, per realisation: label int32 [R, S, C], -1 for a non-member, else the smallest s * C + c of the cell's body; cells int32
+ * [R, S, C], the number of cells of the body at its root (the cell whose index is its label), 0 elsewhere; measure_q int64 [R, S, C],
+ * at the root the sum over the body of q(s, c) = rint((a[s] * t[c]) / unit), one IEEE operation each, 0 elsewhere, a f64 [S] and t
+ * f64 [C] finite and >= 0 (the caller's to check) with q <= 2^30 when unit = (max a * max t) * 2^-30.  a and t may both be NULL: then
+ * measure_q is not written and may be NULL.  sweeps int32 [R, G]: the sweeps of lateral merging the workgroup took (0 for a group
+ * without edges or soundings).  Integer outputs: exact, independent of any order, and a call repeats its bits.
+ * One 1024-thread workgroup per (realisation, group); 4 B of static LDS; no workgroup reads a word another one writes.
+ * GBP_ERR_INVALID_ARG, before any launch: R outside 1 .. 65536, S < 0, C outside 1 .. 4096, E outside 0 .. 2^30 - 1, G outside
+ * 0 .. S, R * S * C >= 2^31, R * G out of range, E > 0 with S < 1, S > 0 with G < 1, one of a / t alone, with a and t a unit that is
+ * not finite and > 0, with S > 0 a NULL group_ptr / raster / label / cells / sweeps (or measure_q with a and t), with E > 0 a NULL
+ * eu / ev, a group_ptr that does not start at 0, end at S or that decreases, an edge's sounding outside 0 .. S - 1, edges not sorted
+ * by the group of eu, an edge that joins two groups.  S == 0 launches nothing. */
+gbp_status gbp_bodies_label(int R, int S, int C, int E, int G, const int64_t *group_ptr, const int32_t *eu, const int32_t *ev,
+                            const double *raster, double lo, double hi, const double *a, const double *t, double unit, int32_t *label,
+                            int32_t *cells, int64_t *measure_q, int32_t *sweeps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
