@@ -189,6 +189,8 @@ SIGNATURES = {
                                        c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_bodies_label": (c_int, [c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                  ctypes.c_double] + [c_void_p] * 4 + [c_void_p]),
+    "gbp_borehole_score": (c_int, [c_int, c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int]
+                           + [c_void_p] * 5 + [c_int, c_double_p, c_double_p, c_double_p, ctypes.c_double] + [c_void_p] * 3 + [c_void_p]),
     "gbp_debug_math": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
     "gbp_bench_time_forward_loglike": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 10 + [c_void_p, c_int,
                                                                                         ctypes.POINTER(ctypes.c_float)]),

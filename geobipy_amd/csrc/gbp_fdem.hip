@@ -2763,3 +2763,75 @@ extern "C" gbp_status gbp_bodies_label(int R, int S, int C, int E, int G, const 
     GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
+
+#include "gbp_boreholes.h"
+
+// Borehole logs as a score of the kept models (gbp_boreholes.h): one launch, one wave per (sounding, 64 models).  att_ptr, att_bore,
+// bore_ptr and cls are device arrays that the kernel follows; the entry copies them to the host first, behind the stream's earlier
+// work, as gbp_bodies_label does with its edges: every refusal comes before the launch.
+extern "C" gbp_status gbp_borehole_score(int S, int n_slots, int K, const int32_t* ens_k, const double* ens_edges, const double* ens_sigma,
+                                         int n, const int32_t* rows, const int32_t* n_used, int A, const int32_t* att_ptr,
+                                         const int32_t* att_bore, const double* att_var, const double* att_shift, int Nb,
+                                         const int32_t* bore_ptr, int I, const double* top, const double* bottom, const double* value,
+                                         const double* sd, const int32_t* cls, int C, const double* class_mean, const double* class_scale,
+                                         const double* class_ln_prior, double class_floor, double* score, double* part, int32_t* skipped,
+                                         void* stream)
+{
+    using namespace boreholes;
+    if (S < 0 || n_slots < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: negative or zero size%s");
+    if (n < 1 || n > MAX_MODELS) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: n outside 1 .. 1024%s");
+    if (K < 1 || K > MAX_K) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: K outside 1 .. 64%s");
+    if (C < 0 || C > MAX_CLASSES) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: C outside 0 .. 16%s");
+    if (A < 0 || Nb < 0 || I < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: A, Nb and I must be >= 0%s");
+    if (A > 0 && Nb < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: an attachment needs a borehole%s");
+    if (!(class_floor > 0.0 && class_floor < 1.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: class_floor must lie in (0, 1)%s");
+    if (C > 0 && (!class_mean || !class_scale || !class_ln_prior))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: NULL pointer (class_mean, class_scale, class_ln_prior)%s");
+    for (int c = 0; c < C; ++c) {
+        if (!std::isfinite(class_mean[c]) || !std::isfinite(class_ln_prior[c]))
+            return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: every class mean and log prior must be finite%s");
+        if (!(std::isfinite(class_scale[c]) && class_scale[c] > 0.0))
+            return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: every class scale must be finite and positive%s");
+    }
+    const int chunks = (n + WAVE - 1) / WAVE;
+    if ((int64_t)S * chunks * WAVE > 0xffffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: S * waves out of range (more than 2^32 - 1 threads)%s");
+    if ((int64_t)A * n > 0x7fffffffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: A * n out of range%s");
+    if (S == 0) return GBP_OK;                     // (an empty block: empty device arrays have no address)
+    if (!ens_k || !ens_edges || !ens_sigma || !rows || !n_used || !att_ptr || !score)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: NULL pointer (ens_k, ens_edges, ens_sigma, rows, n_used, att_ptr, score)%s");
+    if (A > 0 && (!att_bore || !att_var || !att_shift || !bore_ptr))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: NULL pointer (att_bore, att_var, att_shift, bore_ptr)%s");
+    if (A > 0 && I > 0 && (!top || !bottom || !value || !sd || !cls))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: NULL pointer (top, bottom, value, sd, cls)%s");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> ap((size_t)S + 1), ab((size_t)A), bp(A > 0 ? (size_t)Nb + 1 : 0), hc(A > 0 ? (size_t)I : 0);
+    GBP_HIP(hipMemcpyAsync(ap.data(), att_ptr, ap.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (A > 0) {
+        GBP_HIP(hipMemcpyAsync(ab.data(), att_bore, ab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        GBP_HIP(hipMemcpyAsync(bp.data(), bore_ptr, bp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (I > 0) GBP_HIP(hipMemcpyAsync(hc.data(), cls, hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    GBP_HIP(hipStreamSynchronize(st));
+    if (ap[0] != 0 || ap[(size_t)S] != A) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: att_ptr must start at 0 and end at A%s");
+    for (int s = 0; s < S; ++s)
+        if (ap[(size_t)s + 1] < ap[(size_t)s]) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: att_ptr must not decrease%s");
+    if (A > 0) {
+        if (bp[0] != 0 || bp[(size_t)Nb] != I) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: bore_ptr must start at 0 and end at I%s");
+        for (int b = 0; b < Nb; ++b)
+            if (bp[(size_t)b + 1] < bp[(size_t)b]) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: bore_ptr must not decrease%s");
+        for (int e = 0; e < A; ++e)
+            if (ab[(size_t)e] < 0 || ab[(size_t)e] >= Nb) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: an attachment's borehole lies outside 0 .. Nb - 1%s");
+        for (int i = 0; i < I; ++i)
+            if (hc[(size_t)i] < -1 || hc[(size_t)i] >= C) return fail(GBP_ERR_INVALID_ARG, "gbp_borehole_score: an interval's class lies outside -1 .. C - 1%s");
+    }
+    ScoreArgs a = {};
+    a.S = S; a.n_slots = n_slots; a.K = K; a.n = n; a.C = C; a.chunks = chunks;
+    a.ens_k = ens_k; a.ens_edges = ens_edges; a.ens_sigma = ens_sigma; a.rows = rows; a.n_used = n_used;
+    a.att_ptr = att_ptr; a.att_bore = att_bore; a.att_var = att_var; a.att_shift = att_shift; a.bore_ptr = bore_ptr;
+    a.top = top; a.bottom = bottom; a.value = value; a.sd = sd; a.cls = cls;
+    for (int c = 0; c < C; ++c) { a.mean[c] = class_mean[c]; a.scale[c] = class_scale[c]; a.ln_prior[c] = class_ln_prior[c]; }
+    a.floor = class_floor; a.score = score; a.part = part; a.skipped = skipped;
+    hipLaunchKernelGGL(k_borehole_score, dim3((unsigned)((int64_t)S * chunks)), dim3(WAVE), lds_bytes(K), st, a);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}

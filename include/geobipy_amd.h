@@ -1153,6 +1153,37 @@ gbp_status gbp_bodies_label(int R, int S, int C, int E, int G, const int64_t *gr
                             const double *raster, double lo, double hi, const double *a, const double *t, double unit, int32_t *label,
                             int32_t *cells, int64_t *measure_q, int32_t *sweeps, void *stream);
 
+/* Borehole logs as a log weight of the kept models (csrc/gbp_boreholes.h k_borehole_score; the rule is stated in numpy
+ * as boreholes.score_reference).  The ensemble and rows int32 [S, n] / n_used int32 [S] are those of gbp_ensemble_cross_distance; model
+ * m of sounding s is rows[s, m], absent when m >= n_used[s], the row lies outside the slots or k <= 0.  Nb boreholes hold I intervals
+ * (bore_ptr int32 [Nb + 1]): top, bottom f64 [I] in metres below the collar, ascending and not overlapping within a borehole; cls int32
+ * [I] is -1 for a MEASURED interval (value f64 log10 S/m, sd f64 > 0 decades) and a class in 0 .. C - 1 for a LITHOLOGY interval.
+ * The A attachments of borehole att_bore[a] to sounding s are att_ptr[s] .. att_ptr[s + 1] - 1 (int32 [S + 1]), each with att_var >= 0
+ * (decades^2) and att_shift (m).  DEVICE arrays throughout but class_mean, class_scale, class_ln_prior (HOST, f64 [C]).
+ * For every attachment a of s in order, every interval in order and every present model with interfaces e and a_l = log10 sigma_l:
+ * t' = max(top + shift, 0), b' = bottom + shift; b' <= t' is skipped and counted in skipped[a]; h = b' - t'; the segments [p, q] are
+ * the merge of [t', b'] with the layers, from the layer after the last interface <= t', q = fmin(next interface, b'), the layer
+ * advanced where the interface == q; mean = (sum (q - p) f_l) / h.  MEASURED: f_l = a_l, term = -((mean - value)^2) / (2 (sd^2 + var)).
+ * LITHOLOGY of class c: l_q(x) = ln_prior_q - 0.5 ln(v_q) - (x - mean_q)^2 / (2 v_q), v_q = scale_q^2 + var; f_l = 1 / sum_q
+ * exp(l_q(a_l) - l_c(a_l)), q ascending; term = ln(class_floor + (1 - class_floor) mean).  part[a, m] = the sum of the terms,
+ * score[s, m] = the sum of the parts in attachment order; 0.0 for an absent model and for a sounding without attachments.  Constants
+ * common to all models of a sounding are dropped; the interval mean is taken in log10 conductivity.
+ * Outputs: score f64 [S, n], every entry written; part f64 [A, n] and skipped int32 [A], each of which may be NULL.
+ * One wave per (sounding, 64 models); dynamic LDS 64 (2 K - 1) doubles; no atomics: a call repeats its bits.  att_ptr, att_bore,
+ * bore_ptr and cls are copied to the host and checked before the launch, which waits for the stream's earlier work.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, n_slots < 1, n outside 1 .. 1024, K outside 1 .. 64, C outside 0 .. 16, A, Nb or I
+ * < 0, A > 0 with Nb < 1, class_floor outside (0, 1), with C > 0 a NULL class array, a class mean or log prior that is not finite, a
+ * class scale that is not finite and positive, sizes out of range, with S > 0 a NULL ensemble / rows / n_used / att_ptr / score, with
+ * A > 0 a NULL att_bore / att_var / att_shift / bore_ptr, with A > 0 and I > 0 a NULL interval array, an att_ptr or bore_ptr that does
+ * not start at 0, end at A (I) or that decreases, an attachment's borehole outside 0 .. Nb - 1, a class outside -1 .. C - 1.
+ * S == 0 launches nothing. */
+gbp_status gbp_borehole_score(int S, int n_slots, int K, const int32_t *ens_k, const double *ens_edges, const double *ens_sigma, int n,
+                              const int32_t *rows, const int32_t *n_used, int A, const int32_t *att_ptr, const int32_t *att_bore,
+                              const double *att_var, const double *att_shift, int Nb, const int32_t *bore_ptr, int I, const double *top,
+                              const double *bottom, const double *value, const double *sd, const int32_t *cls, int C,
+                              const double *class_mean, const double *class_scale, const double *class_ln_prior, double class_floor,
+                              double *score, double *part, int32_t *skipped, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
