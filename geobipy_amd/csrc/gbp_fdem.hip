@@ -2640,6 +2640,124 @@ extern "C" gbp_status gbp_section_propagate(int S, int E, int n, const int32_t* 
     return GBP_OK;
 }
 
+#include "gbp_section_graph_path.h"
+
+// level_ptr / colour_ptr (HOST, [count + 1]): from 0 to S without a decrease.
+static bool graph_groups_fit(const int32_t* group_ptr, int count, int S)
+{
+    if (group_ptr[0] != 0 || group_ptr[count] != S) return false;
+    for (int c = 0; c < count; ++c)
+        if (group_ptr[c + 1] < group_ptr[c]) return false;
+    return true;
+}
+
+// The most probable section (gbp_section_graph_path.h): the messages start at 0.0, one launch per sweep with one workgroup per undirected
+// edge, the residuals of all sweeps in one launch, the max-marginals, then the decode with one launch per breadth-first level.  Every
+// refusal comes before any launch; no device array is read on the host (level_ptr is a host array).
+extern "C" gbp_status gbp_section_graph_path(int S, int E, int n, const int32_t* eu, const int32_t* ev, const int32_t* n_used,
+                                             const double* score, const double* g, const double* d2, const int32_t* in_ptr,
+                                             const int32_t* in_edge, int sweeps, double damping, int n_levels, const int32_t* level_ptr,
+                                             const int32_t* level_node, const int32_t* level, double* nu, double* resid,
+                                             double* max_marginal, int32_t* decoded_state, double* residual, void* stream)
+{
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: S must be >= 0%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: E must lie in 0 .. 2^30 - 1%s");
+    if (n < 1 || n > section::GRAPH_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: n must lie in 1 .. 256%s");
+    if (sweeps < 1) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: sweeps must be >= 1%s");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: damping must lie in [0, 1)%s");
+    if (E > 0 && S < 2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: an edge needs two soundings%s");
+    if ((long long)S + 2LL * E > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: S + 2 E out of range%s");
+    if (E > 0 && (long long)E > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: E * n * n out of range%s");
+    if (E > 0 && (long long)sweeps > 0x7fffffffffffffffLL / 16 / E) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: sweeps * 2 E out of range%s");
+    if (S > 0 && (n_levels < 1 || n_levels > S)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: n_levels must lie in 1 .. S%s");
+    if (S > 0 && (!n_used || !score || !in_ptr || !level_ptr || !level_node || !level))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: NULL pointer (n_used, score, in_ptr, level_ptr, level_node, level)%s");
+    if (S > 0 && (!max_marginal || !decoded_state || !residual))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: NULL pointer (max_marginal, decoded_state, residual)%s");
+    if (E > 0 && (!eu || !ev || !g || !d2 || !in_edge || !nu || !resid))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: NULL pointer (eu, ev, g, d2, in_edge, nu, resid)%s");
+    if (S == 0) return GBP_OK;
+    if (!graph_groups_fit(level_ptr, n_levels, S))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_path: level_ptr must start at 0, not decrease and end at S%s");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(section::THREADS);
+    const size_t half = (size_t)2 * E * n;                                  // one message buffer
+    if (E > 0) GBP_HIP(hipMemsetAsync(nu, 0, 2 * half * sizeof(double), st));
+    for (int t = 0; E > 0 && t < sweeps; ++t) {
+        const double* from = nu + (size_t)(t & 1) * half;
+        double* to = nu + (size_t)((t + 1) & 1) * half;
+        double* r = resid + (size_t)t * 2 * E;
+#define GBP_GRAPH_MAXSUM(DAMP, MAXN)                                                                                                     \
+    hipLaunchKernelGGL((section::k_graph_maxsum<DAMP, MAXN>), dim3((unsigned)E), block, 0, st, S, E, n, (const int*)eu, (const int*)ev,    \
+                       (const int*)n_used, score, g, d2, (const int*)in_ptr, (const int*)in_edge, from, to, damping, r)
+        if (n <= 64) {
+            if (damping != 0.0) GBP_GRAPH_MAXSUM(true, 64);
+            else GBP_GRAPH_MAXSUM(false, 64);
+        } else {
+            if (damping != 0.0) GBP_GRAPH_MAXSUM(true, section::GRAPH_MAX_STATES);
+            else GBP_GRAPH_MAXSUM(false, section::GRAPH_MAX_STATES);
+        }
+#undef GBP_GRAPH_MAXSUM
+        GBP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(section::k_graph_residual, dim3((unsigned)sweeps), block, 0, st, 2LL * E, (const double*)resid, residual);
+    GBP_HIP(hipGetLastError());
+    const double* last = nu ? nu + (size_t)(sweeps & 1) * half : nu;
+    hipLaunchKernelGGL(section::k_graph_maxmarginal, dim3((unsigned)S), block, 0, st, E, n, (const int*)n_used, score, (const int*)in_ptr,
+                       (const int*)in_edge, last, max_marginal);
+    GBP_HIP(hipGetLastError());
+    for (int l = 0; l < n_levels; ++l) {
+        const int count = level_ptr[l + 1] - level_ptr[l];
+        if (count == 0) continue;
+        hipLaunchKernelGGL(section::k_graph_condition<false>, dim3((unsigned)count), block, 0, st, S, E, n, (const int*)eu, (const int*)ev,
+                           (const int*)n_used, score, g, d2, (const int*)in_ptr, (const int*)in_edge, last, (const int*)level,
+                           (const int*)level_node + level_ptr[l], count, (int*)decoded_state, (int*)nullptr, 0);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
+// Coordinate ascent on the exact score (gbp_section_graph_path.h k_graph_condition<true>): per sweep one launch per colour of soundings,
+// a workgroup for every (candidate, sounding of the colour).  All `refine` sweeps are launched: a candidate that has stopped moving
+// adds nothing to its later counters, and no counter is read on the host.  Every refusal comes before any launch.
+extern "C" gbp_status gbp_section_graph_refine(int S, int E, int n, int C, const int32_t* eu, const int32_t* ev, const int32_t* n_used,
+                                               const double* score, const double* g, const double* d2, const int32_t* in_ptr,
+                                               const int32_t* in_edge, int n_colours, const int32_t* colour_ptr,
+                                               const int32_t* colour_node, int refine, int32_t* state, int32_t* moves, void* stream)
+{
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: S must be >= 0%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: E must lie in 0 .. 2^30 - 1%s");
+    if (n < 1 || n > section::GRAPH_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: n must lie in 1 .. 256%s");
+    if (C < 1 || C > section::MAX_DRAWS + 1) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: C must lie in 1 .. 65537%s");
+    if (refine < 0 || refine > 65536) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: refine must lie in 0 .. 65536%s");
+    if (E > 0 && S < 2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: an edge needs two soundings%s");
+    if ((long long)S + 2LL * E > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: S + 2 E out of range%s");
+    if (E > 0 && (long long)E > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: E * n * n out of range%s");
+    if ((long long)C * S > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: C * S out of range%s");
+    if (S > 0 && (n_colours < 1 || n_colours > S)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: n_colours must lie in 1 .. S%s");
+    if (S > 0 && (!n_used || !score || !in_ptr || !colour_ptr || !colour_node || !state))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: NULL pointer (n_used, score, in_ptr, colour_ptr, colour_node, state)%s");
+    if (S > 0 && refine > 0 && !moves) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: moves is NULL%s");
+    if (E > 0 && (!eu || !ev || !g || !d2 || !in_edge)) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: NULL pointer (eu, ev, g, d2, in_edge)%s");
+    if (S == 0 || refine == 0) return GBP_OK;
+    if (!graph_groups_fit(colour_ptr, n_colours, S))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_refine: colour_ptr must start at 0, not decrease and end at S%s");
+    hipStream_t st = (hipStream_t)stream;
+    GBP_HIP(hipMemsetAsync(moves, 0, (size_t)C * refine * sizeof(int32_t), st));
+    for (int t = 0; t < refine; ++t) {
+        for (int c = 0; c < n_colours; ++c) {
+            const int count = colour_ptr[c + 1] - colour_ptr[c];
+            if (count == 0) continue;
+            hipLaunchKernelGGL(section::k_graph_condition<true>, dim3((unsigned)((long long)C * count)), dim3(section::THREADS), 0, st, S, E, n,
+                               (const int*)eu, (const int*)ev, (const int*)n_used, score, g, d2, (const int*)in_ptr, (const int*)in_edge,
+                               (const double*)nullptr, (const int*)nullptr, (const int*)colour_node + colour_ptr[c], count, (int*)state,
+                               (int*)moves + t, refine);
+            GBP_HIP(hipGetLastError());
+        }
+    }
+    return GBP_OK;
+}
+
 #include "gbp_section_graph_draw.h"
 
 // Joint draws across lines (gbp_section_graph_draw.h): K unless the caller has it, the weights, then per sweep a filter launch and a draw

@@ -54,7 +54,18 @@ its line and to the nearest sounding of every other line within ``max_distance``
 and returns *beliefs*: the marginals on a forest, a documented approximation on a graph with loops; ``spatial`` is all of it for an
 ensemble, with the keys of ``sections`` that still have a meaning, and ``spatial_from_survey`` / ``from_survey(..., spatial=dict(
 max_distance=...))`` / ``--spatial MAX_DISTANCE [--sweeps N] [--damping L]`` (``<name>.spatial.npz``) for a survey.  Left out on
-purpose: max-product on the graph, tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
+purpose: tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
+
+The most probable section across lines (gbp_section_graph_path, gbp_section_graph_refine:
+csrc/gbp_section_graph_path.h).  ``state`` of ``spatial`` is every sounding's most believed model taken alone; ``graph_path`` finds
+one section for the whole graph: max-sum message passing in the log domain (``graph_path_reference`` states the rule, and the device
+has its bits: there is no exp and no reordered sum), a decode that conditions level by level (``decode_levels``) so that equal modes
+are never mixed, and coordinate ascent on the exact score (``refine``, ``sounding_colours``) from the decode and from any candidates
+given, of which the most probable is kept.  Exact on a forest; on loops an approximation that is never below its candidates.
+``spatial(..., path=True)`` adds ``path_state``, ``path_slot``, ``path_k`` / ``path_edges`` / ``path_sigma``, ``path_log_score``
+beside ``state_log_score``, ``path_margin``, ``path_residual``, ``path_candidate_log_score``, ``path_chosen`` and
+``path_edge_distance``; ``--spatial D --path [SWEEPS]`` writes them.  Left out on purpose: tree-reweighted variants, cluster moves,
+learning ``tau``.
 
 Joint draws across lines (gbp_section_graph_draw: csrc/gbp_section_graph_draw.h).  ``graph_draw`` draws R joint
 realisations of the whole graph by Gibbs sampling blocked by flight line (``graph_draw_reference`` states the rule, ``line_colours``
@@ -1394,8 +1405,362 @@ def graph_draw(d2, g, eu, ev, n_used, ptr, n_draws, seed=0, sweeps=8, score=None
     return out
 
 
+# ---- across lines: the most probable section by max-sum message passing ---------------------------------------------
+
+MAX_REFINE = 65536
+MAX_CANDIDATES = 65536
+PATH_KEYS = ("sweeps", "damping", "refine")
+
+
+def _first_above(v):
+    """(position, value) of the first maximum of ``v`` from -inf, replaced on strict >: a NaN never wins, and without an entry above
+    -inf the result is (0, -inf)."""
+    ok = v > -np.inf
+    if not ok.any():
+        return 0, v.dtype.type(-np.inf)
+    i = int(np.argmax(np.where(ok, v, -np.inf)))                              # the first of equal maxima
+    return i, v[i]
+
+
+def _check_edges(eu, ev, n_soundings, what):
+    S = check_int(n_soundings, 0, 2 ** 31 - 1, "%s: n_soundings" % what)
+    eu, ev = host(eu).reshape(-1), host(ev).reshape(-1)
+    if eu.size != ev.size or (eu.size and (eu.dtype.kind not in "iu" or ev.dtype.kind not in "iu")):
+        raise ValueError("%s: eu and ev must hold one integer per edge" % what)
+    eu, ev = eu.astype(np.int64), ev.astype(np.int64)
+    if np.any(eu < 0) or np.any(ev >= S) or np.any(eu >= ev) or np.any(np.diff(eu * S + ev) <= 0):
+        raise ValueError("%s: the edges need 0 <= eu < ev < %d, sorted by (eu, ev) without duplicates" % (what, S))
+    return eu, ev, S
+
+
+def _neighbour_lists(eu, ev, S):
+    """Per sounding the directed edges that come in (ascending neighbour) and the neighbours they come from."""
+    in_ptr, in_edge = incoming(eu, ev, S)
+    src = np.empty(2 * eu.size, dtype=np.int64)
+    src[0::2], src[1::2] = eu, ev
+    inc = [in_edge[in_ptr[s]:in_ptr[s + 1]] for s in range(S)]
+    return inc, src
+
+
+def decode_levels(eu, ev, n_soundings):
+    """The order in which ``graph_path`` decides the soundings (host, numpy): ``level`` int32 [S], the breadth-first level of every
+    sounding counted from the lowest index of its connected piece (that sounding has level 0), neighbours visited in ascending order;
+    ``level_ptr`` int32 [n_levels + 1] and ``level_node`` int32 [S], the soundings sorted by level (ascending index within one).  On a
+    forest every sounding of level l > 0 has exactly one neighbour of a lower level, its parent."""
+    eu, ev, S = _check_edges(eu, ev, n_soundings, "sections.decode_levels")
+    inc, src = _neighbour_lists(eu, ev, S)
+    level = np.full(S, -1, dtype=np.int32)
+    for root in range(S):
+        if level[root] >= 0:
+            continue
+        level[root] = 0
+        queue, at = [root], 0
+        while at < len(queue):
+            s = queue[at]
+            at += 1
+            for q in src[inc[s]]:
+                if level[q] < 0:
+                    level[q] = level[s] + 1
+                    queue.append(int(q))
+    level_ptr = np.concatenate([[0], np.cumsum(np.bincount(level, minlength=1 if S else 0))]).astype(np.int32)
+    return level, level_ptr, np.argsort(level, kind="stable").astype(np.int32)
+
+
+def sounding_colours(eu, ev, n_soundings):
+    """A colouring of the soundings (host, numpy) for the coordinate ascent of ``refine``: greedy in ascending index, every sounding
+    taking the smallest colour no lower-indexed neighbour holds.  Returns ``colour`` int32 [S] and ``n_colours``.  Soundings of one
+    colour share no edge, so moving them together is moving them one after the other."""
+    eu, ev, S = _check_edges(eu, ev, n_soundings, "sections.sounding_colours")
+    inc, src = _neighbour_lists(eu, ev, S)
+    colour = np.zeros(S, dtype=np.int32)
+    for s in range(S):
+        taken = {int(colour[q]) for q in src[inc[s]] if q < s}
+        c = 0
+        while c in taken:
+            c += 1
+        colour[s] = c
+    return colour, int(colour.max(initial=-1)) + 1
+
+
+def _colour_lists(eu, ev, S):
+    """``colour_ptr`` int32 [n_colours + 1] and ``colour_node`` int32 [S]: the soundings sorted by colour."""
+    colour, n_colours = sounding_colours(eu, ev, S)
+    colour_ptr = np.concatenate([[0], np.cumsum(np.bincount(colour, minlength=n_colours))]).astype(np.int32)
+    return colour_ptr, np.argsort(colour, kind="stable").astype(np.int32)
+
+
+def _check_states(state, nu, most, what, name):
+    """``state`` (host or device) as numpy int32 [R, S] with every entry in 0 .. n_used - 1; also whether it came as one row [S]."""
+    x = host(state)
+    single = x.ndim == 1
+    x = x[None, :] if single else x
+    if x.ndim != 2 or x.shape[1] != nu.size or x.dtype.kind not in "iu" or not 1 <= x.shape[0] <= most:
+        raise ValueError("%s: %s must hold one integer per sounding, [S] or [R, S] with S = %d and 1 <= R <= %d" % (what, name, nu.size, most))
+    if np.any(x < 0) or np.any(x >= nu[None, :]):
+        raise ValueError("%s: every entry of %s must lie in 0 .. n_used - 1" % (what, name))
+    return np.ascontiguousarray(x, dtype=np.int32), single
+
+
+def _path_terms(eu, ev, g, d2, nu, score):
+    """theta_s on the prefix (zeros without a score) and c_e = g[e] * d2[e] on the prefixes, one multiply."""
+    g = np.asarray(host(g), dtype=np.float64).reshape(-1)
+    theta = [np.zeros(nu[s]) if score is None else score[s, :nu[s]].copy() for s in range(nu.size)]
+    return theta, [g[e] * d2[e, :nu[eu[e]], :nu[ev[e]]] for e in range(eu.size)]
+
+
+def _cost_to(c, d, x):
+    """The costs of the states of the sounding directed edge ``d`` ends in, its source at state ``x``: 2 e + 1 comes from ev[e] into
+    eu[e] (column x of c_e), 2 e from eu[e] into ev[e] (row x)."""
+    return c[d >> 1][:, x] if d & 1 else c[d >> 1][x, :]
+
+
+def _refine_rule(X, theta, c, eu, ev, sweeps):
+    """Coordinate ascent of one section ``X`` int32 [S], in place; returns the moves of every sweep, int32 [sweeps]."""
+    S = X.size
+    inc, src = _neighbour_lists(eu, ev, S)
+    colour, n_colours = sounding_colours(eu, ev, S)
+    moves = np.zeros(sweeps, dtype=np.int32)
+    for t in range(sweeps):
+        for col in range(n_colours):
+            for s in np.flatnonzero(colour == col):                           # (they share no edge: together is one after the other)
+                v = theta[s].copy()
+                for d in inc[s]:                                              # ascending neighbour
+                    v = v - _cost_to(c, int(d), X[src[d]])
+                i, top = _first_above(v)
+                if top > v[X[s]]:
+                    X[s] = i
+                    moves[t] += 1
+        if moves[t] == 0:
+            break
+    return moves
+
+
+def _host_log_score(X, score, g, d2, eu, ev):
+    """``graph_log_score`` of numpy states on the host."""
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt))      # noqa: E731
+    return graph_log_score(t(X, np.int32), None if score is None else t(score, np.float64), t(host(g).reshape(-1), np.float64), t(d2, np.float64),
+                           t(eu, np.int64), t(ev, np.int64)).numpy()
+
+
+def refine_reference(state, eu, ev, g, d2, n_used, score=None, sweeps=16):
+    """The rule of ``refine`` in numpy: coordinate ascent on the exact log score sum_s score[s, x_s] - sum_e g[e] d2[e, x_u, x_v] of
+    the sections ``state`` int [S] or [R, S] on the graph of ``propagate_reference``.  ``sounding_colours`` colours the soundings; a
+    sweep visits the colours in ascending order and the soundings of a colour together.  For sounding s, v[i] = theta_s[i] (the score,
+    0.0 without one) minus c_e at (x_q, i) for every neighbour q in ascending order, c_e = g[e] * d2[e]; s moves to the first maximum
+    of v over i < m_s (from -inf on strict >) only if v there is strictly greater than v[x_s]: every move raises the score, and a NaN
+    moves nothing.  A section stops after a sweep without a move or after ``sweeps`` sweeps.
+
+    Returns ``state`` int32 (the shape given), ``refine_moves`` int32 [R, sweeps] ([sweeps] for one section) and ``log_score`` f64 [R]
+    (a number for one section; ``graph_log_score``)."""
+    what = "sections.refine_reference"
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    eu, ev, nu, _, _ = _check_graph(eu, ev, g, d2, n_used, score, 1, 0.0, what)
+    sweeps = check_int(sweeps, 0, MAX_REFINE, "%s: sweeps" % what)
+    X, single = _check_states(state, nu, MAX_CANDIDATES + 1, what, "state")
+    X = X.copy()
+    theta, c = _path_terms(eu, ev, g, d2, nu, score)
+    with np.errstate(invalid="ignore"):
+        moves = np.stack([_refine_rule(X[r], theta, c, eu, ev, sweeps) for r in range(X.shape[0])])
+    ls = _host_log_score(X, score, g, d2, eu, ev)
+    return dict(state=X[0] if single else X, refine_moves=moves[0] if single else moves, log_score=ls[0] if single else ls)
+
+
+def graph_path_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.0, refine=16, candidates=None):
+    """The rule of ``graph_path`` in numpy (fp64: what the device is held to, bit for bit): the most probable section of the graph of
+    ``propagate_reference`` -- the same arguments -- by synchronous max-sum message passing, a decode by conditioning and coordinate
+    ascent.  Everything is in the log domain; there is no exp.
+
+    Terms.  theta_s[i] = score[s, i] (None: 0.0); c_e[i, j] = g[e] * d2[e, i, j], one multiply.  Directed edge 2 e is u -> v through
+    c_e, 2 e + 1 is v -> u through its transpose; the message nu[d] has m_dst entries and starts at 0.0.
+    A sweep computes every message from the last sweep's.  For a -> b: h[i] = theta_a[i] + nu[c -> a][i] over the neighbours c != b of
+    a, ascending c; u[j] = the maximum over i < m_a of h[i] - c[i, j], from -inf and replaced on strict >, so a NaN candidate never
+    wins (the convention of ``track_reference``); top = the maximum of u by the same loop; nu' = u - top: the largest entry is 0.0.  A
+    message with no candidate above -inf is NaN through (-inf) - (-inf), as a zero total is in ``propagate_reference``.  With
+    ``damping`` = lam != 0 nu' = (1 - lam) nu' + lam nu_old.  ``residual[t]`` is the largest |nu' - nu_old| of sweep t (NaN if a
+    message is; 0.0 without edges).
+    ``max_marginal`` [S, n] = theta_s plus all incoming messages (ascending neighbour), minus its maximum; -inf for the states >= m_s.
+    On a tree, once the sweeps have reached its diameter, max_marginal[s, i] is exactly the log probability lost by forcing sounding s
+    onto model i.
+    Decode.  ``decode_levels`` gives every sounding a breadth-first level; the levels decide in ascending order, the soundings of a level
+    together: x_s = the first maximum over i < m_s of theta_s[i] plus, per neighbour q ascending, -c at (x_q, i) if level(q) <
+    level(s), else nu[q -> s][i].  On a forest every sounding then conditions on exactly one decided neighbour, its parent, and the
+    decode is a mode whatever the ties -- where the argmax of the max-marginals sounding by sounding mixes equal modes.  On a graph
+    with loops it is an approximation.
+    Refine and choose.  The decode and every row of ``candidates`` (int [C, S], states in 0 .. n_used - 1; None: none) are refined by
+    ``refine`` sweeps of ``refine_reference``; the result is the refined candidate whose ``graph_log_score`` is the first maximum:
+    never less probable than any candidate given.
+
+    Returns ``state`` int32 [S], ``log_score``, ``max_marginal`` [S, n], ``residual`` [sweeps], ``decoded_state`` int32 [S] (before the
+    refinement), ``candidate_state`` int32 [C + 1, S] (refined; row 0 from the decode), ``candidate_log_score`` [C + 1], ``chosen`` and
+    ``refine_moves`` int32 [C + 1, refine]."""
+    what = "sections.graph_path_reference"
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    eu, ev, nu, sweeps, damping = _check_graph(eu, ev, g, d2, n_used, score, sweeps, damping, what)
+    refine = check_int(refine, 0, MAX_REFINE, "%s: refine" % what)
+    given = None if candidates is None else _check_states(candidates, nu, MAX_CANDIDATES, what, "candidates")[0]
+    E, n, S = d2.shape[0], d2.shape[1], nu.size
+    theta, c = _path_terms(eu, ev, g, d2, nu, score)
+    inc, src = _neighbour_lists(eu, ev, S)
+    dst = np.empty(2 * E, dtype=np.int64)
+    dst[0::2], dst[1::2] = ev, eu
+    msg = [np.zeros(nu[dst[d]]) for d in range(2 * E)]
+    residual = np.zeros(sweeps)
+    with np.errstate(invalid="ignore"):
+        for t in range(sweeps):
+            new, r = [], 0.0
+            for d in range(2 * E):
+                a, b = int(src[d]), int(dst[d])
+                h = theta[a].copy()
+                for q in inc[a]:                                             # ascending neighbour
+                    if src[q] != b:
+                        h = h + msg[q]
+                cd = c[d // 2] if d % 2 == 0 else c[d // 2].T
+                u = np.full(nu[b], -np.inf)
+                for i in range(nu[a]):                                       # i ascending, strict >
+                    cand = h[i] - cd[i]
+                    u = np.where(cand > u, cand, u)
+                m = u - _first_above(u)[1]
+                if damping != 0.0:
+                    m = (1.0 - damping) * m + damping * msg[d]
+                r = _nan_max(r, np.abs(m - msg[d]).max())
+                new.append(m)
+            msg = new
+            residual[t] = r
+        max_marginal = np.full((S, n), -np.inf)
+        for s in range(S):
+            b = theta[s].copy()
+            for q in inc[s]:
+                b = b + msg[q]
+            max_marginal[s, :nu[s]] = b - _first_above(b)[1]
+        level, level_ptr, level_node = decode_levels(eu, ev, S)
+        decoded = np.zeros(S, dtype=np.int32)
+        for l in range(level_ptr.size - 1):
+            picks = []
+            for s in level_node[level_ptr[l]:level_ptr[l + 1]]:
+                v = theta[s].copy()
+                for d in inc[s]:
+                    q = src[d]
+                    v = v - _cost_to(c, int(d), decoded[q]) if level[q] < level[s] else v + msg[d]
+                picks.append(_first_above(v)[0])
+            decoded[level_node[level_ptr[l]:level_ptr[l + 1]]] = picks
+        X = decoded[None, :].copy() if given is None else np.concatenate([decoded[None, :], given])
+        moves = np.stack([_refine_rule(X[r], theta, c, eu, ev, refine) for r in range(X.shape[0])])
+    ls = _host_log_score(X, score, g, d2, eu, ev)
+    chosen = _first_above(ls)[0]
+    return dict(state=X[chosen].copy(), log_score=ls[chosen], max_marginal=max_marginal, residual=residual, decoded_state=decoded, candidate_state=X,
+                candidate_log_score=ls, chosen=chosen, refine_moves=moves)
+
+
+def _graph_on_device(eu, ev, nu, g, d2, score, dev):
+    """The tensors the graph entries share: eu, ev, n_used (int32), g, d2, score (zeros without one) and the CSR of incoming edges."""
+    S, n = nu.size, d2.shape[1]
+    in_ptr, in_edge = incoming(eu, ev, S)
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev) if not torch.is_tensor(g) else g.to(dev, torch.float64).reshape(-1).contiguous()
+    t_eu, t_ev, t_nu = (torch.as_tensor(a.astype(np.int32)).to(dev) for a in (eu, ev, nu))
+    t_score = torch.zeros((S, n), dtype=torch.float64, device=dev) if score is None else score.contiguous()
+    return t_eu, t_ev, t_nu, t_score, t_g, d2.contiguous(), torch.as_tensor(in_ptr).to(dev), torch.as_tensor(in_edge).to(dev)
+
+
+def _refine_on_device(X, graph, eu, ev, sweeps):
+    """gbp_section_graph_refine on the sections ``X`` int32 [C, S] (device, contiguous), in place; returns the moves int32 [C, sweeps]."""
+    t_eu, t_ev, t_nu, t_score, t_g, d2, t_ptr, t_edge = graph
+    C, S = X.shape
+    moves = torch.zeros((C, sweeps), dtype=torch.int32, device=X.device)
+    if S == 0 or sweeps == 0:
+        return moves
+    colour_ptr, colour_node = _colour_lists(eu, ev, S)
+    _lib.call("gbp_section_graph_refine", X.device, S, t_eu.numel(), d2.shape[1], C, t_eu, t_ev, t_nu, t_score, t_g, d2, t_ptr, t_edge, colour_ptr.size - 1,
+              np.ctypeslib.as_ctypes(colour_ptr), torch.as_tensor(colour_node).to(X.device), sweeps, X, moves)
+    return moves
+
+
+def _check_path_device(d2, score, module_what, entry):
+    if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
+        raise TypeError("sections.%s: d2 and score are float64" % module_what)
+    on_device((d2,) + (() if score is None else (score,)), "sections", module_what, entry)
+
+
+def refine(state, d2, g, eu, ev, n_used, score=None, sweeps=16):
+    """Coordinate ascent on the exact log score on the device (gbp_section_graph_refine: csrc/gbp_section_graph_path.h
+    k_graph_condition; ``refine_reference`` states the rule): the sections ``state`` int [S] or [R, S] (host or device; R <= 65537)
+    on the graph ``d2`` f64 [E, n, n] on the device, ``g``, ``eu``, ``ev``, ``n_used``, ``score`` as ``propagate`` takes them, move
+    sounding by sounding to their best state given their neighbours until a sweep moves nothing or ``sweeps`` sweeps are done.  What
+    comes back is a local mode of the joint: it polishes a decode, and takes Gibbs draws of ``graph_draw`` to the modes they sit under.
+    Returns on the device ``state`` int32 (the shape given), ``refine_moves`` int32 [R, sweeps] ([sweeps] for one section) and
+    ``log_score`` f64 [R] (0-d for one section).  There is no host fallback."""
+    entry, what = "gbp_section_graph_refine", "sections.refine"
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "refine", entry)
+    eu, ev, nu, _, _ = _check_graph(eu, ev, g, d2, n_used, score, 1, 0.0, what)
+    sweeps = check_int(sweeps, 0, MAX_REFINE, "%s: sweeps" % what)
+    X, single = _check_states(state, nu, MAX_CANDIDATES + 1, what, "state")
+    _check_path_device(d2, score, "refine", entry)
+    dev = d2.device
+    graph = _graph_on_device(eu, ev, nu, g, d2, score, dev)
+    X = torch.as_tensor(X).to(dev)
+    moves = _refine_on_device(X, graph, eu, ev, sweeps)
+    ls = graph_log_score(X, None if score is None else graph[3], graph[4], graph[5], graph[0], graph[1])
+    return dict(state=X[0] if single else X, refine_moves=moves[0] if single else moves, log_score=ls[0] if single else ls)
+
+
+def graph_path(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0, refine=16, candidates=None):
+    """The most probable section of the graph of ``propagate`` on the device (gbp_section_graph_path and gbp_section_graph_refine:
+    csrc/gbp_section_graph_path.h; ``graph_path_reference`` states the rule, and the device has its bits): ``d2`` f64 [E, n, n] on the
+    device, n <= 256; ``g``, ``eu``, ``ev``, ``n_used``, ``n_soundings``, ``score``, ``sweeps`` and ``damping`` as ``propagate`` takes
+    them -- max-sum sweeps in place of sum-product ones, on d2 itself: no buffer of its size is made.  The decode is refined by up to
+    ``refine`` sweeps of coordinate ascent, and so is every row of ``candidates`` (int [C, S], host or device; None: none); the
+    refined section of the highest ``graph_log_score`` is returned.  Exact on a forest once the sweeps reach its diameter
+    (``residual`` is then 0.0); on loops a documented approximation, never below any candidate given.
+
+    Returns on the device ``state`` int32 [S], ``log_score`` f64 (0-d), ``max_marginal`` f64 [S, n] (-inf for the states >= n_used),
+    ``residual`` f64 [sweeps], ``decoded_state`` int32 [S], ``candidate_state`` int32 [C + 1, S], ``candidate_log_score`` f64 [C + 1],
+    ``refine_moves`` int32 [C + 1, refine], and ``chosen``, an integer.  The levels of the decode and the colours of the refinement are
+    made once on the host; the decode takes one launch per breadth-first level."""
+    entry, what = "gbp_section_graph_path", "sections.graph_path"
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "graph_path", entry)
+    S = check_int(n_soundings, 0, 2 ** 31 - 1, "%s: n_soundings" % what)
+    if np.size(host(n_used)) != S:
+        raise ValueError("%s: n_used must hold one integer per sounding (%d)" % (what, S))
+    eu, ev, nu, sweeps, damping = _check_graph(eu, ev, g, d2, n_used, score, sweeps, damping, what)
+    refine = check_int(refine, 0, MAX_REFINE, "%s: refine" % what)
+    given = None if candidates is None else _check_states(candidates, nu, MAX_CANDIDATES, what, "candidates")[0]
+    _check_path_device(d2, score, "graph_path", entry)
+    dev = d2.device
+    E, n = d2.shape[0], d2.shape[1]
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    max_marginal, residual, decoded = torch.empty((S, n), **f64), torch.zeros(sweeps, **f64), torch.zeros(S, **i32)
+    graph = _graph_on_device(eu, ev, nu, g, d2, score, dev)
+    t_eu, t_ev, t_nu, t_score, t_g, d2, t_ptr, t_edge = graph
+    if S:
+        level, level_ptr, level_node = decode_levels(eu, ev, S)
+        nu_buf, resid = torch.empty((2, 2 * E, n), **f64), torch.empty((sweeps, 2 * E), **f64)
+        _lib.call(entry, dev, S, E, n, t_eu, t_ev, t_nu, t_score, t_g, d2, t_ptr, t_edge, sweeps, damping, level_ptr.size - 1,
+                  np.ctypeslib.as_ctypes(level_ptr), torch.as_tensor(level_node).to(dev), torch.as_tensor(level).to(dev), nu_buf, resid, max_marginal,
+                  decoded, residual)
+    X = decoded[None, :].clone() if given is None else torch.cat([decoded[None, :], torch.as_tensor(given).to(dev)]).contiguous()
+    moves = _refine_on_device(X, graph, eu, ev, refine)
+    ls = graph_log_score(X, None if score is None else t_score, t_g, d2, t_eu, t_ev)
+    chosen = _first_above(ls.cpu().numpy())[0]
+    return dict(state=X[chosen].clone(), log_score=ls[chosen].clone(), max_marginal=max_marginal, residual=residual, decoded_state=decoded, candidate_state=X,
+                candidate_log_score=ls, chosen=chosen, refine_moves=moves)
+
+
+def check_path(path, what):
+    """``path`` of ``spatial`` as the keywords of ``graph_path``: None, True or a dictionary with ``sweeps``, ``damping``, ``refine``."""
+    if path is None or path is False:
+        return None
+    if path is True:
+        path = {}
+    if not isinstance(path, dict) or not set(path) <= set(PATH_KEYS):
+        raise ValueError("%s: path is None, True or a dictionary with %s" % (what, ", ".join(PATH_KEYS)))
+    return dict(sweeps=check_int(path.get("sweeps", 32), 1, MAX_SWEEPS, "%s: path sweeps" % what), damping=_check_damping(path.get("damping", 0.0), what),
+                refine=check_int(path.get("refine", 16), 0, MAX_REFINE, "%s: path refine" % what))
+
+
 def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=64, *, max_distance, tau=0.1, length=100.0, min_distance=1.0,
-            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None, draws=None, seed=0, draw_sweeps=8, bodies=None, boreholes=None):
+            score=None, sweeps=32, damping=0.0, budget_bytes=4 << 30, products=None, draws=None, seed=0, draw_sweeps=8, bodies=None, boreholes=None,
+            path=None):
     """One kept model per sounding, and a weight for every kept model, from the whole survey at once: the chain of
     ``sections`` along every sequence of ``ptr`` plus edges to the nearest sounding of every other sequence within ``max_distance``
     (required; about 1.5 line spacings), solved by ``sweeps`` synchronous sweeps of sum-product message passing with ``damping``.
@@ -1426,8 +1791,18 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
 
     ``boreholes`` = dict(logs=, max_distance=, ...) as in ``sections`` (its ``max_distance`` is the reach of a log, not the one of the
     graph): the borehole score is added to ``score`` before the message passing and the draws, and the ``borehole_*`` outputs of
-    ``sections`` are added, ``borehole_log_predictive`` under the beliefs.  With None every other output keeps its bits."""
+    ``sections`` are added, ``borehole_log_predictive`` under the beliefs.  With None every other output keeps its bits.
+
+    ``path`` = True or dict(sweeps=, damping=, refine=) adds the most probable section of the whole graph (``graph_path``; DESIGN.md
+    3.32) -- ``state`` is the first maximum of every sounding's belief taken alone, and neighbouring picks need not go together:
+    ``path_state`` / ``path_slot`` int32 [S] (-1: no models), ``path_k`` / ``path_edges`` / ``path_sigma`` (bit copies of the chosen
+    slots), ``path_log_score`` and ``state_log_score`` (``graph_log_score`` of the path and of ``state``, to compare), ``path_margin``
+    f64 [S] (the gap between the two largest max-marginals: what forcing the sounding off its model costs at least; inf with one model,
+    NaN without), ``path_residual`` f64 [sweeps of the path], ``path_candidate_log_score`` and ``path_chosen`` (the refined candidates:
+    the decode, ``state`` and, with ``draws``, the best-scoring draw; the path is never less probable than any of them) and
+    ``path_edge_distance`` f64 [E].  With None every other output keeps its bits."""
     z0, z1, _ = check_window(z0, z1, measure)
+    path = check_path(path, "sections.spatial")
     if boreholes is not None:
         boreholes = _bh.check_options(boreholes, "sections.spatial")
     if products is not None:
@@ -1501,6 +1876,26 @@ def spatial(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_mod
         out.update(draw_state=draw_state, draw_slot=torch.where(draw_state >= 0, dslot, torch.full_like(dslot, -1)).to(torch.int32),
                    draw_log_score=drawn["log_score_trace"][-1].clone(), draw_share=torch.where(has[:, None], share, torch.full((), nan, **f64)),
                    draw_change_share=drawn["change_share"])
+    if path is not None:
+        l_score, l_u, l_v = None if score is None else score[idx], torch.as_tensor(local[eu]).to(dev), torch.as_tensor(local[ev]).to(dev)
+        t_g = torch.as_tensor(g).to(dev)
+        given = [res["state"]]                                                 # today's section, and the best realisation drawn
+        if R is not None:
+            given.append(drawn["draw_state"][int(torch.argmax(drawn["log_score_trace"][-1]))])
+        found = graph_path(d2, g, local[eu], local[ev], nu[keep], keep.size, score=l_score, candidates=torch.stack(given), **path)
+        path_state = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        path_state[idx] = found["state"]
+        models = _chosen_models(k, edges, sigma, rows, n_used, path_state)
+        two = torch.topk(found["max_marginal"], min(2, n), dim=1).values
+        margin = torch.full((S,), nan, **f64)
+        margin[idx] = two[:, 0] - two[:, 1] if n > 1 else torch.full((keep.size,), float("inf"), **f64)
+        ps = path_state.long()
+        out.update(path_state=path_state, path_slot=models["slot"], path_k=models["section_k"], path_edges=models["section_edges"],
+                   path_sigma=models["section_sigma"], path_log_score=found["log_score"],
+                   state_log_score=graph_log_score(res["state"][None, :], l_score, t_g, d2, l_u, l_v)[0], path_margin=margin,
+                   path_residual=found["residual"], path_candidate_log_score=found["candidate_log_score"],
+                   path_chosen=torch.tensor(found["chosen"], dtype=torch.int32, device=dev),
+                   path_edge_distance=torch.sqrt(d2[torch.arange(E, device=dev), ps[t_u], ps[t_v]]))
     if boreholes is not None:
         out.update(_bh.section_outputs(b_att, b_score, b_part, b_skipped, weight, n_used))
     if products is not None:
@@ -1632,6 +2027,10 @@ def _parser():
                    help="with --spatial: joint realisations of the whole survey to draw, 1 .. 65536 (uses --seed); adds draw_state, draw_slot, "
                         "draw_log_score, draw_share and draw_change_share")
     p.add_argument("--draw-sweeps", type=int, default=None, metavar="T", help="with --spatial-draws: Gibbs sweeps over the lines (default 8)")
+    p.add_argument("--path", type=int, nargs="?", const=True, default=None, metavar="SWEEPS",
+                   help="with --spatial: the most probable section of the whole graph by SWEEPS sweeps of max-sum message passing (default 32), "
+                        "refined by coordinate ascent; adds path_state, path_slot, path_k, path_edges, path_sigma, path_log_score, state_log_score, "
+                        "path_margin, path_residual, path_candidate_log_score, path_chosen and path_edge_distance")
     p.add_argument("--bodies", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                    help="with --depth-axis and --draws (or --spatial-draws): the connected bodies of the realisations' cells with LO <= log10 S/m "
                         "<= HI (a bound far outside, such as -99 or 99: none); adds body_count, body_largest_measure, body_member_measure and body_largest_share")
@@ -1715,8 +2114,8 @@ def parse_args(argv=None):
             except ValueError as e:
                 p.error(str(e))
     if a.spatial is None:
-        if a.sweeps is not None or a.damping is not None or a.spatial_draws is not None:
-            p.error("--sweeps, --damping and --spatial-draws need --spatial")
+        if a.sweeps is not None or a.damping is not None or a.spatial_draws is not None or a.path is not None:
+            p.error("--sweeps, --damping, --spatial-draws and --path need --spatial")
         if a.draw_sweeps is not None:
             p.error("--draw-sweeps needs --spatial-draws")
     else:
@@ -1735,9 +2134,13 @@ def parse_args(argv=None):
                 check_int(a.sweeps, 1, MAX_SWEEPS, "--sweeps")
             if a.damping is not None:
                 _check_damping(a.damping, "--damping")
+            if a.path is not None and a.path is not True:
+                check_int(a.path, 1, MAX_SWEEPS, "--path")
         except ValueError as e:
             p.error(str(e))
         del kw["marginals"]
+        if a.path is not None:
+            kw["path"] = True if a.path is True else dict(sweeps=a.path)
         kw.update(max_distance=a.spatial, **({} if a.sweeps is None else dict(sweeps=a.sweeps)), **({} if a.damping is None else dict(damping=a.damping)))
         if a.spatial_draws is not None:
             kw.update(draws=a.spatial_draws, seed=a.seed, **({} if a.draw_sweeps is None else dict(draw_sweeps=a.draw_sweeps)))

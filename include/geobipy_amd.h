@@ -1129,6 +1129,54 @@ gbp_status gbp_section_graph_draw(int S, int E, int n, int L, const int64_t *ptr
                                   uint64_t seed, int n_draws, int first_draw, int first_sweep, int last_sweep, double *w,
                                   double *filtered, double *scale, int32_t *draw_state, void *stream);
 
+/* The most probable section of the graph of gbp_section_propagate: synchronous max-sum message passing, max-marginals and a decode
+ * by conditioning level by level (csrc/gbp_section_graph_path.h k_graph_maxsum, k_graph_maxmarginal, k_graph_condition; DESIGN.md
+ * 3.32; the rule is stated in numpy as sections.graph_path_reference).  S, E, n, eu, ev, n_used, score, g, d2, in_ptr, in_edge, sweeps
+ * and damping as there: DEVICE arrays, none read on the host.  Everything is in the log domain: theta_s = score[s], c_e[i, j] =
+ * g[e] * d2[e, i, j] (one multiply), a message nu[d] has m_dst entries and starts at 0.0.
+ *   A sweep computes every message from the last sweep's: for a -> b, h[i] = theta_a[i] plus the messages into a from all neighbours
+ *   but b, ascending neighbour; u[j] = the maximum over i < m_a of h[i] - c[i, j], from -inf and replaced on strict > (a NaN candidate
+ *   never wins); top = the maximum of u by the same loop; nu' = u - top; with damping != 0 nu' = (1 - damping) nu' + damping nu_old.
+ *   A message without a candidate above -inf is NaN.  residual f64 [sweeps]: the largest |nu' - nu_old| of the sweep (NaN if a
+ *   message is NaN; 0.0 without edges).
+ *   max_marginal f64 [S, n] = theta_s plus all incoming messages (ascending neighbour), minus its maximum; -inf for the states >= m_s.
+ *   level int32 [S]: the breadth-first level of every sounding; level_node int32 [S]: the soundings sorted by level; level_ptr int32
+ *   [n_levels + 1], a HOST array: the levels' ranges of level_node (sections.decode_levels).  The levels are decided in ascending
+ *   order, one launch each: decoded_state[s] = the first maximum over i < m_s of theta_s[i] plus, per neighbour q ascending,
+ *   -c at (x_q, i) if level[q] < level[s], else nu[q -> s][i].
+ * There is no exp and no reordered sum: the outputs have the rule's bits, and a call repeats them.
+ * Workspaces the caller provides: nu f64 [2, 2 E, n] (it leaves the last sweep's messages in half sweeps & 1) and resid f64 [sweeps,
+ * 2 E].  One 256-thread workgroup per undirected edge and sweep (37 KiB of static LDS for n <= 64, 43 KiB above), one per sounding for
+ * the max-marginals and for the decode.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, E < 0 or > 2^30 - 1, n < 1 or n > 256, sweeps < 1, damping outside [0, 1), E > 0
+ * with S < 2, sizes out of range (S + 2 E, E * n * n, sweeps * 2 E), with S > 0 n_levels outside 1 .. S, a NULL n_used / score /
+ * in_ptr / level_ptr / level_node / level / max_marginal / decoded_state / residual or a level_ptr that does not start at 0, end at S
+ * or that decreases, with E > 0 a NULL eu / ev / g / d2 / in_edge / nu / resid.  S == 0 launches nothing.  An index that does not
+ * fit is skipped on the device, never followed; a neighbour's state is clamped into its prefix. */
+gbp_status gbp_section_graph_path(int S, int E, int n, const int32_t *eu, const int32_t *ev, const int32_t *n_used, const double *score,
+                                  const double *g, const double *d2, const int32_t *in_ptr, const int32_t *in_edge, int sweeps,
+                                  double damping, int n_levels, const int32_t *level_ptr, const int32_t *level_node,
+                                  const int32_t *level, double *nu, double *resid, double *max_marginal, int32_t *decoded_state,
+                                  double *residual, void *stream);
+
+/* Coordinate ascent on the exact score sum_s score[s, x_s] - sum_e g[e] d2[e, x_u, x_v] of C sections of the same graph
+ * (csrc/gbp_section_graph_path.h k_graph_condition; sections.refine_reference states the rule).  state int32 [C, S]
+ * holds the sections (every state < m_s) and is replaced in place.  colour_node int32 [S]: the soundings sorted by colour, soundings
+ * of one colour sharing no edge; colour_ptr int32 [n_colours + 1], a HOST array: the colours' ranges (sections.sounding_colours).
+ * A sweep takes the colours in ascending order, one launch each, the soundings of a colour together: v[i] = theta_s[i] minus, per
+ * neighbour q ascending, c at (x_q, i); the sounding moves to the first maximum of v over i < m_s only if v there is strictly greater
+ * than v at its state, so every move raises the score.  moves int32 [C, refine]: the moves of every section in every sweep, counted
+ * by one integer atomic per workgroup (exact in any order); all `refine` sweeps are launched, and a section that has stopped moving
+ * counts 0 from then on.  A call repeats its bits.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, E < 0 or > 2^30 - 1, n < 1 or n > 256, C outside 1 .. 65537, refine outside
+ * 0 .. 65536, E > 0 with S < 2, sizes out of range (S + 2 E, E * n * n, C * S), with S > 0 n_colours outside 1 .. S, a NULL n_used /
+ * score / in_ptr / colour_ptr / colour_node / state, a NULL moves with refine > 0, or a colour_ptr that does not start at 0, end at S
+ * or that decreases, with E > 0 a NULL eu / ev / g / d2 / in_edge.  S == 0 or refine == 0 launches nothing. */
+gbp_status gbp_section_graph_refine(int S, int E, int n, int C, const int32_t *eu, const int32_t *ev, const int32_t *n_used,
+                                    const double *score, const double *g, const double *d2, const int32_t *in_ptr,
+                                    const int32_t *in_edge, int n_colours, const int32_t *colour_ptr, const int32_t *colour_node,
+                                    int refine, int32_t *state, int32_t *moves, void *stream);
+
 /* Connected bodies of R realisations of a raster (csrc/gbp_bodies.h k_bodies_label; the rule is stated in numpy as
  * bodies.label_reference).  raster f64 [R, S, C]: S soundings, C cells each (depth or ONE elevation axis).  A cell is a member iff
  * lo <= v <= hi in fp64 (a NaN never is; +-inf bounds give one-sided thresholds).  Cells (s, c) and (s, c + 1) are adjacent, and
