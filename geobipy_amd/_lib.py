@@ -190,6 +190,12 @@ SIGNATURES = {
     "gbp_section_graph_path": (c_int, [c_int, c_int, c_int] + [c_void_p] * 8 + [c_int, ctypes.c_double, c_int, c_int32_p] + [c_void_p] * 7 + [c_void_p]),
     "gbp_section_graph_refine": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 8 + [c_int, c_int32_p, c_void_p, c_int, c_void_p, c_void_p]
                                          + [c_void_p]),
+    "gbp_horizon_graph_propagate": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 7 + [c_int, ctypes.c_double]
+                                            + [c_void_p] * 6 + [c_void_p]),
+    "gbp_horizon_graph_path": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 7
+                                       + [c_int, ctypes.c_double, c_int, c_int32_p] + [c_void_p] * 7 + [c_void_p]),
+    "gbp_horizon_graph_refine": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int] + [c_void_p] * 7
+                                         + [c_int, c_int32_p, c_void_p, c_int, c_void_p, c_void_p] + [c_void_p]),
     "gbp_bodies_label": (c_int, [c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                  ctypes.c_double] + [c_void_p] * 4 + [c_void_p]),
     "gbp_borehole_score": (c_int, [c_int, c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int]

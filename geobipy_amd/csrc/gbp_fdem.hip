@@ -2758,6 +2758,221 @@ extern "C" gbp_status gbp_section_graph_refine(int S, int E, int n, int C, const
     return GBP_OK;
 }
 
+#include "gbp_horizon_graph.h"
+
+// Horizons across lines (gbp_horizon_graph.h): the sweeps of both semirings, one launch each with one workgroup per undirected edge.
+namespace {
+
+template <bool SUM, int NJ, bool SPLIT>
+gbp_status hgraph_sweep_launch(int N, int E, int S, int has_absent, double dz, double sw, const int32_t* eu, const int32_t* ev,
+                               const double* node, const double* g, const double* d, const int32_t* in_ptr, const int32_t* in_edge,
+                               const double* from, double* to, double damping, double* resid, hipStream_t st)
+{
+    const size_t lds = horizon_graph::sweep_lds_bytes(S);
+    if (lds > 48 * 1024) {                                                  // (above the default limit of a launch's dynamic LDS)
+        (void)hipFuncSetAttribute((const void*)horizon_graph::k_hgraph_sweep<SUM, false, NJ, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)horizon_graph::k_hgraph_sweep<SUM, true, NJ, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+    }
+    if (damping != 0.0)
+        hipLaunchKernelGGL((horizon_graph::k_hgraph_sweep<SUM, true, NJ, SPLIT>), dim3((unsigned)E), dim3(horizon_graph::THREADS), lds, st, N, E, S,
+                           has_absent, dz, sw, (const int*)eu, (const int*)ev, node, g, d, (const int*)in_ptr, (const int*)in_edge, from, to, damping,
+                           resid);
+    else
+        hipLaunchKernelGGL((horizon_graph::k_hgraph_sweep<SUM, false, NJ, SPLIT>), dim3((unsigned)E), dim3(horizon_graph::THREADS), lds, st, N, E, S,
+                           has_absent, dz, sw, (const int*)eu, (const int*)ev, node, g, d, (const int*)in_ptr, (const int*)in_edge, from, to, damping,
+                           resid);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+// Sweep t = 0 .. sweeps - 1 reads half t & 1 of msg [2, 2 E, SA] and writes the other one; resid [sweeps, 2 E].
+template <bool SUM>
+gbp_status hgraph_sweeps(int N, int E, int S, int has_absent, double dz, double sw, const int32_t* eu, const int32_t* ev, const double* node,
+                         const double* g, const double* d, const int32_t* in_ptr, const int32_t* in_edge, int sweeps, double damping,
+                         double* msg, double* resid, hipStream_t st)
+{
+    const int SA = S + has_absent;
+    const size_t half = (size_t)2 * E * SA;
+    for (int t = 0; t < sweeps; ++t) {
+        const double* from = msg + (size_t)(t & 1) * half;
+        double* to = msg + (size_t)((t + 1) & 1) * half;
+        double* r = resid + (size_t)t * 2 * E;
+        gbp_status rc;
+#define GBP_HGRAPH_CASE(nj) \
+    case nj: rc = hgraph_sweep_launch<SUM, nj, false>(N, E, S, has_absent, dz, sw, eu, ev, node, g, d, in_ptr, in_edge, from, to, damping, r, st); break
+        if (SA <= horizon_graph::SPLIT_STATES) {
+            rc = hgraph_sweep_launch<SUM, 1, true>(N, E, S, has_absent, dz, sw, eu, ev, node, g, d, in_ptr, in_edge, from, to, damping, r, st);
+        } else {
+            switch ((SA + horizon_graph::THREADS - 1) / horizon_graph::THREADS) {
+                GBP_HGRAPH_CASE(1);
+                GBP_HGRAPH_CASE(2);
+                GBP_HGRAPH_CASE(3);
+                GBP_HGRAPH_CASE(4);
+                GBP_HGRAPH_CASE(5);
+                GBP_HGRAPH_CASE(6);
+                GBP_HGRAPH_CASE(7);
+                GBP_HGRAPH_CASE(8);
+                default:
+                    rc = hgraph_sweep_launch<SUM, horizon_graph::MAX_OWNED, false>(N, E, S, has_absent, dz, sw, eu, ev, node, g, d, in_ptr, in_edge, from,
+                                                                                   to, damping, r, st);
+            }
+        }
+#undef GBP_HGRAPH_CASE
+        if (rc != GBP_OK) return rc;
+    }
+    return GBP_OK;
+}
+
+// The refusals the three entries share, without the entry's name (hgraph_fail puts it in front); NULL when the arguments fit.
+const char* hgraph_refusal(int N, int E, int S, int has_absent, double dz, double sw)
+{
+    if (N < 0) return "N must be >= 0";
+    if (E < 0 || E > 0x3fffffff) return "E must lie in 0 .. 2^30 - 1";
+    if (S < 1 || S > horizon_graph::MAX_STATES) return "S must lie in 1 .. 2048 (the states live in LDS)";
+    if (has_absent != 0 && has_absent != 1) return "has_absent must be 0 or 1";
+    if (!(dz > 0.0) || !std::isfinite(dz)) return "dz must be positive and finite";
+    if (!(sw >= 0.0) || !std::isfinite(sw)) return "switch must be >= 0 and finite";
+    if (E > 0 && N < 2) return "an edge needs two soundings";
+    if ((long long)N + 2LL * E > 0x7fffffffLL) return "N + 2 E out of range";
+    return nullptr;
+}
+
+gbp_status hgraph_fail(const char* entry, const char* why)
+{
+    char text[256];
+    std::snprintf(text, sizeof text, "%s: %s", entry, why);
+    return fail(GBP_ERR_INVALID_ARG, "%s", text);
+}
+
+}  // namespace
+
+// Beliefs of a horizon on the survey graph: w and the first messages, one launch per sweep, the residuals of all sweeps in one launch,
+// the beliefs.  Every refusal comes before any launch; no device array is read on the host.
+extern "C" gbp_status gbp_horizon_graph_propagate(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t* eu,
+                                                  const int32_t* ev, const double* score, const double* g, const double* d,
+                                                  const int32_t* in_ptr, const int32_t* in_edge, int sweeps, double damping, double* w,
+                                                  double* mu, double* resid, double* belief, int32_t* state, double* residual, void* stream)
+{
+    static const char* const entry = "gbp_horizon_graph_propagate";
+    if (const char* why = hgraph_refusal(N, E, S, has_absent, dz, switch_cost)) return hgraph_fail(entry, why);
+    const int SA = S + has_absent;
+    if (sweeps < 1) return hgraph_fail(entry, "sweeps must be >= 1");
+    if (!(damping >= 0.0 && damping < 1.0)) return hgraph_fail(entry, "damping must lie in [0, 1)");
+    if ((long long)N > 0x7fffffffffffffffLL / 8 / SA) return hgraph_fail(entry, "N * SA out of range");
+    if ((long long)E > 0x7fffffffffffffffLL / 32 / SA) return hgraph_fail(entry, "2 * 2 E * SA out of range");
+    if (E > 0 && (long long)sweeps > 0x7fffffffffffffffLL / 16 / E) return hgraph_fail(entry, "sweeps * 2 E out of range");
+    if (!residual) return hgraph_fail(entry, "residual is NULL");
+    if (N > 0 && (!score || !in_ptr || !w || !belief || !state)) return hgraph_fail(entry, "NULL pointer (score, in_ptr, w, belief, state)");
+    if (E > 0 && (!eu || !ev || !g || !d || !in_edge || !mu || !resid))
+        return hgraph_fail(entry, "NULL pointer (eu, ev, g, d, in_edge, mu, resid)");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(horizon_graph::THREADS);
+    const size_t half = (size_t)2 * E * SA;
+    if (N > 0) {
+        hipLaunchKernelGGL(horizon_graph::k_hgraph_init, dim3((unsigned)(N + 2 * E)), block, 0, st, N, SA, score, w, mu, mu ? mu + half : mu);
+        GBP_HIP(hipGetLastError());
+    }
+    if (E > 0) {
+        const gbp_status rc = hgraph_sweeps<true>(N, E, S, has_absent, dz, switch_cost, eu, ev, w, g, d, in_ptr, in_edge, sweeps, damping, mu, resid, st);
+        if (rc != GBP_OK) return rc;
+    }
+    hipLaunchKernelGGL(section::k_graph_residual, dim3((unsigned)sweeps), block, 0, st, 2LL * E, (const double*)resid, residual);
+    GBP_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(horizon_graph::k_hgraph_node<true>, dim3((unsigned)N), block, 0, st, E, SA, (const double*)w, (const int*)in_ptr,
+                           (const int*)in_edge, (const double*)(mu ? mu + (size_t)(sweeps & 1) * half : mu), belief, (int*)state);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
+// The most probable horizon: the messages start at 0.0, one launch per sweep, the residuals, the max-marginals, then the decode with one
+// launch per breadth-first level.  Every refusal comes before any launch; level_ptr is a host array, no device array is read on the host.
+extern "C" gbp_status gbp_horizon_graph_path(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t* eu,
+                                             const int32_t* ev, const double* score, const double* g, const double* d,
+                                             const int32_t* in_ptr, const int32_t* in_edge, int sweeps, double damping, int n_levels,
+                                             const int32_t* level_ptr, const int32_t* level_node, const int32_t* level, double* nu,
+                                             double* resid, double* max_marginal, int32_t* decoded_state, double* residual, void* stream)
+{
+    static const char* const entry = "gbp_horizon_graph_path";
+    if (const char* why = hgraph_refusal(N, E, S, has_absent, dz, switch_cost)) return hgraph_fail(entry, why);
+    const int SA = S + has_absent;
+    if (sweeps < 1) return hgraph_fail(entry, "sweeps must be >= 1");
+    if (!(damping >= 0.0 && damping < 1.0)) return hgraph_fail(entry, "damping must lie in [0, 1)");
+    if ((long long)N > 0x7fffffffffffffffLL / 8 / SA) return hgraph_fail(entry, "N * SA out of range");
+    if ((long long)E > 0x7fffffffffffffffLL / 32 / SA) return hgraph_fail(entry, "2 * 2 E * SA out of range");
+    if (E > 0 && (long long)sweeps > 0x7fffffffffffffffLL / 16 / E) return hgraph_fail(entry, "sweeps * 2 E out of range");
+    if (N > 0 && (n_levels < 1 || n_levels > N)) return hgraph_fail(entry, "n_levels must lie in 1 .. N");
+    if (N > 0 && (!score || !in_ptr || !level_ptr || !level_node || !level))
+        return hgraph_fail(entry, "NULL pointer (score, in_ptr, level_ptr, level_node, level)");
+    if (N > 0 && (!max_marginal || !decoded_state || !residual)) return hgraph_fail(entry, "NULL pointer (max_marginal, decoded_state, residual)");
+    if (E > 0 && (!eu || !ev || !g || !d || !in_edge || !nu || !resid))
+        return hgraph_fail(entry, "NULL pointer (eu, ev, g, d, in_edge, nu, resid)");
+    if (N == 0) return GBP_OK;
+    if (!graph_groups_fit(level_ptr, n_levels, N)) return hgraph_fail(entry, "level_ptr must start at 0, not decrease and end at N");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(horizon_graph::THREADS);
+    const size_t half = (size_t)2 * E * SA;
+    if (E > 0) {
+        GBP_HIP(hipMemsetAsync(nu, 0, 2 * half * sizeof(double), st));
+        const gbp_status rc = hgraph_sweeps<false>(N, E, S, has_absent, dz, switch_cost, eu, ev, score, g, d, in_ptr, in_edge, sweeps, damping, nu, resid, st);
+        if (rc != GBP_OK) return rc;
+    }
+    hipLaunchKernelGGL(section::k_graph_residual, dim3((unsigned)sweeps), block, 0, st, 2LL * E, (const double*)resid, residual);
+    GBP_HIP(hipGetLastError());
+    const double* last = nu ? nu + (size_t)(sweeps & 1) * half : nu;
+    hipLaunchKernelGGL(horizon_graph::k_hgraph_node<false>, dim3((unsigned)N), block, 0, st, E, SA, score, (const int*)in_ptr, (const int*)in_edge, last,
+                       max_marginal, (int*)nullptr);
+    GBP_HIP(hipGetLastError());
+    for (int l = 0; l < n_levels; ++l) {
+        const int count = level_ptr[l + 1] - level_ptr[l];
+        if (count == 0) continue;
+        hipLaunchKernelGGL(horizon_graph::k_hgraph_condition<false>, dim3((unsigned)count), block, 0, st, N, E, S, has_absent, dz, switch_cost,
+                           (const int*)eu, (const int*)ev, score, g, d, (const int*)in_ptr, (const int*)in_edge, last, (const int*)level,
+                           (const int*)level_node + level_ptr[l], count, (int*)decoded_state, (int*)nullptr, 0);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
+// Coordinate ascent on the exact score of C horizons: per sweep one launch per colour of soundings, a workgroup for every (candidate,
+// sounding of the colour).  All `refine` sweeps are launched; no counter is read on the host.  Every refusal comes before any launch.
+extern "C" gbp_status gbp_horizon_graph_refine(int N, int E, int S, int has_absent, double dz, double switch_cost, int C, const int32_t* eu,
+                                               const int32_t* ev, const double* score, const double* g, const double* d,
+                                               const int32_t* in_ptr, const int32_t* in_edge, int n_colours, const int32_t* colour_ptr,
+                                               const int32_t* colour_node, int refine, int32_t* state, int32_t* moves, void* stream)
+{
+    static const char* const entry = "gbp_horizon_graph_refine";
+    if (const char* why = hgraph_refusal(N, E, S, has_absent, dz, switch_cost)) return hgraph_fail(entry, why);
+    const int SA = S + has_absent;
+    if (C < 1 || C > section::MAX_DRAWS + 1) return hgraph_fail(entry, "C must lie in 1 .. 65537");
+    if (refine < 0 || refine > 65536) return hgraph_fail(entry, "refine must lie in 0 .. 65536");
+    if ((long long)N > 0x7fffffffffffffffLL / 8 / SA) return hgraph_fail(entry, "N * SA out of range");
+    if ((long long)C * N > 0x7fffffffLL) return hgraph_fail(entry, "C * N out of range");
+    if (N > 0 && (n_colours < 1 || n_colours > N)) return hgraph_fail(entry, "n_colours must lie in 1 .. N");
+    if (N > 0 && (!score || !in_ptr || !colour_ptr || !colour_node || !state))
+        return hgraph_fail(entry, "NULL pointer (score, in_ptr, colour_ptr, colour_node, state)");
+    if (N > 0 && refine > 0 && !moves) return hgraph_fail(entry, "moves is NULL");
+    if (E > 0 && (!eu || !ev || !g || !d || !in_edge)) return hgraph_fail(entry, "NULL pointer (eu, ev, g, d, in_edge)");
+    if (N == 0 || refine == 0) return GBP_OK;
+    if (!graph_groups_fit(colour_ptr, n_colours, N)) return hgraph_fail(entry, "colour_ptr must start at 0, not decrease and end at N");
+    hipStream_t st = (hipStream_t)stream;
+    GBP_HIP(hipMemsetAsync(moves, 0, (size_t)C * refine * sizeof(int32_t), st));
+    for (int t = 0; t < refine; ++t) {
+        for (int c = 0; c < n_colours; ++c) {
+            const int count = colour_ptr[c + 1] - colour_ptr[c];
+            if (count == 0) continue;
+            hipLaunchKernelGGL(horizon_graph::k_hgraph_condition<true>, dim3((unsigned)((long long)C * count)), dim3(horizon_graph::THREADS), 0, st, N, E,
+                               S, has_absent, dz, switch_cost, (const int*)eu, (const int*)ev, score, g, d, (const int*)in_ptr, (const int*)in_edge,
+                               (const double*)nullptr, (const int*)nullptr, (const int*)colour_node + colour_ptr[c], count, (int*)state,
+                               (int*)moves + t, refine);
+            GBP_HIP(hipGetLastError());
+        }
+    }
+    return GBP_OK;
+}
+
 #include "gbp_section_graph_draw.h"
 
 // Joint draws across lines (gbp_section_graph_draw.h): K unless the caller has it, the weights, then per sweep a filter launch and a draw

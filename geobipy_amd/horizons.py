@@ -22,10 +22,26 @@ T_n[k] = g[n] |d[n] - k dz| with k = c' - c, cell <-> absent costs ``switch``, a
   log_partition = sum_n ln s_n.
 
 A window of depth is applied by slicing the state axis, which is exact: the costs depend on differences of cell indices only.  There
-is no host fallback for ``track`` itself.  Left out on purpose: coupling across lines, non-uniform depth cells, several horizons
-tracked jointly with an ordering constraint, and learning ``slope`` (``log_partition`` is returned for whoever wants to scan it).
+is no host fallback for ``track`` itself.
+
+Across lines (csrc/gbp_horizon_graph.h; ``gbp_horizon_graph_propagate``, ``gbp_horizon_graph_path``,
+``gbp_horizon_graph_refine``).  Lines tracked alone give stripes: where a line's evidence is bimodal along its whole length the pick
+sits on the wrong branch for the entire line, and nothing inside that line can tell.  ``spatial`` puts the same states and the same
+pair term on the survey graph of ``sections.neighbours`` -- the steps along every line plus, across lines, every sounding's nearest
+sounding of every other line within ``max_distance`` -- with g[e] = 1 / (slope max(dist_e, min_distance)) and d[e] = surface[ev[e]] -
+surface[eu[e]] of the edge (``graph_steps``).  ``propagate_reference`` states the sum-product rule (beliefs) and
+``graph_path_reference`` the max-sum rule, its decode by conditioning level by level and its coordinate ascent (the most probable
+horizon surface) in numpy; ``propagate``, ``graph_path`` and ``refine`` run them on the device: the max-sum side has numpy's bits, the
+sum side the reference's own rounding.  On a line graph they are the chain's marginals and its Viterbi path; on a graph with loops
+they are an approximation (a belief is not a marginal), and the path is never less probable than any candidate it was given -- the
+lines tracked alone among them.
+
+Left out on purpose: joint draws of horizons, several horizons tracked jointly with an ordering constraint, learning ``slope``
+(``log_partition`` of ``track`` is returned for whoever wants to scan it), non-uniform depth cells, gridding the picks into a surface,
+and a place in ``survey.infer``.
 """
 import argparse
+import os
 
 import numpy as np
 import torch
@@ -321,7 +337,8 @@ def _finish(raw, S, lo, edges, surface, percentiles):
         for p in percentiles:
             i = percentile_cells(m[:, :S], p)
             out[percentile_name(p)] = torch.where(i < 0, nan, centres[(i + lo).clamp(min=0, max=centres.numel() - 1)])
-        out["log_partition"], out["scale"] = raw["log_partition"], raw["scale"]
+        if "log_partition" in raw:                                             # (a chain's; the survey graph has none)
+            out["log_partition"], out["scale"] = raw["log_partition"], raw["scale"]
     return out
 
 
@@ -479,6 +496,554 @@ def as_intervals(top, bottom):
     return {"kind": "horizons", "top": t, "bottom": b}
 
 
+# ---- across lines: the survey graph -----------------------------------------------------------------------------------
+
+MAX_SWEEPS = 65536
+MAX_REFINE = 65536
+MAX_CANDIDATES = 65536
+SURVEY_OUTPUT = "survey.horizons.npz"
+
+
+def graph_steps(x, y, surface, eu, ev, slope=0.05, min_distance=1.0):
+    """(g, d, dist) float64 [E] of the edges ``eu[e]`` < ``ev[e]`` between soundings at ``x``, ``y`` (m) on the ``surface`` elevation
+    (m): dist the horizontal distance, g[e] = 1 / (slope max(dist_e, min_distance)), d[e] = surface[ev[e]] - surface[eu[e]]: the
+    convention of ``steps``, applied to an edge of the survey graph."""
+    from . import sections
+    x, y, s = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y, surface))
+    if not (x.size == y.size == s.size):
+        raise ValueError("horizons.graph_steps: x, y and surface must have one entry per sounding")
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y)) and np.all(np.isfinite(s))):
+        raise ValueError("horizons.graph_steps: x, y and surface must be finite")
+    slope, min_distance = float(slope), float(min_distance)
+    if not (np.isfinite(slope) and slope > 0.0):
+        raise ValueError("horizons.graph_steps: slope must be positive")
+    if not (np.isfinite(min_distance) and min_distance > 0.0):
+        raise ValueError("horizons.graph_steps: min_distance must be positive")
+    eu, ev, _ = sections._check_edges(eu, ev, x.size, "horizons.graph_steps")
+    dist = np.hypot(x[ev] - x[eu], y[ev] - y[eu])
+    return 1.0 / (slope * np.maximum(dist, min_distance)), s[ev] - s[eu], dist
+
+
+def _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what):
+    """The checks the graph functions share, on shapes and host values alone (``score`` numpy or torch, any device); returns eu, ev
+    (numpy int64 [E]), g, d (numpy float64 [E]), dz and switch."""
+    from . import sections
+    if getattr(score, "ndim", 0) != 2 or not 1 <= score.shape[1] <= MAX_STATES:
+        raise ValueError("%s: score must be [N, S] with 1 <= S <= %d (choose a window with between=)" % (what, MAX_STATES))
+    N = score.shape[0]
+    if absent_score is not None and tuple(absent_score.shape) != (N,):
+        raise ValueError("%s: absent_score must hold one entry per sounding" % what)
+    eu, ev, _ = sections._check_edges(eu, ev, N, what)
+    g, d = np.asarray(_args.host(g), dtype=np.float64).reshape(-1), np.asarray(_args.host(d), dtype=np.float64).reshape(-1)
+    if g.size != eu.size or d.size != eu.size:
+        raise ValueError("%s: g and d must hold one entry per edge (%d)" % (what, eu.size))
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(d))):
+        raise ValueError("%s: g and d must be finite" % what)
+    dz, switch = float(dz), float(switch)
+    if not (np.isfinite(dz) and dz > 0.0):
+        raise ValueError("%s: dz must be positive" % what)
+    if not (np.isfinite(switch) and switch >= 0.0):
+        raise ValueError("%s: switch must be >= 0" % what)
+    return eu, ev, g, d, dz, switch
+
+
+def _check_sweeps(sweeps, damping, what):
+    from . import sections
+    return _args.check_int(sweeps, 1, MAX_SWEEPS, "%s: sweeps" % what), sections._check_damping(damping, what)
+
+
+def _theta_reference(score, absent_score, what):
+    """The node terms as numpy float64 [N, SA], the absent state's last; they must be finite, as in ``track_reference``."""
+    score = np.asarray(score, dtype=np.float64)
+    theta = score if absent_score is None else np.concatenate([score, np.asarray(absent_score, dtype=np.float64).reshape(-1, 1)], axis=1)
+    if not np.all(np.isfinite(theta)):
+        raise ValueError("%s: the scores must be finite" % what)
+    return theta
+
+
+def _check_states(state, N, SA, most, what, name):
+    """``state`` (host or device) as numpy int32 [R, N] with every entry in 0 .. SA - 1; also whether it came as one row [N]."""
+    x = _args.host(state)
+    single = x.ndim == 1
+    x = x[None, :] if single else x
+    if x.ndim != 2 or x.shape[1] != N or x.dtype.kind not in "iu" or not 1 <= x.shape[0] <= most:
+        raise ValueError("%s: %s must hold one integer per sounding, [N] or [R, N] with N = %d and 1 <= R <= %d" % (what, name, N, most))
+    if np.any(x < 0) or np.any(x >= SA):
+        raise ValueError("%s: every entry of %s must lie in 0 .. %d (the states; %d with the absent state)" % (what, name, SA - 1, SA))
+    return np.ascontiguousarray(x, dtype=np.int32), single
+
+
+def _edge_tables(g, d, dz, S):
+    """T_e[k + S - 1] = g[e] * |d[e] - k * dz|, k = -(S - 1) .. S - 1: the operations of ``track_reference``, in its order."""
+    kf = np.arange(-(S - 1), S).astype(g.dtype)
+    return [g[e] * np.abs(d[e] - kf * dz) for e in range(g.size)]
+
+
+def _slots(table, S, i, mirror):
+    """The table's entries for source cell i and every destination cell ascending: u -> v (``mirror`` False) reads slot
+    b + S - 1 - i for b ascending, v -> u slot i - a + S - 1 for a ascending."""
+    return table[i:i + S][::-1] if mirror else table[S - 1 - i:2 * S - 1 - i]
+
+
+def _cost_to(T, switch, S, SA, dd, x):
+    """The pair costs [SA] of the states of the sounding directed edge ``dd`` ends in, its source at state ``x``."""
+    c = np.empty(SA, dtype=T.dtype)
+    if x < S:
+        c[:S] = _slots(T, S, x, bool(dd & 1))
+        c[S:] = switch
+    else:
+        c[:S] = switch
+        c[S:] = 0.0
+    return c
+
+
+def propagate_reference(eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=32, damping=0.0, dtype=np.float64):
+    """The rule of ``propagate`` in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the yardstick of the
+    rule's own rounding): synchronous sum-product message passing with the structure of ``sections.propagate_reference`` on the graph
+    of N soundings with the undirected edges ``eu[e]`` < ``ev[e]`` (sorted by (eu, ev), no duplicates), ``g``, ``d`` [E]
+    (``graph_steps``), ``score`` [N, S] and optionally ``absent_score`` [N] (SA = S + 1 states, the absent one last).
+
+    w = exp(score); K_e = exp(-T_e) with T_e[k] = g[e] * |d[e] - k * dz|, k = b - a for cell a under eu[e] and cell b under ev[e];
+    ks = exp(-switch).  Directed edge 2 e is eu -> ev, 2 e + 1 is ev -> eu and reads the same table mirrored.  A message has SA entries
+    and starts at 1 / SA.  One sweep computes every message from the last sweep's.  For a -> b: h = w_a times the messages into a from
+    its neighbours c != b, ascending c; for a cell j u[j] = sum_i h[i] K over the source cells i ascending, u = u + h[i] * K[..], then
+    + h[S] * ks; for the absent state u[S] = the sequential sum of h[i] * ks over the cells, then + h[S]; tot = the sequential sum of u,
+    j ascending; mu' = u / tot; with ``damping`` = lam != 0 mu' = (1 - lam) mu' + lam mu_old.  ``residual[t]`` is the largest
+    |mu' - mu_old| of sweep t (NaN if a message is; 0.0 without edges).  belief_s = w_s times all incoming messages, divided by its
+    sequential sum; ``state[s]`` is its first maximum.  A zero tot gives NaN.
+
+    Exact on a forest once the sweeps reach its diameter (the residual is 0.0 from then on); on loops a belief, not a marginal.
+    Returns ``belief`` [N, SA] (``dtype``), ``state`` int32 [N] and ``residual`` [sweeps]."""
+    from . import sections
+    what = "horizons.propagate_reference"
+    ft = np.dtype(dtype).type
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, np.asarray(score), None if absent_score is None else np.asarray(absent_score), what)
+    sweeps, damping = _check_sweeps(sweeps, damping, what)
+    theta = _theta_reference(score, absent_score, what).astype(ft)
+    N, SA = theta.shape
+    S, E, has_absent = np.asarray(score).shape[1], eu.size, absent_score is not None
+    g, d, dz, switch, lam = g.astype(ft), d.astype(ft), ft(dz), ft(switch), ft(damping)
+    with np.errstate(under="ignore"):
+        w, ks = np.exp(theta), np.exp(-switch)
+        K = [np.exp(-T) for T in _edge_tables(g, d, dz, S)]
+    inc, src = sections._neighbour_lists(eu, ev, N)
+    dst = np.empty(2 * E, dtype=np.int64)
+    dst[0::2], dst[1::2] = ev, eu
+    msg = [np.full(SA, ft(1) / ft(SA), dtype=ft) for _ in range(2 * E)]
+    residual = np.zeros(sweeps, dtype=ft)
+    seq = lambda v: np.cumsum(v)[-1]                                          # noqa: E731  (sequential, ascending)
+    with np.errstate(invalid="ignore", divide="ignore", under="ignore"):
+        for t in range(sweeps):
+            new, r = [], ft(0)
+            for dd in range(2 * E):
+                a, b = int(src[dd]), int(dst[dd])
+                h = w[a].copy()
+                for q in inc[a]:                                             # ascending neighbour
+                    if src[q] != b:
+                        h = h * msg[q]
+                Kd, u = K[dd // 2], np.zeros(SA, dtype=ft)
+                for i in range(S):                                           # source cells ascending
+                    u[:S] = u[:S] + h[i] * _slots(Kd, S, i, bool(dd & 1))
+                if has_absent:
+                    u[:S] = u[:S] + h[S] * ks
+                    u[S] = seq(h[:S] * ks) + h[S]
+                m = u / seq(u)
+                if damping != 0.0:
+                    m = (ft(1) - lam) * m + lam * msg[dd]
+                r = sections._nan_max(r, np.abs(m - msg[dd]).max())
+                new.append(m)
+            msg = new
+            residual[t] = r
+        belief, state = np.zeros((N, SA), dtype=ft), np.zeros(N, dtype=np.int32)
+        for s in range(N):
+            h = w[s].copy()
+            for q in inc[s]:
+                h = h * msg[q]
+            belief[s] = h / seq(h)
+            state[s] = first_max(belief[s])
+    return dict(belief=belief, state=state, residual=residual)
+
+
+def _path_terms(eu, ev, g, d, dz, switch, score, absent_score, what):
+    """The checked arguments of the max-sum rules and their terms: theta [N, SA] and the tables T_e, in fp64."""
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, np.asarray(score), None if absent_score is None else np.asarray(absent_score), what)
+    theta = _theta_reference(score, absent_score, what)
+    S = np.asarray(score).shape[1]
+    return eu, ev, g, d, dz, switch, theta, S, _edge_tables(g, d, dz, S)
+
+
+def _refine_rule(X, theta, T, switch, S, eu, ev, sweeps):
+    """Coordinate ascent of one horizon ``X`` int32 [N], in place, with the move rule of ``sections.refine_reference``; returns the
+    moves of every sweep, int32 [sweeps]."""
+    from . import sections
+    N, SA = theta.shape
+    inc, src = sections._neighbour_lists(eu, ev, N)
+    colour, n_colours = sections.sounding_colours(eu, ev, N)
+    moves = np.zeros(sweeps, dtype=np.int32)
+    for t in range(sweeps):
+        for col in range(n_colours):
+            for s in np.flatnonzero(colour == col):                           # (they share no edge: together is one after the other)
+                v = theta[s].copy()
+                for dd in inc[s]:                                             # ascending neighbour
+                    v = v - _cost_to(T[dd >> 1], switch, S, SA, int(dd), int(X[src[dd]]))
+                i, top = sections._first_above(v)
+                if top > v[X[s]]:
+                    X[s] = i
+                    moves[t] += 1
+        if moves[t] == 0:
+            break
+    return moves
+
+
+def graph_log_score(state, eu, ev, g, d, dz, switch, score, absent_score=None):
+    """The exact log score of the horizons ``state`` int [N] or [R, N] (S: absent) on the graph: the node terms score[s, x_s]
+    (absent_score[s] for the absent state) summed over the soundings ascending, minus the pair costs summed over the edges ascending;
+    both sums sequential in fp64 on the host, so the rule and the device give the same bits.  ``score`` (and ``absent_score``) numpy
+    or torch on any device: only the [R, N] chosen node terms leave it.  Returns float64 numpy [R], or a number for one horizon."""
+    what = "horizons.graph_log_score"
+    if not torch.is_tensor(score):
+        score, absent_score = np.asarray(score, dtype=np.float64), None if absent_score is None else np.asarray(_args.host(absent_score), dtype=np.float64)
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what)
+    N, S = score.shape
+    x, single = _check_states(state, N, S + (absent_score is not None), MAX_CANDIDATES + 1, what, "state")
+    x = x.astype(np.int64)
+    if torch.is_tensor(score):
+        theta = score if absent_score is None else torch.cat([score, torch.as_tensor(absent_score).to(score.device, score.dtype).reshape(-1, 1)], dim=1)
+        xt = torch.as_tensor(x).to(score.device)
+        node = theta.to(torch.float64)[torch.arange(N, device=score.device)[None, :], xt].cpu().numpy()
+    else:
+        theta = np.asarray(score, dtype=np.float64)
+        if absent_score is not None:
+            theta = np.concatenate([theta, np.asarray(absent_score, dtype=np.float64).reshape(-1, 1)], axis=1)
+        node = theta[np.arange(N)[None, :], x]
+    xu, xv = x[:, eu], x[:, ev]
+    cost = np.where((xu < S) & (xv < S), g[None, :] * np.abs(d[None, :] - (xv - xu).astype(np.float64) * dz),
+                    np.where((xu >= S) & (xv >= S), 0.0, switch))
+    total = lambda v: np.cumsum(v, axis=1)[:, -1] if v.shape[1] else np.zeros(v.shape[0])      # noqa: E731  (sequential, ascending)
+    out = total(node) - total(cost)
+    return out[0] if single else out
+
+
+def refine_reference(state, eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=16):
+    """The rule of ``refine`` in numpy: coordinate ascent on ``graph_log_score`` of the horizons ``state`` int [N] or [R, N].
+    ``sections.sounding_colours`` colours the soundings; a sweep visits the colours in ascending order.  For sounding s,
+    v[i] = score[s, i] minus the pair cost to the state of every neighbour, ascending neighbour; s moves to the first maximum of v
+    (from -inf on strict >) only if v there is strictly greater than v[x_s].  A horizon stops after a sweep without a move.
+    Returns ``state`` int32 (the shape given), ``refine_moves`` int32 [R, sweeps] ([sweeps] for one) and ``log_score``."""
+    what = "horizons.refine_reference"
+    eu, ev, g, d, dz, switch, theta, S, T = _path_terms(eu, ev, g, d, dz, switch, score, absent_score, what)
+    sweeps = _args.check_int(sweeps, 0, MAX_REFINE, "%s: sweeps" % what)
+    X, single = _check_states(state, theta.shape[0], theta.shape[1], MAX_CANDIDATES + 1, what, "state")
+    X = X.copy()
+    moves = np.stack([_refine_rule(X[r], theta, T, switch, S, eu, ev, sweeps) for r in range(X.shape[0])])
+    ls = graph_log_score(X, eu, ev, g, d, dz, switch, score, absent_score)
+    return dict(state=X[0] if single else X, refine_moves=moves[0] if single else moves, log_score=ls[0] if single else ls)
+
+
+def graph_path_reference(eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=32, damping=0.0, refine=16, candidates=None):
+    """The rule of ``graph_path`` in numpy (fp64: what the device is held to, bit for bit): the most probable horizon of the graph of
+    ``propagate_reference`` -- the same arguments -- by synchronous max-sum message passing, a decode by conditioning and coordinate
+    ascent, with the structure of ``sections.graph_path_reference``.  Everything is in the log domain; there is no exp.
+
+    A message has SA entries and starts at 0.0.  For a -> b: h = score_a plus the messages into a from its neighbours c != b,
+    ascending c; for a cell j u[j] = the maximum of h[i] - T over the source cells i ascending, from -inf and replaced on strict >,
+    the candidate h[S] - switch last; for the absent state u[S] takes h[i] - switch for i ascending, then h[S]; nu' = u minus its first
+    maximum; damping and ``residual`` as in ``propagate_reference``.  ``max_marginal`` [N, SA] = score_s plus all incoming messages,
+    minus its maximum.  Decode: ``sections.decode_levels``; x_s = the first maximum of score_s[i] minus, per neighbour q ascending, the
+    pair cost at x_q if level(q) < level(s), else plus nu[q -> s][i].  The decode and every row of ``candidates`` (int [C, N], states
+    in 0 .. SA - 1) are refined by ``refine`` sweeps of ``refine_reference``; the first maximum of ``graph_log_score`` is kept.
+
+    Returns ``state`` int32 [N] (S: absent), ``log_score``, ``max_marginal`` [N, SA], ``residual`` [sweeps], ``decoded_state``,
+    ``candidate_state`` int32 [C + 1, N] (refined; row 0 from the decode), ``candidate_log_score`` [C + 1], ``chosen`` and
+    ``refine_moves`` int32 [C + 1, refine]."""
+    from . import sections
+    what = "horizons.graph_path_reference"
+    eu, ev, g, d, dz, switch, theta, S, T = _path_terms(eu, ev, g, d, dz, switch, score, absent_score, what)
+    sweeps, damping = _check_sweeps(sweeps, damping, what)
+    refine = _args.check_int(refine, 0, MAX_REFINE, "%s: refine" % what)
+    N, SA = theta.shape
+    E, has_absent = eu.size, SA > S
+    given = None if candidates is None else _check_states(candidates, N, SA, MAX_CANDIDATES, what, "candidates")[0]
+    inc, src = sections._neighbour_lists(eu, ev, N)
+    dst = np.empty(2 * E, dtype=np.int64)
+    dst[0::2], dst[1::2] = ev, eu
+    msg = [np.zeros(SA) for _ in range(2 * E)]
+    residual = np.zeros(sweeps)
+    with np.errstate(invalid="ignore"):
+        for t in range(sweeps):
+            new, r = [], 0.0
+            for dd in range(2 * E):
+                a, b = int(src[dd]), int(dst[dd])
+                h = theta[a].copy()
+                for q in inc[a]:                                             # ascending neighbour
+                    if src[q] != b:
+                        h = h + msg[q]
+                Td, u = T[dd // 2], np.full(SA, -np.inf)
+                for i in range(S):                                           # source cells ascending, strict >
+                    cand = h[i] - _slots(Td, S, i, bool(dd & 1))
+                    u[:S] = np.where(cand > u[:S], cand, u[:S])
+                if has_absent:
+                    via = h[S] - switch
+                    u[:S] = np.where(via > u[:S], via, u[:S])
+                    top = sections._first_above(h[:S] - switch)[1]
+                    u[S] = h[S] if h[S] > top else top
+                m = u - sections._first_above(u)[1]
+                if damping != 0.0:
+                    m = (1.0 - damping) * m + damping * msg[dd]
+                r = sections._nan_max(r, np.abs(m - msg[dd]).max())
+                new.append(m)
+            msg = new
+            residual[t] = r
+        max_marginal = np.empty((N, SA))
+        for s in range(N):
+            b = theta[s].copy()
+            for q in inc[s]:
+                b = b + msg[q]
+            max_marginal[s] = b - sections._first_above(b)[1]
+        level, level_ptr, level_node = sections.decode_levels(eu, ev, N)
+        decoded = np.zeros(N, dtype=np.int32)
+        for l in range(level_ptr.size - 1):
+            picks = []
+            for s in level_node[level_ptr[l]:level_ptr[l + 1]]:
+                v = theta[s].copy()
+                for dd in inc[s]:
+                    q = src[dd]
+                    v = v - _cost_to(T[dd >> 1], switch, S, SA, int(dd), int(decoded[q])) if level[q] < level[s] else v + msg[dd]
+                picks.append(sections._first_above(v)[0])
+            decoded[level_node[level_ptr[l]:level_ptr[l + 1]]] = picks
+        X = decoded[None, :].copy() if given is None else np.concatenate([decoded[None, :], given])
+        moves = np.stack([_refine_rule(X[r], theta, T, switch, S, eu, ev, refine) for r in range(X.shape[0])])
+    ls = graph_log_score(X, eu, ev, g, d, dz, switch, score, absent_score)
+    chosen = sections._first_above(ls)[0]
+    return dict(state=X[chosen].copy(), log_score=ls[chosen], max_marginal=max_marginal, residual=residual, decoded_state=decoded, candidate_state=X,
+                candidate_log_score=ls, chosen=chosen, refine_moves=moves)
+
+
+def _device_graph(eu, ev, g, d, score, absent_score, module_what, entry):
+    """The refusals of the device entries that come after the values (dtype, then the device last) and the tensors they share: theta
+    [N, SA] (the absent state's score last), eu, ev, g, d and the CSR of incoming edges."""
+    from . import sections
+    if score.dtype != torch.float64 or (absent_score is not None and absent_score.dtype != torch.float64):
+        raise TypeError("horizons.%s: score and absent_score are float64" % module_what)
+    _args.on_device((score,) + (() if absent_score is None else (absent_score,)), "horizons", module_what, entry)
+    dev = score.device
+    theta = score.contiguous() if absent_score is None else torch.cat([score, absent_score.to(dev).reshape(-1, 1)], dim=1).contiguous()
+    in_ptr, in_edge = sections.incoming(eu, ev, score.shape[0])
+    t_eu, t_ev = (torch.as_tensor(a.astype(np.int32)).to(dev) for a in (eu, ev))
+    return theta, t_eu, t_ev, torch.as_tensor(g).to(dev), torch.as_tensor(d).to(dev), torch.as_tensor(in_ptr).to(dev), torch.as_tensor(in_edge).to(dev)
+
+
+def _are_tensors(score, absent_score, module_what, entry):
+    _args.are_tensors((score,) + (() if absent_score is None else (absent_score,)), "horizons", module_what, entry)
+
+
+def propagate(eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=32, damping=0.0):
+    """Beliefs of the graph of ``propagate_reference`` on the device (gbp_horizon_graph_propagate: csrc/gbp_horizon_graph.h):
+    ``score`` f64 [N, S] and ``absent_score`` f64 [N] or None on the device, S <= 2048; ``eu`` < ``ev`` [E] (sorted by (eu, ev), no
+    duplicates), ``g``, ``d`` [E] (host or device; ``graph_steps``), ``dz`` > 0, ``switch`` >= 0, ``sweeps`` >= 1 synchronous sweeps
+    with ``damping`` in [0, 1).  Returns on the device ``belief`` f64 [N, SA] (the absent state last), ``state`` int32 [N] (the first
+    maximum of the belief; S: absent) and ``residual`` f64 [sweeps].  The two message buffers take 2 * 2 E * SA doubles.  There is no
+    host fallback."""
+    entry, what = "gbp_horizon_graph_propagate", "horizons.propagate"
+    _are_tensors(score, absent_score, "propagate", entry)
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what)
+    sweeps, damping = _check_sweeps(sweeps, damping, what)
+    theta, t_eu, t_ev, t_g, t_d, t_ptr, t_edge = _device_graph(eu, ev, g, d, score, absent_score, "propagate", entry)
+    dev, (N, SA), E = theta.device, theta.shape, eu.size
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(belief=torch.empty((N, SA), **f64), state=torch.empty(N, dtype=torch.int32, device=dev), residual=torch.zeros(sweeps, **f64))
+    if N == 0:
+        return out
+    w, mu, resid = torch.empty((N, SA), **f64), torch.empty((2, 2 * E, SA), **f64), torch.empty((sweeps, 2 * E), **f64)
+    _lib.call(entry, dev, N, E, score.shape[1], int(absent_score is not None), dz, switch, t_eu, t_ev, theta, t_g, t_d, t_ptr, t_edge, sweeps, damping,
+              w, mu, resid, out["belief"], out["state"], out["residual"])
+    return out
+
+
+def _refine_on_device(X, graph, S, has_absent, dz, switch, eu, ev, sweeps):
+    """gbp_horizon_graph_refine on the horizons ``X`` int32 [C, N] (device, contiguous), in place; returns the moves int32 [C, sweeps]."""
+    from . import sections
+    theta, t_eu, t_ev, t_g, t_d, t_ptr, t_edge = graph
+    C, N = X.shape
+    moves = torch.zeros((C, sweeps), dtype=torch.int32, device=X.device)
+    if N == 0 or sweeps == 0:
+        return moves
+    colour_ptr, colour_node = sections._colour_lists(eu, ev, N)
+    _lib.call("gbp_horizon_graph_refine", X.device, N, eu.size, S, has_absent, dz, switch, C, t_eu, t_ev, theta, t_g, t_d, t_ptr, t_edge,
+              colour_ptr.size - 1, np.ctypeslib.as_ctypes(colour_ptr), torch.as_tensor(colour_node).to(X.device), sweeps, X, moves)
+    return moves
+
+
+def refine(state, eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=16):
+    """Coordinate ascent on the exact log score on the device (gbp_horizon_graph_refine: csrc/gbp_horizon_graph.h k_hgraph_condition;
+    ``refine_reference`` states the rule): the horizons ``state`` int [N] or [R, N] (host or device; S: absent) on the graph of
+    ``propagate`` move sounding by sounding to their best state given their neighbours until a sweep moves nothing or ``sweeps``
+    sweeps are done.  Returns on the device ``state`` int32 (the shape given) and ``refine_moves`` int32 [R, sweeps] ([sweeps] for
+    one), and ``log_score`` (``graph_log_score``: float64 numpy [R], a number for one).  There is no host fallback."""
+    entry, what = "gbp_horizon_graph_refine", "horizons.refine"
+    _are_tensors(score, absent_score, "refine", entry)
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what)
+    sweeps = _args.check_int(sweeps, 0, MAX_REFINE, "%s: sweeps" % what)
+    S, has_absent = score.shape[1], int(absent_score is not None)
+    X, single = _check_states(state, score.shape[0], S + has_absent, MAX_CANDIDATES + 1, what, "state")
+    graph = _device_graph(eu, ev, g, d, score, absent_score, "refine", entry)
+    X = torch.as_tensor(X).to(score.device)
+    moves = _refine_on_device(X, graph, S, has_absent, dz, switch, eu, ev, sweeps)
+    ls = graph_log_score(X, eu, ev, g, d, dz, switch, score, absent_score)
+    return dict(state=X[0] if single else X, refine_moves=moves[0] if single else moves, log_score=ls[0] if single else ls)
+
+
+def graph_path(eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=32, damping=0.0, refine=16, candidates=None):
+    """The most probable horizon of the graph of ``propagate`` on the device (gbp_horizon_graph_path and gbp_horizon_graph_refine:
+    csrc/gbp_horizon_graph.h; ``graph_path_reference`` states the rule, and the device has its bits): the arguments of ``propagate``,
+    max-sum sweeps in place of sum-product ones.  The decode is refined by up to ``refine`` sweeps of coordinate ascent, and so is
+    every row of ``candidates`` (int [C, N], host or device; None: none); the refined horizon of the highest ``graph_log_score`` is
+    returned.  Exact on a forest once the sweeps reach its diameter; on loops an approximation, never below any candidate given.
+
+    Returns on the device ``state`` int32 [N] (S: absent), ``max_marginal`` f64 [N, SA], ``residual`` f64 [sweeps], ``decoded_state``
+    int32 [N], ``candidate_state`` int32 [C + 1, N], ``refine_moves`` int32 [C + 1, refine]; on the host ``log_score`` (a number),
+    ``candidate_log_score`` float64 [C + 1] and ``chosen``, an integer."""
+    from . import sections
+    entry, what = "gbp_horizon_graph_path", "horizons.graph_path"
+    _are_tensors(score, absent_score, "graph_path", entry)
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what)
+    sweeps, damping = _check_sweeps(sweeps, damping, what)
+    refine = _args.check_int(refine, 0, MAX_REFINE, "%s: refine" % what)
+    N, S = score.shape
+    has_absent = int(absent_score is not None)
+    SA, E = S + has_absent, eu.size
+    given = None if candidates is None else _check_states(candidates, N, SA, MAX_CANDIDATES, what, "candidates")[0]
+    graph = _device_graph(eu, ev, g, d, score, absent_score, "graph_path", entry)
+    theta, t_eu, t_ev, t_g, t_d, t_ptr, t_edge = graph
+    dev = theta.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    max_marginal, residual, decoded = torch.empty((N, SA), **f64), torch.zeros(sweeps, **f64), torch.zeros(N, dtype=torch.int32, device=dev)
+    if N:
+        level, level_ptr, level_node = sections.decode_levels(eu, ev, N)
+        nu, resid = torch.empty((2, 2 * E, SA), **f64), torch.empty((sweeps, 2 * E), **f64)
+        _lib.call(entry, dev, N, E, S, has_absent, dz, switch, t_eu, t_ev, theta, t_g, t_d, t_ptr, t_edge, sweeps, damping, level_ptr.size - 1,
+                  np.ctypeslib.as_ctypes(level_ptr), torch.as_tensor(level_node).to(dev), torch.as_tensor(level).to(dev), nu, resid, max_marginal,
+                  decoded, residual)
+    X = decoded[None, :].clone() if given is None else torch.cat([decoded[None, :], torch.as_tensor(given).to(dev)]).contiguous()
+    moves = _refine_on_device(X, graph, S, has_absent, dz, switch, eu, ev, refine)
+    ls = graph_log_score(X, eu, ev, g, d, dz, switch, score, absent_score)
+    chosen = sections._first_above(ls)[0]
+    return dict(state=X[chosen].clone(), log_score=ls[chosen], max_marginal=max_marginal, residual=residual, decoded_state=decoded, candidate_state=X,
+                candidate_log_score=ls, chosen=chosen, refine_moves=moves)
+
+
+def message_bytes(n_edges, n_states):
+    """The bytes of the two message buffers [2, 2 E, SA] of float64 a graph launch holds."""
+    return 2 * 2 * int(n_edges) * int(n_states) * 8
+
+
+def spatial(evidence, x, y, surface, depth_edges, *, max_distance, ptr=None, absent=None, between=None, slope=0.05, switch=4.6, floor=1e-6,
+            sweeps=32, damping=0.0, path=True, percentiles=(5, 50, 95), message_budget_bytes=8 << 30):
+    """One horizon over the whole survey: the arguments of ``track`` -- ``evidence`` [N, n_depth] on the device, ``x``, ``y``,
+    ``surface`` [N] on the host, the lines as ``ptr`` [L + 1] -- on the survey graph of ``sections.neighbours(x, y, ptr,
+    max_distance=...)`` (``max_distance`` is required, about 1.5 line spacings; its ``g`` is discarded for ``graph_steps``).  The
+    beliefs come from ``propagate`` (``sweeps``, ``damping``) and, with ``path``, the picks from ``graph_path`` with the same sweeps,
+    its candidates being the first maximum of every belief and the lines tracked alone.
+
+    Returns every entry of ``track`` as [N] -- ``cell`` int32 (index on the full axis; -1: absent), ``depth``, ``elevation``,
+    ``marginal`` [N, S] (the beliefs of the window's cells), ``absent_probability``, ``depth_percentile_<p>`` -- with the picks from the
+    chosen path (``path`` False: from the beliefs' first maxima), and ``log_score``, the path's ``graph_log_score``; beside them
+    ``belief_cell`` int32 [N] (the first maximum of every belief, alone), ``state_log_score`` (its ``graph_log_score``, to compare),
+    ``residual`` [sweeps], ``line_cell`` int32 [N] (the pick of ``track``, every line alone: what to compare against), ``edge_u``,
+    ``edge_v``, ``edge_length``; and with ``path`` ``path_margin`` f64 [N] (the gap between the two largest max-marginals; inf with one
+    state), ``path_residual`` [sweeps], ``path_candidate_log_score`` [3] (the refined decode, belief maxima and line picks) and
+    ``path_chosen``.  The two message buffers hold 2 * 2 E * SA doubles; beyond ``message_budget_bytes`` (8 GiB by default: a
+    convention, not a property of the device) a ValueError asks for a narrower window ``between=``."""
+    from . import sections
+    ptr, g_line, d_line, switch = _track_arguments(evidence, x, y, surface, absent, slope, switch, floor, ptr)
+    sweeps, damping = _check_sweeps(sweeps, damping, "horizons.spatial")
+    percentiles = check_percentiles(percentiles)
+    edges, dz = check_depth_edges(depth_edges)
+    if evidence.shape[1] != edges.size - 1:
+        raise ValueError("horizons.spatial: evidence has %d depth cells, depth_edges %d" % (evidence.shape[1], edges.size - 1))
+    lo, hi = window(edges, between)
+    S, N = hi - lo, evidence.shape[0]
+    SA = S + (absent is not None)
+    if S > MAX_STATES:
+        raise ValueError("horizons.spatial: %d states, at most %d (choose a window with between=)" % (S, MAX_STATES))
+    eu, ev, _, dist = sections.neighbours(x, y, ptr, None, max_distance=max_distance)
+    g, d, _ = graph_steps(x, y, surface, eu, ev, slope)
+    if message_bytes(eu.size, SA) > int(message_budget_bytes):
+        raise ValueError("horizons.spatial: the messages of %d edges and %d states take %d bytes, more than message_budget_bytes = %d; choose a "
+                         "narrower window with between=" % (eu.size, SA, message_bytes(eu.size, SA), int(message_budget_bytes)))
+    if evidence.device.type != "cuda":
+        raise _lib.NativeLibraryError("horizons.spatial runs on the device (gbp_horizon_graph_propagate); there is no host fallback")
+    dev = evidence.device
+    score, absent_score = evidence_scores(evidence[:, lo:hi], absent, floor)
+    score = score.contiguous()
+    alone = _launch(score, absent_score, ptr, g_line, d_line, dz, switch, False)["cell"]
+    found = propagate(eu, ev, g, d, dz, switch, score, absent_score, sweeps=sweeps, damping=damping)
+    args = (eu, ev, g, d, dz, switch, score, absent_score)
+    extra = {}
+    if path:
+        best = graph_path(*args, sweeps=sweeps, damping=damping, candidates=torch.stack([found["state"], alone]))
+        state, log_score = best["state"], best["log_score"]
+        two = torch.topk(best["max_marginal"], min(2, SA), dim=1).values
+        margin = two[:, 0] - two[:, 1] if SA > 1 else torch.full((N,), float("inf"), dtype=torch.float64, device=dev)
+        extra = dict(path_margin=margin, path_residual=best["residual"], path_candidate_log_score=torch.as_tensor(best["candidate_log_score"]).to(dev),
+                     path_chosen=torch.tensor(best["chosen"], dtype=torch.int32, device=dev))
+    else:
+        state, log_score = found["state"], graph_log_score(found["state"], *args)
+    f64 = lambda v: torch.tensor(float(v), dtype=torch.float64, device=dev)    # noqa: E731
+    out = _finish(dict(cell=state, log_score=f64(log_score), marginal=found["belief"]), S, lo, edges, surface, percentiles)
+    full_axis = lambda c: torch.where(c >= S, torch.full_like(c, -1), c + lo)  # noqa: E731
+    out.update(belief_cell=full_axis(found["state"]), state_log_score=f64(graph_log_score(found["state"], *args)), residual=found["residual"],
+               line_cell=full_axis(alone), edge_u=eu.astype(np.int32), edge_v=ev.astype(np.int32), edge_length=dist, **extra)
+    return out
+
+
+def spatial_from_products(paths, between, max_distance, slope=0.05, switch=4.6, floor=1e-6, sweeps=32, damping=0.0, path=True,
+                          percentiles=(5, 50, 95), absent=False, device=None, message_budget_bytes=8 << 30):
+    """``spatial`` for results containers (or saved line products with x, y and the surface beside them: what ``from_products`` reads):
+    all ``paths`` given form ONE graph, every container a line, and one horizon is sought per window of ``between`` = [(d0, d1), ...].
+    The containers must share their ``interface_depth_edges``.  The windows run one after the other (each has its own state count
+    and its own graph launch).  Returns the entries of ``spatial`` stacked [H, N] (``log_score``, ``state_log_score``, ``path_chosen``
+    [H]; ``residual``, ``path_residual``, ``path_candidate_log_score`` [H, ..]), ``marginal_<h>`` [N, S_h], ``between`` [H, 2], the
+    graph's ``edge_u``, ``edge_v``, ``edge_length`` once, and ``ptr`` [L + 1], the containers' ranges of soundings."""
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike, dict)) else list(paths)
+    if not paths:
+        raise ValueError("horizons.spatial_from_products: at least one container is needed")
+    wins = [tuple(float(v) for v in w) for w in np.asarray(between, dtype=np.float64).reshape(-1, 2)]
+    if not wins:
+        raise ValueError("horizons.spatial_from_products: at least one window (d0, d1) is needed")
+    read = [_read(p, None) for p in paths]
+    for prob, edges, cx, cy, cs in read:
+        if cx is None or cy is None or cs is None:
+            raise ValueError("horizons.spatial_from_products: every container must hold x, y and the surface elevation")
+        if edges.shape != read[0][1].shape or np.any(edges != read[0][1]):
+            raise ValueError("horizons.spatial_from_products: the containers must share their interface_depth_edges")
+        if prob.ndim != 2 or prob.shape[1] != edges.size - 1:
+            raise ValueError("horizons.spatial_from_products: interface_probability %r does not match its %d depth cells" % (prob.shape, edges.size - 1))
+    edges = read[0][1]
+    prob = np.nan_to_num(np.concatenate([r[0] for r in read]), nan=0.0)
+    x, y, surface = (np.concatenate([np.asarray(r[i], dtype=np.float64).reshape(-1) for r in read]) for i in (2, 3, 4))
+    ptr = np.concatenate([[0], np.cumsum([r[0].shape[0] for r in read])]).astype(np.int64)
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    e = torch.as_tensor(prob).to(dev) if dev.type == "cuda" else torch.as_tensor(prob)
+    parts = []
+    for w in wins:
+        lo, hi = window(edges, w)
+        ab = (e.sum(1) - e[:, lo:hi].sum(1)).clamp(min=0.0) if absent else None
+        parts.append(spatial(e, x, y, surface, edges, max_distance=max_distance, ptr=ptr, absent=ab, between=w, slope=slope, switch=switch, floor=floor,
+                             sweeps=sweeps, damping=damping, path=path, percentiles=percentiles, message_budget_bytes=message_budget_bytes))
+    out = {}
+    for k in parts[0]:
+        if k == "marginal":
+            for h, p in enumerate(parts):
+                out["marginal_%d" % h] = p[k]
+        elif k in ("edge_u", "edge_v", "edge_length"):
+            out[k] = parts[0][k]
+        else:
+            out[k] = torch.stack([p[k] for p in parts])
+    out["between"], out["ptr"] = np.asarray(wins, dtype=np.float64).reshape(-1, 2), ptr
+    return out
+
+
 def output_path(container):
     """``<line>.horizons.npz`` next to the container."""
     from .line_products import output_path as products_path
@@ -498,6 +1063,12 @@ def parser():
     ap.add_argument("--absent", action="store_true", help="add the absent state, weighted by the interface probability outside the window")
     ap.add_argument("--no-marginals", action="store_true", help="only the picks: skip the forward-backward pass")
     ap.add_argument("--device", default=None, help="torch device of the kernels (default cuda:0)")
+    ap.add_argument("--spatial", type=float, default=None, metavar="MAX_DISTANCE",
+                    help="couple the lines: all containers given form one survey graph whose lines are joined across up to this distance (m; "
+                         "about 1.5 line spacings), and survey.horizons.npz is written beside the first container")
+    ap.add_argument("--sweeps", type=int, default=32, help="with --spatial: synchronous sweeps of message passing (default 32)")
+    ap.add_argument("--damping", type=float, default=0.0, help="with --spatial: damping of the messages in [0, 1) (default 0)")
+    ap.add_argument("--no-path", action="store_true", help="with --spatial: the picks are the beliefs' first maxima, not the max-sum path")
     return ap
 
 
@@ -511,12 +1082,27 @@ def parse_args(argv=None):
     for d0, d1 in a.between:
         if not d0 < d1:
             ap.error("--between D0 D1 needs D0 < D1")
+    if a.spatial is None and (a.sweeps != 32 or a.damping != 0.0 or a.no_path):
+        ap.error("--sweeps, --damping and --no-path need --spatial MAX_DISTANCE")
+    if a.spatial is not None and not (np.isfinite(a.spatial) and a.spatial > 0.0):
+        ap.error("--spatial MAX_DISTANCE must be positive")
+    if not 1 <= a.sweeps <= MAX_SWEEPS:
+        ap.error("--sweeps must lie in 1 .. %d" % MAX_SWEEPS)
+    if not 0.0 <= a.damping < 1.0:
+        ap.error("--damping must lie in [0, 1)")
     return a
 
 
 def main(argv=None):
     from .line_products import containers
     a = parse_args(argv)
+    if a.spatial is not None:
+        found = [c for path in a.paths for c in containers(path)]
+        r = spatial_from_products(found, a.between, a.spatial, slope=a.slope, switch=a.switch, sweeps=a.sweeps, damping=a.damping, path=not a.no_path,
+                                  absent=a.absent, device=a.device)
+        written = [save(r, os.path.join(os.path.dirname(os.path.abspath(found[0])), SURVEY_OUTPUT))]
+        print(written[0])
+        return written
     written = []
     for path in a.paths:
         for c in containers(path):

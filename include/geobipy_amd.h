@@ -1177,6 +1177,54 @@ gbp_status gbp_section_graph_refine(int S, int E, int n, int C, const int32_t *e
                                     const int32_t *in_edge, int n_colours, const int32_t *colour_ptr, const int32_t *colour_node,
                                     int refine, int32_t *state, int32_t *moves, void *stream);
 
+/* Horizons across lines: the graph of gbp_section_propagate with the states and the pair term of gbp_horizon_track
+ * (csrc/gbp_horizon_graph.h k_hgraph_init, k_hgraph_sweep, k_hgraph_node, k_hgraph_condition; the rules are stated in
+ * numpy as horizons.propagate_reference, horizons.graph_path_reference and horizons.refine_reference).  DEVICE arrays throughout, none
+ * read on the host but level_ptr / colour_ptr, which are HOST arrays.  N soundings share S cells of width dz (1 .. 2048) and, with
+ * has_absent = 1, the absent state S: SA = S + has_absent states; score f64 [N, SA], the absent state's score last.  E undirected edges
+ * eu[e] < ev[e] int32 [E], sorted by (eu, ev) without duplicates, with g f64 [E] and d f64 [E] (horizons.graph_steps); cell a under
+ * eu[e] and cell b under ev[e] cost T_e[b - a] = g[e] * fabs(d[e] - (double)(b - a) * dz); cell <-> absent costs switch_cost >= 0,
+ * absent <-> absent 0.  Directed edge 2 e is eu -> ev, 2 e + 1 is ev -> eu; in_ptr int32 [N + 1] and in_edge int32 [2 E] are the CSR of
+ * every sounding's incoming directed edges, sorted by the sounding they come from (sections.incoming).  A message's source states are
+ * visited cells ascending, then absent.
+ *   gbp_horizon_graph_propagate: sum-product.  w = exp(score), K_e = exp(-T_e), ks = exp(-switch_cost); messages start at 1 / SA; for
+ *   a -> b, h = w_a times the messages into a from all neighbours but b (ascending neighbour); u[j] = sum_i h[i] K (cells i ascending)
+ *   + h[S] ks for a cell j, u[S] = sum_i h[i] ks + h[S]; tot = sum_j u[j], j ascending, by one lane; mu' = u / tot; with damping != 0
+ *   mu' = (1 - damping) mu' + damping mu_old.  residual f64 [sweeps]: the largest |mu' - mu_old| of the sweep (NaN if a message is;
+ *   0.0 without edges).  belief f64 [N, SA] = w_s times all incoming messages, divided by its sum (ascending); state int32 [N]: its
+ *   first maximum.  A zero tot gives NaN.  The device's exp is not numpy's to the last bit; every other operation is the rule's.
+ *   Workspaces: w f64 [N, SA], mu f64 [2, 2 E, SA], resid f64 [sweeps, 2 E].
+ *   gbp_horizon_graph_path: max-sum in the log domain, no exp.  Messages start at 0.0; u[j] = the maximum of h[i] - T (cells i
+ *   ascending, from -inf on strict >), then h[S] - switch_cost; u[S] of h[i] - switch_cost, then h[S]; nu' = u minus its first maximum;
+ *   damping and residual as above.  max_marginal f64 [N, SA] = score_s plus all incoming messages, minus its maximum.  level,
+ *   level_node, level_ptr as gbp_section_graph_path takes them (sections.decode_levels): decoded_state[s] = the first maximum of
+ *   score_s[i] minus, per neighbour q ascending, the pair cost at x_q if level[q] < level[s], else plus nu[q -> s][i].  The outputs have
+ *   the rule's bits.  Workspaces: nu f64 [2, 2 E, SA] (the last sweep's messages are left in half sweeps & 1), resid f64 [sweeps, 2 E].
+ *   gbp_horizon_graph_refine: coordinate ascent of C horizons state int32 [C, N] in place, as gbp_section_graph_refine: colour_node,
+ *   colour_ptr of sections.sounding_colours; a sounding moves to the first maximum of v[i] = score_s[i] minus the pair costs at its
+ *   neighbours' states only if v there is strictly greater than at its state; moves int32 [C, refine].
+ * One 256-thread workgroup per undirected edge and sweep with (4 S + 2) doubles of dynamic LDS (65 552 B at S = 2048), one per sounding
+ * for the beliefs, the max-marginals, the decode and the ascent.  No float atomics: a call repeats its bits.
+ * GBP_ERR_INVALID_ARG, before any launch and naming the entry: N < 0, E < 0 or > 2^30 - 1, S < 1 or > 2048, has_absent not 0 or 1, dz
+ * not positive, switch_cost negative or not finite, E > 0 with N < 2, sizes out of range (N + 2 E, N * SA, 2 * 2 E * SA, sweeps * 2 E,
+ * C * N), sweeps < 1, damping outside [0, 1), C outside 1 .. 65537, refine outside 0 .. 65536, with N > 0 n_levels / n_colours outside
+ * 1 .. N, a NULL score / in_ptr / output / group array or a group_ptr that does not start at 0, end at N or that decreases, with E > 0 a
+ * NULL eu / ev / g / d / in_edge / message or resid workspace.  N == 0 launches nothing that reads a sounding, E == 0 nothing that reads
+ * an edge.  An index that does not fit is skipped on the device, never followed; a neighbour's state is clamped into 0 .. SA - 1. */
+gbp_status gbp_horizon_graph_propagate(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t *eu,
+                                       const int32_t *ev, const double *score, const double *g, const double *d, const int32_t *in_ptr,
+                                       const int32_t *in_edge, int sweeps, double damping, double *w, double *mu, double *resid,
+                                       double *belief, int32_t *state, double *residual, void *stream);
+gbp_status gbp_horizon_graph_path(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t *eu,
+                                  const int32_t *ev, const double *score, const double *g, const double *d, const int32_t *in_ptr,
+                                  const int32_t *in_edge, int sweeps, double damping, int n_levels, const int32_t *level_ptr,
+                                  const int32_t *level_node, const int32_t *level, double *nu, double *resid, double *max_marginal,
+                                  int32_t *decoded_state, double *residual, void *stream);
+gbp_status gbp_horizon_graph_refine(int N, int E, int S, int has_absent, double dz, double switch_cost, int C, const int32_t *eu,
+                                    const int32_t *ev, const double *score, const double *g, const double *d, const int32_t *in_ptr,
+                                    const int32_t *in_edge, int n_colours, const int32_t *colour_ptr, const int32_t *colour_node,
+                                    int refine, int32_t *state, int32_t *moves, void *stream);
+
 /* Connected bodies of R realisations of a raster (csrc/gbp_bodies.h k_bodies_label; the rule is stated in numpy as
  * bodies.label_reference).  raster f64 [R, S, C]: S soundings, C cells each (depth or ONE elevation axis).  A cell is a member iff
  * lo <= v <= hi in fp64 (a NaN never is; +-inf bounds give one-sided thresholds).  Cells (s, c) and (s, c + 1) are adjacent, and
