@@ -196,6 +196,10 @@ SIGNATURES = {
                                        + [c_int, ctypes.c_double, c_int, c_int32_p] + [c_void_p] * 7 + [c_void_p]),
     "gbp_horizon_graph_refine": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int] + [c_void_p] * 7
                                          + [c_int, c_int32_p, c_void_p, c_int, c_void_p, c_void_p] + [c_void_p]),
+    "gbp_horizon_draw": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 ctypes.c_double, c_void_p, ctypes.c_uint64, c_int] + [c_void_p] * 3 + [c_void_p]),
+    "gbp_horizon_graph_draw": (c_int, [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 5 + [c_int] + [c_void_p] * 4
+                                       + [c_int] + [c_void_p] * 3 + [ctypes.c_uint64, c_int, c_int, c_int, c_int] + [c_void_p] * 3 + [c_void_p]),
     "gbp_bodies_label": (c_int, [c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                  ctypes.c_double] + [c_void_p] * 4 + [c_void_p]),
     "gbp_borehole_score": (c_int, [c_int, c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int]

@@ -2973,6 +2973,153 @@ extern "C" gbp_status gbp_horizon_graph_refine(int N, int E, int S, int has_abse
     return GBP_OK;
 }
 
+#include "gbp_horizon_draw.h"
+
+// Joint draws of horizons (gbp_horizon_draw.h).  Along lines: the filter launch, one workgroup per sequence, then the walks, one
+// workgroup per (sequence, 256 realisations).  On the survey graph: the same pair at the start sweep, then per sweep and colour a
+// conditioned filter launch with a workgroup per (sequence, realisation) and a walk whose lanes read their own alpha rows.  Every
+// refusal comes before any launch; no device array is read on the host.
+namespace {
+
+struct HorizonDrawArgs {
+    int L;
+    const int64_t* ptr;
+    int64_t n_total;
+    int E, S, has_absent;
+    double dz;
+    const double *score, *absent_score, *g, *d;
+    double sw;
+    const int32_t *step_edge, *eu, *ev, *cross_ptr, *cross_edge, *colour_ptr;
+    const int64_t* row_key;
+    uint64_t seed;
+    int n_draws, first_draw;
+    double *filtered, *scale;
+    int32_t* draw_state;
+};
+
+// One filter launch and one walk launch: COND false draws every sequence alone from one shared alpha (lines NULL), COND true the
+// sequences of `colour` given the other colours' states.
+template <int NJ, bool COND>
+gbp_status horizon_draw_pair(const HorizonDrawArgs& a, const int32_t* lines, int colour, unsigned sweep, hipStream_t st)
+{
+    const size_t lds = horizon_draw::filter_lds_doubles(a.S) * sizeof(double);
+    const size_t walk_lds = horizon_draw::walk_lds_doubles(a.S, !COND) * sizeof(double);
+    if (lds > 48 * 1024) {                                                  // (above the default limit of a launch's dynamic LDS)
+        (void)hipFuncSetAttribute((const void*)horizon_draw::k_horizon_filter<NJ, COND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+    }
+    if (walk_lds > 48 * 1024) {
+        (void)hipFuncSetAttribute((const void*)horizon_draw::k_horizon_walk<!COND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds);
+        (void)hipGetLastError();
+    }
+    const unsigned filter_blocks = COND ? (unsigned)((long long)a.L * a.n_draws) : (unsigned)a.L;
+    hipLaunchKernelGGL((horizon_draw::k_horizon_filter<NJ, COND>), dim3(filter_blocks), dim3(horizon_draw::THREADS), lds, st, (const long long*)a.ptr,
+                       a.L, (long long)a.n_total, a.E, a.S, a.has_absent, a.dz, a.score, a.absent_score, a.g, a.d, a.sw, (const int*)a.step_edge,
+                       (const int*)a.eu, (const int*)a.ev, (const int*)a.cross_ptr, (const int*)a.cross_edge, (const int*)a.colour_ptr,
+                       (const int*)lines, colour, (const int*)a.draw_state, a.filtered, a.scale);
+    GBP_HIP(hipGetLastError());
+    hipLaunchKernelGGL((horizon_draw::k_horizon_walk<!COND>),
+                       dim3((unsigned)a.L, (unsigned)((a.n_draws + horizon_draw::THREADS - 1) / horizon_draw::THREADS)), dim3(horizon_draw::THREADS),
+                       walk_lds, st, (const long long*)a.ptr, a.L, (long long)a.n_total, a.E, a.S, a.has_absent, a.dz, a.g, a.d, a.sw,
+                       (const int*)a.step_edge, (const int*)a.colour_ptr, (const int*)lines, colour, (const long long*)a.row_key,
+                       (unsigned long long)a.seed, a.n_draws, a.first_draw, sweep, (const double*)a.filtered, (int*)a.draw_state);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+template <int NJ>
+gbp_status horizon_draw_sweeps(const HorizonDrawArgs& a, const int32_t* colour_line, int n_colours, int first_sweep, int last_sweep, hipStream_t st)
+{
+    for (int t = first_sweep; t <= last_sweep; ++t) {
+        if (t == 0) {                                                       // the start: every sequence alone
+            const gbp_status rc = horizon_draw_pair<NJ, false>(a, nullptr, 0, 0u, st);
+            if (rc != GBP_OK) return rc;
+            continue;
+        }
+        for (int c = 0; c < n_colours; ++c) {
+            const gbp_status rc = horizon_draw_pair<NJ, true>(a, colour_line, c, (unsigned)t, st);
+            if (rc != GBP_OK) return rc;
+        }
+    }
+    return GBP_OK;
+}
+
+gbp_status horizon_draw_dispatch(const HorizonDrawArgs& a, const int32_t* colour_line, int n_colours, int first_sweep, int last_sweep, hipStream_t st)
+{
+#define GBP_HORIZON_DRAW_CASE(nj) \
+    case nj: return horizon_draw_sweeps<nj>(a, colour_line, n_colours, first_sweep, last_sweep, st)
+    switch ((a.S + 1 + horizon::THREADS - 1) / horizon::THREADS) {
+        GBP_HORIZON_DRAW_CASE(1);
+        GBP_HORIZON_DRAW_CASE(2);
+        GBP_HORIZON_DRAW_CASE(3);
+        GBP_HORIZON_DRAW_CASE(4);
+        GBP_HORIZON_DRAW_CASE(5);
+        GBP_HORIZON_DRAW_CASE(6);
+        GBP_HORIZON_DRAW_CASE(7);
+        GBP_HORIZON_DRAW_CASE(8);
+        default: return horizon_draw_sweeps<horizon::MAX_OWNED>(a, colour_line, n_colours, first_sweep, last_sweep, st);
+    }
+#undef GBP_HORIZON_DRAW_CASE
+}
+
+}  // namespace
+
+extern "C" gbp_status gbp_horizon_draw(int L, const int64_t* ptr, int64_t total_n, int max_n, int S, double dz, const double* score,
+                                       const double* absent_score, const double* g, const double* d, double switch_cost,
+                                       const int64_t* row_key, uint64_t seed, int n_draws, double* filtered, double* scale,
+                                       int32_t* draw_state, void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: L must be >= 0%s");
+    if (S < 1 || S > horizon::MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: S must lie in 1 .. 2048 (the states live in LDS)%s");
+    if (n_draws < 1 || n_draws > horizon_draw::MAX_DRAWS) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: n_draws must lie in 1 .. 65536%s");
+    if (!(dz > 0.0) || !std::isfinite(dz)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: dz must be positive and finite%s");
+    if (!(switch_cost >= 0.0) || !std::isfinite(switch_cost)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: switch must be >= 0 and finite%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < 0 || max_n < 0 || max_n > total_n || total_n > (int64_t)max_n * L)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: total_n and max_n do not fit L sequences%s");
+    if (total_n == 0) return GBP_OK;                                        // (every sequence is empty)
+    if (total_n > 0x7fffffffffffffffLL / 8 / (S + 1)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: total_n * (S + 1) out of range%s");
+    if (total_n > 0x7fffffffffffffffLL / 4 / n_draws) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: n_draws * total_n out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: ptr is NULL%s");
+    if (!score || !g || !d) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: NULL pointer (score, g, d)%s");
+    if (!filtered || !scale) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: NULL pointer (filtered, scale)%s");
+    if (!draw_state) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_draw: draw_state is NULL%s");
+    const HorizonDrawArgs a{L, ptr, total_n, 0, S, absent_score ? 1 : 0, dz, score, absent_score, g, d, switch_cost, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, row_key, seed, n_draws, 0, filtered, scale, draw_state};
+    return horizon_draw_dispatch(a, nullptr, 0, 0, 0, (hipStream_t)stream);
+}
+
+extern "C" gbp_status gbp_horizon_graph_draw(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t* eu,
+                                             const int32_t* ev, const double* score, const double* g, const double* d, int L,
+                                             const int64_t* ptr, const int32_t* step_edge, const int32_t* cross_ptr,
+                                             const int32_t* cross_edge, int n_colours, const int32_t* colour_ptr,
+                                             const int32_t* colour_line, const int64_t* row_key, uint64_t seed, int n_draws,
+                                             int first_draw, int first_sweep, int sweeps, double* alpha, double* scale,
+                                             int32_t* draw_state, void* stream)
+{
+    static const char* const entry = "gbp_horizon_graph_draw";
+    if (const char* why = hgraph_refusal(N, E, S, has_absent, dz, switch_cost)) return hgraph_fail(entry, why);
+    const int SA = S + has_absent;
+    if (L < 0) return hgraph_fail(entry, "L must be >= 0");
+    if (n_draws < 1 || n_draws > horizon_draw::MAX_DRAWS) return hgraph_fail(entry, "n_draws must lie in 1 .. 65536");
+    if (first_draw < 0 || first_draw > horizon_draw::MAX_DRAWS - n_draws) return hgraph_fail(entry, "first_draw + n_draws must lie in 1 .. 65536");
+    if (first_sweep < 0 || sweeps < first_sweep || sweeps > horizon_draw::MAX_SWEEPS)
+        return hgraph_fail(entry, "the sweeps need 0 <= first_sweep <= sweeps <= 65535");
+    if (N > 0 && L < 1) return hgraph_fail(entry, "soundings need a sequence (L >= 1)");
+    if (L > 0 && (n_colours < 1 || n_colours > L)) return hgraph_fail(entry, "the colour lists must cover the sequences: n_colours must lie in 1 .. L");
+    if ((long long)n_draws * N > 0x7fffffffffffffffLL / 8 / SA) return hgraph_fail(entry, "n_draws * N * SA out of range");
+    if ((long long)n_draws * N > 0x7fffffffffffffffLL / 4) return hgraph_fail(entry, "n_draws * N out of range");
+    if ((long long)L * n_draws > 0x7fffffffLL) return hgraph_fail(entry, "L * n_draws out of range");
+    if (N > 0 && (!score || !ptr || !step_edge || !cross_ptr || !colour_ptr || !colour_line))
+        return hgraph_fail(entry, "NULL pointer (score, ptr, step_edge, cross_ptr, colour_ptr, colour_line)");
+    if (N > 0 && (!alpha || !scale || !draw_state)) return hgraph_fail(entry, "NULL pointer (alpha, scale, draw_state)");
+    if (E > 0 && (!eu || !ev || !g || !d || !cross_edge)) return hgraph_fail(entry, "NULL pointer (eu, ev, g, d, cross_edge)");
+    if (N == 0) return GBP_OK;
+    const HorizonDrawArgs a{L, ptr, N, E, S, has_absent, dz, score, nullptr, g, d, switch_cost, step_edge, eu, ev, cross_ptr, cross_edge, colour_ptr,
+                            row_key, seed, n_draws, first_draw, alpha, scale, draw_state};
+    return horizon_draw_dispatch(a, colour_line, n_colours, first_sweep, sweeps, (hipStream_t)stream);
+}
+
 #include "gbp_section_graph_draw.h"
 
 // Joint draws across lines (gbp_section_graph_draw.h): K unless the caller has it, the weights, then per sweep a filter launch and a draw

@@ -36,7 +36,16 @@ sum side the reference's own rounding.  On a line graph they are the chain's mar
 they are an approximation (a belief is not a marginal), and the path is never less probable than any candidate it was given -- the
 lines tracked alone among them.
 
-Left out on purpose: joint draws of horizons, several horizons tracked jointly with an ordering constraint, learning ``slope``
+Joint draws (csrc/gbp_horizon_draw.h; ``gbp_horizon_draw``, ``gbp_horizon_graph_draw``).  A pick has no spread and a
+marginal cannot say which depth under one sounding goes with which under the next.  ``draw_reference`` states forward filtering and
+backward sampling of the chain above in numpy, ``draw`` runs it on the device, ``track(draws=R)`` and ``from_products(draws=R)`` return R
+joint realisations per horizon, and ``draw_summary`` / ``connected`` turn them into posteriors of a length, a cross-section, a gap, "no
+gap from a to b".  Across lines ``graph_draw_reference`` states Gibbs sampling blocked by flight line on the survey graph -- the same
+filter and walk per line, its weights multiplied by the pair factors at the neighbouring lines' current states --, ``graph_draw`` runs
+it, and ``spatial(draws=R)`` / ``spatial_from_products(draws=R)`` return the realisations with ``draw_share`` and
+``draw_change_share``.  Where several horizons share a launch or a survey the row key of a draw is sounding index + horizon index * N.
+
+Left out on purpose: several horizons tracked jointly with an ordering constraint, learning ``slope``
 (``log_partition`` of ``track`` is returned for whoever wants to scan it), non-uniform depth cells, gridding the picks into a surface,
 and a place in ``survey.infer``.
 """
@@ -230,6 +239,262 @@ def track_reference(ptr, score, absent_score, g, d, dz, switch, marginals=True, 
     return out
 
 
+MAX_DRAWS = 65536
+
+
+def _check_draw_chain(ptr, score, absent_score, g, d, dz, switch, n_draws, seed, row_key, what):
+    """The checks ``draw_reference`` and ``draw`` share, on shapes and host values alone (``score`` numpy or torch, any device): a
+    sequence of ``ptr`` may be empty.  Returns ptr (int64 numpy), g, d (float64 numpy), dz, switch, R, seed and the keys (int64 numpy;
+    None when ``row_key`` is)."""
+    from . import sections
+    if getattr(score, "ndim", 0) != 2 or not 1 <= score.shape[1] <= MAX_STATES:
+        raise ValueError("%s: score must be [N, S] with 1 <= S <= %d (choose a window with between=)" % (what, MAX_STATES))
+    total = score.shape[0]
+    ptr = _args.check_ptr(ptr, total, "horizons", empty=True)
+    if absent_score is not None and tuple(absent_score.shape) != (total,):
+        raise ValueError("%s: absent_score must hold one entry per sounding" % what)
+    g, d = np.asarray(_args.host(g), dtype=np.float64).reshape(-1), np.asarray(_args.host(d), dtype=np.float64).reshape(-1)
+    if g.size != total or d.size != total:
+        raise ValueError("%s: g and d must hold one entry per sounding" % what)
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(d))):
+        raise ValueError("%s: g and d must be finite" % what)
+    dz, switch = float(dz), float(switch)
+    if not (np.isfinite(dz) and dz > 0.0):
+        raise ValueError("%s: dz must be positive" % what)
+    if not (np.isfinite(switch) and switch >= 0.0):
+        raise ValueError("%s: switch must be >= 0" % what)
+    R = _args.check_int(n_draws, 1, MAX_DRAWS, "%s: n_draws" % what)
+    seed = sections._check_seed(seed)
+    key = None if row_key is None else sections._check_row_key(row_key, total, what)
+    return ptr, g, d, dz, switch, R, seed, key
+
+
+def draw_reference(ptr, score, absent_score, g, d, dz, switch, n_draws, seed=0, row_key=None, dtype=np.float64):
+    """The rule of ``draw`` in numpy, evaluated in ``dtype``: joint draws of whole horizons from the chain of the module's docstring by
+    forward filtering and backward sampling.  The inputs of ``track_reference`` (a sequence of ``ptr`` may be empty here), ``n_draws``
+    = R in 1 .. 65536, ``seed`` (uint64) and ``row_key`` int64 [sum N] (None: the row index).
+
+    Filter, per sequence: the forward half of ``track_reference``'s marginals, word for word -- w = exp(score), K_n[k] = exp(-(g[n] *
+    |d[n] - k * dz|)), ks = exp(-switch); alpha_0 = w_0 / s_0; alpha_{n+1}[c'] = w[n + 1, c'] * (sum_c alpha_n[c] K_n[c' - c] +
+    alpha_n[absent] * ks), c ascending and acc = acc + a * K; the absent row sum_c alpha_n[c] * ks + alpha_n[absent]; each row divided
+    by its sum s.
+    Walk: realisation rho goes n = N - 1 .. 0 over the states i = 0 .. SA - 1, cells ascending and absent last; j is the state just
+    drawn under n + 1.  W[i] = alpha_n[i] at the sequence's last sounding; alpha_n[i] * K_n[j - i] for cells i and j; alpha_n[i] * ks
+    for a cell i and j absent; alpha_n[S] * ks for i absent and a cell j; alpha_n[S], with no multiply, for both absent.  c =
+    cumsum(W), sequential, c = c + w; thr = u * c[SA - 1]; pick = min(#{i : c[i] <= thr}, SA - 1).  A state of weight 0 is never the
+    first to pass thr, so it is never drawn; with a NaN total no comparison holds and the pick is 0.
+    u = ``sections.philox_uniform(seed, rho, row_key[n], sweep=0)``: a draw depends on the seed, the realisation and the sounding's key
+    -- not on R, on the grouping of sequences into calls, or on a launch shape.  Where several horizons (windows, thresholds) share a
+    launch or a survey, the convention is row_key = sounding index + horizon index * N, so that two horizons of one sounding never
+    share a uniform.
+
+    Returns ``draw_state`` int32 [R, sum N] (S: absent), ``filtered`` [sum N, SA] (alpha, the absent state last), ``scale`` [sum N]
+    (s_n) and ``margin`` [R, L]: the smallest min_i |c[i] - thr| / c[SA - 1] over the sequence's soundings (inf for an empty sequence)
+    -- how close the walk came to another outcome (a device whose exp differs in the last bit may decide a draw with a margin of a few
+    ulp the other way, and the walk differs from there on)."""
+    from . import sections
+    what = "horizons.draw_reference"
+    ft = np.dtype(dtype).type
+    score = np.asarray(score, dtype=np.float64)
+    has_absent = absent_score is not None
+    absent_score = np.asarray(absent_score, dtype=np.float64).reshape(-1) if has_absent else None
+    ptr, g, d, dz, switch, R, seed, key = _check_draw_chain(ptr, score, absent_score, g, d, dz, switch, n_draws, seed, row_key, what)
+    if not (np.all(np.isfinite(score)) and (not has_absent or np.all(np.isfinite(absent_score)))):
+        raise ValueError("%s: the scores must be finite" % what)
+    total, S = score.shape
+    key = np.arange(total, dtype=np.int64) if key is None else key
+    score, g, d = score.astype(ft), g.astype(ft), d.astype(ft)
+    absent_score = absent_score.astype(ft) if has_absent else None
+    dz, switch = ft(dz), ft(switch)
+    SA, L = S + int(has_absent), ptr.size - 1
+    kf = np.arange(-(S - 1), S).astype(ft)                                   # k = c' - c at index k + S - 1
+    ks = np.exp(-switch)
+    rho, cells = np.arange(R, dtype=np.int64), np.arange(S, dtype=np.int64)
+    draw_state, filtered, scale = np.zeros((R, total), dtype=np.int32), np.zeros((total, SA), dtype=ft), np.zeros(total, dtype=ft)
+    margin = np.full((R, L), np.inf, dtype=ft)
+    for l in range(L):
+        r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+        if N == 0:
+            continue
+        full = lambda n: score[r0 + n] if not has_absent else np.concatenate([score[r0 + n], absent_score[r0 + n:r0 + n + 1]])  # noqa: E731
+        w = np.exp(np.stack([full(n) for n in range(N)]))                     # [N, SA]
+        alpha, s, Ks = np.zeros((N, SA), dtype=ft), np.zeros(N, dtype=ft), []
+        with np.errstate(invalid="ignore", divide="ignore", under="ignore"):
+            s[0] = w[0].sum()
+            alpha[0] = w[0] / s[0]
+            for n in range(N - 1):
+                K = np.exp(-(g[r0 + n] * np.abs(d[r0 + n] - kf * dz)))
+                Ks.append(K)
+                a = alpha[n]
+                u = np.zeros(SA, dtype=ft)
+                for c in range(S):                                           # c ascending
+                    u[:S] = u[:S] + a[c] * K[S - 1 - c:2 * S - 1 - c]
+                if has_absent:
+                    u[:S] = u[:S] + a[S] * ks
+                    u[S] = np.cumsum(a[:S] * ks)[-1] + a[S]
+                u = w[n + 1] * u
+                s[n + 1] = u.sum()
+                alpha[n + 1] = u / s[n + 1]
+            filtered[r0:r0 + N], scale[r0:r0 + N] = alpha, s
+            j = None
+            for n in range(N - 1, -1, -1):
+                a = alpha[n]
+                W = np.empty((R, SA), dtype=ft)
+                if n == N - 1:
+                    W[:] = a[None, :]
+                else:
+                    Kx = np.append(Ks[n], ks)                                # the switch in slot 2 S - 1
+                    jc = j < S
+                    slot = np.where(jc[:, None], j[:, None] - cells[None, :] + (S - 1), 2 * S - 1)
+                    W[:, :S] = a[None, :S] * Kx[slot]
+                    if has_absent:
+                        W[:, S] = np.where(jc, a[S] * ks, a[S])
+                c = np.cumsum(W, axis=1, dtype=ft)                           # sequential, i ascending
+                thr = sections.philox_uniform(seed, rho, key[r0 + n]).astype(ft) * c[:, -1]
+                j = np.minimum((c <= thr[:, None]).sum(axis=1), SA - 1)
+                margin[:, l] = np.fmin(margin[:, l], np.abs(c - thr[:, None]).min(axis=1) / c[:, -1])
+                draw_state[:, r0 + n] = j
+    return dict(draw_state=draw_state, filtered=filtered, scale=scale, margin=margin)
+
+
+def draw(ptr, score, absent_score, g, d, dz, switch, n_draws, seed=0, row_key=None):
+    """Joint draws of whole horizons from the chain of ``track`` by forward filtering and backward sampling on the device
+    (gbp_horizon_draw: csrc/gbp_horizon_draw.h k_horizon_filter / k_horizon_walk; ``draw_reference`` states the rule): ``score`` f64
+    [sum N, S] and ``absent_score`` f64 [sum N] or None on the device, ``ptr`` [L + 1] (a sequence may be empty), ``g``, ``d`` [sum N]
+    (``steps``; host or device), ``n_draws`` = R in 1 .. 65536, ``seed`` a uint64, ``row_key`` int64 [sum N] (host or device; None: the
+    row index).  The uniform of realisation rho under a sounding is ``sections.philox_uniform(seed, rho, row_key)``, so soundings keep
+    their draws however they are grouped into calls; where several horizons (windows, thresholds) share a launch or a survey,
+    row_key = sounding index + horizon index * N keeps two horizons of one sounding from sharing a uniform.  Returns on the device
+    ``draw_state`` int32 [R, sum N] (S: absent), ``filtered`` [sum N, SA] and ``scale`` [sum N].  There is no host fallback."""
+    entry, what = "gbp_horizon_draw", "horizons.draw"
+    _are_tensors(score, absent_score, "draw", entry)
+    ptr, g, d, dz, switch, R, seed, key = _check_draw_chain(ptr, score, absent_score, g, d, dz, switch, n_draws, seed, row_key, what)
+    if score.dtype != torch.float64 or (absent_score is not None and absent_score.dtype != torch.float64):
+        raise TypeError("%s: score and absent_score are float64" % what)
+    _args.on_device((score,) + (() if absent_score is None else (absent_score,)), "horizons", "draw", entry)
+    dev = score.device
+    total, S = score.shape
+    L, SA = ptr.size - 1, S + (absent_score is not None)
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(draw_state=torch.empty((R, total), dtype=torch.int32, device=dev), filtered=torch.empty((total, SA), **f64),
+               scale=torch.empty(total, **f64))
+    if L > 0 and total > 0:
+        t_key = None if key is None else torch.as_tensor(key).to(dev)
+        _lib.call(entry, dev, L, torch.as_tensor(ptr).to(dev), total, int(np.diff(ptr).max()), S, dz, score.contiguous(),
+                  None if absent_score is None else absent_score.contiguous(), torch.as_tensor(g).to(dev), torch.as_tensor(d).to(dev), switch, t_key,
+                  seed, R, out["filtered"], out["scale"], out["draw_state"])
+    return out
+
+
+def draw_log_scores(draw_state, ptr, score, absent_score, g, d, dz, switch):
+    """The log score of every drawn path on the scale of ``track``'s ``log_score``, f64 [R, L] on the device: per sequence the node
+    terms score[n, x_n] (absent_score[n] for the absent state) summed over its soundings, minus the pair costs of its steps --
+    g[n] |d[n] - (x_{n+1} - x_n) dz| between cells, ``switch`` between a cell and absent, 0 between absent and absent.  With the
+    chain's ``log_partition``, ``draw_log_score - log_partition`` is the path's log probability.  Plain torch."""
+    dev, (total, S) = score.device, score.shape
+    x = draw_state.long()
+    theta = score if absent_score is None else torch.cat([score, absent_score.reshape(-1, 1)], dim=1)
+    node = theta[torch.arange(total, device=dev)[None, :], x]
+    t_g, t_d = torch.as_tensor(g, dtype=torch.float64).to(dev), torch.as_tensor(d, dtype=torch.float64).to(dev)
+    out = torch.zeros((x.shape[0], len(ptr) - 1), dtype=torch.float64, device=dev)
+    for l in range(len(ptr) - 1):
+        a, b = int(ptr[l]), int(ptr[l + 1])
+        if b <= a:
+            continue
+        xa, xb = x[:, a:b - 1], x[:, a + 1:b]
+        cost = torch.where((xa < S) & (xb < S), t_g[None, a:b - 1] * torch.abs(t_d[None, a:b - 1] - (xb - xa).to(torch.float64) * dz),
+                           torch.where((xa >= S) & (xb >= S), torch.zeros((), dtype=torch.float64, device=dev),
+                                       torch.full((), float(switch), dtype=torch.float64, device=dev)))
+        out[:, l] = node[:, a:b].sum(dim=1) - cost.sum(dim=1)
+    return out
+
+
+def _draw_cells(draw_cell, n_depth, what):
+    c = torch.as_tensor(draw_cell)
+    if c.ndim != 2 or c.dtype.is_floating_point or c.dtype == torch.bool:
+        raise ValueError("%s: draw_cell must hold integers [R, N]" % what)
+    if c.numel() and (int(c.min()) < -1 or (n_depth is not None and int(c.max()) >= n_depth)):
+        raise ValueError("%s: every entry of draw_cell must be -1 (absent) or a cell of the depth axis" % what)
+    return c.long()
+
+
+def _summary_arguments(draw_cell, depth_edges, x, y, ptr, weights, what):
+    """The checked arguments of ``draw_summary`` and its reference: cells [R, N] (long), centres, widths (numpy [N]) and ptr."""
+    from . import sections
+    edges, _ = check_depth_edges(depth_edges)
+    c = _draw_cells(draw_cell, edges.size - 1, what)
+    N = c.shape[1]
+    ptr = _args.check_ptr([0, N] if ptr is None else ptr, N, "horizons", empty=True)
+    if weights is None:
+        if np.size(x) != N or np.size(y) != N:
+            raise ValueError("%s: x and y must hold one entry per sounding (%d)" % (what, N))
+        width = sections.section_widths(x, y, ptr)
+    else:
+        width = np.asarray(_args.host(weights), dtype=np.float64).reshape(-1)
+        if width.size != N or not np.all(np.isfinite(width)) or np.any(width < 0.0):
+            raise ValueError("%s: weights must hold one finite non-negative weight per sounding (%d)" % (what, N))
+    return c, 0.5 * (edges[1:] + edges[:-1]), width, ptr
+
+
+def draw_summary_reference(draw_cell, depth_edges, x, y, ptr=None, weights=None):
+    """The rule of ``draw_summary`` in numpy loops: float64 [R, L] each."""
+    c, centres, width, ptr = _summary_arguments(draw_cell, depth_edges, x, y, ptr, weights, "horizons.draw_summary_reference")
+    c = c.cpu().numpy()
+    R, L = c.shape[0], ptr.size - 1
+    out = {k: np.zeros((R, L)) for k in ("present_length", "area_above", "longest_gap")}
+    for r in range(R):
+        for l in range(L):
+            run = 0.0
+            for n in range(int(ptr[l]), int(ptr[l + 1])):
+                if c[r, n] >= 0:
+                    out["present_length"][r, l] += width[n]
+                    out["area_above"][r, l] += width[n] * centres[c[r, n]]
+                    run = 0.0
+                else:
+                    run += width[n]
+                    out["longest_gap"][r, l] = max(out["longest_gap"][r, l], run)
+    return out
+
+
+def draw_summary(draw_cell, depth_edges, x, y, ptr=None, weights=None):
+    """What joint draws are for: per realisation and sequence of ``ptr`` [L + 1] (None: one sequence) of ``draw_cell`` int [R, N]
+    (``track(draws=...)``; index on the axis ``depth_edges``, -1: absent), float64 [R, L] on the draws' device,
+    ``present_length`` (m): the summed ``sections.section_widths`` of the soundings where the horizon is present,
+    ``area_above`` (m^2): sum of width * depth (cell centre) over the present soundings -- the cross-section above the horizon,
+    ``longest_gap`` (m): the largest summed width of a run of absent soundings.
+    With ``weights`` [N] (for example ``bodies.sounding_areas(plan)``, m^2) in place of the widths and one sequence, ``area_above`` is the
+    volume above the surface (and the other two are areas).  Plain torch; ``draw_summary_reference`` states it in numpy loops."""
+    c, centres, width, ptr = _summary_arguments(draw_cell, depth_edges, x, y, ptr, weights, "horizons.draw_summary")
+    dev = c.device
+    w = torch.as_tensor(width).to(dev)
+    depth = torch.as_tensor(centres).to(dev)[c.clamp(min=0)]
+    here = c >= 0
+    R, L = c.shape[0], ptr.size - 1
+    out = {k: torch.zeros((R, L), dtype=torch.float64, device=dev) for k in ("present_length", "area_above", "longest_gap")}
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for l in range(L):
+        a, b = int(ptr[l]), int(ptr[l + 1])
+        if b <= a:
+            continue
+        h, wl = here[:, a:b], w[None, a:b]
+        out["present_length"][:, l] = torch.where(h, wl, zero).sum(dim=1)
+        out["area_above"][:, l] = torch.where(h, wl * depth[:, a:b], zero).sum(dim=1)
+        gone = torch.cumsum(torch.where(h, zero, wl).expand(R, b - a), dim=1)   # the absent width so far; a run is its growth since the
+        base = torch.cummax(torch.where(h, gone, zero), dim=1).values           # last present sounding (the sum never decreases)
+        out["longest_gap"][:, l] = (gone - base).max(dim=1).values
+    return out
+
+
+def connected(draw_cell, a, b):
+    """The share of the realisations ``draw_cell`` int [R, N] (-1: absent) in which the horizon is present under every sounding from
+    ``a`` to ``b`` (both included): the posterior probability of "no gap from a to b", which no product of marginals gives."""
+    c = _draw_cells(draw_cell, None, "horizons.connected")
+    N = c.shape[1]
+    a, b = _args.check_int(a, 0, N - 1, "horizons.connected: a"), _args.check_int(b, 0, N - 1, "horizons.connected: b")
+    lo, hi = min(a, b), max(a, b)
+    return float((c[:, lo:hi + 1] >= 0).all(dim=1).to(torch.float64).mean())
+
+
 def percentile_cells(marginal_cells, p):
     """The first cell at which the cumulated marginal over the CELLS (renormalised without the absent state) reaches ``p`` percent:
     int64 [N], and -1 where the cells hold no mass.  ``marginal_cells`` [N, S], torch."""
@@ -309,14 +574,25 @@ def _track_arguments(evidence, x, y, surface, absent, slope, switch, floor, ptr,
     return ptr, g, d, switch
 
 
-def _track_cells(evidence, absent, ptr, g, d, dz, switch, floor, marginals):
-    """Scores of the (already windowed) evidence and the launch; the outputs are in cells of the window."""
+def _check_draws(draws, seed, what):
+    from . import sections
+    return _args.check_int(draws, 0, MAX_DRAWS, "%s: draws" % what), sections._check_seed(seed)
+
+
+def _track_cells(evidence, absent, ptr, g, d, dz, switch, floor, marginals, draws=0, seed=0, row_key=None):
+    """Scores of the (already windowed) evidence and the launch; the outputs are in cells of the window.  With ``draws`` > 0 a second
+    launch (``draw``) adds ``draw_state`` int32 [R, sum N] and ``draw_log_score`` [R, L]; with 0 nothing else runs."""
     if evidence.shape[1] > MAX_STATES:
         raise ValueError("horizons.track: %d states, at most %d (choose a window with between=)" % (evidence.shape[1], MAX_STATES))
     if evidence.device.type != "cuda":
         raise _lib.NativeLibraryError("horizons.track runs on the device (gbp_horizon_track); there is no host fallback")
     score, absent_score = evidence_scores(evidence, absent, floor)
-    return _launch(score, absent_score, ptr, g, d, dz, switch, marginals)
+    raw = _launch(score, absent_score, ptr, g, d, dz, switch, marginals)
+    if draws:
+        score = score.contiguous()
+        state = draw(ptr, score, absent_score, g, d, dz, switch, draws, seed=seed, row_key=row_key)["draw_state"]
+        raw.update(draw_state=state, draw_log_score=draw_log_scores(state, ptr, score, absent_score, g, d, dz, switch))
+    return raw
 
 
 def _finish(raw, S, lo, edges, surface, percentiles):
@@ -339,6 +615,12 @@ def _finish(raw, S, lo, edges, surface, percentiles):
             out[percentile_name(p)] = torch.where(i < 0, nan, centres[(i + lo).clamp(min=0, max=centres.numel() - 1)])
         if "log_partition" in raw:                                             # (a chain's; the survey graph has none)
             out["log_partition"], out["scale"] = raw["log_partition"], raw["scale"]
+    if "draw_state" in raw:
+        x = raw["draw_state"]
+        gone = x >= S
+        depth = torch.where(gone, nan, centres[(x.long() + lo).clamp(max=centres.numel() - 1)])
+        out.update(draw_cell=torch.where(gone, torch.full_like(x, -1), x + lo), draw_depth=depth, draw_elevation=surf[None, :] - depth,
+                   draw_log_score=raw["draw_log_score"])
     return out
 
 
@@ -350,7 +632,7 @@ def check_percentiles(percentiles):
 
 
 def track(evidence, x, y, surface, depth_edges, absent=None, between=None, slope=0.05, switch=4.6, floor=1e-6, marginals=True,
-          percentiles=(5, 50, 95), ptr=None):
+          percentiles=(5, 50, 95), ptr=None, draws=0, seed=0):
     """Track one horizon per sequence through the ``evidence`` [sum N, n_depth] (a torch tensor on the device: non-negative weights on
     the cells of the uniform ``depth_edges`` [n_depth + 1]) of soundings at ``x``, ``y`` on ``surface`` [sum N] (host arrays; m).
     ``absent`` [sum N]: the weight of "no such horizon here" (None: no absent state).  ``between`` = (d0, d1): only the cells with
@@ -362,14 +644,20 @@ def track(evidence, x, y, surface, depth_edges, absent=None, between=None, slope
     ``elevation`` = surface - depth, ``log_score`` [L]; with ``marginals`` also ``marginal`` [sum N, S] over the window's cells,
     ``absent_probability`` [sum N], ``depth_percentile_<p>`` (centre of the first cell at which the cumulated marginal over the cells,
     renormalised without the absent state, reaches p; NaN without mass), ``log_partition`` [L] (the evidence of the chain) and
-    ``scale`` [sum N] (s_n, the evidence of sounding n given those before it)."""
+    ``scale`` [sum N] (s_n, the evidence of sounding n given those before it).
+
+    ``draws`` = R > 0 adds R joint realisations of every sequence's horizon (``draw``), drawn with ``seed`` and the row
+    index as the key: ``draw_cell`` int32 [R, sum N] (index on the full axis; -1: absent), ``draw_depth`` and ``draw_elevation``
+    [R, sum N] (NaN: absent) and ``draw_log_score`` [R, L] on the scale of ``log_score``, so that ``draw_log_score - log_partition`` is
+    a path's log probability.  With ``draws`` = 0 every other output keeps its bits and nothing else is launched."""
     ptr, g, d, switch = _track_arguments(evidence, x, y, surface, absent, slope, switch, floor, ptr)
+    draws, seed = _check_draws(draws, seed, "horizons.track")
     percentiles = check_percentiles(percentiles)
     edges, dz = check_depth_edges(depth_edges)
     if evidence.shape[1] != edges.size - 1:
         raise ValueError("horizons.track: evidence has %d depth cells, depth_edges %d" % (evidence.shape[1], edges.size - 1))
     lo, hi = window(edges, between)
-    raw = _track_cells(evidence[:, lo:hi], absent, ptr, g, d, dz, switch, floor, marginals)
+    raw = _track_cells(evidence[:, lo:hi], absent, ptr, g, d, dz, switch, floor, marginals, draws, seed)
     return _finish(raw, hi - lo, lo, edges, surface, percentiles)
 
 
@@ -382,6 +670,8 @@ def _stack(parts, between, percentiles):
                 out["marginal_%d" % h] = p[k]
         elif k in ("log_score", "log_partition"):
             out[k] = torch.cat([p[k].reshape(1) for p in parts])
+        elif k == "draw_log_score":
+            out[k] = torch.stack([p[k][:, 0] for p in parts])                  # [H, R]: every horizon is one sequence
         else:
             out[k] = torch.stack([p[k] for p in parts])
     if between is not None:
@@ -391,7 +681,9 @@ def _stack(parts, between, percentiles):
 
 def _split(res, h, N):
     """Sequence ``h`` of a launch of sequences of N soundings each."""
-    return {k: (v[h:h + 1] if k in ("log_score", "log_partition") else v[h * N:(h + 1) * N]) for k, v in res.items()}
+    cut = {"log_score": lambda v: v[h:h + 1], "log_partition": lambda v: v[h:h + 1], "draw_log_score": lambda v: v[:, h:h + 1],
+           "draw_state": lambda v: v[:, h * N:(h + 1) * N]}
+    return {k: cut.get(k, lambda v: v[h * N:(h + 1) * N])(v) for k, v in res.items()}
 
 
 def _read(path_or_products, container):
@@ -424,13 +716,16 @@ def _read(path_or_products, container):
 
 
 def from_products(path_or_products, between, container=None, x=None, y=None, surface=None, slope=0.05, switch=4.6, floor=1e-6,
-                  marginals=True, percentiles=(5, 50, 95), absent=False, device=None):
+                  marginals=True, percentiles=(5, 50, 95), absent=False, device=None, draws=0, seed=0):
     """One horizon per window of ``between`` = [(d0, d1), ...] through the ``interface_probability`` [N, n_depth] on
     ``interface_depth_edges`` of a results container (``<line>.h5``), of line products (a dict of ``line_products.from_results``) or
     of saved line products (``<line>.products.npz``); x, y and the surface elevation come from the ``container`` (with a container
     path as the first argument: that one) unless given.  ``absent`` = True adds the absent state with the weight of the probability
     mass outside the window.  The windows with equal cell counts run in one launch.  Returns the entries of ``track`` stacked
-    [H, N] (``log_score``, ``log_partition`` [H]), ``marginal_<h>`` [N, S_h] and ``between`` [H, 2], on ``device`` (default cuda:0)."""
+    [H, N] (``log_score``, ``log_partition`` [H]), ``marginal_<h>`` [N, S_h] and ``between`` [H, 2], on ``device`` (default cuda:0).
+    ``draws`` = R > 0 adds ``draw_cell``, ``draw_depth``, ``draw_elevation`` [H, R, N] and ``draw_log_score`` [H, R] (``track``); the key
+    of sounding n under window h is n + h N, so two horizons of one sounding never share a uniform, and a window keeps its draws
+    whichever other windows are asked for before it."""
     prob, edges, cx, cy, cs = _read(path_or_products, container)
     x, y, surface = (cx if x is None else x), (cy if y is None else y), (cs if surface is None else surface)
     if x is None or y is None or surface is None:
@@ -440,6 +735,7 @@ def from_products(path_or_products, between, container=None, x=None, y=None, sur
         raise ValueError("horizons.from_products: at least one window (d0, d1) is needed")
     edges, dz = check_depth_edges(edges)
     percentiles = check_percentiles(percentiles)
+    draws, seed = _check_draws(draws, seed, "horizons.from_products")
     N = prob.shape[0]
     if prob.ndim != 2 or prob.shape[1] != edges.size - 1:
         raise ValueError("horizons.from_products: interface_probability %r does not match its %d depth cells" % (prob.shape, edges.size - 1))
@@ -453,7 +749,8 @@ def from_products(path_or_products, between, container=None, x=None, y=None, sur
         ab = torch.cat([e.sum(1) - e[:, ranges[h][0]:ranges[h][1]].sum(1) for h in hs]).clamp(min=0.0) if absent else None
         tile = lambda a: np.tile(np.asarray(a, dtype=np.float64).reshape(-1), len(hs))       # noqa: E731
         ptr, g, d, sw = _track_arguments(ev, tile(x), tile(y), tile(surface), ab, slope, switch, floor, np.arange(len(hs) + 1) * N)
-        raw = _track_cells(ev, ab, ptr, g, d, dz, sw, floor, marginals)
+        key = np.concatenate([np.arange(N, dtype=np.int64) + h * N for h in hs]) if draws else None
+        raw = _track_cells(ev, ab, ptr, g, d, dz, sw, floor, marginals, draws, seed, key)
         for i, h in enumerate(hs):
             parts[h] = _finish(_split(raw, i, N), S, ranges[h][0], edges, surface, percentiles)
     return _stack(parts, wins, percentiles)
@@ -932,13 +1229,208 @@ def graph_path(eu, ev, g, d, dz, switch, score, absent_score=None, sweeps=32, da
                 candidate_log_score=ls, chosen=chosen, refine_moves=moves)
 
 
+def _check_graph_draw(eu, ev, g, d, dz, switch, score, absent_score, ptr, n_draws, seed, sweeps, row_key, state, first_sweep, what):
+    """The host checks ``graph_draw`` and its reference share (shapes, dtypes, values).  Returns eu, ev, g, d, dz, switch, ptr,
+    step_edge, cross, R, seed, sweeps, first_sweep, the keys (int64 [N]) and the states to continue from (int32 [R, N] or None)."""
+    from . import sections
+    eu, ev, g, d, dz, switch = _check_graph(eu, ev, g, d, dz, switch, score, absent_score, what)
+    N, SA = score.shape[0], score.shape[1] + (absent_score is not None)
+    ptr, step_edge, cross = sections.check_lines(eu, ev, ptr, N, what)
+    R = _args.check_int(n_draws, 1, MAX_DRAWS, "%s: n_draws" % what)
+    seed = sections._check_seed(seed)
+    sweeps = _args.check_int(sweeps, 0, sections.MAX_DRAW_SWEEPS, "%s: sweeps" % what)
+    first_sweep = _args.check_int(first_sweep, 0, sweeps, "%s: first_sweep (at most sweeps)" % what)
+    key = sections._check_row_key(row_key, N, what)
+    if (state is None) != (first_sweep == 0):
+        raise ValueError("%s: state holds the states to continue from: it goes with first_sweep > 0, and only with it" % what)
+    if state is not None:
+        state, single = _check_states(state, N, SA, MAX_DRAWS, what, "state")
+        if single or state.shape[0] != R:
+            raise ValueError("%s: state must hold one integer per realisation and sounding [%d, %d]" % (what, R, N))
+    return eu, ev, g, d, dz, switch, ptr, step_edge, cross, R, seed, sweeps, first_sweep, key, state
+
+
+def graph_draw_reference(eu, ev, g, d, dz, switch, score, absent_score, ptr, n_draws, seed=0, sweeps=8, row_key=None, state=None, first_sweep=0,
+                         dtype=np.float64):
+    """The rule of ``graph_draw`` in numpy, evaluated in ``dtype``: R joint realisations of the horizon on the whole graph of
+    ``propagate_reference`` by Gibbs sampling blocked by flight line, with the structure of ``sections.graph_draw_reference``
+    (DESIGN.md 3.34).  The graph as there; ``ptr`` [L + 1]: the sequences (lines) in the same numbering, contiguous, possibly empty.
+
+    Edges (``sections.check_lines``): an edge with ev = eu + 1 inside one sequence is a step, every other edge must join two different
+    sequences, a cross edge; anything else is refused.  Colours: ``sections.line_colours``; cross CSRs: ``sections.cross_incoming``,
+    neighbours ascending.
+    Sweep 0, the start: ``draw_reference`` with the step edges' (g, d), cross edges ignored.
+    Sweep t = 1 .. T: colours ascending; for every sequence of the colour and every realisation the same filter and walk with w' in
+    place of w.  For each cross edge e of s in CSR order w'_s[i] is w_s[i] times the pair factor at the neighbour's current state x_q:
+    exp(-(g_e * |d_e - k * dz|)) between cells, k = x_q - i for s = eu[e] and k = i - x_q for s = ev[e] (the orientation of
+    ``_edge_tables`` / ``_cost_to``); ks between a cell and absent; absent-absent applies no multiply; the multiplies left to right.
+    The step along the line uses the step edge's (g, d).  States are replaced in place.  u = ``sections.philox_uniform(seed, rho,
+    row_key[s], sweep=t)``.  ``first_sweep`` > 0 continues from ``state`` int32 [R, N] and runs the sweeps first_sweep .. T.
+    A draw depends on the seed, the realisation, the row key and the sweep -- not on R, on how realisations are cut into blocks or
+    on a launch shape.  T = 8 is a convention, as in DESIGN.md 3.29, not a measured mixing time.
+
+    Returns ``draw_state`` int32 [R, N] (S: absent), ``filtered`` [R, N, SA] (the alpha of the last sweep in which each sounding was
+    drawn) and ``margin`` [R, N], the minimum over the sweeps run (the start's is its sequence's)."""
+    from . import sections
+    what = "horizons.graph_draw_reference"
+    ft = np.dtype(dtype).type
+    score = np.asarray(score, dtype=np.float64)
+    has_absent = absent_score is not None
+    absent_score = np.asarray(absent_score, dtype=np.float64).reshape(-1) if has_absent else None
+    eu, ev, g, d, dz, switch, ptr, step_edge, cross, R, seed, T, first, key, state = _check_graph_draw(
+        eu, ev, g, d, dz, switch, score, absent_score, ptr, n_draws, seed, sweeps, row_key, state, first_sweep, what)
+    theta = _theta_reference(score, absent_score, what).astype(ft)
+    N, SA = theta.shape
+    S = score.shape[1]
+    X = np.zeros((R, N), dtype=np.int32) if state is None else state.copy()
+    filtered, margin = np.zeros((R, N, SA), dtype=ft), np.full((R, N), np.inf, dtype=ft)
+    if first == 0:                                                            # the start: the chains of the steps alone
+        has = step_edge >= 0
+        gc, dc = np.ones(N), np.zeros(N)
+        gc[has], dc[has] = g[step_edge[has]], d[step_edge[has]]
+        start = draw_reference(ptr, score, absent_score, gc, dc, dz, switch, R, seed=seed, row_key=key, dtype=dtype)
+        X[:], filtered[:] = start["draw_state"], start["filtered"][None, :, :]
+        for l in range(ptr.size - 1):
+            margin[:, ptr[l]:ptr[l + 1]] = start["margin"][:, l:l + 1]
+    if T < max(first, 1):
+        return dict(draw_state=X, filtered=filtered, margin=margin)
+    g, d, dz, switch = g.astype(ft), d.astype(ft), ft(dz), ft(switch)
+    kf = np.arange(-(S - 1), S).astype(ft)
+    rho, cells = np.arange(R, dtype=np.int64), np.arange(S, dtype=np.int64)
+    cross_ptr, cross_edge = sections.cross_incoming(eu, ev, cross, N)
+    colour, n_colours = sections.line_colours(eu, ev, ptr)
+    with np.errstate(invalid="ignore", divide="ignore", under="ignore"):
+        w, ks = np.exp(theta), np.exp(-switch)
+
+        def conditioned(s):
+            """w' [R, SA] under the current states."""
+            v = np.repeat(w[s][None, :], R, axis=0)
+            for dd in cross_edge[cross_ptr[s]:cross_ptr[s + 1]]:              # ascending neighbour
+                e, from_v = int(dd) >> 1, bool(dd & 1)
+                x = X[:, ev[e] if from_v else eu[e]].astype(np.int64)
+                k = (x[:, None] - cells[None, :]) if from_v else (cells[None, :] - x[:, None])
+                fac = np.ones((R, SA), dtype=ft)                              # (times 1: no multiply)
+                fac[:, :S] = np.where((x < S)[:, None], np.exp(-(g[e] * np.abs(d[e] - k.astype(ft) * dz))), ks)
+                if has_absent:
+                    fac[:, S] = np.where(x < S, ks, ft(1))
+                v = v * fac
+            return v
+
+        for t in range(max(first, 1), T + 1):
+            for c in range(n_colours):
+                for l in np.flatnonzero(colour == c):
+                    r0, n_l = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+                    if n_l == 0:
+                        continue
+                    alpha, Ks = [None] * n_l, []
+                    v = conditioned(r0)
+                    alpha[0] = v / v.sum(axis=1)[:, None]
+                    for n in range(n_l - 1):
+                        se = step_edge[r0 + n]
+                        K = np.exp(-(g[se] * np.abs(d[se] - kf * dz)))
+                        Ks.append(K)
+                        a = alpha[n]
+                        u = np.zeros((R, SA), dtype=ft)
+                        for i in range(S):                                   # c ascending
+                            u[:, :S] = u[:, :S] + a[:, i, None] * K[None, S - 1 - i:2 * S - 1 - i]
+                        if has_absent:
+                            u[:, :S] = u[:, :S] + (a[:, S] * ks)[:, None]
+                            u[:, S] = np.cumsum(a[:, :S] * ks, axis=1)[:, -1] + a[:, S]
+                        u = np.ascontiguousarray(conditioned(r0 + n + 1) * u)
+                        alpha[n + 1] = u / u.sum(axis=1)[:, None]
+                    j, new = None, np.zeros((R, n_l), dtype=np.int32)
+                    for n in range(n_l - 1, -1, -1):
+                        a = alpha[n]
+                        filtered[:, r0 + n] = a
+                        if n == n_l - 1:
+                            W = a
+                        else:
+                            Kx = np.append(Ks[n], ks)                        # the switch in slot 2 S - 1
+                            jc = j < S
+                            W = np.empty((R, SA), dtype=ft)
+                            W[:, :S] = a[:, :S] * Kx[np.where(jc[:, None], j[:, None] - cells[None, :] + (S - 1), 2 * S - 1)]
+                            if has_absent:
+                                W[:, S] = np.where(jc, a[:, S] * ks, a[:, S])
+                        cs = np.cumsum(np.ascontiguousarray(W), axis=1, dtype=ft)      # sequential, i ascending
+                        thr = sections.philox_uniform(seed, rho, key[r0 + n], sweep=t).astype(ft) * cs[:, -1]
+                        j = np.minimum((cs <= thr[:, None]).sum(axis=1), SA - 1)
+                        margin[:, r0 + n] = np.fmin(margin[:, r0 + n], np.abs(cs - thr[:, None]).min(axis=1) / cs[:, -1])
+                        new[:, n] = j
+                    X[:, r0:r0 + n_l] = new
+    return dict(draw_state=X, filtered=filtered, margin=margin)
+
+
+def graph_draw(eu, ev, g, d, dz, switch, score, absent_score, ptr, n_draws, seed=0, sweeps=8, row_key=None, state=None, first_sweep=0, block=None,
+               budget_bytes=4 << 30, trace=False, filtered=False):
+    """R joint realisations of the horizon on the whole survey graph on the device by Gibbs sampling blocked by flight line
+    (gbp_horizon_graph_draw: csrc/gbp_horizon_draw.h; ``graph_draw_reference`` states the rule and what its draws are).  ``score`` f64
+    [N, S] and ``absent_score`` f64 [N] or None on the device; ``eu``, ``ev``, ``g``, ``d`` as ``propagate`` takes them; ``ptr``
+    [L + 1] (host): the lines; ``n_draws`` = R in 1 .. 65536, ``seed`` a uint64, ``sweeps`` = T in 0 .. 65535 (8 is a convention, not
+    a measured mixing time), ``row_key`` int64 [N] (None: the index; several horizons of one survey: sounding index + horizon index
+    * N, so that two horizons of one sounding never share a uniform).  ``first_sweep`` > 0 continues from ``state`` int32 [R, N] (host
+    or device).  Realisations are independent chains whose random numbers depend on (seed, realisation, key, sweep): they are
+    processed in blocks of ``block`` (None: as many as keep the block's alpha, R_b N SA 8 bytes, under ``budget_bytes``), and the
+    blocking changes no draw.
+
+    Returns on the device ``draw_state`` int32 [R, N] (S: absent) and, with ``filtered``, ``filtered`` f64 [R, N, SA].  ``trace`` runs
+    sweep by sweep and adds ``log_score_trace`` f64 [T - first_sweep + 1, R] (``graph_log_score`` after every sweep that was run, the
+    start included) and ``change_share`` f64 [T - max(first_sweep, 1) + 1]: the share of (realisation, sounding) pairs whose state a
+    conditioned sweep changed.  There is no host fallback."""
+    from . import sections
+    entry, what = "gbp_horizon_graph_draw", "horizons.graph_draw"
+    _are_tensors(score, absent_score, "graph_draw", entry)
+    eu, ev, g, d, dz, switch, ptr, step_edge, cross, R, seed, T, first, key, state = _check_graph_draw(
+        eu, ev, g, d, dz, switch, score, absent_score, ptr, n_draws, seed, sweeps, row_key, state, first_sweep, what)
+    _args.check_block(block, what)
+    budget_bytes = _args.check_int(budget_bytes, 1, 2 ** 62, "%s: budget_bytes" % what)
+    theta, t_eu, t_ev, t_g, t_d, _, _ = _device_graph(eu, ev, g, d, score, absent_score, "graph_draw", entry)
+    dev, (N, SA), E, L = theta.device, theta.shape, eu.size, ptr.size - 1
+    S, has_absent = score.shape[1], int(absent_score is not None)
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    per = int(block) if block is not None else max(1, min(R, budget_bytes // max(1, N * SA * 8)))
+    per = min(per, R)
+    out = dict(draw_state=torch.zeros((R, N), **i32) if state is None else torch.as_tensor(state).to(dev).contiguous())
+    alpha = torch.zeros((R if filtered else per, N, SA), **f64)
+    if filtered:
+        out["filtered"] = alpha
+    run_first = max(first, 1)
+    if trace:
+        out.update(log_score_trace=torch.zeros((T - first + 1, R), **f64), change_share=torch.zeros(max(T - run_first + 1, 0), **f64))
+    if N == 0:
+        return out
+    colour, n_colours = sections.line_colours(eu, ev, ptr)
+    order = np.argsort(colour, kind="stable")
+    colour_ptr = np.concatenate([[0], np.cumsum(np.bincount(colour, minlength=n_colours))])
+    cross_ptr, cross_edge = sections.cross_incoming(eu, ev, cross, N)
+    to = lambda a, t=np.int32: torch.as_tensor(np.ascontiguousarray(a, dtype=t)).to(dev)      # noqa: E731
+    t_step, t_cptr, t_colptr, t_colline = (to(a) for a in (step_edge, cross_ptr, colour_ptr, order))
+    t_cedge = to(np.concatenate([cross_edge, [-1]]))                           # (never empty: the entry refuses a NULL pointer)
+    t_ptr, t_key = to(ptr, np.int64), None if row_key is None else to(key, np.int64)
+    scale = torch.empty((per, N), **f64)
+    X = out["draw_state"]
+    for a, b in ([(t, t) for t in range(first, T + 1)] if trace else [(first, T)]):
+        before = X.clone() if trace and a >= 1 else None
+        for r0 in range(0, R, per):
+            r1 = min(R, r0 + per)
+            _lib.call(entry, dev, N, E, S, has_absent, dz, switch, t_eu, t_ev, theta, t_g, t_d, L, t_ptr, t_step, t_cptr, t_cedge, n_colours, t_colptr,
+                      t_colline, t_key, seed, r1 - r0, r0, a, b, alpha[r0:r1] if filtered else alpha[:r1 - r0], scale, X[r0:r1])
+            if filtered and b == 0:                                           # the start alone: its one alpha serves every realisation
+                alpha[r0:r1] = alpha[r0].clone()[None]
+        if trace:
+            out["log_score_trace"][a - first] = torch.as_tensor(np.atleast_1d(graph_log_score(X, eu, ev, g, d, dz, switch, score, absent_score))).to(dev)
+            if before is not None:
+                out["change_share"][a - run_first] = (X != before).double().mean()
+    return out
+
+
 def message_bytes(n_edges, n_states):
     """The bytes of the two message buffers [2, 2 E, SA] of float64 a graph launch holds."""
     return 2 * 2 * int(n_edges) * int(n_states) * 8
 
 
 def spatial(evidence, x, y, surface, depth_edges, *, max_distance, ptr=None, absent=None, between=None, slope=0.05, switch=4.6, floor=1e-6,
-            sweeps=32, damping=0.0, path=True, percentiles=(5, 50, 95), message_budget_bytes=8 << 30):
+            sweeps=32, damping=0.0, path=True, percentiles=(5, 50, 95), message_budget_bytes=8 << 30, draws=0, seed=0, draw_sweeps=8,
+            row_key=None):
     """One horizon over the whole survey: the arguments of ``track`` -- ``evidence`` [N, n_depth] on the device, ``x``, ``y``,
     ``surface`` [N] on the host, the lines as ``ptr`` [L + 1] -- on the survey graph of ``sections.neighbours(x, y, ptr,
     max_distance=...)`` (``max_distance`` is required, about 1.5 line spacings; its ``g`` is discarded for ``graph_steps``).  The
@@ -953,9 +1445,19 @@ def spatial(evidence, x, y, surface, depth_edges, *, max_distance, ptr=None, abs
     ``edge_v``, ``edge_length``; and with ``path`` ``path_margin`` f64 [N] (the gap between the two largest max-marginals; inf with one
     state), ``path_residual`` [sweeps], ``path_candidate_log_score`` [3] (the refined decode, belief maxima and line picks) and
     ``path_chosen``.  The two message buffers hold 2 * 2 E * SA doubles; beyond ``message_budget_bytes`` (8 GiB by default: a
-    convention, not a property of the device) a ValueError asks for a narrower window ``between=``."""
+    convention, not a property of the device) a ValueError asks for a narrower window ``between=``.
+
+    ``draws`` = R > 0 adds R joint realisations of the surface on the graph (``graph_draw`` with ``seed``, ``draw_sweeps`` = T sweeps
+    -- 8 is a convention, as in DESIGN.md 3.29, not a measured mixing time -- and ``row_key``; None: the sounding index; for several
+    horizons of one survey sounding index + horizon index * N): ``draw_cell`` int32 [R, N] (full axis; -1: absent), ``draw_depth``,
+    ``draw_elevation`` [R, N] (NaN: absent), ``draw_log_score`` [R] (``graph_log_score`` of every realisation), ``draw_share``
+    [N, SA] (the share of the realisations in every state, the absent one last: to be read against ``marginal`` /
+    ``absent_probability``) and ``draw_change_share`` [T] (the share of states every sweep changed).  With ``draws`` = 0 every other
+    output keeps its bits and nothing else is launched."""
     from . import sections
     ptr, g_line, d_line, switch = _track_arguments(evidence, x, y, surface, absent, slope, switch, floor, ptr)
+    draws, seed = _check_draws(draws, seed, "horizons.spatial")
+    draw_sweeps = _args.check_int(draw_sweeps, 0, sections.MAX_DRAW_SWEEPS, "horizons.spatial: draw_sweeps")
     sweeps, damping = _check_sweeps(sweeps, damping, "horizons.spatial")
     percentiles = check_percentiles(percentiles)
     edges, dz = check_depth_edges(depth_edges)
@@ -990,7 +1492,15 @@ def spatial(evidence, x, y, surface, depth_edges, *, max_distance, ptr=None, abs
     else:
         state, log_score = found["state"], graph_log_score(found["state"], *args)
     f64 = lambda v: torch.tensor(float(v), dtype=torch.float64, device=dev)    # noqa: E731
-    out = _finish(dict(cell=state, log_score=f64(log_score), marginal=found["belief"]), S, lo, edges, surface, percentiles)
+    raw = dict(cell=state, log_score=f64(log_score), marginal=found["belief"])
+    if draws:
+        drawn = graph_draw(*args, ptr, draws, seed=seed, sweeps=draw_sweeps, row_key=row_key, trace=True)
+        X = drawn["draw_state"]
+        count = torch.zeros((N, SA), dtype=torch.float64, device=dev).scatter_add_(1, X.long().T.contiguous(),
+                                                                                   torch.ones((N, draws), dtype=torch.float64, device=dev))
+        raw.update(draw_state=X, draw_log_score=drawn["log_score_trace"][-1])
+        extra.update(draw_share=count / draws, draw_change_share=drawn["change_share"])
+    out = _finish(raw, S, lo, edges, surface, percentiles)
     full_axis = lambda c: torch.where(c >= S, torch.full_like(c, -1), c + lo)  # noqa: E731
     out.update(belief_cell=full_axis(found["state"]), state_log_score=f64(graph_log_score(found["state"], *args)), residual=found["residual"],
                line_cell=full_axis(alone), edge_u=eu.astype(np.int32), edge_v=ev.astype(np.int32), edge_length=dist, **extra)
@@ -998,13 +1508,15 @@ def spatial(evidence, x, y, surface, depth_edges, *, max_distance, ptr=None, abs
 
 
 def spatial_from_products(paths, between, max_distance, slope=0.05, switch=4.6, floor=1e-6, sweeps=32, damping=0.0, path=True,
-                          percentiles=(5, 50, 95), absent=False, device=None, message_budget_bytes=8 << 30):
+                          percentiles=(5, 50, 95), absent=False, device=None, message_budget_bytes=8 << 30, draws=0, seed=0, draw_sweeps=8):
     """``spatial`` for results containers (or saved line products with x, y and the surface beside them: what ``from_products`` reads):
     all ``paths`` given form ONE graph, every container a line, and one horizon is sought per window of ``between`` = [(d0, d1), ...].
     The containers must share their ``interface_depth_edges``.  The windows run one after the other (each has its own state count
     and its own graph launch).  Returns the entries of ``spatial`` stacked [H, N] (``log_score``, ``state_log_score``, ``path_chosen``
     [H]; ``residual``, ``path_residual``, ``path_candidate_log_score`` [H, ..]), ``marginal_<h>`` [N, S_h], ``between`` [H, 2], the
-    graph's ``edge_u``, ``edge_v``, ``edge_length`` once, and ``ptr`` [L + 1], the containers' ranges of soundings."""
+    graph's ``edge_u``, ``edge_v``, ``edge_length`` once, and ``ptr`` [L + 1], the containers' ranges of soundings.  ``draws`` = R > 0
+    adds the draws of ``spatial`` -- ``draw_cell``, ``draw_depth``, ``draw_elevation`` [H, R, N], ``draw_log_score`` [H, R],
+    ``draw_change_share`` [H, T] and ``draw_share_<h>`` [N, SA_h] -- with the row key sounding index + h * N for window h."""
     paths = [paths] if isinstance(paths, (str, bytes, os.PathLike, dict)) else list(paths)
     if not paths:
         raise ValueError("horizons.spatial_from_products: at least one container is needed")
@@ -1030,12 +1542,14 @@ def spatial_from_products(paths, between, max_distance, slope=0.05, switch=4.6, 
         lo, hi = window(edges, w)
         ab = (e.sum(1) - e[:, lo:hi].sum(1)).clamp(min=0.0) if absent else None
         parts.append(spatial(e, x, y, surface, edges, max_distance=max_distance, ptr=ptr, absent=ab, between=w, slope=slope, switch=switch, floor=floor,
-                             sweeps=sweeps, damping=damping, path=path, percentiles=percentiles, message_budget_bytes=message_budget_bytes))
+                             sweeps=sweeps, damping=damping, path=path, percentiles=percentiles, message_budget_bytes=message_budget_bytes,
+                             draws=draws, seed=seed, draw_sweeps=draw_sweeps,
+                             row_key=np.arange(x.size, dtype=np.int64) + len(parts) * x.size if draws else None))
     out = {}
     for k in parts[0]:
-        if k == "marginal":
+        if k in ("marginal", "draw_share"):
             for h, p in enumerate(parts):
-                out["marginal_%d" % h] = p[k]
+                out["%s_%d" % (k, h)] = p[k]
         elif k in ("edge_u", "edge_v", "edge_length"):
             out[k] = parts[0][k]
         else:
@@ -1069,6 +1583,13 @@ def parser():
     ap.add_argument("--sweeps", type=int, default=32, help="with --spatial: synchronous sweeps of message passing (default 32)")
     ap.add_argument("--damping", type=float, default=0.0, help="with --spatial: damping of the messages in [0, 1) (default 0)")
     ap.add_argument("--no-path", action="store_true", help="with --spatial: the picks are the beliefs' first maxima, not the max-sum path")
+    ap.add_argument("--draws", type=int, default=0, metavar="R",
+                    help="also draw R joint realisations of every horizon (draw_cell, draw_depth, draw_elevation, draw_log_score): every line "
+                         "alone, or with --spatial on the survey graph")
+    ap.add_argument("--seed", type=int, default=0, help="with --draws: the seed of the realisations (default 0)")
+    ap.add_argument("--draw-sweeps", type=int, default=None, metavar="T",
+                    help="with --spatial and --draws: sweeps of the line-blocked Gibbs sampler after the line-alone start (default 8: a "
+                         "convention, not a measured mixing time)")
     return ap
 
 
@@ -1090,6 +1611,16 @@ def parse_args(argv=None):
         ap.error("--sweeps must lie in 1 .. %d" % MAX_SWEEPS)
     if not 0.0 <= a.damping < 1.0:
         ap.error("--damping must lie in [0, 1)")
+    if not 0 <= a.draws <= MAX_DRAWS:
+        ap.error("--draws must lie in 0 .. %d" % MAX_DRAWS)
+    if not 0 <= a.seed < 2 ** 64:
+        ap.error("--seed must lie in 0 .. 2^64 - 1")
+    if a.seed != 0 and a.draws == 0:
+        ap.error("--seed needs --draws R")
+    if a.draw_sweeps is not None and (a.spatial is None or a.draws == 0):
+        ap.error("--draw-sweeps needs --spatial MAX_DISTANCE and --draws R (along a line alone a draw is exact: there are no sweeps)")
+    if a.draw_sweeps is not None and not 0 <= a.draw_sweeps <= 65535:
+        ap.error("--draw-sweeps must lie in 0 .. 65535")
     return a
 
 
@@ -1099,14 +1630,15 @@ def main(argv=None):
     if a.spatial is not None:
         found = [c for path in a.paths for c in containers(path)]
         r = spatial_from_products(found, a.between, a.spatial, slope=a.slope, switch=a.switch, sweeps=a.sweeps, damping=a.damping, path=not a.no_path,
-                                  absent=a.absent, device=a.device)
+                                  absent=a.absent, device=a.device, draws=a.draws, seed=a.seed, draw_sweeps=8 if a.draw_sweeps is None else a.draw_sweeps)
         written = [save(r, os.path.join(os.path.dirname(os.path.abspath(found[0])), SURVEY_OUTPUT))]
         print(written[0])
         return written
     written = []
     for path in a.paths:
         for c in containers(path):
-            r = from_products(c, a.between, slope=a.slope, switch=a.switch, marginals=not a.no_marginals, absent=a.absent, device=a.device)
+            r = from_products(c, a.between, slope=a.slope, switch=a.switch, marginals=not a.no_marginals, absent=a.absent, device=a.device,
+                              draws=a.draws, seed=a.seed)
             written.append(save(r, output_path(c)))
             print(written[-1])
     return written

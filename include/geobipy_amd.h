@@ -1225,6 +1225,58 @@ gbp_status gbp_horizon_graph_refine(int N, int E, int S, int has_absent, double 
                                     const int32_t *in_edge, int n_colours, const int32_t *colour_ptr, const int32_t *colour_node,
                                     int refine, int32_t *state, int32_t *moves, void *stream);
 
+/* Joint draws of horizons along lines from the chain of gbp_horizon_track by forward filtering and backward sampling
+ * (csrc/gbp_horizon_draw.h k_horizon_filter, k_horizon_walk; the rule is stated in numpy as horizons.draw_reference).
+ * L, ptr, total_n, max_n, S, dz, score, absent_score (NULL: no absent state), g, d, switch_cost as gbp_horizon_track takes them, with
+ * one difference: a sequence may be empty (ptr repeated; nothing is written for it).  n_states = S + 1 with absent_score, else S.
+ *   Filter: the forward half of the marginals of gbp_horizon_track, operation for operation: filtered f64 [total_n, n_states] =
+ *   alpha_n (the absent state last), scale [total_n] = s_n.
+ *   Walk: realisation rho = 0 .. n_draws - 1 walks n = last .. first of every sequence over the states i = 0 .. n_states - 1, cells
+ *   ascending and absent last; j is the state just drawn under n + 1.  W[i] = alpha_n[i] at the sequence's last row; elsewhere
+ *   alpha_n[i] * K_n[j - i] for cells i and j, alpha_n[i] * ks for a cell i and j absent, alpha_n[S] * ks for i absent and a cell j,
+ *   alpha_n[S] (no multiply) for both absent.  c[i] = c[i - 1] + W[i], i ascending; thr = u * c[n_states - 1]; the state is
+ *   min(#{i : c[i] <= thr}, n_states - 1): a state of weight 0 is never drawn, and with a NaN total the state is 0.  u = u53(x, y) of
+ *   Philox4x32-10 with key seed and counter (rho, key & 0xFFFFFFFF, key >> 32, 0), key = row_key[n] (int64 [total_n]; NULL: n): the
+ *   counter layout of gbp_section_draw.  A draw depends on the seed, the realisation and the row's key, not on n_draws nor on how
+ *   sequences are grouped into launches.  draw_state int32 [n_draws, total_n], S meaning absent.  The device's exp is not numpy's to
+ *   the last bit: a draw whose threshold lies within rounding of a c[i] may fall either way, and the walk differs from there.
+ * One 256-thread workgroup per sequence for the filter, LDS (4 S + 6) doubles; one 256-thread workgroup per (sequence, 256
+ * realisations) for the walk, lane = realisation, LDS (3 S + 1) doubles.  No atomics: a call repeats its bits.
+ * GBP_ERR_INVALID_ARG, before any launch: L < 0, S < 1 or S > 2048, n_draws < 1 or > 65536, dz not positive, switch_cost negative or
+ * not finite, total_n < 0, max_n > total_n, L * max_n < total_n, total_n * (S + 1) or n_draws * total_n out of range, a NULL ptr /
+ * score / g / d / filtered / scale / draw_state.  L == 0 or total_n == 0 launches nothing. */
+gbp_status gbp_horizon_draw(int L, const int64_t *ptr, int64_t total_n, int max_n, int S, double dz, const double *score,
+                            const double *absent_score, const double *g, const double *d, double switch_cost, const int64_t *row_key,
+                            uint64_t seed, int n_draws, double *filtered, double *scale, int32_t *draw_state, void *stream);
+
+/* Joint draws of horizons across lines: Gibbs sampling blocked by flight line on the graph of gbp_horizon_graph_propagate
+ * (csrc/gbp_horizon_draw.h k_horizon_filter<NJ, true>, k_horizon_walk<false>; the rule is stated in numpy as
+ * horizons.graph_draw_reference).  N, E, S, has_absent, dz, switch_cost, eu, ev, score [N, SA] (the absent state's column last), g,
+ * d [E] as gbp_horizon_graph_propagate takes them; L, ptr [L + 1] int64: the sequences (lines) in the same numbering, contiguous,
+ * possibly empty; step_edge int32 [N]: the edge of the step n -> n + 1 inside a sequence, -1 at its last sounding; cross_ptr
+ * [N + 1], cross_edge: the CSR of every sounding's incoming cross edges, ids 2 e (from eu[e]) and 2 e + 1 (from ev[e]), neighbours
+ * ascending; colour_ptr [n_colours + 1], colour_line [L]: the sequences grouped by colour, sequences of one colour sharing no edge.
+ *   Sweep 0 (only when first_sweep == 0): every sequence alone, gbp_horizon_draw's filter and walk with the step edges' (g, d).
+ *   Sweep t = max(first_sweep, 1) .. sweeps: colours ascending; for every sequence of the colour and realisation the same filter and
+ *   walk with w' in place of w: w'_s[i] = w_s[i] times, per cross edge of s in CSR order, exp(-(g_e * fabs(d_e - k * dz))) between
+ *   cells with k = x_q - i for s = eu[e] and i - x_q for s = ev[e], x_q the neighbour's current state (clamped into 0 .. SA - 1);
+ *   exp(-switch_cost) between a cell and absent; nothing between absent and absent.  States are replaced in place.
+ *   u = u53(x, y) of Philox4x32-10 with key seed and counter (first_draw + r, key & 0xFFFFFFFF, key >> 32, t), r the realisation
+ *   within the call, key = row_key[n] (NULL: n): cutting realisations into calls changes no draw.
+ * alpha f64 [n_draws, N, SA] (the filtered rows of the last sweep in which each sounding was drawn; after sweep 0 alone only slab 0 is
+ * written, shared by all realisations), scale f64 [n_draws, N], draw_state int32 [n_draws, N] (read when first_sweep > 0).
+ * An index that does not fit (edge, sounding, sequence, colour) is skipped, never followed.  No atomics: a call repeats its bits.
+ * GBP_ERR_INVALID_ARG, before any launch: the refusals of gbp_horizon_graph_propagate on N, E, S, has_absent, dz, switch_cost; L < 0,
+ * or L < 1 with N > 0; n_draws outside 1 .. 65536; first_draw + n_draws beyond 65536; sweeps outside first_sweep .. 65535; n_colours
+ * outside 1 .. L (the colour lists must cover the sequences); n_draws * N * SA, n_draws * N or L * n_draws out of range; NULL
+ * pointers (row_key may be NULL; eu, ev, g, d, cross_edge only with E > 0).  N == 0 launches nothing. */
+gbp_status gbp_horizon_graph_draw(int N, int E, int S, int has_absent, double dz, double switch_cost, const int32_t *eu,
+                                  const int32_t *ev, const double *score, const double *g, const double *d, int L, const int64_t *ptr,
+                                  const int32_t *step_edge, const int32_t *cross_ptr, const int32_t *cross_edge, int n_colours,
+                                  const int32_t *colour_ptr, const int32_t *colour_line, const int64_t *row_key, uint64_t seed,
+                                  int n_draws, int first_draw, int first_sweep, int sweeps, double *alpha, double *scale,
+                                  int32_t *draw_state, void *stream);
+
 /* Connected bodies of R realisations of a raster (csrc/gbp_bodies.h k_bodies_label; the rule is stated in numpy as
  * bodies.label_reference).  raster f64 [R, S, C]: S soundings, C cells each (depth or ONE elevation axis).  A cell is a member iff
  * lo <= v <= hi in fp64 (a NaN never is; +-inf bounds give one-sided thresholds).  Cells (s, c) and (s, c + 1) are adjacent, and
