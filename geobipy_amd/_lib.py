@@ -184,6 +184,8 @@ SIGNATURES = {
                                   ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
     "gbp_section_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 10 + [c_void_p]),
     "gbp_section_draw": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 5 + [ctypes.c_uint64, c_int] + [c_void_p] * 3 + [c_void_p]),
+    "gbp_section_evidence": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_void_p]),
+    "gbp_section_graph_evidence": (c_int, [c_int, c_int, c_int] + [c_void_p] * 12 + [c_void_p]),
     "gbp_section_propagate": (c_int, [c_int, c_int, c_int] + [c_void_p] * 8 + [c_int, ctypes.c_double] + [c_void_p] * 7 + [c_void_p]),
     "gbp_section_graph_draw": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p, ctypes.c_uint64, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p]),

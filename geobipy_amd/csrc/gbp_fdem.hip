@@ -2578,6 +2578,59 @@ extern "C" gbp_status gbp_section_draw(int L, const int64_t* ptr, int64_t total_
     }
 }
 
+#include "gbp_section_evidence.h"
+
+// The evidence of the lateral coupling (gbp_section_evidence.h): one launch, one workgroup per sequence, an instance per (columns a
+// thread owns, rungs).  Every refusal comes before any launch; ptr is not read on the host.
+namespace {
+
+template <int NJ, int T>
+gbp_status section_evidence_launch(int L, const int64_t* ptr, int n, const int32_t* n_used, const double* score, const double* g,
+                                   const double* d2, double* log_partition, double* dlog_partition, hipStream_t st)
+{
+    const size_t lds = section::evidence_lds_bytes(n, T);
+    if (lds > 48 * 1024) {                                                  // (above the default limit of a launch's dynamic LDS)
+        (void)hipFuncSetAttribute((const void*)section::k_section_evidence<NJ, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL((section::k_section_evidence<NJ, T>), dim3((unsigned)L), dim3(section::THREADS), lds, st, (const long long*)ptr, L, n,
+                       section::evidence_width(n), (const int*)n_used, score, g, d2, log_partition, dlog_partition);
+    GBP_HIP(hipGetLastError());
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" gbp_status gbp_section_evidence(int L, const int64_t* ptr, int64_t total_n, int n, const int32_t* n_used, const double* score,
+                                           const double* g, const double* d2, int T, double* log_partition, double* dlog_partition,
+                                           void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: L must be >= 0%s");
+    if (n < 1 || n > section::MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: n must lie in 1 .. 1024%s");
+    if (T < 1 || T > section::EVIDENCE_MAX_RUNGS) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: T must lie in 1 .. 8%s");
+    if (T * n > section::EVIDENCE_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: T * n must not exceed 2048%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < L) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: total_n does not fit L sequences of at least one sounding%s");
+    if (total_n > 0x7fffffffffffffffLL / 8 / n / n) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: total_n * n * n out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: ptr is NULL%s");
+    if (!n_used || !score || !g || !d2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: NULL pointer (n_used, score, g, d2)%s");
+    if (!log_partition || !dlog_partition)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: NULL pointer (log_partition, dlog_partition)%s");
+    hipStream_t st = (hipStream_t)stream;
+#define GBP_EVIDENCE_CASE(NJ_, T_)                                                                                                         \
+    case (NJ_) * 16 + (T_): return section_evidence_launch<NJ_, T_>(L, ptr, n, n_used, score, g, d2, log_partition, dlog_partition, st)
+    switch ((n + section::THREADS - 1) / section::THREADS * 16 + T) {       // T * n <= 2048 leaves these twenty
+        GBP_EVIDENCE_CASE(1, 1); GBP_EVIDENCE_CASE(1, 2); GBP_EVIDENCE_CASE(1, 3); GBP_EVIDENCE_CASE(1, 4);
+        GBP_EVIDENCE_CASE(1, 5); GBP_EVIDENCE_CASE(1, 6); GBP_EVIDENCE_CASE(1, 7); GBP_EVIDENCE_CASE(1, 8);
+        GBP_EVIDENCE_CASE(2, 1); GBP_EVIDENCE_CASE(2, 2); GBP_EVIDENCE_CASE(2, 3); GBP_EVIDENCE_CASE(2, 4);
+        GBP_EVIDENCE_CASE(2, 5); GBP_EVIDENCE_CASE(2, 6); GBP_EVIDENCE_CASE(2, 7);
+        GBP_EVIDENCE_CASE(3, 1); GBP_EVIDENCE_CASE(3, 2); GBP_EVIDENCE_CASE(3, 3);
+        GBP_EVIDENCE_CASE(4, 1); GBP_EVIDENCE_CASE(4, 2);
+        default: return fail(GBP_ERR_INVALID_ARG, "gbp_section_evidence: T * n must not exceed 2048%s");
+    }
+#undef GBP_EVIDENCE_CASE
+}
+
 #include "gbp_section_graph.h"
 
 // Sections across lines (gbp_section_graph.h): K and the first messages, one launch per sweep with one workgroup per undirected edge,
@@ -2637,6 +2690,31 @@ extern "C" gbp_status gbp_section_propagate(int S, int E, int n, const int32_t* 
                            (const int*)in_edge, (const double*)(mu ? mu + (size_t)(sweeps & 1) * half : mu), belief, (int*)state);
         GBP_HIP(hipGetLastError());
     }
+    return GBP_OK;
+}
+
+// The terms of the Bethe evidence (gbp_section_evidence.h k_graph_evidence): one launch, a workgroup per edge and one per sounding.
+extern "C" gbp_status gbp_section_graph_evidence(int S, int E, int n, const int32_t* eu, const int32_t* ev, const int32_t* n_used,
+                                                 const double* w, const double* g, const double* d2, const int32_t* in_ptr,
+                                                 const int32_t* in_edge, const double* message, double* node_log_z, double* edge_log_z,
+                                                 double* edge_energy, void* stream)
+{
+    if (S < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: S must be >= 0%s");
+    if (E < 0 || E > 0x3fffffff) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: E must lie in 0 .. 2^30 - 1%s");
+    if (n < 1 || n > section::GRAPH_MAX_STATES) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: n must lie in 1 .. 256%s");
+    if (E > 0 && S < 2) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: an edge needs two soundings%s");
+    if ((long long)S + 2LL * E > 0x7fffffffLL) return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: S + 2 E out of range%s");
+    if (E > 0 && (long long)E > 0x7fffffffffffffffLL / 8 / n / n)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: E * n * n out of range%s");
+    if (S > 0 && (!n_used || !w || !in_ptr || !node_log_z))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: NULL pointer (n_used, w, in_ptr, node_log_z)%s");
+    if (E > 0 && (!eu || !ev || !g || !d2 || !in_edge || !message || !edge_log_z || !edge_energy))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_section_graph_evidence: NULL pointer (eu, ev, g, d2, in_edge, message, edge_log_z, edge_energy)%s");
+    if (S == 0) return GBP_OK;
+    hipLaunchKernelGGL(section::k_graph_evidence, dim3((unsigned)(E + S)), dim3(section::THREADS), 0, (hipStream_t)stream, S, E, n, (const int*)eu,
+                       (const int*)ev, (const int*)n_used, w, g, d2, (const int*)in_ptr, (const int*)in_edge, message, node_log_z, edge_log_z,
+                       edge_energy);
+    GBP_HIP(hipGetLastError());
     return GBP_OK;
 }
 

@@ -39,13 +39,13 @@ The rule of the chain.  A launch holds L sequences concatenated with ``ptr`` [L 
   beta_{r+1}[j] / s_{r+1}; gamma = alpha beta normalised per sounding, 0 for the states >= m_r; log_partition = sum ln s.
 Nothing outside the prefixes i < m_r, j < m_{r+1} of d2 is read, nor the entry of a sequence's last sounding.
 
-``python -m geobipy_amd.sections <survey.npz> --depth Z1 [--from Z0] [--measure log] [--tau T] [--length L] [--max-models n]
+``python -m geobipy_amd.sections <survey.npz> --depth Z1 [--from Z0] [--measure log] [--tau T | --fit-tau] [--length L] [--max-models n]
 [--chains C] [--no-marginals] [--draws R [--seed N]] [--depth-axis N WIDTH [--percentiles P ...] [--exceed T ...]]`` writes
 ``<name>.sections.npz``.  There is no host fallback: ``cross_distance``, ``track``, ``draw``, ``sections`` and ``lateral_products``
 refuse tensors that are not on the device.  ``survey.infer`` is not wired: its blocks cut across lines, so a lateral product is a step
-after the run, like ``horizons.from_products``.  Left out on purpose: carrying a sequence across launches, and learning ``tau``
-(``log_partition`` is returned for whoever wants to scan it; a ``score`` is no longer left to the caller alone: ``boreholes=`` makes one
-from borehole logs).  (The weighted re-binning by ``weight`` that this list used to name is
+after the run, like ``horizons.from_products``.  Left out on purpose: carrying a sequence across launches.  (Learning ``tau``, which
+this list used to name, is ``fit_tau`` below; a ``score`` is no longer left to the caller alone: ``boreholes=`` makes one
+from borehole logs.)  (The weighted re-binning by ``weight`` that this list used to name is
 ``lateral_products``; coupling across lines is ``spatial``.)
 
 Across lines (gbp_section_propagate: csrc/gbp_section_graph.h).  ``neighbours`` joins every sounding to the next of
@@ -54,7 +54,7 @@ its line and to the nearest sounding of every other line within ``max_distance``
 and returns *beliefs*: the marginals on a forest, a documented approximation on a graph with loops; ``spatial`` is all of it for an
 ensemble, with the keys of ``sections`` that still have a meaning, and ``spatial_from_survey`` / ``from_survey(..., spatial=dict(
 max_distance=...))`` / ``--spatial MAX_DISTANCE [--sweeps N] [--damping L]`` (``<name>.spatial.npz``) for a survey.  Left out on
-purpose: tree-reweighted variants, learning ``tau``, wiring into ``survey.infer``.
+purpose: tree-reweighted variants, wiring into ``survey.infer`` (learning ``tau`` is ``fit_tau_graph`` below).
 
 The most probable section across lines (gbp_section_graph_path, gbp_section_graph_refine:
 csrc/gbp_section_graph_path.h).  ``state`` of ``spatial`` is every sounding's most believed model taken alone; ``graph_path`` finds
@@ -64,8 +64,7 @@ are never mixed, and coordinate ascent on the exact score (``refine``, ``soundin
 given, of which the most probable is kept.  Exact on a forest; on loops an approximation that is never below its candidates.
 ``spatial(..., path=True)`` adds ``path_state``, ``path_slot``, ``path_k`` / ``path_edges`` / ``path_sigma``, ``path_log_score``
 beside ``state_log_score``, ``path_margin``, ``path_residual``, ``path_candidate_log_score``, ``path_chosen`` and
-``path_edge_distance``; ``--spatial D --path [SWEEPS]`` writes them.  Left out on purpose: tree-reweighted variants, cluster moves,
-learning ``tau``.
+``path_edge_distance``; ``--spatial D --path [SWEEPS]`` writes them.  Left out on purpose: tree-reweighted variants, cluster moves.
 
 Joint draws across lines (gbp_section_graph_draw: csrc/gbp_section_graph_draw.h).  ``graph_draw`` draws R joint
 realisations of the whole graph by Gibbs sampling blocked by flight line (``graph_draw_reference`` states the rule, ``line_colours``
@@ -74,8 +73,8 @@ conditional given its neighbours' current states.  The stationary law is the exa
 draws of it as far as ``sweeps`` sweeps have mixed, and 8 is a convention.  ``propagate(..., keep_kernel=True)`` hands its K on,
 ``spatial(..., draws=R, seed=N, draw_sweeps=T)`` adds ``draw_state``, ``draw_slot``, ``draw_log_score``, ``draw_share`` and
 ``draw_change_share``, and ``--spatial D --spatial-draws R [--seed N] [--draw-sweeps T]`` writes them.  Left out on purpose: the
-filter on the matrix cores, cluster moves and tempering, learning ``tau`` (the pair potential exp(-g D^2) is not a normalised
-transition, so the evidence grows monotonically as g -> 0).  (Draws conditioned on boreholes, which this list used to name, are
+filter on the matrix cores, cluster moves and tempering.  (Learning ``tau``: the pair potential exp(-g D^2) is not a normalised
+transition, so ``log_partition`` alone grows monotonically as g -> 0; ``fit_tau`` below adds the normaliser.)  (Draws conditioned on boreholes, which this list used to name, are
 ``boreholes=`` below.)
 
 Borehole logs (gbp_borehole_score: csrc/gbp_boreholes.h, through ``geobipy_amd.boreholes``).  ``sections(...,
@@ -85,7 +84,22 @@ nearest sounding of every line within ``max_distance``, score every kept model o
 then conditioned on the logs.  They add ``borehole_score``, ``borehole_sounding``, ``borehole_index``, ``borehole_distance``,
 ``borehole_skipped`` and ``borehole_log_predictive``; ``--boreholes LOGS --borehole-distance D [--class-means M ... --class-scales S
 ...] [--class-floor F]`` does the same from the command line, with and without ``--spatial``, ``--draws`` and ``--bodies``.  Left out on
-purpose: deviated wells, fitting ``tau`` or a log's ``sd``, wiring into ``survey.infer``, feeding logs back into the sampler's prior.
+purpose: deviated wells, fitting a log's ``sd``, wiring into ``survey.infer``, feeding logs back into the sampler's prior.
+
+Learning ``tau`` (gbp_section_evidence, gbp_section_graph_evidence: csrc/gbp_section_evidence.h).  The RMS difference
+across a step is a scalar Gaussian of variance tau^2 dx / length, density sqrt(c g / pi) exp(-c g D^2) with g at a base tau0 and c =
+(tau0 / tau)^2; up to a term that does not depend on tau the log evidence of c is log_partition(c) + rank / 2 ln c - sum_s ln sum_i
+w_s[i], rank the number of soundings minus the number of connected pieces (along lines: the steps), and its derivative in lambda =
+ln c is dlog_partition + rank / 2 with dlog_partition = -E[sum c g D^2]: at the fit the expected total cost is rank / 2.  ``evidence``
+gives value and derivative for a ladder of tau (a factor sqrt 2 per rung) from one forward pass over ``d2`` per launch
+(``evidence_reference`` and ``evidence_reference_ladder`` state the rule); ``graph_evidence`` the same for the survey graph through
+the Bethe free energy of the messages ``propagate(..., keep_messages=True)`` hands on (``graph_terms``, ``graph_terms_reference``,
+``graph_evidence_reference``, ``graph_rank``), with ``edge_energy``, the expected cost per edge; ``fit_tau`` / ``fit_tau_graph``
+(``fit_tau_reference`` / ``fit_tau_graph_reference``) find the zero and its Laplace standard error, ``fit_ensemble`` and
+``fit_from_survey`` do so for an ensemble and a survey, and ``--fit-tau [TAU_MAX [RUNGS]]`` runs the fit first, uses tau_hat for
+everything else and stores ``fit_tau``, ``fit_tau_sd_log``, ``fit_tau_ladder`` and ``fit_log_evidence``.  ``tau`` stays 0.1 wherever
+no fit is asked for.  Left out on purpose: learning ``slope`` and ``switch`` of ``horizons`` (the same tangent pass would do), a
+``tau`` per line or per depth window, expected costs per step along lines (they need the backward pass), ``survey.infer``.
 
 Connected bodies of the realisations (gbp_bodies_label: csrc/gbp_bodies.h, through ``geobipy_amd.bodies``).
 ``draw_bodies`` rasters the drawn models, on terrain resamples them onto one elevation axis, labels the connected bodies of the cells
@@ -291,6 +305,161 @@ def track_reference(ptr, score, g, d2, n_used, marginals=True, dtype=np.float64)
     return out
 
 
+# ---- learning tau: the evidence of the coupling and its derivative --------------------------------------------------
+
+MAX_RUNGS = 8                       # the rungs of one launch
+MAX_RUNG_STATES = 2048              # rungs * n of one launch: the filters and their tangents fill the LDS
+FIT_TOLERANCE = 2e-3                # the bracket in lambda = ln c at which the refinement stops
+FIT_EVALUATIONS = 12                # ... or this many single-rung evaluations
+
+
+def evidence_reference(ptr, score, g, d2, n_used, T=1, dtype=np.float64):
+    """The rule of gbp_section_evidence in numpy, evaluated in ``dtype``: ``log_partition`` and ``dlog_partition`` [T, L] of the chain
+    of ``track_reference`` for the ladder of scales c_t = 2^t, t = 0 .. T - 1, of the step costs (``g`` already holds the lowest
+    scale); the derivative is taken in lambda = ln c.  Arguments as ``track_reference`` takes them; prefixes only.
+
+    Per sequence and rung t the normalised filter a_t and its tangent b_t = d a_t / d lambda.  Start: a = w_0 / sum w_0, b = 0,
+    log Z = ln sum w_0, dlog Z = 0 (w = exp(score)).  Per step: cost_0 = g[r] * d2[r, i, j] (one multiply per entry), e_0 =
+    exp(-cost_0) (one exp per entry); e_t = e_{t-1} * e_{t-1}, cost_t = cost_{t-1} + cost_{t-1} (exact); u_j = w_j sum_i a_t[i] e_t[i, j];
+    u'_j = w_j sum_i (b_t[i] - a_t[i] cost_t[i, j]) e_t[i, j]; z = sum_j u_j, z' = sum_j u'_j; log Z += ln z, dlog Z += z' / z; a_t =
+    u / z, b_t = u' / z - a_t (z' / z).  The sums are numpy's (``sum`` over an axis): their order is not part of the rule.  dlog Z is
+    -E[sum c_t g D^2], the expected total cost of a section.  A sequence of one sounding has ln sum w_0 and 0.0; where a step's z
+    underflows to 0 the rung is -inf or NaN from there on, and the rungs below it are not affected."""
+    ft = np.dtype(dtype).type
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.evidence_reference", empty=True)
+    T = check_int(T, 1, MAX_RUNGS, "sections.evidence_reference: T")
+    total, n = d2.shape[0], d2.shape[1]
+    score = (np.zeros((total, n)) if score is None else score).astype(ft)
+    g = np.asarray(g, dtype=np.float64).reshape(-1).astype(ft)
+    L = ptr.size - 1
+    log_z, dlog_z = np.zeros((T, L), dtype=ft), np.zeros((T, L), dtype=ft)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        for l in range(L):
+            r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+            if N <= 0:
+                continue
+            m = [int(v) for v in nu[r0:r0 + N]]
+            w = np.exp(score[r0, :m[0]])
+            s = w.sum()
+            a, b = [w / s for _ in range(T)], [np.zeros(m[0], dtype=ft) for _ in range(T)]
+            log_z[:, l] = np.log(s)
+            for st in range(N - 1):
+                r = r0 + st
+                cost = g[r] * d2[r, :m[st], :m[st + 1]].astype(ft)
+                e = np.exp(-cost)
+                w = np.exp(score[r + 1, :m[st + 1]])
+                for t in range(T):
+                    if t:
+                        e, cost = e * e, cost + cost
+                    u = w * (a[t][:, None] * e).sum(axis=0)
+                    up = w * ((b[t][:, None] - a[t][:, None] * cost) * e).sum(axis=0)
+                    z, zp = u.sum(), up.sum()
+                    log_z[t, l] += np.log(z)
+                    dlog_z[t, l] += zp / z
+                    a[t] = u / z
+                    b[t] = up / z - a[t] * (zp / z)
+    return dict(log_partition=log_z, dlog_partition=dlog_z)
+
+
+def ladder_launches(n, rungs):
+    """[(first rung, rungs)] of the launches a ladder of ``rungs`` rungs over ``n`` states takes: at most 8 rungs and rungs * n <= 2048
+    per launch.  Every launch's lowest rung takes its own exp; the rungs above it are squarings."""
+    per = max(1, min(MAX_RUNGS, MAX_RUNG_STATES // max(int(n), 1)))
+    return [(t, min(per, rungs - t)) for t in range(0, rungs, per)]
+
+
+def _check_ladder(tau0, rungs, scale, what):
+    return _check_number(tau0, "tau0"), check_int(rungs, 1, 64, "%s: rungs" % what), _check_number(scale, "scale")
+
+
+def _log_weights(score, nu):
+    """float64 [T] (numpy): ln sum_i w_s[i] over the prefix of every sounding (``score`` numpy [T, n] or None: ln m_s)."""
+    if score is None:
+        return np.log(nu.astype(np.float64))
+    out = np.empty(nu.size)
+    for s in range(nu.size):
+        v = np.asarray(score[s, :nu[s]], dtype=np.float64)
+        top = v.max()
+        out[s] = top + np.log(np.exp(v - top).sum()) if np.isfinite(top) else top
+    return out
+
+
+def _ladder_result(log_z, dlog_z, ptr, log_w, tau0, scale):
+    """What ``evidence`` and ``evidence_reference_ladder`` return, from log Z and dlog Z [T, L] (numpy float64)."""
+    T = log_z.shape[0]
+    c = scale * 2.0 ** np.arange(T)
+    rank = (np.diff(ptr) - 1).clip(min=0).astype(np.int64)
+    base = np.array([log_w[a:b].sum() for a, b in zip(ptr[:-1], ptr[1:])], dtype=np.float64)
+    return dict(tau=tau0 / np.sqrt(c), scale=c, rank=rank, log_partition=log_z, dlog_partition=dlog_z,
+                log_evidence=log_z + 0.5 * rank[None, :] * np.log(c)[:, None] - base[None, :])
+
+
+def evidence_reference_ladder(d2, g, ptr, n_used, score=None, tau0=0.1, rungs=1, scale=1.0, dtype=np.float64):
+    """The rule of ``evidence``: ``evidence_reference`` launch by launch as ``ladder_launches`` splits the ladder, every launch's ``g``
+    multiplied by its lowest scale (one multiply per step, in float64).  numpy arrays throughout; returns what ``evidence`` returns."""
+    tau0, rungs, scale = _check_ladder(tau0, rungs, scale, "sections.evidence_reference_ladder")
+    d2 = np.asarray(d2, dtype=np.float64)
+    score = None if score is None else np.asarray(score, dtype=np.float64)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.evidence_reference_ladder", empty=True)
+    g = np.asarray(g, dtype=np.float64).reshape(-1)
+    parts = [evidence_reference(ptr, score, g * (scale * 2.0 ** t0), d2, nu, T=T, dtype=dtype) for t0, T in ladder_launches(d2.shape[1], rungs)]
+    log_z, dlog_z = (np.concatenate([p[name] for p in parts]).astype(np.float64) for name in ("log_partition", "dlog_partition"))
+    return _ladder_result(log_z, dlog_z, ptr, _log_weights(score, nu), tau0, scale)
+
+
+def _fit(evaluate, tau_max, rungs):
+    """The fit ``fit_tau`` and ``fit_tau_reference`` share.  ``evaluate(scale, rungs)`` gives the ladder result of ``evidence`` (numpy)
+    with ``g`` at ``tau_max``.  f(lambda) = sum_l dlog_partition + rank / 2 is the derivative of the pooled log evidence in lambda =
+    ln c, c = (tau_max / tau)^2: positive where the walk is too loose, negative where it is too stiff."""
+    lad = evaluate(1.0, rungs)
+    rank = int(lad["rank"].sum())
+    lam = np.log(lad["scale"])
+    f = lad["dlog_partition"].sum(axis=1) + 0.5 * rank
+    pooled = lad["log_evidence"].sum(axis=1)
+    out = dict(tau_ladder=lad["tau"], log_evidence=pooled, log_evidence_sequence=lad["log_evidence"], expected_cost=-lad["dlog_partition"].sum(axis=1),
+               rank=rank, bracketed=False, bracket=(-1, -1), tau_sd_log=float("nan"), evaluations=0)
+    out.update({name: lad[name] for name in ("residual", "edge_energy") if name in lad})      # (the graph's ladder has them)
+    ok = np.flatnonzero(np.isfinite(f) & np.isfinite(pooled))                # non-finite rungs are skipped
+    pair = next(((int(a), int(b)) for a, b in zip(ok[:-1], ok[1:]) if f[a] > 0.0 >= f[b]), None)
+    if pair is None:
+        # no sign change: the ladder's end on the side the derivative points to (its last finite rung where f > 0 throughout)
+        end = (ok[-1] if f[ok[-1]] > 0.0 else ok[0]) if ok.size else rungs - 1
+        out["tau"] = float(lad["tau"][end])
+        return out
+    lo, hi, f_lo, f_hi = float(lam[pair[0]]), float(lam[pair[1]]), float(f[pair[0]]), float(f[pair[1]])
+    n_eval = 0
+    while hi - lo >= FIT_TOLERANCE and n_eval < FIT_EVALUATIONS:              # bisection: every evaluation halves the bracket
+        mid = 0.5 * (lo + hi)
+        one = evaluate(float(np.exp(mid)), 1)
+        f_mid = float(one["dlog_partition"].sum() + 0.5 * rank)
+        n_eval += 1
+        if not np.isfinite(f_mid):
+            break
+        if f_mid > 0.0:
+            lo, f_lo = mid, f_mid
+        else:
+            hi, f_hi = mid, f_mid
+    slope = (f_hi - f_lo) / (hi - lo)                                         # f' < 0: the curvature of the log evidence in lambda
+    root = lo - f_lo / slope                                                  # the secant's zero within the last bracket
+    out.update(tau=float(tau_max * np.exp(-0.5 * root)), tau_sd_log=float(0.5 / np.sqrt(-slope)), bracketed=True, bracket=pair, evaluations=n_eval)
+    return out
+
+
+def _check_fit(tau_max, rungs, what):
+    return _check_number(tau_max, "tau_max"), check_int(rungs, 2, 64, "%s: rungs" % what)
+
+
+def fit_tau_reference(d2, g, ptr, n_used, score=None, tau0=0.1, tau_max=0.8, rungs=11, dtype=np.float64):
+    """``fit_tau`` on the rules (``evidence_reference_ladder``), numpy arrays throughout."""
+    tau_max, rungs = _check_fit(tau_max, rungs, "sections.fit_tau_reference")
+    tau0 = _check_ladder(tau0, 1, 1.0, "sections.fit_tau_reference")[0]
+    g_max = np.asarray(host(g), dtype=np.float64).reshape(-1) * (tau0 / tau_max) ** 2
+    return _fit(lambda scale, T: evidence_reference_ladder(d2, g_max, ptr, n_used, score=score, tau0=tau_max, rungs=T, scale=scale, dtype=dtype),
+                tau_max, rungs)
+
+
 # ---- joint draws: the rule ----------------------------------------------------------------------------------------------------------
 
 _M32 = np.uint64(0xFFFFFFFF)
@@ -484,6 +653,56 @@ def track(d2, g, ptr, n_used, score=None, marginals=True):
         _lib.call(entry, dev, L, t_ptr, total, n, t_nu, score, t_g, d2, back, out["state"], out["log_score"], out.get("marginal"),
                   out.get("log_partition"), out.get("scale"))
     return out
+
+
+def evidence(d2, g, ptr, n_used, score=None, tau0=0.1, rungs=1, scale=1.0):
+    """The evidence of the coupling for a ladder of ``rungs`` values of tau, and its exact derivative (gbp_section_evidence;
+    ``evidence_reference_ladder`` states the rule).  ``d2``, ``g``, ``ptr``, ``n_used``, ``score`` as ``track`` takes
+    them (a sequence of ``ptr`` may be empty); ``g`` is what ``steps`` gives for ``tau0``.  Rung t scales the step costs by c_t =
+    ``scale`` 2^t, that is tau_t = ``tau0`` / sqrt(c_t): tau falls by sqrt 2 per rung.  One forward pass over ``d2`` serves up to 8 rungs
+    with rungs * n <= 2048; a longer ladder takes further launches (``ladder_launches``).  Returns numpy arrays: ``tau`` and ``scale``
+    [rungs], ``rank`` int64 [L] (the steps of every sequence), ``log_partition`` and ``dlog_partition`` [rungs, L] (the derivative in
+    lambda = ln c: minus the expected total cost of a section) and ``log_evidence`` [rungs, L] = log_partition + rank / 2 ln c - sum_s
+    ln sum_i w_s[i], the log evidence of tau up to a term that does not depend on it."""
+    entry = "gbp_section_evidence"
+    are_tensors((d2,) + (() if score is None else (score,)), "sections", "evidence", entry)
+    g = host(g).reshape(-1).astype(np.float64)                               # (every launch scales it on the host)
+    ptr, nu = _check_chain(ptr, score, g, d2, n_used, "sections.evidence", empty=True)
+    tau0, rungs, scale = _check_ladder(tau0, rungs, scale, "sections.evidence")
+    if d2.dtype != torch.float64 or (score is not None and score.dtype != torch.float64):
+        raise TypeError("sections.evidence: d2 and score are float64")
+    on_device((d2,) + (() if score is None else (score,)), "sections", "evidence", entry)
+    dev = d2.device
+    total, n = d2.shape[0], d2.shape[1]
+    L = ptr.size - 1
+    f64 = dict(dtype=torch.float64, device=dev)
+    d2 = d2.contiguous()
+    log_w = _log_weights(None if score is None else score.cpu().numpy(), nu)
+    score = torch.zeros((total, n), **f64) if score is None else score.contiguous()
+    t_ptr = torch.as_tensor(ptr, dtype=torch.int64).to(dev)
+    t_nu = torch.as_tensor(nu.astype(np.int32)).to(dev)
+    log_z, dlog_z = torch.zeros((rungs, L), **f64), torch.zeros((rungs, L), **f64)
+    if L > 0:
+        for t0, T in ladder_launches(n, rungs):
+            t_g = torch.as_tensor(g * (scale * 2.0 ** t0)).to(dev)          # the launch's lowest scale, one multiply per step
+            _lib.call(entry, dev, L, t_ptr, total, n, t_nu, score, t_g, d2, T, log_z[t0:t0 + T], dlog_z[t0:t0 + T])
+    return _ladder_result(log_z.cpu().numpy(), dlog_z.cpu().numpy(), ptr, log_w, tau0, scale)
+
+
+def fit_tau(d2, g, ptr, n_used, score=None, tau0=0.1, tau_max=0.8, rungs=11):
+    """The lateral coupling tau learnt from the sections themselves: the zero of the pooled log evidence's derivative
+    f(lambda) = sum_l dlog_partition + rank / 2 -- equipartition: the expected total cost of a section equals half the number of
+    steps.  Arguments as ``evidence`` takes them, ``g`` at ``tau0``.  A ladder of ``rungs`` values from ``tau_max`` downward by sqrt 2
+    (0.8 .. 0.025 by default) is evaluated in one pass per launch; the first sign change of f among its finite rungs is refined by
+    bisection with single-rung launches until the bracket in lambda is below 2e-3 or 12 evaluations have been made; the zero is the
+    secant's within the last bracket.  Returns ``tau``, ``tau_sd_log`` = 0.5 / sqrt(-f') from that bracket's slope (the Laplace
+    standard error of ln tau), ``tau_ladder`` [rungs], ``log_evidence`` [rungs] pooled and ``log_evidence_sequence`` [rungs, L],
+    ``expected_cost`` [rungs], ``rank``, ``bracketed``, ``bracket`` (the two rungs, (-1, -1) without) and ``evaluations``.  Where f
+    does not change sign ``bracketed`` is False, ``tau`` is the ladder's end on the side f points to and ``tau_sd_log`` is NaN."""
+    tau_max, rungs = _check_fit(tau_max, rungs, "sections.fit_tau")
+    tau0 = _check_ladder(tau0, 1, 1.0, "sections.fit_tau")[0]
+    g_max = host(g).reshape(-1).astype(np.float64) * (tau0 / tau_max) ** 2
+    return _fit(lambda scale, T: evidence(d2, g_max, ptr, n_used, score=score, tau0=tau_max, rungs=T, scale=scale), tau_max, rungs)
 
 
 def draw(d2, g, ptr, n_used, n_draws, seed=0, score=None, row_key=None):
@@ -934,7 +1153,7 @@ def _nan_max(r, d):
     return d if (d > r or d != d) else r
 
 
-def propagate_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.0, dtype=np.float64):
+def propagate_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.0, dtype=np.float64, keep_messages=False):
     """The rule of ``propagate`` in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the yardstick of the
     rule's own rounding): synchronous sum-product message passing on the graph of S = len(n_used) soundings with the undirected edges
     ``eu[e]`` < ``ev[e]`` (sorted by (eu, ev), no duplicates), ``g`` [E] and ``d2`` [E, n, n], entry [e, i, j] between state i of
@@ -952,7 +1171,8 @@ def propagate_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.
     Exact on a tree once the sweeps reach its diameter (the residual is 0.0 from then on: every message has its final bits); on a
     graph with loops a documented approximation: the output is a *belief*, not a marginal.
 
-    Returns ``belief`` [S, n] (``dtype``), ``state`` int32 [S] and ``residual`` [sweeps]."""
+    Returns ``belief`` [S, n] (``dtype``), ``state`` int32 [S] and ``residual`` [sweeps]; with ``keep_messages`` also ``message``
+    [2 E, n], the messages after the last sweep (0.0 beyond m_dst), and ``node_weight`` [S, n], w (0.0 beyond m_s)."""
     ft = np.dtype(dtype).type
     d2 = np.asarray(d2, dtype=np.float64)
     score = None if score is None else np.asarray(score, dtype=np.float64)
@@ -1003,7 +1223,15 @@ def propagate_reference(eu, ev, g, d2, n_used, score=None, sweeps=32, damping=0.
                 tot = tot + h[i]
             belief[s, :nu[s]] = h / tot
             state[s] = first_max(belief[s, :nu[s]])
-    return dict(belief=belief, state=state, residual=residual)
+    out = dict(belief=belief, state=state, residual=residual)
+    if keep_messages:
+        message, node_weight = np.zeros((2 * E, n), dtype=ft), np.zeros((S, n), dtype=ft)
+        for d in range(2 * E):
+            message[d, :nu[dst[d]]] = msg[d]
+        for s in range(S):
+            node_weight[s, :nu[s]] = w[s]
+        out.update(message=message, node_weight=node_weight)
+    return out
 
 
 def neighbours(x, y, ptr=None, n_used=None, *, max_distance, tau=0.1, length=100.0, min_distance=1.0):
@@ -1089,7 +1317,7 @@ def edge_distance(ens, rows, eu, ev, z0, z1, measure="linear"):
     return out
 
 
-def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0, keep_kernel=False):
+def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping=0.0, keep_kernel=False, keep_messages=False):
     """Beliefs of the graph of ``propagate_reference`` on the device (gbp_section_propagate: csrc/gbp_section_graph.h): ``d2`` f64
     [E, n, n] on the device (``edge_distance``), n <= 256; ``g`` [E], ``eu`` < ``ev`` [E] (host or device; sorted by (eu, ev), no
     duplicates), ``n_used`` [S] in 1 .. n with S = ``n_soundings``, ``score`` f64 [S, n] on the device or None: zeros; ``sweeps`` >= 1
@@ -1097,7 +1325,8 @@ def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping
     of the belief) and ``residual`` f64 [sweeps] (the largest change of a message per sweep: 0.0 once a tree has converged).  d2 is
     left as it is; K = exp(-(g d2)) takes a second buffer of its size.  The CSR of incoming edges is made once on the host.
     ``keep_kernel`` adds that K buffer as ``kernel`` f64 [E, n, n] (valid on the prefixes i < m_u, j < m_v): what ``graph_draw`` takes
-    as ``kernel=``."""
+    as ``kernel=``; ``keep_messages`` adds ``message`` f64 [2 E, n], the messages after the last sweep, and ``node_weight`` f64 [S, n],
+    w = exp(score): what ``graph_terms`` takes."""
     entry = "gbp_section_propagate"
     are_tensors((d2,) + (() if score is None else (score,)), "sections", "propagate", entry)
     S = check_int(n_soundings, 0, 2 ** 31 - 1, "sections.propagate: n_soundings")
@@ -1114,6 +1343,8 @@ def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping
     if S == 0:
         if keep_kernel:
             out["kernel"] = torch.empty_like(d2)
+        if keep_messages:
+            out.update(message=torch.empty((2 * E, n), **f64), node_weight=torch.empty((0, n), **f64))
         return out
     in_ptr, in_edge = incoming(eu, ev, S)
     d2 = d2.contiguous()
@@ -1127,7 +1358,179 @@ def propagate(d2, g, eu, ev, n_used, n_soundings, score=None, sweeps=32, damping
               out["residual"])
     if keep_kernel:
         out["kernel"] = K
+    if keep_messages:
+        out.update(message=mu[sweeps & 1], node_weight=w)
     return out
+
+
+# ---- across lines: the Bethe evidence of the coupling ------------------------------------------------------------
+
+def graph_rank(eu, ev, n_soundings):
+    """The number of soundings minus the number of connected components of the graph: the degrees of freedom of the Gaussian step
+    field, whose normaliser grows as c^(rank / 2).  A loop adds an edge and no rank."""
+    eu, ev, S = _check_edges(eu, ev, n_soundings, "sections.graph_rank")
+    root = list(range(S))
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    rank = 0
+    for a, b in zip(eu.tolist(), ev.tolist()):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            root[ra] = rb
+            rank += 1
+    return rank
+
+
+def graph_terms_reference(eu, ev, g, d2, n_used, node_weight, message, dtype=np.float64):
+    """The rule of gbp_section_graph_evidence in numpy, evaluated in ``dtype``: from the messages [2 E, n] and weights [S, n] that
+    ``propagate_reference(..., keep_messages=True)`` returns, per edge e = {u, v} h_u = w_u times the messages into u but v's, h_v
+    likewise (ascending neighbour), K = exp(-(g[e] * d2[e])), ``edge_log_z`` [E] = ln sum_ij h_u[i] K_ij h_v[j] and ``edge_energy``
+    [E] = g[e] sum_ij h_u[i] K_ij d2_ij h_v[j] / that sum; per sounding ``node_log_z`` [S] = ln sum_i w_s[i] times all its incoming
+    messages.  Prefixes only; the sums are numpy's: their order is not part of the rule."""
+    ft = np.dtype(dtype).type
+    d2 = np.asarray(d2, dtype=np.float64)
+    eu, ev, nu, _, _ = _check_graph(eu, ev, g, d2, n_used, None, 1, 0.0, "sections.graph_terms_reference")
+    E, n, S = d2.shape[0], d2.shape[1], nu.size
+    node_weight, message = np.asarray(node_weight), np.asarray(message)
+    if node_weight.shape != (S, n) or message.shape != (2 * E, n):
+        raise ValueError("sections.graph_terms_reference: node_weight [S, n] and message [2 E, n]")
+    g = np.asarray(host(g), dtype=np.float64).reshape(-1).astype(ft)
+    in_ptr, in_edge = incoming(eu, ev, S)
+    src = np.empty(2 * E, dtype=np.int64)
+    src[0::2], src[1::2] = eu, ev
+
+    def h(a, but):
+        out = node_weight[a, :nu[a]].astype(ft)
+        for q in in_edge[in_ptr[a]:in_ptr[a + 1]]:                            # ascending neighbour
+            if src[q] != but:
+                out = out * message[q, :nu[a]].astype(ft)
+        return out
+
+    node, edge, energy = np.zeros(S, dtype=ft), np.zeros(E, dtype=ft), np.zeros(E, dtype=ft)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for s in range(S):
+            node[s] = np.log(h(s, -1).sum())
+        for e in range(E):
+            u, v = int(eu[e]), int(ev[e])
+            d = d2[e, :nu[u], :nu[v]].astype(ft)
+            p = h(u, v)[:, None] * np.exp(-(g[e] * d)) * h(v, u)[None, :]
+            z = p.sum()
+            edge[e], energy[e] = np.log(z), g[e] * (p * d).sum() / z
+    return dict(node_log_z=node, edge_log_z=edge, edge_energy=energy)
+
+
+def _bethe(terms, eu, ev, S, scale, log_w):
+    """log Z_B = sum_s (1 - deg_s) node_log_z[s] + sum_e edge_log_z[e] and dlog Z_B = -sum_e edge_energy[e], summed on the host in
+    index order over the S + 2 E doubles (float64 numpy); the log evidence adds rank / 2 ln c - sum_s ln sum_i w_s[i]."""
+    node, edge, energy = (np.asarray(terms[name], dtype=np.float64) for name in ("node_log_z", "edge_log_z", "edge_energy"))
+    deg = np.bincount(eu, minlength=S) + np.bincount(ev, minlength=S)
+    log_z = dlog_z = 0.0
+    for s in range(S):
+        log_z += (1.0 - deg[s]) * node[s]
+    for e in range(edge.size):
+        log_z += edge[e]
+        dlog_z -= energy[e]
+    rank = graph_rank(eu, ev, S)
+    return dict(log_partition=float(log_z), dlog_partition=float(dlog_z), rank=rank,
+                log_evidence=float(log_z + 0.5 * rank * np.log(scale) - np.sum(log_w)))
+
+
+def graph_evidence_reference(eu, ev, g, d2, n_used, score=None, scale=1.0, sweeps=32, damping=0.0, dtype=np.float64):
+    """The rule of ``graph_evidence``: ``propagate_reference`` with ``g`` times ``scale`` (one multiply per edge, in float64), then
+    ``graph_terms_reference`` on its messages and the sums of the Bethe evidence.  Returns what ``graph_evidence`` returns, in numpy."""
+    scale = _check_ladder(0.1, 1, scale, "sections.graph_evidence_reference")[2]
+    gs = np.asarray(host(g), dtype=np.float64).reshape(-1) * scale
+    prop = propagate_reference(eu, ev, gs, d2, n_used, score, sweeps=sweeps, damping=damping, dtype=dtype, keep_messages=True)
+    terms = graph_terms_reference(eu, ev, gs, d2, n_used, prop["node_weight"], prop["message"], dtype=dtype)
+    nu = host(n_used).reshape(-1).astype(np.int64)
+    out = _bethe(terms, host(eu).reshape(-1).astype(np.int64), host(ev).reshape(-1).astype(np.int64), nu.size, scale,
+                 _log_weights(None if score is None else np.asarray(score, dtype=np.float64), nu))
+    out.update(terms, residual=prop["residual"], belief=prop["belief"])
+    return out
+
+
+def graph_terms(d2, g, eu, ev, n_used, n_soundings, node_weight, message):
+    """``node_log_z`` [S], ``edge_log_z`` [E] and ``edge_energy`` [E] on the device (gbp_section_graph_evidence: csrc/
+    gbp_section_evidence.h k_graph_evidence; ``graph_terms_reference`` states the rule) from the ``node_weight`` and ``message`` of
+    ``propagate(..., keep_messages=True)``; ``d2``, ``g``, ``eu``, ``ev``, ``n_used``, ``n_soundings`` as ``propagate`` takes them."""
+    entry = "gbp_section_graph_evidence"
+    are_tensors((d2, node_weight, message), "sections", "graph_terms", entry)
+    S = check_int(n_soundings, 0, 2 ** 31 - 1, "sections.graph_terms: n_soundings")
+    if np.size(host(n_used)) != S:
+        raise ValueError("sections.graph_terms: n_used must hold one integer per sounding (%d)" % S)
+    eu, ev, nu, _, _ = _check_graph(eu, ev, g, d2, n_used, None, 1, 0.0, "sections.graph_terms")
+    E, n = d2.shape[0], d2.shape[1]
+    if tuple(node_weight.shape) != (S, n) or tuple(message.shape) != (2 * E, n):
+        raise ValueError("sections.graph_terms: node_weight [S, n] and message [2 E, n]")
+    if d2.dtype != torch.float64 or node_weight.dtype != torch.float64 or message.dtype != torch.float64:
+        raise TypeError("sections.graph_terms: d2, node_weight and message are float64")
+    on_device((d2, node_weight, message), "sections", "graph_terms", entry)
+    dev = d2.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(node_log_z=torch.empty(S, **f64), edge_log_z=torch.empty(E, **f64), edge_energy=torch.empty(E, **f64))
+    if S == 0:
+        return out
+    in_ptr, in_edge = incoming(eu, ev, S)
+    t_g = torch.as_tensor(host(g).reshape(-1).astype(np.float64)).to(dev)
+    t_eu, t_ev, t_nu = (torch.as_tensor(a.astype(np.int32)).to(dev) for a in (eu, ev, nu))
+    _lib.call(entry, dev, S, E, n, t_eu, t_ev, t_nu, node_weight.contiguous(), t_g, d2.contiguous(), torch.as_tensor(in_ptr).to(dev),
+              torch.as_tensor(in_edge).to(dev), message.contiguous(), out["node_log_z"], out["edge_log_z"], out["edge_energy"])
+    return out
+
+
+def graph_evidence(d2, g, eu, ev, n_used, n_soundings, score=None, scale=1.0, sweeps=32, damping=0.0):
+    """The Bethe evidence of the coupling on the survey graph and its derivative (``graph_evidence_reference`` states
+    the rule): ``propagate`` with ``g`` times ``scale``, then ``graph_terms`` on its messages.  Arguments as ``propagate`` takes them.
+    Returns floats ``log_partition`` = log Z_B = sum_s (1 - deg_s) node_log_z[s] + sum_e edge_log_z[e], ``dlog_partition`` = -sum_e
+    edge_energy[e] (the derivative in lambda = ln c), ``log_evidence`` = log Z_B + rank / 2 ln scale - sum_s ln sum_i w_s[i] and
+    ``rank`` (``graph_rank``), and numpy arrays ``node_log_z`` [S], ``edge_log_z`` [E], ``edge_energy`` [E] -- which edges of the
+    survey are strained -- ``residual`` [sweeps] and ``belief`` [S, n].  Exact on a forest once ``sweeps`` reach its diameter; on loops
+    an approximation, as the beliefs are."""
+    scale = _check_ladder(0.1, 1, scale, "sections.graph_evidence")[2]
+    gs = host(g).reshape(-1).astype(np.float64) * scale
+    prop = propagate(d2, gs, eu, ev, n_used, n_soundings, score=score, sweeps=sweeps, damping=damping, keep_messages=True)
+    terms = {name: v.cpu().numpy() for name, v in graph_terms(d2, gs, eu, ev, n_used, n_soundings, prop["node_weight"], prop["message"]).items()}
+    nu = host(n_used).reshape(-1).astype(np.int64)
+    out = _bethe(terms, host(eu).reshape(-1).astype(np.int64), host(ev).reshape(-1).astype(np.int64), nu.size, scale,
+                 _log_weights(None if score is None else score.cpu().numpy(), nu))
+    out.update(terms, residual=prop["residual"].cpu().numpy(), belief=prop["belief"].cpu().numpy())
+    return out
+
+
+def _graph_ladder(one, tau_max, scale, rungs):
+    """The ladder result ``_fit`` takes, one ``graph_evidence`` per rung (``one(scale)``); L = 1: the graph is pooled."""
+    c = scale * 2.0 ** np.arange(rungs)
+    got = [one(float(v)) for v in c]
+    col = lambda name: np.array([[r[name]] for r in got], dtype=np.float64)      # noqa: E731
+    return dict(tau=tau_max / np.sqrt(c), scale=c, rank=np.array([got[0]["rank"]]), log_partition=col("log_partition"),
+                dlog_partition=col("dlog_partition"), log_evidence=col("log_evidence"),
+                residual=np.array([r["residual"][-1] for r in got], dtype=np.float64), edge_energy=np.stack([r["edge_energy"] for r in got]))
+
+
+def fit_tau_graph_reference(eu, ev, g, d2, n_used, score=None, tau0=0.1, tau_max=0.8, rungs=11, sweeps=32, damping=0.0, dtype=np.float64):
+    """``fit_tau_graph`` on the rules (``graph_evidence_reference``), numpy arrays throughout."""
+    tau_max, rungs = _check_fit(tau_max, rungs, "sections.fit_tau_graph_reference")
+    tau0 = _check_ladder(tau0, 1, 1.0, "sections.fit_tau_graph_reference")[0]
+    g_max = np.asarray(host(g), dtype=np.float64).reshape(-1) * (tau0 / tau_max) ** 2
+    one = lambda c: graph_evidence_reference(eu, ev, g_max, d2, n_used, score, scale=c, sweeps=sweeps, damping=damping, dtype=dtype)      # noqa: E731
+    return _fit(lambda scale, T: _graph_ladder(one, tau_max, scale, T), tau_max, rungs)
+
+
+def fit_tau_graph(d2, g, eu, ev, n_used, n_soundings, score=None, tau0=0.1, tau_max=0.8, rungs=11, sweeps=32, damping=0.0):
+    """``fit_tau`` for the survey graph: the same ladder, bracket and refinement over ``graph_evidence``, one ``propagate`` of
+    ``sweeps`` sweeps per evaluation; ``g`` (``neighbours``) at ``tau0``.  Returns what ``fit_tau`` returns -- ``log_evidence_sequence``
+    is [rungs, 1], the graph is pooled -- and ``residual`` [rungs], the last sweep's residual of every rung: where the messages had not
+    settled, the Bethe evidence of that rung is not at a fixed point and its derivative is not exact."""
+    tau_max, rungs = _check_fit(tau_max, rungs, "sections.fit_tau_graph")
+    tau0 = _check_ladder(tau0, 1, 1.0, "sections.fit_tau_graph")[0]
+    g_max = host(g).reshape(-1).astype(np.float64) * (tau0 / tau_max) ** 2
+    one = lambda c: graph_evidence(d2, g_max, eu, ev, n_used, n_soundings, score=score, scale=c, sweeps=sweeps, damping=damping)      # noqa: E731
+    return _fit(lambda scale, T: _graph_ladder(one, tau_max, scale, T), tau_max, rungs)
 
 
 # ---- across lines: joint draws by Gibbs sampling blocked by flight line (DESIGN.md 3.29) ----------------------------------------------
@@ -1988,6 +2391,58 @@ def spatial_from_survey(result_or_path, z1, device=None, **kw):
     return out
 
 
+def fit_ensemble(ens, x, y, z1, z0=0.0, measure="linear", ptr=None, chains=1, max_models=128, length=100.0, min_distance=1.0, tau_max=0.8,
+                 rungs=11, spatial=None):
+    """``fit_tau`` for an ensemble, on the plumbing of ``sections``: ``families.used_rows`` (``chains``, ``max_models``), ``steps``
+    at ``tau_max``, ``pieces`` (a sequence is cut at soundings without models), ``cross_distance`` and the fit.  ``spatial`` =
+    dict(max_distance=, sweeps=, damping=) fits on the survey graph instead (``neighbours``, ``edge_distance``, ``fit_tau_graph``;
+    ``max_models`` <= 256).  The distances of the whole survey are held at once: S n^2 8 bytes (E n^2 8 for the graph).  Returns the
+    dictionary of ``fit_tau`` (``fit_tau_graph``)."""
+    z0, z1, _ = check_window(z0, z1, measure)
+    k, edges, sigma = ens.k, ens.edges, ens.sigma
+    are_tensors((k, edges, sigma), "sections", "fit_ensemble", "gbp_ensemble_cross_distance")
+    if k.ndim != 2 or edges.ndim != 3:
+        raise ValueError("ensemble: k [S, n_slots], edges and sigma [S, n_slots, K]")
+    if spatial is not None and (not isinstance(spatial, dict) or "max_distance" not in spatial or set(spatial) - {"max_distance", "sweeps", "damping"}):
+        raise ValueError("sections.fit_ensemble: spatial is a dictionary with max_distance and, optionally, sweeps and damping")
+    tau_max, rungs = _check_fit(tau_max, rungs, "sections.fit_ensemble")
+    C = check_chains(chains, k.shape[1])
+    max_models = check_int(max_models, 1, MAX_STATES if spatial is None else MAX_GRAPH_STATES, "max_models")
+    S = k.shape[0]
+    x, y = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y))
+    if x.size != S or y.size != S:
+        raise ValueError("sections: x and y must hold one entry per sounding (%d)" % S)
+    p = _default_ptr(ptr, S)
+    g = steps(x, y, tau_max, length, min_distance, p)
+    rows, n_used, _ = used_rows(ens, chains=C, max_models=max_models)
+    on_device((k, edges, sigma), "sections", "fit_ensemble", "gbp_ensemble_cross_distance")
+    dev = k.device
+    nu = host(n_used).reshape(-1).astype(np.int64)
+    if spatial is not None:
+        eu, ev, g, _ = neighbours(x, y, p, nu, max_distance=spatial["max_distance"], tau=tau_max, length=length, min_distance=min_distance)
+        d2 = edge_distance(ens, rows, eu, ev, z0, z1, measure=measure)
+        keep = np.flatnonzero(nu > 0)
+        local = np.cumsum(nu > 0) - 1                                          # the soundings with models, renumbered: the order stays
+        return fit_tau_graph(d2, g, local[eu], local[ev], nu[keep], keep.size, tau0=tau_max, tau_max=tau_max, rungs=rungs,
+                             sweeps=spatial.get("sweeps", 32), damping=spatial.get("damping", 0.0))
+    keep, piece_ptr, _ = pieces(p, nu)
+    idx = torch.as_tensor(keep).to(dev)
+    partner = np.arange(1, keep.size + 1, dtype=np.int32)
+    partner[piece_ptr[1:] - 1] = -1
+    sub = Ensemble(k[idx], edges[idx], sigma[idx], None, None, ens.thin, None)
+    d2 = cross_distance(sub, rows[idx], partner, z0, z1, measure=measure, squared=True)
+    return fit_tau(d2, g[keep], piece_ptr, nu[keep], tau0=tau_max, tau_max=tau_max, rungs=rungs)
+
+
+def fit_from_survey(result_or_path, z1, device=None, spatial=None, **kw):
+    """``fit_ensemble`` for a ``survey.SurveyResult`` or its saved file: the sequences are the survey's lines; ``kw``: the keywords of
+    ``fit_ensemble`` but ``ptr``; ``spatial`` = dict(max_distance=, ...) fits on the survey graph."""
+    if "ptr" in kw:
+        raise ValueError("sections.fit_from_survey: the sequences are the survey's lines; ptr is not taken")
+    res, ens = _survey_ensemble(result_or_path, device, "fit_from_survey")
+    return fit_ensemble(ens, res["x"], res["y"], z1, ptr=line_ptr(res["line"]), spatial=spatial, **kw)
+
+
 def output_path(path, suffix=OUTPUT_SUFFIX):
     """<name>.sections.npz (``suffix``) beside the survey result <name>.npz."""
     path = str(path)
@@ -2006,7 +2461,11 @@ def _parser():
     p.add_argument("--depth", type=float, required=True, metavar="Z1", help="the bottom of the depth window (m)")
     p.add_argument("--from", dest="z0", type=float, default=0.0, metavar="Z0", help="the top of the depth window (default 0)")
     p.add_argument("--measure", choices=MEASURES, default="linear", help="weigh depth linearly or by its logarithm (log needs --from > 0)")
-    p.add_argument("--tau", type=float, default=0.1, metavar="T", help="decades of RMS difference per --length metres (default 0.1)")
+    p.add_argument("--tau", type=float, default=None, metavar="T", help="decades of RMS difference per --length metres (default 0.1)")
+    p.add_argument("--fit-tau", type=float, nargs="*", default=None, metavar="TAU_MAX [RUNGS]",
+                   help="learn tau from the sections themselves first (the zero of the evidence's derivative over a ladder of RUNGS values from "
+                        "TAU_MAX downward by sqrt 2; default 0.8 11; with --spatial on the survey graph) and use it for everything else; adds "
+                        "fit_tau, fit_tau_sd_log, fit_tau_ladder and fit_log_evidence; not together with --tau")
     p.add_argument("--length", type=float, default=100.0, metavar="L", help="the distance --tau refers to, m (default 100)")
     p.add_argument("--max-models", type=int, default=128, metavar="n", help="the most models per sounding, 1 .. 1024 (default 128)")
     p.add_argument("--chains", type=int, default=1, metavar="C", help="replicate chains on the slot axis (default 1)")
@@ -2052,6 +2511,18 @@ def parse_args(argv=None):
     """The command line as (path, keywords of ``from_survey``); refuses before any device work."""
     p = _parser()
     a = p.parse_args(argv)
+    fit = None
+    if a.fit_tau is not None:
+        if a.tau is not None:
+            p.error("--fit-tau learns tau: it is not given together with --tau")
+        if len(a.fit_tau) > 2 or (len(a.fit_tau) == 2 and a.fit_tau[1] != int(a.fit_tau[1])):
+            p.error("--fit-tau [TAU_MAX [RUNGS]]: a number and an integer")
+        try:
+            fit = dict(zip(("tau_max", "rungs"), _check_fit(a.fit_tau[0] if a.fit_tau else 0.8, int(a.fit_tau[1]) if len(a.fit_tau) == 2 else 11, "--fit-tau")))
+        except ValueError as e:
+            p.error(str(e))
+    if a.tau is None:
+        a.tau = 0.1
     try:
         check_window(a.z0, a.depth, a.measure)
         _check_number(a.tau, "--tau")
@@ -2144,11 +2615,35 @@ def parse_args(argv=None):
         kw.update(max_distance=a.spatial, **({} if a.sweeps is None else dict(sweeps=a.sweeps)), **({} if a.damping is None else dict(damping=a.damping)))
         if a.spatial_draws is not None:
             kw.update(draws=a.spatial_draws, seed=a.seed, **({} if a.draw_sweeps is None else dict(draw_sweeps=a.draw_sweeps)))
+    if fit is not None:
+        kw["fit_tau"] = fit                                                   # (``main`` takes it out again: no keyword of ``from_survey``)
     return a.survey, kw
+
+
+def _fit_for_main(path, kw):
+    """The fit the command line runs first: on the lines, or with --spatial on the survey graph, with the window, measure, chains,
+    max-models, length, sweeps and damping of the invocation.  Returns the keywords with ``tau`` = tau_hat and what the output file gets."""
+    fit_kw = kw.pop("fit_tau")
+    shared = {name: kw[name] for name in ("z0", "measure", "chains", "max_models", "length", "device") if name in kw}
+    across = dict(max_distance=kw["max_distance"], **{name: kw[name] for name in ("sweeps", "damping") if name in kw}) if "max_distance" in kw else None
+    fit = fit_from_survey(path, kw["z1"], spatial=across, **shared, **fit_kw)
+    factor = float(np.exp(fit["tau_sd_log"]))
+    print("fit: tau = %.4g decades per %g m, error factor %s, %s" % (fit["tau"], kw["length"], "%.3f" % factor if np.isfinite(factor) else "unknown",
+                                                                      "bracketed" if fit["bracketed"] else "NOT bracketed: the ladder's end"))
+    stored = dict(fit_tau=np.float64(fit["tau"]), fit_tau_sd_log=np.float64(fit["tau_sd_log"]), fit_tau_ladder=np.asarray(fit["tau_ladder"]),
+                  fit_log_evidence=np.asarray(fit["log_evidence"]))
+    return dict(kw, tau=fit["tau"]), stored
 
 
 def main(argv=None):
     path, kw = parse_args(argv)
+    if "fit_tau" in kw:
+        kw, stored = _fit_for_main(path, kw)
+        result = spatial_from_survey(path, **kw) if "max_distance" in kw else from_survey(path, **kw)
+        result.update(stored)
+        out = save(result, output_path(path, SPATIAL_SUFFIX if "max_distance" in kw else OUTPUT_SUFFIX))
+        print("wrote", out)
+        return out
     if "max_distance" in kw:
         out = save(spatial_from_survey(path, **kw), output_path(path, SPATIAL_SUFFIX))
     else:

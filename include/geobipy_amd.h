@@ -1065,6 +1065,43 @@ gbp_status gbp_section_draw(int L, const int64_t *ptr, int64_t total_n, int n, c
                             const double *g, const double *d2, const int64_t *row_key, uint64_t seed, int n_draws, double *filtered,
                             double *scale, int32_t *draw_state, void *stream);
 
+/* The evidence of the lateral coupling along lines (csrc/gbp_section_evidence.h k_section_evidence; the rule is
+ * stated in numpy as sections.evidence_reference): log Z of the chain of gbp_section_track and its derivative in lambda = ln c for a
+ * ladder of T scales c_t = 2^t, t = 0 .. T - 1, of the step costs, from one forward pass over d2.  L, ptr, total_n, n, n_used, score,
+ * g, d2 as gbp_section_track takes them; g is already multiplied by the lowest scale.
+ *   Per sequence and rung t the normalised filter a_t and its tangent b_t = d a_t / d lambda.  Start: a = w_0 / sum w_0, b = 0,
+ *   log Z = ln sum w_0 (w = exp(score)), dlog Z = 0.  Per step: cost_0 = g[r] * d2[r, i, j] and e_0 = exp(-cost_0), one multiply and
+ *   one exp per entry; e_t = e_{t-1} * e_{t-1} and cost_t = cost_{t-1} + cost_{t-1}; u_j = w_j sum_i a_t[i] e_t[i, j]; u'_j = w_j
+ *   sum_i (b_t[i] - a_t[i] cost_t[i, j]) e_t[i, j]; z = sum_j u_j, z' = sum_j u'_j; log Z += ln z, dlog Z += z' / z; a_t = u / z,
+ *   b_t = u' / z - a_t (z' / z).  log_partition and dlog_partition f64 [T, L], entry t * L + l.  dlog Z = -E[sum c_t g D^2], the
+ *   expected total cost of a section under rung t.  A sequence of one row gives ln sum w_0 and 0.0.  Where a step's z underflows to 0
+ *   the rung is -inf or NaN from there on; lower rungs are not affected.  The order of the sums over i and j is the device's own: the
+ *   outputs agree with the rule within rounding, not in bits; a call repeats its own bits.
+ * One 256-thread workgroup per sequence; no workspace, no atomics.  LDS: the pairs (a_t, b_t) twice, 4 T n doubles, 8 T partial sums
+ * and for n <= 128 another 512 T doubles where the lane groups meet: 64.5 KiB at most.
+ * GBP_ERR_INVALID_ARG, before any launch: what gbp_section_track refuses of the arguments they share, T < 1 or T > 8, T * n > 2048,
+ * a NULL log_partition or dlog_partition.  L == 0 launches nothing. */
+gbp_status gbp_section_evidence(int L, const int64_t *ptr, int64_t total_n, int n, const int32_t *n_used, const double *score,
+                                const double *g, const double *d2, int T, double *log_partition, double *dlog_partition, void *stream);
+
+/* The terms of the Bethe evidence of the survey graph from the messages of gbp_section_propagate (csrc/gbp_section_evidence.h
+ * k_graph_evidence; the rule is stated in numpy as sections.graph_terms_reference).  S, E, n, eu, ev, n_used, g, d2,
+ * in_ptr, in_edge as gbp_section_propagate takes them; w f64 [S, n] is its w and message f64 [2 E, n] the half (sweeps & 1) of its mu.
+ *   Per edge e = {u, v}: h_u = w_u times the messages into u but v's, h_v likewise (ascending neighbour); K = exp(-(g[e] * d2[e]));
+ *   edge_log_z[e] = ln sum_ij h_u[i] K_ij h_v[j]; edge_energy[e] = g[e] sum_ij h_u[i] K_ij d2_ij h_v[j] / that sum: the expected
+ *   cost of the edge under its belief.  Per sounding s: node_log_z[s] = ln sum_i w_s[i] times all its incoming messages.
+ *   The Bethe evidence is log Z_B = sum_s (1 - deg_s) node_log_z[s] + sum_e edge_log_z[e] -- it does not depend on how the messages
+ *   are normalised -- and its derivative in lambda = ln c, c a scale of every g, is -sum_e edge_energy[e]; both sums are the
+ *   caller's.  Exact on a forest once the messages have converged; on loops an approximation, as the beliefs are.
+ * One launch: a 256-thread workgroup per edge and one per sounding; d2 is read once; no atomics: a call repeats its bits.  The order
+ * of the sums is the device's own.  An edge whose endpoints do not fit 0 .. S - 1 gets 0.0 and 0.0.
+ * GBP_ERR_INVALID_ARG, before any launch: S < 0, E outside 0 .. 2^30 - 1, n < 1 or n > 256, E > 0 with S < 2, sizes out of range, a
+ * NULL n_used / w / in_ptr / node_log_z with S > 0, a NULL eu / ev / g / d2 / in_edge / message / edge_log_z / edge_energy with E > 0.
+ * S == 0 launches nothing. */
+gbp_status gbp_section_graph_evidence(int S, int E, int n, const int32_t *eu, const int32_t *ev, const int32_t *n_used, const double *w,
+                                      const double *g, const double *d2, const int32_t *in_ptr, const int32_t *in_edge,
+                                      const double *message, double *node_log_z, double *edge_log_z, double *edge_energy, void *stream);
+
 /* Sections across lines: synchronous sum-product message passing (loopy belief propagation) on a graph of soundings
  * (csrc/gbp_section_graph.h k_graph_kernel, k_graph_init, k_graph_sweep, k_graph_residual, k_graph_belief; the rule is
  * stated in numpy as sections.propagate_reference).  The conventions of gbp_section_track: DEVICE arrays throughout, none read on
