@@ -182,6 +182,8 @@ SIGNATURES = {
                                        c_void_p]),
     "gbp_horizon_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                   ctypes.c_double] + [c_void_p] * 6 + [c_void_p]),
+    "gbp_horizon_unit_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int, c_int, c_int, ctypes.c_double] + [c_void_p] * 6
+                                       + [ctypes.c_double] + [c_void_p] * 12 + [c_void_p]),
     "gbp_section_track": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 10 + [c_void_p]),
     "gbp_section_draw": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 5 + [ctypes.c_uint64, c_int] + [c_void_p] * 3 + [c_void_p]),
     "gbp_section_evidence": (c_int, [c_int, c_void_p, ctypes.c_int64, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_void_p]),

@@ -2480,6 +2480,63 @@ extern "C" gbp_status gbp_horizon_track(int L, const int64_t* ptr, int64_t total
 #undef GBP_HORIZON_CASE
 }
 
+#include "gbp_horizon_unit.h"
+
+// Horizon pairs (gbp_horizon_unit.h): one workgroup per sequence walks the chain over the ordered pairs of cells; the Viterbi launch
+// always, the forward-backward launch only when the marginals are asked for.  Every refusal comes before any launch; ptr is not read
+// on the host.
+extern "C" gbp_status gbp_horizon_unit_track(int L, const int64_t* ptr, int64_t total_n, int max_n, int S, int min_cells, double dz,
+                                             const double* score_top, const double* score_base, const double* thickness_score,
+                                             const double* absent_score, const double* g, const double* d, double switch_cost, uint8_t* back,
+                                             int32_t* back_absent, int32_t* cell_top, int32_t* cell_base, double* log_score, double* alpha,
+                                             double* marginal_top, double* marginal_base, double* marginal_thickness, double* marginal_absent,
+                                             double* log_partition, double* scale, void* stream)
+{
+    if (L < 0) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: L must be >= 0%s");
+    if (S < 1 || S > horizon_unit::MAX_UNIT_STATES) {
+        char most[16];
+        std::snprintf(most, sizeof(most), "%d", horizon_unit::MAX_UNIT_STATES);
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: S must lie in 1 .. %s (two S x S matrices live in LDS)", most);
+    }
+    if (min_cells < 0 || min_cells > S - 1) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: min_cells must lie in 0 .. S - 1%s");
+    if (!(dz > 0.0) || !std::isfinite(dz)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: dz must be positive and finite%s");
+    if (!(switch_cost >= 0.0) || !std::isfinite(switch_cost))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: switch must be >= 0 and finite%s");
+    if (L == 0) return GBP_OK;
+    if (total_n < L || max_n < 1 || max_n > total_n || total_n > (int64_t)max_n * L)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: total_n and max_n do not fit L sequences of at least one sounding%s");
+    if (total_n > 0x7fffffffffffffffLL / 8 / ((int64_t)S * S + 1))
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: total_n * (S * S + 1) out of range%s");
+    if (!ptr) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: ptr is NULL%s");
+    if (!score_top || !score_base || !g || !d) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: NULL pointer (score_top, score_base, g, d)%s");
+    if (!back || (absent_score && !back_absent)) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: a back workspace is NULL%s");
+    if (!cell_top || !cell_base || !log_score) return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: NULL pointer (cell_top, cell_base, log_score)%s");
+    const int given = (alpha != nullptr) + (marginal_top != nullptr) + (marginal_base != nullptr) + (marginal_thickness != nullptr) +
+                      (marginal_absent != nullptr) + (log_partition != nullptr) + (scale != nullptr);
+    if (given != 0 && given != 7)
+        return fail(GBP_ERR_INVALID_ARG, "gbp_horizon_unit_track: alpha, the four marginals, log_partition and scale go together (all, or all NULL)%s");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = horizon_unit::lds_doubles(S) * sizeof(double);
+    const int has_absent = absent_score ? 1 : 0, has_ts = thickness_score ? 1 : 0;
+    if (lds > 48 * 1024) {                                                  // (above the default limit of a launch's dynamic LDS)
+        (void)hipFuncSetAttribute((const void*)horizon_unit::k_unit_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)horizon_unit::k_unit_marginals, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+    }
+    unsigned char* back1 = (unsigned char*)back;
+    hipLaunchKernelGGL(horizon_unit::k_unit_viterbi, dim3((unsigned)L), dim3(horizon_unit::THREADS), lds, st, (const long long*)ptr, S, min_cells,
+                       has_absent, has_ts, dz, score_top, score_base, thickness_score, absent_score, g, d, switch_cost, back1,
+                       back1 + (size_t)total_n * S * S, (int*)back_absent, (int*)cell_top, (int*)cell_base, log_score);
+    GBP_HIP(hipGetLastError());
+    if (given) {
+        hipLaunchKernelGGL(horizon_unit::k_unit_marginals, dim3((unsigned)L), dim3(horizon_unit::THREADS), lds, st, (const long long*)ptr, S,
+                           min_cells, has_absent, has_ts, dz, score_top, score_base, thickness_score, absent_score, g, d, switch_cost, alpha,
+                           marginal_top, marginal_base, marginal_thickness, marginal_absent, log_partition, scale);
+        GBP_HIP(hipGetLastError());
+    }
+    return GBP_OK;
+}
+
 #include "gbp_section.h"
 
 // Sections of sampled models (gbp_section.h): one workgroup per sequence walks the chain over the kept models; the Viterbi launch

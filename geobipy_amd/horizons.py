@@ -45,7 +45,13 @@ filter and walk per line, its weights multiplied by the pair factors at the neig
 it, and ``spatial(draws=R)`` / ``spatial_from_products(draws=R)`` return the realisations with ``draw_share`` and
 ``draw_change_share``.  Where several horizons share a launch or a survey the row key of a draw is sounding index + horizon index * N.
 
-Left out on purpose: several horizons tracked jointly with an ordering constraint, learning ``slope``
+Horizon pairs (csrc/gbp_horizon_unit.h; ``gbp_horizon_unit_track``).  Two picks tracked one by one can cross, can be
+the same interface twice, and have no joint posterior, so a unit has no thickness.  ``unit_reference`` states one chain over the
+ordered pairs (top, base) of cells of one window, base - top >= ``min_cells`` -- the pair term is separable, so a step is two passes
+of S^3 operations --, ``unit`` and ``unit_from_products`` run it on the device and return the two picks, the thickness and its
+posterior, and ``unit_intervals`` hands the unit to ``line_products``.
+
+Left out on purpose: more than two horizons tracked jointly, pairs on the survey graph and joint draws of pairs, learning ``slope``
 (``log_partition`` of ``track`` is returned for whoever wants to scan it), non-uniform depth cells, gridding the picks into a surface,
 and a place in ``survey.infer``.
 """
@@ -791,6 +797,394 @@ def as_intervals(top, bottom):
     if t.shape != b.shape or t.ndim != 1:
         raise ValueError("horizons.as_intervals: top and bottom must both be [N]")
     return {"kind": "horizons", "top": t, "bottom": b}
+
+
+# ---- horizon pairs: the top and the base of one unit, tracked jointly and ordered ---------------------------------------
+
+MAX_UNIT_STATES = 96
+UNIT_SUFFIX = ".unit.npz"
+
+
+def _check_unit(ptr, score_top, score_base, g, d, dz, switch, min_cells, thickness_score, absent_score, what):
+    """The checks ``unit_reference`` and the launch share, on shapes and host values alone (the scores numpy or torch, any device);
+    returns ptr (int64 numpy), g, d (float64 numpy), dz, switch and min_cells."""
+    if getattr(score_top, "ndim", 0) != 2 or score_top.shape[1] < 1 or tuple(score_base.shape) != tuple(score_top.shape):
+        raise ValueError("%s: score_top and score_base must both be [N, S] with S >= 1" % what)
+    total, S = score_top.shape
+    ptr = check_ptr(ptr, total)
+    g, d = np.asarray(_args.host(g), dtype=np.float64).reshape(-1), np.asarray(_args.host(d), dtype=np.float64).reshape(-1)
+    if g.size != total or d.size != total:
+        raise ValueError("%s: g and d must hold one entry per sounding" % what)
+    if not (np.all(np.isfinite(g)) and np.all(np.isfinite(d))):
+        raise ValueError("%s: g and d must be finite" % what)
+    min_cells = _args.check_int(min_cells, 0, S - 1, "%s: min_cells (S = %d)" % (what, S))
+    if thickness_score is not None and tuple(thickness_score.shape) != (S,):
+        raise ValueError("%s: thickness_score must hold one entry per thickness b - a = 0 .. S - 1 (%d)" % (what, S))
+    if absent_score is not None and tuple(absent_score.shape) != (total,):
+        raise ValueError("%s: absent_score must hold one entry per sounding" % what)
+    dz, switch = float(dz), float(switch)
+    if not (np.isfinite(dz) and dz > 0.0):
+        raise ValueError("%s: dz must be positive" % what)
+    if not (np.isfinite(switch) and switch >= 0.0):
+        raise ValueError("%s: switch must be >= 0" % what)
+    return ptr, g, d, dz, switch, min_cells
+
+
+def unit_reference(ptr, score_top, score_base, g, d, dz, switch, min_cells=1, thickness_score=None, absent_score=None, marginals=True,
+                   dtype=np.float64):
+    """The rule of ``unit`` in numpy, evaluated in ``dtype`` (fp64: what the device is held to; np.longdouble: the yardstick of the
+    rule's own rounding): the top and the base of one unit as ONE Markov chain, so that the base never lies above the top.  ``ptr``,
+    ``g``, ``d`` (``steps``), ``dz`` and ``switch`` as ``track_reference`` takes them; ``score_top``, ``score_base`` [sum N, S] on one
+    shared window of S cells; ``thickness_score`` [S] or None, indexed by b - a and shared by all soundings; ``absent_score`` [sum N]
+    or None.
+
+    States: the pairs (a, b) of cells, a the top and b the base, valid when b - a >= ``min_cells`` (0 .. S - 1; 0 allows a == b, a
+    unit pinched to nothing), and optionally "absent", which comes last in every order.  Node score s[n, a, b] = (score_top[n, a] +
+    score_base[n, b]) + thickness_score[b - a] -- without ``thickness_score`` the term is left out --; invalid pairs hold -inf (weight
+    0 in the linear domain).
+    Step n -> n + 1: T_n[k] = g[n] |d[n] - k dz|, ``track``'s table; pair -> pair costs T_n[a' - a] + T_n[b' - b], applied in two
+    passes whose order defines the bits and the ties: pass 1 M1[a', b] = max over a ascending of V[a, b] - T[a' - a]; pass 2
+    M2[a', b'] = max over b ascending of M1[a', b] - T[b' - b]; then the candidate V[absent] - switch; every maximum keeps the first
+    (strict > replaces).  V'[a', b'] = s[n + 1, a', b'] + M2 for valid pairs.  V'[absent] = absent_score[n + 1] + the first maximum of
+    V[a, b] - switch over the valid pairs in row-major order (a, then b ascending), which V[absent] replaces on strict >.  The path
+    ends at the first maximum of the last V in row-major order, then absent; the walk back follows pass 2's argument, then pass 1's.
+    Marginals: the same two passes as sums, scaled forward-backward in the linear domain laid out as in ``track_reference``: w =
+    exp(s), K = exp(-T), ks = exp(-switch); the sums run a ascending, then b ascending (acc = acc + alpha K); alpha is normalised by
+    its sum s_n; backward the passes run over a', then b', with the mirrored table.
+
+    Returns ``cell_top``, ``cell_base`` int32 [sum N] (both S: absent), ``log_score`` [L], and with ``marginals``
+    ``marginal_top``, ``marginal_base`` [sum N, S] (gamma summed over the other cell), ``marginal_thickness`` [sum N, S] (indexed by
+    b - a), ``marginal_absent`` [sum N], ``log_partition`` [L] and ``scale`` [sum N] (s_n).  The full pair marginal is not returned."""
+    what = "horizons.unit_reference"
+    ft = np.dtype(dtype).type
+    score_top, score_base = np.asarray(score_top, dtype=np.float64), np.asarray(score_base, dtype=np.float64)
+    thickness_score = None if thickness_score is None else np.asarray(thickness_score, dtype=np.float64)
+    has_absent = absent_score is not None
+    absent_score = np.asarray(absent_score, dtype=np.float64).reshape(-1) if has_absent else None
+    ptr, g, d, dz, switch, mc = _check_unit(ptr, score_top, score_base, g, d, dz, switch, min_cells, thickness_score, absent_score, what)
+    if not (np.all(np.isfinite(score_top)) and np.all(np.isfinite(score_base)) and (thickness_score is None or np.all(np.isfinite(thickness_score)))
+            and (not has_absent or np.all(np.isfinite(absent_score)))):
+        raise ValueError("%s: the scores must be finite" % what)
+    total, S = score_top.shape
+    st, sb, g, d = score_top.astype(ft), score_base.astype(ft), g.astype(ft), d.astype(ft)
+    absent_score = absent_score.astype(ft) if has_absent else None
+    dz, switch = ft(dz), ft(switch)
+    L, SS = ptr.size - 1, S * S
+    kf = np.arange(-(S - 1), S).astype(ft)                                   # k = c' - c at index k + S - 1
+    diff = np.arange(S)[None, :] - np.arange(S)[:, None]                     # b - a at [a, b]
+    valid = diff >= mc
+    ts = None if thickness_score is None else thickness_score.astype(ft)[np.maximum(diff, 0)]
+    ninf = ft(-np.inf)
+
+    def node(r):
+        s = st[r][:, None] + sb[r][None, :]
+        return np.where(valid, s if ts is None else s + ts, ninf)
+
+    cell_top, cell_base, log_score = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32), np.zeros(L, dtype=ft)
+    out = dict(cell_top=cell_top, cell_base=cell_base, log_score=log_score)
+    if marginals:
+        m_top, m_base, m_thick = (np.zeros((total, S), dtype=ft) for _ in range(3))
+        m_absent, log_partition, scale = np.zeros(total, dtype=ft), np.zeros(L, dtype=ft), np.zeros(total, dtype=ft)
+        out.update(marginal_top=m_top, marginal_base=m_base, marginal_thickness=m_thick, marginal_absent=m_absent,
+                   log_partition=log_partition, scale=scale)
+    # for a fixed c the costs of all c' are the slice [S - 1 - c, 2 S - 1 - c) of the table; for a fixed c' those of all c the slice
+    # [c', c' + S) reversed (``track_reference``)
+    for l in range(L):
+        r0, N = int(ptr[l]), int(ptr[l + 1] - ptr[l])
+        # ---- Viterbi
+        V = node(r0)
+        Va = absent_score[r0] if has_absent else ninf
+        back1, back2 = np.zeros((N, S, S), dtype=np.int64), np.zeros((N, S, S), dtype=np.int64)
+        back_absent = np.zeros(N, dtype=np.int64)
+        for n in range(N - 1):
+            T = g[r0 + n] * np.abs(d[r0 + n] - kf * dz)
+            m1, a1 = np.full((S, S), ninf, dtype=ft), np.zeros((S, S), dtype=np.int64)            # [a', b]
+            for a in range(S):
+                cand = V[a][None, :] - T[S - 1 - a:2 * S - 1 - a][:, None]
+                repl = cand > m1                                             # strict: the first maximum stays
+                m1, a1 = np.where(repl, cand, m1), np.where(repl, a, a1)
+            m2, a2 = np.full((S, S), ninf, dtype=ft), np.zeros((S, S), dtype=np.int64)            # [a', b']
+            for b in range(S):
+                cand = m1[:, b][:, None] - T[S - 1 - b:2 * S - 1 - b][None, :]
+                repl = cand > m2
+                m2, a2 = np.where(repl, cand, m2), np.where(repl, b, a2)
+            if has_absent:
+                via = Va - switch
+                repl = via > m2
+                m2, a2 = np.where(repl, via, m2), np.where(repl, S, a2)
+                flat = (V - switch).reshape(-1)                              # (-inf where the pair is invalid: never the maximum)
+                a_arg = first_max(flat)
+                a_m = flat[a_arg]
+                if Va > a_m:
+                    a_arg, a_m = SS, Va
+                Va = absent_score[r0 + n + 1] + a_m
+                back_absent[n + 1] = a_arg
+            V = np.where(valid, node(r0 + n + 1) + m2, ninf)
+            back1[n + 1], back2[n + 1] = a1, a2
+        flat = V.reshape(-1)
+        cur = first_max(flat)
+        log_score[l] = flat[cur]
+        if has_absent and Va > flat[cur]:
+            cur, log_score[l] = SS, Va
+        for n in range(N - 1, -1, -1):
+            a, b = divmod(cur, S) if cur < SS else (S, S)
+            cell_top[r0 + n], cell_base[r0 + n] = a, b
+            if n > 0:
+                if cur == SS:
+                    cur = int(back_absent[n])
+                else:
+                    pb = int(back2[n, a, b])
+                    cur = SS if pb == S else int(back1[n, a, pb]) * S + pb
+        if not marginals:
+            continue
+        # ---- scaled forward-backward
+        ks = np.exp(-switch)
+        zero = ft(0.0)
+        w = np.exp(np.stack([node(r0 + n) for n in range(N)]))                 # [N, S, S], 0 where the pair is invalid
+        wa = np.exp(absent_score[r0:r0 + N]) if has_absent else np.zeros(N, dtype=ft)
+        alpha, alpha_a, s = np.zeros((N, S, S), dtype=ft), np.zeros(N, dtype=ft), np.zeros(N, dtype=ft)
+        s[0] = w[0].sum() + (wa[0] if has_absent else zero)
+        alpha[0], alpha_a[0] = w[0] / s[0], wa[0] / s[0]
+        Ks = []
+        for n in range(N - 1):
+            K = np.exp(-(g[r0 + n] * np.abs(d[r0 + n] - kf * dz)))
+            Ks.append(K)
+            p1 = np.zeros((S, S), dtype=ft)                                  # [a', b]
+            for a in range(S):                                               # a ascending
+                p1 = p1 + alpha[n, a][None, :] * K[S - 1 - a:2 * S - 1 - a][:, None]
+            p2 = np.zeros((S, S), dtype=ft)                                  # [a', b']
+            for b in range(S):                                               # b ascending
+                p2 = p2 + p1[:, b][:, None] * K[S - 1 - b:2 * S - 1 - b][None, :]
+            ua = zero
+            if has_absent:
+                p2 = p2 + alpha_a[n] * ks
+                ua = wa[n + 1] * (np.cumsum((alpha[n] * ks).reshape(-1))[-1] + alpha_a[n])
+            u = w[n + 1] * p2
+            s[n + 1] = u.sum() + ua
+            alpha[n + 1], alpha_a[n + 1] = u / s[n + 1], ua / s[n + 1]
+        beta, beta_a = np.ones((S, S), dtype=ft), ft(1.0)
+        for n in range(N - 1, -1, -1):
+            if n < N - 1:
+                K = Ks[n]
+                u, ua = w[n + 1] * beta, wa[n + 1] * beta_a
+                q1 = np.zeros((S, S), dtype=ft)                              # [a, b']
+                for c in range(S):                                           # a' ascending
+                    q1 = q1 + K[c:c + S][::-1][:, None] * u[c][None, :]
+                q2 = np.zeros((S, S), dtype=ft)                              # [a, b]
+                for c in range(S):                                           # b' ascending
+                    q2 = q2 + q1[:, c][:, None] * K[c:c + S][::-1][None, :]
+                if has_absent:
+                    q2 = q2 + ks * ua
+                    beta_a = (np.cumsum((ks * u).reshape(-1))[-1] + ua) / s[n + 1]
+                beta = q2 / s[n + 1]
+            gm = alpha[n] * beta                                             # (0 where the pair is invalid: alpha is)
+            gm_a = alpha_a[n] * beta_a if has_absent else zero
+            tot = gm.sum() + gm_a
+            gamma = gm / tot
+            m_top[r0 + n], m_base[r0 + n] = gamma.sum(axis=1), gamma.sum(axis=0)
+            m_thick[r0 + n] = [np.trace(gamma, offset=k) for k in range(S)]
+            m_absent[r0 + n] = gm_a / tot
+        scale[r0:r0 + N] = s
+        log_partition[l] = np.cumsum(np.log(s))[-1]
+    return out
+
+
+def unit_bytes(total, S, marginals=True):
+    """The bytes of the workspaces a launch of ``total`` soundings and S cells holds: the back-pointers of the two passes, uint8
+    [2, total, S, S], those of the absent state, int32 [total], and with ``marginals`` alpha, float64 [total, S S + 1]."""
+    total, S = int(total), int(S)
+    return total * (2 * S * S + 4) + (total * (S * S + 1) * 8 if marginals else 0)
+
+
+def _unit_launch(score_top, score_base, thickness_score, absent_score, ptr, g, d, dz, switch, min_cells, marginals, budget_bytes=4 << 30):
+    """gbp_horizon_unit_track on device tensors (float64, score_top and score_base [T, S], thickness_score [S] or None, absent_score [T]
+    or None), ptr numpy [L + 1], g, d numpy [T].  The launch is split by whole sequences so that the workspaces of a part
+    (``unit_bytes``) stay under ``budget_bytes``; the parts are independent, so the split changes no bit."""
+    entry, what = "gbp_horizon_unit_track", "horizons.unit"
+    for a in (score_top, score_base, thickness_score, absent_score):
+        if a is not None and not isinstance(a, torch.Tensor):
+            raise TypeError("%s: the scores are torch tensors (%s runs on the device)" % (what, entry))
+    ptr, g, d, dz, switch, mc = _check_unit(ptr, score_top, score_base, g, d, dz, switch, min_cells, thickness_score, absent_score, what)
+    total, S = score_top.shape
+    if S > MAX_UNIT_STATES:
+        raise ValueError("%s: %d states, at most %d (choose a narrower window with between=, or coarsen=)" % (what, S, MAX_UNIT_STATES))
+    budget_bytes = _args.check_int(budget_bytes, 1, 2 ** 62, "%s: budget_bytes" % what)
+    given = tuple(a for a in (score_top, score_base, thickness_score, absent_score) if a is not None)
+    if any(a.dtype != torch.float64 for a in given):
+        raise TypeError("%s: the scores are float64" % what)
+    if thickness_score is not None and not bool(torch.isfinite(thickness_score).all()):      # (S values: the one score array small enough to check)
+        raise ValueError("%s: thickness_score must be finite" % what)
+    L = ptr.size - 1
+    parts, a = [], 0                                                          # [l0, l1) of whole sequences under the budget
+    while a < L:
+        b = a + 1
+        if unit_bytes(ptr[b] - ptr[a], S, marginals) > budget_bytes:
+            raise ValueError("%s: the workspaces of one sequence of %d soundings and %d cells take %d bytes, more than budget_bytes = %d; "
+                             "choose a narrower window with between=, or coarsen=" % (what, ptr[b] - ptr[a], S, unit_bytes(ptr[b] - ptr[a], S, marginals),
+                                                                                     budget_bytes))
+        while b < L and unit_bytes(ptr[b + 1] - ptr[a], S, marginals) <= budget_bytes:
+            b += 1
+        parts.append((a, b))
+        a = b
+    _args.on_device(given, "horizons", "unit", entry)
+    dev = score_top.device
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    score_top, score_base = score_top.contiguous(), score_base.contiguous()
+    thickness_score = None if thickness_score is None else thickness_score.contiguous()
+    absent_score = None if absent_score is None else absent_score.contiguous()
+    t_g, t_d = torch.as_tensor(g).to(dev), torch.as_tensor(d).to(dev)
+    out = dict(cell_top=torch.empty(total, **i32), cell_base=torch.empty(total, **i32), log_score=torch.empty(L, **f64))
+    if marginals:
+        out.update(marginal_top=torch.empty((total, S), **f64), marginal_base=torch.empty((total, S), **f64),
+                   marginal_thickness=torch.empty((total, S), **f64), marginal_absent=torch.empty(total, **f64),
+                   log_partition=torch.empty(L, **f64), scale=torch.empty(total, **f64))
+    rows = ("cell_top", "cell_base", "marginal_top", "marginal_base", "marginal_thickness", "marginal_absent", "scale")
+    for l0, l1 in parts:
+        r0, r1 = int(ptr[l0]), int(ptr[l1])
+        n = r1 - r0
+        cut = {k: (v[r0:r1] if k in rows else v[l0:l1]) for k, v in out.items()}
+        back = torch.empty((2, n, S, S), dtype=torch.uint8, device=dev)
+        back_absent = None if absent_score is None else torch.empty(n, **i32)
+        alpha = torch.empty((n, S * S + 1), **f64) if marginals else None
+        _lib.call(entry, dev, l1 - l0, torch.as_tensor(ptr[l0:l1 + 1] - r0).to(dev), n, int(np.diff(ptr[l0:l1 + 1]).max()), S, mc, dz,
+                  score_top[r0:r1], score_base[r0:r1], thickness_score, None if absent_score is None else absent_score[r0:r1], t_g[r0:r1],
+                  t_d[r0:r1], switch, back, back_absent, cut["cell_top"], cut["cell_base"], cut["log_score"], alpha, cut.get("marginal_top"),
+                  cut.get("marginal_base"), cut.get("marginal_thickness"), cut.get("marginal_absent"), cut.get("log_partition"), cut.get("scale"))
+    return out
+
+
+def _pair(value):
+    """``value`` as (top, base): one object serves both horizons."""
+    return tuple(value) if isinstance(value, (tuple, list)) and len(value) == 2 else (value, value)
+
+
+def unit(evidence_top, evidence_base, x, y, surface, depth_edges, between=None, top_between=None, base_between=None, min_thickness=None,
+         coarsen=1, absent=None, thickness_score=None, slope=0.05, switch=4.6, floor=1e-6, marginals=True, percentiles=(5, 50, 95), ptr=None,
+         budget_bytes=4 << 30):
+    """Track the top and the base of one unit per sequence jointly, the base never less than ``min_thickness`` below the top
+    (gbp_horizon_unit_track; ``unit_reference`` states the rule).  ``evidence_top``, ``evidence_base`` [sum N, n_depth]:
+    torch tensors on the device, non-negative weights on the cells of the uniform ``depth_edges`` (``evidence_base`` None: the same
+    evidence for both); ``x``, ``y``, ``surface`` [sum N], ``slope``, ``switch``, ``floor``, ``ptr`` as ``track`` takes them.
+    ``between`` = (d0, d1): the window the two horizons share.  ``top_between`` / ``base_between`` = (d0, d1): the evidence of that
+    horizon is set to zero in the cells whose centres lie outside it, before anything else.  ``coarsen`` = C: groups of C cells of the
+    window are summed on the device before scoring, and a trailing partial group is dropped from the window; the states are the
+    S <= 96 groups.  ``min_thickness`` (m) becomes min_cells = ceil(min_thickness / (C dz)), 0 allowing a unit pinched to nothing (None:
+    one cell; 0 where the window is a single cell, S = 1, which has no other pair).  Each horizon's scores are ``evidence_scores`` of its evidence; ``absent``: one weight array [sum N] or a pair (top,
+    base) -- the absent state's score is the sum of the two horizons' absent scores (None: no absent state).  ``thickness_score`` [S]:
+    an extra score of the thickness in cells, b - a.  The launch is split by whole sequences under ``budget_bytes`` of workspaces
+    (``unit_bytes``), which changes no bit; one sequence beyond it is a ValueError.  There is no host fallback.
+
+    Returns on the evidence's device ``top_cell``, ``base_cell`` int32 (on the full axis: the cell that holds the centre of the
+    group, lo + C k + C // 2; -1: absent), ``top_depth``, ``base_depth`` (the group's centre; NaN: absent), ``top_elevation``,
+    ``base_elevation``, ``thickness`` (m; NaN: absent), ``log_score`` [L]; with ``marginals`` also ``top_marginal``, ``base_marginal``
+    [sum N, S] over the groups, ``thickness_marginal`` [sum N, S] over b - a, ``absent_probability``, ``pinched_probability`` (the
+    mass of thickness 0; only with min_cells = 0), ``thickness_mean`` (m, given that the unit is present; NaN without mass),
+    ``thickness_percentile_<p>``, ``top_depth_percentile_<p>``, ``base_depth_percentile_<p>`` (``percentile_cells``), ``log_partition``
+    [L] and ``scale``; and ``cell_depth_edges`` [S + 1], the edges of the groups."""
+    what = "horizons.unit"
+    evidence_base = evidence_top if evidence_base is None else evidence_base
+    if not isinstance(evidence_base, torch.Tensor) or not isinstance(evidence_top, torch.Tensor) or evidence_base.shape != evidence_top.shape:
+        raise ValueError("%s: evidence_top and evidence_base must be torch tensors of one shape [N, n_depth]" % what)
+    a_top, a_base = _pair(absent) if absent is not None else (None, None)
+    ptr, g, d, switch = _track_arguments(evidence_top, x, y, surface, a_top, slope, switch, floor, ptr)
+    if a_base is not None and tuple(torch.as_tensor(a_base).shape) != (evidence_top.shape[0],):
+        raise ValueError("%s: absent must hold one weight per sounding" % what)
+    percentiles = check_percentiles(percentiles)
+    edges, dz = check_depth_edges(depth_edges)
+    if evidence_top.shape[1] != edges.size - 1:
+        raise ValueError("%s: the evidence has %d depth cells, depth_edges %d" % (what, evidence_top.shape[1], edges.size - 1))
+    C = _args.check_int(coarsen, 1, edges.size - 1, "%s: coarsen" % what)
+    lo, hi = window(edges, between)
+    S = (hi - lo) // C
+    if S < 1:
+        raise ValueError("%s: the window holds %d cells, fewer than coarsen = %d" % (what, hi - lo, C))
+    hi = lo + S * C
+    if S > MAX_UNIT_STATES:
+        raise ValueError("%s: %d states, at most %d (choose a narrower window with between=, or coarsen=)" % (what, S, MAX_UNIT_STATES))
+    if min_thickness is None:
+        mc = 1 if S > 1 else 0
+    else:
+        min_thickness = float(min_thickness)
+        if not (np.isfinite(min_thickness) and min_thickness >= 0.0):
+            raise ValueError("%s: min_thickness must be >= 0" % what)
+        mc = int(np.ceil(min_thickness / (C * dz) - 1e-9))
+    if mc > S - 1:
+        raise ValueError("%s: min_thickness is %d cells of %g m, the window holds %d (at most %d)" % (what, mc, C * dz, S, S - 1))
+    if thickness_score is not None and tuple(torch.as_tensor(thickness_score).shape) != (S,):
+        raise ValueError("%s: thickness_score must hold one entry per thickness b - a = 0 .. S - 1 (%d)" % (what, S))
+    if evidence_top.device.type != "cuda" or evidence_base.device.type != "cuda":
+        raise _lib.NativeLibraryError("%s runs on the device (gbp_horizon_unit_track); there is no host fallback" % what)
+    dev = evidence_top.device
+    scores = []
+    for ev, sub, ab in ((evidence_top, top_between, a_top), (evidence_base, base_between, a_base)):
+        ev = ev.to(torch.float64)
+        if sub is not None:
+            s0, s1 = window(edges, sub)
+            keep = torch.zeros(edges.size - 1, dtype=torch.bool, device=dev)
+            keep[s0:s1] = True
+            ev = torch.where(keep[None, :], ev, torch.zeros((), dtype=torch.float64, device=dev))
+        ev = ev[:, lo:hi].reshape(ev.shape[0], S, C).sum(dim=2)
+        scores.append(evidence_scores(ev, ab, floor))
+    (score_top, ab_top), (score_base, ab_base) = scores
+    absent_score = None if ab_top is None else ab_top + ab_base
+    t_thick = None if thickness_score is None else torch.as_tensor(thickness_score, dtype=torch.float64).to(dev)
+    raw = _unit_launch(score_top, score_base, t_thick, absent_score, ptr, g, d, C * dz, switch, mc, marginals, budget_bytes)
+    # the public entries: groups of the window lo .. hi of the axis
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    cell_edges = edges[lo] + C * dz * np.arange(S + 1)
+    centres = torch.as_tensor(0.5 * (cell_edges[1:] + cell_edges[:-1]), dtype=torch.float64, device=dev)
+    surf = torch.as_tensor(np.asarray(surface, dtype=np.float64).reshape(-1), device=dev)
+    ct, cb = raw["cell_top"].long(), raw["cell_base"].long()
+    gone = ct >= S
+    full = lambda c: torch.where(gone, torch.full_like(c, -1), lo + C * c + C // 2).to(torch.int32)      # noqa: E731
+    depth = lambda c: torch.where(gone, nan, centres[c.clamp(max=S - 1)])                              # noqa: E731
+    out = dict(top_cell=full(ct), base_cell=full(cb), top_depth=depth(ct), base_depth=depth(cb), log_score=raw["log_score"])
+    out.update(top_elevation=surf - out["top_depth"], base_elevation=surf - out["base_depth"],
+               thickness=torch.where(gone, nan, (cb - ct).to(torch.float64) * (C * dz)), cell_depth_edges=cell_edges, min_cells=mc)
+    if marginals:
+        mt, mb, mk = raw["marginal_top"], raw["marginal_base"], raw["marginal_thickness"]
+        out.update(top_marginal=mt, base_marginal=mb, thickness_marginal=mk, absent_probability=raw["marginal_absent"])
+        if mc == 0:
+            out["pinched_probability"] = mk[:, 0]
+        width = torch.arange(S, dtype=torch.float64, device=dev) * (C * dz)
+        mass = mk.sum(dim=1)
+        out["thickness_mean"] = torch.where(mass > 0, (mk * width[None, :]).sum(dim=1) / torch.where(mass > 0, mass, torch.ones_like(mass)), nan)
+        for p in percentiles:
+            for name, m, value in (("thickness", mk, width), ("top_depth", mt, centres), ("base_depth", mb, centres)):
+                i = percentile_cells(m, p)
+                out["%s_percentile_%g" % (name, p)] = torch.where(i < 0, nan, value[i.clamp(min=0)])
+        out["log_partition"], out["scale"] = raw["log_partition"], raw["scale"]
+    return out
+
+
+def unit_from_products(path_or_products, between, container=None, x=None, y=None, surface=None, absent=False, device=None, **kwargs):
+    """``unit`` on the ``interface_probability`` of a results container, of line products or of saved line products (what
+    ``from_products`` reads, by the same ``_read``), as the evidence of both horizons in the ONE window ``between`` = (d0, d1); x, y
+    and the surface come from the container unless given.  ``absent`` = True adds the absent state with the weight of the probability
+    mass outside the window for each horizon.  The other arguments are ``unit``'s; the result is ``unit``'s, on ``device`` (default
+    cuda:0)."""
+    what = "horizons.unit_from_products"
+    prob, edges, cx, cy, cs = _read(path_or_products, container)
+    x, y, surface = (cx if x is None else x), (cy if y is None else y), (cs if surface is None else surface)
+    if x is None or y is None or surface is None:
+        raise ValueError("%s: x, y and surface are needed (give them, or a container that holds them)" % what)
+    win = np.asarray(between, dtype=np.float64).reshape(-1)
+    if win.size != 2:
+        raise ValueError("%s: between must be one window (d0, d1)" % what)
+    edges, _ = check_depth_edges(edges)
+    if prob.ndim != 2 or prob.shape[1] != edges.size - 1:
+        raise ValueError("%s: interface_probability %r does not match its %d depth cells" % (what, prob.shape, edges.size - 1))
+    lo, hi = window(edges, tuple(win))
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    e = torch.as_tensor(np.nan_to_num(prob, nan=0.0))
+    e = e.to(dev) if dev.type == "cuda" else e
+    ab = (e.sum(1) - e[:, lo:hi].sum(1)).clamp(min=0.0) if absent else None
+    return unit(e, None, x, y, surface, edges, between=tuple(win), absent=ab, **kwargs)
+
+
+def unit_intervals(res):
+    """``as_intervals`` of a result of ``unit``: the unit for ``line_products.from_results(intervals=...)``."""
+    return as_intervals(res["top_depth"], res["base_depth"])
 
 
 # ---- across lines: the survey graph (DESIGN.md 3.33) -----------------------------------------------------------------------------------
@@ -1590,6 +1984,15 @@ def parser():
     ap.add_argument("--draw-sweeps", type=int, default=None, metavar="T",
                     help="with --spatial and --draws: sweeps of the line-blocked Gibbs sampler after the line-alone start (default 8: a "
                          "convention, not a measured mixing time)")
+    ap.add_argument("--unit", action="store_true",
+                    help="track the top and the base of ONE unit jointly in the one --between window, the base never above the top, and write "
+                         "<line>.unit.npz instead")
+    ap.add_argument("--min-thickness", type=float, default=None, metavar="M", help="with --unit: the least thickness (m; default one cell)")
+    ap.add_argument("--coarsen", type=int, default=None, metavar="C", help="with --unit: sum groups of C cells before scoring (default 1)")
+    ap.add_argument("--top-between", type=float, nargs=2, default=None, metavar=("A", "B"),
+                    help="with --unit: the top's evidence counts only in this depth range")
+    ap.add_argument("--base-between", type=float, nargs=2, default=None, metavar=("A", "B"),
+                    help="with --unit: the base's evidence counts only in this depth range")
     return ap
 
 
@@ -1621,6 +2024,22 @@ def parse_args(argv=None):
         ap.error("--draw-sweeps needs --spatial MAX_DISTANCE and --draws R (along a line alone a draw is exact: there are no sweeps)")
     if a.draw_sweeps is not None and not 0 <= a.draw_sweeps <= 65535:
         ap.error("--draw-sweeps must lie in 0 .. 65535")
+    if not a.unit and (a.min_thickness is not None or a.coarsen is not None or a.top_between is not None or a.base_between is not None):
+        ap.error("--min-thickness, --coarsen, --top-between and --base-between need --unit")
+    if a.unit:
+        if len(a.between) != 1:
+            ap.error("--unit needs exactly one --between D0 D1: the window the top and the base share")
+        if a.spatial is not None:
+            ap.error("--unit tracks every line alone: pairs on the survey graph are not supported, drop --spatial")
+        if a.draws:
+            ap.error("--unit has no joint draws of pairs, drop --draws")
+        if a.min_thickness is not None and not (np.isfinite(a.min_thickness) and a.min_thickness >= 0.0):
+            ap.error("--min-thickness must be >= 0")
+        if a.coarsen is not None and a.coarsen < 1:
+            ap.error("--coarsen must be >= 1")
+        for name, w in (("--top-between", a.top_between), ("--base-between", a.base_between)):
+            if w is not None and not w[0] < w[1]:
+                ap.error("%s A B needs A < B" % name)
     return a
 
 
@@ -1635,6 +2054,15 @@ def main(argv=None):
         print(written[0])
         return written
     written = []
+    if a.unit:
+        for path in a.paths:
+            for c in containers(path):
+                r = unit_from_products(c, a.between[0], absent=a.absent, device=a.device, slope=a.slope, switch=a.switch,
+                                       marginals=not a.no_marginals, min_thickness=a.min_thickness, coarsen=1 if a.coarsen is None else a.coarsen,
+                                       top_between=a.top_between, base_between=a.base_between)
+                written.append(save(r, output_path(c)[:-len(OUTPUT_SUFFIX)] + UNIT_SUFFIX))
+                print(written[-1])
+        return written
     for path in a.paths:
         for c in containers(path):
             r = from_products(c, a.between, slope=a.slope, switch=a.switch, marginals=not a.no_marginals, absent=a.absent, device=a.device,

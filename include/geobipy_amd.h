@@ -1021,6 +1021,34 @@ gbp_status gbp_horizon_track(int L, const int64_t *ptr, int64_t total_n, int max
                              const double *absent_score, const double *g, const double *d, double switch_cost, uint16_t *back,
                              int32_t *cell, double *log_score, double *marginal, double *log_partition, double *scale, void *stream);
 
+/* Horizon pairs: the top and the base of one unit tracked jointly and ordered (csrc/gbp_horizon_unit.h k_unit_viterbi,
+ * k_unit_marginals; the rule is stated in numpy as horizons.unit_reference).  The conventions of gbp_horizon_track:
+ * L sequences concatenated by ptr [L + 1] int64 (a sequence has >= 1 row), DEVICE arrays, ptr included; the caller passes total_n =
+ * ptr[L] and max_n.  The state under a row is a pair (a, b) of cells of one window of S <= 96 cells, valid when b - a >= min_cells
+ * (0 .. S - 1), or, where absent_score is given, "absent".  score_top, score_base f64 [total_n, S]; thickness_score f64 [S] or NULL
+ * (the term is left out); absent_score f64 [total_n] or NULL; g, d f64 [total_n] and dz, switch_cost as gbp_horizon_track takes them.
+ *   Node: s[n, a, b] = (score_top[n, a] + score_base[n, b]) + thickness_score[b - a].  Step: T_n[k] = g[n] * fabs(d[n] - (double)k *
+ *   dz); pass 1 M1[a', b] = max over a ascending of V[a, b] - T[a' - a]; pass 2 M2[a', b'] = max over b ascending of M1[a', b] -
+ *   T[b' - b]; then V[absent] - switch_cost; every maximum is the first (strict > replaces).  V'[a', b'] = s[n + 1, a', b'] + M2;
+ *   V'[absent] = absent_score[n + 1] + the first maximum of V[a, b] - switch_cost over the valid pairs in row-major order, then
+ *   V[absent].  The path ends at the first maximum of the last V in row-major order, then absent.  cell_top, cell_base int32
+ *   [total_n] (both S: absent) and log_score [L] equal the numpy rule's in every bit.
+ *   Marginals (only when alpha .. scale are given): the same two passes as sums in the linear domain, scaled forward-backward;
+ *   marginal_top, marginal_base, marginal_thickness (indexed by b - a) f64 [total_n, S], marginal_absent, scale f64 [total_n],
+ *   log_partition f64 [L].  The normalising sums, the absent state's sums and the projections of gamma reduce in the device's order.
+ * Workspaces: back uint8 [2, total_n, S, S]; back_absent int32 [total_n] (needed with absent_score); alpha f64 [total_n, S * S + 1]
+ * (with the marginals).  One 512-thread workgroup per sequence; LDS: (2 S^2 + 5 S + 1040) doubles.
+ * GBP_ERR_INVALID_ARG, before any launch: L < 0, S < 1 or S > 96, min_cells outside 0 .. S - 1, dz not positive, switch_cost negative
+ * or not finite, total_n < L, max_n < 1 or > total_n, L * max_n < total_n, sizes out of range, a NULL ptr / score_top / score_base /
+ * g / d / back / cell_top / cell_base / log_score, back_absent NULL with absent_score, alpha, the four marginals, log_partition and
+ * scale not all given or all NULL.  L == 0 launches nothing. */
+gbp_status gbp_horizon_unit_track(int L, const int64_t *ptr, int64_t total_n, int max_n, int S, int min_cells, double dz,
+                                  const double *score_top, const double *score_base, const double *thickness_score,
+                                  const double *absent_score, const double *g, const double *d, double switch_cost, uint8_t *back,
+                                  int32_t *back_absent, int32_t *cell_top, int32_t *cell_base, double *log_score, double *alpha,
+                                  double *marginal_top, double *marginal_base, double *marginal_thickness, double *marginal_absent,
+                                  double *log_partition, double *scale, void *stream);
+
 /* Sections of sampled models along lines (csrc/gbp_section.h k_section_viterbi, k_section_marginals; the rule is
  * stated in numpy as sections.track_reference): the most probable path and the smoothed marginals of a Markov chain whose states
  * under row r are the first m_r = n_used[r] (1 .. n) of n kept models and whose transition is a dense matrix per step.  The
